@@ -17,12 +17,18 @@ merged by an RCCL all-gather of the per-shard top-k inside the library (no other
 collective on the path).
 
 Prints ONE JSON line (rank 0).  `value` = samples indexed per second over the
-whole step (build + queries), all ranks.  `roofline` is for the kernel group
+whole step (build + queries), all ranks; `ms_per_step` = one timed step.  A plain
+run does only that: set up, warm up, time --steps steps, print.  --full adds
+everything else, as keys of the same line: `roofline` is for the kernel group
 that takes the most time (`rooflines` has all four): algorithmic bytes
  -- or, for the split on the matrix cores, flops -- per launch over
 its HIP-event time on the library's own stream.  `cpu_baseline` times the CPU
 oracle (faithful single-thread restatement of morna + annoy) on a bounded sample
 of the same workload and extrapolates to the full step.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, as
+DIR/<name>.npy (float32 / float64): the neighbours of every query, in the
+queries' own order, and a fixed sample of rows of the feature matrix.
 """
 import argparse
 import json
@@ -60,8 +66,14 @@ def parse():
     ap.add_argument("--search-k", type=int, default=100)
     ap.add_argument("--junctions", type=int, default=70_000,
                     help="junction lines; 70k gives nnz ~ 2000 per sample (SURVEY.md 8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[4] shard pass reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: HIP-event timers, roofline / rooflines, the per-group breakdown, forest "
+                         "stats, the extras below and the CPU baseline (a plain run sets up, warms up, times, prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="(--full) skip the query sweep, the configs[4] passes and the sharded path at one rank")
     ap.add_argument("--cpu-trees", type=int, default=24)
     ap.add_argument("--cpu-queries", type=int, default=200)
     ap.add_argument("--verify", action="store_true",
@@ -70,7 +82,35 @@ def parse():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend; nccl (= RCCL) is the product path, gloo only rehearses "
                          "--gpus N on a box with fewer GPUs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_FEATURE_ROWS = 1024        # rows of the feature matrix written by --dump-outputs (at most 32 MB of them)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, index, res, answer_order, n_items, id_offset, D):
+    """What the last timed step gave its caller: the neighbours of every query (ids as float64, -1 = none; distances
+    float32; counts), put back into the queries' own order, and a fixed, seeded sample of the rows of this rank's
+    feature matrix with their global row numbers."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids, d, cnt = (np.asarray(a) for a in res)
+    if answer_order is not None:
+        # answers come rank 0's queries first; back to the order the queries were drawn in
+        back = np.empty_like(answer_order)
+        back[answer_order] = np.arange(len(answer_order))
+        ids, d, cnt = ids[back], d[back], cnt[back]
+    rows = min(n_items, DUMP_FEATURE_ROWS, max(1, (32 << 20) // (4 * D)))
+    pick = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n_items, size=rows, replace=False))
+    arrays = {"neighbour_ids": ids.astype(np.float64), "neighbour_distances": d.astype(np.float32),
+              "neighbour_counts": cnt.astype(np.float64),
+              "feature_rows": index.get_item_vectors(pick.astype(np.int32)).astype(np.float32),
+              "feature_row_ids": (pick + id_offset).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _cpu_baseline_mt(args, capi, X, items, N, D, t_feat, t_dot):
@@ -412,24 +452,26 @@ def main():
         index.synchronize()
 
     GROUPS = ("features", "two_means", "split", "query")
-    # Warm-up.  Its last step is bracketed with events on every kernel group to find the group that takes the most
-    # time; the timed region then brackets THAT group only (an event pair costs the stream a few microseconds of idle).
+    # Warm-up.  Under --full its last step is bracketed with events on every kernel group to find the group that takes
+    # the most time; the timed region then brackets THAT group only (an event pair costs the stream a few microseconds of
+    # idle).  A plain run brackets nothing.
     dominant = "two_means"
     for w in range(args.warmup):
-        if w == args.warmup - 1:
+        if args.full and w == args.warmup - 1:
             index.timer_reset()
             index.timer_enable(True)
         step()
-    if args.warmup > 0:
-        index.timer_enable(False)
-        probe = index.timers()
-        dominant = max(GROUPS, key=lambda n: probe[n]["ms"])
-    if world > 1:   # every rank brackets the same group
-        code = torch.tensor([GROUPS.index(dominant)], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.broadcast(code, src=0)
-        dominant = GROUPS[int(code.item())]
-    index.timer_reset()
-    index.timer_enable(True, only=[dominant] if os.environ.get("MORNA_BENCH_TIMERS", "dominant") == "dominant" else list(GROUPS))
+    if args.full:
+        if args.warmup > 0:
+            index.timer_enable(False)
+            probe = index.timers()
+            dominant = max(GROUPS, key=lambda n: probe[n]["ms"])
+        if world > 1:   # every rank brackets the same group
+            code = torch.tensor([GROUPS.index(dominant)], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
+            dist.broadcast(code, src=0)
+            dominant = GROUPS[int(code.item())]
+        index.timer_reset()
+        index.timer_enable(True, only=[dominant] if os.environ.get("MORNA_BENCH_TIMERS", "dominant") == "dominant" else list(GROUPS))
     fence()
     t_start = time.perf_counter()
     res = None
@@ -437,25 +479,30 @@ def main():
         _b, _q, res = step()
     fence()
     elapsed = time.perf_counter() - t_start
-    index.timer_enable(False)
-    timed = index.timers()
+    if args.full:
+        index.timer_enable(False)
+        timed = index.timers()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    st = index.forest_stats()
-    # After the timed region (not part of `value`): the same step with every group bracketed, for the breakdown
-    n_bd = max(1, min(args.steps, 5))
-    index.timer_reset()
-    index.timer_enable(True)
-    tb = tq = 0.0
-    for _ in range(n_bd):
-        b, q, _res = step(split=True)
-        tb += b
-        tq += q
-    tb, tq = tb * args.steps / n_bd, tq * args.steps / n_bd     # scaled to the timed region's step count for the keys below
-    index.timer_enable(False)
-    timers = index.timers()
+    if args.dump_outputs and rank == 0:
+        # every rank holds the answers to all queries; rank 0 writes them with a sample of its own rows
+        dump_outputs(args.dump_outputs, index, res, answer_order, n_items, id_offset, D)
+    if args.full:
+        st = index.forest_stats()
+        # After the timed region (not part of `value`): the same step with every group bracketed, for the breakdown
+        n_bd = max(1, min(args.steps, 5))
+        index.timer_reset()
+        index.timer_enable(True)
+        tb = tq = 0.0
+        for _ in range(n_bd):
+            b, q, _res = step(split=True)
+            tb += b
+            tq += q
+        tb, tq = tb * args.steps / n_bd, tq * args.steps / n_bd     # scaled to the timed region's step count for the keys below
+        index.timer_enable(False)
+        timers = index.timers()
 
     verify = None
     if args.verify and strong:
@@ -476,7 +523,7 @@ def main():
                                                                + np.ascontiguousarray(ed, np.float64).tobytes()).hexdigest(),
                   "recall_at_k_vs_exact": rec}
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # One roofline entry per kernel group, from the HIP-event timers of the library (events recorded on the
         # stream the kernels run on) and the algorithmic bytes of SURVEY.md 8(d) that the library counts per launch.
         # The split group is priced at one pass over the rows per level (see below), not per (row, split node).
@@ -581,6 +628,7 @@ def main():
         for n, g in groups.items():
             g["note"] = notes[n]
         roofline = dict(group(dominant, timed, args.steps), note=notes[dominant], measured="HIP events in the timed region")
+    if rank == 0:
         total_samples = n_total * args.steps
         which = "configs[3]" if (strong and N == 200_000 and world == 8) else "configs[2]" if N == 50_000 else "a size of its own"
         if strong:
@@ -605,35 +653,38 @@ def main():
                                       % (world, " (one data set, global idf and ids)" if strong else " (a data set per GPU)",
                                          "" if sharded is None else " -- transport: %s%s" % (
                                              sharded.transport, " (%s)" % sharded.transport_note if sharded.transport_note else ""))},
-            "index_samples_per_sec": n_total * args.steps / tb,
-            "queries_per_sec": Q * args.steps / tq,
             # if the junction lines had to cross PCIe on every step (pageable host buffers, measured once)
             "stage_ms": 1e3 * t_stage,
             "samples_per_sec_pcie_inclusive": n_total / (elapsed / args.steps + t_stage),
-            # build / query halves: from the breakdown pass (the build drained before the queries start), not the timed region
-            "build_ms_per_step": 1e3 * tb / args.steps, "query_ms_per_step": 1e3 * tq / args.steps,
-            # breakdown: %d extra steps AFTER the timed region, every group bracketed with events
-            "kernel_ms_per_step": {n: round(v["ms"] / n_bd, 3) for n, v in timers.items()},
-            "forest": {"n_nodes": st["n_nodes"], "n_split": st["n_split"], "max_depth": st["max_depth"],
-                       "split_rows": st["split_rows"], "split_attempts": st["split_attempts"],
-                       "fallback_nodes": st["fallback_nodes"]},
-            "roofline": roofline,
-            "rooflines": groups,
         }
+        if args.full:
+            out.update({
+                "index_samples_per_sec": n_total * args.steps / tb,
+                "queries_per_sec": Q * args.steps / tq,
+                # build / query halves: from the breakdown pass (the build drained before the queries start), not the timed region
+                "build_ms_per_step": 1e3 * tb / args.steps, "query_ms_per_step": 1e3 * tq / args.steps,
+                # breakdown: %d extra steps AFTER the timed region, every group bracketed with events
+                "kernel_ms_per_step": {n: round(v["ms"] / n_bd, 3) for n, v in timers.items()},
+                "forest": {"n_nodes": st["n_nodes"], "n_split": st["n_split"], "max_depth": st["max_depth"],
+                           "split_rows": st["split_rows"], "split_attempts": st["split_attempts"],
+                           "fallback_nodes": st["fallback_nodes"]},
+                "roofline": roofline,
+                "rooflines": groups,
+            })
         if verify is not None:
             out["verify"] = verify
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["query_sweep"] = query_sweep(args, index, items, k, st)
             if strong and N == 50_000:
                 out["exact_all_pairs"] = exact_all_pairs(args, local_rank, prep, data["sample_count"])
                 out["exact_all_pairs_shard"] = exact_all_pairs(args, local_rank, prep, data["sample_count"], shard_of=(0, 8))
             if sharded is None:
                 out["sharded_path_at_world_1"] = sharded_overhead(args, index, n_items, items, k, step)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             prep["X_host"] = index.get_items()
             out["cpu_baseline"] = cpu_baseline(args, data, prep, items)
             out["cpu_baseline_mt"] = getattr(cpu_baseline, "mt", None)   # extra: the port on all host cores
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
