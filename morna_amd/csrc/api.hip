@@ -180,13 +180,8 @@ int morna_index_destroy(morna_index *h)
     if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->host_counts) (void)hipHostFree(h->host_counts);
-    if (h->host_out) (void)hipHostFree(h->host_out);
-    if (h->host_small) (void)hipHostFree(h->host_small);
-    if (h->host_q) (void)hipHostFree(h->host_q);
-    if (h->host_tables) (void)hipHostFree(h->host_tables);
     hipStream_t s = h->stream, s2 = h->stream2;
-    delete h;   // DevBuf destructors free HBM
+    delete h;   // DevBuf / PinnedBuf destructors free HBM and the page-locked staging
     if (s2) (void)hipStreamDestroy(s2);
     if (s) (void)hipStreamDestroy(s);
     return MORNA_OK;
@@ -326,9 +321,7 @@ int morna_unstage_junctions(morna_index *h)
     MORNA_TRY(settle(h));
     h->s_keys.release(); h->s_key_off.release(); h->s_row_ptr.release();
     h->s_ids.release(); h->s_cov.release(); h->s_idf.release();
-    for (int i = 0; i < 8; i++) h->scratch[i].release();   // feature-build scratch (fp64 column image ...)
-    h->scratch[24].release();                               // tile extents of the lines
-    h->scratch[25].release();                               // positions of the entries' items
+    h->feat.release();
     h->item_rank.release(); h->item_at.release();
     h->order_n = 0;
     h->staged = false;
@@ -708,7 +701,7 @@ static int load_impl(morna_index *h, const char *path, FILE *f)
     bool ok = true;
     std::vector<float> buf;
     h->host_rows.clear(); h->host_n = 0; h->host_dirty = false; h->built = false;
-    h->half_valid = false;
+    h->half.valid = false;
     if (h->n_items != hd.n_items) h->comm_sizes_valid = false;
     h->n_items = hd.n_items;
     MORNA_TRY(h->X.alloc((size_t)std::max<int64_t>(hd.n_items, 1) * h->dpad));

@@ -103,27 +103,6 @@ int sync_sizes(morna_index *h)
     return MORNA_OK;
 }
 
-// result block in HBM -> the caller's arrays, through the handle's page-locked staging; waits for the stream
-int fetch_results(morna_index *h, const uint8_t *d_block, size_t s_ids, size_t s_dist, size_t dist_elt, int64_t nq, int32_t k,
-                  int32_t *ids_out, void *dist_out, int32_t *count_out)
-{
-    const size_t s_cnt = align_up((size_t)nq * 4, 256), out_bytes = s_ids + s_dist + s_cnt;
-    if (out_bytes > h->host_out_cap) {
-        if (h->host_out) (void)hipHostFree(h->host_out);
-        h->host_out = nullptr;
-        h->host_out_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&h->host_out, out_bytes * 2, hipHostMallocDefault));
-        h->host_out_cap = out_bytes * 2;
-    }
-    HIP_TRY(hipMemcpyAsync(h->host_out, d_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->unsettled = false;
-    memcpy(ids_out, h->host_out, (size_t)nq * k * 4);
-    if (dist_out) memcpy(dist_out, h->host_out + s_ids, (size_t)nq * k * dist_elt);
-    if (count_out) memcpy(count_out, h->host_out + s_ids + s_dist, (size_t)nq * 4);
-    return MORNA_OK;
-}
-
 }  // namespace
 
 // ---- merge of the all-gathered exact answers ---------------------------------------------------------------------
@@ -201,7 +180,7 @@ static int merge_exact_dev(morna_index *h, const uint8_t *gathered_dev, int32_t 
     hipLaunchKernelGGL(merge_exact_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, gathered_dev, exact_msg_bytes(nq, kk),
                        exact_msg_dist_offset(nq, kk), world, nq, kk, k, (int32_t *)p, (double *)(p + s_ids), (int32_t *)(p + s_ids + s_dist));
     HIP_TRY(hipGetLastError());
-    return fetch_results(h, p, s_ids, s_dist, 8, nq, k, ids_out, dist_out, count_out);
+    return fetch_results(h, p, s_ids + s_dist + s_cnt, s_ids, s_dist, 8, nq, k, ids_out, dist_out, count_out);
 }
 
 // this rank's stored rows `local_items` as its share of the queries -> every rank's, all-gathered: [sum n_each][dim] fp32
@@ -261,16 +240,10 @@ static int gather_query_rows(morna_index *h, const int32_t *local_items, int64_t
     if (n_local > 0) MORNA_TRY(morna_get_item_vectors_dev(h, local_items, n_local, mine));   // enqueued, no host wait
     // row of the gathered image that holds query j (rank g's i-th query sits at g * n_max + i), through page-locked memory
     const size_t src_bytes = (size_t)total * 8;
-    if (src_bytes > h->host_q_cap) {
-        if (h->host_q) (void)hipHostFree(h->host_q);
-        h->host_q = nullptr;
-        h->host_q_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&h->host_q, src_bytes * 2, hipHostMallocDefault));
-        h->host_q_cap = src_bytes * 2;
-    }
+    MORNA_TRY(h->host_q.reserve(src_bytes));
     // (every user of the staging block ends with a host wait -- fetch_results here, the small-batch path of query_batch --:
     // no earlier copy can still be reading it)
-    int64_t *src = (int64_t *)h->host_q;
+    int64_t *src = (int64_t *)h->host_q.p;
     int64_t at = 0;
     for (int g = 0; g < world; g++)
         for (int64_t i = 0; i < each[(size_t)g]; i++) src[at++] = (int64_t)g * n_max + i;

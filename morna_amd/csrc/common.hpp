@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 #include <vector>
@@ -61,19 +62,49 @@ struct DevBuf {
     }
 };
 
-// typed view of one persistent scratch slot (same .p / .alloc surface as DevBuf)
-template <typename T>
-struct ScratchRef {
-    DevBuf<uint8_t> &b;
-    T *p = nullptr;
-    explicit ScratchRef(DevBuf<uint8_t> &buf) : b(buf), p((T *)buf.p) {}
-    int alloc(size_t count)
+// page-locked host buffer: grows to twice the need (at least `floor` bytes) and keeps nothing when it does
+struct PinnedBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;  // bytes
+    const unsigned flags;  // hipHostMalloc flags
+    explicit PinnedBuf(unsigned f) : flags(f) {}
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    int reserve(size_t bytes, size_t floor = 0)
     {
-        int rc = b.alloc(count * sizeof(T));
-        p = (T *)b.p;
-        return rc;
+        if (bytes <= cap) return MORNA_OK;
+        release();
+        const size_t want = bytes * 2 > floor ? bytes * 2 : floor;
+        hipError_t e = hipHostMalloc((void **)&p, want, flags);
+        if (e != hipSuccess) {
+            p = nullptr;
+            set_error("hipHostMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
+            return MORNA_E_HIP;
+        }
+        cap = want;
+        return MORNA_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // the device's view of a mapped buffer (null when there is none)
+    void *dev() const
+    {
+        void *d = nullptr;
+        return p && hipHostGetDevicePointer(&d, p, 0) == hipSuccess ? d : nullptr;
     }
 };
+
+// switch read from the environment: on unless set to something atoi reads as 0
+inline bool env_on(const char *name)
+{
+    const char *v = getenv(name);
+    return !(v && atoi(v) == 0);
+}
 
 // one split attempt of one node, as the forest kernels see it
 struct SplitTask {
@@ -115,6 +146,67 @@ struct PendingEv {
     int64_t bytes;
 };
 
+// Build scratch kept in the handle between calls, by owner: a rebuild (or the next level) reuses it without hipMalloc.
+// The buffers only grow (DevBuf::alloc); release() gives a group's memory back.
+struct FeatScratch {   // features.hip
+    DevBuf<int32_t> col, col_count, col_off, col_lines;
+    DevBuf<double> sidf;
+    DevBuf<float> colacc;
+    DevBuf<uint8_t> flags;
+    DevBuf<int32_t> bucket_aux;  // [J] rank of a line in its chunk, then [n_chunks][D] chunk counts / bases
+    DevBuf<int32_t> tile_off;    // [J][aw_tiles + 1] where each tile's piece of a line begins
+    DevBuf<int32_t> pid;         // [nnz] position in the order of every entry's item
+    void release()
+    {
+        col.release(); col_count.release(); col_off.release(); col_lines.release(); sidf.release();
+        colacc.release(); flags.release(); bucket_aux.release(); tile_off.release(); pid.release();
+    }
+};
+
+struct ForestScratch {   // forest.hip
+    DevBuf<int32_t> work;        // two images of every tree's permutation (TASK_ITEMS_AT)
+    DevBuf<int32_t> ones;        // right-side count per task
+    DevBuf<uint8_t> side;        // [n_trees][n_items] side of every row
+    DevBuf<SplitTask> tasks;
+    DevBuf<int32_t> hist, cursor;   // launch order of the chunk split: buckets of 32 row ids
+    DevBuf<int2> info, sched;
+    DevBuf<int32_t> inv;         // matrix-core split: position of every item (or row) in every tree's permutation
+    DevBuf<uint8_t> leaves;      // the leaf segments on their way to gather_leaves_kernel
+    void release()
+    {
+        work.release(); ones.release(); side.release(); tasks.release(); hist.release();
+        cursor.release(); info.release(); sched.release(); inv.release(); leaves.release();
+    }
+};
+
+struct HalfRows {   // splitmm.hip: the fp16 image of X, made once per set of rows; the query filter (knn.hip) reads it too
+    DevBuf<_Float16> x16;        // [n_items][dpad]
+    DevBuf<float> xn;            // [0, N): norms; [N, 2N): 2^-e per row (the query filter unscales with it); [2N, 3N): |s x - y|
+    bool valid = false;          // x16 / xn hold the image of the rows as they are now
+    void release()
+    {
+        x16.release(); xn.release();
+        valid = false;
+    }
+};
+
+struct SplitMmScratch {   // splitmm.hip
+    DevBuf<_Float16> h16;        // fp16 hyperplanes of the level
+    DevBuf<float> hn;            // their norms, then their rounding errors' norms
+    DevBuf<uint8_t> amb;         // the open-pair list (first 16 bytes: its counter)
+    DevBuf<uint8_t> active;      // per-tile task lists: which tasks hold a row of each row tile
+    DevBuf<int32_t> lists;
+    // the order of the contraction's rows (split_mm_order_rows): [rank | item_at], inv by row, the counting sort's table (+ keys)
+    DevBuf<int32_t> maps, invr, table;
+    bool ord_valid = false;      // the build under way has ordered its rows (maps / invr)
+    void release()
+    {
+        h16.release(); hn.release(); amb.release(); active.release(); lists.release();
+        maps.release(); invr.release(); table.release();
+        ord_valid = false;
+    }
+};
+
 }  // namespace morna
 
 struct morna_index {
@@ -130,17 +222,13 @@ struct morna_index {
     bool ev_tables_pending = false;
     // right-side counts of a level, written by partition_kernel straight into page-locked host memory ((epoch << 32) |
     // count per task): the host polls them instead of an event hand-over + copy + stream wait per level
-    unsigned long long *host_counts = nullptr;
-    size_t host_counts_cap = 0;
+    morna::PinnedBuf host_counts{hipHostMallocCoherent | hipHostMallocMapped};
     uint32_t count_epoch = 0;
-    uint8_t *host_out = nullptr;       // page-locked staging of query results
-    size_t host_out_cap = 0;
-    uint8_t *host_small = nullptr;     // page-locked, device-visible: the answers of a small query batch, written by the kernel itself
-    size_t host_small_cap = 0;
-    uint8_t *host_q = nullptr;         // page-locked staging of a small batch's query vectors, padded to the row stride
-    size_t host_q_cap = 0;
-    uint8_t *host_tables = nullptr;    // page-locked staging of the node tables on their way to HBM (forest.hip)
-    size_t host_tables_cap = 0;
+    morna::PinnedBuf host_out{hipHostMallocDefault};    // page-locked staging of query results
+    // page-locked, device-visible: the answers of a small query batch, written by the kernel itself
+    morna::PinnedBuf host_small{hipHostMallocMapped | hipHostMallocCoherent};
+    morna::PinnedBuf host_q{hipHostMallocDefault};      // page-locked staging of a small batch's query vectors, padded to the row stride
+    morna::PinnedBuf host_tables{hipHostMallocMapped};  // page-locked staging of the node tables on their way to HBM (forest.hip)
 
     // host staging of add_item() rows until build()
     std::vector<float> host_rows;  // [host_n][dim]
@@ -154,8 +242,6 @@ struct morna_index {
     morna::DevBuf<morna::RowInfo> rowinfo;   // [n_items] norm2 again with what two_means derives from it
     bool norms_valid = false;
     bool unsettled = false;      // build_features() returned without waiting for its kernels: blocking copies must settle() first
-    bool half_valid = false;     // scratch[19] / [20] hold the fp16 image of X, its norms and scales (splitmm.hip)
-    bool ord_valid = false;      // the build under way has ordered its rows for the split contraction (splitmm.hip, scratch[29..33])
 
     // staged junction lines (CSR by line, file order)
     int64_t J = 0, nnz = 0, key_bytes_n = 0;
@@ -189,9 +275,11 @@ struct morna_index {
     morna::DevBuf<int32_t> ex_cand;
     morna::DevBuf<double> ex_cdist;
     int32_t ex_cap = 0;                // candidates per query the last exact search needed room for
-    // build scratch kept between calls (feature and forest builds reuse it instead of
-    // hipMalloc / hipFree on every call); slots are named in features.hip / forest.hip
-    morna::DevBuf<uint8_t> scratch[35];
+    // build scratch kept between calls
+    morna::FeatScratch feat;
+    morna::ForestScratch forest;
+    morna::HalfRows half;
+    morna::SplitMmScratch splitmm;
     // [0] rows read by query kernels (hyperplane dots + candidates + 1 per query)
     morna::DevBuf<unsigned long long> d_stat;
 
@@ -267,6 +355,10 @@ int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_
                         const int32_t **rank_out, int32_t **inv_out);
 int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, int32_t n_slots, const float *hp_level,
                    const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones);
+// result block in HBM (ids at 0, distances at s_ids, counts at s_ids + s_dist; `bytes` in all) -> the caller's arrays
+// through the handle's page-locked staging (knn.hip); waits for the stream
+int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s_ids, size_t s_dist, size_t dist_elt, int64_t nq,
+                  int32_t k, int32_t *ids_out, void *dist_out, int32_t *count_out);
 // packed_dev (device memory, or null): [nq][2k] int32 message of the row-sharded search -- ids + id_offset, distance bits
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
                 int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev = nullptr,

@@ -803,7 +803,7 @@ int compute_norms(morna_index *h)
         HIP_TRY(hipGetLastError());
     }
     h->norms_valid = true;
-    h->half_valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
+    h->half.valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
     return MORNA_OK;
 }
 
@@ -868,18 +868,16 @@ int build_features(morna_index *h, int64_t n_items)
         return MORNA_E_INVALID;
     }
     // scratch lives in the handle (released by morna_unstage_junctions): a rebuild does no hipMalloc
-    ScratchRef<int32_t> col(h->scratch[0]), col_count(h->scratch[1]), col_off(h->scratch[2]), col_lines(h->scratch[3]);
-    ScratchRef<double> sidf(h->scratch[4]);
-    ScratchRef<float> colacc(h->scratch[5]);
-    ScratchRef<uint8_t> flags(h->scratch[6]);
-    ScratchRef<int32_t> bucket_aux(h->scratch[7]);   // [J] rank of a line in its chunk, then [n_chunks][D] chunk counts / bases
+    DevBuf<int32_t> &col = h->feat.col, &col_count = h->feat.col_count, &col_off = h->feat.col_off, &col_lines = h->feat.col_lines;
+    DevBuf<double> &sidf = h->feat.sidf;
+    DevBuf<float> &colacc = h->feat.colacc;
+    DevBuf<uint8_t> &flags = h->feat.flags;
+    DevBuf<int32_t> &bucket_aux = h->feat.bucket_aux, &tile_off = h->feat.tile_off, &pid = h->feat.pid;
     // with an item order whose length matches: the wave-per-tile form (each entry of the nnz stream read once)
-    static const bool wave_on = !(getenv("MORNA_FEATURES_WAVE") && atoi(getenv("MORNA_FEATURES_WAVE")) == 0);
+    static const bool wave_on = env_on("MORNA_FEATURES_WAVE");
     const bool by_order = wave_on && h->order_n == n_items && J > 0 && h->nnz > 0;   // (the kernels read entry 0 as a dummy)
     constexpr int AW_TILE_SHIFT = 12, AW_TILE = 1 << AW_TILE_SHIFT;   // 4096 positions: 0.61 ms at C3 (2048: 0.76, 8192: 0.83)
     const int32_t aw_tiles = (int32_t)((n_items + AW_TILE - 1) / AW_TILE);
-    ScratchRef<int32_t> tile_off(h->scratch[24]);        // [J][aw_tiles + 1] where each tile's piece of a line begins
-    ScratchRef<int32_t> pid(h->scratch[25]);             // [nnz] position in the order of every entry's item
     if (by_order) MORNA_TRY(tile_off.alloc((size_t)J * (size_t)(aw_tiles + 1)));
     if (by_order) MORNA_TRY(pid.alloc((size_t)h->nnz));
     // algorithmic bytes of this pass: 8*nnz + keys + 8*J + 4*N*D
@@ -911,7 +909,7 @@ int build_features(morna_index *h, int64_t n_items)
             if (by_order) {
                 // ascending check + tile extents of every line; the flag kernels below then look at the lines that do
                 // not ascend only (none, for a file whose lines are sorted and an order that says so)
-                static const bool lds_rank = !(getenv("MORNA_PREP_LDS") && atoi(getenv("MORNA_PREP_LDS")) == 0);
+                static const bool lds_rank = env_on("MORNA_PREP_LDS");
                 if (lds_rank && n_items <= 65536) {
                     const size_t lds = ((size_t)n_items * 2 + 15) / 16 * 16;
                     HIP_TRY(hipFuncSetAttribute((const void *)line_prep_lds_kernel<AW_TILE_SHIFT>,
@@ -997,7 +995,7 @@ int build_features(morna_index *h, int64_t n_items)
         h->built = false;
         if (fused) {
             h->norms_valid = true;
-            h->half_valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
+            h->half.valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
         } else {
             MORNA_TRY(compute_norms(h));
         }

@@ -26,9 +26,6 @@
 //                     hyperplane resident in LDS) against its node's hyperplane, one
 //                     workgroup per 64 positions of a node; launch order sorted by row
 //                     id, one run per XCD, so the trees' re-reads hit L2.
-//   split_rw_kernel   the same work at shallow levels (<= 4 split nodes per tree) as
-//                     row windows x tree groups: a row is loaded once into registers
-//                     and used for every tree of the group (runs with MORNA_SPLIT_MM=0).
 //   post_counts_kernel  the level's right-side counts into a page-locked mailbox the host polls
 //   (host)            annoy's 3-attempt / 0.95 imbalance rule on the counts
 //   fallback_kernel   random sides for nodes still above 0.99
@@ -702,138 +699,6 @@ __global__ __launch_bounds__(SP_THREADS) void split_kernel(const float *__restri
     if (tid == 0 && s_ones) atomicAdd(&ones[lo], s_ones);
 }
 
-// ---- shallow levels: row-window form of the split kernel ---------------------------
-// While a tree has at most RW_SLOTS / G split nodes, a workgroup takes a WINDOW of RW_ROWS
-// consecutive row ids and a GROUP of G trees: the <= RW_SLOTS hyperplanes those trees
-// can need sit in LDS, each wave loads a row ONCE into registers and dots it against
-// the hyperplane of its node in every tree of the group.  L2 -> CU traffic per
-// (row, tree) drops from one row to 1/G row; same wave_dot order, same results.
-
-#define RW_THREADS 1024   // 16 waves: the kernel must stay within 128 VGPRs (one row buffer per wave)
-#define RW_WAVES (RW_THREADS / WAVE)
-#define RW_ROWS 256       // rows per window: the hyperplane staging is paid once per 16 rows of every wave
-#define RW_SLOTS 12       // hyperplanes resident in LDS (144 KB at D = 3000): one workgroup per CU
-
-// inverse of the permutation restricted to the tasks: row -> (task index, position in segment)
-__global__ void invert_kernel(const SplitTask *__restrict__ tasks, int32_t n_tasks, int32_t n_chunks,
-                              const int32_t *__restrict__ perm, int64_t n_items, int32_t *__restrict__ row_task,
-                              int32_t *__restrict__ row_pos)
-{
-    const int c = blockIdx.x;
-    if (c >= n_chunks) return;
-    int lo = 0, hi = n_tasks - 1;   // the task owning this chunk (tasks are sorted by chunk0)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tasks[mid].chunk0 <= c) lo = mid; else hi = mid - 1;
-    }
-    const int a = lo;
-    const SplitTask t = tasks[a];
-    const int p = (c - t.chunk0) * 64 + threadIdx.x;
-    if (p < t.count) {
-        const int64_t row = perm[TASK_ITEMS_AT(t, n_items) + p];
-        row_task[(int64_t)t.tree * n_items + row] = a;
-        row_pos[(int64_t)t.tree * n_items + row] = p;
-    }
-}
-
-template <int NV, int GT>   // NV float4 per lane hold one row (dpad / 256); GT trees per group
-__global__ __launch_bounds__(RW_THREADS) void split_rw_kernel(
-    const float *__restrict__ X, int64_t n_items, int32_t dpad, const SplitTask *__restrict__ tasks,
-    const int32_t *__restrict__ tree_first /* [n_trees + 1] */, int32_t n_trees, int32_t G,
-    const int32_t *__restrict__ row_task, const int32_t *__restrict__ row_pos, uint32_t seed,
-    const float *__restrict__ hp, uint8_t *__restrict__ side, int32_t *__restrict__ ones, int32_t n_windows,
-    int32_t n_groups)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float4 *hs = (float4 *)smem;   // [RW_SLOTS][nvec]
-    __shared__ int s_ones[RW_SLOTS], s_start[RW_SLOTS], s_hp[RW_SLOTS];
-    __shared__ uint32_t s_seed[RW_SLOTS];
-
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
-    const int nvec = dpad / 4;
-    // workgroup b runs on XCD b % 8: all tree groups of one window stay on one XCD, back to back
-    const int x = blockIdx.x & 7, r = blockIdx.x >> 3;
-    const int win = (r / n_groups) * 8 + x, g = r % n_groups;
-    if (win >= n_windows) return;
-    const int t0 = g * G, t1 = (t0 + G) < n_trees ? (t0 + G) : n_trees;
-    const int a0 = tree_first[t0], nslots = tree_first[t1] - a0;   // <= RW_SLOTS by construction
-    if (tid < nslots) {
-        const SplitTask t = tasks[a0 + tid];
-        s_ones[tid] = 0;
-        s_start[tid] = t.start;
-        s_hp[tid] = t.slot;
-        s_seed[tid] = node_seed(seed, (uint32_t)t.tree, (uint32_t)t.level, (uint32_t)t.start, (uint32_t)t.attempt);
-    }
-    __syncthreads();
-    // stage the group's hyperplanes as ONE flat copy: only one workgroup fits a CU, nothing else
-    // would hide a slot-by-slot chain of dependent loads
-    for (int idx = tid; idx < nslots * nvec; idx += RW_THREADS) {
-        const int s = idx / nvec, v = idx - s * nvec;
-        hs[idx] = ((const float4 *)(hp + (int64_t)s_hp[s] * dpad))[v];
-    }
-    __syncthreads();
-    if (nslots > 0) {
-        constexpr int LSTEP = WAVE / (GT == 3 ? 4 : GT);
-        const int ng = t1 - t0;
-        const int64_t row_base = (int64_t)win * RW_ROWS;
-        // a row and its (task, position) per tree of the group are fetched one row ahead
-        auto load_row = [&](int rr, float4(&xr)[NV], int &ma, int &mp) {
-            const int64_t row = row_base + rr;
-            const float4 *xp = (const float4 *)(X + row * dpad);
-#pragma unroll
-            for (int k = 0; k < NV; k++) xr[k] = xp[lane + k * WAVE];   // dpad == NV * 256: no idle lane
-            ma = -1;
-            mp = 0;
-            if (lane % LSTEP == 0 && lane / LSTEP < ng) {   // lane gi * LSTEP looks after tree gi of the group
-                ma = row_task[(int64_t)(t0 + lane / LSTEP) * n_items + row];
-                mp = row_pos[(int64_t)(t0 + lane / LSTEP) * n_items + row];
-            }
-        };
-        // the row against its node's hyperplane in every tree of the group, branch-free and with k
-        // outermost: GT independent FMA chains are in flight, a tree that does not own the row reads
-        // slot 0 and its result is dropped.  The GT lane-sums are reduced together
-        // (wave_sum_multi): tree gi's dot arrives in lane gi * LSTEP, the lane that holds the
-        // row's (task, position) for that tree and writes its side byte.
-        auto process = [&](const float4(&xr)[NV], int ma, int mp) {
-            const float4 *hv[GT];
-            Acc4 c[GT];
-#pragma unroll
-            for (int gi = 0; gi < GT; gi++) {
-                const int a = __builtin_amdgcn_readlane(ma, gi * LSTEP);   // lanes of absent trees hold -1
-                hv[gi] = hs + (a < 0 ? 0 : a - a0) * nvec + lane;
-                c[gi] = acc4_zero();
-            }
-#pragma unroll
-            for (int k = 0; k < NV; k++) {
-#pragma unroll
-                for (int gi = 0; gi < GT; gi++) fma4(c[gi], xr[k], hv[gi][k * WAVE]);
-            }
-            float f[GT];
-#pragma unroll
-            for (int gi = 0; gi < GT; gi++) f[gi] = (c[gi].lo.x + c[gi].lo.y) + (c[gi].hi.x + c[gi].hi.y);
-            const float d = wave_sum_multi<GT>(f, lane);
-            if (ma >= 0) {   // only lanes gi * LSTEP of present trees
-                const int s = ma - a0;
-                const int sd = d != 0.f ? (d > 0.f) : pos_flip(s_seed[s], (uint32_t)mp);
-                side[(int64_t)(t0 + lane / LSTEP) * n_items + s_start[s] + mp] = (uint8_t)sd;
-                if (sd) atomicAdd(&s_ones[s], 1);
-            }
-        };
-        auto valid = [&](int rr) { return rr < RW_ROWS && row_base + rr < n_items; };
-        // ONE row buffer per wave (<= 128 VGPRs), 16 waves per CU: the other three waves of the SIMD cover
-        // a wave's load latency.  Measured against two waves per SIMD with three row buffers in rotation
-        // (prefetch distance 2): 2.06 / 2.11 / 3.08 ms instead of 2.29 / 2.70 / 3.70 ms per level.
-        float4 xr[NV];
-        int ma = -1, mp = 0;
-        for (int rr = w; valid(rr); rr += RW_WAVES) {
-            load_row(rr, xr, ma, mp);
-            process(xr, ma, mp);
-        }
-    }
-    __syncthreads();
-    if (tid < nslots && s_ones[tid]) atomicAdd(&ones[a0 + tid], s_ones[tid]);
-}
-
 // random sides for nodes whose best split is still > 0.99 imbalanced
 __global__ __launch_bounds__(256) void fallback_kernel(const SplitTask *__restrict__ tasks, int64_t n_items,
                                                        int32_t dpad, uint32_t seed, uint8_t *__restrict__ side,
@@ -1048,27 +913,25 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
 
     MORNA_TRY(h->perm.alloc((size_t)n_trees * N));
     // scratch lives in the handle: a rebuild (or the next level) reuses it without hipMalloc
-    ScratchRef<int32_t> work(h->scratch[8]), d_ones(h->scratch[9]);   // work: two images of every tree's permutation (TASK_ITEMS_AT)
-    ScratchRef<uint8_t> side(h->scratch[10]);
-    ScratchRef<SplitTask> d_tasks(h->scratch[11]);
+    DevBuf<int32_t> &work = h->forest.work, &d_ones = h->forest.ones;
+    DevBuf<uint8_t> &side = h->forest.side;
+    DevBuf<SplitTask> &d_tasks = h->forest.tasks;
     MORNA_TRY(work.alloc((size_t)n_trees * N * 2));
     MORNA_TRY(side.alloc((size_t)n_trees * N));
     // launch-order scratch of the split kernel: buckets of 32 row ids
-    ScratchRef<int32_t> d_hist(h->scratch[12]), d_cursor(h->scratch[13]);
-    ScratchRef<int2> d_info(h->scratch[14]), d_sched(h->scratch[15]);
+    DevBuf<int32_t> &d_hist = h->forest.hist, &d_cursor = h->forest.cursor;
+    DevBuf<int2> &d_info = h->forest.info, &d_sched = h->forest.sched;
     const int32_t n_buckets = (int32_t)std::min<int64_t>(SCHED_MAX_BUCKETS, std::max<int64_t>(1, (N + 31) / 32));
     MORNA_TRY(d_hist.alloc((size_t)n_buckets));
     MORNA_TRY(d_cursor.alloc((size_t)n_buckets));
-    // row-window form of the shallow levels: inverse permutation per tree
-    ScratchRef<int32_t> row_task(h->scratch[16]), row_pos(h->scratch[17]), d_tree_first(h->scratch[18]);
     // matrix-core split: position of every item in every tree's permutation, kept current by partition_kernel
-    static const bool mm_on = !(getenv("MORNA_SPLIT_MM") && atoi(getenv("MORNA_SPLIT_MM")) == 0);
-    static const bool order_on = !(getenv("MORNA_SPLIT_ORDER") && atoi(getenv("MORNA_SPLIT_ORDER")) == 0);
-    ScratchRef<int32_t> inv(h->scratch[26]);
+    static const bool mm_on = env_on("MORNA_SPLIT_MM");
+    static const bool order_on = env_on("MORNA_SPLIT_ORDER");
+    DevBuf<int32_t> &inv = h->forest.inv;
     if (mm_on) MORNA_TRY(inv.alloc((size_t)n_trees * N));
     int32_t *inv_p = mm_on ? inv.p : nullptr;   // by item; by row once the rows have been ordered (rank_p)
     const int32_t *rank_p = nullptr;
-    h->ord_valid = false;
+    h->splitmm.ord_valid = false;
     std::vector<int32_t> tree_first;
     {
         const int64_t total = (int64_t)n_trees * N;
@@ -1190,21 +1053,14 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
         // that every partition workgroup writes before anything else, tagged with this call's epoch: the host polls the
         // tags (no event hand-over, no copy, no stream wait) and prepares the next attempt or level while the partition runs.
         auto partition_and_fetch_counts = [&](int32_t A, int64_t level_rows) -> int {
-            if ((size_t)A > h->host_counts_cap) {
+            if ((size_t)A * 8 > h->host_counts.cap) {
                 if (hipStreamSynchronize(h->stream) != hipSuccess) return MORNA_E_HIP;   // nobody writes the old buffer any more
-                if (h->host_counts) (void)hipHostFree(h->host_counts);
-                h->host_counts = nullptr;
-                h->host_counts_cap = std::max<size_t>(4096, (size_t)A * 2);
-                if (hipHostMalloc((void **)&h->host_counts, h->host_counts_cap * 8, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-                    h->host_counts_cap = 0;
-                    set_error("forest build: hipHostMalloc of the count mailbox failed");
-                    return MORNA_E_HIP;
-                }
-                memset(h->host_counts, 0, h->host_counts_cap * 8);
+                MORNA_TRY(h->host_counts.reserve((size_t)A * 8, 4096 * 8));
+                memset(h->host_counts.p, 0, h->host_counts.cap);   // the epochs below start from a zeroed mailbox
             }
             const uint32_t epoch = ++h->count_epoch ? h->count_epoch : ++h->count_epoch;   // never 0: the mailbox starts zeroed
-            hipLaunchKernelGGL(post_counts_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, h->stream, d_ones.p, A, h->host_counts,
-                               epoch);
+            hipLaunchKernelGGL(post_counts_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, h->stream, d_ones.p, A,
+                               (unsigned long long *)h->host_counts.p, epoch);
             {
                 ScopedTimer tm(h, MORNA_T_PARTITION, 0);
                 if (level_rows >= (int64_t)A * 2048)
@@ -1220,7 +1076,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             }
             write_late_tables();   // the previous level's node-table entries, while this level's kernels run
             h_ones.resize((size_t)A);
-            volatile unsigned long long *box = h->host_counts;
+            volatile unsigned long long *box = (volatile unsigned long long *)h->host_counts.p;
             int64_t spins = 0;
             for (int32_t a = 0; a < A; a++) {
                 unsigned long long v;
@@ -1245,21 +1101,14 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
         // counts have been read back since)
         auto upload_tasks = [&](const std::vector<SplitTask> &tk) -> int {
             const size_t bytes = tk.size() * sizeof(SplitTask);
-            if (bytes > h->host_tables_cap) {
+            if (bytes > h->host_tables.cap) {
                 if (hipStreamSynchronize(h->stream) != hipSuccess) return MORNA_E_HIP;
-                if (h->host_tables) (void)hipHostFree(h->host_tables);
-                h->host_tables = nullptr;
-                h->host_tables_cap = 0;
-                if (hipHostMalloc((void **)&h->host_tables, std::max<size_t>(bytes * 2, 1 << 16), hipHostMallocMapped) != hipSuccess) {
-                    set_error("forest build: hipHostMalloc of the task staging failed");
-                    return MORNA_E_HIP;
-                }
-                h->host_tables_cap = std::max<size_t>(bytes * 2, 1 << 16);
+                MORNA_TRY(h->host_tables.reserve(bytes, 1 << 16));
             }
-            memcpy(h->host_tables, tk.data(), bytes);
+            memcpy(h->host_tables.p, tk.data(), bytes);
             static_assert(sizeof(SplitTask) % 16 == 0, "tasks are moved in 16-byte words");
-            void *dev_view = nullptr;
-            if (hipHostGetDevicePointer(&dev_view, h->host_tables, 0) != hipSuccess) {
+            void *dev_view = h->host_tables.dev();
+            if (!dev_view) {
                 set_error("forest build: the task staging is not visible to the device");
                 return MORNA_E_HIP;
             }
@@ -1277,7 +1126,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             const int32_t A = (int32_t)tasks.size();
             int64_t rows = 0;
             for (const SplitTask &t : tasks) rows += t.count;
-            // shallow level, whole level pending: row-window form (rows reused across a tree group)
+            // most split nodes of one tree in this attempt (tree_first[t]: the first task of tree t)
             int max_per_tree = 0;
             tree_first.assign((size_t)n_trees + 1, A);
             for (int32_t a = A - 1; a >= 0; a--) tree_first[(size_t)tasks[(size_t)a].tree] = a;
@@ -1285,26 +1134,18 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 if (tree_first[(size_t)t] > tree_first[(size_t)t + 1]) tree_first[(size_t)t] = tree_first[(size_t)t + 1];
             for (int t = 0; t < n_trees; t++)
                 max_per_tree = std::max(max_per_tree, tree_first[(size_t)t + 1] - tree_first[(size_t)t]);
-            const int nv = (dpad / 4 + WAVE - 1) / WAVE;
-            // measured on MI355X (C3, 1e7 rows per level): 2.4 / 2.8 / 3.8 ms with 1 / 2 / 4 nodes per tree
-            // against 4.7 ms for the chunk form, so it is used while a tree has at most 4 split nodes
-            // (MORNA_SPLIT_RW=0 turns it off, =2 restricts it to 2 nodes per tree)
-            static const int rw_max = getenv("MORNA_SPLIT_RW") ? atoi(getenv("MORNA_SPLIT_RW")) : 4;
-            const bool nv_ok = nv == 1 || nv == 2 || nv == 3 || nv == 4 || nv == 6 || nv == 8 || nv == 12;
-            const bool use_rw = attempt == 0 && max_per_tree >= 1 && max_per_tree <= std::min(rw_max, RW_SLOTS / 2) &&
-                                nv_ok && rows * 2 >= (int64_t)n_trees * N;
             // While a tree has few split nodes and most rows still sit in split nodes, the whole level is one
             // contraction on the matrix cores (splitmm.hip): its cost grows with the nodes per tree (every row
             // meets every hyperplane), the chunk form's does not -- they meet near 64 nodes per tree.
-            // MORNA_SPLIT_MM=0 turns it off (row-window / chunk forms as before).
+            // MORNA_SPLIT_MM=0 turns it off (the chunk form at every level).
             // Once the rows of the contraction are ordered and the level has enough tasks for the per-tile lists
             // (splitmm.hip), a row tile meets only the tasks that hold one of its rows, and the cost follows the (tile,
             // task) pairs that exist: then deeper levels (up to 256 nodes per tree) and the retries of a level go there too,
             // as does any set of tasks whose all-pairs product in 128 x 128 tiles is cheaper than streaming the rows once
             // per tree (measured at D = 3000: 0.13 us per tile pair, 0.47 ns per row of the chunk form, both ~ dpad).
             // On a shard of 200k x 3000 the chunk form took 28 of the split's 34 ms, retries and levels 7+.
-            static const bool lists_env = !(getenv("MORNA_SPLIT_LISTS") && atoi(getenv("MORNA_SPLIT_LISTS")) == 0);
-            const bool mm_lists = lists_env && h->ord_valid && A >= 512 && max_per_tree <= 256;
+            static const bool lists_env = env_on("MORNA_SPLIT_LISTS");
+            const bool mm_lists = lists_env && h->splitmm.ord_valid && A >= 512 && max_per_tree <= 256;
             const double mm_dense_us = (double)((N + 127) / 128) * (double)((A + 127) / 128) * 0.13, chunk_us = (double)rows * 0.47e-3;
             const bool use_mm = mm_on && max_per_tree >= 1 &&
                                 (mm_lists || (max_per_tree <= 32 && (attempt == 0 ? rows * 2 >= (int64_t)n_trees * N : mm_dense_us < chunk_us)));
@@ -1312,7 +1153,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             // (d_ones is zeroed by the two_means kernel of the attempt, task by task: a hipMemsetAsync costs ~15 us of
             // idle device around its few microseconds)
             bool side_work = false;
-            if (use_mm && !h->half_valid) {
+            if (use_mm && !h->half.valid) {
                 // once per set of rows: their fp16 image, on the side stream while two_means (a latency chain on few CUs
                 // at the root level) has the main one.  Nothing else of the matrix-core split needs a side stream: a
                 // row's node is looked up through `inv`, which the partition of the previous level left current (round 1
@@ -1322,26 +1163,13 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 if ((rc = split_mm_prepare_rows(h, h->stream2))) { cleanup(); return rc; }
                 F_TRY(hipEventRecord(h->ev_join, h->stream2));
                 side_work = true;
-            } else if (use_mm && order_on && level == 1 && !h->ord_valid && N >= 8192 && N <= ((int64_t)1 << 22) && n_trees >= 2) {
+            } else if (use_mm && order_on && level == 1 && !h->splitmm.ord_valid && N >= 8192 && N <= ((int64_t)1 << 22) && n_trees >= 2) {
                 // second level: the rows of the contraction are put in an order in which neighbours are alike (the sides of
                 // the root splits say which are), on the side stream under this level's two_means; from here on `inv` is
                 // kept by row (splitmm.hip, split_mm_order_rows; its counting sort's table is 16 KB per 256 rows: up to 4 M rows)
                 F_TRY(hipEventRecord(h->ev_fork, h->stream));
                 F_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
                 if ((rc = split_mm_order_rows(h, side.p, inv_p, n_trees, h->stream2, &rank_p, &inv_p))) { cleanup(); return rc; }
-                F_TRY(hipEventRecord(h->ev_join, h->stream2));
-                side_work = true;
-            } else if (use_rw && !use_mm) {
-                // row-window form (MORNA_SPLIT_MM=0): row -> (task, position) per tree on the side stream
-                if ((rc = row_task.alloc((size_t)n_trees * N)) || (rc = row_pos.alloc((size_t)n_trees * N)) ||
-                    (rc = d_tree_first.alloc((size_t)n_trees + 1))) { cleanup(); return rc; }
-                F_TRY(hipEventRecord(h->ev_fork, h->stream));
-                F_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-                F_TRY(hipMemcpyAsync(d_tree_first.p, tree_first.data(), ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, h->stream2));
-                if (rows != (int64_t)n_trees * N)   // rows outside every split node must read "no task"
-                    F_TRY(hipMemsetAsync(row_task.p, 0xFF, (size_t)n_trees * N * 4, h->stream2));
-                hipLaunchKernelGGL(invert_kernel, dim3((unsigned)n_chunks), dim3(64), 0, h->stream2, d_tasks.p, A, n_chunks,
-                                   work.p, N, row_task.p, row_pos.p);
                 F_TRY(hipEventRecord(h->ev_join, h->stream2));
                 side_work = true;
             }
@@ -1356,7 +1184,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 // node's 200-step chain is then 2-3x shorter (C3: 0.32 / 0.28 ms instead of 0.7 ms at the two
                 // shallowest levels).  Deeper levels are bound by the HBM gather of the rows (C3, 1600 nodes: 5.9 TB/s)
                 // and four waves per node only add work there.  MORNA_TM_STRIP=0: one wave per node everywhere.
-                static const bool tm_strip_on = !(getenv("MORNA_TM_STRIP") && atoi(getenv("MORNA_TM_STRIP")) == 0);
+                static const bool tm_strip_on = env_on("MORNA_TM_STRIP");
                 const bool tm_strip = tm_strip_on && A <= 2 * h->n_cus;
                 const bool strip_runs = tm_strip && (nvq == 12 || nvq == 8 || nvq == 4 || (nvq >= 16 && nvq <= 32 && nvq % 4 == 0));
                 ScopedTimer tk(h, strip_runs ? MORNA_T_TM_STRIP : MORNA_T_TM_WAVE, 4 * (int64_t)D * (TM_ITERS + 2) * A);   // per kernel, beside the group
@@ -1384,7 +1212,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
 #undef TMW_LAUNCH
 #undef TMS_LAUNCH
             }
-            if (!use_mm && !use_rw) {
+            if (!use_mm) {
                 // chunk form: launch order = chunks sorted by first row id, one contiguous run per XCD
                 if ((rc = d_info.alloc((size_t)n_chunks)) || (rc = d_sched.alloc((size_t)n_chunks))) { cleanup(); return rc; }
                 F_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)n_buckets * 4, h->stream));
@@ -1402,37 +1230,6 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                     cleanup();
                     return rc;
                 }
-            } else if (use_rw) {
-                // trees per group: 8 / 4 / 3 / 2 with 1 / 2 / 3-4 / 5-6 split nodes per tree (<= RW_SLOTS hyperplanes)
-                const int G = max_per_tree == 1 ? 8 : max_per_tree == 2 ? 4 : max_per_tree <= 4 ? 3 : 2;
-                const int n_windows = (int)((N + RW_ROWS - 1) / RW_ROWS), n_groups = (n_trees + G - 1) / G;
-                ScopedTimer tm(h, MORNA_T_SPLIT, 4 * (int64_t)D * (rows + A));
-                const unsigned grid = 8u * (unsigned)((n_windows + 7) / 8) * (unsigned)n_groups;
-                const size_t lds = (size_t)G * max_per_tree * dpad * 4;
-#define RW_LAUNCH_G(NVV, GTT)                                                                                            \
-    do {                                                                                                                 \
-        F_TRY(hipFuncSetAttribute((const void *)split_rw_kernel<NVV, GTT>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                  (int)lds));                                                                            \
-        hipLaunchKernelGGL((split_rw_kernel<NVV, GTT>), dim3(grid), dim3(RW_THREADS), lds, h->stream, h->X.p, N, dpad,     \
-                           d_tasks.p, d_tree_first.p, n_trees, G, row_task.p, row_pos.p, seed, hp_level, side.p, d_ones.p, \
-                           n_windows, n_groups);                                                                         \
-    } while (0)
-#define RW_LAUNCH(NVV)                          \
-    do {                                        \
-        if (G == 8) RW_LAUNCH_G(NVV, 8);        \
-        else if (G == 4) RW_LAUNCH_G(NVV, 4);   \
-        else if (G == 3) RW_LAUNCH_G(NVV, 3);   \
-        else RW_LAUNCH_G(NVV, 2);               \
-    } while (0)
-                if (nv == 1) RW_LAUNCH(1);
-                else if (nv == 2) RW_LAUNCH(2);
-                else if (nv == 3) RW_LAUNCH(3);
-                else if (nv == 4) RW_LAUNCH(4);
-                else if (nv == 6) RW_LAUNCH(6);
-                else if (nv == 8) RW_LAUNCH(8);
-                else RW_LAUNCH(12);
-#undef RW_LAUNCH
-#undef RW_LAUNCH_G
             } else {
                 // algorithmic bytes: 4*D*sum|node| + 4*D*#split nodes
                 ScopedTimer tm(h, MORNA_T_SPLIT, 4 * (int64_t)D * (rows + A));
@@ -1512,37 +1309,36 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
         const size_t o_tree = b_rec /* 16 bytes per node */, o_hp = (o_tree + b_tree + 15) / 16 * 16, o_leaf = (o_hp + b_hp + 15) / 16 * 16,
                      need = o_leaf + b_leaf;
         static_assert(sizeof(LeafSeg) == 16, "leaves are moved in 16-byte words");
-        if (need > h->host_tables_cap) {
-            if (h->host_tables) {
+        if (need > h->host_tables.cap) {
+            if (h->host_tables.p) {
                 if (h->ev_tables_pending) F_TRY(hipEventSynchronize(h->ev_tables));   // a copy out of the old buffer may be in flight
                 F_TRY(hipStreamSynchronize(h->stream));                               // (or a task list being pulled)
-                (void)hipHostFree(h->host_tables);
             }
-            h->host_tables = nullptr;
-            h->host_tables_cap = 0;
-            F_TRY(hipHostMalloc((void **)&h->host_tables, need * 2, hipHostMallocMapped));
-            h->host_tables_cap = need * 2;
+            if ((rc = h->host_tables.reserve(need))) { cleanup(); return rc; }
         }
-        memcpy(h->host_tables, rec.data(), b_rec);
-        memcpy(h->host_tables + o_tree, ntree.data(), b_tree);
-        memcpy(h->host_tables + o_hp, nhp.data(), b_hp);
-        memcpy(h->host_tables + o_leaf, leaves.data(), b_leaf);
+        memcpy(h->host_tables.p, rec.data(), b_rec);
+        memcpy(h->host_tables.p + o_tree, ntree.data(), b_tree);
+        memcpy(h->host_tables.p + o_hp, nhp.data(), b_hp);
+        memcpy(h->host_tables.p + o_leaf, leaves.data(), b_leaf);
         // (pulled by the device, as the task lists are; the tables are whole 16-byte words apart from their tails)
-        void *dev_view = nullptr;
-        F_TRY(hipHostGetDevicePointer(&dev_view, h->host_tables, 0));
-        const uint8_t *dv = (const uint8_t *)dev_view;
+        const uint8_t *dv = (const uint8_t *)h->host_tables.dev();
+        if (!dv) {
+            set_error("forest build: the node-table staging is not visible to the device");
+            cleanup();
+            return MORNA_E_HIP;
+        }
         auto pull = [&](void *dst, const uint8_t *src, size_t bytes) -> hipError_t {
             const int32_t n16 = (int32_t)(bytes / 16);
             if (n16 > 0)
                 hipLaunchKernelGGL(pull_tasks_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, h->stream, (const int4 *)src,
                                    (int4 *)dst, n16);
             if (bytes % 16)   // the tail, if any
-                return hipMemcpyAsync((uint8_t *)dst + (size_t)n16 * 16, h->host_tables + (src - dv) + (size_t)n16 * 16, bytes % 16,
+                return hipMemcpyAsync((uint8_t *)dst + (size_t)n16 * 16, h->host_tables.p + (src - dv) + (size_t)n16 * 16, bytes % 16,
                                       hipMemcpyHostToDevice, h->stream);
             return hipGetLastError();
         };
         // the leaves first: their items go from the work images into the permutation the searches read
-        ScratchRef<uint8_t> d_leaves(h->scratch[34]);
+        DevBuf<uint8_t> &d_leaves = h->forest.leaves;
         if ((rc = d_leaves.alloc(std::max<size_t>(b_leaf, 16)))) { cleanup(); return rc; }
         F_TRY(pull(d_leaves.p, dv + o_leaf, b_leaf));
         if (!leaves.empty())

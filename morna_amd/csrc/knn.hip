@@ -953,6 +953,19 @@ __global__ void pack_topk_kernel(const int32_t *__restrict__ ids, const float *_
     packed[q * 2 * k + k + r] = __float_as_int(dist[i]);
 }
 
+int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s_ids, size_t s_dist, size_t dist_elt, int64_t nq,
+                  int32_t k, int32_t *ids_out, void *dist_out, int32_t *count_out)
+{
+    MORNA_TRY(h->host_out.reserve(bytes));
+    HIP_TRY(hipMemcpyAsync(h->host_out.p, d_block, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->unsettled = false;
+    memcpy(ids_out, h->host_out.p, (size_t)nq * k * 4);
+    if (dist_out) memcpy(dist_out, h->host_out.p + s_ids, (size_t)nq * k * dist_elt);
+    if (count_out) memcpy(count_out, h->host_out.p + s_ids + s_dist, (size_t)nq * 4);
+    return MORNA_OK;
+}
+
 // q_host: query vectors in host OR device memory (unified addressing), q_stride floats apart (0 = dim)
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
                 int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev, int64_t id_offset)
@@ -985,10 +998,10 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
 
     // candidate filter on the fp16 rows (MORNA_QUERY_FILTER=0: every candidate gets the fp32 dot); pays when a
     // query has many more candidates than results.  MORNA_QUERY_DENSE=0 keeps the per-candidate gather form.
-    static const bool filter_on = !(getenv("MORNA_QUERY_FILTER") && atoi(getenv("MORNA_QUERY_FILTER")) == 0);
-    static const bool dense_on = !(getenv("MORNA_QUERY_DENSE") && atoi(getenv("MORNA_QUERY_DENSE")) == 0);
+    static const bool filter_on = env_on("MORNA_QUERY_FILTER");
+    static const bool dense_on = env_on("MORNA_QUERY_DENSE");
     // fewer queries than would give every CU a workgroup: the spread form (MORNA_QUERY_SPREAD=0: one workgroup per query)
-    const bool spread_on = !(getenv("MORNA_QUERY_SPREAD") && atoi(getenv("MORNA_QUERY_SPREAD")) == 0);
+    const bool spread_on = env_on("MORNA_QUERY_SPREAD");
     const bool filter_pays = filter_on && cap > 4 * (int64_t)k;
     // the whole-batch contraction reads every fp16 row once; the gather form reads min(cap, ~K) rows per query
     // (C3, 48 / 63 queries: 207 us through the contraction, 231 / 282 us through the spread form; 32: the spread form's 174 us)
@@ -1045,8 +1058,8 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         P.X16 = nullptr; P.xscale = nullptr; P.xn16 = P.xe16 = nullptr; P.delta = 0.f;
         P.scores = nullptr; P.qscale = P.qn16 = P.qe16 = nullptr; P.eacc = P.eacc_big = 0.f; P.big_rows = 0;
         if (use_filter) {
-            const float *xn = (const float *)h->scratch[20].p;
-            P.X16 = (const _Float16 *)h->scratch[19].p;
+            const float *xn = h->half.xn.p;
+            P.X16 = h->half.x16.p;
             P.xn16 = xn; P.xscale = xn + N; P.xe16 = xn + 2 * N;
             // gather form: |cos from the fp16 row - cos from the fp32 row| <= 2^-11 (one rounding to 11 bits, the query
             // is not rounded) + the fp32 accumulations of both dots (any order: < dpad * 2^-24 each); the distance is
@@ -1071,14 +1084,8 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 (void)hipGetLastError();   // (an unregistered host pointer reports an error on some runtimes)
                 if (on_host) {
                     const size_t need = (size_t)nb * h->dpad * 4;
-                    if (need > h->host_q_cap) {
-                        if (h->host_q) (void)hipHostFree(h->host_q);
-                        h->host_q = nullptr;
-                        h->host_q_cap = 0;
-                        HIP_TRY(hipHostMalloc((void **)&h->host_q, need * 2, hipHostMallocDefault));
-                        h->host_q_cap = need * 2;
-                    }
-                    float *hq = (float *)h->host_q;
+                    MORNA_TRY(h->host_q.reserve(need));
+                    float *hq = (float *)h->host_q.p;
                     for (int64_t i = 0; i < nb; i++) {
                         memcpy(hq + i * h->dpad, q_host + (q0 + i) * q_stride, (size_t)h->dim * 4);
                         memset(hq + i * h->dpad + h->dim, 0, (size_t)(h->dpad - h->dim) * 4);
@@ -1132,15 +1139,12 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         const bool direct = spread && ids_out && !packed_dev;
         if (direct) {
             const size_t need = 2 * s_ids + s_qf;
-            if (need > h->host_small_cap) {
-                if (h->host_small) (void)hipHostFree(h->host_small);
-                h->host_small = nullptr;
-                h->host_small_cap = 0;
-                HIP_TRY(hipHostMalloc((void **)&h->host_small, need * 2, hipHostMallocMapped | hipHostMallocCoherent));
-                h->host_small_cap = need * 2;
+            MORNA_TRY(h->host_small.reserve(need));
+            uint8_t *dp = (uint8_t *)h->host_small.dev();
+            if (!dp) {
+                set_error("query: the answer staging is not visible to the device");
+                return MORNA_E_HIP;
             }
-            uint8_t *dp = nullptr;
-            HIP_TRY(hipHostGetDevicePointer((void **)&dp, h->host_small, 0));
             P.ids_out = (int32_t *)dp;
             P.dist_out = (float *)(dp + s_ids);
             P.count_out = (int32_t *)(dp + 2 * s_ids);
@@ -1183,7 +1187,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
                 // 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup per CU), the
                 // 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0: for all rows)
-                static const bool big_on = !(getenv("MORNA_QUERY_BIG") && atoi(getenv("MORNA_QUERY_BIG")) == 0);
+                static const bool big_on = env_on("MORNA_QUERY_BIG");
                 int64_t big_tiles = 0;
                 if (big_on && nb >= 512) {
                     const int64_t n_ct_big = (nb + 255) / 256;
@@ -1219,7 +1223,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
             const int nvq = h->dpad / 256;
             const bool nv_ok = h->dpad % 256 == 0 && (nvq == 1 || nvq == 2 || nvq == 3 || nvq == 4 || nvq == 6 || nvq == 8 || nvq == 12);
             const bool split_traverse = nv_ok && N > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024 &&
-                                        !(getenv("MORNA_QUERY_SPLIT_TRAVERSE") && atoi(getenv("MORNA_QUERY_SPLIT_TRAVERSE")) == 0);
+                                        env_on("MORNA_QUERY_SPLIT_TRAVERSE");
             if (split_traverse) {
                 const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((h->n_trees + QR_TREES - 1) / QR_TREES));
                 const size_t ql = (size_t)QR_Q * h->dpad * 4;
@@ -1274,25 +1278,14 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         }
         if (direct) {
             HIP_TRY(hipStreamSynchronize(h->stream));
-            memcpy(ids_out + q0 * k, h->host_small, (size_t)nb * k * 4);
-            if (dist_out) memcpy(dist_out + q0 * k, h->host_small + s_ids, (size_t)nb * k * 4);
-            if (count_out) memcpy(count_out + q0, h->host_small + 2 * s_ids, (size_t)nb * 4);
+            memcpy(ids_out + q0 * k, h->host_small.p, (size_t)nb * k * 4);
+            if (dist_out) memcpy(dist_out + q0 * k, h->host_small.p + s_ids, (size_t)nb * k * 4);
+            if (count_out) memcpy(count_out + q0, h->host_small.p + 2 * s_ids, (size_t)nb * 4);
         } else if (ids_out) {
             // one copy of the whole result block into page-locked memory of the handle (three copies into the caller's
             // pageable arrays cost ~25 us of idle device each), then plain memcpys
-            const size_t out_bytes = 2 * s_ids + s_qf;
-            if (out_bytes > h->host_out_cap) {
-                if (h->host_out) (void)hipHostFree(h->host_out);
-                h->host_out = nullptr;
-                h->host_out_cap = 0;
-                HIP_TRY(hipHostMalloc((void **)&h->host_out, out_bytes * 2, hipHostMallocDefault));
-                h->host_out_cap = out_bytes * 2;
-            }
-            HIP_TRY(hipMemcpyAsync(h->host_out, out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            memcpy(ids_out + q0 * k, h->host_out, (size_t)nb * k * 4);
-            if (dist_out) memcpy(dist_out + q0 * k, h->host_out + s_ids, (size_t)nb * k * 4);
-            if (count_out) memcpy(count_out + q0, h->host_out + 2 * s_ids, (size_t)nb * 4);
+            MORNA_TRY(fetch_results(h, out_block, 2 * s_ids + s_qf, s_ids, s_ids, 4, nb, k, ids_out + q0 * k,
+                                    dist_out ? dist_out + q0 * k : nullptr, count_out ? count_out + q0 : nullptr));
         }
         // (packed answers only: nothing to wait for -- the next batch, and whatever the caller orders on the handle's
         // stream, run behind this one)
@@ -1359,20 +1352,7 @@ int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, i
                        k, d_ids, d_dist, d_cnt);
     HIP_TRY(hipGetLastError());
     // one copy of the result block into the handle's page-locked staging, then plain memcpys (as query_batch)
-    const size_t out_bytes = 2 * s_ids + s_cnt;
-    if (out_bytes > h->host_out_cap) {
-        if (h->host_out) (void)hipHostFree(h->host_out);
-        h->host_out = nullptr;
-        h->host_out_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&h->host_out, out_bytes * 2, hipHostMallocDefault));
-        h->host_out_cap = out_bytes * 2;
-    }
-    HIP_TRY(hipMemcpyAsync(h->host_out, d_ids, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    memcpy(ids_out, h->host_out, (size_t)nq * k * 4);
-    if (dist_out) memcpy(dist_out, h->host_out + s_ids, (size_t)nq * k * 4);
-    if (count_out) memcpy(count_out, h->host_out + 2 * s_ids, (size_t)nq * 4);
-    return MORNA_OK;
+    return fetch_results(h, h->ws.p, 2 * s_ids + s_cnt, s_ids, s_ids, 4, nq, k, ids_out, dist_out, count_out);
 }
 
 // =============================================================== exact search
@@ -1924,7 +1904,7 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
         HIP_TRY(hipGetLastError());
         const float eps = exact_scan_eps(dpad, nb >= 32);   // which scan ran
         ScopedTimer tm_sel(h, MORNA_T_EXACT, 0);            // selection + fp64 re-rank: the same group as the scan
-        const bool select2_on = !(getenv("MORNA_EXACT_SELECT2") && atoi(getenv("MORNA_EXACT_SELECT2")) == 0);   // (read per call: a test switches it)
+        const bool select2_on = env_on("MORNA_EXACT_SELECT2");   // (read per call: a test switches it)
         for (;;) {
             MORNA_TRY(h->ex_cand.alloc((size_t)batch * cap));
             MORNA_TRY(h->ex_cdist.alloc((size_t)batch * cap));
@@ -1953,21 +1933,9 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
             HIP_TRY(hipGetLastError());
             h->unsettled = true;
         }
-        if (ids_out) {
-            const size_t out_bytes = s_ids + s_dist + s_b4;
-            if (out_bytes > h->host_out_cap) {
-                if (h->host_out) (void)hipHostFree(h->host_out);
-                h->host_out = nullptr;
-                h->host_out_cap = 0;
-                HIP_TRY(hipHostMalloc((void **)&h->host_out, out_bytes * 2, hipHostMallocDefault));
-                h->host_out_cap = out_bytes * 2;
-            }
-            HIP_TRY(hipMemcpyAsync(h->host_out, out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            memcpy(ids_out + q0 * k, h->host_out, (size_t)nb * k * 4);
-            if (dist_out) memcpy(dist_out + q0 * k, h->host_out + s_ids, (size_t)nb * k * 8);
-            if (count_out) memcpy(count_out + q0, h->host_out + s_ids + s_dist, (size_t)nb * 4);
-        }
+        if (ids_out)
+            MORNA_TRY(fetch_results(h, out_block, s_ids + s_dist + s_b4, s_ids, s_dist, 8, nb, k, ids_out + q0 * k,
+                                    dist_out ? dist_out + q0 * k : nullptr, count_out ? count_out + q0 : nullptr));
     }
     h->ex_cap = need_max;   // the next call starts with the room this one needed (no more: one query with a tie of thousands
                             // does not size every later call)

@@ -510,14 +510,14 @@ __global__ __launch_bounds__(256) void order_inv_kernel(const int32_t *__restric
     inv[t * n_items + rank[item]] = inv_by_item[i];
 }
 
-// scratch slots 30..32: [rank | item_at], inv by row, the counting sort's table (+ keys).  The fp16 rows stay where they are:
+// h->splitmm.maps / invr / table: [rank | item_at], inv by row, the counting sort's table (+ keys).  The fp16 rows stay where they are:
 // a lane of the contraction fetches its row's address through item_at once (a copy of the image in row order cost 0.17 ms
 // of HBM time beside the second level's two_means).  Enqueued on `stream` (the side stream, under that two_means).
 int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_by_item, int32_t n_trees, hipStream_t stream,
                         const int32_t **rank_out, int32_t **inv_out)
 {
     const int64_t N = h->n_items;
-    ScratchRef<int32_t> maps(h->scratch[30]), invr(h->scratch[31]), table(h->scratch[32]);
+    DevBuf<int32_t> &maps = h->splitmm.maps, &invr = h->splitmm.invr, &table = h->splitmm.table;
     const int32_t n_blocks = (int32_t)((N + ORD_BLOCK - 1) / ORD_BLOCK);
     MORNA_TRY(maps.alloc((size_t)N * 2));
     MORNA_TRY(invr.alloc((size_t)n_trees * N));
@@ -535,25 +535,24 @@ int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_
     const int64_t total = (int64_t)n_trees * N;
     hipLaunchKernelGGL(order_inv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, inv_by_item, rank, N, total, invr.p);
     HIP_TRY(hipGetLastError());
-    h->ord_valid = true;
+    h->splitmm.ord_valid = true;
     *rank_out = rank;
     *inv_out = invr.p;
     return MORNA_OK;
 }
 
-// scratch slots 19..23 of the handle: fp16 rows, their norms, fp16 hyperplanes of the level, their norms,
-// the open-pair list (first 16 bytes: its counter)
+// h->half: the fp16 rows, their norms and scales, made once per set of rows
 int split_mm_prepare_rows(morna_index *h, hipStream_t stream)
 {
-    if (h->half_valid) return MORNA_OK;
-    ScratchRef<_Float16> x16(h->scratch[19]);
-    ScratchRef<float> xn(h->scratch[20]);   // [0, N): norms; [N, 2N): 2^-e per row (the query filter unscales with it); [2N, 3N): |s x - y|
+    if (h->half.valid) return MORNA_OK;
+    DevBuf<_Float16> &x16 = h->half.x16;
+    DevBuf<float> &xn = h->half.xn;
     MORNA_TRY(x16.alloc((size_t)h->n_items * h->dpad));
     MORNA_TRY(xn.alloc((size_t)h->n_items * 3));
     hipLaunchKernelGGL(rows_to_half_kernel, dim3((unsigned)((h->n_items + 3) / 4)), dim3(256), 0, stream, h->X.p,
                        h->n_items, h->dpad, x16.p, xn.p, xn.p + 2 * h->n_items, xn.p + h->n_items, (unsigned int *)nullptr);
     HIP_TRY(hipGetLastError());
-    h->half_valid = true;
+    h->half.valid = true;
     return MORNA_OK;
 }
 
@@ -574,15 +573,14 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
                    const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones)
 {
     const int64_t N = h->n_items;
-    ScratchRef<_Float16> x16(h->scratch[19]), h16(h->scratch[21]);
-    ScratchRef<float> xn(h->scratch[20]), hn(h->scratch[22]);
-    ScratchRef<int32_t> maps(h->scratch[30]);
-    ScratchRef<uint8_t> ambuf(h->scratch[23]);
+    DevBuf<_Float16> &h16 = h->splitmm.h16;
+    DevBuf<float> &hn = h->splitmm.hn;
+    DevBuf<uint8_t> &ambuf = h->splitmm.amb;
     // the rows of the contraction: the items in id order, or in the order split_mm_order_rows made (`inv` is then by row too)
-    const bool ord = h->ord_valid;
-    const _Float16 *rows16 = x16.p;
-    const float *rows_n = xn.p, *rows_e = xn.p + 2 * N;
-    const int32_t *rank = ord ? maps.p : nullptr, *item_at = ord ? maps.p + N : nullptr;
+    const bool ord = h->splitmm.ord_valid;
+    const _Float16 *rows16 = h->half.x16.p;
+    const float *rows_n = h->half.xn.p, *rows_e = h->half.xn.p + 2 * N;
+    const int32_t *rank = ord ? h->splitmm.maps.p : nullptr, *item_at = ord ? h->splitmm.maps.p + N : nullptr;
     const size_t cap = (size_t)N * h->n_trees;   // a row is in at most one split node per tree
     if (cap > 0xFFFFFFF0u) {
         set_error("split_mm_level: %lld x %d (row, tree) pairs exceed the open-pair list", (long long)N, h->n_trees);
@@ -598,15 +596,15 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
                        (int64_t)n_slots, h->dpad, h16.p, hn.p, hn.p + n_slots, (float *)nullptr, amb_count);
     // 256 x 256 tiles once the level has hyperplane tiles enough for them to fill the chip in even rounds (MORNA_SPLIT_BIG=0:
     // the 128 x 128 form everywhere)
-    static const bool big_on = !(getenv("MORNA_SPLIT_BIG") && atoi(getenv("MORNA_SPLIT_BIG")) == 0);
+    static const bool big_on = env_on("MORNA_SPLIT_BIG");
     // the tasks each row tile needs, from the second level of a tree on (MORNA_SPLIT_LISTS=0: every tile x every task)
-    static const bool lists_on = !(getenv("MORNA_SPLIT_LISTS") && atoi(getenv("MORNA_SPLIT_LISTS")) == 0);
+    static const bool lists_on = env_on("MORNA_SPLIT_LISTS");
     if (big_on && (n_tasks >= 1024 || (ord && lists_on && n_tasks >= 512))) {
         const unsigned n_rt = (unsigned)((N + 255) / 256), n_ct = (unsigned)((n_tasks + 255) / 256);
         const int32_t *col_list = nullptr, *col_count = nullptr, *col_first = nullptr;
         if (lists_on) {
-            ScratchRef<uint8_t> active(h->scratch[27]);
-            ScratchRef<int32_t> lists(h->scratch[28]);
+            DevBuf<uint8_t> &active = h->splitmm.active;
+            DevBuf<int32_t> &lists = h->splitmm.lists;
             MORNA_TRY(active.alloc((size_t)n_rt * n_tasks));
             MORNA_TRY(lists.alloc((size_t)n_rt * n_tasks + 2 * n_rt + 1));
             HIP_TRY(hipMemsetAsync(active.p, 0, (size_t)n_rt * n_tasks, h->stream));

@@ -271,8 +271,8 @@ def _compare_forest(a, o, N, T):
 
 @pytest.mark.parametrize("f,N,T", [(16, 3000, 8), (40, 5000, 5), (300, 4000, 3),
                                    (1000, 3000, 3), (2000, 4500, 2),   # 4 and 8 float4 per lane: four-wave two_means
-                                   (3000, 8000, 11),    # the bench's row width: register two_means + row-window split,
-                                                        # 11 trees = one full and one partial tree group
+                                   (3000, 8000, 11),    # the bench's row width: register two_means, matrix-core and chunk splits,
+                                                        # 11 trees (an odd count)
                                    (5000, 6000, 2),     # 20 float4 per lane: strip two_means only (too long for one wave)
                                    (8192, 9000, 2)])    # config 5's width: strip two_means with 32 float4 per lane
 def test_forest_bit_exact_vs_oracle_wave_order(capi, f, N, T):

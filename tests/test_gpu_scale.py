@@ -221,7 +221,7 @@ def test_filters_do_not_change_results(tmp_path):
     """The fp16 MFMA split filter + exact fallback (splitmm.hip) must write exactly the sides of the plain fp32
     kernels, and the fp16 candidate filter of the approximate search must return exactly what the all-fp32
     search returns; likewise the four-wave strip form of two_means and the one-wave form: the same seeded build
-    and searches in four processes -- defaults, MORNA_SPLIT_MM=0 (row-window / chunk forms), MORNA_QUERY_FILTER=0,
+    and searches in four processes -- defaults, MORNA_SPLIT_MM=0 (chunk form at every level), MORNA_QUERY_FILTER=0,
     MORNA_TM_STRIP=0 -- on rows spanning six orders of magnitude in norm, a zero
     row, duplicates, near-duplicates in the 4th digit, exact scaled duplicates, a row of denormal scale and a row
     holding an infinity."""
