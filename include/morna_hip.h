@@ -149,9 +149,10 @@ int morna_get_norms2(morna_index *h, float *out /* [n] */);
 /* ---- forest -------------------------------------------------------------- */
 
 /* AnnoyIndex.build(n_trees); seed 0 selects annoy's default 123456789   morna.py:425
- * Limit that annoy does not have: the build keeps a hyperplane and a row in registers / LDS and rejects dimensions whose
- * padded row (dim rounded up to 256 floats) exceeds 8192 floats (MORNA_E_INVALID).  BASELINE's configurations use 3000
- * and 8192. */
+ * Limit that annoy does not have: two_means keeps one centroid on chip (LDS), so the build, the approximate and the
+ * exact searches reject dimensions whose padded row (dim rounded up to 256 floats) exceeds 32768 floats
+ * (MORNA_E_INVALID, the message names the limit).  Rows past 8192 floats take the wide two_means form.  BASELINE's
+ * configurations use 3000 and 8192. */
 int morna_build(morna_index *h, int32_t n_trees, uint32_t seed);
 int32_t morna_get_n_trees(const morna_index *h);
 
@@ -301,7 +302,8 @@ enum {
     MORNA_T_QUERY_FILTER = 6, /* part of MORNA_T_QUERY: the whole-batch fp16 contraction (bytes = its flops) */
     MORNA_T_EXACT_SCAN = 7, /* part of MORNA_T_EXACT: the fp32 scan (bytes = its flops when it ran on the matrix cores) */
     MORNA_T_SPLIT_MM = 8,   /* part of MORNA_T_SPLIT: the fp16 contraction alone (bytes = the flops of the tiles it LAUNCHED) */
-    MORNA_T_TM_STRIP = 9,   /* part of MORNA_T_TWO_MEANS: levels run by two_means_strip_kernel (four waves per node) */
+    MORNA_T_TM_STRIP = 9,   /* part of MORNA_T_TWO_MEANS: levels run by two_means_strip_kernel (four waves per node), and
+                               by two_means_wide_kernel (the same strips, rows past 8192 floats) */
     MORNA_T_TM_WAVE = 10,   /* part of MORNA_T_TWO_MEANS: levels run by two_means_wave_kernel (one wave per node) */
     MORNA_T_COUNT = 11
 };

@@ -16,7 +16,8 @@
 //                     four waves per node, each owning 16 of the 64 canonical lanes of every
 //                     dot product and that strip of the centroids, for levels whose nodes
 //                     fit the chip at once.  two_means_kernel: the LDS form (one workgroup
-//                     per node) for rows too long for the register file.
+//                     per node) for rows too long for the register file.  two_means_wide_kernel:
+//                     rows past 8192 floats (up to 32768), p in registers, q in LDS, rows streamed.
 //   (splitmm.hip)     the sides of the whole level as one fp16 MFMA product that filters,
 //                     exact fp32 dots for the pairs it cannot decide -- the form that runs
 //                     while a tree has at most 32 split nodes, and, once the rows of the
@@ -556,6 +557,294 @@ __global__ __launch_bounds__(256) void two_means_strip_kernel(const float *__res
     }
 }
 
+// ---- two_means for wide rows, 8192 < dpad <= 32768 ----------------------------------------------
+// The strip layout of two_means_strip_kernel (lane l of wave w owns element 64 w + l of every 256-float k-step,
+// chain (l & 3) of canonical lane 16 w + (l >> 2)), one workgroup per node, for rows whose strips no longer fit
+// the register file three times over.  Of the nk = dpad / 256 k-steps of a lane, the first 4 * nf (nf = nk / 4
+// groups of four, at most NG) are held as float4: centroid p in registers (128 floats per lane at 32768),
+// centroid q in LDS, the lane's own slots only, so it needs no barrier.  The last nk % 4 k-steps of both
+// centroids are LDS slots as well.  Rows are not kept: step l reads row l (the update) and row l+1 (the dots of
+// the next step) strip by strip from HBM / L2 in one pass over the k-steps, so every chain still runs in k order.
+// Same operations on the same values as two_means_strip_kernel and wave_dot, bit for bit.
+// LDS: (4 nf + 2 (nk % 4)) x 1 KiB, 128 KiB at 32768.
+#define TMW_MAX_DPAD 32768
+template <int NG>
+__global__ __launch_bounds__(256) void two_means_wide_kernel(const float *__restrict__ X, const RowInfo *__restrict__ rowinfo,
+                                                           int64_t n_items, int32_t dpad,
+                                                           const int32_t *__restrict__ perm,
+                                                           const SplitTask *__restrict__ tasks, uint32_t seed,
+                                                           float *__restrict__ hp, int32_t *__restrict__ ones)
+{
+    // the launch picks the smallest NG of 12, 16, 24, 32 that holds nf: groups below the next smaller one always exist
+    constexpr int NGLO = NG <= 12 ? 8 : NG <= 16 ? 12 : NG <= 24 ? 16 : 24;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ float ex[2][3][WAVE];
+    if (threadIdx.x == 0) ones[blockIdx.x] = 0;   // the split kernels that follow count this task's right side here
+
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int L = 16 * w + (lane >> 2);
+    const int nk = dpad / 256, nf = nk / 4, nt = nk % 4;   // k-steps, full groups, k-steps of the tail
+    // group g of q at QS(g) (an LDS instruction's offset reaches 64 KiB: groups 16 and up from a second base)
+    float4 *qs = (float4 *)smem + threadIdx.x, *qs_hi = qs + 256 * 16;
+    asm volatile("" : "+v"(qs_hi));
+#define QS(g) ((g) < 16 ? qs : qs_hi)[256 * ((g) & 15)]
+    float *pt = (float *)((float4 *)smem + 256 * nf) + threadIdx.x;   // tail k-step c of p at pt[256 c]
+    float *qt = pt + 256 * nt;                                       // ... and of q
+    const SplitTask t = tasks[blockIdx.x];
+    const int32_t *items = perm + TASK_ITEMS_AT(t, n_items);
+    Kiss32 rng(node_seed(seed, (uint32_t)t.tree, (uint32_t)t.level, (uint32_t)t.start, (uint32_t)t.attempt));
+    const float *Xs = X + 64 * w + lane;
+
+    // the next four k-steps of a row's strip, and the cursor moved past them.  The cursor is stepped in the loop
+    // (opaque to the compiler): hoisted, the offsets of every group of two rows would crowd the registers.
+    auto next4 = [](const float *&r) {
+        const float4 v = make_float4(r[0], r[256], r[512], r[768]);
+        r += 1024;
+        asm volatile("" : "+v"(r));
+        return v;
+    };
+    auto next1 = [](const float *&r) {
+        const float v = r[0];
+        r += 256;
+        return v;
+    };
+    auto chain4 = [](float acc, const float4 a, const float4 b) {
+        acc = fmaf(a.x, b.x, acc);
+        acc = fmaf(a.y, b.y, acc);
+        acc = fmaf(a.z, b.z, acc);
+        acc = fmaf(a.w, b.w, acc);
+        return acc;
+    };
+    int xpar = 0;
+    auto exchange3 = [&](float a, float b, float c) {   // as in two_means_strip_kernel
+        a = a + dpp_move<0xB1>(a);
+        b = b + dpp_move<0xB1>(b);
+        c = c + dpp_move<0xB1>(c);
+        a = a + dpp_move<0x4E>(a);
+        b = b + dpp_move<0x4E>(b);
+        c = c + dpp_move<0x4E>(c);
+        if ((lane & 3) == 0) {
+            ex[xpar][0][L] = a;
+            ex[xpar][1][L] = b;
+            ex[xpar][2][L] = c;
+        }
+        __syncthreads();
+        const float f[3] = {ex[xpar][0][lane], ex[xpar][1][lane], ex[xpar][2][lane]};
+        xpar ^= 1;
+        return wave_sum_multi<3>(f, lane);
+    };
+    auto lane_value = [](float u, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), l)); };
+    auto step1 = [](float c, float x, float f0, float f1, float norm, double r1, float y, unsigned long long force) {
+        return centroid_step4(make_float4(c, 0.f, 0.f, 0.f), make_float4(x, 0.f, 0.f, 0.f), f0, f1, norm, r1, y, force).x;
+    };
+
+    uint32_t i = rng.index((uint32_t)t.count);
+    uint32_t j = rng.index((uint32_t)t.count - 1u);
+    j += (j >= i);
+    float4 p[NG];
+    float pp, qq;
+    {
+        const float *ri_ = Xs + (int64_t)items[i] * dpad, *rj_ = Xs + (int64_t)items[j] * dpad;   // cursors
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+            if (g < NGLO || g < nf) {
+                p[g] = next4(ri_);
+                const float4 qg = next4(rj_);
+                QS(g) = qg;
+                a = chain4(a, p[g], p[g]);
+                b = chain4(b, qg, qg);
+            } else {
+                p[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        for (int c = 0; c < nt; c++) {
+            const float pc = next1(ri_), qc = next1(rj_);
+            pt[256 * c] = pc;
+            qt[256 * c] = qc;
+            a = fmaf(pc, pc, a);
+            b = fmaf(qc, qc, b);
+        }
+        const float u = exchange3(a, b, 0.f);
+        const float np = sqrtf(lane_value(u, 0)), nq = sqrtf(lane_value(u, 16));
+        a = 0.f;
+        b = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+            if (g < NGLO || g < nf) {
+                if (np > 0.f) EW4(p[g], p[g].x / np, p[g].y / np, p[g].z / np, p[g].w / np);
+                float4 qg = QS(g);
+                if (nq > 0.f) EW4(qg, qg.x / nq, qg.y / nq, qg.z / nq, qg.w / nq);
+                QS(g) = qg;
+                a = chain4(a, p[g], p[g]);
+                b = chain4(b, qg, qg);
+            }
+        }
+        for (int c = 0; c < nt; c++) {
+            float pc = pt[256 * c], qc = qt[256 * c];
+            if (np > 0.f) pc = pc / np;
+            if (nq > 0.f) qc = qc / nq;
+            pt[256 * c] = pc;
+            qt[256 * c] = qc;
+            a = fmaf(pc, pc, a);
+            b = fmaf(qc, qc, b);
+        }
+        const float v = exchange3(a, b, 0.f);
+        pp = lane_value(v, 0);
+        qq = lane_value(v, 16);
+    }
+
+    // row 0 and the dots of step 0
+    int32_t it_cur = items[rng.index((uint32_t)t.count)];
+    RowInfo ri_cur = rowinfo[it_cur];
+    float u;
+    {
+        const float *r = Xs + (int64_t)it_cur * dpad;   // cursor
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+            if (g < NGLO || g < nf) {
+                const float4 x = next4(r);
+                a = chain4(a, p[g], x);
+                b = chain4(b, QS(g), x);
+            }
+        }
+        for (int c = 0; c < nt; c++) {
+            const float x = next1(r);
+            a = fmaf(pt[256 * c], x, a);
+            b = fmaf(qt[256 * c], x, b);
+        }
+        u = exchange3(a, b, 0.f);
+    }
+    int ic = 1, jc = 1;
+    float r2p = tm_recip(2), r2q = tm_recip(2);   // RN32 of 1 / (ic + 1), 1 / (jc + 1)
+    int upd_prev = 0;
+    for (int l = 0; l < TM_ITERS; l++) {
+        // the row of the next step (past step 199 a row nobody uses: the stream has more draws, every index is valid)
+        const int32_t it_nxt = vgather(items, rng.index((uint32_t)t.count));
+        const RowInfo ri_nxt = vgather(rowinfo, (uint32_t)it_nxt);
+        // ---- decide (every wave: same values, same decision)
+        if (upd_prev == 1) pp = lane_value(u, 32);
+        if (upd_prev == 2) qq = lane_value(u, 32);
+        const float nk2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ri_cur.norm2)));
+        const int norm_bits = __builtin_amdgcn_readfirstlane(__float_as_int(ri_cur.norm));
+        const long long r1_bits = ((long long)__builtin_amdgcn_readfirstlane((int)(__double_as_longlong(ri_cur.rnorm) >> 32)) << 32) |
+                                  (unsigned)__builtin_amdgcn_readfirstlane((int)__double_as_longlong(ri_cur.rnorm));
+        const float di = (float)ic * ang_dist(pp, nk2, lane_value(u, 0));
+        const float dj = (float)jc * ang_dist(qq, nk2, lane_value(u, 16));
+        const float norm = __int_as_float(norm_bits & 0x7fffffff);   // sqrtf(nk2)
+        const unsigned long long force = norm_bits < 0 ? ~0ull : 0ull;
+        const double r1 = __longlong_as_double(r1_bits);
+        int upd = 0;
+        if (norm > 0.f) upd = di < dj ? 1 : (dj < di ? 2 : 0);
+
+        // ---- one pass over the k-steps: the update of step l with row l, then the chains of the new self-dot and of
+        // the dots of step l+1 with the updated centroids
+        const float *rc = Xs + (int64_t)__builtin_amdgcn_readfirstlane(it_cur) * dpad;   // cursors
+        const float *rn = Xs + (int64_t)__builtin_amdgcn_readfirstlane(it_nxt) * dpad;
+        float a = 0.f, b = 0.f, cc = 0.f;
+        if (upd == 1) {
+            const float f0 = (float)ic, f1 = (float)(ic + 1);
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                if (g < NGLO || g < nf) {
+                    const float4 xc = next4(rc), xn = next4(rn);
+                    p[g] = centroid_step4(p[g], xc, f0, f1, norm, r1, r2p, force);
+                    cc = chain4(cc, p[g], p[g]);
+                    a = chain4(a, p[g], xn);
+                    b = chain4(b, QS(g), xn);
+                }
+            }
+            for (int c = 0; c < nt; c++) {
+                const float xc = next1(rc), xn = next1(rn);
+                const float pc = step1(pt[256 * c], xc, f0, f1, norm, r1, r2p, force);
+                pt[256 * c] = pc;
+                cc = fmaf(pc, pc, cc);
+                a = fmaf(pc, xn, a);
+                b = fmaf(qt[256 * c], xn, b);
+            }
+            ic++;
+            r2p = tm_recip(ic + 1);
+        } else if (upd == 2) {
+            const float f0 = (float)jc, f1 = (float)(jc + 1);
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                if (g < NGLO || g < nf) {
+                    const float4 xc = next4(rc), xn = next4(rn);
+                    const float4 qg = centroid_step4(QS(g), xc, f0, f1, norm, r1, r2q, force);
+                    QS(g) = qg;
+                    cc = chain4(cc, qg, qg);
+                    a = chain4(a, p[g], xn);
+                    b = chain4(b, qg, xn);
+                }
+            }
+            for (int c = 0; c < nt; c++) {
+                const float xc = next1(rc), xn = next1(rn);
+                const float qc = step1(qt[256 * c], xc, f0, f1, norm, r1, r2q, force);
+                qt[256 * c] = qc;
+                cc = fmaf(qc, qc, cc);
+                a = fmaf(pt[256 * c], xn, a);
+                b = fmaf(qc, xn, b);
+            }
+            jc++;
+            r2q = tm_recip(jc + 1);
+        } else {
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                if (g < NGLO || g < nf) {
+                    const float4 xn = next4(rn);
+                    a = chain4(a, p[g], xn);
+                    b = chain4(b, QS(g), xn);
+                }
+            }
+            for (int c = 0; c < nt; c++) {
+                const float xn = next1(rn);
+                a = fmaf(pt[256 * c], xn, a);
+                b = fmaf(qt[256 * c], xn, b);
+            }
+        }
+        upd_prev = upd;
+        u = exchange3(a, b, cc);
+        it_cur = it_nxt;
+        ri_cur = ri_nxt;
+    }
+    // create_split: n = normalize(p - q)
+    float a = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        if (g < NGLO || g < nf) {
+            const float4 qg = QS(g);
+            EW4(p[g], p[g].x - qg.x, p[g].y - qg.y, p[g].z - qg.z, p[g].w - qg.w);
+            a = chain4(a, p[g], p[g]);
+        }
+    }
+    for (int c = 0; c < nt; c++) {
+        const float d = pt[256 * c] - qt[256 * c];
+        pt[256 * c] = d;
+        a = fmaf(d, d, a);
+    }
+    const float nn = sqrtf(lane_value(exchange3(a, 0.f, 0.f), 0));
+    float *out = hp + (int64_t)t.slot * dpad + 64 * w + lane;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        if (g < NGLO || g < nf) {
+            if (nn > 0.f) EW4(p[g], p[g].x / nn, p[g].y / nn, p[g].z / nn, p[g].w / nn);
+            out[(4 * g) * 256] = p[g].x;
+            out[(4 * g + 1) * 256] = p[g].y;
+            out[(4 * g + 2) * 256] = p[g].z;
+            out[(4 * g + 3) * 256] = p[g].w;
+        }
+    }
+    for (int c = 0; c < nt; c++) {
+        float d = pt[256 * c];
+        if (nn > 0.f) d = d / nn;
+        out[(4 * nf + c) * 256] = d;
+    }
+}
+// dynamic LDS of two_means_wide_kernel
+#undef QS
+static inline size_t tm_wide_lds(int32_t dpad) { return (size_t)((dpad / 256) / 4 * 4 + 2 * ((dpad / 256) % 4)) * 256 * 4; }
+
 // ---------------------------------------------------------------- split kernel
 
 #define SP_THREADS 256
@@ -898,8 +1187,8 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
     if (seed == 0) seed = 123456789u;   // Kiss32Random's default seed
     const int64_t N = h->n_items;
     const int32_t dpad = h->dpad, K = h->K, D = h->dim;
-    if (dpad > 8192) {   // two_means prefetches a row in 8 float4 per thread; 3 rows of LDS
-        set_error("build: dimension %d is above the supported 8192", D);
+    if (dpad > TMW_MAX_DPAD) {   // two_means_wide_kernel keeps one centroid in LDS: 128 KiB at 32768
+        set_error("build: dimension %d is above the supported %d", D, TMW_MAX_DPAD);
         return MORNA_E_INVALID;
     }
     h->built = false;
@@ -1187,11 +1476,26 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 static const bool tm_strip_on = env_on("MORNA_TM_STRIP");
                 const bool tm_strip = tm_strip_on && A <= 2 * h->n_cus;
                 const bool strip_runs = tm_strip && (nvq == 12 || nvq == 8 || nvq == 4 || (nvq >= 16 && nvq <= 32 && nvq % 4 == 0));
-                ScopedTimer tk(h, strip_runs ? MORNA_T_TM_STRIP : MORNA_T_TM_WAVE, 4 * (int64_t)D * (TM_ITERS + 2) * A);   // per kernel, beside the group
+                // per kernel, beside the group; the wide form (dpad > 8192: strips, four waves per node) counts as strips
+                ScopedTimer tk(h, strip_runs || dpad > 8192 ? MORNA_T_TM_STRIP : MORNA_T_TM_WAVE, 4 * (int64_t)D * (TM_ITERS + 2) * A);
 #define TMS_LAUNCH(NVV)                                                                                                 \
     hipLaunchKernelGGL((two_means_strip_kernel<NVV, TM_STRIP_DEPTH>), dim3((unsigned)A), dim3(256), 0, h->stream, h->X.p, \
                        h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p)
-                if (tm_strip && nvq == 12) TMS_LAUNCH(12);
+#define TMX_LAUNCH(NGV)                                                                                                   \
+    do {                                                                                                                  \
+        F_TRY(hipFuncSetAttribute((const void *)two_means_wide_kernel<NGV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)tm_wide_lds(dpad)));                                                             \
+        hipLaunchKernelGGL(two_means_wide_kernel<NGV>, dim3((unsigned)A), dim3(256), tm_wide_lds(dpad), h->stream,       \
+                           h->X.p, h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p);                    \
+    } while (0)
+                // rows past 8192 floats: the wide form at every level, whatever the switches (one centroid in LDS)
+                if (dpad > 8192) {
+                    const int ngw = dpad / 256 / 4;   // full groups of four k-steps
+                    if (ngw <= 12) TMX_LAUNCH(12);
+                    else if (ngw <= 16) TMX_LAUNCH(16);
+                    else if (ngw <= 24) TMX_LAUNCH(24);
+                    else TMX_LAUNCH(32);
+                } else if (tm_strip && nvq == 12) TMS_LAUNCH(12);
                 else if (tm_strip && nvq == 8) TMS_LAUNCH(8);
                 else if (tm_strip && nvq == 4) TMS_LAUNCH(4);
                 else if (tm_strip && nvq == 16) TMS_LAUNCH(16);   // rows too long for the one-wave register form: strips
@@ -1211,6 +1515,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                                        h->X.p, h->norm2.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p);
 #undef TMW_LAUNCH
 #undef TMS_LAUNCH
+#undef TMX_LAUNCH
             }
             if (!use_mm) {
                 // chunk form: launch order = chunks sorted by first row id, one contiguous run per XCD
@@ -1234,6 +1539,8 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 // algorithmic bytes: 4*D*sum|node| + 4*D*#split nodes
                 ScopedTimer tm(h, MORNA_T_SPLIT, 4 * (int64_t)D * (rows + A));
                 const unsigned grid = 8u * (unsigned)((n_chunks + 7) / 8);
+                if (dpad > 8192)   // the hyperplane in LDS: up to 128 KiB
+                    F_TRY(hipFuncSetAttribute((const void *)split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dpad * 4));
                 hipLaunchKernelGGL(split_kernel, dim3(grid), dim3(SP_THREADS), (size_t)dpad * 4, h->stream, h->X.p, N, dpad,
                                    work.p, d_tasks.p, d_sched.p, n_chunks, seed, hp_level, side.p, d_ones.p);
             }

@@ -23,6 +23,8 @@ namespace morna {
 
 #define Q_THREADS 256
 #define Q_WAVES (Q_THREADS / WAVE)
+#define Q_MAX_DPAD 32768            // widest row the searches take (the build's limit too)
+#define Q_LDS_MAX (152 * 1024)      // dynamic LDS a query kernel may ask for: 160 KiB less its static arrays
 
 struct QueryParams {
     const float *X;
@@ -979,6 +981,10 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         set_error("get_nns: n must be positive");
         return MORNA_E_INVALID;
     }
+    if (h->dpad > Q_MAX_DPAD) {   // the query image and the traversal's LDS (an index built elsewhere, loaded here)
+        set_error("get_nns: dimension %d is above the supported %d", h->dim, Q_MAX_DPAD);
+        return MORNA_E_INVALID;
+    }
     if (nq == 0) return MORNA_OK;
     if (search_k == -1) search_k = (int32_t)std::min<int64_t>((int64_t)k * h->n_trees, INT32_MAX);
     if (items_host)
@@ -992,8 +998,10 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
     const int64_t cap64 = std::min<int64_t>(N, (int64_t)std::max(search_k, 0) + h->K);
     const int32_t cap = (int32_t)std::max<int64_t>(cap64, 1);
     const int32_t bm_words = (int32_t)((N + 31) / 32);
-    const bool bm_lds = (size_t)bm_words * 4 <= 64 * 1024;
     const size_t lds_q = (size_t)h->dpad * sizeof(float);
+    // the sample bitmap goes to LDS when it is at most 64 KiB and fits beside the query image (always, up to dpad 8192;
+    // past it the 160 KiB of LDS decide, and the global bitmap takes over)
+    const bool bm_lds = (size_t)bm_words * 4 <= 64 * 1024 && lds_q + (size_t)bm_words * 4 <= Q_LDS_MAX;
     const size_t lds = lds_q + (bm_lds ? (size_t)bm_words * 4 : 0);
 
     // candidate filter on the fp16 rows (MORNA_QUERY_FILTER=0: every candidate gets the fp32 dot); pays when a
@@ -1251,6 +1259,9 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL(query_traverse_kernel<true>, dim3((unsigned)nb), dim3(Q_THREADS), lds, ts, P);
             } else {
+                if (lds_q > 48 * 1024)   // the query image alone: up to 128 KiB past dpad 12288
+                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_kernel<false>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
                 hipLaunchKernelGGL(query_traverse_kernel<false>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, ts, P);
             }
             if (dense) {
@@ -1812,11 +1823,15 @@ static float exact_scan_eps(int32_t dpad, bool mfma)
 }
 
 template <int QT>
-static void launch_exact_scan(morna_index *h, int64_t N, int64_t nb, const float *Qf, const float *qn2, float *approx)
+static int launch_exact_scan(morna_index *h, int64_t N, int64_t nb, const float *Qf, const float *qn2, float *approx)
 {
     dim3 grid((unsigned)((N + E_ROWS - 1) / E_ROWS), (unsigned)((nb + QT - 1) / QT));
+    if ((size_t)QT * h->dpad * 4 > 64 * 1024)   // one query image past 16384 floats
+        HIP_TRY(hipFuncSetAttribute((const void *)exact_scan_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)QT * h->dpad * 4)));
     hipLaunchKernelGGL(exact_scan_kernel<QT>, grid, dim3(256), (size_t)QT * h->dpad * 4, h->stream, h->X.p,
                        h->norm2.p, N, h->dpad, Qf, qn2, nb, approx);
+    return MORNA_OK;
 }
 
 // Message of the row-sharded exact search, nq queries: ids int32 [nq][k] (global, -1 = empty) | count int32 [nq] (-1: the
@@ -1851,8 +1866,8 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     // queries resident per pass: their fp32 images share 64 KiB of LDS
     const int qt = (size_t)dpad * 4 * 8 <= 65536 ? 8 : (size_t)dpad * 4 * 4 <= 65536 ? 4
                    : (size_t)dpad * 4 * 2 <= 65536 ? 2 : 1;
-    if ((size_t)dpad * 4 > 160 * 1024 || (size_t)D * 8 > 160 * 1024) {
-        set_error("exact search: dimension %d does not fit LDS", D);
+    if (dpad > Q_MAX_DPAD) {   // exact_scan_kernel<1> keeps the query's fp32 image in LDS (128 KiB at 32768)
+        set_error("exact search: dimension %d is above the supported %d", D, Q_MAX_DPAD);
         return MORNA_E_INVALID;
     }
     // queries per batch: approx[nq][N] floats capped at 2 GiB.  The workspace stays with the handle (a hipMalloc / hipFree
@@ -1896,10 +1911,10 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
                 dim3 grid((unsigned)((N + MM_TILE - 1) / MM_TILE), (unsigned)((nb + MM_TILE - 1) / MM_TILE));
                 hipLaunchKernelGGL(exact_scan_mfma_kernel, grid, dim3(256), 0, h->stream, h->X.p, h->norm2.p, N, dpad, Qf,
                                    qn2, nb, approx);
-            } else if (qt == 8) launch_exact_scan<8>(h, N, nb, Qf, qn2, approx);
-            else if (qt == 4) launch_exact_scan<4>(h, N, nb, Qf, qn2, approx);
-            else if (qt == 2) launch_exact_scan<2>(h, N, nb, Qf, qn2, approx);
-            else launch_exact_scan<1>(h, N, nb, Qf, qn2, approx);
+            } else if (qt == 8) MORNA_TRY((launch_exact_scan<8>(h, N, nb, Qf, qn2, approx)));
+            else if (qt == 4) MORNA_TRY((launch_exact_scan<4>(h, N, nb, Qf, qn2, approx)));
+            else if (qt == 2) MORNA_TRY((launch_exact_scan<2>(h, N, nb, Qf, qn2, approx)));
+            else MORNA_TRY((launch_exact_scan<1>(h, N, nb, Qf, qn2, approx)));
         }
         HIP_TRY(hipGetLastError());
         const float eps = exact_scan_eps(dpad, nb >= 32);   // which scan ran
