@@ -194,6 +194,14 @@ int morna_get_nns_by_item(morna_index *h, const int32_t *items, int64_t nq, int3
  * cosine_distance's radicand rounds below zero and math.sqrt fails (morna.py:101-114); the reference evaluates every row
  * (morna.py:697-700), so the whole query fails whatever that row's rank would have been.  The lists of such a query are
  * filled in for diagnosis only; a caller must test the count before it slices by it.
+ * Domain: the answer is the reference's, bit for bit, for every fp32 stored row (any scale: subnormal, zero, with an
+ * fp32 norm that underflows or overflows, or with NaN / inf elements) and every fp64 query whose elements and sequential
+ * sum of squares are finite, for every k and on every path (this call, by item, sharded, packed).  A query whose fp64 sum
+ * of squares lies outside [2^-900, 2^890] -- where the reference's own pp * qq can leave fp64's normal range -- is compared
+ * with every row, as the reference does (slower: every row is re-ranked).  A host query with a NaN / inf element or an
+ * infinite sum of squares gets MORNA_E_INVALID (the same on every rank of a sharded search: the queries are the same);
+ * fp32 queries in device memory (morna_exact_search_packed) are not checked: one with a non-finite element is compared
+ * with every row.
  */
 int morna_exact_search(morna_index *h, const double *q, int64_t nq, int32_t k,
                        int32_t *ids_out, double *dist_out, int32_t *count_out);

@@ -702,6 +702,7 @@ static int load_impl(morna_index *h, const char *path, FILE *f)
     std::vector<float> buf;
     h->host_rows.clear(); h->host_n = 0; h->host_dirty = false; h->built = false;
     h->half.valid = false;
+    h->ex_out_valid = false;
     if (h->n_items != hd.n_items) h->comm_sizes_valid = false;
     h->n_items = hd.n_items;
     MORNA_TRY(h->X.alloc((size_t)std::max<int64_t>(hd.n_items, 1) * h->dpad));

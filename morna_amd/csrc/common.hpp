@@ -275,6 +275,11 @@ struct morna_index {
     morna::DevBuf<int32_t> ex_cand;
     morna::DevBuf<double> ex_cdist;
     int32_t ex_cap = 0;                // candidates per query the last exact search needed room for
+    // rows outside the domain of the exact scan's window (knn.hip, exact_outside_kernel): re-ranked for every query.
+    // Made at the first exact search after the rows or their norms change; usually empty
+    morna::DevBuf<int32_t> ex_out;     // [0] count, [1..] rows
+    int32_t ex_out_n = 0;
+    bool ex_out_valid = false;
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;

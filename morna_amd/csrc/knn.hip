@@ -11,6 +11,8 @@
 //                  the reference's sequential fp64 order and ranked with the
 //                  bisect_left tie rule, so ids and distances are bit-exact.
 #include <algorithm>
+#include <cfloat>
+#include <cstdint>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -1369,6 +1371,11 @@ int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, i
 // =============================================================== exact search
 
 #define E_ROWS 64       // rows per workgroup
+// the domain of the scan's window (exact_scan_eps): rows by their fp32 norm2, queries by their fp64 sum of squares
+#define EX_N2_LO 1.2621774483536189e-29   // 2^-96, times dpad
+#define EX_N2_HI 8.5070591730234616e37f   // 2^126
+#define EX_QQ_LO 0x1p-900
+#define EX_QQ_HI 0x1p890
 
 // approx[q][row] = 2 - 2 cos in fp32 arithmetic (selection only, never returned)
 template <int E_QT>   // queries sharing one pass over a block of rows
@@ -1417,9 +1424,11 @@ __global__ __launch_bounds__(256) void exact_scan_kernel(const float *__restrict
     }
 }
 
-// per query: threshold = k-th smallest approx value; candidates = everything within eps of it
+// per query: threshold = k-th smallest approx value; candidates = everything within eps of it, and the rows outside the
+// scan's domain (`outs`: their scan values are NaN, so they neither set the threshold nor pass it)
 __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restrict__ approx, int64_t n_items,
                                                            int32_t k, float eps, int32_t cap,
+                                                           const int32_t *__restrict__ outs, int32_t n_outs,
                                                            int32_t *__restrict__ cand /* [nq][cap] */,
                                                            int32_t *__restrict__ ncand_out /* [nq] */)
 {
@@ -1428,7 +1437,7 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const float *a = approx + qi * n_items;
-    const int kk = (int)(k < n_items ? k : n_items);
+    const int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);   // the k-th of the rows with a scan value
     uint64_t prev = 0;
     bool have_prev = false;
     constexpr int HELD = 32;   // a shard of up to 8192 rows: the scan values of the query stay in registers for all k rounds
@@ -1462,7 +1471,7 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
             have_prev = true;
         }
     }
-    const float thr = f32_from_orderable((uint32_t)(prev >> 32)) + eps;
+    const float thr = kk > 0 ? f32_from_orderable((uint32_t)(prev >> 32)) + eps : -INFINITY;
     if (tid == 0) s_n = 0;
     __syncthreads();
     for (int64_t i = tid; i < n_items; i += 256) {
@@ -1470,6 +1479,10 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
             int slot = atomicAdd(&s_n, 1);
             if (slot < cap) cand[qi * cap + slot] = (int32_t)i;
         }
+    }
+    for (int j = tid; j < n_outs; j += 256) {
+        const int slot = atomicAdd(&s_n, 1);
+        if (slot < cap) cand[qi * cap + slot] = outs[j];
     }
     __syncthreads();
     if (tid == 0) ncand_out[qi] = s_n;   // may exceed cap: the host then retries with more room
@@ -1579,8 +1592,11 @@ __global__ __launch_bounds__(RR_THREADS) void exact_rerank_kernel(const float *_
 //   D  the candidates are the collected pairs at or below thr -- the set exact_select_kernel produces.
 // `pairs` is the memory of the re-rank's distance array (not yet in use).  More collected than `cap`: the count is reported
 // and the host retries with room for all of them, as for the candidates themselves.  Needs k <= 256 (one minimum per thread).
+// The rows outside the scan's domain (`outs`, scan value NaN) are appended to the candidates.  When they leave fewer than kk
+// of the 256 minima a value, the bound of A is +inf (B collects every row with a value).
 __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restrict__ approx, int64_t n_items, int32_t k, float eps,
-                                                            int32_t cap, uint2 *__restrict__ pairs /* [nq][cap] */,
+                                                            int32_t cap, const int32_t *__restrict__ outs, int32_t n_outs,
+                                                            uint2 *__restrict__ pairs /* [nq][cap] */,
                                                             int32_t *__restrict__ cand /* [nq][cap] */,
                                                             int32_t *__restrict__ ncand_out /* [nq] */)
 {
@@ -1590,7 +1606,18 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const float *a = approx + qi * n_items;
-    const int kk = (int)(k < n_items ? k : n_items);
+    const int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);
+    if (kk <= 0) {   // every row is outside the domain
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        for (int j = tid; j < n_outs; j += 256) {
+            const int slot = atomicAdd(&s_n, 1);
+            if (slot < cap) cand[qi * cap + slot] = outs[j];
+        }
+        __syncthreads();
+        if (tid == 0) ncand_out[qi] = s_n;
+        return;
+    }
     uint64_t mine = ~0ull;
     for (int64_t i = tid; i < n_items; i += 256) {
         const uint64_t key = ((uint64_t)f32_orderable(a[i]) << 32) | (uint32_t)i;
@@ -1605,7 +1632,8 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
         if (mine != ~0ull && below == kk - 1) s_thr = (uint32_t)(mine >> 32);
     }
     __syncthreads();
-    const float bound = f32_from_orderable(s_thr) + eps;
+    float bound = f32_from_orderable(s_thr) + eps;
+    if (bound != bound) bound = INFINITY;   // the kk-th minimum is a NaN: a thread's share held only rows outside the domain
     uint2 *pr = pairs + qi * cap;
     for (int64_t i = tid; i < n_items; i += 256) {
         const float v = a[i];
@@ -1617,7 +1645,7 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
     __syncthreads();
     const int m = s_n;
     if (m > cap) {
-        if (tid == 0) ncand_out[qi] = m;
+        if (tid == 0) ncand_out[qi] = m + n_outs;
         return;
     }
     for (int t = tid; t < m; t += 256) {
@@ -1638,6 +1666,10 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
     for (int t = tid; t < m; t += 256) {
         const uint2 p = pr[t];
         if (f32_from_orderable(p.x) <= thr) cand[qi * cap + atomicAdd(&s_n, 1)] = (int32_t)p.y;
+    }
+    for (int j = tid; j < n_outs; j += 256) {
+        const int slot = atomicAdd(&s_n, 1);
+        if (slot < cap) cand[qi * cap + slot] = outs[j];
     }
     __syncthreads();
     if (tid == 0) ncand_out[qi] = s_n;
@@ -1668,16 +1700,35 @@ __global__ void exact_pack_kernel(const int32_t *__restrict__ ids, const double 
     if (i < nb) m_cnt[i] = cnt[i];
 }
 
-// fp64 query -> fp32 image + its squared norm (selection pass only)
+// fp64 query -> fp32 image + its squared norm (selection pass only).  The image is of the query times 2^s, s chosen so that
+// its largest |element| lies in [1, 2): cos does not change, no element of a finite query overflows fp32 and the norm is at
+// least 1 (exact_scan_eps).  Where the unscaled image was normal and finite, the scan values are the unscaled ones bit for
+// bit.  A query outside the domain -- its fp64 sum of squares qq outside [EX_QQ_LO, EX_QQ_HI], NaN and inf included (only
+// fp32 queries in device memory are not checked on the host) -- gets a zero image: every row then ties at 2 and is
+// re-ranked, as the reference evaluates it.
 __global__ void exact_prep_kernel(const double *__restrict__ Qd, int64_t nq, int32_t dim, int32_t dpad,
                                   float *__restrict__ Qf, float *__restrict__ qn2)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     if (q >= nq) return;
+    double mx = 0.0, qq = 0.0;
+    for (int i = lane; i < dim; i += WAVE) {
+        const double v = Qd[q * dim + i];
+        mx = fmax(mx, fabs(v));   // (fmax drops a NaN: qq does not)
+        qq += v * v;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mx = fmax(mx, __shfl_xor(mx, off, WAVE));
+        qq += __shfl_xor(qq, off, WAVE);
+    }
+    const bool inside = qq >= EX_QQ_LO && qq <= EX_QQ_HI;   // (any summation order: the bounds keep wide margins)
+    int e = 0;
+    if (mx > 0.0) (void)frexp(mx, &e);   // mx = f 2^e, f in [0.5, 1)
     float s = 0.f;
     for (int i = lane; i < dpad; i += WAVE) {
-        float v = i < dim ? (float)Qd[q * dim + i] : 0.f;
+        float v = i < dim && inside ? (float)ldexp(Qd[q * dim + i], 1 - e) : 0.f;   // (exact where the result reaches fp32's range)
         Qf[q * dpad + i] = v;
         s += v * v;
     }
@@ -1814,12 +1865,74 @@ __global__ __launch_bounds__(256, 2) void exact_scan_mfma_kernel(const float *__
 //                          dpad / MM_FLUSH partial sums added one after the other
 //   norms (norm2 of the row, qn2 of the query): sums of dpad / 64 squares per lane + butterfly; half of each enters cos
 //   the fp32 image of the query and the rounding of the value itself: 2 u
+//   underflow: u / 8 (below)
+// Domain.  Relative error terms hold for normal numbers.  The query's image is scaled so that its largest |element| is in
+// [1, 2) (exact_prep_kernel): |q| >= 1, nothing overflows, and an element lost to underflow costs at most 2^-126 |x_i|.
+// A row is inside the domain when its fp32 norm2 lies in [dpad 2^-96, 2^126] (EX_N2_LO, EX_N2_HI).  Then every partial
+// sum stays finite, and each of the <= dpad products or squares loses at most 2^-124 absolute to underflow (even with
+// denormals flushed), i.e. at most 2^-28 of norm2 and sqrt(dpad) 2^-76 of |x| |q| -- inside the u / 8 term.  Rows outside
+// the domain (norm2 of 0 for a non-zero row, subnormal, tiny, inf or NaN: a row with a non-finite element) are on the list
+// of exact_outside_kernel: their scan values are NaN, they take no part in the threshold, and every query re-ranks them,
+// which gives the reference's value whatever it is.  A zero row is inside: both give 2.
+// The window bounds the error against the TRUE 2 - 2cos; the re-rank returns the reference's fp64 value, which is that
+// only while its own arithmetic stays normal.  For a row inside the domain the fp64 pp lies in [2^-97, 2^127]; a query
+// whose fp64 qq lies in [EX_QQ_LO, EX_QQ_HI] = [2^-900, 2^890] keeps pp qq in [2^-997, 2^1017], normal, and what pq and qq
+// lose to fp64 underflow (<= 32768 2^-1075) is nothing beside sqrt(pp qq) or qq.  Outside those bounds cosine_distance can
+// give 2 where the cosine is not 0 (pp qq underflows to 0 or overflows): such a query is compared with every row
+// (exact_prep_kernel gives it a zero image), as the reference does.
 static float exact_scan_eps(int32_t dpad, bool mfma)
 {
     const double u = 5.9604644775390625e-8;
     const double e_dot = mfma ? (MM_FLUSH + dpad / MM_FLUSH + 8) * u : (dpad / 64 + 8) * u;
     const double e_norm = (dpad / 64 + 8) * u;
-    return (float)(2.0 * 2.0 * (e_dot + e_norm + 2 * u));
+    return (float)(2.0 * 2.0 * (e_dot + e_norm + 2 * u + u / 8));
+}
+
+// The rows outside the scan's domain (exact_scan_eps): non-zero rows whose fp32 norm2 is below lo or above EX_N2_HI (NaN
+// included: a row with a NaN or inf element is one of them).  out[0] counts them into out[1..].  Only those few rows are
+// read.
+__global__ void exact_outside_kernel(const float *__restrict__ X, const float *__restrict__ norm2, int64_t n_items, int32_t dim,
+                                     int32_t dpad, float lo, int32_t *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_items) return;
+    const float n = norm2[r];
+    if (n >= lo && n <= EX_N2_HI) return;
+    bool nonzero = false;
+    const float *x = X + r * dpad;
+    for (int z = 0; z < dim; z++) nonzero |= x[z] != 0.f;   // (a NaN is non-zero)
+    if (nonzero) out[1 + atomicAdd(&out[0], 1)] = (int32_t)r;
+}
+
+// scan value NaN for the rows outside the domain, every query of the batch
+__global__ void exact_mask_kernel(const int32_t *__restrict__ outs, int32_t n_outs, int64_t nb, int64_t n_items,
+                                  float *__restrict__ approx)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb * n_outs) return;
+    const int64_t q = i / n_outs;
+    approx[q * n_items + outs[i - q * n_outs]] = __builtin_nanf("");
+}
+
+// made once per row set (invalidated wherever rows or norms change: compute_norms, the fused feature build, load).  Rows
+// with a non-finite element are not refused: re-ranked like the others on the list, they get the reference's value (2
+// for a NaN row, NaN -- count -1 -- for most inf rows), and every shard of a sharded search answers in the same way.
+static int exact_outside_rows(morna_index *h)
+{
+    if (!h->ex_out_valid) {
+        const int64_t N = h->n_items;
+        MORNA_TRY(h->ex_out.alloc((size_t)N + 1));
+        HIP_TRY(hipMemsetAsync(h->ex_out.p, 0, 4, h->stream));
+        hipLaunchKernelGGL(exact_outside_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->X.p,
+                           h->norm2.p, N, h->dim, h->dpad, (float)(EX_N2_LO * h->dpad), h->ex_out.p);
+        HIP_TRY(hipGetLastError());
+        int32_t got = 0;
+        HIP_TRY(hipMemcpyAsync(&got, h->ex_out.p, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->ex_out_n = got;
+        h->ex_out_valid = true;
+    }
+    return MORNA_OK;
 }
 
 template <int QT>
@@ -1857,6 +1970,18 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     if (nq == 0) return MORNA_OK;
     const int64_t N = h->n_items;
     const int32_t D = h->dim, dpad = h->dpad;
+    if (q_host)   // the contract: finite elements and a finite sum of squares in the reference's order (cosine_distance)
+        for (int64_t i = 0; i < nq; i++) {
+            double qq = 0.0;
+            for (int32_t z = 0; z < D; z++) {
+                const double j = q_host[i * D + z], jj = j * j;
+                qq = qq + jj;
+            }
+            if (!(qq <= DBL_MAX)) {
+                set_error("exact search: query %lld has a non-finite element or sum of squares", (long long)i);
+                return MORNA_E_INVALID;
+            }
+        }
     if (items_host)
         for (int64_t i = 0; i < nq; i++)
             if (items_host[i] < 0 || items_host[i] >= N) {
@@ -1870,6 +1995,9 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
         set_error("exact search: dimension %d is above the supported %d", D, Q_MAX_DPAD);
         return MORNA_E_INVALID;
     }
+    MORNA_TRY(exact_outside_rows(h));
+    const int32_t n_outs = h->ex_out_n;
+    const int32_t *outs = h->ex_out.p + 1;
     // queries per batch: approx[nq][N] floats capped at 2 GiB.  The workspace stays with the handle (a hipMalloc / hipFree
     // pair per array and call cost more than a small search)
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 29) / std::max<int64_t>(N, 1)));
@@ -1889,7 +2017,7 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     double *d_dist = (double *)p; p += s_dist;
     int32_t *d_cnt = (int32_t *)p; p += s_b4;
     std::vector<int32_t> h_ncand((size_t)batch);
-    int32_t cap = std::max<int32_t>(std::max(64, 4 * k), h->ex_cap), need_max = 0;
+    int32_t cap = std::max<int32_t>(std::max(64, 4 * k) + n_outs, h->ex_cap), need_max = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += batch) {
         const int64_t nb = std::min(batch, nq - q0);
         if (q_host) {
@@ -1916,6 +2044,9 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
             else if (qt == 2) MORNA_TRY((launch_exact_scan<2>(h, N, nb, Qf, qn2, approx)));
             else MORNA_TRY((launch_exact_scan<1>(h, N, nb, Qf, qn2, approx)));
         }
+        if (n_outs > 0)
+            hipLaunchKernelGGL(exact_mask_kernel, dim3((unsigned)((nb * n_outs + 255) / 256)), dim3(256), 0, h->stream, outs,
+                               n_outs, nb, N, approx);
         HIP_TRY(hipGetLastError());
         const float eps = exact_scan_eps(dpad, nb >= 32);   // which scan ran
         ScopedTimer tm_sel(h, MORNA_T_EXACT, 0);            // selection + fp64 re-rank: the same group as the scan
@@ -1925,10 +2056,10 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
             MORNA_TRY(h->ex_cdist.alloc((size_t)batch * cap));
             if (N > 8192 && k <= 256 && select2_on)
                 hipLaunchKernelGGL(exact_select2_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, approx, N, k, eps, cap,
-                                   (uint2 *)h->ex_cdist.p, h->ex_cand.p, ncand);
+                                   outs, n_outs, (uint2 *)h->ex_cdist.p, h->ex_cand.p, ncand);
             else
                 hipLaunchKernelGGL(exact_select_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, approx, N, k, eps,
-                                   cap, h->ex_cand.p, ncand);
+                                   cap, outs, n_outs, h->ex_cand.p, ncand);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(h_ncand.data(), ncand, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));

@@ -4,6 +4,7 @@ hard-coded neighbour orderings through the saved index.  -m gpu"""
 import gzip
 import io
 import os
+import re
 
 import numpy as np
 import pytest
@@ -335,6 +336,9 @@ def test_cli_index_shards_one_process_per_rank_under_torchrun(tmp_path):
     assert a.exact_search_nn(8) == b.exact_search_nn(8)
 
 
+_RESULT_LINE = re.compile(r"\d+\.(\t|$)")   # results_output: "<rank>." and a tab before every field
+
+
 def test_cli_search_one_process_per_shard_under_torchrun(tmp_path):
     """`morna search` launched as `torch.distributed.run --nproc-per-node 2` on a file set of two shards: every rank loads ITS
     shard, the ranks answer together (dist.ShardedSearch: RCCL inside the library when every rank has a GPU, gloo through
@@ -374,12 +378,14 @@ def test_cli_search_one_process_per_shard_under_torchrun(tmp_path):
                             "127.0.0.1", "--master-port", str(port), "-m", "morna_amd.cli"] + argv, cwd=root, input=stdin_text,
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
-        return [ln for ln in r.stdout.splitlines() if ln[:1].isdigit()]
+        # the result lines ("rank.<TAB>..."): RCCL may print lines of its own to the ranks' stdout, some of them
+        # starting with a rank number ("1 is connected to 1 peer ranks. ...")
+        return [ln for ln in r.stdout.splitlines() if _RESULT_LINE.match(ln)]
 
     def single(argv, stdin_text=None):
         out = io.StringIO()
         assert cli.main(argv, stdin=io.StringIO(stdin_text or ""), stdout=out) == 0
-        return [ln for ln in out.getvalue().splitlines() if ln[:1].isdigit()]
+        return [ln for ln in out.getvalue().splitlines() if _RESULT_LINE.match(ln)]
 
     by_member = ["search", "-x", base, "-q", str(sample), "-d", "-r", "8", "--search-k", "-1"]
     assert torchrun(by_member) == single(by_member) and len(single(by_member)) == 8

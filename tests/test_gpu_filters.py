@@ -1,10 +1,12 @@
-"""The fp16 matrix-core filters at the row widths that ship (D = 3000: the bench; D = 8192: configs[4]) on rows built
-to defeat them.  -m gpu
+"""The fp16 matrix-core filters at the row widths that ship (D = 3000: the bench; D = 8192: configs[4]) and past them
+(12000, not a multiple of 256; 32768, the widest row) on rows built to defeat them.  -m gpu
 
 The split of a level (splitmm.hip) and the candidate filter of the approximate search decide from fp16 copies only
 what they can PROVE and hand everything else to the canonical fp32 arithmetic, so switching them off must change
 nothing: whole-forest and search digests are compared across MORNA_SPLIT_MM = 0 / 1, MORNA_QUERY_FILTER = 0 / 1 and
-MORNA_QUERY_DENSE = 0 / 1 (the filter dots of a whole batch as one contraction, or candidate by candidate), and across
+MORNA_QUERY_DENSE = 0 / 1 (the filter dots of a whole batch as one contraction, or candidate by candidate),
+MORNA_SPLIT_BIG = 0 / 1 and MORNA_QUERY_BIG = 0 / 1 (the contractions' tile shapes, each with its own accumulation
+bound), and across
 MORNA_QUERY_SPLIT_TRAVERSE = 0 / 1 and MORNA_QUERY_SPREAD = 0 / 1 (how a batch's, and a small batch's, traversal is dealt out),
 MORNA_SPLIT_ORDER = 0 / 1 and MORNA_SPLIT_LISTS = 0 / 1 (the order of the rows of the split contraction, and the per-tile
 task lists: both only choose which products are computed; the 256-wide case with 150 trees has levels with enough split
@@ -37,11 +39,14 @@ rng = np.random.default_rng(2026 + D)
 nc = 5
 C = rng.standard_normal((nc, D)).astype(np.float32)
 lab = rng.integers(0, nc, N)
-X = C[lab] + np.float32(0.25) * rng.standard_normal((N, D), dtype=np.float32)
+X = np.empty((N, D), np.float32)   # made in chunks of rows: at 34000 x 32768 one fp64 temporary would be 9 GB
+for c0 in range(0, N, 2048):
+    c1 = min(N, c0 + 2048)
+    X[c0:c1] = C[lab[c0:c1]] + np.float32(0.25) * rng.standard_normal((c1 - c0, D), dtype=np.float32)
 X *= (10.0 ** rng.uniform(-3, 3, (N, 1))).astype(np.float32)
-unit = X / np.linalg.norm(X.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
-# midpoints of rows from different clusters
+# midpoints of rows from different clusters (a, b among the first m0 rows)
 m0 = 2000
+unit = X[:m0] / np.linalg.norm(X[:m0].astype(np.float64), axis=1, keepdims=True).astype(np.float32)
 for i in range(m0, m0 + 1500):
     a, b = rng.integers(0, m0, 2)
     while lab[a] == lab[b]:
@@ -93,30 +98,72 @@ print("DIGEST", h.hexdigest(), st["n_split"], st["max_depth"])
 """
 
 
-@pytest.mark.parametrize("D,N,T", [(3000, 16000, 6), (8192, 34000, 3), (256, 40000, 150)])
-def test_adversarial_rows_filters_change_nothing(tmp_path, D, N, T):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = str(tmp_path / "digest.py")
-    with open(script, "w") as fh:
-        fh.write(_SCRIPT.format(root=root, N=N, D=D, T=T))
-    out, open_lines = {}, []
-    for name, extra in (("default", {"MORNA_DEBUG_OPEN": "1"}), ("no_mm", {"MORNA_SPLIT_MM": "0"}),
-                        ("no_qf", {"MORNA_QUERY_FILTER": "0"}), ("no_dense", {"MORNA_QUERY_DENSE": "0"}),
-                        ("no_order", {"MORNA_SPLIT_ORDER": "0"}), ("no_lists", {"MORNA_SPLIT_LISTS": "0", "MORNA_SPLIT_ORDER": "0"}),
-                        # round 3: the traversal of a batch as root margins by query groups + one-wave descents, or fused (one
-                        # workgroup per query); small batches dealt out over the chip, or one workgroup per query
-                        ("fused_traverse", {"MORNA_QUERY_SPLIT_TRAVERSE": "0"}), ("no_spread", {"MORNA_QUERY_SPREAD": "0"})):
-        env = dict(os.environ, **extra)
-        r = subprocess.run([sys.executable, script], env=env, capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out[name] = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()[1:]
-        if name == "default":
-            open_lines = [ln for ln in r.stderr.splitlines() if ln.startswith("[morna] split_mm level")]
-    assert out["default"] == out["no_mm"] == out["no_qf"] == out["no_dense"] == out["no_order"] == out["no_lists"], out
-    assert out["default"] == out["fused_traverse"] == out["no_spread"], out
-    assert int(out["default"][2]) >= 2                       # at least two levels went through the contraction
+# one process per switch (they are read once per process); the default one also prints the open-pair share per level
+_RUNS = (("default", {"MORNA_DEBUG_OPEN": "1"}), ("no_mm", {"MORNA_SPLIT_MM": "0"}),
+         ("no_qf", {"MORNA_QUERY_FILTER": "0"}), ("no_dense", {"MORNA_QUERY_DENSE": "0"}),
+         ("no_order", {"MORNA_SPLIT_ORDER": "0"}), ("no_lists", {"MORNA_SPLIT_LISTS": "0", "MORNA_SPLIT_ORDER": "0"}),
+         # round 3: the traversal of a batch as root margins by query groups + one-wave descents, or fused (one
+         # workgroup per query); small batches dealt out over the chip, or one workgroup per query
+         ("fused_traverse", {"MORNA_QUERY_SPLIT_TRAVERSE": "0"}), ("no_spread", {"MORNA_QUERY_SPREAD": "0"}),
+         # one accumulation bound or the other: 128 x 128 contraction tiles only (split, query filter)
+         ("no_split_big", {"MORNA_SPLIT_BIG": "0"}), ("no_query_big", {"MORNA_QUERY_BIG": "0"}))
+
+
+def _digest(script, extra):
+    """(digest fields, split_mm open-pair lines) of one process."""
+    r = subprocess.run([sys.executable, script], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()[1:]
+    return out, [ln for ln in r.stderr.splitlines() if ln.startswith("[morna] split_mm level")]
+
+
+def _check_default(out, open_lines):
+    assert int(out[2]) >= 2                                  # at least two levels went through the contraction
     assert open_lines, "the matrix-core split did not run"
     print("\n".join(open_lines))                             # pytest -s: the open-pair share per level (DESIGN.md)
     # the filter must have left pairs open (the rows above) and still decided most
     shares = [float(ln.split("(")[-1].split("%")[0]) for ln in open_lines]
     assert max(shares) > 0.0 and min(shares) < 50.0, open_lines
+
+
+def _write_script(path, D, N, T):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(path, "w") as fh:
+        fh.write(_SCRIPT.format(root=root, N=N, D=D, T=T))
+    return path
+
+
+@pytest.mark.parametrize("D,N,T", [(3000, 16000, 6), (8192, 34000, 3), (256, 40000, 150), (12000, 34000, 3)])
+def test_adversarial_rows_filters_change_nothing(tmp_path, D, N, T):
+    script = _write_script(str(tmp_path / "digest.py"), D, N, T)
+    out = {}
+    for name, extra in _RUNS:
+        out[name], lines = _digest(script, extra)
+        if name == "default":
+            open_lines = lines
+    assert out["default"] == out["no_mm"] == out["no_qf"] == out["no_dense"] == out["no_order"] == out["no_lists"], out
+    assert out["default"] == out["fused_traverse"] == out["no_spread"], out
+    assert out["default"] == out["no_split_big"] == out["no_query_big"], out
+    _check_default(out["default"], open_lines)
+
+
+# The widest row: 70000 rows of 32768 floats, past twice annoy's leaf of D + 2 rows, so the forest splits below its root
+# (9 GB of rows per process: one test per switch, each against the default process's digest, made once)
+_WIDEST = (32768, 70000, 2)
+
+
+@pytest.fixture(scope="module")
+def widest(tmp_path_factory):
+    script = _write_script(str(tmp_path_factory.mktemp("widest") / "digest.py"), *_WIDEST)
+    out, open_lines = _digest(script, dict(_RUNS)["default"])
+    return script, out, open_lines
+
+
+def test_widest_row_adversarial_rows_default(widest):
+    _check_default(widest[1], widest[2])
+
+
+@pytest.mark.parametrize("name", [n for n, _ in _RUNS if n != "default"])
+def test_widest_row_filters_change_nothing(widest, name):
+    script, default, _ = widest
+    assert _digest(script, dict(_RUNS)[name])[0] == default, name

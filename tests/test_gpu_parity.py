@@ -155,6 +155,44 @@ def test_features_long_lines_with_item_order(capi):
         assert a.get_items().tobytes() == ref["X"].tobytes(), order
 
 
+_SWITCH_SCRIPT = r"""
+import sys
+import numpy as np
+sys.path.insert(0, {root!r})
+sys.path.insert(0, {tests!r})
+from oracle import capi
+from test_gpu_parity import _gpu_features, _synthetic_lines
+# (D, samples, lines, item order): the last has > 65536 samples, so the fused norm pass is the default there only
+for D, n_samples, J, order in ((64, 700, 1500, "ext"), (3000, 2000, 3000, "ext"), (257, 300, 50, None),
+                               (40, 70000, 4500, "reversed")):
+    rng = np.random.default_rng(8675309 + D)
+    keys, rp, s, c = _synthetic_lines(rng, n_samples, J, 5, 120)
+    buf, off = capi.pack_keys(keys)
+    ref = capi.index_features(buf, off, rp, s, c, n_samples, 20, D)
+    a, prep = _gpu_features(keys, rp, s, c, n_samples, 20, D, order)
+    assert a.get_items().tobytes() == ref["X"].tobytes(), D
+    want = np.array([capi.dot(1, x, x) for x in ref["X"]], np.float32)
+    assert a.get_norms2().tobytes() == want.tobytes(), D
+print("SWITCH_OK")
+"""
+
+
+@pytest.mark.parametrize("env", ["MORNA_FEATURES_WAVE=0", "MORNA_PREP_LDS=0", "MORNA_FUSED_NORMS=0", "MORNA_FUSED_NORMS=1"])
+def test_features_switches_vs_oracle(env, tmp_path):
+    """The feature-build switches README lists as result-neutral (read once per process, so each in a process of its own):
+    the matrix and the canonical row norms against the oracle, bit for bit."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = str(tmp_path / "switch.py")
+    with open(script, "w") as fh:
+        fh.write(_SWITCH_SCRIPT.format(root=root, tests=os.path.join(root, "tests")))
+    name, value = env.split("=")
+    r = subprocess.run([sys.executable, script], env=dict(os.environ, **{name: value}), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0 and "SWITCH_OK" in r.stdout, r.stderr[-2000:]
+
+
 def test_row_norms_canonical(capi):
     rng = np.random.default_rng(1)
     for D in (40, 256, 3000):
