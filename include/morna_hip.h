@@ -136,6 +136,36 @@ int morna_lines_from_arrays(const uint8_t *key_bytes, const int64_t *key_off, in
 int morna_write_intropolis(const char *path, const uint8_t *key_bytes, const int64_t *key_off, int64_t J, const int64_t *row_ptr,
                            const int64_t *samples, const int32_t *cov);
 
+/*
+ * ---- many query samples at once (the reference answers one per process: MornaSearch, morna.py:597-629, 632-716) ----
+ * morna_lines_query_terms  host pre-pass, no GPU work.  L: a QUERY file parsed by morna_parse_intropolis with threshold 0
+ *     and a positive sample_count (its idf is not used).  vocab_bytes / vocab_off[V+1] / vocab_df[V]: the index's
+ *     junction -> frequency table (.freq.mor; keys "chrom start end", morna.py:849), sample_count: the index's (.stats.mor
+ *     line 1, > 0).  The result: the lines whose key is in the table, in file order, each (key, sample) entry on the FIRST
+ *     line holding it with its coverages summed (no sample repeats in a line), idf[j] = the key's weight
+ *     log(sample_count / df) from libm (0 when df is 0), ext_ids and the query count as in L -- query q is internal id q,
+ *     numbered by first appearance (morna.py:377-382).  Keys are compared as written (no normalisation: the raw-stream
+ *     key of a canonical decimal coordinate, what intropolis writes).  A summed coverage outside int32 is MORNA_E_INVALID
+ *     naming the sample and the key.
+ * morna_build_query_rows  the rows of those query samples on the GPU, in buffers of their own on the handle (a second
+ *     call replaces them): row[q][c] = +0.0 plus sign(k) * (C(k,q) * w(k)) in fp64, one rounding per operation, once per
+ *     distinct key k of q with mmh3(k) mod dim == c, in the order of the first line holding k and q -- exactly
+ *     finalize_query's dict order (morna.py:609-629).  Also their fp32 image (what get_nns_by_vector sees).  X, its norms,
+ *     the forest and the index's caches are not touched.  Timed under MORNA_T_FEATURES.  With int32 coverages and finite
+ *     weights every row is finite and its sum of squares lies inside the exact search's domain ([2^-900, 2^890], or 0).
+ * morna_get_query_rows  rows64[nq][dim] fp64 and / or rows32[nq][dim] fp32 to host memory (either may be NULL).
+ * morna_get_nns_by_query_rows  morna_get_nns_by_vector with the resident fp32 rows as the queries, nq = the rows built.
+ * morna_exact_search_query_rows  morna_exact_search (morna.py:681-716) with the resident fp64 rows as the queries: no
+ *     PCIe round trip; batching, count -1 and the rows outside the scan's window as in morna_exact_search.  A query with no
+ *     vocabulary junction has the zero row and is answered as the reference answers a zero query_sample.
+ */
+int morna_lines_query_terms(const morna_lines *L, const uint8_t *vocab_bytes, const int64_t *vocab_off, const int64_t *vocab_df,
+                            int64_t V, int64_t sample_count, morna_lines **out);
+int morna_build_query_rows(morna_index *h, const morna_lines *T);
+int morna_get_query_rows(morna_index *h, double *rows64, float *rows32);
+int morna_get_nns_by_query_rows(morna_index *h, int32_t k, int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out);
+int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

@@ -53,6 +53,11 @@ SIGNATURES = {
     "morna_lines_shard_info": (C.c_int, [_p, _p]),
     "morna_lines_from_arrays": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, C.POINTER(_p)]),
     "morna_write_intropolis": (C.c_int, [C.c_char_p, _p, _p, _i64, _p, _p, _p]),
+    "morna_lines_query_terms": (C.c_int, [_p, _p, _p, _p, _i64, _i64, C.POINTER(_p)]),
+    "morna_build_query_rows": (C.c_int, [_p, _p]),
+    "morna_get_query_rows": (C.c_int, [_p, _p, _p]),
+    "morna_get_nns_by_query_rows": (C.c_int, [_p, _i32, _i32, _p, _p, _p]),
+    "morna_exact_search_query_rows": (C.c_int, [_p, _i32, _p, _p, _p]),
     "morna_merge_topk": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_vector_packed": (C.c_int, [_p, _p, _i64, _i32, _i32, _i64, _p]),
     "morna_merge_topk_packed": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),

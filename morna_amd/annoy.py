@@ -237,6 +237,40 @@ class AnnoyIndex(object):
         check(lib().morna_exact_search_by_item(self._h, ptr(items), nq, int(n), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
+    # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
+    def build_query_rows(self, terms):
+        """Rows of the query samples of `terms` (index.ParsedLines from ParsedLines.query_terms) on this handle, beside the
+        index; they replace the rows of an earlier call."""
+        self._qrows_n = 0
+        check(lib().morna_build_query_rows(self._h, terms._p))
+        self._qrows_n = int(terms.n_items)
+
+    def get_query_rows(self):
+        """(fp64 rows [nq, f], their fp32 image [nq, f]) of the last build_query_rows."""
+        nq = getattr(self, "_qrows_n", 0)
+        r64 = np.empty((nq, self.f), np.float64)
+        r32 = np.empty((nq, self.f), np.float32)
+        check(lib().morna_get_query_rows(self._h, ptr(r64), ptr(r32)))
+        return r64, r32
+
+    def get_nns_by_query_rows(self, n, search_k=-1):
+        """get_nns_by_vector_batch with the resident fp32 query rows as the queries."""
+        nq = getattr(self, "_qrows_n", 0)
+        ids = np.empty((nq, n), np.int32)
+        d = np.empty((nq, n), np.float32)
+        cnt = np.empty(nq, np.int32)
+        check(lib().morna_get_nns_by_query_rows(self._h, int(n), int(search_k), ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
+    def exact_search_query_rows(self, n):
+        """exact_search_batch with the resident fp64 query rows as the queries (they do not cross PCIe)."""
+        nq = getattr(self, "_qrows_n", 0)
+        ids = np.empty((nq, n), np.int32)
+        d = np.empty((nq, n), np.float64)
+        cnt = np.empty(nq, np.int32)
+        check(lib().morna_exact_search_query_rows(self._h, int(n), ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
     # ---- row-sharded search, communicator inside the library (comm.hip) --------
     @staticmethod
     def comm_unique_id():

@@ -14,6 +14,7 @@ here do the latter.
 
     python -m morna_amd.cli index --intropolis junctions.tsv.gz -x idx -s 9662 --n-trees 10
     python -m morna_amd.cli search -x idx -q 1234 -d
+    python -m morna_amd.cli search -x idx --intropolis new_samples.tsv.gz -e -d
     cat query.bed | python -m morna_amd.cli search -x idx -f bed --exact -d
 """
 import argparse
@@ -50,6 +51,13 @@ def add_search_parameters(subparser):
                            help='the number of nearest neighbor results to return')
     subparser.add_argument('-rl', '--rawlist', action='store_const', const=True, default=False,
                            help='regurgitate junction list for input sample instead of performing search')
+    subparser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
+                           help='search every sample of this (gzipped) intropolis file at once: one block per sample, '
+                                '"# query <sample id>" and then what -f raw prints for that sample\'s junctions '
+                                '(-f is ignored)')
+    subparser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                           help='comma-separated sample ids already in the index, searched together: one block per id, '
+                                '"# query <id>" and then what -q <id> prints')
     subparser.add_argument('--device', type=str, default='0',
                            help='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
                                 'dealt to these devices in turn')
@@ -95,8 +103,29 @@ def build_parser():
     return parser
 
 
+def _check_batch_flags(parser, args):
+    """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
+    batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
+    if not batch:
+        return
+    if len(batch) > 1:
+        parser.error("--intropolis and --query-ids cannot be used together")
+    for flag, on in (("-q/--query-id", args.query_id is not None), ("-c/--convergence-backoff", args.convergence_backoff is not None),
+                     ("-rl/--rawlist", args.rawlist)):
+        if on:
+            parser.error("%s cannot be used with %s" % (batch[0], flag))
+    if args.query_ids is not None:
+        try:
+            args.query_ids = [int(t) for t in args.query_ids.split(',')]
+        except ValueError:
+            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
+
+
 def main(argv=None, stdin=None, stdout=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.subparser_name == 'search':
+        _check_batch_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -145,9 +174,41 @@ def main(argv=None, stdin=None, stdout=None):
             dist.destroy_process_group()
 
 
+def _search_batch(args, searcher, stdout):
+    """--intropolis / --query-ids: one block per query, in query order; 1 when some exact query failed as the
+    reference's would (math domain error), after all blocks."""
+    from .search import results_output
+    if args.query_ids is not None:
+        internal, results = searcher.search_member_n_batch(args.query_ids, args.results, args.search_k,
+                                                           include_distances=args.distances, meta_db=args.metadata)
+        for query_id, internal_id, res in zip(args.query_ids, internal, results):
+            stdout.write("# query %d\n" % query_id)
+            stdout.write("querying by sample id " + str(query_id) + "\n")      # search_member_n's two lines
+            stdout.write("this is internal id " + str(internal_id) + "\n")
+            results_output(res, stdout)
+        return 0
+    batch = searcher.queries_from_intropolis(args.intropolis)
+    if args.exact:
+        results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata)
+    else:
+        results = searcher.search_nn_batch(batch, args.results, args.search_k, include_distances=args.distances,
+                                           meta_db=args.metadata)
+    failed = False
+    for sample_id, res in zip(batch.ext_ids, results):
+        stdout.write("# query %d\n" % sample_id)
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+        else:
+            results_output(res, stdout)
+    return 1 if failed else 0
+
+
 def _search(args, searcher, stdin, stdout, dist, rank):
     from .search import results_output
     from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
+    if args.intropolis is not None or args.query_ids is not None:
+        return _search_batch(args, searcher, stdout)
     if args.query_id is not None:                              # morna.py:1358-1365
         if dist is not None and rank != 0:
             import contextlib

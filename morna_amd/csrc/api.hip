@@ -563,6 +563,57 @@ int morna_exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, i
     return exact_search(h, q, nq, k, ids_out, dist_out, count_out);
 }
 
+// ---- query rows (morna_build_query_rows is in parse.hip, beside the lines it takes) ---------------------------
+
+static int query_rows_ready(morna_index *h)
+{
+    if (!h->qrows.valid) {
+        set_error("no query rows: call morna_build_query_rows first");
+        return MORNA_E_STATE;
+    }
+    return MORNA_OK;
+}
+
+int morna_get_query_rows(morna_index *h, double *rows64, float *rows32)
+{
+    CHECK_H(h);
+    MORNA_TRY(query_rows_ready(h));
+    HIP_TRY(hipSetDevice(h->device));
+    MORNA_TRY(settle(h));
+    const QueryRows &Q = h->qrows;
+    if (Q.nq == 0) return MORNA_OK;
+    if (rows64) HIP_TRY(hipMemcpy(rows64, Q.rows64.p, (size_t)Q.nq * h->dim * 8, hipMemcpyDeviceToHost));
+    if (rows32)
+        HIP_TRY(hipMemcpy2D(rows32, (size_t)h->dim * 4, Q.rows32.p, (size_t)h->dpad * 4, (size_t)h->dim * 4, (size_t)Q.nq,
+                            hipMemcpyDeviceToHost));
+    return MORNA_OK;
+}
+
+int morna_get_nns_by_query_rows(morna_index *h, int32_t k, int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out)
+{
+    CHECK_H(h);
+    MORNA_TRY(query_rows_ready(h));
+    if (!ids_out) {
+        set_error("get_nns_by_query_rows: null buffer");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    // the resident fp32 image, read in place (query_batch takes device queries, dpad floats apart)
+    return query_batch(h, h->qrows.rows32.p, h->dpad, nullptr, h->qrows.nq, k, search_k, ids_out, dist_out, count_out);
+}
+
+int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out)
+{
+    CHECK_H(h);
+    MORNA_TRY(query_rows_ready(h));
+    if (!ids_out) {
+        set_error("exact_search_query_rows: null buffer");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return exact_search_any(h, nullptr, nullptr, nullptr, h->qrows.nq, k, ids_out, dist_out, count_out, nullptr, 0, h->qrows.rows64.p);
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

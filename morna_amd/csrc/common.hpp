@@ -207,6 +207,28 @@ struct SplitMmScratch {   // splitmm.hip
     }
 };
 
+struct QueryRows {   // features.hip: rows of query samples built against the index's vocabulary; the index itself untouched
+    DevBuf<uint8_t> keys;
+    DevBuf<int64_t> key_off, row_ptr;
+    DevBuf<int32_t> ids, cov;
+    DevBuf<double> w;            // [J] weight of every line's key
+    DevBuf<int32_t> col, col_count, col_off, col_lines, bucket_aux;
+    DevBuf<double> sidf;
+    DevBuf<double> colacc;       // [D][nq] fp64 cell sums
+    DevBuf<double> rows64;       // [nq][dim]
+    DevBuf<float> rows32;        // [nq][dpad], pad columns zero
+    int64_t nq = 0;
+    bool valid = false;          // rows64 / rows32 hold the rows of the last morna_build_query_rows
+    void release()
+    {
+        keys.release(); key_off.release(); row_ptr.release(); ids.release(); cov.release(); w.release();
+        col.release(); col_count.release(); col_off.release(); col_lines.release(); bucket_aux.release();
+        sidf.release(); colacc.release(); rows64.release(); rows32.release();
+        nq = 0;
+        valid = false;
+    }
+};
+
 }  // namespace morna
 
 struct morna_index {
@@ -285,6 +307,7 @@ struct morna_index {
     morna::ForestScratch forest;
     morna::HalfRows half;
     morna::SplitMmScratch splitmm;
+    morna::QueryRows qrows;      // morna_build_query_rows
     // [0] rows read by query kernels (hyperplane dots + candidates + 1 per query)
     morna::DevBuf<unsigned long long> d_stat;
 
@@ -349,6 +372,10 @@ inline int settle(morna_index *h)
 int upload_host_rows(morna_index *h);
 int compute_norms(morna_index *h);
 int build_features(morna_index *h, int64_t n_items);
+// rows of the nq query samples of J deduplicated lines (morna_lines_query_terms) into h->qrows; X, its norms, the forest and
+// every cache of the index stay as they are
+int build_query_rows(morna_index *h, const uint8_t *key_bytes, const int64_t *key_off, int64_t J, const int64_t *row_ptr,
+                     const int32_t *ids, const int32_t *cov, const double *w, int64_t nq);
 int hash_keys_device(morna_index *h, const uint8_t *key_bytes, const int64_t *key_off, int64_t J,
                      int32_t *hash_out, int32_t *col_out, int32_t *sign_out);
 int build_forest(morna_index *h, int32_t n_trees, uint32_t seed);
@@ -373,8 +400,10 @@ int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, i
 int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t *ids_out,
                  double *dist_out, int32_t *count_out);
 // the same for fp32 queries in device memory or for stored rows, answers to the host and / or packed for the sharded merge
+// (q_dev64: fp64 queries [nq][dim] in this device's memory, the query rows of morna_build_query_rows)
 int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
-                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset);
+                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
+                     const double *q_dev64 = nullptr);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

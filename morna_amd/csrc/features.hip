@@ -19,6 +19,8 @@
 //                        order is the file order, with no atomics.
 //   transpose_convert    fp32 [D][N] (each cell rounded once from its fp64 sum) -> fp32 [N][dpad] through an LDS tile
 //   row_norms_kernel     canonical dot(x, x) per row
+// Query rows (morna_build_query_rows): the same hashing and bucketing, then query_accumulate_kernel (fp64 sums kept) and
+// query_rows_transpose_kernel (fp64 rows and their fp32 image), into buffers of their own: the index is not touched.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -789,6 +791,72 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float *__restrict_
     }
 }
 
+// ------------------------------------------------- query rows (morna_build_query_rows)
+//
+// The rows of query samples against the index's vocabulary: the same hashing and column bucketing as the index's
+// matrix, but the cell sums stay fp64 -- the exact search takes the un-rounded query_sample (morna.py:681-716) and the
+// approximate search its fp32 image (annoy's get_nns_by_vector, morna.py:651-659).  The lines come deduplicated from
+// morna_lines_query_terms: no sample repeats in a line, so the lanes of a line touch distinct cells and no serial replay
+// is needed; the lines of a column are walked in file order, one barrier between lines, which is finalize_query's order
+// of the terms of a cell (search.py; morna.py:609-629).
+#define QA_THREADS 256
+#define QA_TILE 4096   // query samples per workgroup: 32 KiB of fp64 sums in LDS
+__global__ __launch_bounds__(QA_THREADS) void query_accumulate_kernel(int32_t n_tiles, int32_t n_cols, const int32_t *__restrict__ col_off,
+                                                                      const int32_t *__restrict__ col_lines, const double *__restrict__ sidf,
+                                                                      const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ ids,
+                                                                      const int32_t *__restrict__ cov, int64_t nq,
+                                                                      double *__restrict__ colacc /* [D][nq] */)
+{
+    __shared__ double acc[QA_TILE];
+    const int c = (int)(blockIdx.x / n_tiles), tile = (int)(blockIdx.x % n_tiles);
+    if (c >= n_cols) return;
+    const int64_t r_lo = (int64_t)tile * QA_TILE;
+    const uint32_t span = (uint32_t)(r_lo + QA_TILE < nq ? QA_TILE : nq - r_lo);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < QA_TILE; i += QA_THREADS) acc[i] = 0.0;
+    __syncthreads();
+    const int nl = col_off[c + 1] - col_off[c];
+    const int32_t *lines = col_lines + col_off[c];
+    for (int l = 0; l < nl; l++) {   // uniform over the workgroup
+        const int32_t j = lines[l];
+        const int64_t b = row_ptr[j], e = row_ptr[j + 1];
+        const double wq = sidf[j];
+        for (int64_t t = b + tid; t < e; t += QA_THREADS) {
+            const uint32_t off = (uint32_t)((int64_t)ids[t] - r_lo);
+            // term = cov * weight (one rounding), with the key's sign, then += (one rounding): finalize_query
+            if (off < span) acc[off] = __dadd_rn(acc[off], __dmul_rn((double)cov[t], wq));
+        }
+        __syncthreads();   // the next line of this column may touch the same cells from other threads
+    }
+    double *out = colacc + (int64_t)c * nq + r_lo;
+    for (int i = tid; i < (int)span; i += QA_THREADS) out[i] = acc[i];
+}
+
+// fp64 [D][nq] -> fp64 rows [nq][dim] and their fp32 image [nq][dpad] (pad columns zero) through an LDS tile
+__global__ __launch_bounds__(256) void query_rows_transpose_kernel(const double *__restrict__ colacc, int64_t nq, int32_t dim,
+                                                                   int32_t dpad, double *__restrict__ rows64, float *__restrict__ rows32)
+{
+    __shared__ double tile[TT][TT + 1];
+    const int64_t n0 = (int64_t)blockIdx.x * TT;
+    const int32_t c0 = blockIdx.y * TT;
+    const int tx = threadIdx.x & (TT - 1), ty = threadIdx.x / TT;   // 64 x 4
+    for (int r = ty; r < TT; r += 4) {
+        const int32_t c = c0 + r;
+        const int64_t n = n0 + tx;
+        tile[r][tx] = c < dim && n < nq ? colacc[(int64_t)c * nq + n] : 0.0;
+    }
+    __syncthreads();
+    for (int r = ty; r < TT; r += 4) {
+        const int64_t n = n0 + r;
+        const int32_t c = c0 + tx;
+        if (n < nq && c < dpad) {
+            const double v = tile[tx][r];
+            if (c < dim) rows64[n * dim + c] = v;
+            rows32[n * dpad + c] = __double2float_rn(v);   // get_nns_by_vector's cast of the query (annoy stores fp32)
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 
 int compute_norms(morna_index *h)
@@ -850,6 +918,26 @@ int hash_keys_device(morna_index *h, const uint8_t *key_bytes, const int64_t *ke
     if (sign_out) HIP_TRY(hipMemcpyAsync(sign_out, ds.p, (size_t)J * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MORNA_OK;
+}
+
+// Lines bucketed by column on the handle's stream (col_scan + the stable counting sort above): col_off[D + 1] from the
+// per-column counts, col_lines[J] the lines of every column in file order.  line_rank[J], chunk_cnt[ceil(J / CR_LINES) * D]:
+// scratch.
+static void bucket_lines(morna_index *h, const int32_t *col, int64_t J, int32_t D, const int32_t *col_count, int32_t *line_rank,
+                         int32_t *chunk_cnt, int32_t *col_off, int32_t *col_lines)
+{
+    hipLaunchKernelGGL(col_scan_kernel, dim3(1), dim3(1024), 0, h->stream, col_count, D, col_off);
+    if (J > 0) {
+        const int32_t n_chunks = (int32_t)((J + CR_LINES - 1) / CR_LINES);
+        hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)n_chunks * D + 255) / 256, 2048)), dim3(256), 0,
+                           h->stream, chunk_cnt, (int64_t)n_chunks * D);
+        hipLaunchKernelGGL(col_rank_kernel, dim3((unsigned)n_chunks), dim3(CR_LINES), 0, h->stream, col, J, n_chunks,
+                           line_rank, chunk_cnt);
+        hipLaunchKernelGGL(col_base_kernel, dim3((unsigned)((D + 256 / WAVE - 1) / (256 / WAVE))), dim3(256), 0, h->stream,
+                           chunk_cnt, n_chunks, (int32_t)D);
+        hipLaunchKernelGGL(col_place_kernel, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, h->stream, col, J, n_chunks,
+                           line_rank, chunk_cnt, col_off, col_lines);
+    }
 }
 
 int build_features(morna_index *h, int64_t n_items)
@@ -946,18 +1034,7 @@ int build_features(morna_index *h, int64_t n_items)
             }
             HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
         }
-        hipLaunchKernelGGL(col_scan_kernel, dim3(1), dim3(1024), 0, h->stream, col_count.p, D, col_off.p);
-        if (J > 0) {
-            const int32_t n_chunks = (int32_t)((J + CR_LINES - 1) / CR_LINES);
-            hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)n_chunks * D + 255) / 256, 2048)), dim3(256), 0,
-                               h->stream, chunk_cnt, (int64_t)n_chunks * D);
-            hipLaunchKernelGGL(col_rank_kernel, dim3((unsigned)n_chunks), dim3(CR_LINES), 0, h->stream, col.p, J, n_chunks,
-                               line_rank, chunk_cnt);
-            hipLaunchKernelGGL(col_base_kernel, dim3((unsigned)((D + 256 / WAVE - 1) / (256 / WAVE))), dim3(256), 0, h->stream,
-                               chunk_cnt, n_chunks, (int32_t)D);
-            hipLaunchKernelGGL(col_place_kernel, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, h->stream, col.p, J, n_chunks,
-                               line_rank, chunk_cnt, col_off.p, col_lines.p);
-        }
+        bucket_lines(h, col.p, J, D, col_count.p, line_rank, chunk_cnt, col_off.p, col_lines.p);
         if (J > 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         if (by_order) {
             hipLaunchKernelGGL(accumulate_piece_kernel<AW_TILE>, dim3((unsigned)D * (unsigned)aw_tiles), dim3(AW_THREADS), 0, h->stream, aw_tiles,
@@ -1006,6 +1083,104 @@ int build_features(morna_index *h, int64_t n_items)
     // whatever the caller does next with the handle (build, queries, get_items) is ordered behind it or synchronises
     // itself -- a forest build that follows starts without the device draining first.  Blocking copies settle() first.
     h->unsettled = true;
+    return MORNA_OK;
+}
+
+int build_query_rows(morna_index *h, const uint8_t *key_bytes, const int64_t *key_off, int64_t J, const int64_t *row_ptr,
+                     const int32_t *ids, const int32_t *cov, const double *w, int64_t nq)
+{
+    MORNA_TRY(settle(h));
+    if (J < 0 || nq < 0 || (J > 0 && (!key_bytes || !key_off || !row_ptr || !ids || !cov || !w))) {
+        set_error("build_query_rows: null input");
+        return MORNA_E_INVALID;
+    }
+    if (J >= INT32_MAX || nq >= INT32_MAX) {
+        set_error("build_query_rows: %lld lines / %lld query samples exceed the 2^31 limit", (long long)J, (long long)nq);
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    QueryRows &Q = h->qrows;
+    Q.valid = false;
+    Q.nq = 0;
+    // what the kernels index with is checked here: offsets, ids inside [0, nq), no sample twice in a line (the accumulation
+    // gives the lanes of a line distinct cells)
+    const int64_t nbytes = J ? key_off[J] : 0, nnz = J ? row_ptr[J] : 0;
+    if (J && (key_off[0] != 0 || row_ptr[0] != 0)) {
+        set_error("build_query_rows: offsets must start at 0");
+        return MORNA_E_INVALID;
+    }
+    try {
+        std::vector<int64_t> stamp((size_t)nq, -1);
+        for (int64_t j = 0; j < J; j++) {
+            if (key_off[j + 1] < key_off[j] || row_ptr[j + 1] < row_ptr[j]) {
+                set_error("build_query_rows: offsets must be non-decreasing (line %lld)", (long long)j);
+                return MORNA_E_INVALID;
+            }
+            for (int64_t t = row_ptr[j]; t < row_ptr[j + 1]; t++) {
+                if (ids[t] < 0 || ids[t] >= nq) {
+                    set_error("build_query_rows: query id %d out of range [0, %lld)", ids[t], (long long)nq);
+                    return MORNA_E_RANGE;
+                }
+                if (stamp[(size_t)ids[t]] == j) {
+                    set_error("build_query_rows: query %d repeats in line %lld (the lines must come from morna_lines_query_terms)",
+                              ids[t], (long long)j);
+                    return MORNA_E_INVALID;
+                }
+                stamp[(size_t)ids[t]] = j;
+            }
+        }
+    } catch (const std::exception &e) {
+        set_error("build_query_rows: %s", e.what());
+        return MORNA_E_INVALID;
+    }
+    if (nq == 0) {
+        Q.valid = true;
+        return MORNA_OK;
+    }
+    const int32_t D = h->dim;
+    MORNA_TRY(Q.keys.alloc((size_t)nbytes));
+    MORNA_TRY(Q.key_off.alloc((size_t)J + 1));
+    MORNA_TRY(Q.row_ptr.alloc((size_t)J + 1));
+    MORNA_TRY(Q.ids.alloc((size_t)nnz));
+    MORNA_TRY(Q.cov.alloc((size_t)nnz));
+    MORNA_TRY(Q.w.alloc((size_t)J));
+    MORNA_TRY(Q.col.alloc((size_t)J));
+    MORNA_TRY(Q.sidf.alloc((size_t)J));
+    MORNA_TRY(Q.col_count.alloc((size_t)D));
+    MORNA_TRY(Q.col_off.alloc((size_t)D + 1));
+    MORNA_TRY(Q.col_lines.alloc((size_t)J));
+    const int64_t n_line_chunks = (J + CR_LINES - 1) / CR_LINES;
+    MORNA_TRY(Q.bucket_aux.alloc((size_t)J + (size_t)n_line_chunks * (size_t)D));
+    MORNA_TRY(Q.colacc.alloc((size_t)D * (size_t)nq));
+    MORNA_TRY(Q.rows64.alloc((size_t)nq * D));
+    MORNA_TRY(Q.rows32.alloc((size_t)nq * h->dpad));
+    if (J > 0) {
+        HIP_TRY(hipMemcpyAsync(Q.keys.p, key_bytes, (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(Q.key_off.p, key_off, (size_t)(J + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(Q.row_ptr.p, row_ptr, (size_t)(J + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(Q.ids.p, ids, (size_t)nnz * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(Q.cov.p, cov, (size_t)nnz * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(Q.w.p, w, (size_t)J * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    {
+        // algorithmic bytes: the nnz stream, keys and line records once, the fp64 cells written, read and written as rows
+        ScopedTimer tm(h, MORNA_T_FEATURES, 8 * nnz + nbytes + 8 * J + 8 * nq * (int64_t)D * 3 + 4 * nq * (int64_t)h->dpad);
+        hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream, Q.col_count.p, (int64_t)D);
+        if (J > 0)
+            hipLaunchKernelGGL(hash_keys_kernel, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, h->stream, Q.keys.p, Q.key_off.p, J, D,
+                               Q.w.p, Q.col.p, Q.sidf.p, (int32_t *)nullptr, (int32_t *)nullptr, Q.col_count.p);
+        bucket_lines(h, Q.col.p, J, D, Q.col_count.p, Q.bucket_aux.p, Q.bucket_aux.p + J, Q.col_off.p, Q.col_lines.p);
+        const int64_t tiles = (nq + QA_TILE - 1) / QA_TILE;
+        hipLaunchKernelGGL(query_accumulate_kernel, dim3((unsigned)(tiles * D)), dim3(QA_THREADS), 0, h->stream, (int32_t)tiles, D,
+                           Q.col_off.p, Q.col_lines.p, Q.sidf.p, Q.row_ptr.p, Q.ids.p, Q.cov.p, nq, Q.colacc.p);
+        dim3 tg((unsigned)((nq + TT - 1) / TT), (unsigned)(h->dpad / TT));
+        hipLaunchKernelGGL(query_rows_transpose_kernel, tg, dim3(256), 0, h->stream, Q.colacc.p, nq, D, h->dpad, Q.rows64.p, Q.rows32.p);
+        HIP_TRY(hipGetLastError());
+    }
+    // the staged lines were copied out of the caller's memory: wait, so that nothing the caller frees is still read
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    Q.nq = nq;
+    Q.valid = true;
     return MORNA_OK;
 }
 

@@ -1952,11 +1952,13 @@ static int launch_exact_scan(morna_index *h, int64_t N, int64_t nb, const float 
 size_t exact_msg_dist_offset(int64_t nq, int32_t k) { return align_up((size_t)nq * ((size_t)k + 1) * 4, 8); }
 size_t exact_msg_bytes(int64_t nq, int32_t k) { return exact_msg_dist_offset(nq, k) + (size_t)nq * k * 8; }
 
-// The queries: q_host fp64 [nq][dim] (host), or q_dev fp32 [nq][dim] (this device's memory), or stored rows items_host.
+// The queries: q_host fp64 [nq][dim] (host), or q_dev fp32 [nq][dim] (this device's memory), or q_dev64 fp64 [nq][dim] (this
+// device's memory: the query rows of morna_build_query_rows, finite by construction), or stored rows items_host.
 // The answers: host arrays, and / or msg_dev (device memory, exact_msg_bytes(nq, k)) with global ids = local + id_offset --
 // then only enqueued on the handle's stream behind the last selection.
 int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
-                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset)
+                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
+                     const double *q_dev64)
 {
     MORNA_TRY(upload_host_rows(h));
     if (h->n_items <= 0) {
@@ -2024,6 +2026,8 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
             HIP_TRY(hipMemcpyAsync(Qd, q_host + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
         } else if (q_dev) {
             hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, q_dev + q0 * D, (int64_t)D, nullptr, D, Qd);
+        } else if (q_dev64) {
+            HIP_TRY(hipMemcpyAsync(Qd, q_dev64 + q0 * D, (size_t)nb * D * 8, hipMemcpyDeviceToDevice, h->stream));
         } else {
             HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
             hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, d_items, D, Qd);

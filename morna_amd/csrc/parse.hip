@@ -897,6 +897,128 @@ int morna_lines_from_arrays(const uint8_t *key_bytes, const int64_t *key_off, in
     return MORNA_OK;
 }
 
+// ---- query terms of a parsed QUERY file against an index's vocabulary (no counterpart in the reference's batch form) ----
+// What MornaSearch builds for one query sample s (morna.py:597-629, the raw-stream loop of morna.py:1383-1472): every line
+// listing s fed in file order as (chrom, start, end, coverage of s), kept when its key is in the index's frequency table,
+// the coverages summed per key in a dict whose insertion order is the order of the FIRST line holding both the key and s.
+// Here: the lines of L whose key is in the vocabulary, in file order, each (key, sample) entry on the first line that holds
+// it with its summed coverage -- so no sample repeats in a line and a cell (sample, column) receives its terms in the dict's
+// order when the lines are walked in file order.  Lines left without an entry are dropped (they touch no cell).  idf of a
+// kept line = the key's weight log(sample_count / df) from libm (0 when df is 0), as finalize_query computes it.
+// Only keys on more than one line, and lines that repeat a sample, need the merge table; every other line is copied.
+int morna_lines_query_terms(const morna_lines *L, const uint8_t *vocab_bytes, const int64_t *vocab_off, const int64_t *vocab_df,
+                            int64_t V, int64_t sample_count, morna_lines **out)
+{
+    if (!L || !out || V < 0 || (V > 0 && (!vocab_bytes || !vocab_off || !vocab_df))) {
+        set_error("lines_query_terms: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    if (sample_count <= 0) {
+        set_error("lines_query_terms: the index's sample count must be positive (got %lld)", (long long)sample_count);
+        return MORNA_E_INVALID;
+    }
+    if (L->shard_world != 1) {
+        set_error("lines_query_terms: the lines are a row shard (pass the whole parse)");
+        return MORNA_E_STATE;
+    }
+    try {
+        std::unordered_map<std::string, int64_t> vocab;   // key -> index into vocab_df
+        vocab.reserve((size_t)V * 2);
+        for (int64_t v = 0; v < V; v++) {
+            if (vocab_off[v + 1] < vocab_off[v] || vocab_df[v] < 0) {
+                set_error("lines_query_terms: vocabulary entry %lld is malformed (offsets or a negative frequency)", (long long)v);
+                return MORNA_E_INVALID;
+            }
+            if (!vocab.emplace(std::string((const char *)vocab_bytes + vocab_off[v], (size_t)(vocab_off[v + 1] - vocab_off[v])), v).second) {
+                set_error("lines_query_terms: vocabulary entry %lld repeats a key", (long long)v);
+                return MORNA_E_INVALID;
+            }
+        }
+        const int64_t J = (int64_t)L->idf.size(), n_items = (int64_t)L->ext_ids.size();
+        // pass 1: the vocabulary entry of every line (-1: not in it) and the lines per entry
+        std::vector<int64_t> kid((size_t)J, -1);
+        std::unordered_map<int64_t, int32_t> lines_of;   // only entries that occur: the vocabulary may be far larger
+        std::string key;
+        for (int64_t j = 0; j < J; j++) {
+            key.assign((const char *)L->key_bytes.data() + L->key_off[(size_t)j], (size_t)(L->key_off[(size_t)j + 1] - L->key_off[(size_t)j]));
+            auto it = vocab.find(key);
+            if (it == vocab.end()) continue;
+            kid[(size_t)j] = it->second;
+            lines_of[it->second]++;
+        }
+        std::unique_ptr<morna_lines> T(new morna_lines());
+        std::vector<int64_t> sum;                            // coverage sums, beside T->item_ids
+        std::vector<int64_t> stamp((size_t)n_items, -1);     // last line that listed a sample
+        std::unordered_map<uint64_t, int64_t> first;         // (entry, sample) -> its position in T, for the merged lines
+        for (int64_t j = 0; j < J; j++) {
+            const int64_t k = kid[(size_t)j];
+            if (k < 0) continue;
+            const int64_t b = L->row_ptr[(size_t)j], e = L->row_ptr[(size_t)j + 1];
+            bool repeats = false;
+            for (int64_t t = b; t < e; t++) {
+                int64_t &st = stamp[(size_t)L->item_ids[(size_t)t]];
+                repeats |= st == j;
+                st = j;
+            }
+            const int64_t at0 = (int64_t)T->item_ids.size();
+            if (!repeats && lines_of[k] == 1) {              // the common case: the line as it is
+                T->item_ids.insert(T->item_ids.end(), L->item_ids.begin() + b, L->item_ids.begin() + e);
+                for (int64_t t = b; t < e; t++) sum.push_back(L->cov[(size_t)t]);
+            } else {
+                for (int64_t t = b; t < e; t++) {
+                    const int32_t s = L->item_ids[(size_t)t];
+                    auto ins = first.emplace(((uint64_t)k << 32) | (uint32_t)s, (int64_t)T->item_ids.size());
+                    if (ins.second) {
+                        T->item_ids.push_back(s);
+                        sum.push_back(L->cov[(size_t)t]);
+                    } else {
+                        sum[(size_t)ins.first->second] += L->cov[(size_t)t];
+                    }
+                }
+            }
+            if ((int64_t)T->item_ids.size() == at0) continue;   // every entry belongs to an earlier line
+            T->key_bytes.insert(T->key_bytes.end(), L->key_bytes.begin() + L->key_off[(size_t)j], L->key_bytes.begin() + L->key_off[(size_t)j + 1]);
+            T->key_off.push_back((int64_t)T->key_bytes.size());
+            T->row_ptr.push_back((int64_t)T->item_ids.size());
+            const int64_t df = vocab_df[k];
+            T->idf.push_back(df ? log((double)sample_count / (double)df) : 0.0);   // search.py finalize_query, morna.py:625
+        }
+        // the summed coverages are staged as int32 (the reference keeps Python ints): refuse what does not fit
+        T->cov.resize(sum.size());
+        for (int64_t j = 0; j < (int64_t)T->idf.size(); j++)
+            for (int64_t t = T->row_ptr[(size_t)j]; t < T->row_ptr[(size_t)j + 1]; t++) {
+                if (sum[(size_t)t] > INT32_MAX || sum[(size_t)t] < INT32_MIN) {
+                    const std::string k((const char *)T->key_bytes.data() + T->key_off[(size_t)j],
+                                        (size_t)(T->key_off[(size_t)j + 1] - T->key_off[(size_t)j]));
+                    set_error("lines_query_terms: the coverage of sample %lld at junction '%s' sums to %lld, which does not fit 32 bits",
+                              (long long)L->ext_ids[(size_t)T->item_ids[(size_t)t]], k.c_str(), (long long)sum[(size_t)t]);
+                    return MORNA_E_INVALID;
+                }
+                T->cov[(size_t)t] = (int32_t)sum[(size_t)t];
+            }
+        T->ext_ids = L->ext_ids;
+        T->sample_count = sample_count;
+        T->lines_read = L->lines_read;
+        *out = T.release();
+    } catch (const std::exception &e) {
+        set_error("lines_query_terms: %s", e.what());
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+// rows of the query samples of T (morna_lines_query_terms) on the GPU, beside the index (features.hip)
+int morna_build_query_rows(morna_index *h, const morna_lines *T)
+{
+    if (!h || !T) {
+        set_error("build_query_rows: null argument");
+        return MORNA_E_INVALID;
+    }
+    return morna::build_query_rows(h, T->key_bytes.data(), T->key_off.data(), (int64_t)T->idf.size(), T->row_ptr.data(),
+                                   T->item_ids.data(), T->cov.data(), T->idf.data(), (int64_t)T->ext_ids.size());
+}
+
 int morna_stage_lines(morna_index *h, const morna_lines *L)
 {
     if (!h || !L) {

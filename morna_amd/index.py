@@ -286,6 +286,27 @@ class ParsedLines(object):
         from ._lib import check, lib
         check(lib().morna_stage_lines(index._h, self._p))
 
+    def query_terms(self, vocab, sample_count):
+        """The lines of a parsed QUERY file against an index's vocabulary (morna_lines_query_terms): the lines whose key
+        is in it, each (key, sample) entry on the first line that holds it with its summed coverage, idf = the key's
+        weight.  vocab: (key_bytes, key_off, df) as pack_vocab gives them; sample_count: the index's."""
+        import ctypes as C
+        from ._lib import check, lib, ptr
+        key_bytes, key_off, df = vocab
+        p = C.c_void_p()
+        check(lib().morna_lines_query_terms(self._p, ptr(key_bytes), ptr(key_off), ptr(df), len(df), int(sample_count),
+                                            C.byref(p)))
+        return ParsedLines(None, _ptr=p)
+
+
+def pack_vocab(frequencies):
+    """junction -> frequency dict (.freq.mor) as the arrays morna_lines_query_terms takes: key bytes, offsets, frequencies."""
+    keys = [k.encode("utf-8") for k in frequencies]
+    key_off = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum([len(k) for k in keys], out=key_off[1:])
+    key_bytes = np.frombuffer(b"".join(keys), np.uint8) if keys else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(key_bytes), key_off, np.array(list(frequencies.values()), np.int64)
+
 
 def shard_bounds(n_items, world):
     """Global id range of every row shard: rank g owns [g * ceil(N / G), (g + 1) * ceil(N / G))."""

@@ -9,6 +9,13 @@ the searches run in libmorna_hip.so.
 
 `meta_db=True` appends the keywords of `<basename>.meta.mor` to the results
 (morna.py:666-676; metadb.py).
+
+Batch form (no counterpart in the reference, which answers one query sample per
+process): `queries_from_intropolis` featurises every sample of an intropolis file
+against the index's vocabulary -- a native pre-pass, then the rows on the GPU --
+and `search_nn_batch` / `exact_search_nn_batch` answer all of them in one call,
+each exactly as `update_query` over that sample's lines, `finalize_query` and
+`search_nn` / `exact_search_nn` would.
 """
 import os
 import pickle
@@ -31,6 +38,19 @@ def results_output(results, out=None):
         for lst in results:
             out.write("\t" + str(lst[i]))
         out.write("\n")
+
+
+class QueryBatch(object):
+    """The query samples of an intropolis file featurised against an index (MornaSearch.queries_from_intropolis):
+    ext_ids[q] is the sample id of query q (first appearance in the file), n the number of queries.  The rows live on
+    the index's handle (a later queries_from_intropolis replaces them); rows64 / rows32 are host copies for an index of
+    row shards, which searches from host memory."""
+
+    def __init__(self, owner, generation, ext_ids, rows64=None, rows32=None):
+        self.owner, self.generation = owner, generation
+        self.ext_ids = [int(x) for x in ext_ids]
+        self.n = len(self.ext_ids)
+        self.rows64, self.rows32 = rows64, rows32
 
 
 class MornaSearch(object):
@@ -120,6 +140,109 @@ class MornaSearch(object):
         if include_distances:
             results += ([float(x) for x in d[0, :m]],)
         return self._with_meta(results, meta_db)
+
+    # ---- many query samples at once ---------------------------------------------------------------------------
+    def _vocab(self):
+        """The frequency table as the arrays of the native pre-pass, made once."""
+        if getattr(self, "_vocab_arrays", None) is None:
+            from .index import pack_vocab
+            self._vocab_arrays = pack_vocab(self.sample_frequencies)
+        return self._vocab_arrays
+
+    def queries_from_intropolis(self, path):
+        """Every sample of the (gzipped) intropolis file `path` as a query: for sample s, the vector update_query over
+        the lines that list s (key "chrom start end" in the index's frequency table, coverage of s) and finalize_query
+        would make -- built on the GPU.  Coordinates are compared as written (intropolis writes canonical decimals,
+        what the raw stream's int() gives).  Returns a QueryBatch."""
+        from .index import ParsedLines
+        from .shards import DistShards, LocalShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if self.sample_count <= 0:
+            raise ValueError("the index's sample count must be positive (got %d)" % self.sample_count)
+        parsed = ParsedLines(path, sample_count=self.sample_count, sample_threshold=0)
+        terms = parsed.query_terms(self._vocab(), self.sample_count)
+        ext_ids = terms.arrays()["ext_ids"].tolist()
+        self._batch_generation = getattr(self, "_batch_generation", 0) + 1
+        if isinstance(self.annoy_index, LocalShards):
+            # the rows are built on shard 0's device and searched from the host by every shard
+            handle = self.annoy_index.shards[0]
+            handle.build_query_rows(terms)
+            rows64, rows32 = handle.get_query_rows()
+            return QueryBatch(self, self._batch_generation, ext_ids, rows64, rows32)
+        self.annoy_index.build_query_rows(terms)
+        return QueryBatch(self, self._batch_generation, ext_ids)
+
+    def _check_batch(self, batch):
+        if batch.owner is not self or batch.generation != getattr(self, "_batch_generation", 0):
+            raise ValueError("the rows of this query batch were replaced by a later queries_from_intropolis call")
+
+    def _inverse_map(self):
+        """internal id -> external sample id, made once (inverse_lookup's contract: a second owner is an error)."""
+        if getattr(self, "_inverse", None) is None:
+            inv = {}
+            for sample_id, internal_id in self.internal_id_map.items():
+                if internal_id in inv:
+                    raise RuntimeError(str(internal_id) + " does not have unique mapping in self.internal_id_map.")
+                inv[internal_id] = sample_id
+            self._inverse = inv
+        return self._inverse
+
+    def _batch_results(self, ids, d, cnt, include_distances, meta_db):
+        """One result per query, shaped as search_nn / exact_search_nn return it; for an exact query the reference raises
+        on (count -1), a ValueError instance."""
+        inv = self._inverse_map() if meta_db else None
+        out = []
+        for q in range(len(cnt)):
+            m = int(cnt[q])
+            if m < 0:
+                out.append(ValueError("math domain error"))
+                continue
+            results = ([int(x) for x in ids[q, :m]],)
+            if include_distances:
+                results += ([float(x) for x in d[q, :m]],)
+            if meta_db:
+                results += (lookup_meta(self.basename, [inv.get(i) for i in results[0]]),)
+            out.append(results)
+        return out
+
+    def search_nn_batch(self, batch, num_neighbors, search_k, include_distances=True, meta_db=False):
+        """search_nn for every query of `batch`: a list of result tuples, in query order."""
+        self._check_batch(batch)
+        if batch.rows32 is not None:
+            ids, d, cnt = self.annoy_index.get_nns_by_vector_batch(batch.rows32, num_neighbors, search_k)
+        else:
+            ids, d, cnt = self.annoy_index.get_nns_by_query_rows(num_neighbors, search_k)
+        return self._batch_results(ids, d, cnt, include_distances, meta_db)
+
+    def exact_search_nn_batch(self, batch, num_neighbors, include_distances=True, meta_db=False):
+        """exact_search_nn for every query of `batch`: a list of result tuples, in query order; a query the reference
+        would raise on gets a ValueError instance in its slot."""
+        self._check_batch(batch)
+        if batch.rows64 is not None:
+            ids, d, cnt = self.annoy_index.exact_search_batch(batch.rows64, num_neighbors)
+        else:
+            ids, d, cnt = self.annoy_index.exact_search_query_rows(num_neighbors)
+        return self._batch_results(ids, d, cnt, include_distances, meta_db)
+
+    def search_member_n_batch(self, query_ids, num_neighbors, search_k, include_distances=True, meta_db=False):
+        """search_member_n for several indexed sample ids, searched together (get_nns_by_item_batch); an unknown id fails
+        before any search, with search_member_n's message.  Returns (internal ids, list of result tuples)."""
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        internal = []
+        for query_id in query_ids:
+            if query_id not in self.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+            internal.append(self.internal_id_map[query_id])
+        ids, d, cnt = self.annoy_index.get_nns_by_item_batch(np.array(internal, np.int32), num_neighbors, search_k)
+        return internal, self._batch_results(ids, d, cnt, include_distances, meta_db)
 
     def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False):
         """Neighbours of an indexed sample (morna.py:733-787)."""

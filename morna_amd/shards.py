@@ -131,6 +131,17 @@ class LocalShards(object):
         out = [int(x) for x in ids[0, :m]]
         return (out, [float(x) for x in d[0, :m]]) if include_distances else out
 
+    def get_nns_by_item_batch(self, items, n, search_k=-1):
+        """get_nns_by_item for several global items: their stored rows, fetched from their owners, as the queries."""
+        items = np.asarray(items, np.int64)
+        rows = np.empty((len(items), self.f), np.float32)
+        owner = [self._owner(int(i)) for i in items]
+        for g, shard in enumerate(self.shards):
+            at = [q for q, (o, _) in enumerate(owner) if o == g]
+            if at:
+                rows[at] = shard.get_item_vectors(np.array([owner[q][1] for q in at], np.int32))
+        return self.get_nns_by_vector_batch(rows, n, search_k)
+
     def exact_search_batch(self, Q, n):
         per = [s.exact_search_batch(Q, n) for s in self.shards]
         ids, d, cnt = merge_topk_exact(np.stack([self._global(g, p[0]) for g, p in enumerate(per)]),

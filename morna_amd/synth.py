@@ -79,3 +79,39 @@ def query_items(n_items, nq, seed=QUERY_SEED):
     (mirrors the reference's tests/all_gtex_pancreas_nns.bash:19)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.choice(n_items, size=min(nq, n_items), replace=False).astype(np.int32)
+
+
+def index_and_query_files(index_path, query_path, n_index, n_queries, J=200_000, seed=SEED, query_seed=QUERY_SEED):
+    """One synthetic data set (synthetic_intropolis over n_index + n_queries samples) cut into an intropolis file to index
+    and one of new query samples: the same junction keys, disjoint samples (n_queries of them, drawn with query_seed,
+    spread over the clusters).  Lines left without a sample are not written.  ".gz" paths are gzipped; index_path None:
+    only the query file is written.  Returns dict(index_ids, query_ids) -- the external sample ids in each file,
+    ascending -- and index: the index file's lines as synthetic_intropolis returns them (keys, row_ptr, samples, cov,
+    sample_count = its number of samples)."""
+    import ctypes as C
+    from ._lib import check, lib
+    data = synthetic_intropolis(n_index + n_queries, J=J, seed=seed)
+    rng = np.random.Generator(np.random.PCG64(query_seed))
+    query_ids = np.sort(rng.choice(np.arange(1, n_index + n_queries + 1), size=n_queries, replace=False)).astype(np.int64)
+    keys = [k.encode("ascii") for k in data["keys"]]
+    key_len = np.array([len(k) for k in keys], np.int64)
+    line_of = np.repeat(np.arange(len(keys)), np.diff(data["row_ptr"]))
+    is_query = np.isin(data["samples"], query_ids)
+    index = None
+    for path, keep in ((index_path, ~is_query), (query_path, is_query)):
+        counts = np.bincount(line_of[keep], minlength=len(keys))
+        lines = np.nonzero(counts)[0]
+        row_ptr = np.concatenate([[0], np.cumsum(counts[lines])]).astype(np.int64)
+        samples = np.ascontiguousarray(data["samples"][keep], np.int64)
+        cov = np.ascontiguousarray(data["cov"][keep], np.int32)
+        if index is None:
+            index = dict(keys=[data["keys"][j] for j in lines.tolist()], row_ptr=row_ptr, samples=samples, cov=cov,
+                         sample_count=int(n_index))
+        if path is None:
+            continue
+        key_off = np.concatenate([[0], np.cumsum(key_len[lines])]).astype(np.int64)
+        key_bytes = np.frombuffer(b"".join(keys[j] for j in lines.tolist()), np.uint8)
+        p = [a.ctypes.data_as(C.c_void_p) for a in (key_bytes, key_off, row_ptr, samples, cov)]
+        check(lib().morna_write_intropolis(str(path).encode(), p[0], p[1], len(lines), p[2], p[3], p[4]))
+    index_ids = np.setdiff1d(np.arange(1, n_index + n_queries + 1), query_ids)
+    return dict(index_ids=index_ids, query_ids=query_ids, index=index)
