@@ -166,6 +166,64 @@ int morna_get_query_rows(morna_index *h, double *rows64, float *rows32);
 int morna_get_nns_by_query_rows(morna_index *h, int32_t k, int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out);
 int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out);
 
+/*
+ * ---- junctions by sample: the store and the filter of `morna junctions` ---------------------------------------------
+ * Stand-ins for update_junction_dbs and the per-sample sqlite tables (morna.py:221-341: 100 shards of run-length strings)
+ * and for the retention step of the junctions subcommand (morna.py:1501-1569).  The store is the transpose of the
+ * junction x sample CSR of a parse: for every sample id of ANY line of the file (update_junction_dbs runs before the
+ * threshold test, morna.py:359 vs 361-363) the ascending list of (0-based line number, coverage) (morna.py:215, 357, 1591).
+ * A store is one object on one device; one host thread per store.  Limits: 2^31 - 1 lines and samples.
+ *   morna_jstore_build        morna.py:221-341 for a whole file: the transpose on the GPU from a parse with threshold 0
+ *                             (MORNA_E_INVALID when the lines kept are not the lines read: kept line j must be file line j).
+ *                             Deterministic: a stable counting sort without global atomics, the same bytes on every run, a
+ *                             sample's lines ascending whatever order a line lists its samples in.  A line that lists a
+ *                             sample twice is MORNA_E_INVALID naming the line and the sample.  The store is resident in
+ *                             HBM and mirrored on the host (what save writes).
+ *   morna_jstore_from_arrays  a store from the caller's arrays: ext_ids[n_samples], ptr[n_samples + 1], line / cov
+ *                             [ptr[n_samples]].  Validated as load validates (MORNA_E_INVALID).  No GPU work: the arrays
+ *                             go to `device` at the first retain.
+ *   morna_jstore_save / load  one little-endian blob, <basename>.junc.mor (stands in for the files of morna.py:221-260,
+ *                             read back at 1505-1533).  Load checks that ptr is monotone and ends at the entry count, that
+ *                             every sample's lines ascend and lie below n_lines, and that the sample ids are distinct:
+ *                             MORNA_E_IO for a missing, truncated or inconsistent file.  No GPU work (as from_arrays).
+ *   morna_jstore_counts       counts[3] = samples, entries, lines of the file
+ *   morna_jstore_samples      ext_ids_out[samples]: the sample ids, the parse's first-seen order
+ *   morna_jstore_sample       one sample's list (the SELECT of morna.py:1516-1532): *n_out entries; line_out / cov_out
+ *                             (either may be NULL) must hold that many.  MORNA_E_RANGE for an id the store lacks.
+ *   morna_jstore_retain       morna.py:1539-1569 for nq result lists at once, on the GPU.  results[nq][k]: EXTERNAL sample
+ *                             ids in rank order (morna.py:1501-1504), the first n_results[q] of a row used; min_count[q]:
+ *                             int(ceil(frequency_filter * n_results[q])), computed by the caller (morna.py:1551, so that the
+ *                             rounding is Python's).  A line is retained when at least one and at least min_count of the
+ *                             results hold it, or when one of them covers it coverage_filter times or more.  1 <= k <= 64:
+ *                             found_in is one 64-bit word per line (MORNA_E_INVALID beyond, the message names the limit).
+ *                             An id the store lacks: MORNA_E_RANGE naming it.
+ *   morna_jretained_counts    count_out[nq]: retained lines of every list (len(retain_junctions), morna.py:1573)
+ *   morna_jretained_query     borrowed views of list q, valid until morna_jretained_free: lines[count] ascending
+ *                             (sorted(retain_junctions), morna.py:1585), masks[count] (bit r set: result r holds the line --
+ *                             found_in_map, morna.py:1555), cov_ptr[count + 1] and cov: the coverages of line i in rank
+ *                             order are cov[cov_ptr[i] .. cov_ptr[i + 1]) (new_covs, morna.py:1619-1623).  Any may be NULL.
+ *   morna_jstore_timers       ms[2] / bytes[2]: HIP-event time of the kernels of the build and of the last retain, and
+ *                             their algorithmic bytes (2 x 8 per entry; 8 per entry of the lists named)
+ */
+typedef struct morna_jstore morna_jstore;
+typedef struct morna_jretained morna_jretained;
+int morna_jstore_build(int32_t device, const morna_lines *all_lines, morna_jstore **out);
+int morna_jstore_from_arrays(int32_t device, const int64_t *ext_ids, int64_t n_samples, const int64_t *ptr, const int32_t *line,
+                             const int32_t *cov, int64_t n_lines, morna_jstore **out);
+int morna_jstore_save(const morna_jstore *s, const char *path);
+int morna_jstore_load(const char *path, int32_t device, morna_jstore **out);
+int morna_jstore_free(morna_jstore *s);
+int morna_jstore_counts(const morna_jstore *s, int64_t *counts);
+int morna_jstore_samples(const morna_jstore *s, int64_t *ext_ids_out);
+int morna_jstore_sample(const morna_jstore *s, int64_t ext_id, int64_t *n_out, int32_t *line_out, int32_t *cov_out);
+int morna_jstore_retain(morna_jstore *s, const int64_t *results, const int32_t *n_results, const int32_t *min_count, int64_t nq,
+                        int32_t k, int64_t coverage_filter, morna_jretained **out);
+int morna_jretained_counts(const morna_jretained *r, int64_t *count_out);
+int morna_jretained_query(const morna_jretained *r, int64_t q, const int32_t **lines, const uint64_t **masks,
+                          const int64_t **cov_ptr, const int32_t **cov);
+int morna_jretained_free(morna_jretained *r);
+int morna_jstore_timers(const morna_jstore *s, double *ms, int64_t *bytes);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

@@ -58,6 +58,19 @@ SIGNATURES = {
     "morna_get_query_rows": (C.c_int, [_p, _p, _p]),
     "morna_get_nns_by_query_rows": (C.c_int, [_p, _i32, _i32, _p, _p, _p]),
     "morna_exact_search_query_rows": (C.c_int, [_p, _i32, _p, _p, _p]),
+    "morna_jstore_build": (C.c_int, [_i32, _p, C.POINTER(_p)]),
+    "morna_jstore_from_arrays": (C.c_int, [_i32, _p, _i64, _p, _p, _p, _i64, C.POINTER(_p)]),
+    "morna_jstore_save": (C.c_int, [_p, C.c_char_p]),
+    "morna_jstore_load": (C.c_int, [C.c_char_p, _i32, C.POINTER(_p)]),
+    "morna_jstore_free": (C.c_int, [_p]),
+    "morna_jstore_counts": (C.c_int, [_p, _p]),
+    "morna_jstore_samples": (C.c_int, [_p, _p]),
+    "morna_jstore_sample": (C.c_int, [_p, _i64, C.POINTER(_i64), _p, _p]),
+    "morna_jstore_retain": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i64, C.POINTER(_p)]),
+    "morna_jretained_counts": (C.c_int, [_p, _p]),
+    "morna_jretained_query": (C.c_int, [_p, _i64] + [C.POINTER(_p)] * 4),
+    "morna_jretained_free": (C.c_int, [_p]),
+    "morna_jstore_timers": (C.c_int, [_p, _p, _p]),
     "morna_merge_topk": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_vector_packed": (C.c_int, [_p, _p, _i64, _i32, _i32, _i64, _p]),
     "morna_merge_topk_packed": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),

@@ -1,10 +1,20 @@
-"""`morna index` / `morna search` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
-morna.py:867-1054, 1338-1484): same subcommands, flag names, defaults and output
-format for the hot path, including the metadata join (-m) and the convergence
-back-off loop (-c / -ch, sam input only).  Not carried over:
-`junctions` and the junctions-by-sample shards (-b is accepted and ignored).
+morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
+format, including the metadata join (-m) and the convergence back-off loop
+(-c / -ch, sam input only, `search` only).
+
+`junctions` searches as `search` does and then pools the junctions of the results
+(morna.py:1486-1638): those found in at least a share of the result samples, or
+covered often enough in one of them, written as an intropolis-like splice file
+for the aligner's second pass.  The junctions-by-sample databases it reads are
+one file here, <basename>.junc.mor, written by `index --junction-store` (-b, the
+buffer size of the reference's sqlite writer, is accepted and ignored), and the
+filter runs on the GPU for all queries of a batch at once.  Differences from the
+reference, all deliberate: its debug prints (shard ids, list lengths) are not
+reproduced, an empty retained set writes an empty splice file (the reference
+dies in ordered_junctions.pop(0)), -i is optional, and -c is refused.
 
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
@@ -16,6 +26,9 @@ here do the latter.
     python -m morna_amd.cli search -x idx -q 1234 -d
     python -m morna_amd.cli search -x idx --intropolis new_samples.tsv.gz -e -d
     cat query.bed | python -m morna_amd.cli search -x idx -f bed --exact -d
+    python -m morna_amd.cli index --intropolis junctions.tsv.gz -x idx -s 9662 --junction-store
+    python -m morna_amd.cli junctions -x idx -p1 pass1.sam --junction-file junctions.tsv.gz -sf splices.txt
+    python -m morna_amd.cli junctions -x idx --intropolis new_samples.tsv.gz --junction-file junctions.tsv.gz -sf splices
 """
 import argparse
 import sys
@@ -82,7 +95,8 @@ def build_parser():
     index_parser.add_argument('-t', '--sample-threshold', metavar='<int>', type=int, required=False, default=100,
                               help='minimum number of samples in which a junction should appear')
     index_parser.add_argument('-b', '--buffer-size', metavar='<int>', type=int, required=False, default=1024,
-                              help='accepted for compatibility; the per-sample junction database is out of scope')
+                              help='accepted for compatibility and ignored: the junctions-by-sample store is written '
+                                   'in one piece (--junction-store)')
     index_parser.add_argument('-v', '--verbose', action='store_const', const=True, default=False, help='be talkative')
     index_parser.add_argument('-m', '--metafile', metavar='<file>', type=str, required=False, default=None,
                               help='path to metadata file with sample index in first column '
@@ -99,7 +113,29 @@ def build_parser():
                                    'forest file (one per GPU); global idf and internal ids, so the shards together are '
                                    'the index.  Under torchrun with WORLD_SIZE equal to --shards every rank builds its '
                                    'own shard on its own GPU; otherwise one process builds them one after the other')
+    index_parser.add_argument('--junction-store', action='store_const', const=True, default=False,
+                              help='also write <basename>.junc.mor, the junctions-by-sample store `morna junctions` reads '
+                                   '(a second parse of the file, every line kept, transposed on the GPU); without this '
+                                   'flag a store left by an earlier index of the same basename is removed')
     add_search_parameters(search_parser)
+    junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
+                                                               'results for a second alignment pass')
+    add_search_parameters(junctions_parser)                    # morna.py:1023
+    junctions_parser.add_argument('-i', '--index', metavar='<idx>', type=str, required=False, default=None,
+                                  help='accepted for compatibility and ignored (the aligner\'s index; morna.py:1025)')
+    junctions_parser.add_argument('-p1', '--pass1-sam', metavar='<sam>', type=str, required=False, default="pass1.sam",
+                                  help='first pass alignment file output by the aligner: the query, read in place of '
+                                       'stdin when no other query is named')
+    junctions_parser.add_argument('--junction-filter', type=str, required=False, default=".05,5",
+                                  help='two parts separated by a comma: retain the junctions found in at least {first part} '
+                                       'proportion of the result samples, or with at least {second part} coverage in any '
+                                       'one result sample')
+    junctions_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
+                                  help='path to the (gzipped) intropolis file the index was made from')
+    junctions_parser.add_argument('-sf', '--splicefile', type=str, metavar='<file>', required=True,
+                                  help='intropolis-like output file with the retained junctions and, as one more field, '
+                                       'the ranks of the results that hold each; a batch (--intropolis, --query-ids) '
+                                       'writes <file>.<sample id> per query')
     return parser
 
 
@@ -121,11 +157,25 @@ def _check_batch_flags(parser, args):
             parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
 
 
+def _check_junction_flags(parser, args):
+    """`junctions`: the filter's two parts, what the result limit allows, and the flags that make no sense here."""
+    from .junctions import parse_junction_filter
+    try:
+        args.junction_filter_parts = parse_junction_filter(args.junction_filter)
+    except ValueError:
+        parser.error("--junction-filter takes <proportion>,<coverage>, such as .05,5 (got %r)" % args.junction_filter)
+    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
+        if on:
+            parser.error("%s cannot be used with junctions" % flag)
+
+
 def main(argv=None, stdin=None, stdout=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.subparser_name == 'search':
+    if args.subparser_name in ('search', 'junctions'):
         _check_batch_flags(parser, args)
+    if args.subparser_name == 'junctions':
+        _check_junction_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -138,9 +188,10 @@ def main(argv=None, stdin=None, stdout=None):
             device = int(os.environ.get("LOCAL_RANK", "0")) % device_count()   # (fewer GPUs than ranks: the ranks share them)
         go_index(args.intropolis, args.basename, args.features, args.n_trees, args.sample_count,
                  args.sample_threshold, args.buffer_size, args.verbose, args.metafile, device=device,
-                 native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank)
+                 native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank,
+                 junction_store=args.junction_store)
         return 0
-    if args.subparser_name != 'search':
+    if args.subparser_name not in ('search', 'junctions'):
         build_parser().print_help()
         return 2
     from .search import MornaSearch, results_output
@@ -149,6 +200,18 @@ def main(argv=None, stdin=None, stdout=None):
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dist = None
+    junctions = args.subparser_name == 'junctions'
+    if junctions:
+        from .junctions import MAX_RESULTS, STORE_SUFFIX
+        if world > 1 and os.path.exists(args.basename + ".shards.mor"):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if args.results > MAX_RESULTS:
+            raise ValueError("-r %d: junctions takes at most %d results (found_in is one 64-bit word per junction)"
+                             % (args.results, MAX_RESULTS))
+        if not os.path.exists(args.basename + STORE_SUFFIX):
+            raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
+                          % (args.basename + STORE_SUFFIX))
     if world > 1 and os.path.exists(args.basename + ".shards.mor"):
         # torchrun with one process per shard: every rank runs this function with the same query (rank 0 reads the stream
         # and hands it over) and calls the same collectives; rank 0 prints
@@ -167,6 +230,8 @@ def main(argv=None, stdin=None, stdout=None):
     else:
         searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
     try:
+        if junctions:
+            return _junctions(args, searcher, stdin, stdout)
         return _search(args, searcher, stdin, stdout, dist, rank)
     finally:
         if dist is not None:
@@ -174,9 +239,36 @@ def main(argv=None, stdin=None, stdout=None):
             dist.destroy_process_group()
 
 
-def _search_batch(args, searcher, stdout):
+def _junctions(args, searcher, stdin, stdout):
+    """morna.py:1351-1353, 1486-1638: the search, printed as `search` prints it, then the junctions of every query's
+    results filtered on the GPU in one call and written in one pass over --junction-file."""
+    import sys
+    from .junctions import write_splice_files
+    batch = args.intropolis is not None or args.query_ids is not None
+    collected = []
+    if not batch and args.query_id is None:
+        args.format = "sam"                                    # morna.py:1352-1353
+        with open(args.pass1_sam) as sam:
+            rc = _search(args, searcher, sam, stdout, None, 0, collect=collected)
+    else:
+        rc = _search(args, searcher, stdin, stdout, None, 0, collect=collected)
+    frequency_filter, coverage_filter = args.junction_filter_parts
+    retained = searcher.retain_junctions([res[0] for _, res in collected], frequency_filter, coverage_filter)
+    jobs = []
+    for (label, res), kept in zip(collected, retained):
+        stdout.write("Number of retained junctions: " + str(len(kept)) + "\n")      # morna.py:1573
+        sys.stderr.write(str(len(kept)) + " junctions to begin with\n")             # morna.py:1586
+        path = args.splicefile + "." + str(label) if batch else args.splicefile
+        jobs.append((path, kept, searcher.result_sample_ids(res[0])))
+    sys.stderr.flush()
+    write_splice_files(args.junction_file, jobs)
+    return rc
+
+
+def _search_batch(args, searcher, stdout, collect=None):
     """--intropolis / --query-ids: one block per query, in query order; 1 when some exact query failed as the
-    reference's would (math domain error), after all blocks."""
+    reference's would (math domain error), after all blocks.  collect: a list that receives (sample id, results) of
+    every answered query."""
     from .search import results_output
     if args.query_ids is not None:
         internal, results = searcher.search_member_n_batch(args.query_ids, args.results, args.search_k,
@@ -186,6 +278,8 @@ def _search_batch(args, searcher, stdout):
             stdout.write("querying by sample id " + str(query_id) + "\n")      # search_member_n's two lines
             stdout.write("this is internal id " + str(internal_id) + "\n")
             results_output(res, stdout)
+            if collect is not None:
+                collect.append((query_id, res))
         return 0
     batch = searcher.queries_from_intropolis(args.intropolis)
     if args.exact:
@@ -201,14 +295,17 @@ def _search_batch(args, searcher, stdout):
             failed = True
         else:
             results_output(res, stdout)
+            if collect is not None:
+                collect.append((sample_id, res))
     return 1 if failed else 0
 
 
-def _search(args, searcher, stdin, stdout, dist, rank):
+def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
+    """collect: a list that receives (label, results) of every query answered (`junctions` goes on from there)."""
     from .search import results_output
     from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
     if args.intropolis is not None or args.query_ids is not None:
-        return _search_batch(args, searcher, stdout)
+        return _search_batch(args, searcher, stdout, collect)
     if args.query_id is not None:                              # morna.py:1358-1365
         if dist is not None and rank != 0:
             import contextlib
@@ -219,6 +316,8 @@ def _search(args, searcher, stdin, stdout, dist, rank):
             results = searcher.search_member_n(args.query_id, args.results, args.search_k,
                                                include_distances=args.distances, meta_db=args.metadata)
         results_output(results, stdout)
+        if collect is not None:
+            collect.append((args.query_id, results))
         return 0
     if dist is not None:
         # only rank 0 has the stream: it parses it and every rank walks the same list of junctions
@@ -283,6 +382,8 @@ def _search(args, searcher, stdin, stdout, dist, rank):
         results = searcher.search_nn(args.results, args.search_k, include_distances=args.distances,
                                      meta_db=args.metadata)
     results_output(results, stdout)
+    if collect is not None:
+        collect.append((None, results))
     return 0
 
 

@@ -1,0 +1,901 @@
+// jstore.hip -- the junctions-by-sample store of `morna junctions` and its filter, on the GPU.
+//
+// Counterpart of the reference's junction databases and of the retention step of its `junctions` subcommand
+// (commanderson/morna morna.py:221-341 update_junction_dbs, 1486-1638), stripped of their storage format (100 sqlite
+// shards of run-length strings): the computation is
+//   * the STORE: the transpose of the junction x sample CSR the intropolis parse yields -- per sample, the ascending
+//     list of (line number, coverage) over ALL lines of the file (update_junction_dbs runs before the threshold test,
+//     morna.py:359 vs 361-363);
+//   * the FILTER: a set operation over the k rows of one result list -- keep every line at least min_count of the
+//     results hold, or that one of them covers at least coverage_filter times (morna.py:1539-1569).
+//
+// Store build (deterministic, no atomics on global memory): a stable counting sort of the entries by sample.
+//   jstore_count_kernel  one workgroup per block of consecutive lines walks ITS lines in file order and counts the
+//                        entries of every sample (cnt[block][sample]); a sample occurs at most once in a line, so the
+//                        entries of one line never meet -- which the kernel checks with an LDS bitmap (a repeat is
+//                        reported, smallest (line, sample) first, and the build fails before anything is placed)
+//   jstore_scan_kernel   per sample: exclusive prefix of its counts over the blocks, in place, and its total
+//   jstore_ptr_kernel    exclusive prefix of the totals over the samples: ptr[S + 1]
+//   jstore_place_kernel  the same walk: entry -> ptr[sample] + cnt[block][sample]++
+// Lines are visited in ascending order by exactly one workgroup per sample and block, so a sample's list ascends by
+// line number whatever order a line lists its samples in, and two builds give the same bytes.
+//
+// Filter: grid over (tile of JT_LINES line numbers) x (query).  The tile's 64-bit found_in words and its coverage
+// flags sit in LDS; one lane per result binary-searches the tile's first and last line in that sample's list, the
+// waves then walk the runs and OR bit `rank` into the line's word (LDS atomics: the OR is order-independent).  A
+// first pass counts the retained lines and their found_in bits per tile; a scan over the tiles of a query gives each
+// tile its place; the second pass writes the lines ascending, their words and the coverages in rank order.
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "common.hpp"
+
+using morna::DevBuf;
+using morna::set_error;
+
+struct morna_jstore {
+    int32_t device = 0;
+    int64_t n_lines = 0;
+    // host image (what save writes)
+    std::vector<int64_t> ext_ids;   // [S] external sample id, the parse's first-seen order
+    std::vector<int64_t> ptr{0};    // [S + 1]
+    std::vector<int32_t> line, cov; // [nnz]
+    std::unordered_map<int64_t, int32_t> row_of;   // external sample id -> row
+    // HBM image (made by build, or at the first retain of a loaded store)
+    bool resident = false;
+    hipStream_t stream = nullptr;
+    DevBuf<int64_t> d_ptr;
+    DevBuf<int32_t> d_line, d_cov;
+    // kernel time of the build and of the last retain (HIP events), with their algorithmic bytes
+    double ms[2] = {0, 0};
+    int64_t bytes[2] = {0, 0};
+    ~morna_jstore()
+    {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct morna_jretained {
+    int64_t nq = 0;
+    std::vector<int64_t> off{0};       // [nq + 1] first retained line of every query in the flat arrays
+    std::vector<int32_t> lines;        // retained line numbers, ascending inside a query
+    std::vector<uint64_t> masks;       // found_in: bit r set = result r holds the line
+    std::vector<int64_t> cov_ptr{0};   // [total + 1] extent of every retained line's coverages in `cov`
+    std::vector<int32_t> cov;          // coverages, rank order inside a line
+};
+
+namespace {
+
+#define JS_THREADS 512
+#define JS_BITMAP_WORDS 8192            // per bitmap; two of them: 64 KiB of LDS, up to 262144 samples
+#define JT_LINES 4096                   // lines of a filter tile: 32 KiB of found_in words
+#define JT_THREADS 256
+#define JT_PER (JT_LINES / JT_THREADS)  // consecutive lines per thread when a tile is compacted
+
+// err[0]: smallest (line << 32 | sample) of a repeated sample, err[1]: entries whose sample is out of range
+__global__ __launch_bounds__(JS_THREADS) void jstore_count_kernel(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ ids,
+                                                                  int64_t J, int32_t lines_per_block, int32_t S, int32_t check_dup,
+                                                                  int32_t *cnt, unsigned long long *__restrict__ err)
+{
+    extern __shared__ uint32_t s_bits[];   // two bitmaps of JS_BITMAP_WORDS words, used by alternate lines
+    const int tid = threadIdx.x;
+    if (check_dup)
+        for (int i = tid; i < 2 * JS_BITMAP_WORDS; i += JS_THREADS) s_bits[i] = 0;
+    __syncthreads();
+    int32_t *my = cnt + (int64_t)blockIdx.x * S;
+    const int64_t l0 = (int64_t)blockIdx.x * lines_per_block;
+    const int64_t l1 = l0 + lines_per_block < J ? l0 + lines_per_block : J;
+    for (int64_t l = l0; l < l1; l++) {
+        const int64_t a = row_ptr[l], b = row_ptr[l + 1];
+        uint32_t *bits = s_bits + (l & 1) * JS_BITMAP_WORDS;
+        for (int64_t e = a + tid; e < b; e += JS_THREADS) {
+            const int32_t s = ids[e];
+            if (s < 0 || s >= S) {
+                atomicAdd(&err[1], 1ull);
+                continue;
+            }
+            if (check_dup) {
+                const uint32_t bit = 1u << (s & 31);
+                if (atomicOr(&bits[s >> 5], bit) & bit) atomicMin(&err[0], ((unsigned long long)l << 32) | (uint32_t)s);
+            }
+            my[s] += 1;   // no other entry of this line has sample s
+        }
+        __syncthreads();   // the next line's entries see this line's counts
+        if (check_dup)     // (the line after next is the first to use this bitmap again, a barrier away)
+            for (int64_t e = a + tid; e < b; e += JS_THREADS) {
+                const int32_t s = ids[e];
+                if (s >= 0 && s < S) atomicAnd(&bits[s >> 5], ~(1u << (s & 31)));
+            }
+    }
+}
+
+// one thread per sample: cnt[0 .. n_blocks)[s] -> its exclusive prefix over the blocks; total[s]
+__global__ __launch_bounds__(256) void jstore_scan_kernel(int32_t *__restrict__ cnt, int32_t n_blocks, int32_t S, int64_t *__restrict__ total)
+{
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    int64_t run = 0;
+    for (int32_t b = 0; b < n_blocks; b++) {
+        int32_t *c = cnt + (int64_t)b * S + s;
+        const int32_t t = *c;
+        *c = (int32_t)run;   // a sample holds at most one entry per line: fewer than 2^31 in all
+        run += t;
+    }
+    total[s] = run;
+}
+
+// exclusive scan of total[S] into ptr[S + 1] (one workgroup)
+__global__ __launch_bounds__(1024) void jstore_ptr_kernel(const int64_t *__restrict__ total, int32_t S, int64_t *__restrict__ ptr)
+{
+    __shared__ int64_t s_part[1024];
+    const int tid = threadIdx.x;
+    const int64_t per = ((int64_t)S + 1023) / 1024;
+    const int64_t lo = tid * per < S ? tid * per : S, hi = lo + per < S ? lo + per : S;
+    int64_t sum = 0;
+    for (int64_t i = lo; i < hi; i++) sum += total[i];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t v = tid >= o ? s_part[tid - o] : 0;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    int64_t run = tid ? s_part[tid - 1] : 0;
+    for (int64_t i = lo; i < hi; i++) {
+        ptr[i] = run;
+        run += total[i];
+    }
+    if (tid == 1023) ptr[S] = s_part[1023];
+}
+
+__global__ __launch_bounds__(JS_THREADS) void jstore_place_kernel(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ ids,
+                                                                  const int32_t *__restrict__ cov, int64_t J, int32_t lines_per_block,
+                                                                  int32_t S, int64_t nnz, const int64_t *__restrict__ ptr,
+                                                                  int32_t *cnt, int32_t *__restrict__ line_out,
+                                                                  int32_t *__restrict__ cov_out)
+{
+    const int tid = threadIdx.x;
+    int32_t *my = cnt + (int64_t)blockIdx.x * S;
+    const int64_t l0 = (int64_t)blockIdx.x * lines_per_block;
+    const int64_t l1 = l0 + lines_per_block < J ? l0 + lines_per_block : J;
+    for (int64_t l = l0; l < l1; l++) {
+        const int64_t a = row_ptr[l], b = row_ptr[l + 1];
+        for (int64_t e = a + tid; e < b; e += JS_THREADS) {
+            const int32_t s = ids[e];   // in range and once per line: the count pass has checked both
+            const int32_t at = my[s];
+            my[s] = at + 1;
+            const int64_t p = ptr[s] + at;
+            if (p >= 0 && p < nnz) {
+                line_out[p] = (int32_t)l;
+                cov_out[p] = cov[e];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the filter ------------------------------------------------------------------------------------------------
+
+// first index in [lo, hi) whose line is >= key
+__device__ inline int64_t lower_bound_line(const int32_t *__restrict__ line, int64_t lo, int64_t hi, int64_t key)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)line[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One workgroup per (tile, query).  write == 0: tile_n[q][tile] = {retained lines, their found_in bits}.
+// write != 0: tile_n holds the exclusive prefix of those pairs over the query's tiles, q_off[q] / q_cov_off[q] the
+// query's place in the flat outputs.
+__global__ __launch_bounds__(JT_THREADS) void jstore_retain_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                                                   const int32_t *__restrict__ cov, int64_t n_lines, int32_t n_tiles,
+                                                                   const int32_t *__restrict__ rows, const int32_t *__restrict__ n_results,
+                                                                   const int32_t *__restrict__ min_count, int32_t k, int64_t coverage_filter,
+                                                                   int32_t write, int64_t *__restrict__ tile_n,
+                                                                   const int64_t *__restrict__ q_off, const int64_t *__restrict__ q_cov_off,
+                                                                   int32_t *__restrict__ lines_out, unsigned long long *__restrict__ masks_out,
+                                                                   int64_t *__restrict__ cov_ptr_out, int32_t *__restrict__ cov_out)
+{
+    __shared__ unsigned long long s_mask[JT_LINES];
+    __shared__ uint32_t s_flag[JT_LINES / 32];
+    __shared__ int64_t s_lo[64], s_hi[64];
+    __shared__ int32_t s_keep[JT_THREADS], s_bitsum[JT_THREADS];
+    __shared__ int32_t s_covoff[JT_LINES];   // write pass: a retained line's first coverage, relative to the tile; -1: not retained
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x / n_tiles;
+    const int32_t tile = (int32_t)(blockIdx.x % n_tiles);
+    const int64_t t0 = (int64_t)tile * JT_LINES;
+    const int64_t t1 = t0 + JT_LINES < n_lines ? t0 + JT_LINES : n_lines;
+    int32_t m = n_results[q];
+    m = m < 0 ? 0 : (m > k ? k : m);
+    for (int i = tid; i < JT_LINES; i += JT_THREADS) s_mask[i] = 0;
+    for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) s_flag[i] = 0;
+    if (tid < 128) {   // lanes 0-63: where the tile begins in result tid's list; lanes 64-127: where it ends
+        const int r = tid & 63;
+        if (r < m) {
+            const int32_t row = rows[q * k + r];
+            const int64_t a = ptr[row], b = ptr[row + 1];
+            const int64_t at = lower_bound_line(line, a, b, tid < 64 ? t0 : t1);
+            if (tid < 64) s_lo[r] = at;
+            else s_hi[r] = at;
+        }
+    }
+    __syncthreads();
+    const int wave = tid / WAVE, lane = tid % WAVE;
+    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
+        const int64_t hi = s_hi[r];
+        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
+            const int64_t l = (int64_t)line[i] - t0;
+            if (l < 0 || l >= JT_LINES) continue;   // (cannot happen in an ascending list)
+            atomicOr(&s_mask[l], 1ull << r);
+            if ((int64_t)cov[i] >= coverage_filter) atomicOr(&s_flag[l >> 5], 1u << (l & 31));
+        }
+    }
+    __syncthreads();
+    // compaction: thread t owns lines [t * JT_PER, (t + 1) * JT_PER) of the tile
+    const int32_t mc = min_count[q];
+    int32_t keep = 0, bitsum = 0;
+    uint32_t kept_bits = 0;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = tid * JT_PER + j;
+        const unsigned long long w = s_mask[l];
+        const int c = __popcll(w);
+        const bool on = t0 + l < t1 && c >= 1 && (c >= mc || ((s_flag[l >> 5] >> (l & 31)) & 1u));
+        if (on) {
+            kept_bits |= 1u << j;
+            keep++;
+            bitsum += c;
+        }
+    }
+    s_keep[tid] = keep;
+    s_bitsum[tid] = bitsum;
+    __syncthreads();
+    for (int o = 1; o < JT_THREADS; o <<= 1) {   // inclusive scans over the threads
+        const int32_t a = tid >= o ? s_keep[tid - o] : 0, b = tid >= o ? s_bitsum[tid - o] : 0;
+        __syncthreads();
+        s_keep[tid] += a;
+        s_bitsum[tid] += b;
+        __syncthreads();
+    }
+    int64_t *mine = tile_n + 2 * ((int64_t)q * n_tiles + tile);
+    if (!write) {
+        if (tid == JT_THREADS - 1) {
+            mine[0] = s_keep[tid];
+            mine[1] = s_bitsum[tid];
+        }
+        return;
+    }
+    const int64_t line_base = q_off[q] + mine[0], cov_base = q_cov_off[q] + mine[1];
+    int64_t at = line_base + s_keep[tid] - keep;
+    int32_t cat = s_bitsum[tid] - bitsum;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = tid * JT_PER + j;
+        if ((kept_bits >> j) & 1u) {
+            const unsigned long long w = s_mask[l];
+            lines_out[at] = (int32_t)(t0 + l);
+            masks_out[at] = w;
+            cov_ptr_out[at] = cov_base + cat;
+            s_covoff[l] = cat;
+            cat += __popcll(w);
+            at++;
+        } else {
+            s_covoff[l] = -1;
+        }
+    }
+    __syncthreads();
+    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
+        const int64_t hi = s_hi[r];
+        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
+            const int64_t l = (int64_t)line[i] - t0;
+            if (l < 0 || l >= JT_LINES) continue;
+            const int32_t o = s_covoff[l];
+            if (o < 0) continue;
+            cov_out[cov_base + o + __popcll(s_mask[l] & ((1ull << r) - 1ull))] = cov[i];
+        }
+    }
+}
+
+// one wave per query: the (lines, bits) pairs of its tiles -> their exclusive prefix, in place; totals[q] = the sums
+__global__ __launch_bounds__(256) void jstore_tile_scan_kernel(int64_t *__restrict__ tile_n, int32_t n_tiles, int64_t nq,
+                                                               int64_t *__restrict__ totals)
+{
+    const int lane = threadIdx.x % WAVE;
+    const int64_t q = (int64_t)blockIdx.x * (256 / WAVE) + threadIdx.x / WAVE;
+    if (q >= nq) return;
+    int64_t *t = tile_n + 2 * q * n_tiles;
+    int64_t run0 = 0, run1 = 0;
+    for (int32_t b0 = 0; b0 < n_tiles; b0 += WAVE) {
+        const int32_t b = b0 + lane;
+        const int64_t v0 = b < n_tiles ? t[2 * b] : 0, v1 = b < n_tiles ? t[2 * b + 1] : 0;
+        int64_t i0 = v0, i1 = v1;
+#pragma unroll
+        for (int off = 1; off < WAVE; off <<= 1) {
+            const int64_t o0 = __shfl_up(i0, off, WAVE), o1 = __shfl_up(i1, off, WAVE);
+            if (lane >= off) {
+                i0 += o0;
+                i1 += o1;
+            }
+        }
+        if (b < n_tiles) {
+            t[2 * b] = run0 + i0 - v0;
+            t[2 * b + 1] = run1 + i1 - v1;
+        }
+        run0 += __shfl(i0, WAVE - 1, WAVE);
+        run1 += __shfl(i1, WAVE - 1, WAVE);
+    }
+    if (lane == 0) {
+        totals[2 * q] = run0;
+        totals[2 * q + 1] = run1;
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------
+
+const char JSTORE_MAGIC[8] = {'M', 'O', 'R', 'N', 'A', 'J', 'S', '1'};
+
+// what load and from_arrays require of a store; `what` names its source in the message
+int validate_store(morna_jstore *st, const char *what, int code)
+{
+    const int64_t S = (int64_t)st->ext_ids.size(), nnz = (int64_t)st->line.size();
+    const char *why = nullptr;
+    if (S > INT32_MAX || st->n_lines < 0 || st->n_lines > INT32_MAX) why = "more than 2^31 - 1 samples or lines";
+    else if ((int64_t)st->ptr.size() != S + 1 || st->ptr[0] != 0 || st->ptr[(size_t)S] != nnz || st->cov.size() != st->line.size())
+        why = "the offsets do not describe the arrays";
+    for (int64_t s = 0; !why && s < S; s++) {
+        const int64_t a = st->ptr[(size_t)s], b = st->ptr[(size_t)s + 1];
+        if (a > b || b > nnz) {
+            why = "the offsets do not ascend";
+            break;
+        }
+        for (int64_t i = a; i < b; i++)
+            if (st->line[(size_t)i] < 0 || st->line[(size_t)i] >= st->n_lines || (i > a && st->line[(size_t)i] <= st->line[(size_t)i - 1])) {
+                why = "a sample's line numbers do not ascend below the line count";
+                break;
+            }
+    }
+    if (!why) {
+        st->row_of.clear();
+        st->row_of.reserve((size_t)S);
+        for (int64_t s = 0; s < S; s++)
+            if (!st->row_of.emplace(st->ext_ids[(size_t)s], (int32_t)s).second) {
+                why = "a sample id occurs twice";
+                break;
+            }
+    }
+    if (why) {
+        set_error("%s is not a consistent junction store: %s", what, why);
+        return code;
+    }
+    return MORNA_OK;
+}
+
+int check_device(int32_t device)
+{
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        set_error("no HIP device available (%s): libmorna_hip has no CPU path", hipGetErrorString(e));
+        return MORNA_E_HIP;
+    }
+    if (device < 0 || device >= ndev) {
+        set_error("device %d out of range (%d visible)", device, ndev);
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(device));
+    return MORNA_OK;
+}
+
+int ensure_stream(morna_jstore *st)
+{
+    MORNA_TRY(check_device(st->device));
+    if (!st->stream) HIP_TRY(hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
+    return MORNA_OK;
+}
+
+// the host image into HBM (a loaded store, at its first retain)
+int make_resident(morna_jstore *st)
+{
+    MORNA_TRY(ensure_stream(st));
+    if (st->resident) return MORNA_OK;
+    const size_t S = st->ext_ids.size(), nnz = st->line.size();
+    MORNA_TRY(st->d_ptr.alloc(S + 1));
+    MORNA_TRY(st->d_line.alloc(nnz));
+    MORNA_TRY(st->d_cov.alloc(nnz));
+    HIP_TRY(hipMemcpy(st->d_ptr.p, st->ptr.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz) {
+        HIP_TRY(hipMemcpy(st->d_line.p, st->line.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(st->d_cov.p, st->cov.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    st->resident = true;
+    return MORNA_OK;
+}
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int create()
+    {
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        return MORNA_OK;
+    }
+};
+
+int build_impl(morna_jstore *st, const morna_lines *L)
+{
+    int64_t counts[8], info[4];
+    MORNA_TRY(morna_lines_counts(L, counts));
+    MORNA_TRY(morna_lines_shard_info(L, info));
+    const int64_t J = counts[0], nnz = counts[1], S = counts[2];
+    if (counts[0] != counts[7] || info[1] != 1) {
+        set_error("jstore_build: the lines are not a whole parse with threshold 0 (%lld lines kept of %lld read, shard %lld of %lld): "
+                  "kept line j would not be line j of the file", (long long)counts[0], (long long)counts[7], (long long)info[0],
+                  (long long)info[1]);
+        return MORNA_E_INVALID;
+    }
+    if (J > INT32_MAX || S > INT32_MAX) {
+        set_error("jstore_build: %lld lines and %lld samples: the store holds at most 2^31 - 1 of each", (long long)J, (long long)S);
+        return MORNA_E_INVALID;
+    }
+    const int64_t *row_ptr = nullptr, *ext = nullptr;
+    const int32_t *ids = nullptr, *cov = nullptr;
+    MORNA_TRY(morna_lines_arrays(L, nullptr, nullptr, &row_ptr, &ids, &cov, nullptr, &ext));
+    st->n_lines = J;
+    st->ext_ids.assign(ext, ext + S);
+    st->ptr.assign((size_t)S + 1, 0);
+    st->line.assign((size_t)nnz, 0);
+    st->cov.assign((size_t)nnz, 0);
+    MORNA_TRY(ensure_stream(st));
+    MORNA_TRY(st->d_ptr.alloc((size_t)S + 1));
+    MORNA_TRY(st->d_line.alloc((size_t)nnz));
+    MORNA_TRY(st->d_cov.alloc((size_t)nnz));
+    if (J == 0 || S == 0 || nnz == 0) {
+        HIP_TRY(hipMemset(st->d_ptr.p, 0, ((size_t)S + 1) * sizeof(int64_t)));
+        st->resident = true;
+        return validate_store(st, "the built store", MORNA_E_INVALID);
+    }
+    // blocks of lines: about 1024 of them, fewer while their count table would pass 1 GiB
+    int64_t per = std::max<int64_t>(16, (J + 1023) / 1024);
+    while (((J + per - 1) / per) * S * (int64_t)sizeof(int32_t) > ((int64_t)1 << 30) && per < J) per *= 2;
+    if (per > INT32_MAX) per = INT32_MAX;
+    const int64_t n_blocks = (J + per - 1) / per;
+    const bool dup_on_device = (S + 31) / 32 <= JS_BITMAP_WORDS;
+    if (!dup_on_device) {   // more samples than the LDS bitmap holds: the same check on the host
+        std::vector<int32_t> last((size_t)S, -1);
+        for (int64_t l = 0; l < J; l++)
+            for (int64_t e = row_ptr[l]; e < row_ptr[l + 1]; e++) {
+                const int32_t s = ids[e];
+                if (s < 0 || s >= S) continue;   // (reported by the count kernel)
+                if (last[(size_t)s] == (int32_t)l) {
+                    set_error("jstore_build: line %lld lists sample %lld twice", (long long)l, (long long)ext[s]);
+                    return MORNA_E_INVALID;
+                }
+                last[(size_t)s] = (int32_t)l;
+            }
+    }
+    DevBuf<int64_t> d_row_ptr, d_total;
+    DevBuf<int32_t> d_ids, d_covin, d_cnt;
+    DevBuf<unsigned long long> d_err;
+    MORNA_TRY(d_row_ptr.alloc((size_t)J + 1));
+    MORNA_TRY(d_ids.alloc((size_t)nnz));
+    MORNA_TRY(d_covin.alloc((size_t)nnz));
+    MORNA_TRY(d_cnt.alloc((size_t)(n_blocks * S)));
+    MORNA_TRY(d_total.alloc((size_t)S));
+    MORNA_TRY(d_err.alloc(2));
+    HIP_TRY(hipMemcpy(d_row_ptr.p, row_ptr, ((size_t)J + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ids.p, ids, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_covin.p, cov, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    const unsigned long long err0[2] = {~0ull, 0ull};
+    HIP_TRY(hipMemcpy(d_err.p, err0, sizeof(err0), hipMemcpyHostToDevice));
+    EventPair ev;
+    MORNA_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev.a, st->stream));
+    HIP_TRY(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_blocks * S) * sizeof(int32_t), st->stream));
+    hipLaunchKernelGGL(jstore_count_kernel, dim3((unsigned)n_blocks), dim3(JS_THREADS), dup_on_device ? 2 * JS_BITMAP_WORDS * sizeof(uint32_t) : 0,
+                       st->stream, d_row_ptr.p, d_ids.p, J, (int32_t)per, (int32_t)S, dup_on_device ? 1 : 0, d_cnt.p, d_err.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long err[2];
+    HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    if (err[1]) {
+        set_error("jstore_build: %llu entries name a sample outside [0, %lld)", err[1], (long long)S);
+        return MORNA_E_INVALID;
+    }
+    if (err[0] != ~0ull) {
+        set_error("jstore_build: line %lld lists sample %lld twice", (long long)(err[0] >> 32), (long long)ext[(size_t)(err[0] & 0xffffffffu)]);
+        return MORNA_E_INVALID;
+    }
+    hipLaunchKernelGGL(jstore_scan_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st->stream, d_cnt.p, (int32_t)n_blocks, (int32_t)S,
+                       d_total.p);
+    hipLaunchKernelGGL(jstore_ptr_kernel, dim3(1), dim3(1024), 0, st->stream, d_total.p, (int32_t)S, st->d_ptr.p);
+    hipLaunchKernelGGL(jstore_place_kernel, dim3((unsigned)n_blocks), dim3(JS_THREADS), 0, st->stream, d_row_ptr.p, d_ids.p, d_covin.p, J,
+                       (int32_t)per, (int32_t)S, nnz, st->d_ptr.p, d_cnt.p, st->d_line.p, st->d_cov.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.b, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    st->ms[0] = ms;
+    st->bytes[0] = 2 * 8 * nnz;   // every (sample, coverage) pair read once, every (line, coverage) pair written once
+    HIP_TRY(hipMemcpy(st->ptr.data(), st->d_ptr.p, ((size_t)S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st->line.data(), st->d_line.p, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st->cov.data(), st->d_cov.p, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    st->resident = true;
+    return validate_store(st, "the built store", MORNA_E_INVALID);
+}
+
+int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, const int32_t *min_count, int64_t nq, int32_t k,
+                int64_t coverage_filter, morna_jretained *R)
+{
+    R->nq = nq;
+    R->off.assign((size_t)nq + 1, 0);
+    if (nq == 0) return MORNA_OK;
+    std::vector<int32_t> rows((size_t)(nq * k), 0);
+    int64_t list_entries = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        if (n_results[q] < 0 || n_results[q] > k) {
+            set_error("jstore_retain: result list %lld holds %d results, outside [0, %d]", (long long)q, n_results[q], k);
+            return MORNA_E_INVALID;
+        }
+        for (int32_t r = 0; r < n_results[q]; r++) {
+            const int64_t id = results[q * k + r];
+            auto it = st->row_of.find(id);
+            if (it == st->row_of.end()) {
+                set_error("jstore_retain: sample id %lld (result %d of list %lld) is not in the junction store", (long long)id, r, (long long)q);
+                return MORNA_E_RANGE;
+            }
+            rows[(size_t)(q * k + r)] = it->second;
+            list_entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
+        }
+    }
+    MORNA_TRY(make_resident(st));
+    const int64_t n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
+    if (nq * n_tiles > INT32_MAX) {
+        set_error("jstore_retain: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
+                  "pass fewer lists per call", (long long)nq, (long long)n_tiles);
+        return MORNA_E_INVALID;
+    }
+    DevBuf<int32_t> d_rows, d_nres, d_minc, d_lines, d_cov;
+    DevBuf<int64_t> d_tile, d_totals, d_off, d_covptr;
+    DevBuf<unsigned long long> d_masks;
+    MORNA_TRY(d_rows.alloc((size_t)(nq * k)));
+    MORNA_TRY(d_nres.alloc((size_t)nq));
+    MORNA_TRY(d_minc.alloc((size_t)nq));
+    MORNA_TRY(d_tile.alloc((size_t)(2 * nq * n_tiles)));
+    MORNA_TRY(d_totals.alloc((size_t)(2 * nq)));
+    MORNA_TRY(d_off.alloc((size_t)(2 * nq)));
+    HIP_TRY(hipMemcpy(d_rows.p, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_nres.p, n_results, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_minc.p, min_count, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice));
+    EventPair ev1, ev2;
+    MORNA_TRY(ev1.create());
+    MORNA_TRY(ev2.create());
+    const dim3 grid((unsigned)(nq * n_tiles));
+    HIP_TRY(hipEventRecord(ev1.a, st->stream));
+    hipLaunchKernelGGL(jstore_retain_kernel, grid, dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p, st->d_cov.p, st->n_lines,
+                       (int32_t)n_tiles, d_rows.p, d_nres.p, d_minc.p, k, coverage_filter, 0, d_tile.p, (const int64_t *)nullptr,
+                       (const int64_t *)nullptr, (int32_t *)nullptr, (unsigned long long *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr);
+    hipLaunchKernelGGL(jstore_tile_scan_kernel, dim3((unsigned)((nq + 256 / WAVE - 1) / (256 / WAVE))), dim3(256), 0, st->stream, d_tile.p,
+                       (int32_t)n_tiles, nq, d_totals.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1.b, st->stream));
+    std::vector<int64_t> totals((size_t)(2 * nq));
+    HIP_TRY(hipMemcpyAsync(totals.data(), d_totals.p, totals.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    std::vector<int64_t> off((size_t)(2 * nq));   // [0, nq): first line of every query, [nq, 2 nq): its first coverage
+    int64_t n_kept = 0, n_cov = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        R->off[(size_t)q] = off[(size_t)q] = n_kept;
+        off[(size_t)(nq + q)] = n_cov;
+        n_kept += totals[(size_t)(2 * q)];
+        n_cov += totals[(size_t)(2 * q + 1)];
+    }
+    R->off[(size_t)nq] = n_kept;
+    R->lines.assign((size_t)n_kept, 0);
+    R->masks.assign((size_t)n_kept, 0);
+    R->cov_ptr.assign((size_t)n_kept + 1, 0);
+    R->cov.assign((size_t)n_cov, 0);
+    R->cov_ptr[(size_t)n_kept] = n_cov;
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(hipEventElapsedTime(&ms1, ev1.a, ev1.b));
+    if (n_kept) {
+        MORNA_TRY(d_lines.alloc((size_t)n_kept));
+        MORNA_TRY(d_masks.alloc((size_t)n_kept));
+        MORNA_TRY(d_covptr.alloc((size_t)n_kept));
+        MORNA_TRY(d_cov.alloc((size_t)n_cov));
+        HIP_TRY(hipMemcpy(d_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipEventRecord(ev2.a, st->stream));
+        hipLaunchKernelGGL(jstore_retain_kernel, grid, dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p, st->d_cov.p, st->n_lines,
+                           (int32_t)n_tiles, d_rows.p, d_nres.p, d_minc.p, k, coverage_filter, 1, d_tile.p, (const int64_t *)d_off.p,
+                           (const int64_t *)(d_off.p + nq), d_lines.p, d_masks.p, d_covptr.p, d_cov.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev2.b, st->stream));
+        HIP_TRY(hipStreamSynchronize(st->stream));
+        HIP_TRY(hipEventElapsedTime(&ms2, ev2.a, ev2.b));
+        HIP_TRY(hipMemcpy(R->lines.data(), d_lines.p, (size_t)n_kept * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->masks.data(), d_masks.p, (size_t)n_kept * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->cov_ptr.data(), d_covptr.p, (size_t)n_kept * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->cov.data(), d_cov.p, (size_t)n_cov * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    st->ms[1] = (double)ms1 + (double)ms2;
+    st->bytes[1] = 8 * list_entries;   // the k lists of every query, read once
+    return MORNA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int morna_jstore_free(morna_jstore *s)
+{
+    if (s && s->resident) (void)hipSetDevice(s->device);
+    delete s;
+    return MORNA_OK;
+}
+
+int morna_jstore_build(int32_t device, const morna_lines *all_lines, morna_jstore **out)
+{
+    if (!all_lines || !out) {
+        set_error("jstore_build: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    int rc;
+    std::unique_ptr<morna_jstore> st;
+    try {
+        st.reset(new morna_jstore());
+        st->device = device;
+        rc = build_impl(st.get(), all_lines);
+    } catch (const std::exception &e) {
+        set_error("jstore_build: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK) return rc;
+    *out = st.release();
+    return MORNA_OK;
+}
+
+int morna_jstore_from_arrays(int32_t device, const int64_t *ext_ids, int64_t n_samples, const int64_t *ptr, const int32_t *line,
+                             const int32_t *cov, int64_t n_lines, morna_jstore **out)
+{
+    if (!out || n_samples < 0 || !ptr || (n_samples > 0 && !ext_ids)) {
+        set_error("jstore_from_arrays: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    const int64_t nnz = ptr[n_samples];
+    if (nnz < 0 || (nnz > 0 && (!line || !cov))) {
+        set_error("jstore_from_arrays: the offsets end at %lld", (long long)nnz);
+        return MORNA_E_INVALID;
+    }
+    int rc;
+    std::unique_ptr<morna_jstore> st;
+    try {
+        st.reset(new morna_jstore());
+        st->device = device;
+        st->n_lines = n_lines;
+        st->ext_ids.assign(ext_ids, ext_ids + n_samples);
+        st->ptr.assign(ptr, ptr + n_samples + 1);
+        st->line.assign(line, line + nnz);
+        st->cov.assign(cov, cov + nnz);
+        rc = validate_store(st.get(), "jstore_from_arrays: the input", MORNA_E_INVALID);
+    } catch (const std::exception &e) {
+        set_error("jstore_from_arrays: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK) return rc;
+    *out = st.release();
+    return MORNA_OK;
+}
+
+// "MORNAJS1", S, nnz, n_lines (int64 each), ext_ids[S] int64, ptr[S + 1] int64, line[nnz] int32, cov[nnz] int32
+int morna_jstore_save(const morna_jstore *s, const char *path)
+{
+    if (!s || !path) {
+        set_error("jstore_save: null argument");
+        return MORNA_E_INVALID;
+    }
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long long)getpid());
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) {
+        set_error("Unable to open %s for writing", tmp.c_str());
+        return MORNA_E_IO;
+    }
+    const int64_t head[3] = {(int64_t)s->ext_ids.size(), (int64_t)s->line.size(), s->n_lines};
+    auto put = [&](const void *p, size_t elt, size_t n) { return n == 0 || fwrite(p, elt, n, f) == n; };
+    bool ok = put(JSTORE_MAGIC, 1, 8) && put(head, 8, 3) && put(s->ext_ids.data(), 8, s->ext_ids.size()) &&
+              put(s->ptr.data(), 8, s->ptr.size()) && put(s->line.data(), 4, s->line.size()) && put(s->cov.data(), 4, s->cov.size());
+    ok = (fclose(f) == 0) && ok;
+    ok = ok && rename(tmp.c_str(), path) == 0;
+    if (!ok) {
+        (void)remove(tmp.c_str());
+        set_error("short write to %s", path);
+        return MORNA_E_IO;
+    }
+    return MORNA_OK;
+}
+
+int morna_jstore_load(const char *path, int32_t device, morna_jstore **out)
+{
+    if (!path || !out) {
+        set_error("jstore_load: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        set_error("Unable to open %s", path);
+        return MORNA_E_IO;
+    }
+    int rc = MORNA_OK;
+    std::unique_ptr<morna_jstore> st;
+    try {
+        st.reset(new morna_jstore());
+        st->device = device;
+        char magic[8];
+        int64_t head[3] = {0, 0, 0};
+        bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, JSTORE_MAGIC, 8) == 0 && fread(head, 8, 3, f) == 3;
+        if (ok) {   // the counts must account for the file's size exactly before anything is allocated from them
+            for (int i = 0; i < 3; i++) ok = ok && head[i] >= 0 && head[i] < ((int64_t)1 << 56);
+            const long here = ftell(f);
+            ok = ok && fseek(f, 0, SEEK_END) == 0;
+            const long size = ftell(f);
+            ok = ok && fseek(f, here, SEEK_SET) == 0;
+            ok = ok && (double)size == (double)here + 8.0 * (double)head[0] + 8.0 * ((double)head[0] + 1) + 8.0 * (double)head[1];
+        }
+        auto get = [&](void *p, size_t elt, size_t n) { return n == 0 || fread(p, elt, n, f) == n; };
+        if (ok) {
+            st->n_lines = head[2];
+            st->ext_ids.resize((size_t)head[0]);
+            st->ptr.resize((size_t)head[0] + 1);
+            st->line.resize((size_t)head[1]);
+            st->cov.resize((size_t)head[1]);
+            ok = get(st->ext_ids.data(), 8, st->ext_ids.size()) && get(st->ptr.data(), 8, st->ptr.size()) &&
+                 get(st->line.data(), 4, st->line.size()) && get(st->cov.data(), 4, st->cov.size()) && fgetc(f) == EOF;
+        }
+        if (!ok) {
+            set_error("%s is not a junction store (or is truncated)", path);
+            rc = MORNA_E_IO;
+        } else {
+            rc = validate_store(st.get(), path, MORNA_E_IO);
+        }
+    } catch (const std::exception &e) {
+        set_error("jstore_load: %s", e.what());
+        rc = MORNA_E_IO;
+    }
+    fclose(f);
+    if (rc != MORNA_OK) return rc;
+    *out = st.release();
+    return MORNA_OK;
+}
+
+int morna_jstore_counts(const morna_jstore *s, int64_t *counts)
+{
+    if (!s || !counts) {
+        set_error("jstore_counts: null argument");
+        return MORNA_E_INVALID;
+    }
+    counts[0] = (int64_t)s->ext_ids.size();
+    counts[1] = (int64_t)s->line.size();
+    counts[2] = s->n_lines;
+    return MORNA_OK;
+}
+
+int morna_jstore_samples(const morna_jstore *s, int64_t *ext_ids_out)
+{
+    if (!s || !ext_ids_out) {
+        set_error("jstore_samples: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (!s->ext_ids.empty()) memcpy(ext_ids_out, s->ext_ids.data(), s->ext_ids.size() * sizeof(int64_t));
+    return MORNA_OK;
+}
+
+int morna_jstore_sample(const morna_jstore *s, int64_t ext_id, int64_t *n_out, int32_t *line_out, int32_t *cov_out)
+{
+    if (!s || !n_out) {
+        set_error("jstore_sample: null argument");
+        return MORNA_E_INVALID;
+    }
+    auto it = s->row_of.find(ext_id);
+    if (it == s->row_of.end()) {
+        set_error("sample id %lld is not in the junction store", (long long)ext_id);
+        return MORNA_E_RANGE;
+    }
+    const int64_t a = s->ptr[(size_t)it->second], b = s->ptr[(size_t)it->second + 1];
+    *n_out = b - a;
+    if (line_out && b > a) memcpy(line_out, s->line.data() + a, (size_t)(b - a) * sizeof(int32_t));
+    if (cov_out && b > a) memcpy(cov_out, s->cov.data() + a, (size_t)(b - a) * sizeof(int32_t));
+    return MORNA_OK;
+}
+
+int morna_jstore_timers(const morna_jstore *s, double *ms, int64_t *bytes)
+{
+    if (!s || !ms || !bytes) {
+        set_error("jstore_timers: null argument");
+        return MORNA_E_INVALID;
+    }
+    for (int i = 0; i < 2; i++) {
+        ms[i] = s->ms[i];
+        bytes[i] = s->bytes[i];
+    }
+    return MORNA_OK;
+}
+
+int morna_jstore_retain(morna_jstore *s, const int64_t *results, const int32_t *n_results, const int32_t *min_count, int64_t nq, int32_t k,
+                        int64_t coverage_filter, morna_jretained **out)
+{
+    if (!s || !out || nq < 0 || (nq > 0 && (!results || !n_results || !min_count))) {
+        set_error("jstore_retain: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    if (k < 1 || k > 64) {
+        set_error("jstore_retain: %d results per list: the filter takes 1 to 64 (found_in is one 64-bit word per line)", k);
+        return MORNA_E_INVALID;
+    }
+    int rc;
+    std::unique_ptr<morna_jretained> R;
+    try {
+        R.reset(new morna_jretained());
+        rc = retain_impl(s, results, n_results, min_count, nq, k, coverage_filter, R.get());
+    } catch (const std::exception &e) {
+        set_error("jstore_retain: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK) return rc;
+    *out = R.release();
+    return MORNA_OK;
+}
+
+int morna_jretained_counts(const morna_jretained *r, int64_t *count_out)
+{
+    if (!r || (r->nq > 0 && !count_out)) {
+        set_error("jretained_counts: null argument");
+        return MORNA_E_INVALID;
+    }
+    for (int64_t q = 0; q < r->nq; q++) count_out[q] = r->off[(size_t)q + 1] - r->off[(size_t)q];
+    return MORNA_OK;
+}
+
+int morna_jretained_query(const morna_jretained *r, int64_t q, const int32_t **lines, const uint64_t **masks, const int64_t **cov_ptr,
+                          const int32_t **cov)
+{
+    if (!r) {
+        set_error("jretained_query: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (q < 0 || q >= r->nq) {
+        set_error("jretained_query: query %lld out of range [0, %lld)", (long long)q, (long long)r->nq);
+        return MORNA_E_RANGE;
+    }
+    const size_t at = (size_t)r->off[(size_t)q];
+    if (lines) *lines = r->lines.data() + at;
+    if (masks) *masks = r->masks.data() + at;
+    if (cov_ptr) *cov_ptr = r->cov_ptr.data() + at;
+    if (cov) *cov = r->cov.data();
+    return MORNA_OK;
+}
+
+int morna_jretained_free(morna_jretained *r)
+{
+    delete r;
+    return MORNA_OK;
+}
+
+}  // extern "C"

@@ -9,8 +9,10 @@ idf = log(sample_count / freq) (libm, so it is bit-identical to Python's).
 Everything per-nnz and everything numeric runs in libmorna_hip.so: junction
 lines are buffered as CSR arrays and handed over once by build().
 
-Out of scope here: the junctions-by-sample
-sqlite shards (update_junction_dbs).
+The junctions-by-sample databases (update_junction_dbs, morna.py:221-341) are one
+blob, <basename>.junc.mor, written on request (`junction_store=True`, the command
+line's --junction-store) from a second parse of the file with threshold 0 and a
+transpose on the GPU (junctions.py, csrc/jstore.hip).
 """
 import gzip
 import pickle
@@ -355,7 +357,7 @@ def build_shard(parsed, features, n_trees, rank, world, device=0, seed=0):
 
 
 def go_index_native(intropolis, basename, features, n_trees, sample_count, sample_threshold, buffer_size, verbose,
-                    metafile, device=0, save=True, seed=0, cache=None, shards=1, rank=None):
+                    metafile, device=0, save=True, seed=0, cache=None, shards=1, rank=None, junction_store=False):
     """go_index with the tokenising loop done by the library (morna_parse_intropolis)
     instead of the Python interpreter; same index, same files.  `cache`: binary
     pre-tokenised cache file to reuse / write (ParsedLines).
@@ -368,8 +370,11 @@ def go_index_native(intropolis, basename, features, n_trees, sample_count, sampl
     if verbose:
         print('\nThere are {} samples.'.format(parsed.sample_count))
     if shards > 1:
-        return _go_index_sharded(parsed, basename, features, n_trees, sample_threshold, buffer_size, verbose, metafile,
-                                 device, save, seed, shards, rank)
+        built = _go_index_sharded(parsed, basename, features, n_trees, sample_threshold, buffer_size, verbose, metafile,
+                                  device, save, seed, shards, rank)
+        if save and (rank is None or rank == 0):       # one global store, keyed by external sample id; rank 0 writes it
+            _junction_store(intropolis, basename, parsed.sample_count, device, junction_store)
+        return built
     morna_index = MornaIndex(parsed.sample_count, basename, dim=features, sample_threshold=sample_threshold,
                              metafile=metafile, buffer_size=buffer_size, device=device)
     morna_index.junc_id = parsed.lines_read - 1
@@ -387,7 +392,19 @@ def go_index_native(intropolis, basename, features, n_trees, sample_count, sampl
     AnnoyIndex.build(morna_index, n_trees, seed=seed)
     if save:
         morna_index.save(basename)
+        _junction_store(intropolis, basename, parsed.sample_count, device, junction_store)
     return morna_index
+
+
+def _junction_store(intropolis, basename, sample_count, device, wanted):
+    """<basename>.junc.mor next to the index files just written: built from a SECOND parse of the file (threshold 0: the
+    store holds the lines under the index's threshold too, morna.py:359 vs 361-363), or removed when this index has
+    none -- a store left by an earlier index of the same basename would describe another file."""
+    from .junctions import build_store, remove_stale_store
+    if wanted:
+        build_store(intropolis, basename, sample_count, device=device)
+    else:
+        remove_stale_store(basename)
 
 
 def _go_index_sharded(parsed, basename, features, n_trees, sample_threshold, buffer_size, verbose, metafile, device,
@@ -416,12 +433,13 @@ def _go_index_sharded(parsed, basename, features, n_trees, sample_threshold, buf
 
 
 def go_index(intropolis, basename, features, n_trees, sample_count, sample_threshold, buffer_size, verbose,
-             metafile, device=0, save=True, seed=0, native=False, cache=None, shards=1, rank=None):
-    """`morna index` (morna.py:824-865): gzipped intropolis file -> index files."""
+             metafile, device=0, save=True, seed=0, native=False, cache=None, shards=1, rank=None, junction_store=False):
+    """`morna index` (morna.py:824-865): gzipped intropolis file -> index files.  junction_store: also write
+    <basename>.junc.mor, the junctions-by-sample store `morna junctions` reads (otherwise a stale one is removed)."""
     if native or cache or shards > 1:
         return go_index_native(intropolis, basename, features, n_trees, sample_count, sample_threshold, buffer_size,
                                verbose, metafile, device=device, save=save, seed=seed, cache=cache, shards=shards,
-                               rank=rank)
+                               rank=rank, junction_store=junction_store)
     if not sample_count:
         with gzip.open(intropolis, "rt") as introp_file_handle:
             sample_count = count_samples(introp_file_handle, verbose)
@@ -440,6 +458,7 @@ def go_index(intropolis, basename, features, n_trees, sample_count, sample_thres
     morna_index.build(n_trees, verbose=verbose, seed=seed)
     if save:
         morna_index.save(basename)
+        _junction_store(intropolis, basename, sample_count, device, junction_store)
     return morna_index
 
 

@@ -1,0 +1,243 @@
+"""Host side of `morna junctions`: the junctions-by-sample store and the splice-file writer.
+
+Stands in for commanderson/morna morna.py:221-341 (update_junction_dbs and its 100 sqlite shards) and 1486-1638 (the
+retention step and the output loop of the `junctions` subcommand).  The store -- for every sample id of any line of the
+indexed intropolis file, its ascending (line number, coverage) list -- is built, kept and filtered by libmorna_hip.so
+(csrc/jstore.hip); this module marshals numpy buffers, computes min_count with the reference's own expression and
+writes the text.
+
+    store = JunctionStore.build(ParsedLines(path, sample_count=n, sample_threshold=0))
+    store.save(basename + ".junc.mor")
+    kept = JunctionStore.load(basename + ".junc.mor").retain([[sample ids in rank order], ...], 0.05, 5)
+"""
+import ctypes as C
+import gzip
+from math import ceil
+
+import numpy as np
+
+from ._lib import check, lib, ptr
+
+MAX_RESULTS = 64        # found_in is one 64-bit word per line (morna_jstore_retain)
+STORE_SUFFIX = ".junc.mor"
+
+
+def parse_junction_filter(text):
+    """--junction-filter "<frequency>,<coverage>" as (float, int) (morna.py:1487-1489); ValueError otherwise."""
+    parts = str(text).split(",")
+    if len(parts) != 2:
+        raise ValueError("--junction-filter takes two parts separated by a comma, such as .05,5 (got %r)" % (text,))
+    return float(parts[0]), int(parts[1])
+
+
+def min_count(frequency_filter, n_results):
+    """Results that must hold a junction for the frequency filter to keep it (morna.py:1551)."""
+    return int(ceil(frequency_filter * n_results))
+
+
+class Retained(object):
+    """The junctions retained for one result list: lines (ascending line numbers, int32 array), found_in (per line, the
+    ranks of the results that hold it, ascending) and coverages (per line, their coverages in that order)."""
+
+    def __init__(self, lines, masks, cov_ptr, cov):
+        self.lines = lines
+        self.masks = masks
+        self._cov_ptr, self._cov = cov_ptr, cov
+
+    def __len__(self):
+        return len(self.lines)
+
+    @property
+    def found_in(self):
+        return [[r for r in range(MAX_RESULTS) if (m >> r) & 1] for m in self.masks.tolist()]
+
+    @property
+    def coverages(self):
+        p = self._cov_ptr
+        return [self._cov[p[i]:p[i + 1]].tolist() for i in range(len(self.lines))]
+
+
+def view(pp, ctype, count):
+    """A copy of `count` elements of library-owned memory."""
+    if count == 0 or not pp.value:
+        return np.zeros(0, np.dtype(ctype))
+    return np.ctypeslib.as_array(C.cast(pp, C.POINTER(ctype)), shape=(count,)).copy()
+
+
+class JunctionStore(object):
+    """A junction store held by the library (morna_jstore)."""
+
+    def __init__(self, _ptr):
+        self._p = _ptr
+        counts = np.zeros(3, np.int64)
+        check(lib().morna_jstore_counts(self._p, ptr(counts)))
+        self.n_samples, self.nnz, self.n_lines = [int(x) for x in counts]
+
+    @classmethod
+    def build(cls, parsed, device=0):
+        """From a ParsedLines of the whole file with sample_threshold=0 (every line kept), on the GPU."""
+        p = C.c_void_p()
+        check(lib().morna_jstore_build(int(device), parsed._p, C.byref(p)))
+        return cls(p)
+
+    @classmethod
+    def from_arrays(cls, ext_ids, ptr_, line, cov, n_lines, device=0):
+        a = [np.ascontiguousarray(x, t) for x, t in ((ext_ids, np.int64), (ptr_, np.int64), (line, np.int32), (cov, np.int32))]
+        if len(a[1]) != len(a[0]) + 1 or len(a[2]) != len(a[3]) or (len(a[1]) and a[1][-1] != len(a[2])):
+            raise ValueError("junction store arrays: ptr must hold one more entry than ext_ids and end at the length of line / cov")
+        p = C.c_void_p()
+        check(lib().morna_jstore_from_arrays(int(device), ptr(a[0]), len(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), int(n_lines),
+                                             C.byref(p)))
+        return cls(p)
+
+    @classmethod
+    def load(cls, path, device=0):
+        p = C.c_void_p()
+        check(lib().morna_jstore_load(str(path).encode(), int(device), C.byref(p)))
+        return cls(p)
+
+    def save(self, path):
+        check(lib().morna_jstore_save(self._p, str(path).encode()))
+
+    def __del__(self):
+        p = getattr(self, "_p", None)
+        if p is not None and p.value:
+            try:
+                lib().morna_jstore_free(p)
+            except Exception:                          # interpreter shutting down
+                pass
+            self._p = None
+
+    def sample_ids(self):
+        out = np.zeros(self.n_samples, np.int64)
+        check(lib().morna_jstore_samples(self._p, ptr(out)))
+        return out
+
+    def sample(self, ext_id):
+        """(line numbers, coverages) of one sample; IndexError for an id the store lacks."""
+        n = C.c_int64()
+        check(lib().morna_jstore_sample(self._p, int(ext_id), C.byref(n), None, None))
+        line, cov = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        check(lib().morna_jstore_sample(self._p, int(ext_id), C.byref(n), ptr(line), ptr(cov)))
+        return line, cov
+
+    def timers(self):
+        """{"build": (ms, bytes), "retain": (ms, bytes)}: kernel time of the build and of the last retain."""
+        ms, nbytes = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        check(lib().morna_jstore_timers(self._p, ptr(ms), ptr(nbytes)))
+        return {"build": (float(ms[0]), int(nbytes[0])), "retain": (float(ms[1]), int(nbytes[1]))}
+
+    def retain(self, result_sample_ids, frequency_filter, coverage_filter):
+        """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
+        order, at most 64 per list) in one call on the GPU.  Returns one Retained per list."""
+        lists = [[int(s) for s in lst] for lst in result_sample_ids]
+        k = max([len(lst) for lst in lists] + [1])
+        if k > MAX_RESULTS:
+            raise ValueError("a result list holds %d results: the junction filter takes at most %d (found_in is one 64-bit "
+                             "word per line)" % (k, MAX_RESULTS))
+        nq = len(lists)
+        res = np.zeros((nq, k), np.int64)
+        n_res = np.zeros(nq, np.int32)
+        minc = np.zeros(nq, np.int32)
+        for q, lst in enumerate(lists):
+            res[q, :len(lst)] = lst
+            n_res[q] = len(lst)
+            minc[q] = min(max(min_count(frequency_filter, len(lst)), -1), MAX_RESULTS + 1)
+        cf = min(max(int(coverage_filter), -2**62), 2**62)
+        r = C.c_void_p()
+        check(lib().morna_jstore_retain(self._p, ptr(res), ptr(n_res), ptr(minc), nq, k, cf, C.byref(r)))
+        try:
+            counts = np.zeros(nq, np.int64)
+            check(lib().morna_jretained_counts(r, ptr(counts)))
+            out = []
+            for q in range(nq):
+                n = int(counts[q])
+                p = [C.c_void_p() for _ in range(4)]
+                check(lib().morna_jretained_query(r, q, *[C.byref(x) for x in p]))
+                cov_ptr = view(p[2], C.c_int64, n + 1)
+                lo, hi = (int(cov_ptr[0]), int(cov_ptr[-1])) if n else (0, 0)
+                cov = view(C.c_void_p(p[3].value + 4 * lo) if p[3].value else p[3], C.c_int32, hi - lo)
+                out.append(Retained(view(p[0], C.c_int32, n), view(p[1], C.c_uint64, n), cov_ptr - lo, cov))
+            return out
+        finally:
+            lib().morna_jretained_free(r)
+
+
+def build_store(intropolis, basename, sample_count, device=0):
+    """`morna index --junction-store`: the intropolis file parsed once more with threshold 0 -- every line kept, so kept
+    line j is file line j -- then transposed on the GPU and saved as <basename>.junc.mor."""
+    from .index import ParsedLines
+    parsed = ParsedLines(intropolis, sample_count=max(1, int(sample_count or 0)), sample_threshold=0)
+    store = JunctionStore.build(parsed, device=device)
+    store.save(basename + STORE_SUFFIX)
+    return store
+
+
+def remove_stale_store(basename):
+    """An index written without --junction-store must not be found next to the store of an earlier one."""
+    import os
+    if os.path.exists(basename + STORE_SUFFIX):
+        os.remove(basename + STORE_SUFFIX)
+
+
+def _open_text(path):
+    with open(path, "rb") as fh:
+        gz = fh.read(2) == b"\x1f\x8b"
+    return gzip.open(path, "rt") if gz else open(path, "r")
+
+
+def write_splice_files(junction_file, jobs):
+    """The output loop of morna.py:1582-1635 for several queries in one pass over `junction_file`.
+
+    jobs: (path, Retained, result_sample_ids) per query.  For every retained line j, ascending, line j of the file is
+    written with tokens[1] - 2, the sample ids of found_in[j] in rank order, their coverages, and str(found_in[j]) as
+    one more field.  The named samples must be in the line's own sample list with the same coverage (the reference's
+    old_samples.index look-up, here the check that the file is the one indexed): ValueError naming the line otherwise.
+    An empty retained set writes an empty file."""
+    jobs = list(jobs)
+    handles = [open(path, "w") for path, _, _ in jobs]
+    try:
+        if not jobs:
+            return
+        # every (line, job, position in the job's list), by line
+        line = np.concatenate([np.asarray(r.lines, np.int64) for _, r, _ in jobs])
+        job = np.concatenate([np.full(len(r.lines), i, np.int64) for i, (_, r, _) in enumerate(jobs)])
+        pos = np.concatenate([np.arange(len(r.lines), dtype=np.int64) for _, r, _ in jobs])
+        order = np.lexsort((job, line))
+        line, job, pos = line[order].tolist(), job[order].tolist(), pos[order].tolist()
+        if not line:
+            return
+        found = [r.found_in for _, r, _ in jobs]
+        covs = [r.coverages for _, r, _ in jobs]
+        at = 0
+        with _open_text(junction_file) as names:
+            for i, text in enumerate(names):
+                if line[at] != i:
+                    continue
+                tokens = text.strip().split("\t")
+                if len(tokens) < 8:
+                    raise ValueError("line %d of %s has %d tab-separated fields, an intropolis line has 8" % (i, junction_file, len(tokens)))
+                start = str(int(tokens[1]) - 2)
+                old = dict(zip((int(x) for x in tokens[6].split(",")), (int(x) for x in tokens[7].split(","))))
+                while at < len(line) and line[at] == i:
+                    q, p = job[at], pos[at]
+                    ranks = found[q][p]
+                    sample_ids = [jobs[q][2][r] for r in ranks]
+                    cov = covs[q][p]
+                    for s, c in zip(sample_ids, cov):
+                        if old.get(s) != c:
+                            raise ValueError("line %d of %s does not list sample %d with coverage %d: it is not the file "
+                                             "that was indexed" % (i, junction_file, s, c))
+                    out = list(tokens)
+                    out[1] = start
+                    out[6] = ",".join(str(s) for s in sample_ids)
+                    out[7] = ",".join(str(c) for c in cov)
+                    handles[q].write("\t".join(out) + "\t" + str(ranks) + "\n")
+                    at += 1
+                if at == len(line):
+                    break
+        if at < len(line):
+            raise ValueError("%s ends before line %d: it is not the file that was indexed" % (junction_file, line[at]))
+    finally:
+        for fh in handles:
+            fh.close()

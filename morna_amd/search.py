@@ -58,6 +58,8 @@ class MornaSearch(object):
         """rank / world: one process per shard of an index built with --shards (shards.DistShards); None: this process
         holds the whole index (or all of its shards, shards.LocalShards)."""
         self.basename = basename
+        self._device = int(device[0] if isinstance(device, (list, tuple)) else device)
+        self._junction_store = None
         with open(basename + ".stats.mor") as stats_stream:
             self.sample_count = int(stats_stream.readline())
             self.index_size = int(stats_stream.readline())
@@ -243,6 +245,35 @@ class MornaSearch(object):
             internal.append(self.internal_id_map[query_id])
         ids, d, cnt = self.annoy_index.get_nns_by_item_batch(np.array(internal, np.int32), num_neighbors, search_k)
         return internal, self._batch_results(ids, d, cnt, include_distances, meta_db)
+
+    # ---- junctions of the results (morna.py:1486-1569) ----------------------------------------------------------
+    def junction_store(self):
+        """<basename>.junc.mor, loaded on first use."""
+        if self._junction_store is None:
+            from .junctions import STORE_SUFFIX, JunctionStore
+            from .shards import DistShards
+            if isinstance(self.annoy_index, DistShards):
+                raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                                   "run it in one process, which loads every shard of the index")
+            path = self.basename + STORE_SUFFIX
+            if not os.path.exists(path):
+                raise IOError("%s not found: this index has no junction store; build it with `morna index "
+                              "--junction-store`" % path)
+            self._junction_store = JunctionStore.load(path, device=self._device)
+        return self._junction_store
+
+    def result_sample_ids(self, result_list):
+        """External sample ids of a list of internal ids (inverse_lookup, morna.py:1501-1504)."""
+        inv = self._inverse_map()
+        return [inv[int(i)] for i in result_list]
+
+    def retain_junctions(self, result_lists, frequency_filter, coverage_filter):
+        """The junctions to hand to the aligner for each list of results (internal ids in rank order, as search_nn
+        returns them; at most 64 per list): those found in at least ceil(frequency_filter * len(list)) of the list's
+        samples, or covered at least coverage_filter times in one of them (morna.py:1539-1569).  All lists are answered
+        in one call on the GPU.  Returns one junctions.Retained per list: lines, found_in, coverages."""
+        store = self.junction_store()
+        return store.retain([self.result_sample_ids(lst) for lst in result_lists], frequency_filter, coverage_filter)
 
     def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False):
         """Neighbours of an indexed sample (morna.py:733-787)."""
