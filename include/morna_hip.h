@@ -224,6 +224,36 @@ int morna_jretained_query(const morna_jretained *r, int64_t q, const int32_t **l
 int morna_jretained_free(morna_jretained *r);
 int morna_jstore_timers(const morna_jstore *s, double *ms, int64_t *bytes);
 
+/*
+ * ---- unhashed TF-IDF search over the junction store -------------------------------------------------
+ * The store is the sample-major CSR of the UNHASHED matrix: dimension j is file line j, a sample's component there is
+ * RN(double(coverage) * w[j]).  The distance is cosine_distance's (morna.py:101-114) with its sums taken in ascending
+ * line order, `sqrt(max(radicand, 0.0))` at the end; answers are bit-identical to that loop, on every run.
+ *   morna_jstore_set_weights  w[n_lines]: the weight of every line; n_lines must be the store's.  Every weight is 0 or a
+ *                             finite number in [2^-200, 2^64] (MORNA_E_INVALID naming the line otherwise).  No GPU work:
+ *                             the weights go to the device, and the row norms are made, at the first search after it.
+ *   morna_jstore_nearest      nq sparse queries: query q holds lines q_line[q_ptr[q] .. q_ptr[q + 1]), ascending, distinct
+ *                             and below n_lines, with coverages q_cov >= 0 (MORNA_E_INVALID otherwise); the library forms
+ *                             coverage * w itself.  The population is the store samples pop_ext[n_pop] (external ids,
+ *                             distinct); results are POSITIONS in pop_ext.  ids_out / dist_out [nq][k], count_out[nq]:
+ *                             ascending distance, equal distances by descending position, min(k, n_pop) results and the
+ *                             rest -1 / +inf.  1 <= k <= 1024 (MORNA_E_INVALID names the limit).  A negative coverage in a
+ *                             population row is MORNA_E_INVALID naming sample and line; an id the store lacks (or one named
+ *                             twice in pop_ext) MORNA_E_RANGE naming it.  Any nq: the queries are tiled inside the call.
+ *   morna_jstore_nearest_by_sample   the same with the queries taken from the store rows q_ext[nq] (external ids, need not
+ *                             be in the population): nothing but ids crosses to the device.
+ *   morna_jstore_nearest_stats       of the last call, stats[8]: candidates re-ranked in all, the most for one query, passes
+ *                             over the store, kernel ms (HIP events), algorithmic bytes (8 per store entry of the population
+ *                             per pass), queries per pass (QT), kernel ms of the row-norm pass (0 when cached), the window.
+ */
+#define MORNA_JNEAREST_MAX_K 1024
+int morna_jstore_set_weights(morna_jstore *s, const double *w, int64_t n_lines);
+int morna_jstore_nearest(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop, const int64_t *q_ptr, const int32_t *q_line,
+                         const int32_t *q_cov, int64_t nq, int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out);
+int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop, const int64_t *q_ext, int64_t nq,
+                                   int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out);
+int morna_jstore_nearest_stats(const morna_jstore *s, double *stats);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

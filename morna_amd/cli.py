@@ -38,11 +38,19 @@ patterns similar to those in a query sample (MI355X build of the index/search ho
 """
 
 
+class _StoreGiven(argparse.Action):
+    """store, and note in <dest>_given that the flag was on the command line"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
 def add_search_parameters(subparser):
     subparser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
                            help='path to junction index basename for search')
     subparser.add_argument('-v', '--verbose', action='store_const', const=True, default=False, help='be talkative')
-    subparser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100,
+    subparser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
                            help='a larger value makes for more accurate search')
     subparser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
                            help='one of {sam, bed, raw}')
@@ -71,6 +79,10 @@ def add_search_parameters(subparser):
     subparser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
                            help='comma-separated sample ids already in the index, searched together: one block per id, '
                                 '"# query <id>" and then what -q <id> prints')
+    subparser.add_argument('--unhashed', action='store_const', const=True, default=False,
+                           help='rank by the TF-IDF cosine distance over the junctions themselves, one dimension per '
+                                'line of the indexed file, instead of the hashed features (needs the store and weights '
+                                'of `index --junction-store`; `search` only)')
     subparser.add_argument('--device', type=str, default='0',
                            help='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
                                 'dealt to these devices in turn')
@@ -118,9 +130,14 @@ def build_parser():
                                    '(a second parse of the file, every line kept, transposed on the GPU); without this '
                                    'flag a store left by an earlier index of the same basename is removed')
     add_search_parameters(search_parser)
+    search_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None, dest='unhashed_junction_file',
+                               help='with --unhashed and a query that is not already in the index (a stream, --intropolis): '
+                                    'path to the (gzipped) intropolis file the index was made from, which names the '
+                                    'junction of every line')
     junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
                                                                'results for a second alignment pass')
     add_search_parameters(junctions_parser)                    # morna.py:1023
+    junctions_parser.set_defaults(unhashed_junction_file=None)   # (search's --junction-file: the unhashed search's; not this one)
     junctions_parser.add_argument('-i', '--index', metavar='<idx>', type=str, required=False, default=None,
                                   help='accepted for compatibility and ignored (the aligner\'s index; morna.py:1025)')
     junctions_parser.add_argument('-p1', '--pass1-sam', metavar='<sam>', type=str, required=False, default="pass1.sam",
@@ -157,6 +174,22 @@ def _check_batch_flags(parser, args):
             parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
 
 
+def _check_unhashed_flags(parser, args):
+    """--unhashed: `search` only, without the flags of the hashed searches; a query from outside the index needs the file
+    that names the lines."""
+    if not args.unhashed:
+        return
+    if args.subparser_name == 'junctions':
+        parser.error("--unhashed cannot be used with junctions")
+    for flag, on in (("-e/--exact", args.exact), ("-c/--convergence-backoff", args.convergence_backoff is not None),
+                     ("-rl/--rawlist", args.rawlist), ("--search-k", getattr(args, "search_k_given", False))):
+        if on:
+            parser.error("--unhashed cannot be used with %s" % flag)
+    if args.query_id is None and args.query_ids is None and args.unhashed_junction_file is None:
+        parser.error("--unhashed with a query from %s needs --junction-file, the intropolis file the index was made from"
+                     % ("--intropolis" if args.intropolis is not None else "a stream"))
+
+
 def _check_junction_flags(parser, args):
     """`junctions`: the filter's two parts, what the result limit allows, and the flags that make no sense here."""
     from .junctions import parse_junction_filter
@@ -174,6 +207,7 @@ def main(argv=None, stdin=None, stdout=None):
     args = parser.parse_args(argv)
     if args.subparser_name in ('search', 'junctions'):
         _check_batch_flags(parser, args)
+        _check_unhashed_flags(parser, args)
     if args.subparser_name == 'junctions':
         _check_junction_flags(parser, args)
     stdin = stdin or sys.stdin
@@ -212,6 +246,9 @@ def main(argv=None, stdin=None, stdout=None):
         if not os.path.exists(args.basename + STORE_SUFFIX):
             raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
                           % (args.basename + STORE_SUFFIX))
+    if args.unhashed and world > 1 and os.path.exists(args.basename + ".shards.mor"):
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
     if world > 1 and os.path.exists(args.basename + ".shards.mor"):
         # torchrun with one process per shard: every rank runs this function with the same query (rank 0 reads the stream
         # and hands it over) and calls the same collectives; rank 0 prints
@@ -230,6 +267,8 @@ def main(argv=None, stdin=None, stdout=None):
     else:
         searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
     try:
+        if args.unhashed:
+            return _search_unhashed(args, searcher, stdin, stdout)
         if junctions:
             return _junctions(args, searcher, stdin, stdout)
         return _search(args, searcher, stdin, stdout, dist, rank)
@@ -263,6 +302,43 @@ def _junctions(args, searcher, stdin, stdout):
     sys.stderr.flush()
     write_splice_files(args.junction_file, jobs)
     return rc
+
+
+def _search_unhashed(args, searcher, stdin, stdout):
+    """search --unhashed: the queries of `search`, ranked in the space of the junctions themselves; printed as `search`
+    prints them."""
+    from .junctions import intropolis_query_terms, key_lines, query_terms
+    from .search import results_output
+    from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
+    by_item = args.query_ids if args.query_ids is not None else ([args.query_id] if args.query_id is not None else None)
+    if by_item is not None:
+        results = searcher.unhashed_search_member_n_batch(by_item, args.results, include_distances=args.distances,
+                                                          meta_db=args.metadata)
+        for query_id, res in zip(by_item, results):
+            if args.query_ids is not None:
+                stdout.write("# query %d\n" % query_id)
+            stdout.write("querying by sample id " + str(query_id) + "\n")      # search_member_n's two lines
+            stdout.write("this is internal id " + str(searcher.internal_id_map[query_id]) + "\n")
+            results_output(res, stdout)
+        return 0
+    store, w = searcher.unhashed_store()
+    key_line = key_lines(args.unhashed_junction_file, store.n_lines)
+    if args.intropolis is not None:
+        sample_ids, terms = intropolis_query_terms(args.intropolis, key_line, w)
+        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata)
+        for sample_id, res in zip(sample_ids, results):
+            stdout.write("# query %d\n" % sample_id)
+            results_output(res, stdout)
+        return 0
+    gen = {"sam": junctions_from_sam_stream, "bed": junctions_from_bed_stream, "raw": junctions_from_raw_stream}[args.format]
+    coverage = {}
+    for junction in gen(stdin):                                # summed per junction, as update_query sums them
+        key = " ".join(str(_) for _ in junction[:3])
+        coverage[key] = coverage.get(key, 0) + int(junction[3])
+    results = searcher.unhashed_search_nn_batch([query_terms(coverage, key_line, w)], args.results,
+                                                include_distances=args.distances, meta_db=args.metadata)
+    results_output(results[0], stdout)
+    return 0
 
 
 def _search_batch(args, searcher, stdout, collect=None):

@@ -35,32 +35,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.hpp"
+#include "jstore.hpp"
 
 using morna::DevBuf;
+using morna::EventPair;
 using morna::set_error;
-
-struct morna_jstore {
-    int32_t device = 0;
-    int64_t n_lines = 0;
-    // host image (what save writes)
-    std::vector<int64_t> ext_ids;   // [S] external sample id, the parse's first-seen order
-    std::vector<int64_t> ptr{0};    // [S + 1]
-    std::vector<int32_t> line, cov; // [nnz]
-    std::unordered_map<int64_t, int32_t> row_of;   // external sample id -> row
-    // HBM image (made by build, or at the first retain of a loaded store)
-    bool resident = false;
-    hipStream_t stream = nullptr;
-    DevBuf<int64_t> d_ptr;
-    DevBuf<int32_t> d_line, d_cov;
-    // kernel time of the build and of the last retain (HIP events), with their algorithmic bytes
-    double ms[2] = {0, 0};
-    int64_t bytes[2] = {0, 0};
-    ~morna_jstore()
-    {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
 
 struct morna_jretained {
     int64_t nq = 0;
@@ -421,21 +400,6 @@ int make_resident(morna_jstore *st)
     return MORNA_OK;
 }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    int create()
-    {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        return MORNA_OK;
-    }
-};
-
 int build_impl(morna_jstore *st, const morna_lines *L)
 {
     int64_t counts[8], info[4];
@@ -638,6 +602,8 @@ int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_resul
 }
 
 }  // namespace
+
+int morna::jstore_make_resident(morna_jstore *st) { return make_resident(st); }
 
 extern "C" {
 

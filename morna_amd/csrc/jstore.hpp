@@ -1,0 +1,55 @@
+// jstore.hpp -- the junction store as jstore.hip (build, load, filter) and nearest.hip (unhashed search) share it.
+#pragma once
+#include <memory>
+#include <unordered_map>
+#include <vector>
+
+#include "common.hpp"
+
+struct morna_jnearest;   // nearest.hip: weights, cached row norms and statistics of the unhashed search
+
+struct morna_jstore {
+    int32_t device = 0;
+    int64_t n_lines = 0;
+    // host image (what save writes)
+    std::vector<int64_t> ext_ids;   // [S] external sample id, the parse's first-seen order
+    std::vector<int64_t> ptr{0};    // [S + 1]
+    std::vector<int32_t> line, cov; // [nnz]
+    std::unordered_map<int64_t, int32_t> row_of;   // external sample id -> row
+    // HBM image (made by build, or at the first retain / nearest of a loaded store)
+    bool resident = false;
+    hipStream_t stream = nullptr;
+    morna::DevBuf<int64_t> d_ptr;
+    morna::DevBuf<int32_t> d_line, d_cov;
+    // kernel time of the build and of the last retain (HIP events), with their algorithmic bytes
+    double ms[2] = {0, 0};
+    int64_t bytes[2] = {0, 0};
+    std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
+    ~morna_jstore()
+    {
+        nearest.reset();   // its buffers go before the stream does
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace morna {
+
+// the store's stream exists and its host image is in HBM (jstore.hip)
+int jstore_make_resident(morna_jstore *st);
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int create()
+    {
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        return MORNA_OK;
+    }
+};
+
+}  // namespace morna

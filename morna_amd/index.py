@@ -373,7 +373,7 @@ def go_index_native(intropolis, basename, features, n_trees, sample_count, sampl
         built = _go_index_sharded(parsed, basename, features, n_trees, sample_threshold, buffer_size, verbose, metafile,
                                   device, save, seed, shards, rank)
         if save and (rank is None or rank == 0):       # one global store, keyed by external sample id; rank 0 writes it
-            _junction_store(intropolis, basename, parsed.sample_count, device, junction_store)
+            _junction_store(intropolis, basename, parsed.sample_count, device, junction_store, sample_threshold)
         return built
     morna_index = MornaIndex(parsed.sample_count, basename, dim=features, sample_threshold=sample_threshold,
                              metafile=metafile, buffer_size=buffer_size, device=device)
@@ -392,17 +392,19 @@ def go_index_native(intropolis, basename, features, n_trees, sample_count, sampl
     AnnoyIndex.build(morna_index, n_trees, seed=seed)
     if save:
         morna_index.save(basename)
-        _junction_store(intropolis, basename, parsed.sample_count, device, junction_store)
+        _junction_store(intropolis, basename, parsed.sample_count, device, junction_store, sample_threshold)
     return morna_index
 
 
-def _junction_store(intropolis, basename, sample_count, device, wanted):
+def _junction_store(intropolis, basename, sample_count, device, wanted, sample_threshold):
     """<basename>.junc.mor next to the index files just written: built from a SECOND parse of the file (threshold 0: the
     store holds the lines under the index's threshold too, morna.py:359 vs 361-363), or removed when this index has
-    none -- a store left by an earlier index of the same basename would describe another file."""
+    none -- a store left by an earlier index of the same basename would describe another file.  The same parse gives
+    <basename>.jw.mor, the line weights of `search --unhashed` (junctions.line_weights), with the index's sample count
+    and threshold."""
     from .junctions import build_store, remove_stale_store
     if wanted:
-        build_store(intropolis, basename, sample_count, device=device)
+        build_store(intropolis, basename, sample_count, device=device, sample_threshold=sample_threshold)
     else:
         remove_stale_store(basename)
 
@@ -458,7 +460,7 @@ def go_index(intropolis, basename, features, n_trees, sample_count, sample_thres
     morna_index.build(n_trees, verbose=verbose, seed=seed)
     if save:
         morna_index.save(basename)
-        _junction_store(intropolis, basename, sample_count, device, junction_store)
+        _junction_store(intropolis, basename, sample_count, device, junction_store, sample_threshold)
     return morna_index
 
 

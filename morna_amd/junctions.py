@@ -20,6 +20,9 @@ from ._lib import check, lib, ptr
 
 MAX_RESULTS = 64        # found_in is one 64-bit word per line (morna_jstore_retain)
 STORE_SUFFIX = ".junc.mor"
+WEIGHTS_SUFFIX = ".jw.mor"      # the line weights of the unhashed search (save_weights)
+WEIGHTS_MAGIC = b"MORNAJW1"
+MAX_NEAREST = 1024              # neighbours per query of the unhashed search (MORNA_JNEAREST_MAX_K)
 
 
 def parse_junction_filter(text):
@@ -127,6 +130,56 @@ class JunctionStore(object):
         check(lib().morna_jstore_timers(self._p, ptr(ms), ptr(nbytes)))
         return {"build": (float(ms[0]), int(nbytes[0])), "retain": (float(ms[1]), int(nbytes[1]))}
 
+    # ---- unhashed TF-IDF search (csrc/nearest.hip) -------------------------------------------------
+    def set_weights(self, w):
+        """The weight of every line (line_weights / load_weights): len(w) must be the store's line count, every weight
+        0 or a finite number in [2^-200, 2^64]; ValueError otherwise.  No GPU work before the first search."""
+        w = np.ascontiguousarray(w, np.float64)
+        if w.ndim != 1:
+            raise ValueError("set_weights takes one weight per line (a 1-d array)")
+        check(lib().morna_jstore_set_weights(self._p, ptr(w), len(w)))
+
+    def _nearest_out(self, nq, k):
+        return np.zeros((nq, k), np.int32), np.zeros((nq, k), np.float64), np.zeros(nq, np.int32)
+
+    def nearest(self, population, queries, k):
+        """The k nearest samples of `population` (external sample ids; results are positions in it) to every query, a
+        (lines ascending, coverages >= 0) pair each, by the unhashed cosine distance.  Returns (ids [nq][k] int32,
+        distances [nq][k] fp64, counts [nq]): ascending distance, equal distances by descending position, -1 / +inf
+        past min(k, len(population)).  IndexError for a population id the store lacks, ValueError for a negative
+        coverage, unsorted lines, or k outside [1, 1024]."""
+        pop = np.ascontiguousarray(population, np.int64)
+        queries = [(np.ascontiguousarray(l, np.int32), np.ascontiguousarray(c, np.int32)) for l, c in queries]
+        for l, c in queries:
+            if l.ndim != 1 or l.shape != c.shape:
+                raise ValueError("an unhashed query is a pair of 1-d arrays of one length: lines and coverages")
+        q_ptr = np.zeros(len(queries) + 1, np.int64)
+        np.cumsum([len(l) for l, _ in queries], out=q_ptr[1:])
+        q_line = np.concatenate([l for l, _ in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+        q_cov = np.concatenate([c for _, c in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+        ids, d, cnt = self._nearest_out(len(queries), max(int(k), 1))
+        check(lib().morna_jstore_nearest(self._p, ptr(pop), len(pop), ptr(q_ptr), ptr(q_line), ptr(q_cov), len(queries), int(k),
+                                         ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
+    def nearest_by_sample(self, population, query_sample_ids, k):
+        """nearest() with the store's own rows as the queries (external sample ids, in the population or not): only ids
+        go to the device."""
+        pop = np.ascontiguousarray(population, np.int64)
+        q = np.ascontiguousarray(query_sample_ids, np.int64)
+        ids, d, cnt = self._nearest_out(len(q), max(int(k), 1))
+        check(lib().morna_jstore_nearest_by_sample(self._p, ptr(pop), len(pop), ptr(q), len(q), int(k), ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
+    def nearest_stats(self):
+        """Of the last nearest / nearest_by_sample: candidates re-ranked in all and the most for one query, passes over
+        the store, kernel ms (HIP events), algorithmic bytes (8 per store entry of the population per pass), queries per
+        pass, kernel ms of the row-norm pass (0.0 when the norms were cached), and the selection window."""
+        s = np.zeros(8, np.float64)
+        check(lib().morna_jstore_nearest_stats(self._p, ptr(s)))
+        return {"candidates": int(s[0]), "max_candidates": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]),
+                "bytes": int(s[4]), "queries_per_pass": int(s[5]), "norms_ms": float(s[6]), "window": float(s[7])}
+
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
         order, at most 64 per list) in one call on the GPU.  Returns one Retained per list."""
@@ -163,21 +216,133 @@ class JunctionStore(object):
             lib().morna_jretained_free(r)
 
 
-def build_store(intropolis, basename, sample_count, device=0):
+def line_weights(parsed, sample_threshold):
+    """The unhashed search's weight of every line of a threshold-0 parse: the parse's own idf,
+    log(float(sample_count) / samples listed) (morna.py:372-374), for a line that lists at least `sample_threshold`
+    samples, 0.0 for a line the index skipped.  None when a "chrom start end" key repeats in the file: the index then
+    weighs a line by its key's cumulative frequency and sums the repeats into one term, which is not this definition."""
+    if parsed.n_keys != parsed.lines_read or parsed.n_lines != parsed.lines_read:
+        return None
+    a = parsed.arrays()
+    w = np.array(a["idf"], np.float64)
+    w[np.diff(a["row_ptr"]) < int(sample_threshold)] = 0.0
+    return w
+
+
+def save_weights(path, w, sample_count, sample_threshold):
+    """<basename>.jw.mor: "MORNAJW1", n_lines, sample_count, threshold (int64 each), w[n_lines] fp64, little-endian."""
+    import os
+    w = np.ascontiguousarray(w, "<f8")
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    with open(tmp, "wb") as fh:
+        fh.write(WEIGHTS_MAGIC)
+        fh.write(np.array([len(w), int(sample_count), int(sample_threshold)], "<i8").tobytes())
+        fh.write(w.tobytes())
+    os.replace(tmp, path)
+
+
+def load_weights(path, n_lines=None):
+    """(w, sample_count, sample_threshold) of a weights file; IOError for a missing or truncated file, one that is not a
+    weights file, or one whose line count is not `n_lines` (the store's)."""
+    try:
+        with open(path, "rb") as fh:
+            blob = fh.read()
+    except (IOError, OSError) as e:
+        raise IOError("%s: %s" % (path, e))
+    if len(blob) < 32 or blob[:8] != WEIGHTS_MAGIC:
+        raise IOError("%s is not a weights file of the unhashed search (or is truncated)" % path)
+    n, sample_count, threshold = [int(x) for x in np.frombuffer(blob, "<i8", 3, 8)]
+    if n < 0 or len(blob) != 32 + 8 * n:
+        raise IOError("%s is truncated or damaged: %d bytes do not hold %d weights" % (path, len(blob), n))
+    if n_lines is not None and n != int(n_lines):
+        raise IOError("%s holds the weights of %d lines, the junction store has %d: they are not of the same index"
+                      % (path, n, int(n_lines)))
+    return np.frombuffer(blob, "<f8", n, 32).astype(np.float64), sample_count, threshold
+
+
+def build_store(intropolis, basename, sample_count, device=0, sample_threshold=None):
     """`morna index --junction-store`: the intropolis file parsed once more with threshold 0 -- every line kept, so kept
-    line j is file line j -- then transposed on the GPU and saved as <basename>.junc.mor."""
+    line j is file line j -- then transposed on the GPU and saved as <basename>.junc.mor.  With the index's
+    sample_threshold, the same parse also gives <basename>.jw.mor, the line weights of `search --unhashed` -- unless a key
+    repeats in the file (line_weights), which one line on stderr reports."""
     from .index import ParsedLines
     parsed = ParsedLines(intropolis, sample_count=max(1, int(sample_count or 0)), sample_threshold=0)
     store = JunctionStore.build(parsed, device=device)
     store.save(basename + STORE_SUFFIX)
+    write_weights(parsed, basename, sample_threshold, intropolis)
     return store
 
 
-def remove_stale_store(basename):
-    """An index written without --junction-store must not be found next to the store of an earlier one."""
+def write_weights(parsed, basename, sample_threshold, source="the indexed file"):
+    """<basename>.jw.mor from the threshold-0 parse of the indexed file; True when written.  A weights file of an earlier
+    index goes first; sample_threshold None writes none; a file with repeated junctions gets none and one line on stderr."""
     import os
-    if os.path.exists(basename + STORE_SUFFIX):
-        os.remove(basename + STORE_SUFFIX)
+    import sys
+    path = basename + WEIGHTS_SUFFIX
+    if os.path.exists(path):
+        os.remove(path)
+    if sample_threshold is None:
+        return False
+    w = line_weights(parsed, sample_threshold)
+    if w is None:
+        sys.stderr.write("%s not written: the %d lines of %s hold %d distinct junctions, and the unhashed search is defined "
+                         "for files without repeated junctions\n" % (path, parsed.lines_read, source, parsed.n_keys))
+        return False
+    save_weights(path, w, parsed.sample_count, sample_threshold)
+    return True
+
+
+def remove_stale_store(basename):
+    """An index written without --junction-store must not be found next to the store of an earlier one, nor next to
+    that store's weights."""
+    import os
+    for suffix in (STORE_SUFFIX, WEIGHTS_SUFFIX):
+        if os.path.exists(basename + suffix):
+            os.remove(basename + suffix)
+
+
+def key_lines(junction_file, n_lines=None):
+    """"chrom start end" -> line number of the indexed intropolis file, from the key arrays of a threshold-0 parse;
+    ValueError when the file's line count is not `n_lines` (the store's)."""
+    from .index import ParsedLines
+    parsed = ParsedLines(junction_file, sample_count=1, sample_threshold=0)
+    if n_lines is not None and parsed.lines_read != int(n_lines):
+        raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
+                         % (junction_file, parsed.lines_read, int(n_lines)))
+    a = parsed.arrays()
+    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
+    return {blob[off[j]:off[j + 1]].decode("ascii"): j for j in range(parsed.n_lines)}
+
+
+def query_terms(coverage_by_key, key_line, w):
+    """One unhashed query: {"chrom start end": summed coverage} -> (lines ascending, coverages) int32 arrays.  Keys the
+    file lacks and keys on lines of weight 0 drop out."""
+    pairs = sorted((key_line[key], int(c)) for key, c in coverage_by_key.items() if key in key_line and w[key_line[key]] != 0.0)
+    return (np.array([p[0] for p in pairs], np.int32), np.array([p[1] for p in pairs], np.int32))
+
+
+def intropolis_query_terms(path, key_line, w):
+    """Every sample of the intropolis file `path` as an unhashed query: (sample ids in first-seen order, one
+    (lines, coverages) pair per sample), the coverages of a key the file repeats summed per sample as update_query and
+    morna_lines_query_terms sum them."""
+    from .index import ParsedLines
+    parsed = ParsedLines(path, sample_count=1, sample_threshold=0)
+    a = parsed.arrays()
+    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
+    at = np.array([key_line.get(blob[off[j]:off[j + 1]].decode("ascii"), -1) for j in range(parsed.n_lines)], np.int64)
+    at[at >= 0] = np.where(np.asarray(w)[at[at >= 0]] != 0.0, at[at >= 0], -1)
+    line = np.repeat(at, np.diff(a["row_ptr"]))
+    keep = line >= 0
+    n_lines = max(len(w), 1)
+    cell, inv = np.unique(np.asarray(a["ids"], np.int64)[keep] * n_lines + line[keep], return_inverse=True)
+    cov = np.zeros(len(cell), np.int64)
+    np.add.at(cov, inv.reshape(-1), np.asarray(a["cov"], np.int64)[keep])
+    if len(cov) and cov.max() > 2**31 - 1:
+        raise ValueError("%s: a query sample's summed coverage of one junction passes 2^31 - 1" % path)
+    sample, line = cell // n_lines, cell % n_lines
+    cut = np.searchsorted(sample, np.arange(parsed.n_items + 1))
+    terms = [(line[cut[s]:cut[s + 1]].astype(np.int32), cov[cut[s]:cut[s + 1]].astype(np.int32)) for s in range(parsed.n_items)]
+    return [int(x) for x in a["ext_ids"]], terms
 
 
 def _open_text(path):

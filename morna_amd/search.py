@@ -275,6 +275,47 @@ class MornaSearch(object):
         store = self.junction_store()
         return store.retain([self.result_sample_ids(lst) for lst in result_lists], frequency_filter, coverage_filter)
 
+    # ---- unhashed TF-IDF search: no counterpart the reference finished -------------------------
+    def unhashed_store(self):
+        """The junction store with the line weights of <basename>.jw.mor set, and those weights; on first use."""
+        if getattr(self, "_unhashed_weights", None) is None:
+            from .junctions import WEIGHTS_SUFFIX, load_weights
+            store = self.junction_store()
+            path = self.basename + WEIGHTS_SUFFIX
+            if not os.path.exists(path):
+                raise IOError("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
+                              "to the junction store. They are not written when a junction repeats in the indexed file: "
+                              "the unhashed search is defined for files without repeated junctions" % path)
+            w, _, _ = load_weights(path, store.n_lines)
+            store.set_weights(w)
+            self._unhashed_weights = w
+        return self.junction_store(), self._unhashed_weights
+
+    def _unhashed_population(self):
+        """The items of the index as external sample ids, in internal-id order."""
+        inv = self._inverse_map()
+        return np.array([inv[i] for i in range(len(inv))], np.int64)
+
+    def unhashed_search_member_n_batch(self, query_ids, num_neighbors, include_distances=True, meta_db=False):
+        """The unhashed neighbours of several indexed sample ids: a list of result tuples in query order, as
+        exact_search_nn_batch returns them (internal ids); an unknown id fails with search_member_n's message."""
+        for query_id in query_ids:
+            if query_id not in self.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+        store, _ = self.unhashed_store()
+        ids, d, cnt = store.nearest_by_sample(self._unhashed_population(), [int(q) for q in query_ids], num_neighbors)
+        return self._batch_results(ids, d, cnt, include_distances, meta_db)
+
+    def unhashed_search_nn_batch(self, term_lists, num_neighbors, include_distances=True, meta_db=False):
+        """The unhashed neighbours of queries given as (lines ascending, coverages) pairs over the lines of the indexed
+        file (junctions.query_terms / intropolis_query_terms): a list of result tuples in query order."""
+        store, _ = self.unhashed_store()
+        ids, d, cnt = store.nearest(self._unhashed_population(), term_lists, num_neighbors)
+        return self._batch_results(ids, d, cnt, include_distances, meta_db)
+
     def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False):
         """Neighbours of an indexed sample (morna.py:733-787)."""
         print("querying by sample id " + str(query_id))
