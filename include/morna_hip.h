@@ -254,6 +254,37 @@ int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int6
                                    int32_t k, int32_t *ids_out, double *dist_out, int32_t *count_out);
 int morna_jstore_nearest_stats(const morna_jstore *s, double *stats);
 
+/*
+ * ---- junction recovery tables over the filter grid -------------------------------------------------
+ * How much of a truth set of lines the retention step gives back under EVERY (frequency, coverage) pair of a grid, from
+ * one pass over the result rows.  (The quantities are those junction_recovery_performance.py of the reference's tests/
+ * prints per run of its aligner pipeline; here the truth comes from the store or from the caller.)  For list q and line j:
+ * cnt = the ranks r < n_results[q] whose row holds j (an id at two ranks counts twice, as retain's one bit per rank does),
+ * maxcov = the largest coverage of j among those rows, b = the number of i with cov_grid[i] <= maxcov (0 when cnt = 0),
+ * t = 1 when j is a true line of q.  hist_out[nq][2][65][n_grid + 1], int32: entry [q][t][cnt][b] is the number of lines of
+ * that class, except that plane t = 0 is left 0 at cnt = 0 (lines nobody holds and nobody wants).  Integer throughout:
+ * the same numbers on every run.  retain(f, cov_grid[i]) keeps exactly the lines with cnt >= 1 and (cnt >= min_count or
+ * b > i), so every cell of the grid is a sum over hist on the host.
+ *   morna_jstore_recovery            results / n_results / k as morna_jstore_retain takes them (1 <= k <= 64, MORNA_E_INVALID
+ *                             beyond, the message names the limit; an id the store lacks: MORNA_E_RANGE naming it).  Truth
+ *                             as a CSR: the true lines of list q are t_line[t_ptr[q] .. t_ptr[q + 1]), ascending, distinct
+ *                             and below the store's line count (MORNA_E_INVALID naming the list and the position otherwise).
+ *                             cov_grid[n_grid]: strictly ascending, 1 <= n_grid <= 15 (MORNA_E_INVALID naming the limit).
+ *                             nq = 0 succeeds and does no work.  Only hist leaves the device.
+ *   morna_jstore_recovery_by_sample  the same with the truth of list q taken from store row truth_ext[q] (an external id,
+ *                             in the list or not): its lines covered at least truth_min_cov times.  An id the store lacks:
+ *                             MORNA_E_RANGE naming it.
+ *   morna_jstore_recovery_stats      of the last call, stats[3]: kernel ms (HIP events), algorithmic bytes (8 per entry of the
+ *                             result and truth rows named, 4 per line of a CSR truth), workgroups launched.  All 0 after a
+ *                             call with nq = 0 or one that failed its checks.
+ */
+int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                          const int64_t *t_ptr, const int32_t *t_line, const int64_t *cov_grid, int32_t n_grid, int32_t *hist_out);
+int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                    const int64_t *truth_ext, int64_t truth_min_cov, const int64_t *cov_grid, int32_t n_grid,
+                                    int32_t *hist_out);
+int morna_jstore_recovery_stats(const morna_jstore *s, double *stats);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

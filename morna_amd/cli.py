@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -16,6 +16,13 @@ reference, all deliberate: its debug prints (shard ids, list lengths) are not
 reproduced, an empty retained set writes an empty splice file (the reference
 dies in ordered_junctions.pop(0)), -i is optional, and -c is refused.
 
+`recovery` answers the question `junctions` leaves open -- which --junction-filter and -r to use on an index: it
+searches as `search` does, and prints for every pair of a grid of filters how many junctions the results give back and
+how many of the query's true junctions are among them (the columns junction_recovery_performance.py of the
+reference's tests/ prints for one run of its aligner pipeline).  The truth is the query sample's own row of the
+store, the sample itself left out of its results (-q / --query-ids), or the same sample in a second, deeper
+intropolis file (--intropolis shallow --truth deep).  One pass on the GPU per run, whatever the size of the grid.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -29,6 +36,8 @@ here do the latter.
     python -m morna_amd.cli index --intropolis junctions.tsv.gz -x idx -s 9662 --junction-store
     python -m morna_amd.cli junctions -x idx -p1 pass1.sam --junction-file junctions.tsv.gz -sf splices.txt
     python -m morna_amd.cli junctions -x idx --intropolis new_samples.tsv.gz --junction-file junctions.tsv.gz -sf splices
+    python -m morna_amd.cli recovery -x idx --query-ids 12,34,56 -r 20 --grid 0,.05,.5:1,5,50
+    python -m morna_amd.cli recovery -x idx --intropolis shallow.tsv.gz --truth deep.tsv.gz --junction-file junctions.tsv.gz
 """
 import argparse
 import sys
@@ -153,7 +162,45 @@ def build_parser():
                                   help='intropolis-like output file with the retained junctions and, as one more field, '
                                        'the ranks of the results that hold each; a batch (--intropolis, --query-ids) '
                                        'writes <file>.<sample id> per query')
+    recovery_parser = subparsers.add_parser('recovery', help='searches a morna index and tabulates, over a grid of junction '
+                                                             'filters, how many of a query\'s true junctions its results '
+                                                             'give back')
+    add_search_parameters(recovery_parser)
+    recovery_parser.set_defaults(unhashed_junction_file=None)
+    recovery_parser.add_argument('--grid', type=str, required=False, default=None,
+                                 help='the filters to tabulate, "<f1>,<f2>,...:<c1>,<c2>,...": every frequency with every '
+                                      'coverage (at most 15 coverages); default 0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000')
+    recovery_parser.add_argument('--truth-coverage', metavar='<int>', type=int, required=False, default=1,
+                                 help='a junction is true for a query when the truth covers it at least this many times')
+    recovery_parser.add_argument('--truth', type=str, metavar='<gz>', required=False, default=None,
+                                 help='with --intropolis: the (gzipped) intropolis file that holds the true junctions of the '
+                                      'same sample ids (the samples sequenced deeply)')
+    recovery_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None,
+                                 help='with --truth: path to the (gzipped) intropolis file the index was made from, which '
+                                      'names the junction of every line')
+    recovery_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                                 help='print only the table over all queries')
     return parser
+
+
+def _check_recovery_flags(parser, args):
+    """`recovery`: the grid, the flags that make no sense here, and a query that names its truth."""
+    from .junctions import parse_recovery_grid
+    try:
+        args.grid_parts = parse_recovery_grid(args.grid)
+    except ValueError as e:
+        parser.error("--grid takes <frequencies>:<coverages>, such as 0,.05,.5:1,5,50, with at most 15 coverages (%s)" % e)
+    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist),
+                     ("-m/--metadata", args.metadata), ("-d/--distances", args.distances), ("--unhashed", args.unhashed)):
+        if on:
+            parser.error("%s cannot be used with recovery" % flag)
+    if args.query_id is None and args.query_ids is None and args.intropolis is None:
+        parser.error("recovery needs a query whose true junctions are known: -q, --query-ids, or --intropolis with --truth")
+    if args.intropolis is not None and (args.truth is None or args.junction_file is None):
+        parser.error("recovery --intropolis needs --truth, the file with the true junctions of the same samples, and "
+                     "--junction-file, the intropolis file the index was made from")
+    if args.truth is not None and args.intropolis is None:
+        parser.error("--truth cannot be used without --intropolis")
 
 
 def _check_batch_flags(parser, args):
@@ -208,6 +255,9 @@ def main(argv=None, stdin=None, stdout=None):
     if args.subparser_name in ('search', 'junctions'):
         _check_batch_flags(parser, args)
         _check_unhashed_flags(parser, args)
+    if args.subparser_name == 'recovery':
+        _check_recovery_flags(parser, args)
+        _check_batch_flags(parser, args)
     if args.subparser_name == 'junctions':
         _check_junction_flags(parser, args)
     stdin = stdin or sys.stdin
@@ -225,7 +275,7 @@ def main(argv=None, stdin=None, stdout=None):
                  native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank,
                  junction_store=args.junction_store)
         return 0
-    if args.subparser_name not in ('search', 'junctions'):
+    if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
     from .search import MornaSearch, results_output
@@ -235,7 +285,7 @@ def main(argv=None, stdin=None, stdout=None):
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dist = None
     junctions = args.subparser_name == 'junctions'
-    if junctions:
+    if args.subparser_name in ('junctions', 'recovery'):
         from .junctions import MAX_RESULTS, STORE_SUFFIX
         if world > 1 and os.path.exists(args.basename + ".shards.mor"):
             raise RuntimeError("batch search is not available with one process per shard (torchrun): "
@@ -271,6 +321,8 @@ def main(argv=None, stdin=None, stdout=None):
             return _search_unhashed(args, searcher, stdin, stdout)
         if junctions:
             return _junctions(args, searcher, stdin, stdout)
+        if args.subparser_name == 'recovery':
+            return _recovery(args, searcher, stdin, stdout)
         return _search(args, searcher, stdin, stdout, dist, rank)
     finally:
         if dist is not None:
@@ -301,6 +353,56 @@ def _junctions(args, searcher, stdin, stdout):
         jobs.append((path, kept, searcher.result_sample_ids(res[0])))
     sys.stderr.flush()
     write_splice_files(args.junction_file, jobs)
+    return rc
+
+
+def _recovery(args, searcher, stdin, stdout):
+    """The search of `search` (its result lines are not printed), then one histogram per query on the GPU and the tables
+    of every (frequency, coverage) pair of the grid from it."""
+    import contextlib
+    import io
+    import sys
+    from .junctions import format_recovery_rows, intropolis_truth, key_lines, recovery_rows, sum_recovery_rows
+    frequencies, coverages = args.grid_parts
+    wanted = args.results
+    collected = []
+    by_item = args.intropolis is None
+    if by_item:
+        args.results = wanted + 1                              # leave one out: the query is its own nearest neighbour
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):                     # (search_member_n prints its two lines itself)
+        rc = _search(args, searcher, stdin, sink, None, 0, collect=collected)
+    args.results = wanted
+    labels = [label for label, _ in collected]
+    extra = [0] * len(collected)
+    if by_item:
+        lists, truth = [], []
+        for label, res in collected:
+            own = searcher.internal_id_map[label]
+            lists.append([i for i in res[0] if i != own][:wanted])
+            truth.append(own)
+        hist = searcher.junction_recovery(lists, truth, coverages, args.truth_coverage)
+    else:
+        lists = [list(res[0])[:wanted] for _, res in collected]
+        truth_of = intropolis_truth(args.truth, key_lines(args.junction_file, searcher.junction_store().n_lines), args.truth_coverage)
+        truth = []
+        for q, label in enumerate(labels):
+            if label not in truth_of:
+                raise ValueError("query sample %d of %s is not in %s: it has no truth" % (label, args.intropolis, args.truth))
+            truth.append(truth_of[label][0])
+            extra[q] = truth_of[label][1]
+        sys.stderr.write("%d true junctions of %s are not in %s: they count as false negatives\n"
+                         % (sum(extra), args.truth, args.junction_file))
+        hist = searcher.junction_recovery(lists, truth, coverages) if lists else []
+    tables = []
+    for q, label in enumerate(labels):
+        rows = recovery_rows(hist[q], len(lists[q]), frequencies, coverages, extra_true=extra[q])
+        tables.append(rows)
+        if not args.summary_only:
+            stdout.write("# query %s\tresults %d\ttrue %d\n" % (label, len(lists[q]), rows[0]["true_positive"] + rows[0]["false_negative"]))
+            stdout.write(format_recovery_rows(rows))
+    stdout.write("# all %d queries\n" % len(tables))
+    stdout.write(format_recovery_rows(sum_recovery_rows(tables)))
     return rc
 
 

@@ -25,6 +25,13 @@
 // waves then walk the runs and OR bit `rank` into the line's word (LDS atomics: the OR is order-independent).  A
 // first pass counts the retained lines and their found_in bits per tile; a scan over the tiles of a query gives each
 // tile its place; the second pass writes the lines ascending, their words and the coverages in rank order.
+//
+// Recovery: the same grid and the same walk as the filter's first pass, but what leaves the tile is a
+// histogram, not lines.  Whether a line is retained under ANY (frequency, coverage) pair follows from two small integers,
+// the number of results that hold it and the largest coverage among them; with a truth bit per line that is one of
+// 2 x 65 x (B + 1) classes for a grid of B coverage thresholds.  The tile counts its lines per class in LDS and adds its
+// non-zero classes to hist[q] with integer atomics: every cell of a filter grid is then a sum over classes on the host,
+// and nothing of the size of the line count comes back.
 #include <unistd.h>
 
 #include <algorithm>
@@ -319,6 +326,122 @@ __global__ __launch_bounds__(256) void jstore_tile_scan_kernel(int64_t *__restri
     }
 }
 
+// ---- recovery: the classes of every line under a result list and a truth set -------------------------------------------
+
+#define JR_MAX_GRID 15                   // coverage thresholds of one call: b takes 0 .. 15
+#define JR_COUNTS 65                     // cnt takes 0 .. 64
+
+struct JRGrid {
+    int64_t c[JR_MAX_GRID];   // strictly ascending
+    int32_t n;
+};
+
+// One workgroup per (tile, query).  hist[q][t][cnt][b] += the lines of the tile with truth bit t that cnt of the results
+// hold and whose largest coverage among them reaches b of the thresholds (b = 0 when cnt = 0); plane t = 0 at cnt = 0 is
+// not counted.  Truth: the entries of store row truth_rows[q] covered at least truth_min_cov times, or, with truth_rows
+// NULL, the lines t_line[t_ptr[q] .. t_ptr[q + 1]).
+__global__ __launch_bounds__(JT_THREADS) void jstore_recovery_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                                                     const int32_t *__restrict__ cov, int64_t n_lines, int32_t n_tiles,
+                                                                     const int32_t *__restrict__ rows, const int32_t *__restrict__ n_results,
+                                                                     int32_t k, const int32_t *__restrict__ truth_rows, int64_t truth_min_cov,
+                                                                     const int64_t *__restrict__ t_ptr, const int32_t *__restrict__ t_line,
+                                                                     JRGrid grid, int32_t *__restrict__ hist)
+{
+    __shared__ unsigned long long s_mask[JT_LINES];
+    __shared__ int32_t s_max[JT_LINES];
+    __shared__ uint32_t s_truth[JT_LINES / 32];
+    __shared__ int64_t s_lo[65], s_hi[65];   // slot 64: the truth
+    __shared__ uint32_t s_hist[2 * JR_COUNTS * (JR_MAX_GRID + 1)];
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x / n_tiles;
+    const int32_t tile = (int32_t)(blockIdx.x % n_tiles);
+    const int64_t t0 = (int64_t)tile * JT_LINES;
+    const int64_t t1 = t0 + JT_LINES < n_lines ? t0 + JT_LINES : n_lines;
+    const int nb = grid.n + 1, n_bins = 2 * JR_COUNTS * nb;
+    int32_t m = n_results[q];
+    m = m < 0 ? 0 : (m > k ? k : m);
+    const int32_t *t_arr = truth_rows ? line : t_line;
+    for (int i = tid; i < JT_LINES; i += JT_THREADS) {
+        s_mask[i] = 0;
+        s_max[i] = INT32_MIN;   // below every coverage, a negative one included
+    }
+    for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) s_truth[i] = 0;
+    for (int i = tid; i < n_bins; i += JT_THREADS) s_hist[i] = 0;
+    if (tid < 128) {   // lanes 0-63: where the tile begins in result tid's list; lanes 64-127: where it ends
+        const int r = tid & 63;
+        if (r < m) {
+            const int32_t row = rows[q * k + r];
+            const int64_t a = ptr[row], b = ptr[row + 1];
+            const int64_t at = lower_bound_line(line, a, b, tid < 64 ? t0 : t1);
+            if (tid < 64) s_lo[r] = at;
+            else s_hi[r] = at;
+        }
+    } else if (tid < 130) {   // and in the truth
+        int64_t a, b;
+        if (truth_rows) {
+            const int32_t row = truth_rows[q];
+            a = ptr[row];
+            b = ptr[row + 1];
+        } else {
+            a = t_ptr[q];
+            b = t_ptr[q + 1];
+        }
+        const int64_t at = lower_bound_line(t_arr, a, b, tid == 128 ? t0 : t1);
+        if (tid == 128) s_lo[64] = at;
+        else s_hi[64] = at;
+    }
+    __syncthreads();
+    const int wave = tid / WAVE, lane = tid % WAVE;
+    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
+        const int64_t hi = s_hi[r];
+        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
+            const int64_t l = (int64_t)line[i] - t0;
+            if (l < 0 || l >= JT_LINES) continue;   // (cannot happen in an ascending list)
+            atomicOr(&s_mask[l], 1ull << r);
+            atomicMax(&s_max[l], cov[i]);
+        }
+    }
+    {
+        const int64_t hi = s_hi[64];
+        for (int64_t i = s_lo[64] + tid; i < hi; i += JT_THREADS) {
+            const int64_t l = (int64_t)t_arr[i] - t0;
+            if (l < 0 || l >= JT_LINES) continue;
+            if (!truth_rows || (int64_t)cov[i] >= truth_min_cov) atomicOr(&s_truth[l >> 5], 1u << (l & 31));
+        }
+    }
+    __syncthreads();
+    // thread t classifies lines [t * JT_PER, (t + 1) * JT_PER) of the tile; a run of one class is one LDS add
+    int cur = -1;
+    uint32_t run = 0;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = tid * JT_PER + j;
+        if (t0 + l >= t1) break;
+        const int c = __popcll(s_mask[l]);
+        const int t = (int)((s_truth[l >> 5] >> (l & 31)) & 1u);
+        if (c == 0 && t == 0) continue;
+        int b = 0;
+        if (c) {
+            const int64_t mx = s_max[l];
+#pragma unroll
+            for (int i = 0; i < JR_MAX_GRID; i++) b += (i < grid.n && grid.c[i] <= mx) ? 1 : 0;
+        }
+        const int bin = (t * JR_COUNTS + c) * nb + b;
+        if (bin != cur) {
+            if (run) atomicAdd(&s_hist[cur], run);
+            cur = bin;
+            run = 0;
+        }
+        run++;
+    }
+    if (run) atomicAdd(&s_hist[cur], run);
+    __syncthreads();
+    int32_t *mine = hist + q * n_bins;
+    for (int i = tid; i < n_bins; i += JT_THREADS) {
+        const uint32_t v = s_hist[i];
+        if (v) atomicAdd(&mine[i], (int32_t)v);   // at most n_lines < 2^31 in all
+    }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------
 
 const char JSTORE_MAGIC[8] = {'M', 'O', 'R', 'N', 'A', 'J', 'S', '1'};
@@ -601,6 +724,141 @@ int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_resul
     return MORNA_OK;
 }
 
+// truth_ext != NULL: truth by sample; otherwise the CSR (t_ptr, t_line)
+int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k, const int64_t *t_ptr,
+                  const int32_t *t_line, const int64_t *truth_ext, int64_t truth_min_cov, const JRGrid &grid, int32_t *hist_out)
+{
+    st->rec_ms = 0;
+    st->rec_bytes = 0;
+    st->rec_groups = 0;
+    if (nq == 0) return MORNA_OK;
+    std::vector<int32_t> rows((size_t)(nq * k), 0), truth_rows;
+    std::vector<int64_t> tp;
+    int64_t entries = 0, t_base = 0, t_n = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        if (n_results[q] < 0 || n_results[q] > k) {
+            set_error("jstore_recovery: result list %lld holds %d results, outside [0, %d]", (long long)q, n_results[q], k);
+            return MORNA_E_INVALID;
+        }
+        for (int32_t r = 0; r < n_results[q]; r++) {
+            const int64_t id = results[q * k + r];
+            auto it = st->row_of.find(id);
+            if (it == st->row_of.end()) {
+                set_error("jstore_recovery: sample id %lld (result %d of list %lld) is not in the junction store", (long long)id, r,
+                          (long long)q);
+                return MORNA_E_RANGE;
+            }
+            rows[(size_t)(q * k + r)] = it->second;
+            entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
+        }
+    }
+    if (truth_ext) {
+        truth_rows.assign((size_t)nq, 0);
+        for (int64_t q = 0; q < nq; q++) {
+            auto it = st->row_of.find(truth_ext[q]);
+            if (it == st->row_of.end()) {
+                set_error("jstore_recovery: sample id %lld (truth of list %lld) is not in the junction store", (long long)truth_ext[q],
+                          (long long)q);
+                return MORNA_E_RANGE;
+            }
+            truth_rows[(size_t)q] = it->second;
+            entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
+        }
+    } else {
+        t_base = t_ptr[0];
+        tp.assign((size_t)nq + 1, 0);
+        for (int64_t q = 0; q < nq; q++) {
+            const int64_t a = t_ptr[q], b = t_ptr[q + 1];
+            if (a < 0 || b < a) {
+                set_error("jstore_recovery: the truth offsets of list %lld do not ascend (%lld, %lld)", (long long)q, (long long)a,
+                          (long long)b);
+                return MORNA_E_INVALID;
+            }
+            for (int64_t i = a; i < b; i++)
+                if (t_line[i] < 0 || (int64_t)t_line[i] >= st->n_lines || (i > a && t_line[i] <= t_line[i - 1])) {
+                    set_error("jstore_recovery: truth line %d at position %lld of list %lld: the true lines of a list must ascend, "
+                              "distinct, inside [0, %lld)", t_line[i], (long long)(i - a), (long long)q, (long long)st->n_lines);
+                    return MORNA_E_INVALID;
+                }
+            tp[(size_t)q + 1] = b - t_base;
+        }
+        t_n = t_ptr[nq] - t_base;
+    }
+    MORNA_TRY(make_resident(st));
+    const int64_t n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
+    if (nq * n_tiles > INT32_MAX) {
+        set_error("jstore_recovery: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
+                  "pass fewer lists per call", (long long)nq, (long long)n_tiles);
+        return MORNA_E_INVALID;
+    }
+    const size_t n_hist = (size_t)nq * 2 * JR_COUNTS * (size_t)(grid.n + 1);
+    DevBuf<int32_t> d_rows, d_nres, d_truth_rows, d_tline, d_hist;
+    DevBuf<int64_t> d_tptr;
+    MORNA_TRY(d_rows.alloc((size_t)(nq * k)));
+    MORNA_TRY(d_nres.alloc((size_t)nq));
+    MORNA_TRY(d_hist.alloc(n_hist));
+    HIP_TRY(hipMemcpy(d_rows.p, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_nres.p, n_results, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (truth_ext) {
+        MORNA_TRY(d_truth_rows.alloc((size_t)nq));
+        HIP_TRY(hipMemcpy(d_truth_rows.p, truth_rows.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice));
+    } else {
+        MORNA_TRY(d_tptr.alloc((size_t)nq + 1));
+        MORNA_TRY(d_tline.alloc((size_t)std::max<int64_t>(t_n, 1)));
+        HIP_TRY(hipMemcpy(d_tptr.p, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (t_n) HIP_TRY(hipMemcpy(d_tline.p, t_line + t_base, (size_t)t_n * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    EventPair ev;
+    MORNA_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev.a, st->stream));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, n_hist * sizeof(int32_t), st->stream));
+    hipLaunchKernelGGL(jstore_recovery_kernel, dim3((unsigned)(nq * n_tiles)), dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p,
+                       st->d_cov.p, st->n_lines, (int32_t)n_tiles, d_rows.p, d_nres.p, k, (const int32_t *)d_truth_rows.p, truth_min_cov,
+                       (const int64_t *)d_tptr.p, (const int32_t *)d_tline.p, grid, d_hist.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.b, st->stream));
+    HIP_TRY(hipMemcpyAsync(hist_out, d_hist.p, n_hist * sizeof(int32_t), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    st->rec_ms = ms;
+    st->rec_bytes = 8 * entries + 4 * t_n;   // (line, coverage) of every row named, read once; a CSR truth has lines only
+    st->rec_groups = nq * n_tiles;
+    return MORNA_OK;
+}
+
+// the checks both entry points share; MORNA_OK with *grid filled
+int recovery_arguments(const morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                       const int64_t *cov_grid, int32_t n_grid, const int32_t *hist_out, JRGrid *grid)
+{
+    if (!s || nq < 0 || (nq > 0 && (!results || !n_results || !hist_out))) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (k < 1 || k > 64) {
+        set_error("jstore_recovery: %d results per list: the recovery tables take 1 to 64, as the filter does (one bit per rank in "
+                  "a 64-bit word per line)", k);
+        return MORNA_E_INVALID;
+    }
+    if (n_grid < 1 || n_grid > JR_MAX_GRID) {
+        set_error("jstore_recovery: %d coverage thresholds: a grid holds 1 to %d", n_grid, JR_MAX_GRID);
+        return MORNA_E_INVALID;
+    }
+    if (!cov_grid) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    for (int32_t i = 0; i < JR_MAX_GRID; i++) grid->c[i] = i < n_grid ? cov_grid[i] : INT64_MAX;
+    grid->n = n_grid;
+    for (int32_t i = 1; i < n_grid; i++)
+        if (cov_grid[i] <= cov_grid[i - 1]) {
+            set_error("jstore_recovery: coverage threshold %d (%lld) is not above threshold %d (%lld): the grid must ascend strictly",
+                      i, (long long)cov_grid[i], i - 1, (long long)cov_grid[i - 1]);
+            return MORNA_E_INVALID;
+        }
+    return MORNA_OK;
+}
+
 }  // namespace
 
 int morna::jstore_make_resident(morna_jstore *st) { return make_resident(st); }
@@ -826,6 +1084,53 @@ int morna_jstore_retain(morna_jstore *s, const int64_t *results, const int32_t *
     }
     if (rc != MORNA_OK) return rc;
     *out = R.release();
+    return MORNA_OK;
+}
+
+int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k, const int64_t *t_ptr,
+                          const int32_t *t_line, const int64_t *cov_grid, int32_t n_grid, int32_t *hist_out)
+{
+    JRGrid grid;
+    MORNA_TRY(recovery_arguments(s, results, n_results, nq, k, cov_grid, n_grid, hist_out, &grid));
+    if (nq > 0 && (!t_ptr || (t_ptr[nq] > t_ptr[0] && !t_line))) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    try {
+        return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, hist_out);
+    } catch (const std::exception &e) {
+        set_error("jstore_recovery: %s", e.what());
+        return MORNA_E_INVALID;
+    }
+}
+
+int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                    const int64_t *truth_ext, int64_t truth_min_cov, const int64_t *cov_grid, int32_t n_grid,
+                                    int32_t *hist_out)
+{
+    JRGrid grid;
+    MORNA_TRY(recovery_arguments(s, results, n_results, nq, k, cov_grid, n_grid, hist_out, &grid));
+    if (nq > 0 && !truth_ext) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    try {
+        return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, hist_out);
+    } catch (const std::exception &e) {
+        set_error("jstore_recovery: %s", e.what());
+        return MORNA_E_INVALID;
+    }
+}
+
+int morna_jstore_recovery_stats(const morna_jstore *s, double *stats)
+{
+    if (!s || !stats) {
+        set_error("jstore_recovery_stats: null argument");
+        return MORNA_E_INVALID;
+    }
+    stats[0] = s->rec_ms;
+    stats[1] = (double)s->rec_bytes;
+    stats[2] = (double)s->rec_groups;
     return MORNA_OK;
 }
 

@@ -24,6 +24,9 @@ struct morna_jstore {
     // kernel time of the build and of the last retain (HIP events), with their algorithmic bytes
     double ms[2] = {0, 0};
     int64_t bytes[2] = {0, 0};
+    // of the last recovery: kernel ms, algorithmic bytes, workgroups launched
+    double rec_ms = 0;
+    int64_t rec_bytes = 0, rec_groups = 0;
     std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
     ~morna_jstore()
     {

@@ -12,7 +12,7 @@ writes the text.
 """
 import ctypes as C
 import gzip
-from math import ceil
+from math import ceil, isfinite
 
 import numpy as np
 
@@ -23,6 +23,10 @@ STORE_SUFFIX = ".junc.mor"
 WEIGHTS_SUFFIX = ".jw.mor"      # the line weights of the unhashed search (save_weights)
 WEIGHTS_MAGIC = b"MORNAJW1"
 MAX_NEAREST = 1024              # neighbours per query of the unhashed search (MORNA_JNEAREST_MAX_K)
+MAX_GRID = 15                   # coverage thresholds of one recovery call (morna_jstore_recovery)
+DEFAULT_RECOVERY_GRID = "0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000"
+RECOVERY_COLUMNS = ("frequency_filter", "coverage_filter", "min_count", "retrieved", "true_positive", "false_positive",
+                    "false_negative", "precision", "recall", "fscore")
 
 
 def parse_junction_filter(text):
@@ -36,6 +40,80 @@ def parse_junction_filter(text):
 def min_count(frequency_filter, n_results):
     """Results that must hold a junction for the frequency filter to keep it (morna.py:1551)."""
     return int(ceil(frequency_filter * n_results))
+
+
+def parse_recovery_grid(text=None):
+    """--grid "<f1>,<f2>,...:<c1>,<c2>,..." as (frequencies, coverages); None is the default grid.  The frequencies are
+    kept as given, in any number and order, each the text float() reads (so that a table prints them as they were
+    typed); the coverages are integers, sorted and de-duplicated, at most 15.  ValueError otherwise."""
+    text = DEFAULT_RECOVERY_GRID if text is None else str(text)
+    halves = text.split(":")
+    if len(halves) != 2:
+        raise ValueError("--grid takes frequencies and coverages separated by a colon, such as 0,.05,.5:1,5,50 (got %r)" % (text,))
+    frequencies = [t.strip() for t in halves[0].split(",")]
+    for t in frequencies:
+        if not isfinite(float(t)):                             # (float() raises on anything that is no number)
+            raise ValueError("--grid: a frequency must be a finite number (got %r)" % (text,))
+    coverages = sorted(set(int(t) for t in halves[1].split(",")))
+    if len(coverages) > MAX_GRID:
+        raise ValueError("--grid holds %d distinct coverages: one recovery call takes at most %d" % (len(coverages), MAX_GRID))
+    return frequencies, coverages
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else float("nan")
+
+
+def _recovery_row(frequency, coverage, mc, retrieved, tp, true):
+    """One row of a recovery table from its three counts (the expressions of junction_recovery_performance.py:320-330,
+    with nan where that script would divide by zero)."""
+    p, r = _ratio(tp, retrieved), _ratio(tp, true)
+    f = 2 * p * r / (p + r) if p + r > 0 else float("nan")
+    return dict(zip(RECOVERY_COLUMNS, (frequency, coverage, mc, retrieved, tp, retrieved - tp, true - tp, p, r, f)))
+
+
+def recovery_rows(hist_q, n_results, frequencies, coverages, extra_true=0):
+    """The recovery table of one query from its histogram hist_q[2][65][B + 1] (JunctionStore.recovery made over the grid
+    `coverages`, B of them ascending): one dict of RECOVERY_COLUMNS per (frequency, coverage), frequency-major in the
+    order given.  A line of class (cnt, b) is retrieved under (f, coverages[i]) when cnt >= 1 and (cnt >= min_count(f,
+    n_results) or b > i) -- what retain(f, coverages[i]) keeps.  extra_true: true junctions that are no line of the file
+    and so can never be retrieved; they add to `true` and false_negative.  Pure host code."""
+    h = np.asarray(hist_q, np.int64)
+    if h.ndim != 3 or h.shape[0] != 2 or h.shape[2] != len(coverages) + 1:
+        raise ValueError("recovery_rows takes the histogram of one query, [2][%d][%d] for %d coverages (got shape %r)"
+                         % (h.shape[1] if h.ndim == 3 else MAX_RESULTS + 1, len(coverages) + 1, len(coverages), h.shape))
+    true = int(h[1].sum()) + int(extra_true)
+    cnt = np.arange(h.shape[1])[:, None]
+    b = np.arange(h.shape[2])[None, :]
+    rows = []
+    for frequency in frequencies:
+        mc = min_count(float(frequency), n_results)
+        for i, coverage in enumerate(coverages):
+            kept = (cnt >= 1) & ((cnt >= mc) | (b > i))
+            rows.append(_recovery_row(frequency, coverage, mc, int(h[:, kept].sum()), int(h[1][kept].sum()), true))
+    return rows
+
+
+def sum_recovery_rows(tables):
+    """The micro-average of several queries' tables (recovery_rows of the same grid): the counts summed cell by cell and
+    the ratios taken from the sums; min_count, which differs from query to query, is "-"."""
+    tables = list(tables)
+    out = []
+    for cell in zip(*tables):
+        retrieved = sum(r["retrieved"] for r in cell)
+        tp = sum(r["true_positive"] for r in cell)
+        true = sum(r["true_positive"] + r["false_negative"] for r in cell)
+        out.append(_recovery_row(cell[0]["frequency_filter"], cell[0]["coverage_filter"], "-", retrieved, tp, true))
+    return out
+
+
+def format_recovery_rows(rows):
+    """The column line and one tab-separated line per row: floats as %.12f, or nan."""
+    def cell(v):
+        if isinstance(v, float):
+            return "nan" if v != v else "%.12f" % v
+        return str(v)
+    return "\t".join(RECOVERY_COLUMNS) + "\n" + "".join("\t".join(cell(r[c]) for c in RECOVERY_COLUMNS) + "\n" for r in rows)
 
 
 class Retained(object):
@@ -179,6 +257,63 @@ class JunctionStore(object):
         check(lib().morna_jstore_nearest_stats(self._p, ptr(s)))
         return {"candidates": int(s[0]), "max_candidates": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]),
                 "bytes": int(s[4]), "queries_per_pass": int(s[5]), "norms_ms": float(s[6]), "window": float(s[7])}
+
+    # ---- recovery tables over the filter grid -------------------------------------------------------
+    def _recovery_arguments(self, result_sample_ids, coverage_grid):
+        lists = [[int(s) for s in lst] for lst in result_sample_ids]
+        k = max([len(lst) for lst in lists] + [1])
+        if k > MAX_RESULTS:
+            raise ValueError("a result list holds %d results: the recovery tables take at most %d, as the junction filter "
+                             "does" % (k, MAX_RESULTS))
+        res = np.zeros((len(lists), k), np.int64)
+        n_res = np.zeros(len(lists), np.int32)
+        for q, lst in enumerate(lists):
+            res[q, :len(lst)] = lst
+            n_res[q] = len(lst)
+        grid = np.array([min(max(int(c), -2**62), 2**62) for c in coverage_grid], np.int64)
+        hist = np.zeros((len(lists), 2, MAX_RESULTS + 1, max(min(len(grid), MAX_GRID), 0) + 1), np.int32)
+        return res, n_res, k, grid, hist
+
+    def recovery(self, result_sample_ids, truth_lines, coverage_grid):
+        """For every list of `result_sample_ids` (external sample ids in rank order, at most 64 per list) and its truth --
+        truth_lines[q]: line numbers, ascending and distinct -- the histogram from which every cell of a filter grid
+        follows (recovery_rows): int64 [nq][2][65][B + 1], entry [q][t][cnt][b] the number of lines with truth bit t that
+        cnt of the results hold and whose largest coverage among them reaches b of the B thresholds of `coverage_grid`
+        (strictly ascending, at most 15); plane t = 0 is left 0 at cnt = 0.  One pass on the GPU; only the histogram
+        comes back."""
+        res, n_res, k, grid, hist = self._recovery_arguments(result_sample_ids, coverage_grid)
+        truth = [np.ascontiguousarray(t, np.int64).reshape(-1) for t in truth_lines]
+        if len(truth) != len(n_res):
+            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (len(n_res), len(truth)))
+        for q, t in enumerate(truth):
+            if len(t) and (t.min() < 0 or t.max() >= self.n_lines):
+                raise ValueError("the truth of list %d names line %d: the store has lines 0 to %d"
+                                 % (q, int(t.min() if t.min() < 0 else t.max()), self.n_lines - 1))
+        t_ptr = np.zeros(len(truth) + 1, np.int64)
+        np.cumsum([len(t) for t in truth], out=t_ptr[1:])
+        t_line = np.concatenate(truth + [np.zeros(0, np.int64)]).astype(np.int32)
+        check(lib().morna_jstore_recovery(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(t_ptr), ptr(t_line), ptr(grid),
+                                          len(grid), ptr(hist)))
+        return hist.astype(np.int64)
+
+    def recovery_by_sample(self, result_sample_ids, truth_sample_ids, coverage_grid, truth_min_coverage=1):
+        """recovery() with the truth of list q taken from the store's own row of truth_sample_ids[q] (an external id): its
+        lines covered at least truth_min_coverage times.  Only ids go to the device."""
+        res, n_res, k, grid, hist = self._recovery_arguments(result_sample_ids, coverage_grid)
+        truth = np.ascontiguousarray([int(t) for t in truth_sample_ids], np.int64)
+        if len(truth) != len(n_res):
+            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (len(n_res), len(truth)))
+        check(lib().morna_jstore_recovery_by_sample(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(truth),
+                                                    min(max(int(truth_min_coverage), -2**62), 2**62), ptr(grid), len(grid),
+                                                    ptr(hist)))
+        return hist.astype(np.int64)
+
+    def recovery_stats(self):
+        """Of the last recovery / recovery_by_sample: kernel ms (HIP events), algorithmic bytes (8 per entry of the result
+        and truth rows named, 4 per line of a truth given as lines) and workgroups launched."""
+        s = np.zeros(3, np.float64)
+        check(lib().morna_jstore_recovery_stats(self._p, ptr(s)))
+        return {"kernel_ms": float(s[0]), "bytes": int(s[1]), "workgroups": int(s[2])}
 
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
@@ -343,6 +478,35 @@ def intropolis_query_terms(path, key_line, w):
     cut = np.searchsorted(sample, np.arange(parsed.n_items + 1))
     terms = [(line[cut[s]:cut[s + 1]].astype(np.int32), cov[cut[s]:cut[s + 1]].astype(np.int32)) for s in range(parsed.n_items)]
     return [int(x) for x in a["ext_ids"]], terms
+
+
+def intropolis_truth(path, key_line, min_coverage=1):
+    """The truth sets of `morna recovery --truth`: for every sample of the intropolis file `path`, {sample id: (lines,
+    extra)} -- the ascending line numbers (through key_line, key_lines of the indexed file) of the junctions it covers
+    at least min_coverage times, the coverages of a key the file repeats summed, and the number of such junctions that
+    are no line of the indexed file."""
+    from .index import ParsedLines
+    parsed = ParsedLines(path, sample_count=1, sample_threshold=0)
+    a = parsed.arrays()
+    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
+    unknown = {}
+    at = np.zeros(parsed.n_lines, np.int64)
+    for j in range(parsed.n_lines):
+        key = blob[off[j]:off[j + 1]].decode("ascii")
+        at[j] = key_line[key] if key in key_line else -1 - unknown.setdefault(key, len(unknown))
+    span = max(len(key_line), int(at.max()) + 1 if len(at) else 0, 1) + len(unknown)
+    code = np.repeat(at + len(unknown), np.diff(a["row_ptr"]))           # unknown keys first, then the lines
+    cell, inv = np.unique(np.asarray(a["ids"], np.int64) * span + code, return_inverse=True)
+    cov = np.zeros(len(cell), np.int64)
+    np.add.at(cov, inv.reshape(-1), np.asarray(a["cov"], np.int64))
+    cell = cell[cov >= int(min_coverage)]
+    sample, code = cell // span, cell % span - len(unknown)
+    cut = np.searchsorted(sample, np.arange(parsed.n_items + 1))
+    out = {}
+    for s, ext in enumerate(a["ext_ids"].tolist()):
+        mine = code[cut[s]:cut[s + 1]]
+        out[int(ext)] = (mine[mine >= 0].astype(np.int32), int((mine < 0).sum()))
+    return out
 
 
 def _open_text(path):

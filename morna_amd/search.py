@@ -275,6 +275,18 @@ class MornaSearch(object):
         store = self.junction_store()
         return store.retain([self.result_sample_ids(lst) for lst in result_lists], frequency_filter, coverage_filter)
 
+    def junction_recovery(self, result_lists, truth, coverage_grid, truth_min_coverage=1):
+        """The recovery histograms (junctions.JunctionStore.recovery) of every list of results (internal
+        ids in rank order, as retain_junctions takes them).  truth: per list, either an internal id -- the truth is that
+        sample's own junctions covered at least truth_min_coverage times -- or an array of line numbers of the indexed
+        file.  Returns int64 [len(result_lists)][2][65][len(coverage_grid) + 1] for junctions.recovery_rows."""
+        store = self.junction_store()
+        lists = [self.result_sample_ids(lst) for lst in result_lists]
+        truth = list(truth)
+        if all(np.ndim(t) == 0 for t in truth):
+            return store.recovery_by_sample(lists, self.result_sample_ids(truth), coverage_grid, truth_min_coverage)
+        return store.recovery(lists, truth, coverage_grid)
+
     # ---- unhashed TF-IDF search (DESIGN.md 8, N5): no counterpart the reference finished -------------------------
     def unhashed_store(self):
         """The junction store with the line weights of <basename>.jw.mor set, and those weights; on first use."""
