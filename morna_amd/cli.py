@@ -278,28 +278,25 @@ def main(argv=None, stdin=None, stdout=None):
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
-    from .search import MornaSearch, results_output
-    from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
+    from .search import MornaSearch
     devices = [int(d) for d in str(args.device).split(',')]
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dist = None
     junctions = args.subparser_name == 'junctions'
+    sharded = world > 1 and os.path.exists(args.basename + ".shards.mor")
+    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed):
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
     if args.subparser_name in ('junctions', 'recovery'):
         from .junctions import MAX_RESULTS, STORE_SUFFIX
-        if world > 1 and os.path.exists(args.basename + ".shards.mor"):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
         if args.results > MAX_RESULTS:
             raise ValueError("-r %d: junctions takes at most %d results (found_in is one 64-bit word per junction)"
                              % (args.results, MAX_RESULTS))
         if not os.path.exists(args.basename + STORE_SUFFIX):
             raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
                           % (args.basename + STORE_SUFFIX))
-    if args.unhashed and world > 1 and os.path.exists(args.basename + ".shards.mor"):
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if world > 1 and os.path.exists(args.basename + ".shards.mor"):
+    if sharded:
         # torchrun with one process per shard: every rank runs this function with the same query (rank 0 reads the stream
         # and hands it over) and calls the same collectives; rank 0 prints
         import io
@@ -328,6 +325,21 @@ def main(argv=None, stdin=None, stdout=None):
         if dist is not None:
             searcher.annoy_index.close()
             dist.destroy_process_group()
+
+
+def _stream_parser(fmt):
+    """The generator of junctions for -f sam / bed / raw."""
+    from . import streams
+    return {"sam": streams.junctions_from_sam_stream, "bed": streams.junctions_from_bed_stream,
+            "raw": streams.junctions_from_raw_stream}[fmt]
+
+
+def _write_member_header(stdout, query_id, internal_id, numbered):
+    """A by-sample query's "# query" line (in a batch) and search_member_n's two lines."""
+    if numbered:
+        stdout.write("# query %d\n" % query_id)
+    stdout.write("querying by sample id " + str(query_id) + "\n")
+    stdout.write("this is internal id " + str(internal_id) + "\n")
 
 
 def _junctions(args, searcher, stdin, stdout):
@@ -411,16 +423,12 @@ def _search_unhashed(args, searcher, stdin, stdout):
     prints them."""
     from .junctions import intropolis_query_terms, key_lines, query_terms
     from .search import results_output
-    from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
     by_item = args.query_ids if args.query_ids is not None else ([args.query_id] if args.query_id is not None else None)
     if by_item is not None:
         results = searcher.unhashed_search_member_n_batch(by_item, args.results, include_distances=args.distances,
                                                           meta_db=args.metadata)
         for query_id, res in zip(by_item, results):
-            if args.query_ids is not None:
-                stdout.write("# query %d\n" % query_id)
-            stdout.write("querying by sample id " + str(query_id) + "\n")      # search_member_n's two lines
-            stdout.write("this is internal id " + str(searcher.internal_id_map[query_id]) + "\n")
+            _write_member_header(stdout, query_id, searcher.internal_id_map[query_id], args.query_ids is not None)
             results_output(res, stdout)
         return 0
     store, w = searcher.unhashed_store()
@@ -432,9 +440,8 @@ def _search_unhashed(args, searcher, stdin, stdout):
             stdout.write("# query %d\n" % sample_id)
             results_output(res, stdout)
         return 0
-    gen = {"sam": junctions_from_sam_stream, "bed": junctions_from_bed_stream, "raw": junctions_from_raw_stream}[args.format]
     coverage = {}
-    for junction in gen(stdin):                                # summed per junction, as update_query sums them
+    for junction in _stream_parser(args.format)(stdin):        # summed per junction, as update_query sums them
         key = " ".join(str(_) for _ in junction[:3])
         coverage[key] = coverage.get(key, 0) + int(junction[3])
     results = searcher.unhashed_search_nn_batch([query_terms(coverage, key_line, w)], args.results,
@@ -452,9 +459,7 @@ def _search_batch(args, searcher, stdout, collect=None):
         internal, results = searcher.search_member_n_batch(args.query_ids, args.results, args.search_k,
                                                            include_distances=args.distances, meta_db=args.metadata)
         for query_id, internal_id, res in zip(args.query_ids, internal, results):
-            stdout.write("# query %d\n" % query_id)
-            stdout.write("querying by sample id " + str(query_id) + "\n")      # search_member_n's two lines
-            stdout.write("this is internal id " + str(internal_id) + "\n")
+            _write_member_header(stdout, query_id, internal_id, True)
             results_output(res, stdout)
             if collect is not None:
                 collect.append((query_id, res))
@@ -481,7 +486,6 @@ def _search_batch(args, searcher, stdout, collect=None):
 def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     """collect: a list that receives (label, results) of every query answered (`junctions` goes on from there)."""
     from .search import results_output
-    from .streams import junctions_from_bed_stream, junctions_from_raw_stream, junctions_from_sam_stream
     if args.intropolis is not None or args.query_ids is not None:
         return _search_batch(args, searcher, stdout, collect)
     if args.query_id is not None:                              # morna.py:1358-1365
@@ -501,17 +505,11 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
         # only rank 0 has the stream: it parses it and every rank walks the same list of junctions
         box = [None]
         if rank == 0:
-            gen = {"sam": junctions_from_sam_stream, "bed": junctions_from_bed_stream, "raw": junctions_from_raw_stream}[args.format]
-            box[0] = list(gen(stdin))
+            box[0] = list(_stream_parser(args.format)(stdin))
         dist.broadcast_object_list(box, src=0)
         junction_generator = iter(box[0])
-    elif args.format == "sam":
-        junction_generator = junctions_from_sam_stream(stdin)
-    elif args.format == "bed":
-        junction_generator = junctions_from_bed_stream(stdin)
     else:
-        assert args.format == "raw"
-        junction_generator = junctions_from_raw_stream(stdin)
+        junction_generator = _stream_parser(args.format)(stdin)
     if args.rawlist:
         for junction in junction_generator:
             stdout.write(str(junction) + "\n")

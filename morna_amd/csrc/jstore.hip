@@ -20,14 +20,18 @@
 // Lines are visited in ascending order by exactly one workgroup per sample and block, so a sample's list ascends by
 // line number whatever order a line lists its samples in, and two builds give the same bytes.
 //
-// Filter: grid over (tile of JT_LINES line numbers) x (query).  The tile's 64-bit found_in words and its coverage
-// flags sit in LDS; one lane per result binary-searches the tile's first and last line in that sample's list, the
-// waves then walk the runs and OR bit `rank` into the line's word (LDS atomics: the OR is order-independent).  A
-// first pass counts the retained lines and their found_in bits per tile; a scan over the tiles of a query gives each
-// tile its place; the second pass writes the lines ascending, their words and the coverages in rank order.
+// The tile walk, which the filter and recovery share: grid over (tile of JT_LINES line numbers) x (query).
+//   tile_of_block  the workgroup's tile and query, and how many results the query's list holds
+//   tile_ranges    one thread per result binary-searches the tile's first line in that sample's list, another its last
+//   walk_tile      a wave per result walks that run and hands every entry (rank, index, line in the tile) to a body
 //
-// Recovery: the same grid and the same walk as the filter's first pass, but what leaves the tile is a
-// histogram, not lines.  Whether a line is retained under ANY (frequency, coverage) pair follows from two small integers,
+// Filter: the tile's 64-bit found_in words and its coverage flags sit in LDS; the walk ORs bit `rank` into the line's
+// word (LDS atomics: the OR is order-independent).  A first pass counts the retained lines and their found_in bits per
+// tile; a scan over the tiles of a query gives each tile its place; the second pass writes the lines ascending and
+// their words, and walks the tile again to write the coverages in rank order.
+//
+// Recovery: the same walk, with the largest coverage kept beside the word, but what leaves the tile is
+// a histogram, not lines.  Whether a line is retained under ANY (frequency, coverage) pair follows from two small integers,
 // the number of results that hold it and the largest coverage among them; with a truth bit per line that is one of
 // 2 x 65 x (B + 1) classes for a grid of B coverage thresholds.  The tile counts its lines per class in LDS and adds its
 // non-zero classes to hist[q] with integer atomics: every cell of a filter grid is then a sum over classes on the host,
@@ -46,6 +50,7 @@
 
 using morna::DevBuf;
 using morna::EventPair;
+using morna::guarded;
 using morna::set_error;
 
 struct morna_jretained {
@@ -181,6 +186,53 @@ __device__ inline int64_t lower_bound_line(const int32_t *__restrict__ line, int
     return lo;
 }
 
+// the (tile, query) of a workgroup: lines [t0, t1) of the file against the first m results of list q
+struct JTile {
+    int64_t q, t0, t1;
+    int32_t tile, m;
+};
+
+__device__ __forceinline__ JTile tile_of_block(int64_t n_lines, int32_t n_tiles, const int32_t *__restrict__ n_results, int32_t k)
+{
+    JTile T;
+    T.q = blockIdx.x / n_tiles;
+    T.tile = (int32_t)(blockIdx.x % n_tiles);
+    T.t0 = (int64_t)T.tile * JT_LINES;
+    T.t1 = T.t0 + JT_LINES < n_lines ? T.t0 + JT_LINES : n_lines;
+    const int32_t m = n_results[T.q];
+    T.m = m < 0 ? 0 : (m > k ? k : m);
+    return T;
+}
+
+// threads 0-63: s_lo[r], where the tile begins in result r's list; threads 64-127: s_hi[r], where it ends
+__device__ __forceinline__ void tile_ranges(const JTile &T, const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                            const int32_t *__restrict__ rows, int32_t k, int64_t *s_lo, int64_t *s_hi)
+{
+    const int tid = threadIdx.x, r = tid & 63;
+    if (tid < 128 && r < T.m) {
+        const int32_t row = rows[T.q * k + r];
+        const int64_t a = ptr[row], b = ptr[row + 1];
+        const int64_t at = lower_bound_line(line, a, b, tid < 64 ? T.t0 : T.t1);
+        if (tid < 64) s_lo[r] = at;
+        else s_hi[r] = at;
+    }
+}
+
+// the walk: one wave per result r, f(r, i, l) for every entry i of its list on line t0 + l of the tile
+template <typename F>
+__device__ __forceinline__ void walk_tile(const JTile &T, const int32_t *__restrict__ line, const int64_t *s_lo, const int64_t *s_hi, F f)
+{
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    for (int r = wave; r < T.m; r += JT_THREADS / WAVE) {
+        const int64_t hi = s_hi[r];
+        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
+            const int64_t l = (int64_t)line[i] - T.t0;
+            if (l < 0 || l >= JT_LINES) continue;   // (cannot happen in an ascending list)
+            f(r, i, l);
+        }
+    }
+}
+
 // One workgroup per (tile, query).  write == 0: tile_n[q][tile] = {retained lines, their found_in bits}.
 // write != 0: tile_n holds the exclusive prefix of those pairs over the query's tiles, q_off[q] / q_cov_off[q] the
 // query's place in the flat outputs.
@@ -199,35 +251,17 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_retain_kernel(const int64_t
     __shared__ int32_t s_keep[JT_THREADS], s_bitsum[JT_THREADS];
     __shared__ int32_t s_covoff[JT_LINES];   // write pass: a retained line's first coverage, relative to the tile; -1: not retained
     const int tid = threadIdx.x;
-    const int64_t q = blockIdx.x / n_tiles;
-    const int32_t tile = (int32_t)(blockIdx.x % n_tiles);
-    const int64_t t0 = (int64_t)tile * JT_LINES;
-    const int64_t t1 = t0 + JT_LINES < n_lines ? t0 + JT_LINES : n_lines;
-    int32_t m = n_results[q];
-    m = m < 0 ? 0 : (m > k ? k : m);
+    const JTile T = tile_of_block(n_lines, n_tiles, n_results, k);
+    const int64_t q = T.q, t0 = T.t0, t1 = T.t1;
+    const int32_t tile = T.tile;
     for (int i = tid; i < JT_LINES; i += JT_THREADS) s_mask[i] = 0;
     for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) s_flag[i] = 0;
-    if (tid < 128) {   // lanes 0-63: where the tile begins in result tid's list; lanes 64-127: where it ends
-        const int r = tid & 63;
-        if (r < m) {
-            const int32_t row = rows[q * k + r];
-            const int64_t a = ptr[row], b = ptr[row + 1];
-            const int64_t at = lower_bound_line(line, a, b, tid < 64 ? t0 : t1);
-            if (tid < 64) s_lo[r] = at;
-            else s_hi[r] = at;
-        }
-    }
+    tile_ranges(T, ptr, line, rows, k, s_lo, s_hi);
     __syncthreads();
-    const int wave = tid / WAVE, lane = tid % WAVE;
-    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
-        const int64_t hi = s_hi[r];
-        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
-            const int64_t l = (int64_t)line[i] - t0;
-            if (l < 0 || l >= JT_LINES) continue;   // (cannot happen in an ascending list)
-            atomicOr(&s_mask[l], 1ull << r);
-            if ((int64_t)cov[i] >= coverage_filter) atomicOr(&s_flag[l >> 5], 1u << (l & 31));
-        }
-    }
+    walk_tile(T, line, s_lo, s_hi, [&](int r, int64_t i, int64_t l) {
+        atomicOr(&s_mask[l], 1ull << r);
+        if ((int64_t)cov[i] >= coverage_filter) atomicOr(&s_flag[l >> 5], 1u << (l & 31));
+    });
     __syncthreads();
     // compaction: thread t owns lines [t * JT_PER, (t + 1) * JT_PER) of the tile
     const int32_t mc = min_count[q];
@@ -280,16 +314,10 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_retain_kernel(const int64_t
         }
     }
     __syncthreads();
-    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
-        const int64_t hi = s_hi[r];
-        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
-            const int64_t l = (int64_t)line[i] - t0;
-            if (l < 0 || l >= JT_LINES) continue;
-            const int32_t o = s_covoff[l];
-            if (o < 0) continue;
-            cov_out[cov_base + o + __popcll(s_mask[l] & ((1ull << r) - 1ull))] = cov[i];
-        }
-    }
+    walk_tile(T, line, s_lo, s_hi, [&](int r, int64_t i, int64_t l) {
+        const int32_t o = s_covoff[l];
+        if (o >= 0) cov_out[cov_base + o + __popcll(s_mask[l] & ((1ull << r) - 1ull))] = cov[i];
+    });
 }
 
 // one wave per query: the (lines, bits) pairs of its tiles -> their exclusive prefix, in place; totals[q] = the sums
@@ -353,13 +381,9 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_recovery_kernel(const int64
     __shared__ int64_t s_lo[65], s_hi[65];   // slot 64: the truth
     __shared__ uint32_t s_hist[2 * JR_COUNTS * (JR_MAX_GRID + 1)];
     const int tid = threadIdx.x;
-    const int64_t q = blockIdx.x / n_tiles;
-    const int32_t tile = (int32_t)(blockIdx.x % n_tiles);
-    const int64_t t0 = (int64_t)tile * JT_LINES;
-    const int64_t t1 = t0 + JT_LINES < n_lines ? t0 + JT_LINES : n_lines;
+    const JTile T = tile_of_block(n_lines, n_tiles, n_results, k);
+    const int64_t q = T.q, t0 = T.t0, t1 = T.t1;
     const int nb = grid.n + 1, n_bins = 2 * JR_COUNTS * nb;
-    int32_t m = n_results[q];
-    m = m < 0 ? 0 : (m > k ? k : m);
     const int32_t *t_arr = truth_rows ? line : t_line;
     for (int i = tid; i < JT_LINES; i += JT_THREADS) {
         s_mask[i] = 0;
@@ -367,16 +391,8 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_recovery_kernel(const int64
     }
     for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) s_truth[i] = 0;
     for (int i = tid; i < n_bins; i += JT_THREADS) s_hist[i] = 0;
-    if (tid < 128) {   // lanes 0-63: where the tile begins in result tid's list; lanes 64-127: where it ends
-        const int r = tid & 63;
-        if (r < m) {
-            const int32_t row = rows[q * k + r];
-            const int64_t a = ptr[row], b = ptr[row + 1];
-            const int64_t at = lower_bound_line(line, a, b, tid < 64 ? t0 : t1);
-            if (tid < 64) s_lo[r] = at;
-            else s_hi[r] = at;
-        }
-    } else if (tid < 130) {   // and in the truth
+    tile_ranges(T, ptr, line, rows, k, s_lo, s_hi);
+    if (tid >= 128 && tid < 130) {   // threads 128 and 129: the same in the truth
         int64_t a, b;
         if (truth_rows) {
             const int32_t row = truth_rows[q];
@@ -391,16 +407,10 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_recovery_kernel(const int64
         else s_hi[64] = at;
     }
     __syncthreads();
-    const int wave = tid / WAVE, lane = tid % WAVE;
-    for (int r = wave; r < m; r += JT_THREADS / WAVE) {
-        const int64_t hi = s_hi[r];
-        for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
-            const int64_t l = (int64_t)line[i] - t0;
-            if (l < 0 || l >= JT_LINES) continue;   // (cannot happen in an ascending list)
-            atomicOr(&s_mask[l], 1ull << r);
-            atomicMax(&s_max[l], cov[i]);
-        }
-    }
+    walk_tile(T, line, s_lo, s_hi, [&](int r, int64_t i, int64_t l) {
+        atomicOr(&s_mask[l], 1ull << r);
+        atomicMax(&s_max[l], cov[i]);
+    });
     {
         const int64_t hi = s_hi[64];
         for (int64_t i = s_lo[64] + tid; i < hi; i += JT_THREADS) {
@@ -626,37 +636,55 @@ int build_impl(morna_jstore *st, const morna_lines *L)
     return validate_store(st, "the built store", MORNA_E_INVALID);
 }
 
-int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, const int32_t *min_count, int64_t nq, int32_t k,
-                int64_t coverage_filter, morna_jretained *R)
+// the store rows of nq result lists of up to k external sample ids each (rows[q * k + r]) and the entries those rows
+// hold in all; `who` is the entry point the messages name
+int resolve_lists(const morna_jstore *st, const char *who, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                  std::vector<int32_t> &rows, int64_t &entries)
 {
-    R->nq = nq;
-    R->off.assign((size_t)nq + 1, 0);
-    if (nq == 0) return MORNA_OK;
-    std::vector<int32_t> rows((size_t)(nq * k), 0);
-    int64_t list_entries = 0;
+    rows.assign((size_t)(nq * k), 0);
+    entries = 0;
     for (int64_t q = 0; q < nq; q++) {
         if (n_results[q] < 0 || n_results[q] > k) {
-            set_error("jstore_retain: result list %lld holds %d results, outside [0, %d]", (long long)q, n_results[q], k);
+            set_error("%s: result list %lld holds %d results, outside [0, %d]", who, (long long)q, n_results[q], k);
             return MORNA_E_INVALID;
         }
         for (int32_t r = 0; r < n_results[q]; r++) {
             const int64_t id = results[q * k + r];
             auto it = st->row_of.find(id);
             if (it == st->row_of.end()) {
-                set_error("jstore_retain: sample id %lld (result %d of list %lld) is not in the junction store", (long long)id, r, (long long)q);
+                set_error("%s: sample id %lld (result %d of list %lld) is not in the junction store", who, (long long)id, r, (long long)q);
                 return MORNA_E_RANGE;
             }
             rows[(size_t)(q * k + r)] = it->second;
-            list_entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
+            entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
         }
     }
-    MORNA_TRY(make_resident(st));
-    const int64_t n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
-    if (nq * n_tiles > INT32_MAX) {
-        set_error("jstore_retain: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
-                  "pass fewer lists per call", (long long)nq, (long long)n_tiles);
+    return MORNA_OK;
+}
+
+// the tiles of lines one query takes; nq of them must fit one launch
+int tile_count(const morna_jstore *st, const char *who, int64_t nq, int64_t *n_tiles)
+{
+    *n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
+    if (nq * *n_tiles > INT32_MAX) {
+        set_error("%s: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
+                  "pass fewer lists per call", who, (long long)nq, (long long)*n_tiles);
         return MORNA_E_INVALID;
     }
+    return MORNA_OK;
+}
+
+int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, const int32_t *min_count, int64_t nq, int32_t k,
+                int64_t coverage_filter, morna_jretained *R)
+{
+    R->nq = nq;
+    R->off.assign((size_t)nq + 1, 0);
+    if (nq == 0) return MORNA_OK;
+    std::vector<int32_t> rows;
+    int64_t list_entries = 0, n_tiles = 0;
+    MORNA_TRY(resolve_lists(st, "jstore_retain", results, n_results, nq, k, rows, list_entries));
+    MORNA_TRY(make_resident(st));
+    MORNA_TRY(tile_count(st, "jstore_retain", nq, &n_tiles));
     DevBuf<int32_t> d_rows, d_nres, d_minc, d_lines, d_cov;
     DevBuf<int64_t> d_tile, d_totals, d_off, d_covptr;
     DevBuf<unsigned long long> d_masks;
@@ -732,26 +760,10 @@ int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_res
     st->rec_bytes = 0;
     st->rec_groups = 0;
     if (nq == 0) return MORNA_OK;
-    std::vector<int32_t> rows((size_t)(nq * k), 0), truth_rows;
+    std::vector<int32_t> rows, truth_rows;
     std::vector<int64_t> tp;
-    int64_t entries = 0, t_base = 0, t_n = 0;
-    for (int64_t q = 0; q < nq; q++) {
-        if (n_results[q] < 0 || n_results[q] > k) {
-            set_error("jstore_recovery: result list %lld holds %d results, outside [0, %d]", (long long)q, n_results[q], k);
-            return MORNA_E_INVALID;
-        }
-        for (int32_t r = 0; r < n_results[q]; r++) {
-            const int64_t id = results[q * k + r];
-            auto it = st->row_of.find(id);
-            if (it == st->row_of.end()) {
-                set_error("jstore_recovery: sample id %lld (result %d of list %lld) is not in the junction store", (long long)id, r,
-                          (long long)q);
-                return MORNA_E_RANGE;
-            }
-            rows[(size_t)(q * k + r)] = it->second;
-            entries += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
-        }
-    }
+    int64_t entries = 0, t_base = 0, t_n = 0, n_tiles = 0;
+    MORNA_TRY(resolve_lists(st, "jstore_recovery", results, n_results, nq, k, rows, entries));
     if (truth_ext) {
         truth_rows.assign((size_t)nq, 0);
         for (int64_t q = 0; q < nq; q++) {
@@ -785,12 +797,7 @@ int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_res
         t_n = t_ptr[nq] - t_base;
     }
     MORNA_TRY(make_resident(st));
-    const int64_t n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
-    if (nq * n_tiles > INT32_MAX) {
-        set_error("jstore_recovery: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
-                  "pass fewer lists per call", (long long)nq, (long long)n_tiles);
-        return MORNA_E_INVALID;
-    }
+    MORNA_TRY(tile_count(st, "jstore_recovery", nq, &n_tiles));
     const size_t n_hist = (size_t)nq * 2 * JR_COUNTS * (size_t)(grid.n + 1);
     DevBuf<int32_t> d_rows, d_nres, d_truth_rows, d_tline, d_hist;
     DevBuf<int64_t> d_tptr;
@@ -879,19 +886,13 @@ int morna_jstore_build(int32_t device, const morna_lines *all_lines, morna_jstor
         return MORNA_E_INVALID;
     }
     *out = nullptr;
-    int rc;
-    std::unique_ptr<morna_jstore> st;
-    try {
-        st.reset(new morna_jstore());
+    return guarded("jstore_build", MORNA_E_INVALID, [&] {
+        std::unique_ptr<morna_jstore> st(new morna_jstore());
         st->device = device;
-        rc = build_impl(st.get(), all_lines);
-    } catch (const std::exception &e) {
-        set_error("jstore_build: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK) return rc;
-    *out = st.release();
-    return MORNA_OK;
+        MORNA_TRY(build_impl(st.get(), all_lines));
+        *out = st.release();
+        return MORNA_OK;
+    });
 }
 
 int morna_jstore_from_arrays(int32_t device, const int64_t *ext_ids, int64_t n_samples, const int64_t *ptr, const int32_t *line,
@@ -907,24 +908,18 @@ int morna_jstore_from_arrays(int32_t device, const int64_t *ext_ids, int64_t n_s
         set_error("jstore_from_arrays: the offsets end at %lld", (long long)nnz);
         return MORNA_E_INVALID;
     }
-    int rc;
-    std::unique_ptr<morna_jstore> st;
-    try {
-        st.reset(new morna_jstore());
+    return guarded("jstore_from_arrays", MORNA_E_INVALID, [&] {
+        std::unique_ptr<morna_jstore> st(new morna_jstore());
         st->device = device;
         st->n_lines = n_lines;
         st->ext_ids.assign(ext_ids, ext_ids + n_samples);
         st->ptr.assign(ptr, ptr + n_samples + 1);
         st->line.assign(line, line + nnz);
         st->cov.assign(cov, cov + nnz);
-        rc = validate_store(st.get(), "jstore_from_arrays: the input", MORNA_E_INVALID);
-    } catch (const std::exception &e) {
-        set_error("jstore_from_arrays: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK) return rc;
-    *out = st.release();
-    return MORNA_OK;
+        MORNA_TRY(validate_store(st.get(), "jstore_from_arrays: the input", MORNA_E_INVALID));
+        *out = st.release();
+        return MORNA_OK;
+    });
 }
 
 // "MORNAJS1", S, nnz, n_lines (int64 each), ext_ids[S] int64, ptr[S + 1] int64, line[nnz] int32, cov[nnz] int32
@@ -966,10 +961,8 @@ int morna_jstore_load(const char *path, int32_t device, morna_jstore **out)
         set_error("Unable to open %s", path);
         return MORNA_E_IO;
     }
-    int rc = MORNA_OK;
-    std::unique_ptr<morna_jstore> st;
-    try {
-        st.reset(new morna_jstore());
+    const int rc = guarded("jstore_load", MORNA_E_IO, [&] {
+        std::unique_ptr<morna_jstore> st(new morna_jstore());
         st->device = device;
         char magic[8];
         int64_t head[3] = {0, 0, 0};
@@ -994,18 +987,14 @@ int morna_jstore_load(const char *path, int32_t device, morna_jstore **out)
         }
         if (!ok) {
             set_error("%s is not a junction store (or is truncated)", path);
-            rc = MORNA_E_IO;
-        } else {
-            rc = validate_store(st.get(), path, MORNA_E_IO);
+            return MORNA_E_IO;
         }
-    } catch (const std::exception &e) {
-        set_error("jstore_load: %s", e.what());
-        rc = MORNA_E_IO;
-    }
-    fclose(f);
-    if (rc != MORNA_OK) return rc;
-    *out = st.release();
-    return MORNA_OK;
+        MORNA_TRY(validate_store(st.get(), path, MORNA_E_IO));
+        *out = st.release();
+        return MORNA_OK;
+    });
+    fclose(f);   // on every path: nothing above returns or throws past the guard
+    return rc;
 }
 
 int morna_jstore_counts(const morna_jstore *s, int64_t *counts)
@@ -1073,18 +1062,12 @@ int morna_jstore_retain(morna_jstore *s, const int64_t *results, const int32_t *
         set_error("jstore_retain: %d results per list: the filter takes 1 to 64 (found_in is one 64-bit word per line)", k);
         return MORNA_E_INVALID;
     }
-    int rc;
-    std::unique_ptr<morna_jretained> R;
-    try {
-        R.reset(new morna_jretained());
-        rc = retain_impl(s, results, n_results, min_count, nq, k, coverage_filter, R.get());
-    } catch (const std::exception &e) {
-        set_error("jstore_retain: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK) return rc;
-    *out = R.release();
-    return MORNA_OK;
+    return guarded("jstore_retain", MORNA_E_INVALID, [&] {
+        std::unique_ptr<morna_jretained> R(new morna_jretained());
+        MORNA_TRY(retain_impl(s, results, n_results, min_count, nq, k, coverage_filter, R.get()));
+        *out = R.release();
+        return MORNA_OK;
+    });
 }
 
 int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k, const int64_t *t_ptr,
@@ -1096,12 +1079,8 @@ int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t
         set_error("jstore_recovery: null argument");
         return MORNA_E_INVALID;
     }
-    try {
-        return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, hist_out);
-    } catch (const std::exception &e) {
-        set_error("jstore_recovery: %s", e.what());
-        return MORNA_E_INVALID;
-    }
+    return guarded("jstore_recovery", MORNA_E_INVALID,
+                   [&] { return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, hist_out); });
 }
 
 int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
@@ -1114,12 +1093,8 @@ int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, con
         set_error("jstore_recovery: null argument");
         return MORNA_E_INVALID;
     }
-    try {
-        return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, hist_out);
-    } catch (const std::exception &e) {
-        set_error("jstore_recovery: %s", e.what());
-        return MORNA_E_INVALID;
-    }
+    return guarded("jstore_recovery", MORNA_E_INVALID,
+                   [&] { return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, hist_out); });
 }
 
 int morna_jstore_recovery_stats(const morna_jstore *s, double *stats)

@@ -1,5 +1,6 @@
 // jstore.hpp -- the junction store as jstore.hip (build, load, filter) and nearest.hip (unhashed search) share it.
 #pragma once
+#include <exception>
 #include <memory>
 #include <unordered_map>
 #include <vector>
@@ -39,6 +40,18 @@ namespace morna {
 
 // the store's stream exists and its host image is in HBM (jstore.hip)
 int jstore_make_resident(morna_jstore *st);
+
+// The body of a C entry point: its code, or `code` with the error "<who>: <what>" for an exception that leaves it.
+template <typename F>
+int guarded(const char *who, int code, F body)
+{
+    try {
+        return body();
+    } catch (const std::exception &e) {
+        set_error("%s: %s", who, e.what());
+        return code;
+    }
+}
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;

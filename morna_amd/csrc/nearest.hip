@@ -34,6 +34,7 @@
 
 using morna::DevBuf;
 using morna::EventPair;
+using morna::guarded;
 using morna::set_error;
 
 struct morna_jnearest {
@@ -508,18 +509,15 @@ int morna_jstore_set_weights(morna_jstore *s, const double *w, int64_t n_lines)
             return MORNA_E_INVALID;
         }
     }
-    try {
+    return guarded("jstore_set_weights", MORNA_E_INVALID, [&] {
         auto nr = std::make_shared<morna_jnearest>();
         nr->w.assign(w, w + n_lines);
         for (auto &x : nr->w)
             if (x == 0.0) x = 0.0;   // -0.0 weighs nothing, as +0.0
         if (s->nearest) (void)hipSetDevice(s->device);   // the buffers of the weights replaced are freed here
         s->nearest = nr;
-    } catch (const std::exception &e) {
-        set_error("jstore_set_weights: %s", e.what());
-        return MORNA_E_INVALID;
-    }
-    return MORNA_OK;
+        return MORNA_OK;
+    });
 }
 
 int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop, const int64_t *q_ext, int64_t nq, int32_t k,
@@ -531,7 +529,7 @@ int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int6
         set_error("jstore_nearest: null argument");
         return MORNA_E_INVALID;
     }
-    try {
+    return guarded("jstore_nearest", MORNA_E_INVALID, [&] {
         std::vector<int64_t> qrange((size_t)(2 * nq));
         for (int64_t q = 0; q < nq; q++) {
             auto it = s->row_of.find(q_ext[q]);
@@ -553,10 +551,7 @@ int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int6
         MORNA_TRY(morna::jstore_make_resident(s));
         MORNA_TRY(prepare_weights(s, s->nearest.get()));
         return search_impl(s, s->nearest.get(), pop_ext, n_pop, s->d_line.p, s->d_cov.p, qrange, nq, k, ids_out, dist_out, count_out);
-    } catch (const std::exception &e) {
-        set_error("jstore_nearest: %s", e.what());
-        return MORNA_E_INVALID;
-    }
+    });
 }
 
 int morna_jstore_nearest(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop, const int64_t *q_ptr, const int32_t *q_line,
@@ -568,7 +563,7 @@ int morna_jstore_nearest(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop,
         set_error("jstore_nearest: null argument, or query offsets that do not begin at 0");
         return MORNA_E_INVALID;
     }
-    try {
+    return guarded("jstore_nearest", MORNA_E_INVALID, [&] {
         std::vector<int64_t> qrange((size_t)(2 * nq));
         for (int64_t q = 0; q < nq; q++) {
             const int64_t a = q_ptr[q], b = q_ptr[q + 1];
@@ -603,10 +598,7 @@ int morna_jstore_nearest(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop,
             HIP_TRY(hipMemcpy(nr->d_qcov.p, q_cov, n_terms * sizeof(int32_t), hipMemcpyHostToDevice));
         }
         return search_impl(s, nr, pop_ext, n_pop, nr->d_qline.p, nr->d_qcov.p, qrange, nq, k, ids_out, dist_out, count_out);
-    } catch (const std::exception &e) {
-        set_error("jstore_nearest: %s", e.what());
-        return MORNA_E_INVALID;
-    }
+    });
 }
 
 int morna_jstore_nearest_stats(const morna_jstore *s, double *stats)

@@ -145,6 +145,26 @@ def view(pp, ctype, count):
     return np.ctypeslib.as_array(C.cast(pp, C.POINTER(ctype)), shape=(count,)).copy()
 
 
+def _clamp62(x):
+    """int(x) held inside [-2^62, 2^62]: every threshold the library takes as an int64."""
+    return min(max(int(x), -2**62), 2**62)
+
+
+def _pack_lists(lists, what):
+    """Result lists (external sample ids in rank order) as (res [nq][k] int64, n_res [nq] int32, k), k the longest
+    list's length, at least 1; past 64 results ValueError, `what` the words for who takes no more."""
+    lists = [[int(s) for s in lst] for lst in lists]
+    k = max([len(lst) for lst in lists] + [1])
+    if k > MAX_RESULTS:
+        raise ValueError(("a result list holds %d results: " + what) % (k, MAX_RESULTS))
+    res = np.zeros((len(lists), k), np.int64)
+    n_res = np.zeros(len(lists), np.int32)
+    for q, lst in enumerate(lists):
+        res[q, :len(lst)] = lst
+        n_res[q] = len(lst)
+    return res, n_res, k
+
+
 class JunctionStore(object):
     """A junction store held by the library (morna_jstore)."""
 
@@ -260,18 +280,9 @@ class JunctionStore(object):
 
     # ---- recovery tables over the filter grid -------------------------------------------------------
     def _recovery_arguments(self, result_sample_ids, coverage_grid):
-        lists = [[int(s) for s in lst] for lst in result_sample_ids]
-        k = max([len(lst) for lst in lists] + [1])
-        if k > MAX_RESULTS:
-            raise ValueError("a result list holds %d results: the recovery tables take at most %d, as the junction filter "
-                             "does" % (k, MAX_RESULTS))
-        res = np.zeros((len(lists), k), np.int64)
-        n_res = np.zeros(len(lists), np.int32)
-        for q, lst in enumerate(lists):
-            res[q, :len(lst)] = lst
-            n_res[q] = len(lst)
-        grid = np.array([min(max(int(c), -2**62), 2**62) for c in coverage_grid], np.int64)
-        hist = np.zeros((len(lists), 2, MAX_RESULTS + 1, max(min(len(grid), MAX_GRID), 0) + 1), np.int32)
+        res, n_res, k = _pack_lists(result_sample_ids, "the recovery tables take at most %d, as the junction filter does")
+        grid = np.array([_clamp62(c) for c in coverage_grid], np.int64)
+        hist = np.zeros((len(n_res), 2, MAX_RESULTS + 1, max(min(len(grid), MAX_GRID), 0) + 1), np.int32)
         return res, n_res, k, grid, hist
 
     def recovery(self, result_sample_ids, truth_lines, coverage_grid):
@@ -304,8 +315,7 @@ class JunctionStore(object):
         if len(truth) != len(n_res):
             raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (len(n_res), len(truth)))
         check(lib().morna_jstore_recovery_by_sample(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(truth),
-                                                    min(max(int(truth_min_coverage), -2**62), 2**62), ptr(grid), len(grid),
-                                                    ptr(hist)))
+                                                    _clamp62(truth_min_coverage), ptr(grid), len(grid), ptr(hist)))
         return hist.astype(np.int64)
 
     def recovery_stats(self):
@@ -318,22 +328,11 @@ class JunctionStore(object):
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
         order, at most 64 per list) in one call on the GPU.  Returns one Retained per list."""
-        lists = [[int(s) for s in lst] for lst in result_sample_ids]
-        k = max([len(lst) for lst in lists] + [1])
-        if k > MAX_RESULTS:
-            raise ValueError("a result list holds %d results: the junction filter takes at most %d (found_in is one 64-bit "
-                             "word per line)" % (k, MAX_RESULTS))
-        nq = len(lists)
-        res = np.zeros((nq, k), np.int64)
-        n_res = np.zeros(nq, np.int32)
-        minc = np.zeros(nq, np.int32)
-        for q, lst in enumerate(lists):
-            res[q, :len(lst)] = lst
-            n_res[q] = len(lst)
-            minc[q] = min(max(min_count(frequency_filter, len(lst)), -1), MAX_RESULTS + 1)
-        cf = min(max(int(coverage_filter), -2**62), 2**62)
+        res, n_res, k = _pack_lists(result_sample_ids, "the junction filter takes at most %d (found_in is one 64-bit word per line)")
+        nq = len(n_res)
+        minc = np.array([min(max(min_count(frequency_filter, int(n)), -1), MAX_RESULTS + 1) for n in n_res], np.int32)
         r = C.c_void_p()
-        check(lib().morna_jstore_retain(self._p, ptr(res), ptr(n_res), ptr(minc), nq, k, cf, C.byref(r)))
+        check(lib().morna_jstore_retain(self._p, ptr(res), ptr(n_res), ptr(minc), nq, k, _clamp62(coverage_filter), C.byref(r)))
         try:
             counts = np.zeros(nq, np.int64)
             check(lib().morna_jretained_counts(r, ptr(counts)))
@@ -436,6 +435,21 @@ def remove_stale_store(basename):
             os.remove(basename + suffix)
 
 
+def _line_keys(parsed):
+    """The "chrom start end" key of every line of a parse, in line order."""
+    a = parsed.arrays()
+    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
+    return [blob[off[j]:off[j + 1]].decode("ascii") for j in range(parsed.n_lines)]
+
+
+def _sum_cells(sample, code, cov, span):
+    """(sample, code, summed coverage) of every distinct (sample, code) cell, code in [0, span), ascending."""
+    cell, inv = np.unique(np.asarray(sample, np.int64) * span + code, return_inverse=True)
+    total = np.zeros(len(cell), np.int64)
+    np.add.at(total, inv.reshape(-1), np.asarray(cov, np.int64))
+    return cell // span, cell % span, total
+
+
 def key_lines(junction_file, n_lines=None):
     """"chrom start end" -> line number of the indexed intropolis file, from the key arrays of a threshold-0 parse;
     ValueError when the file's line count is not `n_lines` (the store's)."""
@@ -444,9 +458,7 @@ def key_lines(junction_file, n_lines=None):
     if n_lines is not None and parsed.lines_read != int(n_lines):
         raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
                          % (junction_file, parsed.lines_read, int(n_lines)))
-    a = parsed.arrays()
-    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
-    return {blob[off[j]:off[j + 1]].decode("ascii"): j for j in range(parsed.n_lines)}
+    return {key: j for j, key in enumerate(_line_keys(parsed))}
 
 
 def query_terms(coverage_by_key, key_line, w):
@@ -463,18 +475,13 @@ def intropolis_query_terms(path, key_line, w):
     from .index import ParsedLines
     parsed = ParsedLines(path, sample_count=1, sample_threshold=0)
     a = parsed.arrays()
-    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
-    at = np.array([key_line.get(blob[off[j]:off[j + 1]].decode("ascii"), -1) for j in range(parsed.n_lines)], np.int64)
+    at = np.array([key_line.get(key, -1) for key in _line_keys(parsed)], np.int64)
     at[at >= 0] = np.where(np.asarray(w)[at[at >= 0]] != 0.0, at[at >= 0], -1)
     line = np.repeat(at, np.diff(a["row_ptr"]))
     keep = line >= 0
-    n_lines = max(len(w), 1)
-    cell, inv = np.unique(np.asarray(a["ids"], np.int64)[keep] * n_lines + line[keep], return_inverse=True)
-    cov = np.zeros(len(cell), np.int64)
-    np.add.at(cov, inv.reshape(-1), np.asarray(a["cov"], np.int64)[keep])
+    sample, line, cov = _sum_cells(a["ids"][keep], line[keep], a["cov"][keep], max(len(w), 1))
     if len(cov) and cov.max() > 2**31 - 1:
         raise ValueError("%s: a query sample's summed coverage of one junction passes 2^31 - 1" % path)
-    sample, line = cell // n_lines, cell % n_lines
     cut = np.searchsorted(sample, np.arange(parsed.n_items + 1))
     terms = [(line[cut[s]:cut[s + 1]].astype(np.int32), cov[cut[s]:cut[s + 1]].astype(np.int32)) for s in range(parsed.n_items)]
     return [int(x) for x in a["ext_ids"]], terms
@@ -488,19 +495,13 @@ def intropolis_truth(path, key_line, min_coverage=1):
     from .index import ParsedLines
     parsed = ParsedLines(path, sample_count=1, sample_threshold=0)
     a = parsed.arrays()
-    blob, off = a["key_bytes"].tobytes(), a["key_off"].tolist()
     unknown = {}
-    at = np.zeros(parsed.n_lines, np.int64)
-    for j in range(parsed.n_lines):
-        key = blob[off[j]:off[j + 1]].decode("ascii")
-        at[j] = key_line[key] if key in key_line else -1 - unknown.setdefault(key, len(unknown))
+    at = np.array([key_line[key] if key in key_line else -1 - unknown.setdefault(key, len(unknown))
+                   for key in _line_keys(parsed)], np.int64)
     span = max(len(key_line), int(at.max()) + 1 if len(at) else 0, 1) + len(unknown)
     code = np.repeat(at + len(unknown), np.diff(a["row_ptr"]))           # unknown keys first, then the lines
-    cell, inv = np.unique(np.asarray(a["ids"], np.int64) * span + code, return_inverse=True)
-    cov = np.zeros(len(cell), np.int64)
-    np.add.at(cov, inv.reshape(-1), np.asarray(a["cov"], np.int64))
-    cell = cell[cov >= int(min_coverage)]
-    sample, code = cell // span, cell % span - len(unknown)
+    sample, code, cov = _sum_cells(a["ids"], code, a["cov"], span)
+    sample, code = sample[cov >= int(min_coverage)], code[cov >= int(min_coverage)] - len(unknown)
     cut = np.searchsorted(sample, np.arange(parsed.n_items + 1))
     out = {}
     for s, ext in enumerate(a["ext_ids"].tolist()):

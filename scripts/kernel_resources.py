@@ -42,7 +42,7 @@ def main():
     print("%-60s %5s %5s %7s %4s %6s %6s %7s" % ("kernel", "VGPR", "AGPR", "scratch", "occ", "sSpill", "vSpill", "LDS"))
     for name, cur in rows:
         short = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip()
-        short = re.sub(r"\(.*", "", short).replace("morna::", "").replace("void ", "")
+        short = re.sub(r"\(.*", "", short.replace("(anonymous namespace)::", "")).replace("morna::", "").replace("void ", "")
         if want not in short:
             continue
         print("%-60s %5d %5d %7d %4d %6d %6d %7d" % tuple([short[:60]] + [cur.get(f, -1) for f in FIELDS]))

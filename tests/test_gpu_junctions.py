@@ -10,7 +10,7 @@ import re
 
 import pytest
 
-from test_junctions_cpu import ref_junctions, sample_lists, tiny_lines
+from test_junctions_cpu import ref_junctions, ref_retain, sample_lists, tiny_lines
 
 pytestmark = pytest.mark.gpu
 
@@ -352,3 +352,28 @@ def test_store_build_rejects_bad_input(tmp_path, embedded):
     _write_gz(good, embedded["generic"])
     with pytest.raises(ValueError, match="threshold 0"):                    # lines dropped: kept line j is not file line j
         JunctionStore.build(ParsedLines(good, sample_count=10, sample_threshold=4))
+
+
+# ---- the filter's written output at the tile edges ---------------------------------------------------------------------------
+def test_retained_output_equals_restatement_at_the_tile_edges():
+    """lines, found_in and coverages of `retain` against ref_retain on the stores of test_gpu_recovery: one tile, both
+    sides of the tile edge, three tiles and a remainder, with lines 4095 and 4096 held by every seventh sample.  Recovery
+    and the filter walk a tile with the same code, so that recovery agrees with the filter there pins neither."""
+    from test_gpu_recovery import SIZES, make_store            # (that module imports this one)
+    for n_lines in SIZES:
+        case = make_store(n_lines)
+        store, rows, lists = case["store"], case["rows"], case["lists"]
+        cov_at = {s: dict(zip(line.tolist(), cov.tolist())) for s, (line, cov) in rows.items()}
+        for f, c in [(0.0, 10**6), (0.5, 3), (1.0, 1)]:
+            kept = store.retain(lists, f, c)
+            assert len(kept) == len(lists)
+            seen = set()
+            for q, lst in enumerate(lists):
+                retained, found_in = ref_retain([rows[s][0].tolist() for s in lst], [rows[s][1].tolist() for s in lst], f, c)
+                lines = sorted(retained)
+                assert kept[q].lines.tolist() == lines, (n_lines, f, c, q)
+                assert kept[q].found_in == [found_in[j] for j in lines], (n_lines, f, c, q)
+                assert kept[q].coverages == [[cov_at[lst[r]][j] for r in found_in[j]] for j in lines], (n_lines, f, c, q)
+                seen.update(lines)
+            if n_lines > 4096 and (f, c) == (0.0, 10**6):
+                assert 4095 in seen and 4096 in seen
