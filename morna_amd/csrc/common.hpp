@@ -124,6 +124,14 @@ struct alignas(16) RowInfo {
 };
 static_assert(sizeof(RowInfo) == 16, "RowInfo is one dwordx4");
 
+// Where a two_means kernel that holds its hyperplane in registers leaves the fp16 image the matrix-core split filters with
+// (splitmm.hip, rows_to_half_kernel's image of the same row); h16 null: nowhere, the image is made by a conversion launch.
+struct HalfImageOut {
+    _Float16 *h16;           // [slots of the level][dpad]
+    float *norm, *err;       // [slots] upper bounds of the image's norm and of its rounding error's norm
+    unsigned int *zero_me;   // the level's open-pair counter, reset by the kernel's first workgroup
+};
+
 // A node of the forest as the host driver tracks it (perm segment of one tree).
 struct Seg {
     int32_t tree, level, start, count, node;
@@ -385,8 +393,14 @@ int split_mm_convert_rows(morna_index *h, const float *src, int64_t rows, _Float
                           float *inv_scale, hipStream_t stream);
 int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_by_item, int32_t n_trees, hipStream_t stream,
                         const int32_t **rank_out, int32_t **inv_out);
+// a level: begin (buffers; before its two_means is launched), its per-tile task lists (any stream, once the tasks are on the
+// device), then the contraction
+bool split_mm_level_uses_lists(const morna_index *h, int32_t n_tasks);
+int split_mm_level_begin(morna_index *h, int32_t n_tasks, int32_t n_slots, HalfImageOut *img);
+int split_mm_level_lists(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, const int32_t *perm, hipStream_t stream);
 int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, int32_t n_slots, const float *hp_level,
-                   const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones);
+                   const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones, const char *image_from,
+                   bool lists_ready);
 // result block in HBM (ids at 0, distances at s_ids, counts at s_ids + s_dist; `bytes` in all) -> the caller's arrays
 // through the handle's page-locked staging (knn.hip); waits for the stream
 int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s_ids, size_t s_dist, size_t dist_elt, int64_t nq,

@@ -340,6 +340,107 @@ __device__ inline float wave_dot(PA a, PB b, int nvec, int lane)
     return acc4_finish(s);
 }
 
+// ---- fp16 image of a row (splitmm.hip): dst = fp16(2^e * row) with max |2^e x_i| in [2^14, 2^15) ----------------
+// The pieces rows_to_half_kernel is made of, shared with the two_means kernels that write the image of a hyperplane
+// while they still hold it in registers (forest.hip).  The image's bits depend on the row's largest element only; the two
+// norm bounds are sums whose order is the caller's.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// largest |element| of four; bad: an inf or NaN among them
+__device__ inline float half_absmax4(const float4 v, bool &bad)
+{
+    const float a = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+    bad |= !(a <= 3.0e38f);   // inf or NaN
+    return a;
+}
+// the scale 2^e of a row whose largest |element| is m (0 when the row cannot be scaled: `bad`)
+__device__ inline float half_row_scale(float m, bool &bad, int &e)
+{
+    e = 0;
+    if (m > 0.f) e = 14 - ilogbf(m);
+    if (e > 126 || e < -126) bad = true;   // the scale itself must be a normal float
+    return bad ? 0.f : ldexpf(1.f, e);
+}
+// one element of the image; its square and the square of its rounding error are added to the caller's sums
+__device__ inline _Float16 half_convert1(float v, float s, float &sum, float &sume)
+{
+    const _Float16 h = (_Float16)(v * s);
+    const float f = (float)h;
+    sum += f * f;
+    const float e = v * s - f;   // exactly: s x is exact (power of two), y has 11 bits of it
+    sume += e * e;
+    return h;
+}
+__device__ inline f16x4 half_convert4(const float4 v, float s, float &sum, float &sume)
+{
+    const _Float16 h0 = (_Float16)(v.x * s), h1 = (_Float16)(v.y * s), h2 = (_Float16)(v.z * s), h3 = (_Float16)(v.w * s);
+    const float f0 = (float)h0, f1 = (float)h1, f2 = (float)h2, f3 = (float)h3;
+    sum += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
+    // the rounding error of each element, exactly: s x_i is exact (power of two), y_i has 11 bits of it
+    const float e0 = v.x * s - f0, e1 = v.y * s - f1, e2 = v.z * s - f2, e3 = v.w * s - f3;
+    sume += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
+    return (f16x4){h0, h1, h2, h3};
+}
+// The two bounds from the sums of squares.  fp32 sum of <= 32768 squares (rows of up to 32768 floats reach this code):
+// relative error < 32768 * 2^-24 ~ 2e-3 in ANY order of summation, < 1e-3 after the sqrt; the bounds are widened by 0.2 %
+__device__ inline float half_norm_bound(float sum, bool bad) { return bad ? INFINITY : sqrtf(sum) * 1.002f; }
+__device__ inline float half_err_bound(float sume, bool bad)
+{
+    return bad ? 0.f : sqrtf(sume) * 1.002f + 1e-30f;   // (elements of s x below the fp32 normal range: < 1e-38 each)
+}
+// A row held by ONE wave as rows_to_half_kernel reads it (lane l: float4 l + 64 k): the same image and, the sums being
+// taken in the same order, the same two bounds.
+template <int NV>
+__device__ inline void half_image_wave(const float4 (&v)[NV], int lane, _Float16 *dst, float *norm, float *err)
+{
+    float m = 0.f;
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < NV; k++) m = fmaxf(m, half_absmax4(v[k], bad));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, WAVE));
+    bad = __any(bad);
+    int e;
+    const float s = half_row_scale(m, bad, e);
+    float sum = 0.f, sume = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; k++) *(f16x4 *)(dst + 4 * (lane + k * WAVE)) = half_convert4(v[k], s, sum, sume);
+    sum = wave_sum_xor(sum);
+    sume = wave_sum_xor(sume);
+    if (lane == 0) {
+        *norm = half_norm_bound(sum, bad);
+        *err = half_err_bound(sume, bad);
+    }
+}
+// A row spread over the FOUR waves of a workgroup, in any layout: the largest element and the two sums meet in LDS
+// (red: 12 floats), a barrier each.  Every thread of the workgroup must call both.
+__device__ inline float half_block_scale(float m, bool bad, int lane, int w, float *red, bool &bad_out)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, WAVE));
+    bad = __any(bad);
+    if (lane == 0) red[w] = bad ? -1.f : m;   // (m >= 0)
+    __syncthreads();
+    const float m0 = red[0], m1 = red[1], m2 = red[2], m3 = red[3];
+    bad_out = m0 < 0.f || m1 < 0.f || m2 < 0.f || m3 < 0.f;
+    int e;
+    return half_row_scale(fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), bad_out, e);
+}
+__device__ inline void half_block_bounds(float sum, float sume, bool bad, int lane, int w, float *red, float *norm, float *err)
+{
+    sum = wave_sum_xor(sum);
+    sume = wave_sum_xor(sume);
+    if (lane == 0) {
+        red[4 + w] = sum;
+        red[8 + w] = sume;
+    }
+    __syncthreads();
+    if (w == 0 && lane == 0) {
+        *norm = half_norm_bound((red[4] + red[5]) + (red[6] + red[7]), bad);
+        *err = half_err_bound((red[8] + red[9]) + (red[10] + red[11]), bad);
+    }
+}
+
 // 64-bit butterfly helpers for (key) reductions
 __device__ inline uint64_t shfl_xor_u64(uint64_t v, int off)
 {

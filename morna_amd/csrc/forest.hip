@@ -252,7 +252,8 @@ __global__ __launch_bounds__(256, 3) void two_means_wave_kernel(const float *__r
                                                              int64_t n_items, int32_t dpad,
                                                              const int32_t *__restrict__ perm,
                                                              const SplitTask *__restrict__ tasks, int32_t n_tasks,
-                                                             uint32_t seed, float *__restrict__ hp, int32_t *__restrict__ ones)
+                                                             uint32_t seed, float *__restrict__ hp, int32_t *__restrict__ ones,
+                                                             const HalfImageOut img)
 {
     __shared__ float4 xnext[256 / WAVE][NV * WAVE];   // per wave: the row of the coming step
     const int lane = threadIdx.x & (WAVE - 1);
@@ -262,6 +263,7 @@ __global__ __launch_bounds__(256, 3) void two_means_wave_kernel(const float *__r
     const int ti = blockIdx.x * (256 / WAVE) + wv;
     if (ti >= n_tasks) return;   // no barrier below: waves are independent
     if (lane == 0) ones[ti] = 0;   // the split kernels that follow count this task's right side here
+    if (img.h16 && ti == 0 && lane == 0) *img.zero_me = 0u;   // ... and list the pairs their filter leaves open from here
     const SplitTask t = tasks[ti];
     const int nvec = dpad / 4;
     const int32_t *items = perm + TASK_ITEMS_AT(t, n_items);
@@ -351,6 +353,8 @@ __global__ __launch_bounds__(256, 3) void two_means_wave_kernel(const float *__r
     float4 *out = (float4 *)(hp + (int64_t)t.slot * dpad);
 #pragma unroll
     for (int kk = 0; kk < NV; kk++) out[lane + kk * WAVE] = p[kk];
+    // the fp16 image the matrix-core split filters with: the lane holds what a lane of rows_to_half_kernel would read back
+    if (img.h16) half_image_wave<NV>(p, lane, img.h16 + (int64_t)t.slot * dpad, img.norm + t.slot, img.err + t.slot);
 }
 
 // ---- two_means, four waves per node, by STRIPS of the canonical lanes ----------------------
@@ -373,10 +377,13 @@ __global__ __launch_bounds__(256) void two_means_strip_kernel(const float *__res
                                                             int64_t n_items, int32_t dpad,
                                                             const int32_t *__restrict__ perm,
                                                             const SplitTask *__restrict__ tasks, uint32_t seed,
-                                                            float *__restrict__ hp, int32_t *__restrict__ ones)
+                                                            float *__restrict__ hp, int32_t *__restrict__ ones,
+                                                            const HalfImageOut img)
 {
     static_assert(NV % 4 == 0, "the update works on groups of four k-steps");
     if (threadIdx.x == 0) ones[blockIdx.x] = 0;   // the split kernels that follow count this task's right side here
+    if (img.h16 && blockIdx.x == 0 && threadIdx.x == 0) *img.zero_me = 0u;   // ... and list their open pairs from here
+    __shared__ float s_img[12];   // the image's largest element and two sums, per wave (half_block_*)
     static_assert(TM_ITERS % DEPTH == 0, "the step loop is unrolled DEPTH times");
     constexpr int NS = NV / 4;
     __shared__ float ex[2][3][WAVE];   // folded values of up to three dots per canonical lane, by exchange parity
@@ -555,6 +562,25 @@ __global__ __launch_bounds__(256) void two_means_strip_kernel(const float *__res
         out[(4 * s + 2) * 256] = p[s].z;
         out[(4 * s + 3) * 256] = p[s].w;
     }
+    // the fp16 image the matrix-core split filters with (rows_to_half_kernel's, from the strips in registers): the scale
+    // needs the row's largest element and the bounds two sums over all four waves, a barrier each
+    if (img.h16) {   // uniform
+        float m = 0.f;
+        bool bad = false;
+#pragma unroll
+        for (int s = 0; s < NS; s++) m = fmaxf(m, half_absmax4(p[s], bad));
+        const float sc = half_block_scale(m, bad, lane, w, s_img, bad);
+        float sum = 0.f, sume = 0.f;
+        _Float16 *o16 = img.h16 + (int64_t)t.slot * dpad + 64 * w + lane;
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            o16[(4 * s) * 256] = half_convert1(p[s].x, sc, sum, sume);
+            o16[(4 * s + 1) * 256] = half_convert1(p[s].y, sc, sum, sume);
+            o16[(4 * s + 2) * 256] = half_convert1(p[s].z, sc, sum, sume);
+            o16[(4 * s + 3) * 256] = half_convert1(p[s].w, sc, sum, sume);
+        }
+        half_block_bounds(sum, sume, bad, lane, w, s_img, img.norm + t.slot, img.err + t.slot);
+    }
 }
 
 // ---- two_means for wide rows, 8192 < dpad <= 32768 ----------------------------------------------
@@ -573,13 +599,16 @@ __global__ __launch_bounds__(256) void two_means_wide_kernel(const float *__rest
                                                            int64_t n_items, int32_t dpad,
                                                            const int32_t *__restrict__ perm,
                                                            const SplitTask *__restrict__ tasks, uint32_t seed,
-                                                           float *__restrict__ hp, int32_t *__restrict__ ones)
+                                                           float *__restrict__ hp, int32_t *__restrict__ ones,
+                                                           const HalfImageOut img)
 {
     // the launch picks the smallest NG of 12, 16, 24, 32 that holds nf: groups below the next smaller one always exist
     constexpr int NGLO = NG <= 12 ? 8 : NG <= 16 ? 12 : NG <= 24 ? 16 : 24;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ float ex[2][3][WAVE];
+    __shared__ float s_img[12];   // the image's largest element and two sums, per wave (half_block_*)
     if (threadIdx.x == 0) ones[blockIdx.x] = 0;   // the split kernels that follow count this task's right side here
+    if (img.h16 && blockIdx.x == 0 && threadIdx.x == 0) *img.zero_me = 0u;   // ... and list their open pairs from here
 
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     const int L = 16 * w + (lane >> 2);
@@ -839,6 +868,30 @@ __global__ __launch_bounds__(256) void two_means_wide_kernel(const float *__rest
         float d = pt[256 * c];
         if (nn > 0.f) d = d / nn;
         out[(4 * nf + c) * 256] = d;
+        pt[256 * c] = d;   // (the lane's own slot: read back below)
+    }
+    // the fp16 image the matrix-core split filters with, as in two_means_strip_kernel: the hyperplane is p and the tail slots
+    if (img.h16) {   // uniform
+        float m = 0.f;
+        bool bad = false;
+#pragma unroll
+        for (int g = 0; g < NG; g++)
+            if (g < NGLO || g < nf) m = fmaxf(m, half_absmax4(p[g], bad));
+        for (int c = 0; c < nt; c++) m = fmaxf(m, half_absmax4(make_float4(pt[256 * c], 0.f, 0.f, 0.f), bad));
+        const float sc = half_block_scale(m, bad, lane, w, s_img, bad);
+        float sum = 0.f, sume = 0.f;
+        _Float16 *o16 = img.h16 + (int64_t)t.slot * dpad + 64 * w + lane;
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+            if (g < NGLO || g < nf) {
+                o16[(4 * g) * 256] = half_convert1(p[g].x, sc, sum, sume);
+                o16[(4 * g + 1) * 256] = half_convert1(p[g].y, sc, sum, sume);
+                o16[(4 * g + 2) * 256] = half_convert1(p[g].z, sc, sum, sume);
+                o16[(4 * g + 3) * 256] = half_convert1(p[g].w, sc, sum, sume);
+            }
+        }
+        for (int c = 0; c < nt; c++) o16[(4 * nf + c) * 256] = half_convert1(pt[256 * c], sc, sum, sume);
+        half_block_bounds(sum, sume, bad, lane, w, s_img, img.norm + t.slot, img.err + t.slot);
     }
 }
 // dynamic LDS of two_means_wide_kernel
@@ -1441,34 +1494,57 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             if ((rc = upload_tasks(tasks))) { cleanup(); return rc; }
             // (d_ones is zeroed by the two_means kernel of the attempt, task by task: a hipMemsetAsync costs ~15 us of
             // idle device around its few microseconds)
+            // Work of the level that does not depend on its hyperplanes goes to the side stream, under two_means: ONE fork
+            // behind the task list (and so behind the previous level's partition), one join in front of the split.
             bool side_work = false;
+            auto fork_side = [&]() -> hipError_t {
+                if (side_work) return hipSuccess;
+                side_work = true;
+                const hipError_t e = hipEventRecord(h->ev_fork, h->stream);
+                return e != hipSuccess ? e : hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
+            };
             if (use_mm && !h->half.valid) {
                 // once per set of rows: their fp16 image, on the side stream while two_means (a latency chain on few CUs
                 // at the root level) has the main one.  Nothing else of the matrix-core split needs a side stream: a
                 // row's node is looked up through `inv`, which the partition of the previous level left current (round 1
                 // inverted the permutations in a kernel of its own per level, behind two event hand-overs of ~17 us each).
-                F_TRY(hipEventRecord(h->ev_fork, h->stream));
-                F_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+                F_TRY(fork_side());
                 if ((rc = split_mm_prepare_rows(h, h->stream2))) { cleanup(); return rc; }
-                F_TRY(hipEventRecord(h->ev_join, h->stream2));
-                side_work = true;
             } else if (use_mm && order_on && level == 1 && !h->splitmm.ord_valid && N >= 8192 && N <= ((int64_t)1 << 22) && n_trees >= 2) {
                 // second level: the rows of the contraction are put in an order in which neighbours are alike (the sides of
                 // the root splits say which are), on the side stream under this level's two_means; from here on `inv` is
                 // kept by row (splitmm.hip, split_mm_order_rows; its counting sort's table is 16 KB per 256 rows: up to 4 M rows)
-                F_TRY(hipEventRecord(h->ev_fork, h->stream));
-                F_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+                F_TRY(fork_side());
                 if ((rc = split_mm_order_rows(h, side.p, inv_p, n_trees, h->stream2, &rank_p, &inv_p))) { cleanup(); return rc; }
-                F_TRY(hipEventRecord(h->ev_join, h->stream2));
-                side_work = true;
             }
+            // The matrix-core split's buffers for this attempt, before anything of it is enqueued.  Its per-tile task lists
+            // read the tasks, the permutations and the order of the rows (on the side stream already, if it is this
+            // level's) -- nothing two_means makes: they are built beside it (MORNA_SPLIT_LISTS_AHEAD=0: in front of the
+            // contraction, behind two_means).
+            HalfImageOut img = {nullptr, nullptr, nullptr, nullptr};
+            bool lists_ahead = false;
+            if (use_mm) {
+                static const bool ahead_on = env_on("MORNA_SPLIT_LISTS_AHEAD");
+                if ((rc = split_mm_level_begin(h, A, S, &img))) { cleanup(); return rc; }
+                if (ahead_on && split_mm_level_uses_lists(h, A)) {
+                    F_TRY(fork_side());
+                    if ((rc = split_mm_level_lists(h, d_tasks.p, A, work.p, h->stream2))) { cleanup(); return rc; }
+                    lists_ahead = true;
+                }
+            }
+            if (side_work) F_TRY(hipEventRecord(h->ev_join, h->stream2));
+            // the two_means forms that end with the hyperplane in registers also write its fp16 image for the split
+            // (MORNA_TM_HALF_EPILOGUE=0: a conversion launch behind two_means, as for the LDS form)
+            static const bool tm_half_on = env_on("MORNA_TM_HALF_EPILOGUE");
+            if (!tm_half_on) img.h16 = nullptr;
+            const char *image_from = nullptr;
             {
                 ScopedTimer tm(h, MORNA_T_TWO_MEANS, 4 * (int64_t)D * (TM_ITERS + 2) * A);
                 const int nvq = (dpad / 4 + WAVE - 1) / WAVE;   // float4 per lane per row
                 const unsigned wg = (unsigned)((A + 3) / 4);
 #define TMW_LAUNCH(NVV)                                                                                              \
     hipLaunchKernelGGL(two_means_wave_kernel<NVV>, dim3(wg), dim3(256), 0, h->stream, h->X.p, h->rowinfo.p, N, dpad, \
-                       work.p, d_tasks.p, A, seed, hp_level, d_ones.p)
+                       work.p, d_tasks.p, A, seed, hp_level, d_ones.p, img)
                 // Four waves per node (strips) while the level's nodes fit the chip at once (2 workgroups per CU): the
                 // node's 200-step chain is then 2-3x shorter (C3: 0.32 / 0.28 ms instead of 0.7 ms at the two
                 // shallowest levels).  Deeper levels are bound by the HBM gather of the rows (C3, 1600 nodes: 5.9 TB/s)
@@ -1480,14 +1556,17 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 ScopedTimer tk(h, strip_runs || dpad > 8192 ? MORNA_T_TM_STRIP : MORNA_T_TM_WAVE, 4 * (int64_t)D * (TM_ITERS + 2) * A);
 #define TMS_LAUNCH(NVV)                                                                                                 \
     hipLaunchKernelGGL((two_means_strip_kernel<NVV, TM_STRIP_DEPTH>), dim3((unsigned)A), dim3(256), 0, h->stream, h->X.p, \
-                       h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p)
+                       h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p, img)
 #define TMX_LAUNCH(NGV)                                                                                                   \
     do {                                                                                                                  \
         F_TRY(hipFuncSetAttribute((const void *)two_means_wide_kernel<NGV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)tm_wide_lds(dpad)));                                                             \
         hipLaunchKernelGGL(two_means_wide_kernel<NGV>, dim3((unsigned)A), dim3(256), tm_wide_lds(dpad), h->stream,       \
-                           h->X.p, h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p);                    \
+                           h->X.p, h->rowinfo.p, N, dpad, work.p, d_tasks.p, seed, hp_level, d_ones.p, img);               \
     } while (0)
+                // who leaves the image: every form but the LDS one (row lengths without a register form)
+                const bool wave_runs = nvq == 1 || nvq == 2 || nvq == 3 || nvq == 4 || nvq == 6 || nvq == 8 || nvq == 12;
+                if (img.h16) image_from = dpad > 8192 ? "wide" : strip_runs ? "strip" : wave_runs ? "wave" : nullptr;
                 // rows past 8192 floats: the wide form at every level, whatever the switches (one centroid in LDS)
                 if (dpad > 8192) {
                     const int ngw = dpad / 256 / 4;   // full groups of four k-steps
@@ -1531,7 +1610,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             if (side_work) F_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             if (use_mm) {
                 ScopedTimer tm(h, MORNA_T_SPLIT, 4 * (int64_t)D * (rows + A));
-                if ((rc = split_mm_level(h, d_tasks.p, A, S, hp_level, work.p, inv_p, seed, side.p, d_ones.p))) {
+                if ((rc = split_mm_level(h, d_tasks.p, A, S, hp_level, work.p, inv_p, seed, side.p, d_ones.p, image_from, lists_ahead))) {
                     cleanup();
                     return rc;
                 }

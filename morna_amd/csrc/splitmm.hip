@@ -52,39 +52,21 @@ __global__ __launch_bounds__(256) void rows_to_half_kernel(const float *__restri
     const int nvec = dpad / 4;
     float m = 0.f;
     bool bad = false;
-    for (int i = lane; i < nvec; i += WAVE) {
-        const float4 v = x[i];
-        const float a = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-        bad |= !(a <= 3.0e38f);   // inf or NaN
-        m = fmaxf(m, a);
-    }
+    // (the arithmetic is devutil.hpp's half_*: the two_means kernels write the same image of the hyperplanes they make)
+    for (int i = lane; i < nvec; i += WAVE) m = fmaxf(m, half_absmax4(x[i], bad));
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, WAVE));
     bad = __any(bad);
-    int e = 0;
-    if (m > 0.f) e = 14 - ilogbf(m);
-    if (e > 126 || e < -126) bad = true;   // the scale itself must be a normal float
-    const float s = bad ? 0.f : ldexpf(1.f, e);
+    int e;
+    const float s = half_row_scale(m, bad, e);
     float sum = 0.f, sume = 0.f;
     _Float16 *d = dst + r * dpad;
-    for (int i = lane; i < nvec; i += WAVE) {
-        const float4 v = x[i];
-        const _Float16 h0 = (_Float16)(v.x * s), h1 = (_Float16)(v.y * s), h2 = (_Float16)(v.z * s), h3 = (_Float16)(v.w * s);
-        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-        *(f16x4 *)(d + 4 * i) = (f16x4){h0, h1, h2, h3};
-        const float f0 = (float)h0, f1 = (float)h1, f2 = (float)h2, f3 = (float)h3;
-        sum += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
-        // the rounding error of each element, exactly: s x_i is exact (power of two), y_i has 11 bits of it
-        const float e0 = v.x * s - f0, e1 = v.y * s - f1, e2 = v.z * s - f2, e3 = v.w * s - f3;
-        sume += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-    }
+    for (int i = lane; i < nvec; i += WAVE) *(f16x4 *)(d + 4 * i) = half_convert4(x[i], s, sum, sume);
     sum = wave_sum_xor(sum);
     sume = wave_sum_xor(sume);
-    // fp32 sum of <= 32768 squares (rows of up to 32768 floats reach this code): relative error < 32768 * 2^-24 ~ 2e-3
-    // even as one naive chain, < 1e-3 after the sqrt; the bound is widened by 0.2 %
     if (lane == 0) {
-        norm[r] = bad ? INFINITY : sqrtf(sum) * 1.002f;
-        err[r] = bad ? 0.f : sqrtf(sume) * 1.002f + 1e-30f;   // (elements of s x below the fp32 normal range: < 1e-38 each)
+        norm[r] = half_norm_bound(sum, bad);
+        err[r] = half_err_bound(sume, bad);
         if (inv_scale) inv_scale[r] = bad ? 0.f : ldexpf(1.f, -e);
     }
 }
@@ -568,10 +550,78 @@ int split_mm_convert_rows(morna_index *h, const float *src, int64_t rows, _Float
     return MORNA_OK;
 }
 
+// 256 x 256 tiles once the level has hyperplane tiles enough for them to fill the chip in even rounds (MORNA_SPLIT_BIG=0: the
+// 128 x 128 form everywhere); the rows are those of the contraction as they are NOW (ordered or not)
+static bool split_mm_big(const morna_index *h, int32_t n_tasks)
+{
+    static const bool big_on = env_on("MORNA_SPLIT_BIG");
+    static const bool lists_on = env_on("MORNA_SPLIT_LISTS");
+    return big_on && (n_tasks >= 1024 || (h->splitmm.ord_valid && lists_on && n_tasks >= 512));
+}
+
+// Will split_mm_level multiply every row tile with its own list of tasks (the 256 x 256 form, from the second level of a tree
+// on; MORNA_SPLIT_LISTS=0: every tile x every task)?  The forest build asks before the level's two_means is launched.
+bool split_mm_level_uses_lists(const morna_index *h, int32_t n_tasks)
+{
+    static const bool lists_on = env_on("MORNA_SPLIT_LISTS");
+    return lists_on && split_mm_big(h, n_tasks);
+}
+
+// The buffers of a level, grown before anything of the level is enqueued: the fp16 image of its n_slots hyperplanes with the
+// two bounds per slot, the open-pair list, the per-tile task lists when the level uses them.  img: where a two_means kernel
+// that holds its hyperplane in registers leaves the image (forest.hip).
+int split_mm_level_begin(morna_index *h, int32_t n_tasks, int32_t n_slots, HalfImageOut *img)
+{
+    const int64_t N = h->n_items;
+    const size_t cap = (size_t)N * h->n_trees;   // a row is in at most one split node per tree
+    if (cap > 0xFFFFFFF0u) {
+        set_error("split_mm_level: %lld x %d (row, tree) pairs exceed the open-pair list", (long long)N, h->n_trees);
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(h->splitmm.h16.alloc((size_t)n_slots * h->dpad));
+    MORNA_TRY(h->splitmm.hn.alloc((size_t)n_slots * 2));   // norms, then rounding-error norms
+    MORNA_TRY(h->splitmm.amb.alloc(16 + cap * sizeof(int2)));
+    if (split_mm_level_uses_lists(h, n_tasks)) {
+        const size_t n_rt = (size_t)((N + 255) / 256);
+        MORNA_TRY(h->splitmm.active.alloc(n_rt * n_tasks));
+        MORNA_TRY(h->splitmm.lists.alloc(n_rt * n_tasks + 2 * n_rt + 1));
+    }
+    img->h16 = h->splitmm.h16.p;
+    img->norm = h->splitmm.hn.p;
+    img->err = h->splitmm.hn.p + n_slots;
+    img->zero_me = (unsigned int *)h->splitmm.amb.p;
+    return MORNA_OK;
+}
+
+// The tasks each row tile of 256 rows needs (split_active_*_kernel), into the buffers split_mm_level_begin made: they depend
+// on the level's tasks, the trees' permutations and the order of the rows, not on the level's hyperplanes, so the forest
+// build enqueues them on its side stream under the level's two_means.
+int split_mm_level_lists(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, const int32_t *perm, hipStream_t stream)
+{
+    const int64_t N = h->n_items;
+    const unsigned n_rt = (unsigned)((N + 255) / 256);
+    const int32_t *rank = h->splitmm.ord_valid ? h->splitmm.maps.p : nullptr;
+    uint8_t *active = h->splitmm.active.p;
+    int32_t *col_list = h->splitmm.lists.p, *col_count = col_list + (size_t)n_rt * n_tasks, *col_first = col_count + n_rt;
+    HIP_TRY(hipMemsetAsync(active, 0, (size_t)n_rt * n_tasks, stream));
+    hipLaunchKernelGGL(split_active_mark_kernel, dim3((unsigned)n_tasks), dim3(256), 0, stream, d_tasks, perm, N, rank, 8, n_tasks,
+                       active);
+    hipLaunchKernelGGL(split_active_list_kernel, dim3(n_rt), dim3(256), 0, stream, active, n_tasks, col_list, col_count);
+    // d_stat[1]: 256 x 256 tiles launched through the lists while the MORNA_T_SPLIT_MM timer is on (resolve_timers prices them)
+    const bool count_tiles = h->timing && (h->timing_mask & (1u << MORNA_T_SPLIT_MM));
+    hipLaunchKernelGGL(split_active_scan_kernel, dim3(1), dim3(1024), 0, stream, col_count, (int32_t)n_rt, 256, col_first,
+                       count_tiles ? h->d_stat.p + 1 : (unsigned long long *)nullptr);
+    HIP_TRY(hipGetLastError());
+    return MORNA_OK;
+}
+
 // n_slots: hyperplanes of the level (hp_level[slot]); the tasks are all of them in order (a first attempt: slot = task
-// number) or the retried ones among them
+// number) or the retried ones among them.  After split_mm_level_begin for the same level.  image_from: the two_means form
+// that has written the image of the tasks' slots and reset the open-pair counter, or null: both are done here.
+// lists_ready: split_mm_level_lists has run for these tasks (the caller has ordered it in front of h->stream).
 int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, int32_t n_slots, const float *hp_level,
-                   const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones)
+                   const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones, const char *image_from,
+                   bool lists_ready)
 {
     const int64_t N = h->n_items;
     DevBuf<_Float16> &h16 = h->splitmm.h16;
@@ -581,49 +631,28 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
     const bool ord = h->splitmm.ord_valid;
     const _Float16 *rows16 = h->half.x16.p;
     const float *rows_n = h->half.xn.p, *rows_e = h->half.xn.p + 2 * N;
-    const int32_t *rank = ord ? h->splitmm.maps.p : nullptr, *item_at = ord ? h->splitmm.maps.p + N : nullptr;
+    const int32_t *item_at = ord ? h->splitmm.maps.p + N : nullptr;
     const size_t cap = (size_t)N * h->n_trees;   // a row is in at most one split node per tree
-    if (cap > 0xFFFFFFF0u) {
-        set_error("split_mm_level: %lld x %d (row, tree) pairs exceed the open-pair list", (long long)N, h->n_trees);
-        return MORNA_E_INVALID;
-    }
-    MORNA_TRY(h16.alloc((size_t)n_slots * h->dpad));
-    MORNA_TRY(hn.alloc((size_t)n_slots * 2));   // norms, then rounding-error norms
-    MORNA_TRY(ambuf.alloc(16 + cap * sizeof(int2)));
     unsigned int *amb_count = (unsigned int *)ambuf.p;
     int2 *amb = (int2 *)(ambuf.p + 16);
-    // the open-pair counter is reset by the kernel that converts the level's hyperplanes (same stream, just before)
-    hipLaunchKernelGGL(rows_to_half_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, h->stream, hp_level,
-                       (int64_t)n_slots, h->dpad, h16.p, hn.p, hn.p + n_slots, (float *)nullptr, amb_count);
-    // 256 x 256 tiles once the level has hyperplane tiles enough for them to fill the chip in even rounds (MORNA_SPLIT_BIG=0:
-    // the 128 x 128 form everywhere)
-    static const bool big_on = env_on("MORNA_SPLIT_BIG");
-    // the tasks each row tile needs, from the second level of a tree on (MORNA_SPLIT_LISTS=0: every tile x every task)
-    static const bool lists_on = env_on("MORNA_SPLIT_LISTS");
-    if (big_on && (n_tasks >= 1024 || (ord && lists_on && n_tasks >= 512))) {
+    // a producer that did not have the hyperplanes in registers: the image is made from hp_level, by the kernel that also
+    // resets the open-pair counter (same stream, just before)
+    if (!image_from)
+        hipLaunchKernelGGL(rows_to_half_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, h->stream, hp_level,
+                           (int64_t)n_slots, h->dpad, h16.p, hn.p, hn.p + n_slots, (float *)nullptr, amb_count);
+    const bool big = split_mm_big(h, n_tasks), lists = split_mm_level_uses_lists(h, n_tasks);
+    if (big) {
         const unsigned n_rt = (unsigned)((N + 255) / 256), n_ct = (unsigned)((n_tasks + 255) / 256);
         const int32_t *col_list = nullptr, *col_count = nullptr, *col_first = nullptr;
-        if (lists_on) {
-            DevBuf<uint8_t> &active = h->splitmm.active;
-            DevBuf<int32_t> &lists = h->splitmm.lists;
-            MORNA_TRY(active.alloc((size_t)n_rt * n_tasks));
-            MORNA_TRY(lists.alloc((size_t)n_rt * n_tasks + 2 * n_rt + 1));
-            HIP_TRY(hipMemsetAsync(active.p, 0, (size_t)n_rt * n_tasks, h->stream));
-            hipLaunchKernelGGL(split_active_mark_kernel, dim3((unsigned)n_tasks), dim3(256), 0, h->stream, d_tasks, perm, N, rank, 8,
-                               n_tasks, active.p);
-            hipLaunchKernelGGL(split_active_list_kernel, dim3(n_rt), dim3(256), 0, h->stream, active.p, n_tasks, lists.p,
-                               lists.p + (size_t)n_rt * n_tasks);
-            col_list = lists.p;
-            col_count = lists.p + (size_t)n_rt * n_tasks;
-            // d_stat[1]: 256 x 256 tiles launched through the lists while the MORNA_T_SPLIT_MM timer is on (resolve_timers prices them)
-            const bool count_tiles = h->timing && (h->timing_mask & (1u << MORNA_T_SPLIT_MM));
-            hipLaunchKernelGGL(split_active_scan_kernel, dim3(1), dim3(1024), 0, h->stream, col_count, (int32_t)n_rt, 256,
-                               lists.p + (size_t)n_rt * n_tasks + n_rt, count_tiles ? h->d_stat.p + 1 : (unsigned long long *)nullptr);
+        if (lists) {
+            if (!lists_ready) MORNA_TRY(split_mm_level_lists(h, d_tasks, n_tasks, perm, h->stream));
+            col_list = h->splitmm.lists.p;
+            col_count = col_list + (size_t)n_rt * n_tasks;
             col_first = col_count + n_rt;
         }
         // executed flops: every launched (row tile, chunk of 256 tasks) pair is a 256 x 256 x dpad product; through the lists
-        // their number is only known on the device (counted above)
-        ScopedTimer tmm(h, MORNA_T_SPLIT_MM, lists_on ? 0 : 2ll * 256 * 256 * h->dpad * (int64_t)n_rt * n_ct);
+        // their number is only known on the device (counted by split_active_scan_kernel)
+        ScopedTimer tmm(h, MORNA_T_SPLIT_MM, lists ? 0 : 2ll * 256 * 256 * h->dpad * (int64_t)n_rt * n_ct);
         const float eps1 = (4.f * (float)h->dpad + 2.f) * 5.9604645e-8f + 4.1e-6f;   // EACC for ONE chain of dpad products
         HIP_TRY(hipFuncSetAttribute((const void *)split_mm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 256 * 4));
         hipLaunchKernelGGL(split_mm_kernel<true>, dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(1024), 128 * 256 * 4, h->stream, rows16, rows_n,
@@ -650,6 +679,9 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
         HIP_TRY(hipMemcpy(&n_open, amb_count, 4, hipMemcpyDeviceToHost));
         fprintf(stderr, "[morna] split_mm level: D=%d split nodes=%d (row, tree) pairs<=%lld open=%u (%.4f %%)\n", h->dim,
                 n_tasks, (long long)cap, n_open, 100.0 * n_open / (double)cap);
+        // which way the level went: the tile form, where its task lists were built, who made the hyperplanes' image
+        fprintf(stderr, "[morna] split_mm path: split nodes=%d tiles=%d lists=%s image=%s\n", n_tasks, big ? 256 : 128,
+                !lists ? "none" : lists_ready ? "ahead" : "inline", image_from ? image_from : "converted");
     }
     return MORNA_OK;
 }
