@@ -276,13 +276,30 @@ int morna_jstore_nearest_stats(const morna_jstore *s, double *stats);
  *                             MORNA_E_RANGE naming it.
  *   morna_jstore_recovery_stats      of the last call, stats[3]: kernel ms (HIP events), algorithmic bytes (8 per entry of the
  *                             result and truth rows named, 4 per line of a CSR truth), workgroups launched.  All 0 after a
- *                             call with nq = 0 or one that failed its checks.
+ *                             call with nq = 0 or one that failed its checks.  After a sweep (below): the sweep's.
+ *
+ * Several result counts from one pass.  prefixes[n_prefixes]: list lengths p_1 < ... < p_P, each in 1 .. 64,
+ * 1 <= P <= 8 (MORNA_E_INVALID naming the offending value otherwise; a null pointer likewise).  hist_out is int32
+ * [nq][P][2][65][n_grid + 1]; slice [q][i] is, entry for entry, what morna_jstore_recovery returns for list q cut to its first
+ * min(p_i, n_results[q]) results with the same truth and grid -- so two prefixes past the end of a list give equal slices.
+ * Ranks at or beyond p_P are not read by the kernel (their ids are still looked up: MORNA_E_RANGE for one the store lacks).
+ * The rows are read once and one kernel is launched, whatever P.
+ *   morna_jstore_recovery_sweep            the arguments and checks of morna_jstore_recovery, truth as a CSR of lines.
+ *   morna_jstore_recovery_sweep_by_sample  those of morna_jstore_recovery_by_sample, truth as a store row and a minimum coverage.
+ * morna_jstore_recovery_stats after a sweep: bytes = 8 per entry of the first min(p_P, n_results[q]) result rows of every
+ * list, counted once, plus the truth as above; workgroups = nq x tiles.
  */
 int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
                           const int64_t *t_ptr, const int32_t *t_line, const int64_t *cov_grid, int32_t n_grid, int32_t *hist_out);
 int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
                                     const int64_t *truth_ext, int64_t truth_min_cov, const int64_t *cov_grid, int32_t n_grid,
                                     int32_t *hist_out);
+int morna_jstore_recovery_sweep(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                const int64_t *t_ptr, const int32_t *t_line, const int64_t *cov_grid, int32_t n_grid,
+                                const int32_t *prefixes, int32_t n_prefixes, int32_t *hist_out);
+int morna_jstore_recovery_sweep_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                          const int64_t *truth_ext, int64_t truth_min_cov, const int64_t *cov_grid, int32_t n_grid,
+                                          const int32_t *prefixes, int32_t n_prefixes, int32_t *hist_out);
 int morna_jstore_recovery_stats(const morna_jstore *s, double *stats);
 
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */

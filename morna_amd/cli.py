@@ -22,6 +22,9 @@ how many of the query's true junctions are among them (the columns junction_reco
 reference's tests/ prints for one run of its aligner pipeline).  The truth is the query sample's own row of the
 store, the sample itself left out of its results (-q / --query-ids), or the same sample in a second, deeper
 intropolis file (--intropolis shallow --truth deep).  One pass on the GPU per run, whatever the size of the grid.
+--results-sweep 5,10,20 tabulates those result counts too from the same pass: the lists are the prefixes of the one search
+-r deep (for -e the lists of separate -r runs; for the approximate search, whose default search_k grows with -r, the
+prefixes of the deeper and so better search).
 
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
@@ -37,6 +40,7 @@ here do the latter.
     python -m morna_amd.cli junctions -x idx -p1 pass1.sam --junction-file junctions.tsv.gz -sf splices.txt
     python -m morna_amd.cli junctions -x idx --intropolis new_samples.tsv.gz --junction-file junctions.tsv.gz -sf splices
     python -m morna_amd.cli recovery -x idx --query-ids 12,34,56 -r 20 --grid 0,.05,.5:1,5,50
+    python -m morna_amd.cli recovery -x idx --query-ids 12,34,56 -r 64 --results-sweep 5,10,20,40,64 --summary-only
     python -m morna_amd.cli recovery -x idx --intropolis shallow.tsv.gz --truth deep.tsv.gz --junction-file junctions.tsv.gz
 """
 import argparse
@@ -180,6 +184,10 @@ def build_parser():
                                       'names the junction of every line')
     recovery_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
                                  help='print only the table over all queries')
+    recovery_parser.add_argument('--results-sweep', type=str, metavar='<p1,p2,...>', required=False, default=None,
+                                 help='tabulate these result counts (at most 8, each at most -r) from the one search -r deep '
+                                      'and one pass over its results: a block per count for every query, then a table over '
+                                      'all queries per count')
     return parser
 
 
@@ -190,6 +198,16 @@ def _check_recovery_flags(parser, args):
         args.grid_parts = parse_recovery_grid(args.grid)
     except ValueError as e:
         parser.error("--grid takes <frequencies>:<coverages>, such as 0,.05,.5:1,5,50, with at most 15 coverages (%s)" % e)
+    args.sweep = None
+    if args.results_sweep is not None:
+        from .junctions import parse_results_sweep
+        try:
+            args.sweep = parse_results_sweep(args.results_sweep)
+        except ValueError as e:
+            parser.error("--results-sweep takes at most 8 comma-separated result counts, each 1 to 64, such as 5,10,20 (%s)" % e)
+        if args.sweep[-1] > args.results:
+            parser.error("--results-sweep %d is more than -r %d: the counts are prefixes of the one search -r deep"
+                         % (args.sweep[-1], args.results))
     for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist),
                      ("-m/--metadata", args.metadata), ("-d/--distances", args.distances), ("--unhashed", args.unhashed)):
         if on:
@@ -393,7 +411,7 @@ def _recovery(args, searcher, stdin, stdout):
             own = searcher.internal_id_map[label]
             lists.append([i for i in res[0] if i != own][:wanted])
             truth.append(own)
-        hist = searcher.junction_recovery(lists, truth, coverages, args.truth_coverage)
+        min_coverage = args.truth_coverage
     else:
         lists = [list(res[0])[:wanted] for _, res in collected]
         truth_of = intropolis_truth(args.truth, key_lines(args.junction_file, searcher.junction_store().n_lines), args.truth_coverage)
@@ -405,16 +423,25 @@ def _recovery(args, searcher, stdin, stdout):
             extra[q] = truth_of[label][1]
         sys.stderr.write("%d true junctions of %s are not in %s: they count as false negatives\n"
                          % (sum(extra), args.truth, args.junction_file))
-        hist = searcher.junction_recovery(lists, truth, coverages) if lists else []
-    tables = []
+        min_coverage = 1                                       # (intropolis_truth has applied --truth-coverage)
+    if args.sweep is None:
+        hist = searcher.junction_recovery(lists, truth, coverages, min_coverage) if lists else []
+        slices = [(None, [hist[q] for q in range(len(lists))])]
+    else:
+        hist = searcher.junction_recovery_sweep(lists, truth, coverages, args.sweep, min_coverage) if lists else []
+        slices = [(p, [hist[q][i] for q in range(len(lists))]) for i, p in enumerate(args.sweep)]
+    tables = [[] for _ in slices]                              # per result count, per query
     for q, label in enumerate(labels):
-        rows = recovery_rows(hist[q], len(lists[q]), frequencies, coverages, extra_true=extra[q])
-        tables.append(rows)
-        if not args.summary_only:
-            stdout.write("# query %s\tresults %d\ttrue %d\n" % (label, len(lists[q]), rows[0]["true_positive"] + rows[0]["false_negative"]))
-            stdout.write(format_recovery_rows(rows))
-    stdout.write("# all %d queries\n" % len(tables))
-    stdout.write(format_recovery_rows(sum_recovery_rows(tables)))
+        for i, (p, hists) in enumerate(slices):
+            m = len(lists[q]) if p is None else min(p, len(lists[q]))
+            rows = recovery_rows(hists[q], m, frequencies, coverages, extra_true=extra[q])
+            tables[i].append(rows)
+            if not args.summary_only:
+                stdout.write("# query %s\tresults %d\ttrue %d\n" % (label, m, rows[0]["true_positive"] + rows[0]["false_negative"]))
+                stdout.write(format_recovery_rows(rows))
+    for i, (p, _) in enumerate(slices):
+        stdout.write("# all %d queries%s\n" % (len(labels), "" if p is None else "\tresults %d" % p))
+        stdout.write(format_recovery_rows(sum_recovery_rows(tables[i])))
     return rc
 
 

@@ -36,6 +36,10 @@
 // 2 x 65 x (B + 1) classes for a grid of B coverage thresholds.  The tile counts its lines per class in LDS and adds its
 // non-zero classes to hist[q] with integer atomics: every cell of a filter grid is then a sum over classes on the host,
 // and nothing of the size of the line count comes back.
+//
+// Recovery sweep: the recovery tile for several lengths of every list at once.  The walk takes the ranks
+// in the buckets the lengths cut; at every boundary the tile's words and maxima are those of the shorter list, so it is
+// classified and added to that length's histogram before the walk goes on.  One read of the rows, one launch.
 #include <unistd.h>
 
 #include <algorithm>
@@ -218,12 +222,14 @@ __device__ __forceinline__ void tile_ranges(const JTile &T, const int64_t *__res
     }
 }
 
-// the walk: one wave per result r, f(r, i, l) for every entry i of its list on line t0 + l of the tile
+// the walk: one wave per result r of the ranks [r_first, r_end), a workgroup-uniform range inside [0, T.m):
+// f(r, i, l) for every entry i of its list on line t0 + l of the tile
 template <typename F>
-__device__ __forceinline__ void walk_tile(const JTile &T, const int32_t *__restrict__ line, const int64_t *s_lo, const int64_t *s_hi, F f)
+__device__ __forceinline__ void walk_tile(const JTile &T, const int32_t *__restrict__ line, const int64_t *s_lo, const int64_t *s_hi,
+                                          int r_first, int r_end, F f)
 {
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    for (int r = wave; r < T.m; r += JT_THREADS / WAVE) {
+    for (int r = r_first + wave; r < r_end; r += JT_THREADS / WAVE) {
         const int64_t hi = s_hi[r];
         for (int64_t i = s_lo[r] + lane; i < hi; i += WAVE) {
             const int64_t l = (int64_t)line[i] - T.t0;
@@ -231,6 +237,13 @@ __device__ __forceinline__ void walk_tile(const JTile &T, const int32_t *__restr
             f(r, i, l);
         }
     }
+}
+
+// every result of the list
+template <typename F>
+__device__ __forceinline__ void walk_tile(const JTile &T, const int32_t *__restrict__ line, const int64_t *s_lo, const int64_t *s_hi, F f)
+{
+    walk_tile(T, line, s_lo, s_hi, 0, T.m, f);
 }
 
 // One workgroup per (tile, query).  write == 0: tile_n[q][tile] = {retained lines, their found_in bits}.
@@ -358,11 +371,98 @@ __global__ __launch_bounds__(256) void jstore_tile_scan_kernel(int64_t *__restri
 
 #define JR_MAX_GRID 15                   // coverage thresholds of one call: b takes 0 .. 15
 #define JR_COUNTS 65                     // cnt takes 0 .. 64
+#define JR_MAX_PREFIXES 8                // list lengths of one sweep
 
 struct JRGrid {
     int64_t c[JR_MAX_GRID];   // strictly ascending
     int32_t n;
 };
+
+struct JRPrefixes {
+    int32_t p[JR_MAX_PREFIXES];   // strictly ascending, 1 .. 64
+    int32_t n;
+};
+
+// the LDS of a recovery tile, 58 KiB
+struct JRTile {
+    unsigned long long *mask;   // [JT_LINES] found_in of every line
+    int32_t *max;               // [JT_LINES] its largest coverage among the results that hold it
+    uint32_t *truth;            // [JT_LINES / 32] its truth bit
+    int64_t *lo, *hi;           // [65] the tile's extent in every result's list; slot 64: in the truth
+    uint32_t *hist;             // [2 * JR_COUNTS * (grid.n + 1)] the tile's lines per class
+};
+
+// The tile's LDS cleared and its extents found (a barrier must follow).  Truth: the entries of store row truth_rows[q], or,
+// with truth_rows NULL, t_line[t_ptr[q] .. t_ptr[q + 1]); t_arr is the array those positions index.
+__device__ __forceinline__ void recovery_begin(const JTile &T, const JRTile &L, int n_bins, const int64_t *__restrict__ ptr,
+                                               const int32_t *__restrict__ line, const int32_t *__restrict__ rows, int32_t k,
+                                               const int32_t *__restrict__ truth_rows, const int64_t *__restrict__ t_ptr,
+                                               const int32_t *__restrict__ t_arr)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < JT_LINES; i += JT_THREADS) {
+        L.mask[i] = 0;
+        L.max[i] = INT32_MIN;   // below every coverage, a negative one included
+    }
+    for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) L.truth[i] = 0;
+    for (int i = tid; i < n_bins; i += JT_THREADS) L.hist[i] = 0;
+    tile_ranges(T, ptr, line, rows, k, L.lo, L.hi);
+    if (tid >= 128 && tid < 130) {   // threads 128 and 129: the same in the truth
+        int64_t a, b;
+        if (truth_rows) {
+            const int32_t row = truth_rows[T.q];
+            a = ptr[row];
+            b = ptr[row + 1];
+        } else {
+            a = t_ptr[T.q];
+            b = t_ptr[T.q + 1];
+        }
+        const int64_t at = lower_bound_line(t_arr, a, b, tid == 128 ? T.t0 : T.t1);
+        if (tid == 128) L.lo[64] = at;
+        else L.hi[64] = at;
+    }
+}
+
+// the truth run of the tile into its bitmap, by the whole workgroup; by_sample: only entries covered truth_min_cov times
+__device__ __forceinline__ void recovery_mark_truth(const JTile &T, const JRTile &L, const int32_t *__restrict__ t_arr,
+                                                    const int32_t *__restrict__ cov, bool by_sample, int64_t truth_min_cov)
+{
+    const int64_t hi = L.hi[64];
+    for (int64_t i = L.lo[64] + threadIdx.x; i < hi; i += JT_THREADS) {
+        const int64_t l = (int64_t)t_arr[i] - T.t0;
+        if (l < 0 || l >= JT_LINES) continue;
+        if (!by_sample || (int64_t)cov[i] >= truth_min_cov) atomicOr(&L.truth[l >> 5], 1u << (l & 31));
+    }
+}
+
+// thread t classifies lines [t * JT_PER, (t + 1) * JT_PER) of the tile into L.hist; a run of one class is one LDS add
+__device__ __forceinline__ void recovery_classify(const JTile &T, const JRTile &L, const JRGrid &grid)
+{
+    const int nb = grid.n + 1;
+    int cur = -1;
+    uint32_t run = 0;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = threadIdx.x * JT_PER + j;
+        if (T.t0 + l >= T.t1) break;
+        const int c = __popcll(L.mask[l]);
+        const int t = (int)((L.truth[l >> 5] >> (l & 31)) & 1u);
+        if (c == 0 && t == 0) continue;
+        int b = 0;
+        if (c) {
+            const int64_t mx = L.max[l];
+#pragma unroll
+            for (int i = 0; i < JR_MAX_GRID; i++) b += (i < grid.n && grid.c[i] <= mx) ? 1 : 0;
+        }
+        const int bin = (t * JR_COUNTS + c) * nb + b;
+        if (bin != cur) {
+            if (run) atomicAdd(&L.hist[cur], run);
+            cur = bin;
+            run = 0;
+        }
+        run++;
+    }
+    if (run) atomicAdd(&L.hist[cur], run);
+}
 
 // One workgroup per (tile, query).  hist[q][t][cnt][b] += the lines of the tile with truth bit t that cnt of the results
 // hold and whose largest coverage among them reaches b of the thresholds (b = 0 when cnt = 0); plane t = 0 at cnt = 0 is
@@ -380,75 +480,75 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_recovery_kernel(const int64
     __shared__ uint32_t s_truth[JT_LINES / 32];
     __shared__ int64_t s_lo[65], s_hi[65];   // slot 64: the truth
     __shared__ uint32_t s_hist[2 * JR_COUNTS * (JR_MAX_GRID + 1)];
+    const JRTile L = {s_mask, s_max, s_truth, s_lo, s_hi, s_hist};
     const int tid = threadIdx.x;
     const JTile T = tile_of_block(n_lines, n_tiles, n_results, k);
-    const int64_t q = T.q, t0 = T.t0, t1 = T.t1;
-    const int nb = grid.n + 1, n_bins = 2 * JR_COUNTS * nb;
+    const int n_bins = 2 * JR_COUNTS * (grid.n + 1);
     const int32_t *t_arr = truth_rows ? line : t_line;
-    for (int i = tid; i < JT_LINES; i += JT_THREADS) {
-        s_mask[i] = 0;
-        s_max[i] = INT32_MIN;   // below every coverage, a negative one included
-    }
-    for (int i = tid; i < JT_LINES / 32; i += JT_THREADS) s_truth[i] = 0;
-    for (int i = tid; i < n_bins; i += JT_THREADS) s_hist[i] = 0;
-    tile_ranges(T, ptr, line, rows, k, s_lo, s_hi);
-    if (tid >= 128 && tid < 130) {   // threads 128 and 129: the same in the truth
-        int64_t a, b;
-        if (truth_rows) {
-            const int32_t row = truth_rows[q];
-            a = ptr[row];
-            b = ptr[row + 1];
-        } else {
-            a = t_ptr[q];
-            b = t_ptr[q + 1];
-        }
-        const int64_t at = lower_bound_line(t_arr, a, b, tid == 128 ? t0 : t1);
-        if (tid == 128) s_lo[64] = at;
-        else s_hi[64] = at;
-    }
+    recovery_begin(T, L, n_bins, ptr, line, rows, k, truth_rows, t_ptr, t_arr);
     __syncthreads();
     walk_tile(T, line, s_lo, s_hi, [&](int r, int64_t i, int64_t l) {
         atomicOr(&s_mask[l], 1ull << r);
         atomicMax(&s_max[l], cov[i]);
     });
-    {
-        const int64_t hi = s_hi[64];
-        for (int64_t i = s_lo[64] + tid; i < hi; i += JT_THREADS) {
-            const int64_t l = (int64_t)t_arr[i] - t0;
-            if (l < 0 || l >= JT_LINES) continue;
-            if (!truth_rows || (int64_t)cov[i] >= truth_min_cov) atomicOr(&s_truth[l >> 5], 1u << (l & 31));
-        }
-    }
+    recovery_mark_truth(T, L, t_arr, cov, truth_rows != nullptr, truth_min_cov);
     __syncthreads();
-    // thread t classifies lines [t * JT_PER, (t + 1) * JT_PER) of the tile; a run of one class is one LDS add
-    int cur = -1;
-    uint32_t run = 0;
-    for (int j = 0; j < JT_PER; j++) {
-        const int l = tid * JT_PER + j;
-        if (t0 + l >= t1) break;
-        const int c = __popcll(s_mask[l]);
-        const int t = (int)((s_truth[l >> 5] >> (l & 31)) & 1u);
-        if (c == 0 && t == 0) continue;
-        int b = 0;
-        if (c) {
-            const int64_t mx = s_max[l];
-#pragma unroll
-            for (int i = 0; i < JR_MAX_GRID; i++) b += (i < grid.n && grid.c[i] <= mx) ? 1 : 0;
-        }
-        const int bin = (t * JR_COUNTS + c) * nb + b;
-        if (bin != cur) {
-            if (run) atomicAdd(&s_hist[cur], run);
-            cur = bin;
-            run = 0;
-        }
-        run++;
-    }
-    if (run) atomicAdd(&s_hist[cur], run);
+    recovery_classify(T, L, grid);
     __syncthreads();
-    int32_t *mine = hist + q * n_bins;
+    int32_t *mine = hist + T.q * n_bins;
     for (int i = tid; i < n_bins; i += JT_THREADS) {
         const uint32_t v = s_hist[i];
         if (v) atomicAdd(&mine[i], (int32_t)v);   // at most n_lines < 2^31 in all
+    }
+}
+
+// The recovery kernel for several lengths of every list in one walk: hist[q][i] is what
+// jstore_recovery_kernel gives for list q cut to its first min(pre.p[i], m) results.  cnt of a prefix is the popcount of
+// the low bits of found_in and maxcov a running maximum over ranks, so the walk visits the ranks in the buckets the
+// prefixes cut, and at every boundary s_mask / s_max ARE the shorter list's: classify, add to that slice, go on.  The
+// phase count and every boundary are the same for all threads of a workgroup (kernel arguments and n_results[q]), so
+// every barrier is reached by all.
+__global__ __launch_bounds__(JT_THREADS) void jstore_recovery_sweep_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                                                           const int32_t *__restrict__ cov, int64_t n_lines, int32_t n_tiles,
+                                                                           const int32_t *__restrict__ rows,
+                                                                           const int32_t *__restrict__ n_results, int32_t k,
+                                                                           const int32_t *__restrict__ truth_rows, int64_t truth_min_cov,
+                                                                           const int64_t *__restrict__ t_ptr, const int32_t *__restrict__ t_line,
+                                                                           JRGrid grid, JRPrefixes pre, int32_t *__restrict__ hist)
+{
+    __shared__ unsigned long long s_mask[JT_LINES];
+    __shared__ int32_t s_max[JT_LINES];
+    __shared__ uint32_t s_truth[JT_LINES / 32];
+    __shared__ int64_t s_lo[65], s_hi[65];   // slot 64: the truth
+    __shared__ uint32_t s_hist[2 * JR_COUNTS * (JR_MAX_GRID + 1)];   // one, reused by every prefix
+    const JRTile L = {s_mask, s_max, s_truth, s_lo, s_hi, s_hist};
+    const int tid = threadIdx.x;
+    const JTile T = tile_of_block(n_lines, n_tiles, n_results, k);
+    const int n_bins = 2 * JR_COUNTS * (grid.n + 1);
+    const int32_t *t_arr = truth_rows ? line : t_line;
+    recovery_begin(T, L, n_bins, ptr, line, rows, k, truth_rows, t_ptr, t_arr);
+    __syncthreads();
+    int32_t m_done = 0;
+    for (int32_t p = 0; p < pre.n; p++) {
+        const int32_t m_p = pre.p[p] < T.m ? pre.p[p] : T.m;   // an empty bucket once the list has ended: the slices repeat
+        walk_tile(T, line, s_lo, s_hi, m_done, m_p, [&](int r, int64_t i, int64_t l) {
+            atomicOr(&s_mask[l], 1ull << r);
+            atomicMax(&s_max[l], cov[i]);
+        });
+        m_done = m_p;
+        if (p == 0) recovery_mark_truth(T, L, t_arr, cov, truth_rows != nullptr, truth_min_cov);
+        __syncthreads();
+        recovery_classify(T, L, grid);
+        __syncthreads();
+        int32_t *mine = hist + (T.q * pre.n + p) * n_bins;
+        for (int i = tid; i < n_bins; i += JT_THREADS) {
+            const uint32_t v = s_hist[i];
+            if (v) {
+                atomicAdd(&mine[i], (int32_t)v);   // at most n_lines < 2^31 in all
+                s_hist[i] = 0;
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -752,9 +852,11 @@ int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_resul
     return MORNA_OK;
 }
 
-// truth_ext != NULL: truth by sample; otherwise the CSR (t_ptr, t_line)
+// truth_ext != NULL: truth by sample; otherwise the CSR (t_ptr, t_line).  pre != NULL: the sweep, one histogram per prefix
+// of every list (hist_out[nq][pre->n][...]) from the first pre->p[pre->n - 1] rows of each
 int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k, const int64_t *t_ptr,
-                  const int32_t *t_line, const int64_t *truth_ext, int64_t truth_min_cov, const JRGrid &grid, int32_t *hist_out)
+                  const int32_t *t_line, const int64_t *truth_ext, int64_t truth_min_cov, const JRGrid &grid, const JRPrefixes *pre,
+                  int32_t *hist_out)
 {
     st->rec_ms = 0;
     st->rec_bytes = 0;
@@ -764,6 +866,14 @@ int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_res
     std::vector<int64_t> tp;
     int64_t entries = 0, t_base = 0, t_n = 0, n_tiles = 0;
     MORNA_TRY(resolve_lists(st, "jstore_recovery", results, n_results, nq, k, rows, entries));
+    if (pre) {   // the rows the longest prefix reaches, each counted once
+        entries = 0;
+        for (int64_t q = 0; q < nq; q++)
+            for (int32_t r = 0; r < std::min(n_results[q], pre->p[pre->n - 1]); r++) {
+                const size_t row = (size_t)rows[(size_t)(q * k + r)];
+                entries += st->ptr[row + 1] - st->ptr[row];
+            }
+    }
     if (truth_ext) {
         truth_rows.assign((size_t)nq, 0);
         for (int64_t q = 0; q < nq; q++) {
@@ -798,7 +908,7 @@ int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_res
     }
     MORNA_TRY(make_resident(st));
     MORNA_TRY(tile_count(st, "jstore_recovery", nq, &n_tiles));
-    const size_t n_hist = (size_t)nq * 2 * JR_COUNTS * (size_t)(grid.n + 1);
+    const size_t n_hist = (size_t)nq * (size_t)(pre ? pre->n : 1) * 2 * JR_COUNTS * (size_t)(grid.n + 1);
     DevBuf<int32_t> d_rows, d_nres, d_truth_rows, d_tline, d_hist;
     DevBuf<int64_t> d_tptr;
     MORNA_TRY(d_rows.alloc((size_t)(nq * k)));
@@ -819,9 +929,14 @@ int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_res
     MORNA_TRY(ev.create());
     HIP_TRY(hipEventRecord(ev.a, st->stream));
     HIP_TRY(hipMemsetAsync(d_hist.p, 0, n_hist * sizeof(int32_t), st->stream));
-    hipLaunchKernelGGL(jstore_recovery_kernel, dim3((unsigned)(nq * n_tiles)), dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p,
-                       st->d_cov.p, st->n_lines, (int32_t)n_tiles, d_rows.p, d_nres.p, k, (const int32_t *)d_truth_rows.p, truth_min_cov,
-                       (const int64_t *)d_tptr.p, (const int32_t *)d_tline.p, grid, d_hist.p);
+    if (pre)
+        hipLaunchKernelGGL(jstore_recovery_sweep_kernel, dim3((unsigned)(nq * n_tiles)), dim3(JT_THREADS), 0, st->stream, st->d_ptr.p,
+                           st->d_line.p, st->d_cov.p, st->n_lines, (int32_t)n_tiles, d_rows.p, d_nres.p, k, (const int32_t *)d_truth_rows.p,
+                           truth_min_cov, (const int64_t *)d_tptr.p, (const int32_t *)d_tline.p, grid, *pre, d_hist.p);
+    else
+        hipLaunchKernelGGL(jstore_recovery_kernel, dim3((unsigned)(nq * n_tiles)), dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p,
+                           st->d_cov.p, st->n_lines, (int32_t)n_tiles, d_rows.p, d_nres.p, k, (const int32_t *)d_truth_rows.p, truth_min_cov,
+                           (const int64_t *)d_tptr.p, (const int32_t *)d_tline.p, grid, d_hist.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, st->stream));
     HIP_TRY(hipMemcpyAsync(hist_out, d_hist.p, n_hist * sizeof(int32_t), hipMemcpyDeviceToHost, st->stream));
@@ -863,6 +978,33 @@ int recovery_arguments(const morna_jstore *s, const int64_t *results, const int3
                       i, (long long)cov_grid[i], i - 1, (long long)cov_grid[i - 1]);
             return MORNA_E_INVALID;
         }
+    return MORNA_OK;
+}
+
+// the prefix lengths of a sweep; MORNA_OK with *pre filled
+int sweep_arguments(const int32_t *prefixes, int32_t n_prefixes, JRPrefixes *pre)
+{
+    if (!prefixes) {
+        set_error("jstore_recovery_sweep: null argument (prefixes)");
+        return MORNA_E_INVALID;
+    }
+    if (n_prefixes < 1 || n_prefixes > JR_MAX_PREFIXES) {
+        set_error("jstore_recovery_sweep: %d prefix lengths: a sweep holds 1 to %d", n_prefixes, JR_MAX_PREFIXES);
+        return MORNA_E_INVALID;
+    }
+    for (int32_t i = 0; i < JR_MAX_PREFIXES; i++) pre->p[i] = i < n_prefixes ? prefixes[i] : 64;
+    pre->n = n_prefixes;
+    for (int32_t i = 0; i < n_prefixes; i++) {
+        if (prefixes[i] < 1 || prefixes[i] > 64) {
+            set_error("jstore_recovery_sweep: prefix length %d (%d) is outside 1 to 64, the results a list holds", i, prefixes[i]);
+            return MORNA_E_INVALID;
+        }
+        if (i > 0 && prefixes[i] <= prefixes[i - 1]) {
+            set_error("jstore_recovery_sweep: prefix length %d (%d) is not above prefix length %d (%d): the lengths must ascend strictly",
+                      i, prefixes[i], i - 1, prefixes[i - 1]);
+            return MORNA_E_INVALID;
+        }
+    }
     return MORNA_OK;
 }
 
@@ -1080,7 +1222,7 @@ int morna_jstore_recovery(morna_jstore *s, const int64_t *results, const int32_t
         return MORNA_E_INVALID;
     }
     return guarded("jstore_recovery", MORNA_E_INVALID,
-                   [&] { return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, hist_out); });
+                   [&] { return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, nullptr, hist_out); });
 }
 
 int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
@@ -1094,7 +1236,40 @@ int morna_jstore_recovery_by_sample(morna_jstore *s, const int64_t *results, con
         return MORNA_E_INVALID;
     }
     return guarded("jstore_recovery", MORNA_E_INVALID,
-                   [&] { return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, hist_out); });
+                   [&] { return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, nullptr, hist_out); });
+}
+
+int morna_jstore_recovery_sweep(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                const int64_t *t_ptr, const int32_t *t_line, const int64_t *cov_grid, int32_t n_grid,
+                                const int32_t *prefixes, int32_t n_prefixes, int32_t *hist_out)
+{
+    JRGrid grid;
+    JRPrefixes pre;
+    MORNA_TRY(recovery_arguments(s, results, n_results, nq, k, cov_grid, n_grid, hist_out, &grid));
+    MORNA_TRY(sweep_arguments(prefixes, n_prefixes, &pre));
+    if (nq > 0 && (!t_ptr || (t_ptr[nq] > t_ptr[0] && !t_line))) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    return guarded("jstore_recovery_sweep", MORNA_E_INVALID,
+                   [&] { return recovery_impl(s, results, n_results, nq, k, t_ptr, t_line, nullptr, 0, grid, &pre, hist_out); });
+}
+
+int morna_jstore_recovery_sweep_by_sample(morna_jstore *s, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k,
+                                          const int64_t *truth_ext, int64_t truth_min_cov, const int64_t *cov_grid, int32_t n_grid,
+                                          const int32_t *prefixes, int32_t n_prefixes, int32_t *hist_out)
+{
+    JRGrid grid;
+    JRPrefixes pre;
+    MORNA_TRY(recovery_arguments(s, results, n_results, nq, k, cov_grid, n_grid, hist_out, &grid));
+    MORNA_TRY(sweep_arguments(prefixes, n_prefixes, &pre));
+    if (nq > 0 && !truth_ext) {
+        set_error("jstore_recovery: null argument");
+        return MORNA_E_INVALID;
+    }
+    return guarded("jstore_recovery_sweep", MORNA_E_INVALID, [&] {
+        return recovery_impl(s, results, n_results, nq, k, nullptr, nullptr, truth_ext, truth_min_cov, grid, &pre, hist_out);
+    });
 }
 
 int morna_jstore_recovery_stats(const morna_jstore *s, double *stats)

@@ -24,6 +24,7 @@ WEIGHTS_SUFFIX = ".jw.mor"      # the line weights of the unhashed search (save_
 WEIGHTS_MAGIC = b"MORNAJW1"
 MAX_NEAREST = 1024              # neighbours per query of the unhashed search (MORNA_JNEAREST_MAX_K)
 MAX_GRID = 15                   # coverage thresholds of one recovery call (morna_jstore_recovery)
+MAX_PREFIXES = 8                # list lengths of one recovery sweep (morna_jstore_recovery_sweep)
 DEFAULT_RECOVERY_GRID = "0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000"
 RECOVERY_COLUMNS = ("frequency_filter", "coverage_filter", "min_count", "retrieved", "true_positive", "false_positive",
                     "false_negative", "precision", "recall", "fscore")
@@ -58,6 +59,18 @@ def parse_recovery_grid(text=None):
     if len(coverages) > MAX_GRID:
         raise ValueError("--grid holds %d distinct coverages: one recovery call takes at most %d" % (len(coverages), MAX_GRID))
     return frequencies, coverages
+
+
+def parse_results_sweep(text):
+    """--results-sweep "<p1>,<p2>,...": the result counts to tabulate, as integers sorted and de-duplicated; each in 1 to
+    64, at most 8 distinct ones.  ValueError otherwise."""
+    values = sorted(set(int(t) for t in str(text).split(",")))             # (int() raises on "", "1.5" and "a")
+    for p in values:
+        if p < 1 or p > MAX_RESULTS:
+            raise ValueError("--results-sweep: %d is outside 1 to %d, the results a list holds" % (p, MAX_RESULTS))
+    if len(values) > MAX_PREFIXES:
+        raise ValueError("--results-sweep holds %d distinct values: one sweep takes at most %d" % (len(values), MAX_PREFIXES))
+    return values
 
 
 def _ratio(a, b):
@@ -279,11 +292,34 @@ class JunctionStore(object):
                 "bytes": int(s[4]), "queries_per_pass": int(s[5]), "norms_ms": float(s[6]), "window": float(s[7])}
 
     # ---- recovery tables over the filter grid -------------------------------------------------------
-    def _recovery_arguments(self, result_sample_ids, coverage_grid):
+    def _recovery_arguments(self, result_sample_ids, coverage_grid, prefixes=None):
+        """prefixes: of a sweep, which adds them (int32) to what is returned and an axis of their number to hist."""
         res, n_res, k = _pack_lists(result_sample_ids, "the recovery tables take at most %d, as the junction filter does")
         grid = np.array([_clamp62(c) for c in coverage_grid], np.int64)
-        hist = np.zeros((len(n_res), 2, MAX_RESULTS + 1, max(min(len(grid), MAX_GRID), 0) + 1), np.int32)
-        return res, n_res, k, grid, hist
+        planes = (2, MAX_RESULTS + 1, max(min(len(grid), MAX_GRID), 0) + 1)
+        if prefixes is None:
+            return res, n_res, k, grid, np.zeros((len(n_res),) + planes, np.int32)
+        pre = np.array([min(max(int(p), -2**31), 2**31 - 1) for p in prefixes], np.int32)
+        return res, n_res, k, grid, pre, np.zeros((len(n_res), max(min(len(pre), MAX_PREFIXES), 1)) + planes, np.int32)
+
+    def _truth_csr(self, truth_lines, n_lists):
+        """truth_lines[q], line numbers, as (t_ptr int64 [nq + 1], t_line int32); ValueError for a line the store lacks."""
+        truth = [np.ascontiguousarray(t, np.int64).reshape(-1) for t in truth_lines]
+        if len(truth) != n_lists:
+            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (n_lists, len(truth)))
+        for q, t in enumerate(truth):
+            if len(t) and (t.min() < 0 or t.max() >= self.n_lines):
+                raise ValueError("the truth of list %d names line %d: the store has lines 0 to %d"
+                                 % (q, int(t.min() if t.min() < 0 else t.max()), self.n_lines - 1))
+        t_ptr = np.zeros(len(truth) + 1, np.int64)
+        np.cumsum([len(t) for t in truth], out=t_ptr[1:])
+        return t_ptr, np.concatenate(truth + [np.zeros(0, np.int64)]).astype(np.int32)
+
+    def _truth_ids(self, truth_sample_ids, n_lists):
+        truth = np.ascontiguousarray([int(t) for t in truth_sample_ids], np.int64)
+        if len(truth) != n_lists:
+            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (n_lists, len(truth)))
+        return truth
 
     def recovery(self, result_sample_ids, truth_lines, coverage_grid):
         """For every list of `result_sample_ids` (external sample ids in rank order, at most 64 per list) and its truth --
@@ -293,16 +329,7 @@ class JunctionStore(object):
         (strictly ascending, at most 15); plane t = 0 is left 0 at cnt = 0.  One pass on the GPU; only the histogram
         comes back."""
         res, n_res, k, grid, hist = self._recovery_arguments(result_sample_ids, coverage_grid)
-        truth = [np.ascontiguousarray(t, np.int64).reshape(-1) for t in truth_lines]
-        if len(truth) != len(n_res):
-            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (len(n_res), len(truth)))
-        for q, t in enumerate(truth):
-            if len(t) and (t.min() < 0 or t.max() >= self.n_lines):
-                raise ValueError("the truth of list %d names line %d: the store has lines 0 to %d"
-                                 % (q, int(t.min() if t.min() < 0 else t.max()), self.n_lines - 1))
-        t_ptr = np.zeros(len(truth) + 1, np.int64)
-        np.cumsum([len(t) for t in truth], out=t_ptr[1:])
-        t_line = np.concatenate(truth + [np.zeros(0, np.int64)]).astype(np.int32)
+        t_ptr, t_line = self._truth_csr(truth_lines, len(n_res))
         check(lib().morna_jstore_recovery(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(t_ptr), ptr(t_line), ptr(grid),
                                           len(grid), ptr(hist)))
         return hist.astype(np.int64)
@@ -311,16 +338,35 @@ class JunctionStore(object):
         """recovery() with the truth of list q taken from the store's own row of truth_sample_ids[q] (an external id): its
         lines covered at least truth_min_coverage times.  Only ids go to the device."""
         res, n_res, k, grid, hist = self._recovery_arguments(result_sample_ids, coverage_grid)
-        truth = np.ascontiguousarray([int(t) for t in truth_sample_ids], np.int64)
-        if len(truth) != len(n_res):
-            raise ValueError("recovery takes one truth per result list (%d lists, %d truths)" % (len(n_res), len(truth)))
+        truth = self._truth_ids(truth_sample_ids, len(n_res))
         check(lib().morna_jstore_recovery_by_sample(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(truth),
                                                     _clamp62(truth_min_coverage), ptr(grid), len(grid), ptr(hist)))
         return hist.astype(np.int64)
 
+    def recovery_sweep(self, result_sample_ids, truth_lines, coverage_grid, prefixes):
+        """recovery() for several lengths of every list from one pass over its rows.  prefixes: list
+        lengths, strictly ascending, each 1 to 64, at most 8.  Returns int64 [nq][P][2][65][B + 1]: [q][i] is what recovery()
+        returns for list q cut to its first min(prefixes[i], len(list)) results, so its table is recovery_rows(hist[q][i],
+        min(prefixes[i], len(list)), ...); results at or beyond the last prefix are not used."""
+        res, n_res, k, grid, pre, hist = self._recovery_arguments(result_sample_ids, coverage_grid, prefixes)
+        t_ptr, t_line = self._truth_csr(truth_lines, len(n_res))
+        check(lib().morna_jstore_recovery_sweep(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(t_ptr), ptr(t_line), ptr(grid),
+                                                len(grid), ptr(pre), len(pre), ptr(hist)))
+        return hist.astype(np.int64)
+
+    def recovery_sweep_by_sample(self, result_sample_ids, truth_sample_ids, coverage_grid, prefixes, truth_min_coverage=1):
+        """recovery_sweep() with the truth of recovery_by_sample(): the store's own row of truth_sample_ids[q]."""
+        res, n_res, k, grid, pre, hist = self._recovery_arguments(result_sample_ids, coverage_grid, prefixes)
+        truth = self._truth_ids(truth_sample_ids, len(n_res))
+        check(lib().morna_jstore_recovery_sweep_by_sample(self._p, ptr(res), ptr(n_res), len(n_res), k, ptr(truth),
+                                                          _clamp62(truth_min_coverage), ptr(grid), len(grid), ptr(pre), len(pre),
+                                                          ptr(hist)))
+        return hist.astype(np.int64)
+
     def recovery_stats(self):
-        """Of the last recovery / recovery_by_sample: kernel ms (HIP events), algorithmic bytes (8 per entry of the result
-        and truth rows named, 4 per line of a truth given as lines) and workgroups launched."""
+        """Of the last recovery / recovery_by_sample or sweep: kernel ms (HIP events), algorithmic bytes (8 per entry of the
+        result and truth rows named, 4 per line of a truth given as lines; a sweep reads the rows up to its last prefix,
+        once) and workgroups launched."""
         s = np.zeros(3, np.float64)
         check(lib().morna_jstore_recovery_stats(self._p, ptr(s)))
         return {"kernel_ms": float(s[0]), "bytes": int(s[1]), "workgroups": int(s[2])}

@@ -287,6 +287,17 @@ class MornaSearch(object):
             return store.recovery_by_sample(lists, self.result_sample_ids(truth), coverage_grid, truth_min_coverage)
         return store.recovery(lists, truth, coverage_grid)
 
+    def junction_recovery_sweep(self, result_lists, truth, coverage_grid, prefixes, truth_min_coverage=1):
+        """junction_recovery for several lengths of every list from one pass (junctions.JunctionStore.recovery_sweep;
+        DESIGN.md 8, N7): prefixes ascending, 1 to 64, at most 8.  Returns int64 [len(result_lists)][len(prefixes)][2][65]
+        [len(coverage_grid) + 1]; [q][i] is the histogram of list q cut to its first prefixes[i] results."""
+        store = self.junction_store()
+        lists = [self.result_sample_ids(lst) for lst in result_lists]
+        truth = list(truth)
+        if all(np.ndim(t) == 0 for t in truth):
+            return store.recovery_sweep_by_sample(lists, self.result_sample_ids(truth), coverage_grid, prefixes, truth_min_coverage)
+        return store.recovery_sweep(lists, truth, coverage_grid, prefixes)
+
     # ---- unhashed TF-IDF search (DESIGN.md 8, N5): no counterpart the reference finished -------------------------
     def unhashed_store(self):
         """The junction store with the line weights of <basename>.jw.mor set, and those weights; on first use."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The recovery tables (`morna recovery`, DESIGN.md 8 N6) at the data set of scripts/bench_junctions.py
+"""The recovery tables (`morna recovery`, DESIGN.md 8 N6 and N7) at the data set of scripts/bench_junctions.py
 (synth.synthetic_intropolis, 50k samples, 70k junctions, ~1e8 entries).  Reports, as one JSON line and as the text kept
 in profiles/recovery.txt:
 
@@ -11,11 +11,16 @@ in profiles/recovery.txt:
                of every retained list with the truth.  For N = 1 and 64 all 64 cells are run; for N = 1000 ONE cell
                (.05,5) is run and its time multiplied by 64 -- the line says so
   equal        that the cells both routes computed hold the same retrieved and true-positive counts
+  sweep_N      morna_jstore_recovery_sweep_by_sample (N7) for N lists of 64 consecutive sample ids and the prefixes 5, 10, 20,
+               40, 64: kernel time, row bytes and rate of the one call, from recovery_stats; and the route there was before,
+               five recovery_by_sample calls on the lists cut to those lengths: the sum of their kernel times and of their
+               bytes.  Both best of three repeats after a warm-up, with the spread (largest minus smallest) of the three;
+               and whether the five slices equal the five histograms
 
 A result list is 20 consecutive sample ids (one latent cluster of the data set, what a neighbour search returns), the
 query the sample just before them: leave one out, its own junctions the truth.
 
-    python3 scripts/bench_recovery.py [--samples 50000] [--junctions 70000] [--json out.json] [--text out.txt]
+    python3 scripts/bench_recovery.py [--samples 50000] [--junctions 70000] [--sweep 5,10,20,40,64] [--json out.json] [--text out.txt]
 """
 import argparse
 import json
@@ -31,7 +36,7 @@ sys.path.insert(0, ROOT)
 
 from morna_amd._lib import check, lib, ptr  # noqa: E402
 from morna_amd.index import ParsedLines  # noqa: E402
-from morna_amd.junctions import JunctionStore, parse_recovery_grid, recovery_rows  # noqa: E402
+from morna_amd.junctions import JunctionStore, parse_recovery_grid, parse_results_sweep, recovery_rows  # noqa: E402
 from morna_amd.synth import synthetic_intropolis  # noqa: E402
 
 
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--samples", type=int, default=50_000)
     ap.add_argument("--junctions", type=int, default=70_000)
     ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--sweep", default="5,10,20,40,64", help="the prefixes of the sweep case")
     ap.add_argument("--json", default=None)
     ap.add_argument("--text", default=None)
     args = ap.parse_args()
@@ -98,6 +104,38 @@ def main():
             at = cells.index(cell)
             equal = equal and counts == [(tables[q][at]["retrieved"], tables[q][at]["true_positive"]) for q in range(n)]
         res["retain_%d" % n] = dict(cells_run=len(run), ms_run=retain_ms, ms_all_cells=retain_ms * len(cells) / len(run))
+    prefixes = parse_results_sweep(args.sweep)
+    deep = [ids[min(s, len(ids) - prefixes[-1] - 1) + 1:][:prefixes[-1]].tolist() for s in starts.tolist()]
+    for n in (1, 64, 1000):
+        batch, who = deep[:n], queries[:n]
+        cuts = [[lst[:p] for lst in batch] for p in prefixes]
+
+        def one_call():
+            hist = store.recovery_sweep_by_sample(batch, who, coverages, prefixes)
+            return hist, store.recovery_stats()
+
+        def five_calls():
+            hists, ms, nbytes = [], 0.0, 0
+            for cut in cuts:
+                hists.append(store.recovery_by_sample(cut, who, coverages))
+                stats = store.recovery_stats()
+                ms, nbytes = ms + stats["kernel_ms"], nbytes + stats["bytes"]
+            return hists, ms, nbytes
+        one_call()                                             # warm-up
+        five_calls()
+        sweep_ms, five_ms = [], []
+        for _ in range(3):
+            hist, stats = one_call()
+            sweep_ms.append(stats["kernel_ms"])
+            hists, ms, five_bytes = five_calls()
+            five_ms.append(ms)
+        same = all(np.array_equal(hist[:, i], hists[i]) for i in range(len(prefixes)))
+        equal = equal and same
+        res["sweep_%d" % n] = dict(prefixes=prefixes, kernel_ms=min(sweep_ms), kernel_ms_spread=max(sweep_ms) - min(sweep_ms),
+                                   row_bytes=stats["bytes"], row_GBps=stats["bytes"] / min(sweep_ms) / 1e6,
+                                   workgroups=stats["workgroups"], five_calls_kernel_ms=min(five_ms),
+                                   five_calls_kernel_ms_spread=max(five_ms) - min(five_ms), five_calls_row_bytes=five_bytes,
+                                   five_calls_row_GBps=five_bytes / min(five_ms) / 1e6, equal=bool(same))
     res["equal"] = bool(equal)
     line = json.dumps(res, sort_keys=True)
     print(line)
@@ -113,7 +151,19 @@ def main():
                     (n, args.k, r["kernel_ms"], r["row_bytes"] / 1e6, r["row_GBps"], r["workgroups"], len(cells), r["wall_ms"],
                      r["hist_bytes"] / 1e6, o["ms_all_cells"],
                      "" if o["cells_run"] == len(cells) else " (%d cell timed, %.0f ms, times %d)" % (o["cells_run"], o["ms_run"], len(cells))))
-    text.append("answers of the two routes equal in every cell both computed: %s" % res["equal"])
+    for n in (1, 64, 1000):
+        r = res["sweep_%d" % n]
+        text.append("sweep    %4d x -r %s   one call: kernel %.3f ms (spread %.3f) for %.1f MB of rows: %.1f GB/s, %d workgroups; "
+                    "%d recovery calls on the cut lists: kernel %.3f ms in all (spread %.3f) for %.1f MB: %.1f GB/s; slices equal: %s" %
+                    (n, ",".join(str(p) for p in r["prefixes"]), r["kernel_ms"], r["kernel_ms_spread"], r["row_bytes"] / 1e6,
+                     r["row_GBps"], r["workgroups"], len(r["prefixes"]), r["five_calls_kernel_ms"], r["five_calls_kernel_ms_spread"],
+                     r["five_calls_row_bytes"] / 1e6, r["five_calls_row_GBps"], r["equal"]))
+    r = res["sweep_1000"]
+    spread = max(r["kernel_ms_spread"], r["five_calls_kernel_ms_spread"])
+    text.append("sweep at 1000 lists: %.3f ms against %.3f ms of the separate calls, spread of the three repeats %.3f ms: the sweep "
+                "is %s" % (r["kernel_ms"], r["five_calls_kernel_ms"], spread,
+                           "no slower" if r["kernel_ms"] <= r["five_calls_kernel_ms"] + spread else "SLOWER"))
+    text.append("equal: %s (the retain route's cells and the sweep's slices)" % res["equal"])
     print("\n".join(text))
     if args.text:
         with open(args.text, "w") as fh:
