@@ -302,6 +302,35 @@ int morna_jstore_recovery_sweep_by_sample(morna_jstore *s, const int64_t *result
                                           const int32_t *prefixes, int32_t n_prefixes, int32_t *hist_out);
 int morna_jstore_recovery_stats(const morna_jstore *s, double *stats);
 
+/*
+ * ---- pooled samples: the summed coverages of groups of store rows -----------------------------------
+ * Stand-in for create_supersample.py of the reference's tests/ (the "supersample" its README searches with: all samples of a
+ * tissue summed junction by junction), on the store's rows in place of the intropolis text.  n_groups groups; group g holds
+ * the EXTERNAL sample ids members[g_ptr[g] .. g_ptr[g + 1]), distinct inside the group, any number of them up to the store's
+ * sample count (the kernel takes them in rounds of 64); an id may be in several groups.  For group g the result is every
+ * line at least one member holds, ascending, with holders (int32: the members whose row holds it) and sum (int64: their
+ * summed coverage).  A line is there because it is held, not because its sum is non-zero.  Integer throughout: the same
+ * numbers whatever the batch, the order of the members and the order in which workgroups finish.
+ *   morna_jstore_pool        checks first, all before any GPU work and with the store left usable: a null pointer, or g_ptr
+ *                            that does not start at 0 or descends: MORNA_E_INVALID; an id the store lacks: MORNA_E_RANGE
+ *                            naming it; an id twice in one group: MORNA_E_INVALID naming the group and the id.  n_groups = 0
+ *                            returns an empty result without GPU work (members and g_ptr may then be NULL).  Two passes
+ *                            over the member rows: count per tile of 4096 lines, then write.
+ *   morna_jpooled_counts     count_out[n_groups]: the held lines of every group
+ *   morna_jpooled_group      borrowed views of group g, valid until morna_jpooled_free: lines / sums / holders [count].
+ *                            Any may be NULL.  MORNA_E_RANGE for a g outside [0, n_groups).
+ *   morna_jstore_pool_stats  of the last call, stats[4]: kernel ms (HIP events, both passes), bytes read (8 per entry of every
+ *                            member row, per pass), bytes written (16 per held line), workgroups per pass (n_groups x tiles).
+ *                            All 0 after a call with n_groups = 0 or one that failed its checks.  The timers of retain,
+ *                            nearest and recovery stay their own.
+ */
+typedef struct morna_jpooled morna_jpooled;
+int morna_jstore_pool(morna_jstore *s, const int64_t *members, const int64_t *g_ptr, int64_t n_groups, morna_jpooled **out);
+int morna_jpooled_counts(const morna_jpooled *r, int64_t *count_out /* [n_groups] */);
+int morna_jpooled_group(const morna_jpooled *r, int64_t g, const int32_t **lines, const int64_t **sums, const int32_t **holders);
+int morna_jpooled_free(morna_jpooled *r);
+int morna_jstore_pool_stats(const morna_jstore *s, double *stats);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

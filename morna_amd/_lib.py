@@ -80,6 +80,11 @@ SIGNATURES = {
     "morna_jstore_recovery_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _p, _i32, _p]),
     "morna_jstore_recovery_sweep_by_sample": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _p, _i32, _p, _i32, _p]),
     "morna_jstore_recovery_stats": (C.c_int, [_p, _p]),
+    "morna_jstore_pool": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_p)]),
+    "morna_jpooled_counts": (C.c_int, [_p, _p]),
+    "morna_jpooled_group": (C.c_int, [_p, _i64] + [C.POINTER(_p)] * 3),
+    "morna_jpooled_free": (C.c_int, [_p]),
+    "morna_jstore_pool_stats": (C.c_int, [_p, _p]),
     "morna_merge_topk": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_vector_packed": (C.c_int, [_p, _p, _i64, _i32, _i32, _i64, _p]),
     "morna_merge_topk_packed": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),

@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -26,6 +26,14 @@ intropolis file (--intropolis shallow --truth deep).  One pass on the GPU per ru
 -r deep (for -e the lists of separate -r runs; for the approximate search, whose default search_k grows with -r, the
 prefixes of the deeper and so better search).
 
+`supersample` is create_supersample.py of the reference's tests/ on the junction store: for a list of sample ids
+(--sample-ids, that script's file) or several labelled lists (--groups), the coverage of every junction summed over the
+listed samples, written as that script writes it -- "chrom start end sum" for every line of --junction-file, the same
+bytes -- from one pass on the GPU over the listed samples' rows and one pass over the file.  `search --supersamples
+groups.tsv` searches with those sums directly, one block per group, without the files in between.  Differences from that
+script, deliberate: its progress prints are not reproduced, and a sample id the store lacks is an error naming it (the
+script sums nothing for it, silently).
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -42,6 +50,8 @@ here do the latter.
     python -m morna_amd.cli recovery -x idx --query-ids 12,34,56 -r 20 --grid 0,.05,.5:1,5,50
     python -m morna_amd.cli recovery -x idx --query-ids 12,34,56 -r 64 --results-sweep 5,10,20,40,64 --summary-only
     python -m morna_amd.cli recovery -x idx --intropolis shallow.tsv.gz --truth deep.tsv.gz --junction-file junctions.tsv.gz
+    python -m morna_amd.cli supersample -x idx --sample-ids pancreas.txt --junction-file junctions.tsv.gz -o pancreas.qry
+    python -m morna_amd.cli search -x idx --supersamples tissues.tsv --junction-file junctions.tsv.gz -e -d
 """
 import argparse
 import sys
@@ -92,6 +102,12 @@ def add_search_parameters(subparser):
     subparser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
                            help='comma-separated sample ids already in the index, searched together: one block per id, '
                                 '"# query <id>" and then what -q <id> prints')
+    subparser.add_argument('--supersamples', metavar='<file>', type=str, required=False, default=None,
+                           help='search with pooled samples: a groups file, "<label><TAB><id>,<id>,..." per line; every '
+                                'group\'s samples are summed junction by junction on the GPU (needs the store of `index '
+                                '--junction-store`) and the sums searched together: one block per group, "# query <label>" '
+                                'and then what --intropolis prints for a sample with those sums (`search` only; needs '
+                                '--junction-file)')
     subparser.add_argument('--unhashed', action='store_const', const=True, default=False,
                            help='rank by the TF-IDF cosine distance over the junctions themselves, one dimension per '
                                 'line of the indexed file, instead of the hashed features (needs the store and weights '
@@ -144,9 +160,9 @@ def build_parser():
                                    'flag a store left by an earlier index of the same basename is removed')
     add_search_parameters(search_parser)
     search_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None, dest='unhashed_junction_file',
-                               help='with --unhashed and a query that is not already in the index (a stream, --intropolis): '
-                                    'path to the (gzipped) intropolis file the index was made from, which names the '
-                                    'junction of every line')
+                               help='with --unhashed and a query that is not already in the index (a stream, --intropolis), '
+                                    'and with --supersamples: path to the (gzipped) intropolis file the index was made '
+                                    'from, which names the junction of every line')
     junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
                                                                'results for a second alignment pass')
     add_search_parameters(junctions_parser)                    # morna.py:1023
@@ -188,7 +204,36 @@ def build_parser():
                                  help='tabulate these result counts (at most 8, each at most -r) from the one search -r deep '
                                       'and one pass over its results: a block per count for every query, then a table over '
                                       'all queries per count')
+    super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
+                                                             'samples (create_supersample.py on the junction store)')
+    super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                              help='basename of an index built with --junction-store')
+    which = super_parser.add_mutually_exclusive_group(required=True)
+    which.add_argument('--sample-ids', metavar='<file>', type=str, default=None,
+                       help='one integer sample id per line (the --sampleids file of create_supersample.py): one output file')
+    which.add_argument('--groups', metavar='<file>', type=str, default=None,
+                       help='"<label><TAB><id>,<id>,..." per line: one output file per group, <out>.<label>')
+    super_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
+                              help='path to the (gzipped) intropolis file the index was made from')
+    super_parser.add_argument('-o', '--output', type=str, metavar='<file>', required=True,
+                              help='output file: "chrom start end sum" for every line of --junction-file')
+    super_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     return parser
+
+
+def _check_supersample_flags(parser, args):
+    """--supersamples: `search` only, with the file that names the lines and without another query."""
+    if args.supersamples is None:
+        return
+    if args.subparser_name != 'search':
+        parser.error("--supersamples cannot be used with %s" % args.subparser_name)
+    if args.unhashed_junction_file is None:
+        parser.error("--supersamples needs --junction-file, the intropolis file the index was made from")
+    for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+                     ("--intropolis", args.intropolis is not None),
+                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
+        if on:
+            parser.error("--supersamples cannot be used with %s" % flag)
 
 
 def _check_recovery_flags(parser, args):
@@ -270,6 +315,8 @@ def _check_junction_flags(parser, args):
 def main(argv=None, stdin=None, stdout=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.subparser_name in ('search', 'junctions', 'recovery'):
+        _check_supersample_flags(parser, args)
     if args.subparser_name in ('search', 'junctions'):
         _check_batch_flags(parser, args)
         _check_unhashed_flags(parser, args)
@@ -293,6 +340,8 @@ def main(argv=None, stdin=None, stdout=None):
                  native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank,
                  junction_store=args.junction_store)
         return 0
+    if args.subparser_name == 'supersample':
+        return _supersample(args, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -303,7 +352,7 @@ def main(argv=None, stdin=None, stdout=None):
     dist = None
     junctions = args.subparser_name == 'junctions'
     sharded = world > 1 and os.path.exists(args.basename + ".shards.mor")
-    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed):
+    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed or args.supersamples is not None):
         raise RuntimeError("batch search is not available with one process per shard (torchrun): "
                            "run it in one process, which loads every shard of the index")
     if args.subparser_name in ('junctions', 'recovery'):
@@ -332,6 +381,8 @@ def main(argv=None, stdin=None, stdout=None):
     else:
         searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
     try:
+        if args.supersamples is not None:
+            return _search_supersamples(args, searcher, stdout)
         if args.unhashed:
             return _search_unhashed(args, searcher, stdin, stdout)
         if junctions:
@@ -443,6 +494,60 @@ def _recovery(args, searcher, stdin, stdout):
         stdout.write("# all %d queries%s\n" % (len(labels), "" if p is None else "\tresults %d" % p))
         stdout.write(format_recovery_rows(sum_recovery_rows(tables[i])))
     return rc
+
+
+def _supersample(args, stdout):
+    """create_supersample.py for one id list or several: the sums on the GPU in one call, the files in one pass over
+    --junction-file."""
+    import os
+    from .junctions import STORE_SUFFIX, JunctionStore, parse_groups_file, parse_sample_ids_file, write_supersample_files
+    if args.sample_ids is not None:
+        groups = [("supersample", parse_sample_ids_file(args.sample_ids))]
+        paths = [args.output]
+    else:
+        groups = parse_groups_file(args.groups)
+        paths = [args.output + "." + label for label, _ in groups]
+    if not os.path.exists(args.basename + STORE_SUFFIX):
+        raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
+                      % (args.basename + STORE_SUFFIX))
+    store = JunctionStore.load(args.basename + STORE_SUFFIX, device=int(str(args.device).split(',')[0]))
+    pooled = store.pool([ids for _, ids in groups])
+    write_supersample_files(args.junction_file, zip(paths, pooled))
+    for (label, ids), r in zip(groups, pooled):
+        stdout.write("# group %s\tsamples %d\tjunctions %d\tcoverage %d\n"
+                     % (label, len(set(ids)), len(r), sum(r.sums.tolist())))
+    return 0
+
+
+def _search_supersamples(args, searcher, stdout):
+    """search --supersamples: every group pooled in one call and searched in one batch; a block per group, printed as
+    --intropolis prints a sample's."""
+    from .junctions import parse_groups_file
+    from .search import results_output
+    groups = parse_groups_file(args.supersamples)
+    if not groups:
+        return 0
+    labels = [label for label, _ in groups]
+    pooled = searcher.pool_samples([ids for _, ids in groups])
+    if args.unhashed:
+        terms = searcher.unhashed_terms_from_pooled(pooled, labels)
+        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata)
+    else:
+        batch = searcher.queries_from_pooled(pooled, labels, args.unhashed_junction_file)
+        if args.exact:
+            results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata)
+        else:
+            results = searcher.search_nn_batch(batch, args.results, args.search_k, include_distances=args.distances,
+                                               meta_db=args.metadata)
+    failed = False
+    for label, res in zip(labels, results):
+        stdout.write("# query %s\n" % label)
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+        else:
+            results_output(res, stdout)
+    return 1 if failed else 0
 
 
 def _search_unhashed(args, searcher, stdin, stdout):

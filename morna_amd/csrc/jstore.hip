@@ -40,6 +40,11 @@
 // Recovery sweep: the recovery tile for several lengths of every list at once.  The walk takes the ranks
 // in the buckets the lengths cut; at every boundary the tile's words and maxima are those of the shorter list, so it is
 // classified and added to that length's histogram before the walk goes on.  One read of the rows, one launch.
+//
+// Pool: the same walk with sums in place of bits.  A group of samples of any size is taken in rounds of 64
+// rows; every entry adds its coverage to the line's 64-bit sum and 1 to its holder count (LDS integer atomics: the sums do
+// not depend on the order).  Two passes as the filter's: count the held lines per tile, scan, write (line, sum, holders)
+// ascending.
 #include <unistd.h>
 
 #include <algorithm>
@@ -64,6 +69,14 @@ struct morna_jretained {
     std::vector<uint64_t> masks;       // found_in: bit r set = result r holds the line
     std::vector<int64_t> cov_ptr{0};   // [total + 1] extent of every retained line's coverages in `cov`
     std::vector<int32_t> cov;          // coverages, rank order inside a line
+};
+
+struct morna_jpooled {
+    int64_t ng = 0;
+    std::vector<int64_t> off{0};       // [ng + 1] first held line of every group in the flat arrays
+    std::vector<int32_t> lines;        // held line numbers, ascending inside a group
+    std::vector<int64_t> sums;         // the members' summed coverage of the line
+    std::vector<int32_t> holders;      // the members that hold it
 };
 
 namespace {
@@ -196,30 +209,47 @@ struct JTile {
     int32_t tile, m;
 };
 
-__device__ __forceinline__ JTile tile_of_block(int64_t n_lines, int32_t n_tiles, const int32_t *__restrict__ n_results, int32_t k)
+// the tile alone, of no list yet (m = 0)
+__device__ __forceinline__ JTile tile_of_block(int64_t n_lines, int32_t n_tiles)
 {
     JTile T;
     T.q = blockIdx.x / n_tiles;
     T.tile = (int32_t)(blockIdx.x % n_tiles);
     T.t0 = (int64_t)T.tile * JT_LINES;
     T.t1 = T.t0 + JT_LINES < n_lines ? T.t0 + JT_LINES : n_lines;
+    T.m = 0;
+    return T;
+}
+
+__device__ __forceinline__ JTile tile_of_block(int64_t n_lines, int32_t n_tiles, const int32_t *__restrict__ n_results, int32_t k)
+{
+    JTile T = tile_of_block(n_lines, n_tiles);
     const int32_t m = n_results[T.q];
     T.m = m < 0 ? 0 : (m > k ? k : m);
     return T;
 }
 
-// threads 0-63: s_lo[r], where the tile begins in result r's list; threads 64-127: s_hi[r], where it ends
+// threads 0-63: s_lo[r], where the tile begins in the list of row rows[T.q * k + r_first + r]; threads 64-127: s_hi[r], where
+// it ends; for r < n, at most 64 (a round of a longer list: the pool's)
 __device__ __forceinline__ void tile_ranges(const JTile &T, const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
-                                            const int32_t *__restrict__ rows, int32_t k, int64_t *s_lo, int64_t *s_hi)
+                                            const int32_t *__restrict__ rows, int32_t k, int64_t *s_lo, int64_t *s_hi, int64_t r_first,
+                                            int32_t n)
 {
     const int tid = threadIdx.x, r = tid & 63;
-    if (tid < 128 && r < T.m) {
-        const int32_t row = rows[T.q * k + r];
+    if (tid < 128 && r < n) {
+        const int32_t row = rows[T.q * k + r_first + r];
         const int64_t a = ptr[row], b = ptr[row + 1];
         const int64_t at = lower_bound_line(line, a, b, tid < 64 ? T.t0 : T.t1);
         if (tid < 64) s_lo[r] = at;
         else s_hi[r] = at;
     }
+}
+
+// every result of the list
+__device__ __forceinline__ void tile_ranges(const JTile &T, const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                            const int32_t *__restrict__ rows, int32_t k, int64_t *s_lo, int64_t *s_hi)
+{
+    tile_ranges(T, ptr, line, rows, k, s_lo, s_hi, 0, T.m);
 }
 
 // the walk: one wave per result r of the ranks [r_first, r_end), a workgroup-uniform range inside [0, T.m):
@@ -364,6 +394,87 @@ __global__ __launch_bounds__(256) void jstore_tile_scan_kernel(int64_t *__restri
     if (lane == 0) {
         totals[2 * q] = run0;
         totals[2 * q + 1] = run1;
+    }
+}
+
+// ---- pool: the summed coverages of a group of samples -----------------------------------------------------------------
+
+// One workgroup per (tile, group).  Group g holds the store rows rows[g_ptr[g] .. g_ptr[g + 1]), distinct, any number of them.
+// write == 0: tile_n[g][tile] = {lines at least one member holds, entries of the members in the tile}.  write != 0: tile_n
+// holds the exclusive prefix of those pairs over the group's tiles, g_off[g] the group's place in the flat outputs of n_out
+// lines.  The number of rounds follows from g_ptr alone, so every barrier is reached by every thread of a workgroup.
+// LDS: 32 KiB of sums, 16 KiB of holder counts, 1 KiB of extents, 2 KiB of scan arrays: 51 KiB.
+__global__ __launch_bounds__(JT_THREADS) void jstore_pool_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ line,
+                                                                 const int32_t *__restrict__ cov, int64_t n_lines, int32_t n_tiles,
+                                                                 const int32_t *__restrict__ rows, const int64_t *__restrict__ g_ptr,
+                                                                 int32_t write, int64_t *__restrict__ tile_n,
+                                                                 const int64_t *__restrict__ g_off, int64_t n_out,
+                                                                 int32_t *__restrict__ lines_out, int64_t *__restrict__ sums_out,
+                                                                 int32_t *__restrict__ holders_out)
+{
+    __shared__ unsigned long long s_sum[JT_LINES];   // two's complement: a negative coverage adds its 64-bit pattern
+    __shared__ int32_t s_cnt[JT_LINES];
+    __shared__ int64_t s_lo[64], s_hi[64];
+    __shared__ int32_t s_keep[JT_THREADS], s_ent[JT_THREADS];
+    const int tid = threadIdx.x;
+    const JTile T = tile_of_block(n_lines, n_tiles);
+    const int64_t g = T.q, t0 = T.t0, t1 = T.t1;
+    for (int i = tid; i < JT_LINES; i += JT_THREADS) {
+        s_sum[i] = 0;
+        s_cnt[i] = 0;
+    }
+    __syncthreads();
+    const int64_t m_first = g_ptr[g], m = g_ptr[g + 1] - m_first;
+    for (int64_t done = 0; done < m; done += 64) {   // rounds of 64 members
+        const int32_t n = (int32_t)(m - done < 64 ? m - done : 64);
+        tile_ranges(T, ptr, line, rows + m_first, 0, s_lo, s_hi, done, n);
+        __syncthreads();
+        walk_tile(T, line, s_lo, s_hi, 0, n, [&](int, int64_t i, int64_t l) {
+            atomicAdd(&s_sum[l], (unsigned long long)(long long)cov[i]);
+            atomicAdd(&s_cnt[l], 1);
+        });
+        __syncthreads();   // before the next round overwrites the extents; after the last, before the sums are read
+    }
+    // compaction: thread t owns lines [t * JT_PER, (t + 1) * JT_PER) of the tile
+    int32_t keep = 0, ent = 0;
+    uint32_t kept_bits = 0;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = tid * JT_PER + j;
+        const int32_t c = s_cnt[l];
+        if (t0 + l < t1 && c >= 1) {   // held: whatever its sum is
+            kept_bits |= 1u << j;
+            keep++;
+            ent += c;
+        }
+    }
+    s_keep[tid] = keep;
+    s_ent[tid] = ent;
+    __syncthreads();
+    for (int o = 1; o < JT_THREADS; o <<= 1) {   // inclusive scans over the threads
+        const int32_t a = tid >= o ? s_keep[tid - o] : 0, b = tid >= o ? s_ent[tid - o] : 0;
+        __syncthreads();
+        s_keep[tid] += a;
+        s_ent[tid] += b;
+        __syncthreads();
+    }
+    int64_t *mine = tile_n + 2 * ((int64_t)g * n_tiles + T.tile);
+    if (!write) {
+        if (tid == JT_THREADS - 1) {
+            mine[0] = s_keep[tid];
+            mine[1] = s_ent[tid];
+        }
+        return;
+    }
+    int64_t at = g_off[g] + mine[0] + s_keep[tid] - keep;
+    for (int j = 0; j < JT_PER; j++) {
+        const int l = tid * JT_PER + j;
+        if (!((kept_bits >> j) & 1u)) continue;
+        if (at >= 0 && at < n_out) {
+            lines_out[at] = (int32_t)(t0 + l);
+            sums_out[at] = (int64_t)s_sum[l];
+            holders_out[at] = s_cnt[l];
+        }
+        at++;
     }
 }
 
@@ -762,13 +873,13 @@ int resolve_lists(const morna_jstore *st, const char *who, const int64_t *result
     return MORNA_OK;
 }
 
-// the tiles of lines one query takes; nq of them must fit one launch
-int tile_count(const morna_jstore *st, const char *who, int64_t nq, int64_t *n_tiles)
+// the tiles of lines one query takes; nq of them must fit one launch (`lists`: what the caller's queries are)
+int tile_count(const morna_jstore *st, const char *who, int64_t nq, int64_t *n_tiles, const char *lists = "result lists")
 {
     *n_tiles = std::max<int64_t>(1, (st->n_lines + JT_LINES - 1) / JT_LINES);
     if (nq * *n_tiles > INT32_MAX) {
-        set_error("%s: %lld result lists over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
-                  "pass fewer lists per call", who, (long long)nq, (long long)*n_tiles);
+        set_error("%s: %lld %s over %lld tiles of lines are more than one launch holds (2^31 - 1 workgroups): "
+                  "pass fewer per call", who, (long long)nq, lists, (long long)*n_tiles);
         return MORNA_E_INVALID;
     }
     return MORNA_OK;
@@ -849,6 +960,126 @@ int retain_impl(morna_jstore *st, const int64_t *results, const int32_t *n_resul
     }
     st->ms[1] = (double)ms1 + (double)ms2;
     st->bytes[1] = 8 * list_entries;   // the k lists of every query, read once
+    return MORNA_OK;
+}
+
+// the groups of a pool as store rows, group-major; every refusal of morna_jstore_pool that needs the store
+int resolve_groups(const morna_jstore *st, const int64_t *members, const int64_t *g_ptr, int64_t ng, std::vector<int32_t> &rows,
+                   std::vector<int64_t> &entries)
+{
+    if (g_ptr[0] != 0) {
+        set_error("jstore_pool: the group offsets start at %lld, not at 0", (long long)g_ptr[0]);
+        return MORNA_E_INVALID;
+    }
+    for (int64_t g = 0; g < ng; g++)
+        if (g_ptr[g + 1] < g_ptr[g]) {
+            set_error("jstore_pool: the offsets of group %lld descend (%lld, %lld)", (long long)g, (long long)g_ptr[g],
+                      (long long)g_ptr[g + 1]);
+            return MORNA_E_INVALID;
+        }
+    if (g_ptr[ng] > 0 && !members) {
+        set_error("jstore_pool: null argument");
+        return MORNA_E_INVALID;
+    }
+    rows.assign((size_t)g_ptr[ng], 0);
+    entries.assign((size_t)ng, 0);
+    std::vector<int64_t> seen_in(st->ext_ids.size(), -1);   // the last group that named a row
+    for (int64_t g = 0; g < ng; g++)
+        for (int64_t i = g_ptr[g]; i < g_ptr[g + 1]; i++) {
+            auto it = st->row_of.find(members[i]);
+            if (it == st->row_of.end()) {
+                set_error("jstore_pool: sample id %lld (member %lld of group %lld) is not in the junction store", (long long)members[i],
+                          (long long)(i - g_ptr[g]), (long long)g);
+                return MORNA_E_RANGE;
+            }
+            if (seen_in[(size_t)it->second] == g) {
+                set_error("jstore_pool: group %lld names sample id %lld twice: the members of a group must be distinct", (long long)g,
+                          (long long)members[i]);
+                return MORNA_E_INVALID;
+            }
+            seen_in[(size_t)it->second] = g;
+            rows[(size_t)i] = it->second;
+            entries[(size_t)g] += st->ptr[(size_t)it->second + 1] - st->ptr[(size_t)it->second];
+        }
+    return MORNA_OK;
+}
+
+int pool_impl(morna_jstore *st, const int64_t *members, const int64_t *g_ptr, int64_t ng, morna_jpooled *R)
+{
+    st->pool_ms = 0;
+    st->pool_read = st->pool_written = st->pool_groups = 0;
+    R->ng = ng;
+    R->off.assign((size_t)ng + 1, 0);
+    if (ng == 0) return MORNA_OK;
+    std::vector<int32_t> rows;
+    std::vector<int64_t> entries;
+    int64_t n_tiles = 0, all_entries = 0;
+    MORNA_TRY(resolve_groups(st, members, g_ptr, ng, rows, entries));
+    MORNA_TRY(tile_count(st, "jstore_pool", ng, &n_tiles, "groups"));
+    MORNA_TRY(make_resident(st));
+    DevBuf<int32_t> d_rows, d_lines, d_holders;
+    DevBuf<int64_t> d_gptr, d_tile, d_totals, d_off, d_sums;
+    MORNA_TRY(d_rows.alloc(std::max<size_t>(rows.size(), 1)));
+    MORNA_TRY(d_gptr.alloc((size_t)ng + 1));
+    MORNA_TRY(d_tile.alloc((size_t)(2 * ng * n_tiles)));
+    MORNA_TRY(d_totals.alloc((size_t)(2 * ng)));
+    MORNA_TRY(d_off.alloc((size_t)ng));
+    if (!rows.empty()) HIP_TRY(hipMemcpy(d_rows.p, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_gptr.p, g_ptr, ((size_t)ng + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    EventPair ev1, ev2;
+    MORNA_TRY(ev1.create());
+    MORNA_TRY(ev2.create());
+    const dim3 grid((unsigned)(ng * n_tiles));
+    HIP_TRY(hipEventRecord(ev1.a, st->stream));
+    hipLaunchKernelGGL(jstore_pool_kernel, grid, dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p, st->d_cov.p, st->n_lines,
+                       (int32_t)n_tiles, d_rows.p, d_gptr.p, 0, d_tile.p, (const int64_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
+                       (int64_t *)nullptr, (int32_t *)nullptr);
+    hipLaunchKernelGGL(jstore_tile_scan_kernel, dim3((unsigned)((ng + 256 / WAVE - 1) / (256 / WAVE))), dim3(256), 0, st->stream, d_tile.p,
+                       (int32_t)n_tiles, ng, d_totals.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1.b, st->stream));
+    std::vector<int64_t> totals((size_t)(2 * ng));
+    HIP_TRY(hipMemcpyAsync(totals.data(), d_totals.p, totals.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    int64_t n_held = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        if (totals[(size_t)(2 * g + 1)] != entries[(size_t)g] || totals[(size_t)(2 * g)] < 0 || totals[(size_t)(2 * g)] > st->n_lines) {
+            set_error("jstore_pool: the tiles of group %lld hold %lld lines and %lld entries, its rows %lld entries over %lld lines: "
+                      "the store on the device is not the store on the host", (long long)g, (long long)totals[(size_t)(2 * g)],
+                      (long long)totals[(size_t)(2 * g + 1)], (long long)entries[(size_t)g], (long long)st->n_lines);
+            return MORNA_E_STATE;
+        }
+        R->off[(size_t)g] = n_held;
+        n_held += totals[(size_t)(2 * g)];
+        all_entries += entries[(size_t)g];
+    }
+    R->off[(size_t)ng] = n_held;
+    R->lines.assign((size_t)n_held, 0);
+    R->sums.assign((size_t)n_held, 0);
+    R->holders.assign((size_t)n_held, 0);
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(hipEventElapsedTime(&ms1, ev1.a, ev1.b));
+    if (n_held) {
+        MORNA_TRY(d_lines.alloc((size_t)n_held));
+        MORNA_TRY(d_sums.alloc((size_t)n_held));
+        MORNA_TRY(d_holders.alloc((size_t)n_held));
+        HIP_TRY(hipMemcpy(d_off.p, R->off.data(), (size_t)ng * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipEventRecord(ev2.a, st->stream));
+        hipLaunchKernelGGL(jstore_pool_kernel, grid, dim3(JT_THREADS), 0, st->stream, st->d_ptr.p, st->d_line.p, st->d_cov.p, st->n_lines,
+                           (int32_t)n_tiles, d_rows.p, d_gptr.p, 1, d_tile.p, (const int64_t *)d_off.p, n_held, d_lines.p, d_sums.p,
+                           d_holders.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev2.b, st->stream));
+        HIP_TRY(hipStreamSynchronize(st->stream));
+        HIP_TRY(hipEventElapsedTime(&ms2, ev2.a, ev2.b));
+        HIP_TRY(hipMemcpy(R->lines.data(), d_lines.p, (size_t)n_held * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->sums.data(), d_sums.p, (size_t)n_held * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->holders.data(), d_holders.p, (size_t)n_held * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    st->pool_ms = (double)ms1 + (double)ms2;
+    st->pool_read = 2 * 8 * all_entries;   // (line, coverage) of every member row, once per pass
+    st->pool_written = 16 * n_held;
+    st->pool_groups = ng * n_tiles;
     return MORNA_OK;
 }
 
@@ -1281,6 +1512,67 @@ int morna_jstore_recovery_stats(const morna_jstore *s, double *stats)
     stats[0] = s->rec_ms;
     stats[1] = (double)s->rec_bytes;
     stats[2] = (double)s->rec_groups;
+    return MORNA_OK;
+}
+
+int morna_jstore_pool(morna_jstore *s, const int64_t *members, const int64_t *g_ptr, int64_t n_groups, morna_jpooled **out)
+{
+    if (!s || !out || n_groups < 0 || (n_groups > 0 && !g_ptr)) {
+        set_error("jstore_pool: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    return guarded("jstore_pool", MORNA_E_INVALID, [&] {
+        std::unique_ptr<morna_jpooled> R(new morna_jpooled());
+        MORNA_TRY(pool_impl(s, members, g_ptr, n_groups, R.get()));
+        *out = R.release();
+        return MORNA_OK;
+    });
+}
+
+int morna_jpooled_counts(const morna_jpooled *r, int64_t *count_out)
+{
+    if (!r || (r->ng > 0 && !count_out)) {
+        set_error("jpooled_counts: null argument");
+        return MORNA_E_INVALID;
+    }
+    for (int64_t g = 0; g < r->ng; g++) count_out[g] = r->off[(size_t)g + 1] - r->off[(size_t)g];
+    return MORNA_OK;
+}
+
+int morna_jpooled_group(const morna_jpooled *r, int64_t g, const int32_t **lines, const int64_t **sums, const int32_t **holders)
+{
+    if (!r) {
+        set_error("jpooled_group: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (g < 0 || g >= r->ng) {
+        set_error("jpooled_group: group %lld out of range [0, %lld)", (long long)g, (long long)r->ng);
+        return MORNA_E_RANGE;
+    }
+    const size_t at = (size_t)r->off[(size_t)g];
+    if (lines) *lines = r->lines.data() + at;
+    if (sums) *sums = r->sums.data() + at;
+    if (holders) *holders = r->holders.data() + at;
+    return MORNA_OK;
+}
+
+int morna_jpooled_free(morna_jpooled *r)
+{
+    delete r;
+    return MORNA_OK;
+}
+
+int morna_jstore_pool_stats(const morna_jstore *s, double *stats)
+{
+    if (!s || !stats) {
+        set_error("jstore_pool_stats: null argument");
+        return MORNA_E_INVALID;
+    }
+    stats[0] = s->pool_ms;
+    stats[1] = (double)s->pool_read;
+    stats[2] = (double)s->pool_written;
+    stats[3] = (double)s->pool_groups;
     return MORNA_OK;
 }
 

@@ -28,6 +28,9 @@ struct morna_jstore {
     // of the last recovery: kernel ms, algorithmic bytes, workgroups launched
     double rec_ms = 0;
     int64_t rec_bytes = 0, rec_groups = 0;
+    // of the last pool: kernel ms, bytes read and written, workgroups per pass
+    double pool_ms = 0;
+    int64_t pool_read = 0, pool_written = 0, pool_groups = 0;
     std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
     ~morna_jstore()
     {

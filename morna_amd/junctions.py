@@ -9,9 +9,13 @@ writes the text.
     store = JunctionStore.build(ParsedLines(path, sample_count=n, sample_threshold=0))
     store.save(basename + ".junc.mor")
     kept = JunctionStore.load(basename + ".junc.mor").retain([[sample ids in rank order], ...], 0.05, 5)
+
+Pooled samples (create_supersample.py of the reference's tests/): `JunctionStore.pool` sums the rows of
+groups of samples on the GPU, `write_supersample_files` writes the "chrom start end sum" files of that script.
 """
 import ctypes as C
 import gzip
+import re
 from math import ceil, isfinite
 
 import numpy as np
@@ -149,6 +153,17 @@ class Retained(object):
     def coverages(self):
         p = self._cov_ptr
         return [self._cov[p[i]:p[i + 1]].tolist() for i in range(len(self.lines))]
+
+
+class Pooled(object):
+    """A group of samples summed (JunctionStore.pool): lines (the line numbers at least one member holds, ascending, int32),
+    sums (the members' summed coverage of each, int64) and holders (the members that hold it, int32)."""
+
+    def __init__(self, lines, sums, holders):
+        self.lines, self.sums, self.holders = lines, sums, holders
+
+    def __len__(self):
+        return len(self.lines)
 
 
 def view(pp, ctype, count):
@@ -370,6 +385,38 @@ class JunctionStore(object):
         s = np.zeros(3, np.float64)
         check(lib().morna_jstore_recovery_stats(self._p, ptr(s)))
         return {"kernel_ms": float(s[0]), "bytes": int(s[1]), "workgroups": int(s[2])}
+
+    # ---- pooled samples -------------------------------------------------------------------------------
+    def pool(self, groups):
+        """One Pooled per group of `groups` (external sample ids, any number per group): every line at least one sample of
+        the group holds, with the group's summed coverage and the number of its samples that hold it.  All groups in one
+        call on the GPU.  An id repeated inside a group counts once, the first time (the `sample in wanted_ids` of
+        create_supersample.py); IndexError for an id the store lacks."""
+        groups = [list(dict.fromkeys(int(s) for s in grp)) for grp in groups]
+        g_ptr = np.zeros(len(groups) + 1, np.int64)
+        np.cumsum([len(grp) for grp in groups], out=g_ptr[1:])
+        members = np.array([s for grp in groups for s in grp], np.int64)
+        r = C.c_void_p()
+        check(lib().morna_jstore_pool(self._p, ptr(members), ptr(g_ptr), len(groups), C.byref(r)))
+        try:
+            counts = np.zeros(len(groups), np.int64)
+            check(lib().morna_jpooled_counts(r, ptr(counts)))
+            out = []
+            for g in range(len(groups)):
+                p = [C.c_void_p() for _ in range(3)]
+                check(lib().morna_jpooled_group(r, g, *[C.byref(x) for x in p]))
+                n = int(counts[g])
+                out.append(Pooled(view(p[0], C.c_int32, n), view(p[1], C.c_int64, n), view(p[2], C.c_int32, n)))
+            return out
+        finally:
+            lib().morna_jpooled_free(r)
+
+    def pool_stats(self):
+        """Of the last pool: kernel ms (HIP events, both passes), bytes read (8 per entry of every member row, per pass),
+        bytes written (16 per held line) and workgroups per pass."""
+        s = np.zeros(4, np.float64)
+        check(lib().morna_jstore_pool_stats(self._p, ptr(s)))
+        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "workgroups": int(s[3])}
 
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
@@ -614,6 +661,92 @@ def write_splice_files(junction_file, jobs):
                     break
         if at < len(line):
             raise ValueError("%s ends before line %d: it is not the file that was indexed" % (junction_file, line[at]))
+    finally:
+        for fh in handles:
+            fh.close()
+
+
+# ---- pooled samples: the files of create_supersample.py ----------------------------------------------
+_LABEL = re.compile(r"[A-Za-z0-9._-]+\Z")
+
+
+def parse_sample_ids_file(path):
+    """The --sampleids file of create_supersample.py: one integer sample id per line; blank lines are ignored.  ValueError
+    naming the line otherwise."""
+    ids = []
+    with open(path) as fh:
+        for n, text in enumerate(fh, 1):
+            if not text.strip():
+                continue
+            try:
+                ids.append(int(text))
+            except ValueError:
+                raise ValueError("line %d of %s is not an integer sample id (got %r)" % (n, path, text.strip()))
+    return ids
+
+
+def parse_groups_file(path):
+    """A groups file, "<label><TAB><id>,<id>,..." per line, as [(label, [ids])] in file order.  Labels match
+    [A-Za-z0-9._-]+ and are distinct; a label alone, or followed by a tab and nothing, is an empty group; blank lines are
+    ignored.  ValueError naming the line otherwise."""
+    groups, seen = [], set()
+    with open(path) as fh:
+        for n, text in enumerate(fh, 1):
+            text = text.rstrip("\r\n")
+            if not text.strip():
+                continue
+            parts = text.split("\t")
+            if len(parts) > 2:
+                raise ValueError("line %d of %s has %d tab-separated fields: a group is <label><TAB><id>,<id>,..."
+                                 % (n, path, len(parts)))
+            label = parts[0]
+            if not _LABEL.match(label):
+                raise ValueError("line %d of %s: the label %r is not made of letters, digits, '.', '_' and '-'" % (n, path, label))
+            if label in seen:
+                raise ValueError("line %d of %s: the label %r names a second group" % (n, path, label))
+            seen.add(label)
+            ids = []
+            if len(parts) == 2 and parts[1].strip():
+                for t in parts[1].split(","):
+                    try:
+                        ids.append(int(t))
+                    except ValueError:
+                        raise ValueError("line %d of %s: %r is not an integer sample id" % (n, path, t.strip()))
+            groups.append((label, ids))
+    return groups
+
+
+def write_supersample_files(junction_file, jobs):
+    """The output loop of create_supersample.py for several groups in one pass over `junction_file`.
+
+    jobs: (path, Pooled) per group.  For EVERY line of the file: its first three whitespace-separated fields joined by
+    tabs, a tab, the group's summed coverage of the line -- 0 where none of its samples holds it -- and a newline.
+    ValueError when the file ends before a pooled line or a line has fewer than three fields."""
+    jobs = list(jobs)
+    handles = [open(path, "w") for path, _ in jobs]
+    try:
+        if not jobs:
+            return
+        last = max([int(r.lines[-1]) for _, r in jobs if len(r)] + [-1])
+        at = [0] * len(jobs)
+        lines = [np.asarray(r.lines).tolist() for _, r in jobs]
+        sums = [np.asarray(r.sums).tolist() for _, r in jobs]
+        i = -1
+        with _open_text(junction_file) as names:
+            for i, text in enumerate(names):
+                pieces = text.split()
+                if len(pieces) < 3:
+                    raise ValueError("line %d of %s has %d fields, a junction has at least 3" % (i, junction_file, len(pieces)))
+                head = "\t".join(pieces[:3]) + "\t"
+                for q, fh in enumerate(handles):
+                    a = at[q]
+                    if a < len(lines[q]) and lines[q][a] == i:
+                        fh.write(head + str(sums[q][a]) + "\n")
+                        at[q] = a + 1
+                    else:
+                        fh.write(head + "0\n")
+        if i < last:
+            raise ValueError("%s ends before line %d: it is not the file that was indexed" % (junction_file, last))
     finally:
         for fh in handles:
             fh.close()

@@ -151,20 +151,27 @@ class MornaSearch(object):
             self._vocab_arrays = pack_vocab(self.sample_frequencies)
         return self._vocab_arrays
 
+    def _check_batch_possible(self):
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if self.sample_count <= 0:
+            raise ValueError("the index's sample count must be positive (got %d)" % self.sample_count)
+
     def queries_from_intropolis(self, path):
         """Every sample of the (gzipped) intropolis file `path` as a query: for sample s, the vector update_query over
         the lines that list s (key "chrom start end" in the index's frequency table, coverage of s) and finalize_query
         would make -- built on the GPU.  Coordinates are compared as written (intropolis writes canonical decimals,
         what the raw stream's int() gives).  Returns a QueryBatch."""
         from .index import ParsedLines
-        from .shards import DistShards, LocalShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        if self.sample_count <= 0:
-            raise ValueError("the index's sample count must be positive (got %d)" % self.sample_count)
+        self._check_batch_possible()
         parsed = ParsedLines(path, sample_count=self.sample_count, sample_threshold=0)
-        terms = parsed.query_terms(self._vocab(), self.sample_count)
+        return self._batch_from_terms(parsed.query_terms(self._vocab(), self.sample_count))
+
+    def _batch_from_terms(self, terms):
+        """The QueryBatch of the query terms of a parse (ParsedLines.query_terms): its rows built on the GPU."""
+        from .shards import LocalShards
         ext_ids = terms.arrays()["ext_ids"].tolist()
         self._batch_generation = getattr(self, "_batch_generation", 0) + 1
         if isinstance(self.annoy_index, LocalShards):
@@ -297,6 +304,71 @@ class MornaSearch(object):
         if all(np.ndim(t) == 0 for t in truth):
             return store.recovery_sweep_by_sample(lists, self.result_sample_ids(truth), coverage_grid, prefixes, truth_min_coverage)
         return store.recovery_sweep(lists, truth, coverage_grid, prefixes)
+
+    # ---- pooled samples as queries (create_supersample.py of the reference's tests/) -------------------
+    def pool_samples(self, groups):
+        """One junctions.Pooled per group of external sample ids (junctions.JunctionStore.pool): the summed coverage of
+        every junction line a sample of the group holds, all groups in one call on the GPU."""
+        return self.junction_store().pool(groups)
+
+    @staticmethod
+    def _check_pooled_coverages(pooled, labels):
+        """The query paths take int32 coverages: ValueError naming the group and the line for a sum that does not fit."""
+        for label, r in zip(labels, pooled):
+            sums = np.asarray(r.sums, np.int64)
+            bad = np.nonzero((sums > 2**31 - 1) | (sums < -2**31))[0]
+            if len(bad):
+                raise ValueError("group %s: the summed coverage of line %d is %d, which does not fit 32 bits (2^31 - 1 at the "
+                                 "most): a query takes int32 coverages; `morna supersample` writes such a group's file"
+                                 % (label, int(r.lines[bad[0]]), int(sums[bad[0]])))
+
+    def queries_from_pooled(self, pooled, labels, junction_file):
+        """The groups of pool_samples as queries of the hashed searches: for group g the vector update_query over the
+        lines it holds (key "chrom start end" of that line of `junction_file`, the (gzipped) intropolis file the index
+        was made from; the group's summed coverage) and finalize_query would make -- bit for bit the row of an intropolis
+        file that lists the groups as samples with those sums.  Returns a QueryBatch whose query q is group q; `labels`
+        name the groups in messages.  ValueError when the file's line count is not the store's, or a sum does not fit
+        int32."""
+        from .index import ParsedLines
+        self._check_batch_possible()
+        pooled, labels = list(pooled), list(labels)
+        self._check_pooled_coverages(pooled, labels)
+        n_lines = self.junction_store().n_lines
+        parsed = ParsedLines(junction_file, sample_count=1, sample_threshold=0)
+        if parsed.lines_read != n_lines:
+            raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
+                             % (junction_file, parsed.lines_read, n_lines))
+        a = parsed.arrays()
+        # group-major (line, sum) lists -> line-major rows of (group, sum); a group's lines ascend, so file order is kept
+        line = np.concatenate([np.asarray(r.lines, np.int64) for r in pooled] + [np.zeros(0, np.int64)])
+        group = np.concatenate([np.full(len(r), g, np.int64) for g, r in enumerate(pooled)] + [np.zeros(0, np.int64)])
+        cov = np.concatenate([np.asarray(r.sums, np.int64) for r in pooled] + [np.zeros(0, np.int64)])
+        order = np.lexsort((group, line))
+        line, group, cov = line[order], group[order], cov[order]
+        held, per_line = np.unique(line, return_counts=True)
+        row_ptr = np.zeros(len(held) + 1, np.int64)
+        np.cumsum(per_line, out=row_ptr[1:])
+        key_off, key_bytes = np.asarray(a["key_off"]), np.asarray(a["key_bytes"])
+        key_len = key_off[held + 1] - key_off[held]
+        out_off = np.zeros(len(held) + 1, np.int64)
+        np.cumsum(key_len, out=out_off[1:])
+        take = np.repeat(key_off[held] - out_off[:-1], key_len) + np.arange(int(out_off[-1]), dtype=np.int64)
+        prep = dict(key_bytes=key_bytes[take], key_off=out_off, row_ptr=row_ptr, ids=group, cov=cov,
+                    idf=np.zeros(len(held), np.float64), ext_ids=np.arange(len(pooled), dtype=np.int64))
+        lines = ParsedLines.from_arrays(prep, self.sample_count)
+        return self._batch_from_terms(lines.query_terms(self._vocab(), self.sample_count))
+
+    def unhashed_terms_from_pooled(self, pooled, labels):
+        """The groups of pool_samples as the term lists of unhashed_search_nn_batch: (lines ascending, coverages) per
+        group, the lines of weight 0 left out as junctions.query_terms leaves them out."""
+        pooled, labels = list(pooled), list(labels)
+        self._check_pooled_coverages(pooled, labels)
+        _, w = self.unhashed_store()
+        terms = []
+        for r in pooled:
+            keep = np.asarray(w)[np.asarray(r.lines, np.int64)] != 0.0
+            terms.append((np.asarray(r.lines, np.int32)[keep], np.asarray(r.sums, np.int64)[keep].astype(np.int32)))
+        return terms
 
     # ---- unhashed TF-IDF search (DESIGN.md 8, N5): no counterpart the reference finished -------------------------
     def unhashed_store(self):
