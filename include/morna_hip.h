@@ -331,6 +331,43 @@ int morna_jpooled_group(const morna_jpooled *r, int64_t g, const int32_t **lines
 int morna_jpooled_free(morna_jpooled *r);
 int morna_jstore_pool_stats(const morna_jstore *s, double *stats);
 
+/*
+ * ---- depth thinning: store rows with every read kept with probability keep / 2^32 -----------------------
+ * A shallower sequencing of a sample is, to first order, its store row with every read kept independently with one
+ * probability: binomial thinning of the coverages (the reference's tests/downsample_fastqs.py keeps a fixed number of reads of
+ * the fastq instead, and needs the aligner after it).  nq jobs; job q is (ext[q], keep[q]): an EXTERNAL sample id of the store,
+ * which may be named by many jobs, and a threshold in [0, 2^32].  Integers only, uint32 arithmetic modulo 2^32:
+ *   fmix32(h)   h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16   (MurmurHash3's finalizer)
+ *   s = fmix32(seed);  u = fmix32(lo32(ext) ^ fmix32(hi32(ext) ^ s)), ext as the two's-complement uint64 of the id
+ *   v = fmix32(u ^ uint32(line))                        the key of an entry
+ *   h_i = fmix32(v + 0x9e3779b9 * (i + 1)), 0 <= i < c  draw i of an entry of coverage c
+ *   c' = #{ i < c : h_i < keep }                        compared in 64 bits: keep = 2^32 keeps every read, 0 none
+ * The result of job q is every line of the row with c' >= 1, ascending, with c' (int32).  It depends on (seed, ext, line, c,
+ * keep) alone: not on the row's place in the store, the batch, or the order workgroups finish in.  The thresholds nest:
+ * keep_a <= keep_b gives c'(a) <= c'(b) entry by entry, as a subsample of a subsample.
+ *   morna_jstore_thin        checks first, all before any GPU work and with the store left usable: a null pointer or a
+ *                            keep above 2^32: MORNA_E_INVALID; an id the store lacks: MORNA_E_RANGE naming it; a named row
+ *                            with a coverage outside [0, 2^24]: MORNA_E_INVALID naming the sample and the line (one entry's
+ *                            draws are then at most 2^18 iterations of a wave).  nq = 0 returns an empty result without GPU
+ *                            work (ext and keep may then be NULL).  Two passes over chunks of 2048 entries of the named rows
+ *                            and a scan of the chunks' survivor counts between them.
+ *   morna_jthinned_counts    count_out[nq]: the surviving lines of every job
+ *   morna_jthinned_job       borrowed views of job q, valid until morna_jthinned_free: lines / cov [count].  Either may be
+ *                            NULL.  MORNA_E_RANGE for a q outside [0, nq).
+ *   morna_jstore_thin_stats  of the last call, stats[5]: kernel ms (HIP events: both passes and the scan); bytes read (16 per
+ *                            entry of every named row: line and coverage in pass 1, line and scratch in pass 2); bytes written
+ *                            (4 per entry, the scratch, and 8 per surviving line); draws made (the summed coverage of the
+ *                            named rows); workgroups per pass (the chunks).  All 0 after a call with nq = 0 or one that failed
+ *                            its checks.  The timers of retain, nearest, recovery and pool stay their own.
+ */
+typedef struct morna_jthinned morna_jthinned;
+int morna_jstore_thin(morna_jstore *s, const int64_t *ext /* [nq] */, const uint64_t *keep /* [nq] */, int64_t nq, uint32_t seed,
+                      morna_jthinned **out);
+int morna_jthinned_counts(const morna_jthinned *r, int64_t *count_out /* [nq] */);
+int morna_jthinned_job(const morna_jthinned *r, int64_t q, const int32_t **lines, const int32_t **cov);
+int morna_jthinned_free(morna_jthinned *r);
+int morna_jstore_thin_stats(const morna_jstore *s, double *stats);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

@@ -85,6 +85,11 @@ SIGNATURES = {
     "morna_jpooled_group": (C.c_int, [_p, _i64] + [C.POINTER(_p)] * 3),
     "morna_jpooled_free": (C.c_int, [_p]),
     "morna_jstore_pool_stats": (C.c_int, [_p, _p]),
+    "morna_jstore_thin": (C.c_int, [_p, _p, _p, _i64, _u32, C.POINTER(_p)]),
+    "morna_jthinned_counts": (C.c_int, [_p, _p]),
+    "morna_jthinned_job": (C.c_int, [_p, _i64] + [C.POINTER(_p)] * 2),
+    "morna_jthinned_free": (C.c_int, [_p]),
+    "morna_jstore_thin_stats": (C.c_int, [_p, _p]),
     "morna_merge_topk": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_vector_packed": (C.c_int, [_p, _p, _i64, _i32, _i32, _i64, _p]),
     "morna_merge_topk_packed": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),

@@ -34,6 +34,15 @@ groups.tsv` searches with those sums directly, one block per group, without the 
 script, deliberate: its progress prints are not reproduced, and a sample id the store lacks is an error naming it (the
 script sums nothing for it, silently).
 
+`search --downsample 0.5,0.1` and `recovery --downsample 0.5,0.1` (with -q or --query-ids) ask their question at the depth it
+is about: each query is the sample's row of the junction store with every read of every junction kept independently with
+that probability -- binomial thinning of the coverages, made on the GPU by a counter-based integer hash, so the same
+--downsample-seed keeps the same reads, and a lower rate keeps a subsample of a higher one's.  It stands in for
+downsample_fastqs.py of the reference's tests/ and the aligner run after it, which keep a fixed number of reads of the fastq;
+here the number kept is binomial and reads that span no junction do not exist.  `recovery --downsample` is that script's
+downsample -> align -> recover experiment in one call: the truth is the sample's full row, or with --lost-only the junctions
+of it the thinned row no longer holds.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -52,6 +61,8 @@ here do the latter.
     python -m morna_amd.cli recovery -x idx --intropolis shallow.tsv.gz --truth deep.tsv.gz --junction-file junctions.tsv.gz
     python -m morna_amd.cli supersample -x idx --sample-ids pancreas.txt --junction-file junctions.tsv.gz -o pancreas.qry
     python -m morna_amd.cli search -x idx --supersamples tissues.tsv --junction-file junctions.tsv.gz -e -d
+    python -m morna_amd.cli search -x idx --query-ids 12,34 --downsample 0.5,0.1,0.01 --junction-file junctions.tsv.gz -d
+    python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --downsample 0.5,0.1,0.01 --junction-file junctions.tsv.gz --lost-only
 """
 import argparse
 import sys
@@ -112,6 +123,15 @@ def add_search_parameters(subparser):
                            help='rank by the TF-IDF cosine distance over the junctions themselves, one dimension per '
                                 'line of the indexed file, instead of the hashed features (needs the store and weights '
                                 'of `index --junction-store`; `search` only)')
+    subparser.add_argument('--downsample', metavar='<p1,p2,...>', type=str, required=False, default=None,
+                           help='with -q or --query-ids: search with each sample\'s row of the junction store at these '
+                                'fractions of its depth (1 to 16 rates in [0, 1]): every read of every junction is kept '
+                                'independently with that probability, on the GPU and reproducibly (needs the store of `index '
+                                '--junction-store`, and --junction-file unless --unhashed); one block per id and rate, '
+                                '"# query <id><TAB>keep <rate>" and then what --intropolis prints for a sample with the '
+                                'thinned coverages (`search` and `recovery`)')
+    subparser.add_argument('--downsample-seed', metavar='<int>', type=int, required=False, default=8675309, action=_StoreGiven,
+                           help='the seed of --downsample (default 8675309); the same seed gives the same reads')
     subparser.add_argument('--device', type=str, default='0',
                            help='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
                                 'dealt to these devices in turn')
@@ -161,7 +181,7 @@ def build_parser():
     add_search_parameters(search_parser)
     search_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None, dest='unhashed_junction_file',
                                help='with --unhashed and a query that is not already in the index (a stream, --intropolis), '
-                                    'and with --supersamples: path to the (gzipped) intropolis file the index was made '
+                                    'with --supersamples, and with --downsample unless --unhashed: path to the (gzipped) intropolis file the index was made '
                                     'from, which names the junction of every line')
     junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
                                                                'results for a second alignment pass')
@@ -196,7 +216,7 @@ def build_parser():
                                  help='with --intropolis: the (gzipped) intropolis file that holds the true junctions of the '
                                       'same sample ids (the samples sequenced deeply)')
     recovery_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None,
-                                 help='with --truth: path to the (gzipped) intropolis file the index was made from, which '
+                                 help='with --truth and with --downsample: path to the (gzipped) intropolis file the index was made from, which '
                                       'names the junction of every line')
     recovery_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
                                  help='print only the table over all queries')
@@ -204,6 +224,11 @@ def build_parser():
                                  help='tabulate these result counts (at most 8, each at most -r) from the one search -r deep '
                                       'and one pass over its results: a block per count for every query, then a table over '
                                       'all queries per count')
+    recovery_parser.add_argument('--lost-only', action='store_const', const=True, default=False,
+                                 help='with --downsample: the truth of a query is only the junctions of its full row (at '
+                                      '--truth-coverage) that its thinned row does not hold, those the shallow run lost. '
+                                      'Precision is then against the lost junctions only, so a result that gives back a '
+                                      'junction the query kept counts as a false positive: recall is the number of interest')
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
     super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
@@ -219,6 +244,35 @@ def build_parser():
                               help='output file: "chrom start end sum" for every line of --junction-file')
     super_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     return parser
+
+
+def _check_downsample_flags(parser, args):
+    """--downsample: `search` and `recovery`, by item only, with the file that names the lines unless --unhashed; --lost-only
+    and --downsample-seed only with it.  Leaves the rates in args.downsample_parts."""
+    args.downsample_parts = None
+    if args.downsample is None:
+        for flag, on in (("--lost-only", getattr(args, "lost_only", False)),
+                         ("--downsample-seed", getattr(args, "downsample_seed_given", False))):
+            if on:
+                parser.error("%s cannot be used without --downsample" % flag)
+        return
+    if args.subparser_name == 'junctions':
+        parser.error("--downsample cannot be used with junctions")
+    for flag, on in (("--intropolis", args.intropolis is not None), ("--supersamples", args.supersamples is not None),
+                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist),
+                     ("--results-sweep", getattr(args, "results_sweep", None) is not None)):
+        if on:
+            parser.error("--downsample cannot be used with %s" % flag)
+    if args.query_id is None and args.query_ids is None:
+        parser.error("--downsample thins samples of the index: it needs -q or --query-ids, not a query from a stream")
+    junction_file = args.junction_file if args.subparser_name == 'recovery' else args.unhashed_junction_file
+    if junction_file is None and not args.unhashed:
+        parser.error("--downsample needs --junction-file, the intropolis file the index was made from (unless --unhashed)")
+    from .junctions import parse_downsample
+    try:
+        args.downsample_parts = parse_downsample(args.downsample)
+    except ValueError as e:
+        parser.error("--downsample takes 1 to 16 distinct comma-separated rates in [0, 1], such as 0.5,0.1,0.01 (%s)" % e)
 
 
 def _check_supersample_flags(parser, args):
@@ -316,6 +370,7 @@ def main(argv=None, stdin=None, stdout=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.subparser_name in ('search', 'junctions', 'recovery'):
+        _check_downsample_flags(parser, args)
         _check_supersample_flags(parser, args)
     if args.subparser_name in ('search', 'junctions'):
         _check_batch_flags(parser, args)
@@ -352,7 +407,8 @@ def main(argv=None, stdin=None, stdout=None):
     dist = None
     junctions = args.subparser_name == 'junctions'
     sharded = world > 1 and os.path.exists(args.basename + ".shards.mor")
-    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed or args.supersamples is not None):
+    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed or args.supersamples is not None
+                    or args.downsample is not None):
         raise RuntimeError("batch search is not available with one process per shard (torchrun): "
                            "run it in one process, which loads every shard of the index")
     if args.subparser_name in ('junctions', 'recovery'):
@@ -360,6 +416,8 @@ def main(argv=None, stdin=None, stdout=None):
         if args.results > MAX_RESULTS:
             raise ValueError("-r %d: junctions takes at most %d results (found_in is one 64-bit word per junction)"
                              % (args.results, MAX_RESULTS))
+    if args.subparser_name in ('junctions', 'recovery') or args.downsample is not None:
+        from .junctions import STORE_SUFFIX
         if not os.path.exists(args.basename + STORE_SUFFIX):
             raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
                           % (args.basename + STORE_SUFFIX))
@@ -383,6 +441,8 @@ def main(argv=None, stdin=None, stdout=None):
     try:
         if args.supersamples is not None:
             return _search_supersamples(args, searcher, stdout)
+        if args.downsample is not None and args.subparser_name == 'search':
+            return _search_downsample(args, searcher, stdout)
         if args.unhashed:
             return _search_unhashed(args, searcher, stdin, stdout)
         if junctions:
@@ -444,6 +504,8 @@ def _recovery(args, searcher, stdin, stdout):
     import io
     import sys
     from .junctions import format_recovery_rows, intropolis_truth, key_lines, recovery_rows, sum_recovery_rows
+    if args.downsample is not None:
+        return _recovery_downsample(args, searcher, stdout)
     frequencies, coverages = args.grid_parts
     wanted = args.results
     collected = []
@@ -494,6 +556,91 @@ def _recovery(args, searcher, stdin, stdout):
         stdout.write("# all %d queries%s\n" % (len(labels), "" if p is None else "\tresults %d" % p))
         stdout.write(format_recovery_rows(sum_recovery_rows(tables[i])))
     return rc
+
+
+def _downsample_search(args, searcher, n_results, junction_file):
+    """--downsample: every (query id, rate) a job, all jobs thinned in one call and searched in one batch.  Returns (jobs:
+    (sample id, rate as typed) in the order (id given, rate typed), their junctions.Thinned, their results, an Exception
+    instance where the reference's search would raise)."""
+    ids = args.query_ids if args.query_ids is not None else [args.query_id]
+    for query_id in ids:
+        if query_id not in searcher.internal_id_map:
+            raise ValueError("Querying sample id " + str(query_id)
+                             + " is not possible because no internal id is mapped to that "
+                             + "sample id. Likely no sample with that id was included "
+                             + "in the index.")
+    typed, keep = args.downsample_parts
+    jobs = [(query_id, t) for query_id in ids for t in typed]
+    thinned = searcher.thin_samples([query_id for query_id, _ in jobs], keep * len(ids), args.downsample_seed)
+    for (query_id, rate), row in zip(jobs, thinned):
+        if len(row) == 0:
+            sys.stderr.write("query %s at keep %s keeps no read: it is searched as a sample without junctions\n" % (query_id, rate))
+    if args.unhashed:
+        results = searcher.unhashed_search_nn_batch(searcher.unhashed_terms_from_thinned(thinned), n_results,
+                                                    include_distances=args.distances, meta_db=args.metadata)
+    else:
+        batch = searcher.queries_from_thinned(thinned, junction_file)
+        if args.exact:
+            results = searcher.exact_search_nn_batch(batch, n_results, include_distances=args.distances, meta_db=args.metadata)
+        else:
+            results = searcher.search_nn_batch(batch, n_results, args.search_k, include_distances=args.distances,
+                                               meta_db=args.metadata)
+    return jobs, thinned, results
+
+
+def _search_downsample(args, searcher, stdout):
+    """search --downsample: a block per (query id, rate), printed as --intropolis prints a sample's."""
+    from .search import results_output
+    jobs, _, results = _downsample_search(args, searcher, args.results, args.unhashed_junction_file)
+    failed = False
+    for (query_id, rate), res in zip(jobs, results):
+        stdout.write("# query %d\tkeep %s\n" % (query_id, rate))
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+        else:
+            results_output(res, stdout)
+    return 1 if failed else 0
+
+
+def _recovery_downsample(args, searcher, stdout):
+    """recovery --downsample: the reference's downsample -> align -> recover experiment on the store.  Every (query id, rate)
+    is searched with the thinned row, leave one out; the truth is the query's full row at --truth-coverage, or with
+    --lost-only the lines of it the thinned row does not hold.  A job no search answers (no read kept, under -e) is tabulated
+    with no results, named on stderr, and makes the return code 1, as `search --downsample` returns 1 for it."""
+    import sys
+    from .junctions import format_recovery_rows, lost_lines, recovery_rows, sum_recovery_rows
+    frequencies, coverages = args.grid_parts
+    wanted = args.results
+    jobs, thinned, results = _downsample_search(args, searcher, wanted + 1, args.junction_file)
+    typed = args.downsample_parts[0]
+    store = searcher.junction_store()
+    lists, truth, failed = [], [], False
+    for (query_id, rate), row, res in zip(jobs, thinned, results):
+        own = searcher.internal_id_map[query_id]
+        if isinstance(res, Exception):
+            sys.stderr.write("query %s at keep %s was not searched (%s): its table has no results\n" % (query_id, rate, res))
+            failed = True
+        found = [] if isinstance(res, Exception) else list(res[0])
+        lists.append([i for i in found if i != own][:wanted])
+        if args.lost_only:
+            line, cov = store.sample(query_id)
+            truth.append(lost_lines(line, cov, row.lines, args.truth_coverage))
+        else:
+            truth.append(own)
+    hist = searcher.junction_recovery(lists, truth, coverages, args.truth_coverage) if lists else []
+    tables = {rate: [] for rate in typed}
+    for q, (query_id, rate) in enumerate(jobs):
+        rows = recovery_rows(hist[q], len(lists[q]), frequencies, coverages)
+        tables[rate].append(rows)
+        if not args.summary_only:
+            stdout.write("# query %s\tkeep %s\tresults %d\ttrue %d\n"
+                         % (query_id, rate, len(lists[q]), rows[0]["true_positive"] + rows[0]["false_negative"]))
+            stdout.write(format_recovery_rows(rows))
+    for rate in typed:
+        stdout.write("# all %d queries\tkeep %s\n" % (len(tables[rate]), rate))
+        stdout.write(format_recovery_rows(sum_recovery_rows(tables[rate])))
+    return 1 if failed else 0
 
 
 def _supersample(args, stdout):

@@ -45,6 +45,13 @@
 // rows; every entry adds its coverage to the line's 64-bit sum and 1 to its holder count (LDS integer atomics: the sums do
 // not depend on the order).  Two passes as the filter's: count the held lines per tile, scan, write (line, sum, holders)
 // ascending.
+//
+// Thin: a store row at a fraction of its depth.  Every read of every entry is kept when an integer hash
+// of (seed, sample id, line, read number) falls below the job's threshold, so the answer is a function of those alone.  A
+// job's row is one contiguous run, so this does not use the tile walk: the host cuts the named rows into chunks of
+// JH_CHUNK entries, one workgroup each.  Pass 1 counts the kept reads of every entry into a scratch array (a lane makes
+// the draws of a light entry, the wave those of a heavy one) and the survivors of the chunk; jstore_ptr_kernel scans the
+// chunk counts; pass 2 writes (line, kept reads) of the survivors, ascending.  No atomics, no floating point.
 #include <unistd.h>
 
 #include <algorithm>
@@ -77,6 +84,13 @@ struct morna_jpooled {
     std::vector<int32_t> lines;        // held line numbers, ascending inside a group
     std::vector<int64_t> sums;         // the members' summed coverage of the line
     std::vector<int32_t> holders;      // the members that hold it
+};
+
+struct morna_jthinned {
+    int64_t nq = 0;
+    std::vector<int64_t> off{0};       // [nq + 1] first surviving line of every job in the flat arrays
+    std::vector<int32_t> lines;        // surviving line numbers, ascending inside a job
+    std::vector<int32_t> cov;          // their thinned coverages, 1 at the least
 };
 
 namespace {
@@ -475,6 +489,159 @@ __global__ __launch_bounds__(JT_THREADS) void jstore_pool_kernel(const int64_t *
             holders_out[at] = s_cnt[l];
         }
         at++;
+    }
+}
+
+// ---- thin: the rows of a batch of jobs with every read kept with probability keep / 2^32 ----------------------------------
+
+#define JH_THREADS 256
+#define JH_PER 8                         // entries per thread
+#define JH_CHUNK (JH_THREADS * JH_PER)   // entries of a chunk: one workgroup's
+#define JH_WAVES (JH_THREADS / WAVE)
+#define JH_LANE_MAX 32                   // a lane makes the draws of an entry covered at most this often; the wave those of the others
+#define JH_MAX_COV (1 << 24)             // the domain: one entry is at most 2^18 iterations of the wave's loop
+#define JH_GOLDEN 0x9e3779b9u
+
+// entries [first, first + n) of the store belong to job `job`; their thinned coverages sit at scratch[scratch ...]
+struct JHChunk {
+    int64_t first, scratch;
+    int32_t job, n;
+};
+
+// MurmurHash3's finalizer
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h)
+{
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// what a job's hashing needs: u of (seed, sample id), and the threshold as 32 bits and "keeps everything" (keep = 2^32)
+struct JHJob {
+    uint32_t u, a;
+    bool all;
+};
+
+__device__ __forceinline__ JHJob thin_job(const JHChunk &ch, const int64_t *__restrict__ j_ext, const unsigned long long *__restrict__ j_keep,
+                                          uint32_t s)
+{
+    const unsigned long long ext = (unsigned long long)j_ext[ch.job], keep = j_keep[ch.job];
+    JHJob J;
+    J.u = fmix32((uint32_t)ext ^ fmix32((uint32_t)(ext >> 32) ^ s));
+    J.a = (uint32_t)keep;
+    J.all = (keep >> 32) != 0;
+    return J;
+}
+
+// the draw whose hash input is x = v + JH_GOLDEN * (i + 1): kept?
+__device__ __forceinline__ uint32_t thin_kept(const JHJob &J, uint32_t x)
+{
+    return (J.all || fmix32(x) < J.a) ? 1u : 0u;
+}
+
+// Pass 1.  One workgroup per chunk; thread t takes entries t, t + JH_THREADS, ... of it (coalesced).  scratch[ch.scratch + e] =
+// the kept reads of entry e; chunk_n[chunk] = the entries that keep at least one.  s = fmix32(seed).  Every loop bound that
+// a cross-lane operation sits in is wave-uniform; the one barrier is reached by all.
+__global__ __launch_bounds__(JH_THREADS) void jstore_thin_count_kernel(const int32_t *__restrict__ line, const int32_t *__restrict__ cov,
+                                                                       const JHChunk *__restrict__ chunks, const int64_t *__restrict__ j_ext,
+                                                                       const unsigned long long *__restrict__ j_keep, uint32_t s,
+                                                                       int32_t *__restrict__ scratch, int64_t *__restrict__ chunk_n)
+{
+    __shared__ int32_t s_wave[JH_WAVES];
+    const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
+    const JHChunk ch = chunks[blockIdx.x];
+    const JHJob J = thin_job(ch, j_ext, j_keep, s);
+    int32_t survivors = 0;
+    for (int j = 0; j < JH_PER; j++) {
+        const int e = j * JH_THREADS + tid;
+        const bool in = e < ch.n;
+        uint32_t c = 0, v = 0;
+        if (in) {
+            c = (uint32_t)cov[ch.first + e];
+            v = fmix32(J.u ^ (uint32_t)line[ch.first + e]);
+            if (c > JH_MAX_COV) c = 0;   // (the host has refused such a row: this only bounds the loops below)
+        }
+        uint32_t k = 0;
+        if (c <= JH_LANE_MAX) {
+            uint32_t x = v;
+            for (uint32_t i = 0; i < c; i++) {
+                x += JH_GOLDEN;
+                k += thin_kept(J, x);
+            }
+        }
+        unsigned long long heavy = __ballot(c > JH_LANE_MAX);
+        while (heavy) {   // one heavy entry at a time, its draws dealt over the lanes
+            const int src = __ffsll((long long)heavy) - 1;
+            heavy &= heavy - 1;
+            const uint32_t cc = (uint32_t)__shfl((int)c, src, WAVE), cv = (uint32_t)__shfl((int)v, src, WAVE);
+            uint32_t part = 0, x = cv + JH_GOLDEN * (uint32_t)(lane + 1);
+            for (uint32_t base = 0; base < cc; base += WAVE) {   // draw i = base + lane
+                if (base + (uint32_t)lane < cc) part += thin_kept(J, x);
+                x += JH_GOLDEN * (uint32_t)WAVE;
+            }
+#pragma unroll
+            for (int off = WAVE / 2; off; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, WAVE);
+            if (lane == src) k = part;
+        }
+        if (in) {
+            scratch[ch.scratch + e] = (int32_t)k;
+            survivors += k ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int off = WAVE / 2; off; off >>= 1) survivors += __shfl_xor(survivors, off, WAVE);
+    if (lane == 0) s_wave[wave] = survivors;
+    __syncthreads();
+    if (tid == 0) {
+        int64_t n = 0;
+        for (int w = 0; w < JH_WAVES; w++) n += s_wave[w];
+        chunk_n[blockIdx.x] = n;
+    }
+}
+
+// Pass 2.  chunk_off: the exclusive scan of chunk_n, which is the chunk's place in the flat outputs of n_out lines (a job's
+// chunks are consecutive and jobs follow each other, so a job's lines are contiguous and ascend).  Entry e = j * JH_THREADS
+// + t: the survivors before it are those of the slots (j', wave') before (j, wave) and of the lower lanes of its own ballot.
+__global__ __launch_bounds__(JH_THREADS) void jstore_thin_write_kernel(const int32_t *__restrict__ line, const JHChunk *__restrict__ chunks,
+                                                                       const int32_t *__restrict__ scratch,
+                                                                       const int64_t *__restrict__ chunk_off, int64_t n_out,
+                                                                       int32_t *__restrict__ lines_out, int32_t *__restrict__ cov_out)
+{
+    __shared__ int32_t s_slot[JH_PER * JH_WAVES];
+    const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
+    const JHChunk ch = chunks[blockIdx.x];
+    int32_t k[JH_PER];
+    unsigned long long below[JH_PER];
+#pragma unroll
+    for (int j = 0; j < JH_PER; j++) {
+        const int e = j * JH_THREADS + tid;
+        k[j] = e < ch.n ? scratch[ch.scratch + e] : 0;
+        const unsigned long long m = __ballot(k[j] >= 1);
+        below[j] = m & ((1ull << lane) - 1ull);
+        if (lane == 0) s_slot[j * JH_WAVES + wave] = __popcll(m);
+    }
+    __syncthreads();
+    if (tid == 0) {   // 32 counts -> their exclusive prefix
+        int32_t run = 0;
+        for (int t = 0; t < JH_PER * JH_WAVES; t++) {
+            const int32_t c = s_slot[t];
+            s_slot[t] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    const int64_t base = chunk_off[blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < JH_PER; j++) {
+        if (k[j] < 1) continue;
+        const int64_t at = base + s_slot[j * JH_WAVES + wave] + __popcll(below[j]);
+        if (at >= 0 && at < n_out) {
+            lines_out[at] = line[ch.first + j * JH_THREADS + tid];
+            cov_out[at] = k[j];
+        }
     }
 }
 
@@ -1083,6 +1250,130 @@ int pool_impl(morna_jstore *st, const int64_t *members, const int64_t *g_ptr, in
     return MORNA_OK;
 }
 
+// The rows of the jobs of a thin, every refusal of morna_jstore_thin that needs the store, and the chunks: a job's are
+// consecutive, jobs in order.  first_chunk[q]: job q's first chunk (n_chunks for the jobs after the last entry).
+int resolve_thin_jobs(const morna_jstore *st, const int64_t *ext, const uint64_t *keep, int64_t nq, std::vector<JHChunk> &chunks,
+                      std::vector<int64_t> &first_chunk, int64_t &entries, int64_t &draws)
+{
+    std::vector<char> checked(st->ext_ids.size(), 0);
+    std::vector<int64_t> row_draws(st->ext_ids.size(), 0);
+    chunks.clear();
+    first_chunk.assign((size_t)nq + 1, 0);
+    entries = draws = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        if (keep[q] > ((uint64_t)1 << 32)) {
+            set_error("jstore_thin: job %lld keeps a read when its hash is below %llu: a threshold is at most 2^32", (long long)q,
+                      (unsigned long long)keep[q]);
+            return MORNA_E_INVALID;
+        }
+        auto it = st->row_of.find(ext[q]);
+        if (it == st->row_of.end()) {
+            set_error("jstore_thin: sample id %lld (job %lld) is not in the junction store", (long long)ext[q], (long long)q);
+            return MORNA_E_RANGE;
+        }
+        const size_t row = (size_t)it->second;
+        const int64_t a = st->ptr[row], b = st->ptr[row + 1];
+        if (!checked[row]) {
+            int64_t sum = 0;
+            for (int64_t i = a; i < b; i++) {
+                const int32_t c = st->cov[(size_t)i];
+                if (c < 0 || c > JH_MAX_COV) {
+                    set_error("jstore_thin: sample id %lld holds line %d with coverage %d: a thinned row's coverages lie in [0, 2^24]",
+                              (long long)ext[q], st->line[(size_t)i], c);
+                    return MORNA_E_INVALID;
+                }
+                sum += c;
+            }
+            checked[row] = 1;
+            row_draws[row] = sum;
+        }
+        first_chunk[(size_t)q] = (int64_t)chunks.size();
+        for (int64_t at = a; at < b; at += JH_CHUNK)
+            chunks.push_back(JHChunk{at, entries + (at - a), (int32_t)q, (int32_t)std::min<int64_t>(JH_CHUNK, b - at)});
+        entries += b - a;
+        draws += row_draws[row];
+    }
+    first_chunk[(size_t)nq] = (int64_t)chunks.size();
+    if ((int64_t)chunks.size() > INT32_MAX || nq > INT32_MAX) {
+        set_error("jstore_thin: %lld jobs in %lld chunks of %d entries are more than one launch holds (2^31 - 1 workgroups): "
+                  "pass fewer per call", (long long)nq, (long long)chunks.size(), JH_CHUNK);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+int thin_impl(morna_jstore *st, const int64_t *ext, const uint64_t *keep, int64_t nq, uint32_t seed, morna_jthinned *R)
+{
+    st->thin_ms = 0;
+    st->thin_read = st->thin_written = st->thin_draws = st->thin_groups = 0;
+    R->nq = nq;
+    R->off.assign((size_t)nq + 1, 0);
+    if (nq == 0) return MORNA_OK;
+    std::vector<JHChunk> chunks;
+    std::vector<int64_t> first_chunk;
+    int64_t entries = 0, draws = 0;
+    MORNA_TRY(resolve_thin_jobs(st, ext, keep, nq, chunks, first_chunk, entries, draws));
+    const int64_t n_chunks = (int64_t)chunks.size();
+    if (n_chunks == 0) return MORNA_OK;   // every named row is empty
+    MORNA_TRY(make_resident(st));
+    DevBuf<JHChunk> d_chunks;
+    DevBuf<int64_t> d_ext, d_chunk_n, d_chunk_off;
+    DevBuf<unsigned long long> d_keep;
+    DevBuf<int32_t> d_scratch, d_lines, d_cov;
+    MORNA_TRY(d_chunks.alloc((size_t)n_chunks));
+    MORNA_TRY(d_ext.alloc((size_t)nq));
+    MORNA_TRY(d_keep.alloc((size_t)nq));
+    MORNA_TRY(d_chunk_n.alloc((size_t)n_chunks));
+    MORNA_TRY(d_chunk_off.alloc((size_t)n_chunks + 1));
+    MORNA_TRY(d_scratch.alloc((size_t)entries));
+    HIP_TRY(hipMemcpy(d_chunks.p, chunks.data(), (size_t)n_chunks * sizeof(JHChunk), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ext.p, ext, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_keep.p, keep, (size_t)nq * sizeof(uint64_t), hipMemcpyHostToDevice));
+    EventPair ev1, ev2;
+    MORNA_TRY(ev1.create());
+    MORNA_TRY(ev2.create());
+    const dim3 grid((unsigned)n_chunks);
+    HIP_TRY(hipEventRecord(ev1.a, st->stream));
+    hipLaunchKernelGGL(jstore_thin_count_kernel, grid, dim3(JH_THREADS), 0, st->stream, st->d_line.p, st->d_cov.p, d_chunks.p, d_ext.p,
+                       d_keep.p, fmix32(seed), d_scratch.p, d_chunk_n.p);
+    hipLaunchKernelGGL(jstore_ptr_kernel, dim3(1), dim3(1024), 0, st->stream, d_chunk_n.p, (int32_t)n_chunks, d_chunk_off.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1.b, st->stream));
+    std::vector<int64_t> chunk_off((size_t)n_chunks + 1);
+    HIP_TRY(hipMemcpyAsync(chunk_off.data(), d_chunk_off.p, chunk_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    const int64_t n_kept = chunk_off[(size_t)n_chunks];
+    if (n_kept < 0 || n_kept > entries) {
+        set_error("jstore_thin: the chunks keep %lld lines of %lld entries: the store on the device is not the store on the host",
+                  (long long)n_kept, (long long)entries);
+        return MORNA_E_STATE;
+    }
+    for (int64_t q = 0; q <= nq; q++) R->off[(size_t)q] = chunk_off[(size_t)first_chunk[(size_t)q]];
+    R->lines.assign((size_t)n_kept, 0);
+    R->cov.assign((size_t)n_kept, 0);
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(hipEventElapsedTime(&ms1, ev1.a, ev1.b));
+    MORNA_TRY(d_lines.alloc((size_t)n_kept));   // (pass 2 runs for no survivor too: the statistics are then one formula)
+    MORNA_TRY(d_cov.alloc((size_t)n_kept));
+    HIP_TRY(hipEventRecord(ev2.a, st->stream));
+    hipLaunchKernelGGL(jstore_thin_write_kernel, grid, dim3(JH_THREADS), 0, st->stream, st->d_line.p, d_chunks.p, d_scratch.p, d_chunk_off.p,
+                       n_kept, d_lines.p, d_cov.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev2.b, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    HIP_TRY(hipEventElapsedTime(&ms2, ev2.a, ev2.b));
+    if (n_kept) {
+        HIP_TRY(hipMemcpy(R->lines.data(), d_lines.p, (size_t)n_kept * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(R->cov.data(), d_cov.p, (size_t)n_kept * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    st->thin_ms = (double)ms1 + (double)ms2;
+    st->thin_read = 16 * entries;                               // pass 1: (line, coverage); pass 2: (line, scratch)
+    st->thin_written = 4 * entries + 8 * n_kept;                // the scratch; (line, thinned coverage) of every survivor
+    st->thin_draws = draws;
+    st->thin_groups = n_chunks;
+    return MORNA_OK;
+}
+
 // truth_ext != NULL: truth by sample; otherwise the CSR (t_ptr, t_line).  pre != NULL: the sweep, one histogram per prefix
 // of every list (hist_out[nq][pre->n][...]) from the first pre->p[pre->n - 1] rows of each
 int recovery_impl(morna_jstore *st, const int64_t *results, const int32_t *n_results, int64_t nq, int32_t k, const int64_t *t_ptr,
@@ -1573,6 +1864,71 @@ int morna_jstore_pool_stats(const morna_jstore *s, double *stats)
     stats[1] = (double)s->pool_read;
     stats[2] = (double)s->pool_written;
     stats[3] = (double)s->pool_groups;
+    return MORNA_OK;
+}
+
+int morna_jstore_thin(morna_jstore *s, const int64_t *ext, const uint64_t *keep, int64_t nq, uint32_t seed, morna_jthinned **out)
+{
+    if (s) {   // a refused call leaves no statistics of an earlier one
+        s->thin_ms = 0;
+        s->thin_read = s->thin_written = s->thin_draws = s->thin_groups = 0;
+    }
+    if (!s || !out || nq < 0 || (nq > 0 && (!ext || !keep))) {
+        set_error("jstore_thin: null argument");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    return guarded("jstore_thin", MORNA_E_INVALID, [&] {
+        std::unique_ptr<morna_jthinned> R(new morna_jthinned());
+        MORNA_TRY(thin_impl(s, ext, keep, nq, seed, R.get()));
+        *out = R.release();
+        return MORNA_OK;
+    });
+}
+
+int morna_jthinned_counts(const morna_jthinned *r, int64_t *count_out)
+{
+    if (!r || (r->nq > 0 && !count_out)) {
+        set_error("jthinned_counts: null argument");
+        return MORNA_E_INVALID;
+    }
+    for (int64_t q = 0; q < r->nq; q++) count_out[q] = r->off[(size_t)q + 1] - r->off[(size_t)q];
+    return MORNA_OK;
+}
+
+int morna_jthinned_job(const morna_jthinned *r, int64_t q, const int32_t **lines, const int32_t **cov)
+{
+    if (!r) {
+        set_error("jthinned_job: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (q < 0 || q >= r->nq) {
+        set_error("jthinned_job: job %lld out of range [0, %lld)", (long long)q, (long long)r->nq);
+        return MORNA_E_RANGE;
+    }
+    const size_t at = (size_t)r->off[(size_t)q];
+    if (lines) *lines = r->lines.data() + at;
+    if (cov) *cov = r->cov.data() + at;
+    return MORNA_OK;
+}
+
+int morna_jthinned_free(morna_jthinned *r)
+{
+    delete r;
+    return MORNA_OK;
+}
+
+int morna_jstore_thin_stats(const morna_jstore *s, double *stats)
+{
+    if (!s || !stats) {
+        set_error("jstore_thin_stats: null argument");
+        return MORNA_E_INVALID;
+    }
+    stats[0] = s->thin_ms;
+    stats[1] = (double)s->thin_read;
+    stats[2] = (double)s->thin_written;
+    stats[3] = (double)s->thin_draws;
+    stats[4] = (double)s->thin_groups;
     return MORNA_OK;
 }
 

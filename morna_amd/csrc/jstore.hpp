@@ -31,6 +31,9 @@ struct morna_jstore {
     // of the last pool: kernel ms, bytes read and written, workgroups per pass
     double pool_ms = 0;
     int64_t pool_read = 0, pool_written = 0, pool_groups = 0;
+    // of the last thin: kernel ms, bytes read and written, draws made, workgroups per pass
+    double thin_ms = 0;
+    int64_t thin_read = 0, thin_written = 0, thin_draws = 0, thin_groups = 0;
     std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
     ~morna_jstore()
     {

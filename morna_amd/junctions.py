@@ -12,6 +12,9 @@ writes the text.
 
 Pooled samples (create_supersample.py of the reference's tests/): `JunctionStore.pool` sums the rows of
 groups of samples on the GPU, `write_supersample_files` writes the "chrom start end sum" files of that script.
+
+Depth thinning: `JunctionStore.thin` gives store rows with every read kept with one probability, by a
+counter-based integer hash on the GPU; `parse_downsample` reads the rates of `--downsample`.
 """
 import ctypes as C
 import gzip
@@ -29,6 +32,10 @@ WEIGHTS_MAGIC = b"MORNAJW1"
 MAX_NEAREST = 1024              # neighbours per query of the unhashed search (MORNA_JNEAREST_MAX_K)
 MAX_GRID = 15                   # coverage thresholds of one recovery call (morna_jstore_recovery)
 MAX_PREFIXES = 8                # list lengths of one recovery sweep (morna_jstore_recovery_sweep)
+MAX_RATES = 16                  # rates of one --downsample
+KEEP_ALL = 2**32                # the threshold that keeps every read (morna_jstore_thin)
+MAX_THIN_COVERAGE = 2**24       # the largest coverage of a row that can be thinned
+DEFAULT_DOWNSAMPLE_SEED = 8675309
 DEFAULT_RECOVERY_GRID = "0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000"
 RECOVERY_COLUMNS = ("frequency_filter", "coverage_filter", "min_count", "retrieved", "true_positive", "false_positive",
                     "false_negative", "precision", "recall", "fscore")
@@ -75,6 +82,23 @@ def parse_results_sweep(text):
     if len(values) > MAX_PREFIXES:
         raise ValueError("--results-sweep holds %d distinct values: one sweep takes at most %d" % (len(values), MAX_PREFIXES))
     return values
+
+
+def parse_downsample(text):
+    """--downsample "<p1>,<p2>,...": 1 to 16 distinct rates, each a float in [0, 1], in the order typed.  Returns (the rates
+    as typed, the thresholds int(round(rate * 2^32)) of morna_jstore_thin).  ValueError otherwise."""
+    typed = [t.strip() for t in str(text).split(",")]
+    if len(typed) > MAX_RATES:
+        raise ValueError("--downsample holds %d rates: one run takes at most %d" % (len(typed), MAX_RATES))
+    rates = []
+    for t in typed:
+        rate = float(t)                                        # (float() raises on "", "a" and "1/2")
+        if not 0.0 <= rate <= 1.0:                             # (nan fails both comparisons)
+            raise ValueError("--downsample: a rate is a number in [0, 1] (got %r)" % (t,))
+        if rate in rates:
+            raise ValueError("--downsample names the rate %r twice" % (t,))
+        rates.append(rate)
+    return typed, [int(round(rate * 4294967296.0)) for rate in rates]
 
 
 def _ratio(a, b):
@@ -164,6 +188,25 @@ class Pooled(object):
 
     def __len__(self):
         return len(self.lines)
+
+
+class Thinned(object):
+    """A store row at a fraction of its depth (JunctionStore.thin): lines (the line numbers that keep at least one read,
+    ascending, int32) and cov (the reads each keeps, int32)."""
+
+    def __init__(self, lines, cov):
+        self.lines, self.cov = lines, cov
+
+    def __len__(self):
+        return len(self.lines)
+
+
+def lost_lines(row_lines, row_cov, thinned_lines, min_coverage=1):
+    """The truth of `recovery --downsample --lost-only`: the lines of a sample's full row covered at least min_coverage
+    times that its thinned row does not hold -- what the shallow sequencing lost -- ascending, int32.  Pure host code."""
+    row_lines, row_cov = np.asarray(row_lines, np.int64), np.asarray(row_cov, np.int64)
+    full = row_lines[row_cov >= int(min_coverage)]
+    return np.setdiff1d(full, np.asarray(thinned_lines, np.int64)).astype(np.int32)
 
 
 def view(pp, ctype, count):
@@ -417,6 +460,45 @@ class JunctionStore(object):
         s = np.zeros(4, np.float64)
         check(lib().morna_jstore_pool_stats(self._p, ptr(s)))
         return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "workgroups": int(s[3])}
+
+    # ---- depth thinning -----------------------------------------------------------------------------------
+    def thin(self, sample_ids, keep, seed):
+        """One Thinned per job (sample_ids[q], keep[q]): the row of that external sample id with every read kept when its
+        hash is below keep[q], an integer in [0, 2^32] (parse_downsample: round(rate * 2^32)); a scalar `keep` serves every
+        job.  The same id may be named by many jobs.  All jobs in one call on the GPU; the answer depends on (seed, sample
+        id, line, coverage, keep) alone.  IndexError for an id the store lacks, ValueError for a threshold outside [0, 2^32]
+        or a row with a coverage outside [0, 2^24]."""
+        ids = np.ascontiguousarray([int(s) for s in sample_ids], np.int64)
+        keep = [int(keep)] * len(ids) if np.ndim(keep) == 0 else [int(a) for a in keep]
+        if len(keep) != len(ids):
+            raise ValueError("thin takes one threshold per job (%d jobs, %d thresholds)" % (len(ids), len(keep)))
+        for a in keep:
+            if a < 0 or a > KEEP_ALL:
+                raise ValueError("thin: the threshold %d is outside [0, 2^32]" % a)
+        keep = np.array(keep, np.uint64)
+        r = C.c_void_p()
+        check(lib().morna_jstore_thin(self._p, ptr(ids), ptr(keep), len(ids), int(seed) & 0xffffffff, C.byref(r)))
+        try:
+            counts = np.zeros(len(ids), np.int64)
+            check(lib().morna_jthinned_counts(r, ptr(counts)))
+            out = []
+            for q in range(len(ids)):
+                p = [C.c_void_p() for _ in range(2)]
+                check(lib().morna_jthinned_job(r, q, *[C.byref(x) for x in p]))
+                n = int(counts[q])
+                out.append(Thinned(view(p[0], C.c_int32, n), view(p[1], C.c_int32, n)))
+            return out
+        finally:
+            lib().morna_jthinned_free(r)
+
+    def thin_stats(self):
+        """Of the last thin: kernel ms (HIP events: both passes and the scan), bytes read (16 per entry of every named row),
+        bytes written (4 per entry and 8 per surviving line), draws made (the summed coverage of the named rows) and
+        workgroups per pass."""
+        s = np.zeros(5, np.float64)
+        check(lib().morna_jstore_thin_stats(self._p, ptr(s)))
+        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "draws": int(s[3]),
+                "workgroups": int(s[4])}
 
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank

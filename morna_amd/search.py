@@ -322,27 +322,23 @@ class MornaSearch(object):
                                  "most): a query takes int32 coverages; `morna supersample` writes such a group's file"
                                  % (label, int(r.lines[bad[0]]), int(sums[bad[0]])))
 
-    def queries_from_pooled(self, pooled, labels, junction_file):
-        """The groups of pool_samples as queries of the hashed searches: for group g the vector update_query over the
-        lines it holds (key "chrom start end" of that line of `junction_file`, the (gzipped) intropolis file the index
-        was made from; the group's summed coverage) and finalize_query would make -- bit for bit the row of an intropolis
-        file that lists the groups as samples with those sums.  Returns a QueryBatch whose query q is group q; `labels`
-        name the groups in messages.  ValueError when the file's line count is not the store's, or a sum does not fit
-        int32."""
+    def _queries_from_rows(self, rows, junction_file):
+        """(lines ascending, integer coverages that fit int32) lists as queries of the hashed searches: for list g the
+        vector update_query over its lines (key "chrom start end" of that line of `junction_file`, the (gzipped) intropolis
+        file the index was made from; its coverage) and finalize_query would make -- bit for bit the row of an intropolis
+        file that lists the lists as samples with those coverages.  ValueError when the file's line count is not the
+        store's."""
         from .index import ParsedLines
-        self._check_batch_possible()
-        pooled, labels = list(pooled), list(labels)
-        self._check_pooled_coverages(pooled, labels)
         n_lines = self.junction_store().n_lines
         parsed = ParsedLines(junction_file, sample_count=1, sample_threshold=0)
         if parsed.lines_read != n_lines:
             raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
                              % (junction_file, parsed.lines_read, n_lines))
         a = parsed.arrays()
-        # group-major (line, sum) lists -> line-major rows of (group, sum); a group's lines ascend, so file order is kept
-        line = np.concatenate([np.asarray(r.lines, np.int64) for r in pooled] + [np.zeros(0, np.int64)])
-        group = np.concatenate([np.full(len(r), g, np.int64) for g, r in enumerate(pooled)] + [np.zeros(0, np.int64)])
-        cov = np.concatenate([np.asarray(r.sums, np.int64) for r in pooled] + [np.zeros(0, np.int64)])
+        # list-major (line, coverage) lists -> line-major rows of (list, coverage); a list's lines ascend, so file order is kept
+        line = np.concatenate([np.asarray(l, np.int64) for l, _ in rows] + [np.zeros(0, np.int64)])
+        group = np.concatenate([np.full(len(l), g, np.int64) for g, (l, _) in enumerate(rows)] + [np.zeros(0, np.int64)])
+        cov = np.concatenate([np.asarray(c, np.int64) for _, c in rows] + [np.zeros(0, np.int64)])
         order = np.lexsort((group, line))
         line, group, cov = line[order], group[order], cov[order]
         held, per_line = np.unique(line, return_counts=True)
@@ -354,21 +350,54 @@ class MornaSearch(object):
         np.cumsum(key_len, out=out_off[1:])
         take = np.repeat(key_off[held] - out_off[:-1], key_len) + np.arange(int(out_off[-1]), dtype=np.int64)
         prep = dict(key_bytes=key_bytes[take], key_off=out_off, row_ptr=row_ptr, ids=group, cov=cov,
-                    idf=np.zeros(len(held), np.float64), ext_ids=np.arange(len(pooled), dtype=np.int64))
+                    idf=np.zeros(len(held), np.float64), ext_ids=np.arange(len(rows), dtype=np.int64))
         lines = ParsedLines.from_arrays(prep, self.sample_count)
         return self._batch_from_terms(lines.query_terms(self._vocab(), self.sample_count))
+
+    def _unhashed_terms_from_rows(self, rows):
+        """(lines ascending, integer coverages that fit int32) lists as the term lists of unhashed_search_nn_batch, the
+        lines of weight 0 left out as junctions.query_terms leaves them out."""
+        _, w = self.unhashed_store()
+        terms = []
+        for l, c in rows:
+            keep = np.asarray(w)[np.asarray(l, np.int64)] != 0.0
+            terms.append((np.asarray(l, np.int32)[keep], np.asarray(c, np.int64)[keep].astype(np.int32)))
+        return terms
+
+    def queries_from_pooled(self, pooled, labels, junction_file):
+        """The groups of pool_samples as queries of the hashed searches: for group g the vector update_query over the
+        lines it holds (key "chrom start end" of that line of `junction_file`, the (gzipped) intropolis file the index
+        was made from; the group's summed coverage) and finalize_query would make -- bit for bit the row of an intropolis
+        file that lists the groups as samples with those sums.  Returns a QueryBatch whose query q is group q; `labels`
+        name the groups in messages.  ValueError when the file's line count is not the store's, or a sum does not fit
+        int32."""
+        self._check_batch_possible()
+        pooled, labels = list(pooled), list(labels)
+        self._check_pooled_coverages(pooled, labels)
+        return self._queries_from_rows([(r.lines, r.sums) for r in pooled], junction_file)
 
     def unhashed_terms_from_pooled(self, pooled, labels):
         """The groups of pool_samples as the term lists of unhashed_search_nn_batch: (lines ascending, coverages) per
         group, the lines of weight 0 left out as junctions.query_terms leaves them out."""
         pooled, labels = list(pooled), list(labels)
         self._check_pooled_coverages(pooled, labels)
-        _, w = self.unhashed_store()
-        terms = []
-        for r in pooled:
-            keep = np.asarray(w)[np.asarray(r.lines, np.int64)] != 0.0
-            terms.append((np.asarray(r.lines, np.int32)[keep], np.asarray(r.sums, np.int64)[keep].astype(np.int32)))
-        return terms
+        return self._unhashed_terms_from_rows([(r.lines, r.sums) for r in pooled])
+
+    # ---- store rows at a fraction of their depth as queries (DESIGN.md 8, N9) -----------------------------------------------
+    def thin_samples(self, sample_ids, keep, seed):
+        """One junctions.Thinned per job (external sample id, keep threshold in [0, 2^32]) (junctions.JunctionStore.thin):
+        the sample's row with every read kept with probability keep / 2^32, all jobs in one call on the GPU."""
+        return self.junction_store().thin(sample_ids, keep, seed)
+
+    def queries_from_thinned(self, thinned, junction_file):
+        """The rows of thin_samples as queries of the hashed searches: bit for bit the rows of an intropolis file that lists
+        every job as a sample of its own with the thinned coverages.  Returns a QueryBatch whose query q is job q."""
+        self._check_batch_possible()
+        return self._queries_from_rows([(r.lines, r.cov) for r in thinned], junction_file)
+
+    def unhashed_terms_from_thinned(self, thinned):
+        """The rows of thin_samples as the term lists of unhashed_search_nn_batch."""
+        return self._unhashed_terms_from_rows([(r.lines, r.cov) for r in thinned])
 
     # ---- unhashed TF-IDF search (DESIGN.md 8, N5): no counterpart the reference finished -------------------------
     def unhashed_store(self):
