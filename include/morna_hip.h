@@ -447,6 +447,41 @@ int morna_exact_search_by_item(morna_index *h, const int32_t *items, int64_t nq,
                                int32_t *ids_out, double *dist_out, int32_t *count_out);
 
 /*
+ * Restricted search (no counterpart in the reference): sample allow-lists and leave-out groups.
+ * A restriction on an index of n items has two optional parts: an allow bitmap (bit i of allow_bits[i / 32]; NULL: every
+ * item is allowed; the bits past n_items in the last word are ignored) and a group label per item (item_group[i], negative:
+ * none; NULL: no item has one).  Every query q of a restricted call carries g_q (q_group[q], negative or q_group NULL:
+ * none).  Item i is ELIGIBLE for q iff allow[i] holds and (g_q < 0 or item_group[i] != g_q); call that set E(q).
+ *   Exact: the answer for q is what morna_exact_search returns on an index that holds exactly the rows of E(q) in
+ *     ascending id order, ids mapped back: same ids, bit-identical fp64 distances, same tie order (equal distance: higher
+ *     id first), a short count when |E(q)| < k, and count -1 only when an ELIGIBLE row makes the reference's math.sqrt
+ *     raise (a near-parallel row that is not eligible does not fail the query).
+ *   Approximate: the traversal is the unrestricted one -- same pops, same search_k accounting, ids that are duplicates
+ *     or not eligible included -- and the candidate set is the unrestricted one intersected with E(q); the answer is its k
+ *     nearest by the same distances and tie order.  It equals the unrestricted answer with k = n_items, filtered to E(q)
+ *     and cut to k.  search_k = -1 is k * n_trees as everywhere: a caller with a small allow-list passes a larger one
+ *     (morna_amd.search scales its default by n / n_allowed).
+ * The bitmap and the labels are copied to the handle's device and live with the restriction object.  It is bound to the
+ * handle and to the handle's n_items at creation: a search after the item count changed returns MORNA_E_STATE, with
+ * another handle MORNA_E_INVALID.  Free it before the handle is destroyed.
+ * Query sources: q ([nq][dim], fp32 for the approximate search, fp64 for the exact one), or items ([nq] stored rows), or
+ * both NULL: the staged query rows of morna_build_query_rows (nq must be their count).
+ * r == NULL is MORNA_E_INVALID here, never a silent unrestricted search; so is q_group with a restriction made without
+ * item_group.  Outputs as morna_get_nns_by_vector / morna_exact_search.  Not available on the row-sharded paths.
+ * morna_restriction_counts: counts[0..2] = n_items, allowed items, items with a label >= 0.
+ */
+typedef struct morna_restriction morna_restriction;
+int morna_restriction_create(morna_index *h, const uint32_t *allow_bits /* [(n_items+31)/32] or NULL */,
+                             const int32_t *item_group /* [n_items] or NULL */, morna_restriction **out);
+int morna_restriction_counts(const morna_restriction *r, int64_t *counts /* n_items, n_allowed, n_grouped */);
+int morna_restriction_free(morna_restriction *r);
+int morna_get_nns_restricted(morna_index *h, const morna_restriction *r, const float *q, const int32_t *items, int64_t nq,
+                             const int32_t *q_group /* [nq] or NULL */, int32_t k, int32_t search_k,
+                             int32_t *ids, float *dist, int32_t *count);
+int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
+                                  const int32_t *q_group, int32_t k, int32_t *ids, double *dist, int32_t *count);
+
+/*
  * Row-sharded search (one handle per GPU; the reference has no such path): merge of the
  * per-shard answers to the same queries after their all-gather.  ids / dist: [world][nq][kk], each
  * [kk] list as get_nns_* returns it -- ascending (distance, id), empty slots id -1 last -- with ids

@@ -108,6 +108,11 @@ SIGNATURES = {
     "morna_get_nns_by_item": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "morna_exact_search": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p]),
     "morna_exact_search_by_item": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p]),
+    "morna_restriction_create": (C.c_int, [_p, _p, _p, C.POINTER(_p)]),
+    "morna_restriction_counts": (C.c_int, [_p, _p]),
+    "morna_restriction_free": (C.c_int, [_p]),
+    "morna_get_nns_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p]),
+    "morna_exact_search_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _p, _p, _p]),
     "morna_comm_unique_id": (C.c_int, [_p]),
     "morna_comm_init": (C.c_int, [_p, _p, _i32, _i32]),
     "morna_comm_destroy": (C.c_int, [_p]),

@@ -19,6 +19,36 @@ from . import _lib
 from ._lib import check, lib, ptr
 
 
+def pack_allow_bits(allow):
+    """A boolean array [n] as the uint32 words of morna_restriction_create: bit i of word i // 32, low bit first."""
+    allow = np.ascontiguousarray(allow, dtype=bool)
+    padded = np.zeros((len(allow) + 31) // 32 * 32, bool)
+    padded[:len(allow)] = allow
+    return np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
+
+
+class Restriction(object):
+    """A restriction of the searches of one AnnoyIndex (AnnoyIndex.restriction; include/morna_hip.h, "restricted search"):
+    n_items, n_allowed and n_grouped as the library counted them, `groups` the items' labels (int32 [n_items]) or None.
+    The bitmap and the labels live on the index's device until the object goes."""
+
+    def __init__(self, owner, handle, groups):
+        self.owner, self._p, self.groups = owner, handle, groups
+        counts = np.zeros(3, np.int64)
+        check(lib().morna_restriction_counts(self._p, ptr(counts)))
+        self.n_items, self.n_allowed, self.n_grouped = (int(x) for x in counts)
+
+    def __del__(self):
+        p = getattr(self, "_p", None)
+        owner = getattr(self, "owner", None)
+        if p is not None and p.value and owner is not None and getattr(owner, "_h", None) is not None and owner._h.value:
+            try:
+                lib().morna_restriction_free(p)
+            except Exception:
+                pass
+        self._p = C.c_void_p()
+
+
 class AnnoyIndex(object):
     def __init__(self, f, metric='angular', device=0):
         if metric != 'angular':
@@ -235,6 +265,74 @@ class AnnoyIndex(object):
         d = np.empty((nq, n), np.float64)
         cnt = np.empty(nq, np.int32)
         check(lib().morna_exact_search_by_item(self._h, ptr(items), nq, int(n), ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
+    # ---- restricted search (allow-lists and leave-out groups; no counterpart in annoy) ----
+    def restriction(self, allow=None, groups=None):
+        """A Restriction of this index's searches.  allow: booleans [n_items], the items a search may return (None: all);
+        groups: int32 labels [n_items], negative for none (None: no item has one).  A query of a restricted search that
+        carries the label g >= 0 is not answered with an item of label g."""
+        n = self.get_n_items()
+        bits = None
+        if allow is not None:
+            allow = np.asarray(allow)
+            if allow.shape != (n,):
+                raise ValueError("allow must hold one entry per item (%d), got shape %r" % (n, allow.shape))
+            bits = pack_allow_bits(allow)
+        if groups is not None:
+            if np.shape(groups) != (n,):
+                raise ValueError("groups must hold one label per item (%d), got shape %r" % (n, np.shape(groups)))
+            groups = np.ascontiguousarray(groups, dtype=np.int32)
+        out = C.c_void_p()
+        check(lib().morna_restriction_create(self._h, ptr(bits), ptr(groups), C.byref(out)))
+        return Restriction(self, out, groups)
+
+    def _restricted_queries(self, restriction, Q, items, query_groups, qtype):
+        """(q pointer, items pointer, nq, q_group pointer and the arrays that must outlive the call)"""
+        if not isinstance(restriction, Restriction) or restriction.owner is not self:
+            raise ValueError("the restriction was not made by this index (AnnoyIndex.restriction)")
+        if Q is not None and items is not None:
+            raise ValueError("give query vectors or items, not both")
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=qtype)
+            if Q.ndim != 2 or Q.shape[1] != self.f:
+                raise IndexError("queries must be [nq, %d]" % self.f)
+            nq = Q.shape[0]
+        elif items is not None:
+            items = np.ascontiguousarray(items, dtype=np.int32)
+            if items.ndim != 1:
+                raise ValueError("items must be one-dimensional")
+            nq = items.shape[0]
+        else:
+            nq = getattr(self, "_qrows_n", 0)
+        if query_groups is not None:
+            if restriction.groups is None:
+                raise ValueError("query groups need a restriction made with groups")
+            query_groups = np.ascontiguousarray(query_groups, dtype=np.int32)
+            if query_groups.shape != (nq,):
+                raise ValueError("query_groups must hold one label per query (%d), got shape %r" % (nq, query_groups.shape))
+        return Q, items, nq, query_groups
+
+    def get_nns_restricted(self, restriction, n, search_k=-1, Q=None, items=None, query_groups=None):
+        """get_nns_by_vector_batch (Q), get_nns_by_item_batch (items) or get_nns_by_query_rows (neither) under a
+        restriction; query_groups: the label every query carries (int32 [nq], negative: none), None: no query has one."""
+        Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float32)
+        ids = np.empty((nq, n), np.int32)
+        d = np.empty((nq, n), np.float32)
+        cnt = np.empty(nq, np.int32)
+        check(lib().morna_get_nns_restricted(self._h, restriction._p, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
+                                             int(search_k), ptr(ids), ptr(d), ptr(cnt)))
+        return ids, d, cnt
+
+    def exact_search_restricted(self, restriction, n, Q=None, items=None, query_groups=None):
+        """exact_search_batch (Q, fp64), exact_search_by_item_batch (items) or exact_search_query_rows (neither) under a
+        restriction: the answer of the same search on an index of the eligible rows only, ids mapped back."""
+        Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
+        ids = np.empty((nq, n), np.int32)
+        d = np.empty((nq, n), np.float64)
+        cnt = np.empty(nq, np.int32)
+        check(lib().morna_exact_search_restricted(self._h, restriction._p, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
+                                                  ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----

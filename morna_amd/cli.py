@@ -43,6 +43,13 @@ here the number kept is binomial and reads that span no junction do not exist.  
 downsample -> align -> recover experiment in one call: the truth is the sample's full row, or with --lost-only the junctions
 of it the thinned row no longer holds.
 
+`--within ids.txt` / `--without ids.txt` (`search`, `junctions`, `recovery`; every query kind, -e, the approximate search and
+--unhashed) answer only with, or never with, the listed samples; `--leave-out-groups groups.tsv` (with -q, --query-ids and
+--downsample) never answers a query with a sample of its own group -- a donor's other tissues, a study's replicates -- the
+query included, and `recovery` then asks for exactly -r results instead of -r + 1 with the query dropped.  The searches
+themselves are restricted on the GPU; the output format is unchanged, one line on stderr says what the
+restriction holds.  Without --search-k an allow-list searches with n_trees * r * ceil(n / n_allowed) instead of 100.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -63,6 +70,8 @@ here do the latter.
     python -m morna_amd.cli search -x idx --supersamples tissues.tsv --junction-file junctions.tsv.gz -e -d
     python -m morna_amd.cli search -x idx --query-ids 12,34 --downsample 0.5,0.1,0.01 --junction-file junctions.tsv.gz -d
     python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --downsample 0.5,0.1,0.01 --junction-file junctions.tsv.gz --lost-only
+    python -m morna_amd.cli search -x idx --intropolis new_samples.tsv.gz --within gtex_ids.txt -e -d
+    python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --leave-out-groups donors.tsv
 """
 import argparse
 import sys
@@ -132,6 +141,15 @@ def add_search_parameters(subparser):
                                 'thinned coverages (`search` and `recovery`)')
     subparser.add_argument('--downsample-seed', metavar='<int>', type=int, required=False, default=8675309, action=_StoreGiven,
                            help='the seed of --downsample (default 8675309); the same seed gives the same reads')
+    subparser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                           help='answer only with the samples this file lists, one integer sample id per line')
+    subparser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                           help='never answer with a sample this file lists, one integer sample id per line')
+    subparser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
+                           help='with -q, --query-ids and --downsample: a groups file, "<label><TAB><id>,<id>,..." per line; '
+                                'a query is never answered with a sample of its own group, itself included, and a query '
+                                'sample the file does not name is a group of its own.  `recovery` then asks for exactly -r '
+                                'results instead of -r + 1 with the query dropped')
     subparser.add_argument('--device', type=str, default='0',
                            help='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
                                 'dealt to these devices in turn')
@@ -275,6 +293,79 @@ def _check_downsample_flags(parser, args):
         parser.error("--downsample takes 1 to 16 distinct comma-separated rates in [0, 1], such as 0.5,0.1,0.01 (%s)" % e)
 
 
+def _check_restriction_flags(parser, args):
+    """--within / --without / --leave-out-groups: the files read and checked against each other and against the query
+    kind; argparse errors, before any index is read.  Leaves the ids in args.within_ids / args.without_ids and the groups in
+    args.leave_out (None where the flag is absent), and args.restriction = None for main() to fill in."""
+    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
+    if args.within is None and args.without is None and args.leave_out_groups is None:
+        return
+    from .junctions import parse_groups_file, parse_sample_ids_file
+    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
+        if on:
+            parser.error("--within, --without and --leave-out-groups cannot be used with %s" % flag)
+    try:
+        if args.within is not None:
+            args.within_ids = parse_sample_ids_file(args.within)
+        if args.without is not None:
+            args.without_ids = parse_sample_ids_file(args.without)
+        if args.leave_out_groups is not None:
+            args.leave_out = parse_groups_file(args.leave_out_groups)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+    if args.within_ids is not None and args.without_ids is not None:
+        both = sorted(set(args.within_ids) & set(args.without_ids))
+        if both:
+            parser.error("--within and --without both name sample id %d" % both[0])
+    if args.leave_out is not None:
+        for flag, on in (("--intropolis", args.intropolis is not None), ("--supersamples", args.supersamples is not None),
+                         ("--unhashed", args.unhashed)):
+            if on:
+                parser.error("--leave-out-groups cannot be used with %s: it takes queries that are samples of the index "
+                             "(-q, --query-ids, --downsample)" % flag)
+        if args.query_id is None and args.query_ids is None:
+            parser.error("--leave-out-groups cannot be used with a query from a stream: it takes queries that are samples of "
+                         "the index (-q, --query-ids, --downsample)")
+
+
+def _make_restriction(args, searcher):
+    """The searcher's restriction of the three flags (None without them), its one line on stderr.  Every query sample the
+    groups file does not name becomes a group of its own."""
+    if args.within_ids is None and args.without_ids is None and args.leave_out is None:
+        return None
+    groups = None
+    if args.leave_out is not None:
+        groups = list(args.leave_out)
+        named = set(i for _, ids in groups for i in ids)
+        query_ids = args.query_ids if isinstance(args.query_ids, list) else ([args.query_id] if args.query_id is not None else [])
+        for query_id in query_ids:
+            if query_id not in named and query_id in searcher.internal_id_map:
+                groups.append(("query-%d" % query_id, [query_id]))
+                named.add(query_id)
+    restriction = searcher.restriction(args.within_ids, args.without_ids, groups)
+    sys.stderr.write(restriction.summary() + "\n")
+    return restriction
+
+
+def _restriction(args):
+    """The restriction main() made of the three flags; None without them (and for a caller that made `args` itself)."""
+    return getattr(args, "restriction", None)
+
+
+def _leaves_out(args):
+    """--leave-out-groups was given: the search itself leaves the query out."""
+    return getattr(args, "leave_out", None) is not None
+
+
+def _search_k(args):
+    """--search-k as given; without it the command's default of 100, or under an allow-list -1: the searcher then scales
+    annoy's default by the share of the index that is allowed (search.restricted_search_k)."""
+    r = _restriction(args)
+    if r is not None and r.allow is not None and not getattr(args, "search_k_given", False):
+        return -1
+    return args.search_k
+
+
 def _check_supersample_flags(parser, args):
     """--supersamples: `search` only, with the file that names the lines and without another query."""
     if args.supersamples is None:
@@ -380,6 +471,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_batch_flags(parser, args)
     if args.subparser_name == 'junctions':
         _check_junction_flags(parser, args)
+    if args.subparser_name in ('search', 'junctions', 'recovery'):
+        _check_restriction_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -439,6 +532,7 @@ def main(argv=None, stdin=None, stdout=None):
     else:
         searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
     try:
+        args.restriction = _make_restriction(args, searcher)
         if args.supersamples is not None:
             return _search_supersamples(args, searcher, stdout)
         if args.downsample is not None and args.subparser_name == 'search':
@@ -510,8 +604,9 @@ def _recovery(args, searcher, stdin, stdout):
     wanted = args.results
     collected = []
     by_item = args.intropolis is None
-    if by_item:
+    if by_item and not _leaves_out(args):
         args.results = wanted + 1                              # leave one out: the query is its own nearest neighbour
+    # (--leave-out-groups: the search itself leaves the query's whole group out, the query included: exactly -r)
     sink = io.StringIO()
     with contextlib.redirect_stdout(sink):                     # (search_member_n prints its two lines itself)
         rc = _search(args, searcher, stdin, sink, None, 0, collect=collected)
@@ -575,16 +670,21 @@ def _downsample_search(args, searcher, n_results, junction_file):
     for (query_id, rate), row in zip(jobs, thinned):
         if len(row) == 0:
             sys.stderr.write("query %s at keep %s keeps no read: it is searched as a sample without junctions\n" % (query_id, rate))
+    r = _restriction(args)
+    own = None                                                 # every job carries its sample's group
+    if r is not None and r.item_group is not None:
+        own = r.own_groups([searcher.internal_id_map[query_id] for query_id, _ in jobs])
     if args.unhashed:
         results = searcher.unhashed_search_nn_batch(searcher.unhashed_terms_from_thinned(thinned), n_results,
-                                                    include_distances=args.distances, meta_db=args.metadata)
+                                                    include_distances=args.distances, meta_db=args.metadata, restriction=r)
     else:
         batch = searcher.queries_from_thinned(thinned, junction_file)
         if args.exact:
-            results = searcher.exact_search_nn_batch(batch, n_results, include_distances=args.distances, meta_db=args.metadata)
+            results = searcher.exact_search_nn_batch(batch, n_results, include_distances=args.distances, meta_db=args.metadata,
+                                                     restriction=r, query_groups=own)
         else:
-            results = searcher.search_nn_batch(batch, n_results, args.search_k, include_distances=args.distances,
-                                               meta_db=args.metadata)
+            results = searcher.search_nn_batch(batch, n_results, _search_k(args), include_distances=args.distances,
+                                               meta_db=args.metadata, restriction=r, query_groups=own)
     return jobs, thinned, results
 
 
@@ -612,7 +712,7 @@ def _recovery_downsample(args, searcher, stdout):
     from .junctions import format_recovery_rows, lost_lines, recovery_rows, sum_recovery_rows
     frequencies, coverages = args.grid_parts
     wanted = args.results
-    jobs, thinned, results = _downsample_search(args, searcher, wanted + 1, args.junction_file)
+    jobs, thinned, results = _downsample_search(args, searcher, wanted + (1 if not _leaves_out(args) else 0), args.junction_file)
     typed = args.downsample_parts[0]
     store = searcher.junction_store()
     lists, truth, failed = [], [], False
@@ -678,14 +778,16 @@ def _search_supersamples(args, searcher, stdout):
     pooled = searcher.pool_samples([ids for _, ids in groups])
     if args.unhashed:
         terms = searcher.unhashed_terms_from_pooled(pooled, labels)
-        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata)
+        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata,
+                                                    restriction=_restriction(args))
     else:
         batch = searcher.queries_from_pooled(pooled, labels, args.unhashed_junction_file)
         if args.exact:
-            results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata)
+            results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
+                                                     restriction=_restriction(args))
         else:
-            results = searcher.search_nn_batch(batch, args.results, args.search_k, include_distances=args.distances,
-                                               meta_db=args.metadata)
+            results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
+                                               meta_db=args.metadata, restriction=_restriction(args))
     failed = False
     for label, res in zip(labels, results):
         stdout.write("# query %s\n" % label)
@@ -705,7 +807,7 @@ def _search_unhashed(args, searcher, stdin, stdout):
     by_item = args.query_ids if args.query_ids is not None else ([args.query_id] if args.query_id is not None else None)
     if by_item is not None:
         results = searcher.unhashed_search_member_n_batch(by_item, args.results, include_distances=args.distances,
-                                                          meta_db=args.metadata)
+                                                          meta_db=args.metadata, restriction=_restriction(args))
         for query_id, res in zip(by_item, results):
             _write_member_header(stdout, query_id, searcher.internal_id_map[query_id], args.query_ids is not None)
             results_output(res, stdout)
@@ -714,7 +816,8 @@ def _search_unhashed(args, searcher, stdin, stdout):
     key_line = key_lines(args.unhashed_junction_file, store.n_lines)
     if args.intropolis is not None:
         sample_ids, terms = intropolis_query_terms(args.intropolis, key_line, w)
-        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata)
+        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata,
+                                                    restriction=_restriction(args))
         for sample_id, res in zip(sample_ids, results):
             stdout.write("# query %d\n" % sample_id)
             results_output(res, stdout)
@@ -724,7 +827,8 @@ def _search_unhashed(args, searcher, stdin, stdout):
         key = " ".join(str(_) for _ in junction[:3])
         coverage[key] = coverage.get(key, 0) + int(junction[3])
     results = searcher.unhashed_search_nn_batch([query_terms(coverage, key_line, w)], args.results,
-                                                include_distances=args.distances, meta_db=args.metadata)
+                                                include_distances=args.distances, meta_db=args.metadata,
+                                                restriction=_restriction(args))
     results_output(results[0], stdout)
     return 0
 
@@ -735,8 +839,9 @@ def _search_batch(args, searcher, stdout, collect=None):
     every answered query."""
     from .search import results_output
     if args.query_ids is not None:
-        internal, results = searcher.search_member_n_batch(args.query_ids, args.results, args.search_k,
-                                                           include_distances=args.distances, meta_db=args.metadata)
+        internal, results = searcher.search_member_n_batch(args.query_ids, args.results, _search_k(args),
+                                                           include_distances=args.distances, meta_db=args.metadata,
+                                                           restriction=_restriction(args))
         for query_id, internal_id, res in zip(args.query_ids, internal, results):
             _write_member_header(stdout, query_id, internal_id, True)
             results_output(res, stdout)
@@ -745,10 +850,11 @@ def _search_batch(args, searcher, stdout, collect=None):
         return 0
     batch = searcher.queries_from_intropolis(args.intropolis)
     if args.exact:
-        results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata)
+        results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
+                                                 restriction=_restriction(args))
     else:
-        results = searcher.search_nn_batch(batch, args.results, args.search_k, include_distances=args.distances,
-                                           meta_db=args.metadata)
+        results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
+                                           meta_db=args.metadata, restriction=_restriction(args))
     failed = False
     for sample_id, res in zip(batch.ext_ids, results):
         stdout.write("# query %d\n" % sample_id)
@@ -767,6 +873,16 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     from .search import results_output
     if args.intropolis is not None or args.query_ids is not None:
         return _search_batch(args, searcher, stdout, collect)
+    if args.query_id is not None and _restriction(args) is not None:
+        # search_member_n under a restriction: its two lines, then the restricted search by item
+        internal, results = searcher.search_member_n_batch([args.query_id], args.results, _search_k(args),
+                                                           include_distances=args.distances, meta_db=args.metadata,
+                                                           restriction=_restriction(args))
+        _write_member_header(stdout, args.query_id, internal[0], False)
+        results_output(results[0], stdout)
+        if collect is not None:
+            collect.append((args.query_id, results[0]))
+        return 0
     if args.query_id is not None:                              # morna.py:1358-1365
         if dist is not None and rank != 0:
             import contextlib
@@ -831,7 +947,14 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     searcher.finalize_query()
     if args.verbose:
         sys.stderr.write("\n")
-    if args.exact and not converge:
+    if _restriction(args) is not None:
+        if args.exact:
+            results = searcher.exact_search_nn(args.results, include_distances=args.distances, meta_db=args.metadata,
+                                               restriction=_restriction(args))
+        else:
+            results = searcher.search_nn(args.results, _search_k(args), include_distances=args.distances, meta_db=args.metadata,
+                                         restriction=_restriction(args))
+    elif args.exact and not converge:
         results = searcher.exact_search_nn(args.results, include_distances=args.distances, meta_db=args.metadata)
     else:
         results = searcher.search_nn(args.results, args.search_k, include_distances=args.distances,

@@ -614,6 +614,152 @@ int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, d
     return exact_search_any(h, nullptr, nullptr, nullptr, h->qrows.nq, k, ids_out, dist_out, count_out, nullptr, 0, h->qrows.rows64.p);
 }
 
+// ---- restricted search (the contract is in morna_hip.h) ---------------------------------------------------------
+
+int morna_restriction_create(morna_index *h, const uint32_t *allow_bits, const int32_t *item_group, morna_restriction **out)
+{
+    CHECK_H(h);
+    if (!out) {
+        set_error("restriction_create: null pointer");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    const int64_t n = morna_get_n_items(h);
+    if (n <= 0) {
+        set_error("restriction_create: the index holds no items");
+        return MORNA_E_EMPTY;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    MORNA_TRY(settle(h));
+    morna_restriction *r = new (std::nothrow) morna_restriction();
+    if (!r) {
+        set_error("out of host memory");
+        return MORNA_E_INVALID;
+    }
+    int rc = MORNA_OK;
+    try {
+        const int64_t words = (n + 31) / 32;
+        std::vector<uint32_t> deny((size_t)words, 0u);
+        int64_t allowed = n;
+        if (allow_bits) {
+            allowed = 0;
+            for (int64_t w = 0; w < words; w++) deny[(size_t)w] = ~allow_bits[w];
+        }
+        if (n & 31) deny[(size_t)words - 1] |= ~0u << (n & 31);   // the bits past n_items: never candidates
+        if (allow_bits)
+            for (int64_t w = 0; w < words; w++) allowed += 32 - __builtin_popcount(deny[(size_t)w]);
+        r->h = h;
+        r->device = h->device;
+        r->n_items = n;
+        r->n_allowed = allowed;
+        rc = r->deny.alloc((size_t)words);
+        if (rc == MORNA_OK && hipMemcpy(r->deny.p, deny.data(), (size_t)words * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("restriction_create: copy to the device failed");
+            rc = MORNA_E_HIP;
+        }
+        if (rc == MORNA_OK && item_group) {
+            for (int64_t i = 0; i < n; i++) r->n_grouped += item_group[i] >= 0 ? 1 : 0;
+            r->has_group = true;
+            rc = r->group.alloc((size_t)n);
+            if (rc == MORNA_OK && hipMemcpy(r->group.p, item_group, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
+                set_error("restriction_create: copy to the device failed");
+                rc = MORNA_E_HIP;
+            }
+        }
+    } catch (const std::exception &e) {
+        set_error("restriction_create: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK) {
+        delete r;
+        return rc;
+    }
+    *out = r;
+    return MORNA_OK;
+}
+
+int morna_restriction_counts(const morna_restriction *r, int64_t *counts)
+{
+    if (!r || !counts) {
+        set_error("restriction_counts: null pointer");
+        return MORNA_E_INVALID;
+    }
+    counts[0] = r->n_items;
+    counts[1] = r->n_allowed;
+    counts[2] = r->n_grouped;
+    return MORNA_OK;
+}
+
+int morna_restriction_free(morna_restriction *r)
+{
+    if (!r) return MORNA_OK;
+    (void)hipSetDevice(r->device);
+    delete r;
+    return MORNA_OK;
+}
+
+// r == NULL with q_group == NULL is refused: such a call would be an unrestricted search under another name
+static int restricted_args_ok(const morna_restriction *r, const int32_t *q_group, const void *ids, const char *who)
+{
+    if (!ids) {
+        set_error("%s: null buffer", who);
+        return MORNA_E_INVALID;
+    }
+    if (!r) {
+        set_error(q_group ? "%s: query groups need a restriction that holds the items' groups"
+                          : "%s: no restriction (use the unrestricted call)", who);
+        return MORNA_E_INVALID;
+    }
+    if (q_group && !r->has_group) {
+        set_error("%s: query groups need a restriction that holds the items' groups", who);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+int morna_get_nns_restricted(morna_index *h, const morna_restriction *r, const float *q, const int32_t *items, int64_t nq,
+                             const int32_t *q_group, int32_t k, int32_t search_k, int32_t *ids, float *dist, int32_t *count)
+{
+    CHECK_H(h);
+    MORNA_TRY(restricted_args_ok(r, q_group, ids, "get_nns_restricted"));
+    if (q && items) {
+        set_error("get_nns_restricted: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (!q && !items) {   // the staged query rows
+        MORNA_TRY(query_rows_ready(h));
+        if (nq != h->qrows.nq) {
+            set_error("get_nns_restricted: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        return query_batch(h, h->qrows.rows32.p, h->dpad, nullptr, nq, k, search_k, ids, dist, count, nullptr, 0, r, q_group);
+    }
+    return query_batch(h, q, 0, items, nq, k, search_k, ids, dist, count, nullptr, 0, r, q_group);
+}
+
+int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
+                                  const int32_t *q_group, int32_t k, int32_t *ids, double *dist, int32_t *count)
+{
+    CHECK_H(h);
+    MORNA_TRY(restricted_args_ok(r, q_group, ids, "exact_search_restricted"));
+    if (q && items) {
+        set_error("exact_search_restricted: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (!q && !items) {
+        MORNA_TRY(query_rows_ready(h));
+        if (nq != h->qrows.nq) {
+            set_error("exact_search_restricted: %lld queries asked for, %lld query rows are staged", (long long)nq,
+                      (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        return exact_search_any(h, nullptr, nullptr, nullptr, nq, k, ids, dist, count, nullptr, 0, h->qrows.rows64.p, r, q_group);
+    }
+    return exact_search_any(h, q, nullptr, items, nq, k, ids, dist, count, nullptr, 0, nullptr, r, q_group);
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

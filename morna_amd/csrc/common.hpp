@@ -334,6 +334,18 @@ struct morna_index {
     std::vector<hipEvent_t> free_ev;
 };
 
+// A restriction of the searches of one handle (morna_hip.h, "restricted search"): the complement of the allow bitmap and
+// the items' group labels, in the handle's device memory.
+struct morna_restriction {
+    morna_index *h = nullptr;
+    int32_t device = 0;
+    int64_t n_items = 0;               // the handle's items when it was made: a search checks them
+    int64_t n_allowed = 0, n_grouped = 0;
+    morna::DevBuf<uint32_t> deny;      // [(n_items + 31) / 32], the bits past n_items set
+    morna::DevBuf<int32_t> group;      // [n_items]
+    bool has_group = false;
+};
+
 namespace morna {
 
 // scope timer: records a HIP event pair on the handle's stream around a launch
@@ -408,7 +420,7 @@ int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s
 // packed_dev (device memory, or null): [nq][2k] int32 message of the row-sharded search -- ids + id_offset, distance bits
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
                 int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev = nullptr,
-                int64_t id_offset = 0);
+                int64_t id_offset = 0, const morna_restriction *rst = nullptr, const int32_t *q_group_host = nullptr);
 int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, int64_t nq, int32_t kk, int32_t k,
                    int32_t *ids_out, float *dist_out, int32_t *count_out);
 int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t *ids_out,
@@ -417,7 +429,8 @@ int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t
 // (q_dev64: fp64 queries [nq][dim] in this device's memory, the query rows of morna_build_query_rows)
 int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
                      int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
-                     const double *q_dev64 = nullptr);
+                     const double *q_dev64 = nullptr, const morna_restriction *rst = nullptr,
+                     const int32_t *q_group_host = nullptr);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

@@ -76,6 +76,25 @@ struct QueryParams {
     int64_t big_rows;
 };
 
+// A restriction of one search call (include/morna_hip.h, "restricted search"): item i is eligible for query q iff its
+// deny bit is clear and (g_q < 0 or group[i] != g_q).  Only the *_restricted_kernel forms take it.
+struct RestrictArgs {
+    const uint32_t *deny;      // [(n_items + 31) / 32] complement of the allow bitmap; the bits past n_items are SET
+    const int32_t *group;      // [n_items] label of every item (negative: none), or null
+    const int32_t *q_group;    // [nq] g_q of every query of the launch, or null: every g_q is -1
+};
+
+__device__ inline int32_t restrict_query_group(const RestrictArgs &R, int64_t qi)
+{
+    return R.group && R.q_group ? R.q_group[qi] : -1;
+}
+
+__device__ inline bool restrict_eligible(const RestrictArgs &R, int32_t gq, int64_t i)
+{
+    if ((R.deny[i >> 5] >> (i & 31)) & 1u) return false;
+    return gq < 0 || R.group[i] != gq;
+}
+
 __device__ inline uint64_t pq_key(float d, int32_t node)
 {
     return ((uint64_t)f32_orderable(d) << 32) | (uint32_t)node;
@@ -165,8 +184,10 @@ __device__ inline float wave_dot_held(const float4 *__restrict__ row, const floa
 // ---- traversal: annoy's _get_all_nns up to the candidate set (oracle/annoy_oracle.c:453-504) -------------------
 // One workgroup per query: all root margins (every wave takes trees), then the best-first descent by wave 0 (array
 // priority queue, bitmap de-duplication of the leaves' ids).  Leaves the unique candidates in cand[].
-template <bool BM_LDS>
-__global__ __launch_bounds__(Q_THREADS) void query_traverse_kernel(QueryParams P)
+// RST: the restricted form -- the same pops and the same nn accounting, but the bitmap starts as the complement of the
+// allow-list (an item that is not allowed counts as seen already) and a leaf's ids of the query's own group are passed over.
+template <bool BM_LDS, bool RST>
+__device__ __forceinline__ void query_traverse_body(const QueryParams &P, const RestrictArgs &R)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4 *qv = (float4 *)smem;
@@ -182,9 +203,15 @@ __global__ __launch_bounds__(Q_THREADS) void query_traverse_kernel(QueryParams P
     const float4 *src = P.items ? (const float4 *)(P.X + (int64_t)P.items[qi] * P.dpad)
                                 : (const float4 *)(P.Q + qi * P.dpad);
     for (int i = tid; i < nvec; i += Q_THREADS) qv[i] = src[i];
-    for (int i = tid; i < P.bm_words; i += Q_THREADS) bm[i] = 0u;
+    if constexpr (RST) {
+        for (int i = tid; i < P.bm_words; i += Q_THREADS) bm[i] = R.deny[i];
+    } else {
+        for (int i = tid; i < P.bm_words; i += Q_THREADS) bm[i] = 0u;
+    }
     if (tid == 0) s_ncand = 0;
     __syncthreads();
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(R, qi);
 
     uint64_t *pq = P.pq + qi * P.n_nodes;
     int32_t *cand = P.cand + qi * P.cap;
@@ -236,6 +263,9 @@ __global__ __launch_bounds__(Q_THREADS) void query_traverse_kernel(QueryParams P
                 const int32_t *src_ids = P.perm + (int64_t)P.node_tree[node] * P.n_items + start;
                 for (int i = lane; i < count; i += WAVE) {
                     const int32_t id = src_ids[i];
+                    if constexpr (RST) {
+                        if (gq >= 0 && R.group[id] == gq) continue;
+                    }
                     const uint32_t bit = 1u << (id & 31);
                     const uint32_t old = atomicOr(&bm[id >> 5], bit);
                     if (!(old & bit)) {
@@ -258,6 +288,18 @@ __global__ __launch_bounds__(Q_THREADS) void query_traverse_kernel(QueryParams P
             atomicAdd(P.stat, (unsigned long long)(ndots + (nc < P.cap ? nc : P.cap) + 1));
         }
     }
+}
+
+template <bool BM_LDS>
+__global__ __launch_bounds__(Q_THREADS) void query_traverse_kernel(QueryParams P)
+{
+    query_traverse_body<BM_LDS, false>(P, RestrictArgs());
+}
+
+template <bool BM_LDS>
+__global__ __launch_bounds__(Q_THREADS) void query_traverse_restricted_kernel(QueryParams P, RestrictArgs R)
+{
+    query_traverse_body<BM_LDS, true>(P, R);
 }
 
 // ---- small batches: ONE query spread over the chip ----------------------------------------------------------------
@@ -382,8 +424,10 @@ __device__ inline uint32_t wave_max_u32_fast(uint32_t v)
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-template <bool BM_LDS, int NV>
-__global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
+// RST: the restricted form, as in query_traverse_body; the group test sits in the leaf branch only (the pops' chain does
+// not see it), and the first leaf is always copied: its slice of the permutation is not filtered.
+template <bool BM_LDS, int NV, bool RST>
+__device__ __forceinline__ void query_descend_body(const QueryParams &P, const RestrictArgs &R)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // a queue entry = (bound as an orderable 32-bit word, node); an empty slot has bound word 0 (no real bound maps to 0:
@@ -443,7 +487,13 @@ __global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
     }
     if (!roots_split)
         for (int i = PQ_LDS + lane; i < hn; i += WAVE) gpq[i] = pq_key(INFINITY, i);
-    for (int i = lane; i < P.bm_words; i += WAVE) bm[i] = 0u;
+    int32_t gq = -1;
+    if constexpr (RST) {
+        for (int i = lane; i < P.bm_words; i += WAVE) bm[i] = R.deny[i];
+        gq = restrict_query_group(R, qi);
+    } else {
+        for (int i = lane; i < P.bm_words; i += WAVE) bm[i] = 0u;
+    }
     if (lane == 0) s_ncand = 0;
     __syncthreads();   // (one wave: orders the LDS / global initialisation in front of the loop)
     int ndots = roots_split ? T : 0, n_leaves = 0;
@@ -512,7 +562,9 @@ __global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
             const int4 rec = *(const int4 *)(P.node_rec + 4 * (int64_t)node);
             const int32_t *src_ids = P.perm + (int64_t)P.node_tree[node] * P.n_items + rec.z;
             const int count = rec.w;
-            if (P.zero_copy && n_leaves == 0 && nn + count >= search_k) {
+            bool whole_leaf = false;
+            if constexpr (!RST) whole_leaf = P.zero_copy && n_leaves == 0 && nn + count >= search_k;
+            if (whole_leaf) {
                 // the first leaf ends the search: its ids ARE the candidates -- not copied
                 if (lane == 0) {
                     s_ncand = count;
@@ -525,6 +577,15 @@ __global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
                     for (int u = 0; u < 8; u++) {
                         const int i = base + u * WAVE + lane;
                         idv[u] = i < count ? src_ids[i] : -1;
+                    }
+                    if constexpr (RST) {
+                        if (gq >= 0) {   // uniform; the eight labels in flight together, the own group's ids dropped
+                            int32_t gv[8];
+#pragma unroll
+                            for (int u = 0; u < 8; u++) gv[u] = idv[u] >= 0 ? R.group[idv[u]] : -1;
+#pragma unroll
+                            for (int u = 0; u < 8; u++) idv[u] = gv[u] == gq ? -1 : idv[u];
+                        }
                     }
 #pragma unroll
                     for (int u = 0; u < 8; u++) {
@@ -583,6 +644,18 @@ __global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
     }
 #endif
 #undef TP
+}
+
+template <bool BM_LDS, int NV>
+__global__ __launch_bounds__(WAVE) void query_descend_kernel(QueryParams P)
+{
+    query_descend_body<BM_LDS, NV, false>(P, RestrictArgs());
+}
+
+template <bool BM_LDS, int NV>
+__global__ __launch_bounds__(WAVE) void query_descend_restricted_kernel(QueryParams P, RestrictArgs R)
+{
+    query_descend_body<BM_LDS, NV, true>(P, R);
 }
 
 #define QS_CPW 1   // candidates per wave of query_cand_dots_kernel
@@ -971,8 +1044,26 @@ int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s
 }
 
 // q_host: query vectors in host OR device memory (unified addressing), q_stride floats apart (0 = dim)
+// A restriction a search is about to use: made for this handle and for the rows it holds now.
+static int restriction_usable(const morna_index *h, const morna_restriction *rst)
+{
+    if (rst->h != h) {
+        set_error("the restriction was made for another index handle");
+        return MORNA_E_INVALID;
+    }
+    if (rst->n_items != h->n_items) {
+        set_error("the restriction was made for %lld items, the index now holds %lld: make it again", (long long)rst->n_items,
+                  (long long)h->n_items);
+        return MORNA_E_STATE;
+    }
+    return MORNA_OK;
+}
+
+// rst (or null): the restriction of the call, q_group_host [nq] (or null) the queries' own groups (morna_hip.h, "restricted
+// search"); only the traversal kernels differ, every kernel behind them reads candidate lists.
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
-                int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev, int64_t id_offset)
+                int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev, int64_t id_offset,
+                const morna_restriction *rst, const int32_t *q_group_host)
 {
     if (q_stride <= 0) q_stride = h->dim;
     if (!h->built) {
@@ -987,6 +1078,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         set_error("get_nns: dimension %d is above the supported %d", h->dim, Q_MAX_DPAD);
         return MORNA_E_INVALID;
     }
+    if (rst) MORNA_TRY(restriction_usable(h, rst));
     if (nq == 0) return MORNA_OK;
     if (search_k == -1) search_k = (int32_t)std::min<int64_t>((int64_t)k * h->n_trees, INT32_MAX);
     if (items_host)
@@ -1031,7 +1123,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                  s_bm = bm_lds ? 0 : align_up((size_t)batch * bm_words * 4, 256),
                  s_ids = align_up((size_t)batch * k * 4, 256),
                  s_scores = may_dense ? align_up((size_t)batch * N * 4, 256) : 0;
-    MORNA_TRY(h->ws.alloc(s_pq + s_keys + s_q + s_q16 + 9 * s_qf + 2 * s_cand + s_bm + 2 * s_ids + s_scores));
+    MORNA_TRY(h->ws.alloc(s_pq + s_keys + s_q + s_q16 + 9 * s_qf + 2 * s_cand + s_bm + 2 * s_ids + s_scores + (rst ? s_qf : 0)));
     MORNA_TRY(h->d_stat.alloc(4));
     if (use_filter) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
 
@@ -1055,7 +1147,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         P.ncand = (int32_t *)p; p += s_qf;
         int32_t *d_items = (int32_t *)p; p += s_qf;   // (part of the workspace: a hipMalloc / hipFree per call costs tens of microseconds)
         P.cand_off = (int64_t *)p; p += 2 * s_qf;
-        P.zero_copy = spread ? 1 : 0;
+        P.zero_copy = spread && !rst ? 1 : 0;   // (a restricted call never takes a leaf's slice of perm as its candidates)
         P.cand = (int32_t *)p; p += s_cand;
         P.low = (float *)p; p += s_cand;
         P.bm_global = (uint32_t *)p; p += s_bm;
@@ -1064,6 +1156,16 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         P.dist_out = (float *)p; p += s_ids;
         P.count_out = (int32_t *)p; p += s_qf;
         float *scores = (float *)p; p += s_scores;
+        RestrictArgs R = {nullptr, nullptr, nullptr};
+        if (rst) {
+            R.deny = rst->deny.p;
+            R.group = rst->has_group ? rst->group.p : nullptr;
+            if (R.group && q_group_host) {
+                int32_t *d_qg = (int32_t *)p; p += s_qf;
+                HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+                R.q_group = d_qg;
+            }
+        }
         P.stat = h->d_stat.p;
         P.X16 = nullptr; P.xscale = nullptr; P.xn16 = P.xe16 = nullptr; P.delta = 0.f;
         P.scores = nullptr; P.qscale = P.qn16 = P.qe16 = nullptr; P.eacc = P.eacc_big = 0.f; P.big_rows = 0;
@@ -1119,7 +1221,16 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
             const size_t bl = bm_lds ? (size_t)bm_words * 4 : 0;
 #define DESCEND(NVV)                                                                                                              \
     do {                                                                                                                          \
-        if (bm_lds) {                                                                                                             \
+        if (rst) {                                                                                                                \
+            if (bm_lds) {                                                                                                         \
+                if (bl > 32 * 1024)                                                                                               \
+                    HIP_TRY(hipFuncSetAttribute((const void *)query_descend_restricted_kernel<true, NVV>,                         \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bl));                            \
+                hipLaunchKernelGGL((query_descend_restricted_kernel<true, NVV>), dim3((unsigned)nb), dim3(WAVE), bl, st, P, R);   \
+            } else {                                                                                                              \
+                hipLaunchKernelGGL((query_descend_restricted_kernel<false, NVV>), dim3((unsigned)nb), dim3(WAVE), 0, st, P, R);   \
+            }                                                                                                                     \
+        } else if (bm_lds) {                                                                                                      \
             if (bl > 32 * 1024)                                                                                                   \
                 HIP_TRY(hipFuncSetAttribute((const void *)query_descend_kernel<true, NVV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                             (int)bl));                                                                            \
@@ -1255,6 +1366,16 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 }
 #undef ROOTSB
                 MORNA_TRY(launch_descend(ts));
+            } else if (rst && bm_lds) {
+                if (lds > 48 * 1024)
+                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_restricted_kernel<true>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(query_traverse_restricted_kernel<true>, dim3((unsigned)nb), dim3(Q_THREADS), lds, ts, P, R);
+            } else if (rst) {
+                if (lds_q > 48 * 1024)
+                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_restricted_kernel<false>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
+                hipLaunchKernelGGL(query_traverse_restricted_kernel<false>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, ts, P, R);
             } else if (bm_lds) {
                 if (lds > 48 * 1024)   // query image + sample bitmap can pass the default dynamic-LDS limit
                     HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_kernel<true>,
@@ -1426,18 +1547,40 @@ __global__ __launch_bounds__(256) void exact_scan_kernel(const float *__restrict
 
 // per query: threshold = k-th smallest approx value; candidates = everything within eps of it, and the rows outside the
 // scan's domain (`outs`: their scan values are NaN, so they neither set the threshold nor pass it)
-__global__ __launch_bounds__(256) void exact_select_kernel(const float *__restrict__ approx, int64_t n_items,
-                                                           int32_t k, float eps, int32_t cap,
-                                                           const int32_t *__restrict__ outs, int32_t n_outs,
-                                                           int32_t *__restrict__ cand /* [nq][cap] */,
-                                                           int32_t *__restrict__ ncand_out /* [nq] */)
+// RST: the restricted form.  A row that is not eligible for the query has the scan value NaN, as a row outside the domain
+// has; the rows with a value are then counted per query (kk), and only the eligible rows of `outs` are appended.
+template <bool RST>
+__device__ __forceinline__ void exact_select_body(const float *__restrict__ approx, int64_t n_items,
+                                                  int32_t k, float eps, int32_t cap,
+                                                  const int32_t *__restrict__ outs, int32_t n_outs,
+                                                  int32_t *__restrict__ cand /* [nq][cap] */,
+                                                  int32_t *__restrict__ ncand_out /* [nq] */, const RestrictArgs &R)
 {
     __shared__ uint64_t s_red[Q_WAVES];
     __shared__ int s_n;
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const float *a = approx + qi * n_items;
-    const int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);   // the k-th of the rows with a scan value
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(R, qi);
+    auto value = [&](int64_t i) -> float {   // the scan value of row i as the selection sees it
+        if constexpr (RST) return restrict_eligible(R, gq, i) ? a[i] : __builtin_nanf("");
+        else return a[i];
+    };
+    int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);   // the k-th of the rows with a scan value
+    if constexpr (RST) {
+        __shared__ int s_valid;
+        if (tid == 0) s_valid = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int64_t i = tid; i < n_items; i += 256) {
+            const float v = value(i);
+            mine += v == v ? 1 : 0;
+        }
+        atomicAdd(&s_valid, mine);
+        __syncthreads();
+        kk = k < s_valid ? k : s_valid;
+    }
     uint64_t prev = 0;
     bool have_prev = false;
     constexpr int HELD = 32;   // a shard of up to 8192 rows: the scan values of the query stay in registers for all k rounds
@@ -1446,7 +1589,7 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
 #pragma unroll
         for (int u = 0; u < HELD; u++) {
             const int64_t i = tid + 256 * u;
-            key32[u] = i < n_items ? f32_orderable(a[i]) : 0xffffffffu;
+            key32[u] = i < n_items ? f32_orderable(value(i)) : 0xffffffffu;
         }
         for (int r = 0; r < kk; r++) {
             uint64_t best = ~0ull;
@@ -1463,7 +1606,7 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
         for (int r = 0; r < kk; r++) {
             uint64_t best = ~0ull;
             for (int64_t i = tid; i < n_items; i += 256) {
-                const uint64_t key = ((uint64_t)f32_orderable(a[i]) << 32) | (uint32_t)i;
+                const uint64_t key = ((uint64_t)f32_orderable(value(i)) << 32) | (uint32_t)i;
                 if ((!have_prev || key > prev) && key < best) best = key;
             }
             best = block_min_u64(best, s_red, tid);
@@ -1475,17 +1618,38 @@ __global__ __launch_bounds__(256) void exact_select_kernel(const float *__restri
     if (tid == 0) s_n = 0;
     __syncthreads();
     for (int64_t i = tid; i < n_items; i += 256) {
-        if (a[i] <= thr) {
+        if (value(i) <= thr) {
             int slot = atomicAdd(&s_n, 1);
             if (slot < cap) cand[qi * cap + slot] = (int32_t)i;
         }
     }
     for (int j = tid; j < n_outs; j += 256) {
+        if constexpr (RST) {
+            if (!restrict_eligible(R, gq, outs[j])) continue;
+        }
         const int slot = atomicAdd(&s_n, 1);
         if (slot < cap) cand[qi * cap + slot] = outs[j];
     }
     __syncthreads();
     if (tid == 0) ncand_out[qi] = s_n;   // may exceed cap: the host then retries with more room
+}
+
+__global__ __launch_bounds__(256) void exact_select_kernel(const float *__restrict__ approx, int64_t n_items,
+                                                           int32_t k, float eps, int32_t cap,
+                                                           const int32_t *__restrict__ outs, int32_t n_outs,
+                                                           int32_t *__restrict__ cand /* [nq][cap] */,
+                                                           int32_t *__restrict__ ncand_out /* [nq] */)
+{
+    exact_select_body<false>(approx, n_items, k, eps, cap, outs, n_outs, cand, ncand_out, RestrictArgs());
+}
+
+__global__ __launch_bounds__(256) void exact_select_restricted_kernel(const float *__restrict__ approx, int64_t n_items,
+                                                                      int32_t k, float eps, int32_t cap,
+                                                                      const int32_t *__restrict__ outs, int32_t n_outs,
+                                                                      int32_t *__restrict__ cand /* [nq][cap] */,
+                                                                      int32_t *__restrict__ ncand_out /* [nq] */, RestrictArgs R)
+{
+    exact_select_body<true>(approx, n_items, k, eps, cap, outs, n_outs, cand, ncand_out, R);
 }
 
 // cosine_distance in the reference's order (morna.py:101-114): one thread per candidate walks ITS row front to back in
@@ -1594,11 +1758,14 @@ __global__ __launch_bounds__(RR_THREADS) void exact_rerank_kernel(const float *_
 // and the host retries with room for all of them, as for the candidates themselves.  Needs k <= 256 (one minimum per thread).
 // The rows outside the scan's domain (`outs`, scan value NaN) are appended to the candidates.  When they leave fewer than kk
 // of the 256 minima a value, the bound of A is +inf (B collects every row with a value).
-__global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restrict__ approx, int64_t n_items, int32_t k, float eps,
-                                                            int32_t cap, const int32_t *__restrict__ outs, int32_t n_outs,
-                                                            uint2 *__restrict__ pairs /* [nq][cap] */,
-                                                            int32_t *__restrict__ cand /* [nq][cap] */,
-                                                            int32_t *__restrict__ ncand_out /* [nq] */)
+// RST: the restricted form, as in exact_select_body: a row that is not eligible has the value NaN, the rows with a value
+// are counted in pass A (which reads every value anyway), and a thread's share without an eligible value is a share of NaNs.
+template <bool RST>
+__device__ __forceinline__ void exact_select2_body(const float *__restrict__ approx, int64_t n_items, int32_t k, float eps,
+                                                   int32_t cap, const int32_t *__restrict__ outs, int32_t n_outs,
+                                                   uint2 *__restrict__ pairs /* [nq][cap] */,
+                                                   int32_t *__restrict__ cand /* [nq][cap] */,
+                                                   int32_t *__restrict__ ncand_out /* [nq] */, const RestrictArgs &R)
 {
     __shared__ uint64_t s_key[256];
     __shared__ int s_n;
@@ -1606,22 +1773,58 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const float *a = approx + qi * n_items;
-    const int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);
-    if (kk <= 0) {   // every row is outside the domain
-        if (tid == 0) s_n = 0;
-        __syncthreads();
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(R, qi);
+    auto value = [&](int64_t i) -> float {
+        if constexpr (RST) return restrict_eligible(R, gq, i) ? a[i] : __builtin_nanf("");
+        else return a[i];
+    };
+    auto append_outs = [&]() {
         for (int j = tid; j < n_outs; j += 256) {
+            if constexpr (RST) {
+                if (!restrict_eligible(R, gq, outs[j])) continue;
+            }
             const int slot = atomicAdd(&s_n, 1);
             if (slot < cap) cand[qi * cap + slot] = outs[j];
         }
-        __syncthreads();
-        if (tid == 0) ncand_out[qi] = s_n;
-        return;
-    }
+    };
+    int kk = (int)(k < n_items - n_outs ? k : n_items - n_outs);
     uint64_t mine = ~0ull;
-    for (int64_t i = tid; i < n_items; i += 256) {
-        const uint64_t key = ((uint64_t)f32_orderable(a[i]) << 32) | (uint32_t)i;
-        mine = key < mine ? key : mine;
+    if constexpr (!RST) {
+        if (kk <= 0) {   // every row is outside the domain
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            append_outs();
+            __syncthreads();
+            if (tid == 0) ncand_out[qi] = s_n;
+            return;
+        }
+        for (int64_t i = tid; i < n_items; i += 256) {
+            const uint64_t key = ((uint64_t)f32_orderable(a[i]) << 32) | (uint32_t)i;
+            mine = key < mine ? key : mine;
+        }
+    } else {
+        __shared__ int s_valid;
+        if (tid == 0) s_valid = 0;
+        __syncthreads();
+        int valid = 0;
+        for (int64_t i = tid; i < n_items; i += 256) {
+            const float v = value(i);
+            valid += v == v ? 1 : 0;
+            const uint64_t key = ((uint64_t)f32_orderable(v) << 32) | (uint32_t)i;
+            mine = key < mine ? key : mine;
+        }
+        atomicAdd(&s_valid, valid);
+        __syncthreads();
+        kk = k < s_valid ? k : s_valid;
+        if (kk <= 0) {   // no eligible row has a scan value
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            append_outs();
+            __syncthreads();
+            if (tid == 0) ncand_out[qi] = s_n;
+            return;
+        }
     }
     s_key[tid] = mine;
     if (tid == 0) s_n = 0;
@@ -1636,7 +1839,7 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
     if (bound != bound) bound = INFINITY;   // the kk-th minimum is a NaN: a thread's share held only rows outside the domain
     uint2 *pr = pairs + qi * cap;
     for (int64_t i = tid; i < n_items; i += 256) {
-        const float v = a[i];
+        const float v = value(i);
         if (v <= bound) {
             const int slot = atomicAdd(&s_n, 1);
             if (slot < cap) pr[slot] = make_uint2(f32_orderable(v), (uint32_t)i);
@@ -1667,12 +1870,27 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restr
         const uint2 p = pr[t];
         if (f32_from_orderable(p.x) <= thr) cand[qi * cap + atomicAdd(&s_n, 1)] = (int32_t)p.y;
     }
-    for (int j = tid; j < n_outs; j += 256) {
-        const int slot = atomicAdd(&s_n, 1);
-        if (slot < cap) cand[qi * cap + slot] = outs[j];
-    }
+    append_outs();
     __syncthreads();
     if (tid == 0) ncand_out[qi] = s_n;
+}
+
+__global__ __launch_bounds__(256) void exact_select2_kernel(const float *__restrict__ approx, int64_t n_items, int32_t k, float eps,
+                                                            int32_t cap, const int32_t *__restrict__ outs, int32_t n_outs,
+                                                            uint2 *__restrict__ pairs /* [nq][cap] */,
+                                                            int32_t *__restrict__ cand /* [nq][cap] */,
+                                                            int32_t *__restrict__ ncand_out /* [nq] */)
+{
+    exact_select2_body<false>(approx, n_items, k, eps, cap, outs, n_outs, pairs, cand, ncand_out, RestrictArgs());
+}
+
+__global__ __launch_bounds__(256) void exact_select2_restricted_kernel(const float *__restrict__ approx, int64_t n_items, int32_t k,
+                                                                       float eps, int32_t cap, const int32_t *__restrict__ outs,
+                                                                       int32_t n_outs, uint2 *__restrict__ pairs /* [nq][cap] */,
+                                                                       int32_t *__restrict__ cand /* [nq][cap] */,
+                                                                       int32_t *__restrict__ ncand_out /* [nq] */, RestrictArgs R)
+{
+    exact_select2_body<true>(approx, n_items, k, eps, cap, outs, n_outs, pairs, cand, ncand_out, R);
 }
 
 // The query of exact_search_nn when it is a STORED row (or an fp32 row handed over in device memory): the fp32 values
@@ -1958,9 +2176,10 @@ size_t exact_msg_bytes(int64_t nq, int32_t k) { return exact_msg_dist_offset(nq,
 // then only enqueued on the handle's stream behind the last selection.
 int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
                      int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
-                     const double *q_dev64)
+                     const double *q_dev64, const morna_restriction *rst, const int32_t *q_group_host)
 {
     MORNA_TRY(upload_host_rows(h));
+    if (rst) MORNA_TRY(restriction_usable(h, rst));
     if (h->n_items <= 0) {
         set_error("exact search on an empty index");
         return MORNA_E_EMPTY;
@@ -2006,7 +2225,7 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     const size_t s_qd = align_up((size_t)batch * D * 8, 256), s_qf = align_up((size_t)batch * dpad * 4, 256),
                  s_b4 = align_up((size_t)batch * 4, 256), s_ap = align_up((size_t)batch * N * 4, 256),
                  s_ids = align_up((size_t)batch * k * 4, 256), s_dist = align_up((size_t)batch * k * 8, 256);
-    MORNA_TRY(h->ex_ws.alloc(s_qd + s_qf + 4 * s_b4 + s_ap + s_ids + s_dist));
+    MORNA_TRY(h->ex_ws.alloc(s_qd + s_qf + 4 * s_b4 + s_ap + s_ids + s_dist + (rst ? s_b4 : 0)));
     uint8_t *p = h->ex_ws.p;
     double *Qd = (double *)p; p += s_qd;
     float *Qf = (float *)p; p += s_qf;
@@ -2018,10 +2237,19 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     int32_t *d_ids = (int32_t *)p; p += s_ids;
     double *d_dist = (double *)p; p += s_dist;
     int32_t *d_cnt = (int32_t *)p; p += s_b4;
+    RestrictArgs R = {nullptr, nullptr, nullptr};
+    int32_t *d_qg = nullptr;
+    if (rst) {
+        R.deny = rst->deny.p;
+        R.group = rst->has_group ? rst->group.p : nullptr;
+        if (R.group && q_group_host) { d_qg = (int32_t *)p; p += s_b4; }
+        R.q_group = d_qg;
+    }
     std::vector<int32_t> h_ncand((size_t)batch);
     int32_t cap = std::max<int32_t>(std::max(64, 4 * k) + n_outs, h->ex_cap), need_max = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += batch) {
         const int64_t nb = std::min(batch, nq - q0);
+        if (d_qg) HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
         if (q_host) {
             HIP_TRY(hipMemcpyAsync(Qd, q_host + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
         } else if (q_dev) {
@@ -2058,7 +2286,13 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
         for (;;) {
             MORNA_TRY(h->ex_cand.alloc((size_t)batch * cap));
             MORNA_TRY(h->ex_cdist.alloc((size_t)batch * cap));
-            if (N > 8192 && k <= 256 && select2_on)
+            if (rst && N > 8192 && k <= 256 && select2_on)
+                hipLaunchKernelGGL(exact_select2_restricted_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, approx, N, k, eps, cap,
+                                   outs, n_outs, (uint2 *)h->ex_cdist.p, h->ex_cand.p, ncand, R);
+            else if (rst)
+                hipLaunchKernelGGL(exact_select_restricted_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, approx, N, k, eps,
+                                   cap, outs, n_outs, h->ex_cand.p, ncand, R);
+            else if (N > 8192 && k <= 256 && select2_on)
                 hipLaunchKernelGGL(exact_select2_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, approx, N, k, eps, cap,
                                    outs, n_outs, (uint2 *)h->ex_cdist.p, h->ex_cand.p, ncand);
             else

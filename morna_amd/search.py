@@ -40,6 +40,74 @@ def results_output(results, out=None):
         out.write("\n")
 
 
+INT32_MAX = 2**31 - 1
+
+SHARDS_REFUSAL = ("restricted search (--within, --without, --leave-out-groups) is not available on an index of row shards "
+                  "(.shards.mor, one process per shard, --device a,b): run it on an index built without --shards")
+
+
+def restriction_arrays(internal_id_map, n_items, within=None, without=None, groups=None):
+    """The host side of MornaSearch.restriction: EXTERNAL sample ids -> (allow, item_group, n_groups) over the n_items
+    internal ids.  allow: booleans [n_items] -- `within` (None: every item) less `without` -- or None when neither is
+    given; item_group: int32 [n_items], the position of an item's group in `groups` ([(label, [ids])]) or -1, or None when
+    groups is None.  ValueError naming the id for an id the index lacks, and for an id in two groups."""
+    def internal(sample_id, what):
+        if sample_id not in internal_id_map:
+            raise ValueError("%s names sample id %s, which is not in the index" % (what, sample_id))
+        i = internal_id_map[sample_id]
+        if not 0 <= i < n_items:
+            raise ValueError("%s names sample id %s, whose internal id %d is outside the index's %d items"
+                             % (what, sample_id, i, n_items))
+        return i
+    allow = None
+    if within is not None or without is not None:
+        allow = np.ones(n_items, bool)
+        if within is not None:
+            allow[:] = False
+            for sample_id in within:
+                allow[internal(sample_id, "within")] = True
+        for sample_id in (without or ()):
+            allow[internal(sample_id, "without")] = False
+    item_group, n_groups = None, 0
+    if groups is not None:
+        groups = list(groups)
+        n_groups = len(groups)
+        item_group = np.full(n_items, -1, np.int32)
+        for g, (label, ids) in enumerate(groups):
+            for sample_id in ids:
+                i = internal(sample_id, "group %s" % label)
+                if item_group[i] >= 0 and item_group[i] != g:
+                    raise ValueError("sample id %s is in two groups, %s and %s" % (sample_id, groups[item_group[i]][0], label))
+                item_group[i] = g
+    return allow, item_group, n_groups
+
+
+def restricted_search_k(n_trees, k, n_items, n_allowed):
+    """The default search_k of a search under an allow-list: annoy's n_trees * k scaled by ceil(n / n_allowed), so that the
+    traversal collects about as many ALLOWED candidates as the unrestricted default collects candidates; at most 2^31 - 1.
+    (A deliberate departure from annoy's default; an explicit search_k is taken as given.)"""
+    scale = -(-int(n_items) // max(int(n_allowed), 1))
+    return min(int(n_trees) * int(k) * scale, INT32_MAX)
+
+
+class SearchRestriction(object):
+    """MornaSearch.restriction: allow (booleans [n] or None), item_group (int32 [n] or None), the counts, and `handle`,
+    the annoy.Restriction on the index's device."""
+
+    def __init__(self, owner, handle, allow, item_group, n_groups):
+        self.owner, self.handle, self.allow, self.item_group, self.n_groups = owner, handle, allow, item_group, n_groups
+        self.n_items, self.n_allowed = handle.n_items, handle.n_allowed
+
+    def summary(self):
+        return "restriction: %d of %d samples allowed, %d leave-out groups" % (self.n_allowed, self.n_items, self.n_groups)
+
+    def own_groups(self, internal_ids):
+        """g_q of by-member queries: every query carries its own item's label (None without groups)."""
+        if self.item_group is None:
+            return None
+        return self.item_group[np.asarray(internal_ids, np.int64)]
+
+
 class QueryBatch(object):
     """The query samples of an intropolis file featurised against an index (MornaSearch.queries_from_intropolis):
     ext_ids[q] is the sample id of query q (first appearance in the file), n the number of queries.  The rows live on
@@ -119,8 +187,14 @@ class MornaSearch(object):
         sample_ids = [self.inverse_lookup(internal_id) for internal_id in results[0]]
         return results + (lookup_meta(self.basename, sample_ids),)
 
-    def search_nn(self, num_neighbors, search_k, include_distances=True, meta_db=False):
-        """Approximate neighbours of query_sample (morna.py:632-678)."""
+    def search_nn(self, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None):
+        """Approximate neighbours of query_sample (morna.py:632-678); restriction: MornaSearch.restriction."""
+        if restriction is not None:
+            self._check_restriction(restriction, None)
+            ids, d, cnt = self.annoy_index.get_nns_restricted(
+                restriction.handle, num_neighbors, self._restricted_search_k(restriction, num_neighbors, search_k),
+                Q=np.array([self.query_sample], dtype=np.float32))
+            return self._batch_results(ids, d, cnt, include_distances, meta_db)[0]
         if include_distances:
             results = self.annoy_index.get_nns_by_vector([feature for feature in self.query_sample],
                                                          num_neighbors, search_k, include_distances)
@@ -129,10 +203,15 @@ class MornaSearch(object):
                                                           num_neighbors, search_k, include_distances),)
         return self._with_meta(results, meta_db)
 
-    def exact_search_nn(self, num_neighbors, include_distances=True, meta_db=False):
-        """Brute-force neighbours with cosine_distance (morna.py:681-730)."""
-        ids, d, cnt = self.annoy_index.exact_search_batch(np.array([self.query_sample], dtype=np.float64),
-                                                          num_neighbors)
+    def exact_search_nn(self, num_neighbors, include_distances=True, meta_db=False, restriction=None):
+        """Brute-force neighbours with cosine_distance (morna.py:681-730); restriction: MornaSearch.restriction."""
+        if restriction is not None:
+            self._check_restriction(restriction, None)
+            ids, d, cnt = self.annoy_index.exact_search_restricted(restriction.handle, num_neighbors,
+                                                                   Q=np.array([self.query_sample], dtype=np.float64))
+        else:
+            ids, d, cnt = self.annoy_index.exact_search_batch(np.array([self.query_sample], dtype=np.float64),
+                                                              num_neighbors)
         m = int(cnt[0])
         if m < 0:
             # some indexed row gives cosine_distance a negative radicand: the reference's math.sqrt raises while it
@@ -216,28 +295,81 @@ class MornaSearch(object):
             out.append(results)
         return out
 
-    def search_nn_batch(self, batch, num_neighbors, search_k, include_distances=True, meta_db=False):
-        """search_nn for every query of `batch`: a list of result tuples, in query order."""
+    # ---- restricted search -------------------------------------------------------------------
+    def restriction(self, within=None, without=None, groups=None):
+        """A SearchRestriction for the *_batch searches' restriction=: EXTERNAL sample ids.  The searches answer only with
+        the samples of `within` (None: all) that are not in `without`; groups, [(label, [ids])] as parse_groups_file returns
+        it, are leave-out groups: a query that carries a group (query_groups=, or a by-member query's own) gets no member of
+        it back.  ValueError for an id the index lacks, for an id in two groups, and on an index of row shards."""
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(SHARDS_REFUSAL)
+        n = self.annoy_index.get_n_items()
+        allow, item_group, n_groups = restriction_arrays(self.internal_id_map, n, within, without, groups)
+        return SearchRestriction(self, self.annoy_index.restriction(allow, item_group), allow, item_group, n_groups)
+
+    def _check_restriction(self, restriction, query_groups):
+        if restriction is None:
+            if query_groups is not None:
+                raise ValueError("query_groups needs a restriction made with groups")
+            return
+        if not isinstance(restriction, SearchRestriction) or restriction.owner is not self:
+            raise ValueError("the restriction was not made by this MornaSearch (MornaSearch.restriction)")
+
+    def _restricted_search_k(self, restriction, num_neighbors, search_k):
+        """search_k None or -1 under an allow-list: restricted_search_k; anything else as given."""
+        if search_k is None or search_k == -1:
+            if restriction.allow is None:
+                return -1
+            return restricted_search_k(self.annoy_index.get_n_trees(), num_neighbors, restriction.n_items, restriction.n_allowed)
+        return search_k
+
+    def _unhashed_population_of(self, restriction):
+        """_unhashed_population narrowed to the allowed samples (the unhashed search takes its population from the host)."""
+        pop = self._unhashed_population()
+        if restriction is None or restriction.allow is None:
+            return pop
+        self._check_restriction(restriction, None)
+        return pop[restriction.allow]
+
+    def search_nn_batch(self, batch, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None,
+                        query_groups=None):
+        """search_nn for every query of `batch`: a list of result tuples, in query order.  restriction / query_groups:
+        MornaSearch.restriction and the group label every query carries (positions in its groups, negative: none)."""
         self._check_batch(batch)
+        self._check_restriction(restriction, query_groups)
+        if restriction is not None:
+            ids, d, cnt = self.annoy_index.get_nns_restricted(
+                restriction.handle, num_neighbors, self._restricted_search_k(restriction, num_neighbors, search_k),
+                query_groups=query_groups)
+            return self._batch_results(ids, d, cnt, include_distances, meta_db)
         if batch.rows32 is not None:
             ids, d, cnt = self.annoy_index.get_nns_by_vector_batch(batch.rows32, num_neighbors, search_k)
         else:
             ids, d, cnt = self.annoy_index.get_nns_by_query_rows(num_neighbors, search_k)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
-    def exact_search_nn_batch(self, batch, num_neighbors, include_distances=True, meta_db=False):
+    def exact_search_nn_batch(self, batch, num_neighbors, include_distances=True, meta_db=False, restriction=None,
+                              query_groups=None):
         """exact_search_nn for every query of `batch`: a list of result tuples, in query order; a query the reference
-        would raise on gets a ValueError instance in its slot."""
+        would raise on gets a ValueError instance in its slot.  restriction / query_groups: as search_nn_batch; the answer
+        is then the reference's on an index of the eligible samples only."""
         self._check_batch(batch)
+        self._check_restriction(restriction, query_groups)
+        if restriction is not None:
+            ids, d, cnt = self.annoy_index.exact_search_restricted(restriction.handle, num_neighbors, query_groups=query_groups)
+            return self._batch_results(ids, d, cnt, include_distances, meta_db)
         if batch.rows64 is not None:
             ids, d, cnt = self.annoy_index.exact_search_batch(batch.rows64, num_neighbors)
         else:
             ids, d, cnt = self.annoy_index.exact_search_query_rows(num_neighbors)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
-    def search_member_n_batch(self, query_ids, num_neighbors, search_k, include_distances=True, meta_db=False):
+    def search_member_n_batch(self, query_ids, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None,
+                              query_groups=None):
         """search_member_n for several indexed sample ids, searched together (get_nns_by_item_batch); an unknown id fails
-        before any search, with search_member_n's message.  Returns (internal ids, list of result tuples)."""
+        before any search, with search_member_n's message.  Returns (internal ids, list of result tuples).  restriction:
+        MornaSearch.restriction; query_groups None under a restriction with groups: every query carries its own sample's
+        group."""
         from .shards import DistShards
         if isinstance(self.annoy_index, DistShards):
             raise RuntimeError("batch search is not available with one process per shard (torchrun): "
@@ -250,6 +382,14 @@ class MornaSearch(object):
                                  + "sample id. Likely no sample with that id was included "
                                  + "in the index.")
             internal.append(self.internal_id_map[query_id])
+        self._check_restriction(restriction, query_groups)
+        if restriction is not None:
+            if query_groups is None:
+                query_groups = restriction.own_groups(internal)
+            ids, d, cnt = self.annoy_index.get_nns_restricted(
+                restriction.handle, num_neighbors, self._restricted_search_k(restriction, num_neighbors, search_k),
+                items=np.array(internal, np.int32), query_groups=query_groups)
+            return internal, self._batch_results(ids, d, cnt, include_distances, meta_db)
         ids, d, cnt = self.annoy_index.get_nns_by_item_batch(np.array(internal, np.int32), num_neighbors, search_k)
         return internal, self._batch_results(ids, d, cnt, include_distances, meta_db)
 
@@ -420,7 +560,17 @@ class MornaSearch(object):
         inv = self._inverse_map()
         return np.array([inv[i] for i in range(len(inv))], np.int64)
 
-    def unhashed_search_member_n_batch(self, query_ids, num_neighbors, include_distances=True, meta_db=False):
+    @staticmethod
+    def _unhashed_ids(ids, restriction):
+        """Positions in a narrowed population back to internal ids (-1 stays -1)."""
+        if restriction is None or restriction.allow is None:
+            return ids
+        at = np.nonzero(restriction.allow)[0].astype(np.int32)
+        if len(at) == 0:
+            return np.full_like(ids, -1)
+        return np.where(ids >= 0, at[np.clip(ids, 0, len(at) - 1)], -1).astype(np.int32)
+
+    def unhashed_search_member_n_batch(self, query_ids, num_neighbors, include_distances=True, meta_db=False, restriction=None):
         """The unhashed neighbours of several indexed sample ids: a list of result tuples in query order, as
         exact_search_nn_batch returns them (internal ids); an unknown id fails with search_member_n's message."""
         for query_id in query_ids:
@@ -430,14 +580,16 @@ class MornaSearch(object):
                                  + "sample id. Likely no sample with that id was included "
                                  + "in the index.")
         store, _ = self.unhashed_store()
-        ids, d, cnt = store.nearest_by_sample(self._unhashed_population(), [int(q) for q in query_ids], num_neighbors)
+        ids, d, cnt = store.nearest_by_sample(self._unhashed_population_of(restriction), [int(q) for q in query_ids], num_neighbors)
+        ids = self._unhashed_ids(ids, restriction)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
-    def unhashed_search_nn_batch(self, term_lists, num_neighbors, include_distances=True, meta_db=False):
+    def unhashed_search_nn_batch(self, term_lists, num_neighbors, include_distances=True, meta_db=False, restriction=None):
         """The unhashed neighbours of queries given as (lines ascending, coverages) pairs over the lines of the indexed
         file (junctions.query_terms / intropolis_query_terms): a list of result tuples in query order."""
         store, _ = self.unhashed_store()
-        ids, d, cnt = store.nearest(self._unhashed_population(), term_lists, num_neighbors)
+        ids, d, cnt = store.nearest(self._unhashed_population_of(restriction), term_lists, num_neighbors)
+        ids = self._unhashed_ids(ids, restriction)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
     def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False):

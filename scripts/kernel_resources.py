@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from morna_amd.build import FLAGS  # noqa: E402
 
-FIELDS = ["VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
+FIELDS = ["VGPRs", "AGPRs", "SGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
           "LDS Size [bytes/block]"]
 
 
@@ -39,13 +39,13 @@ def main():
                 cur[f] = int(m.group(1))
     if name:
         rows.append((name, cur))
-    print("%-60s %5s %5s %7s %4s %6s %6s %7s" % ("kernel", "VGPR", "AGPR", "scratch", "occ", "sSpill", "vSpill", "LDS"))
+    print("%-60s %5s %5s %5s %7s %4s %6s %6s %7s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "sSpill", "vSpill", "LDS"))
     for name, cur in rows:
         short = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip()
         short = re.sub(r"\(.*", "", short.replace("(anonymous namespace)::", "")).replace("morna::", "").replace("void ", "")
         if want not in short:
             continue
-        print("%-60s %5d %5d %7d %4d %6d %6d %7d" % tuple([short[:60]] + [cur.get(f, -1) for f in FIELDS]))
+        print("%-60s %5d %5d %5d %7d %4d %6d %6d %7d" % tuple([short[:60]] + [cur.get(f, -1) for f in FIELDS]))
 
 
 if __name__ == "__main__":
