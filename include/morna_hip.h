@@ -482,6 +482,53 @@ int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, co
                                   const int32_t *q_group, int32_t k, int32_t *ids, double *dist, int32_t *count);
 
 /*
+ * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
+ * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
+ * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the
+ * forest is cut to its first t trees; so the searches below answer, from ONE built index, what an index built with
+ * n_trees = t on the same rows and seed would answer: the same ids, fp32 distance bytes and counts.
+ *   morna_get_nns_prefix  morna_get_nns_by_vector / _by_item / _by_query_rows (q, or items, or both NULL: the staged
+ *       query rows, as below; q and items together: MORNA_E_INVALID) over the first n_trees_used trees.  search_k = -1 is k * n_trees_used.  n_trees_used = the forest's tree
+ *       count is the plain call.  n_trees_used < 1 or above the forest's: MORNA_E_RANGE naming both numbers.  An index
+ *       that is not built: MORNA_E_STATE.
+ *   morna_search_sweep    every cell of trees[n_t] x search_ks[n_s] at once.  Both lists strictly ascending and positive,
+ *       1 <= n_t, n_s <= 64 (MORNA_E_INVALID naming the entry or the limit; -1 is not accepted in search_ks: the caller
+ *       writes k * t itself), trees[n_t - 1] at most the forest's tree count (MORNA_E_RANGE naming both numbers).
+ *       Outputs, host memory, each may be NULL and is then not copied: ids_out / dist_out [n_t][n_s][nq][k], count_out /
+ *       ncand_out / ndots_out [n_t][n_s][nq].  Cell (i, j, q) equals morna_get_nns_prefix with n_trees_used = trees[i] and
+ *       search_k = search_ks[j] for query q in ids, distance bytes and count; ncand is that call's number of unique
+ *       candidates, ndots its number of hyperplane dots, the trees[i] root dots included (0 of them when the roots are
+ *       leaves).  The work: the queries are staged and the root margins taken once per batch, one descent runs per
+ *       (query, tree count) to the largest search_k and records where every smaller one stops, every candidate of the
+ *       deepest lists gets its canonical dot once, and each cell ranks a prefix of those keys.  A batch that
+ *       morna_get_nns_by_* would send through the whole-batch fp16 contraction gets that contraction, once: the canonical
+ *       dots are then taken only for the candidates that the fp16 filter of some cell lets through.
+ *   morna_recall_sweep    the sweep beside ONE exact search of the same queries (morna_exact_search of the fp32 queries
+ *       widened to fp64, or morna_exact_search_by_item), 1 <= k <= MORNA_RECALL_MAX_K (MORNA_E_INVALID naming the limit).
+ *       hits_out [n_t][n_s][nq] (required) = the number of ids cell (i, j, q) shares with the exact answer of q, counted on
+ *       the device; -1 in every cell of a query whose exact count is -1 (morna_exact_search).  exact_count_out [nq],
+ *       exact_ids_out [nq][k] and the sweep's outputs may each be NULL.
+ *   Query sources of the prefix call and the two sweeps: q ([nq][dim] fp32), or items ([nq] stored rows), or both NULL: the staged query rows
+ *       of morna_build_query_rows (nq must be their count; the exact search then takes their fp64 rows, as
+ *       morna_exact_search_query_rows does).  q and items together: MORNA_E_INVALID.
+ *   morna_search_sweep_stats  of the last sweep or recall sweep, stats[4]: descents run (queries x tree counts), cells
+ *       answered, rows read by canonical candidate dots, whether the whole-batch fp16 contraction ran (0 or 1).  All 0
+ *       after a call with nq = 0 or one that failed its checks.
+ */
+#define MORNA_SWEEP_MAX_LIST 64
+#define MORNA_RECALL_MAX_K 256
+int morna_get_nns_prefix(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, int32_t search_k,
+                         int32_t n_trees_used, int32_t *ids, float *dist, int32_t *count);
+int morna_search_sweep(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, const int32_t *trees,
+                       int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out, int32_t *count_out,
+                       int32_t *ncand_out, int32_t *ndots_out);
+int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, const int32_t *trees,
+                       int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *hits_out, int32_t *exact_count_out,
+                       int32_t *ncand_out, int32_t *ndots_out, int32_t *ids_out, float *dist_out, int32_t *count_out,
+                       int32_t *exact_ids_out);
+int morna_search_sweep_stats(const morna_index *h, double *stats);
+
+/*
  * Row-sharded search (one handle per GPU; the reference has no such path): merge of the
  * per-shard answers to the same queries after their all-gather.  ids / dist: [world][nq][kk], each
  * [kk] list as get_nns_* returns it -- ascending (distance, id), empty slots id -1 last -- with ids

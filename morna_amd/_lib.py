@@ -113,6 +113,10 @@ SIGNATURES = {
     "morna_restriction_free": (C.c_int, [_p]),
     "morna_get_nns_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p]),
     "morna_exact_search_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _p, _p, _p]),
+    "morna_get_nns_prefix": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
+    "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "morna_search_sweep_stats": (C.c_int, [_p, _p]),
     "morna_comm_unique_id": (C.c_int, [_p]),
     "morna_comm_init": (C.c_int, [_p, _p, _i32, _i32]),
     "morna_comm_destroy": (C.c_int, [_p]),

@@ -206,7 +206,9 @@ class AnnoyIndex(object):
         return dict(node_rec=rec, perm=perm, hyperplanes=hp[:st["n_split"]], hp_node=hp_node[:st["n_split"]])
 
     # ---- search ------------------------------------------------------------
-    def get_nns_by_vector_batch(self, Q, n, search_k=-1):
+    def get_nns_by_vector_batch(self, Q, n, search_k=-1, n_trees=None):
+        """n_trees: search the first n_trees trees only (morna_get_nns_prefix): the answer of an index built with that
+        many trees on the same rows and seed; None: the whole forest."""
         Q = np.ascontiguousarray(Q, dtype=np.float32)
         if Q.ndim != 2 or Q.shape[1] != self.f:
             raise IndexError("queries must be [nq, %d]" % self.f)
@@ -214,31 +216,98 @@ class AnnoyIndex(object):
         ids = np.empty((nq, n), np.int32)
         d = np.empty((nq, n), np.float32)
         cnt = np.empty(nq, np.int32)
+        if n_trees is not None:
+            check(lib().morna_get_nns_prefix(self._h, ptr(Q), None, nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
+                                             ptr(cnt)))
+            return ids, d, cnt
         check(lib().morna_get_nns_by_vector(self._h, ptr(Q), nq, int(n), int(search_k), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
-    def get_nns_by_item_batch(self, items, n, search_k=-1):
+    def get_nns_by_item_batch(self, items, n, search_k=-1, n_trees=None):
+        """n_trees: as get_nns_by_vector_batch."""
         items = np.ascontiguousarray(items, dtype=np.int32)
         nq = items.shape[0]
         ids = np.empty((nq, n), np.int32)
         d = np.empty((nq, n), np.float32)
         cnt = np.empty(nq, np.int32)
+        if n_trees is not None:
+            check(lib().morna_get_nns_prefix(self._h, None, ptr(items), nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
+                                             ptr(cnt)))
+            return ids, d, cnt
         check(lib().morna_get_nns_by_item(self._h, ptr(items), nq, int(n), int(search_k), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
-    def get_nns_by_vector(self, vector, n, search_k=-1, include_distances=False):
+    def get_nns_by_vector(self, vector, n, search_k=-1, include_distances=False, n_trees=None):
         v = np.ascontiguousarray(vector, dtype=np.float32)   # annoy stores/queries fp32
         if v.shape != (self.f,):
             raise IndexError("Vector has wrong length (expected %d, got %d)" % (self.f, v.size))
-        ids, d, cnt = self.get_nns_by_vector_batch(v[None, :], n, search_k)
+        ids, d, cnt = self.get_nns_by_vector_batch(v[None, :], n, search_k, n_trees=n_trees)
         m = int(cnt[0])
         out = [int(x) for x in ids[0, :m]]
         if include_distances:
             return out, [float(x) for x in d[0, :m]]
         return out
 
-    def get_nns_by_item(self, i, n, search_k=-1, include_distances=False):
-        ids, d, cnt = self.get_nns_by_item_batch(np.array([i], np.int32), n, search_k)
+    def _sweep_args(self, trees, search_ks, Q, items):
+        if Q is not None and items is not None:
+            raise ValueError("give query vectors or items, not both")
+        if Q is None and items is None:
+            nq = getattr(self, "_qrows_n", 0)          # the staged query rows (build_query_rows)
+        elif Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=np.float32)
+            if Q.ndim != 2 or Q.shape[1] != self.f:
+                raise IndexError("queries must be [nq, %d]" % self.f)
+            nq = Q.shape[0]
+        else:
+            items = np.ascontiguousarray(items, dtype=np.int32)
+            if items.ndim != 1:
+                raise ValueError("items must be one-dimensional")
+            nq = items.shape[0]
+        trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
+        search_ks = np.ascontiguousarray(search_ks, dtype=np.int32).reshape(-1)
+        return Q, items, nq, trees, search_ks
+
+    def search_sweep(self, n, trees, search_ks, Q=None, items=None, lists=True):
+        """Every cell of trees x search_ks from this one forest (morna_search_sweep), for the query vectors Q, the stored
+        rows `items`, or (neither) the rows of build_query_rows: cell (i, j) is what
+        get_nns_*_batch(..., n, search_ks[j], n_trees=trees[i]) answers.  Both lists strictly ascending and positive, at
+        most 64 entries.  Returns a dict: ids / dist [n_t, n_s, nq, n] and count [n_t, n_s, nq] (lists=False: left out and
+        not copied), ncand and ndots [n_t, n_s, nq] (unique candidates and hyperplane dots of every cell)."""
+        Q, items, nq, trees, search_ks = self._sweep_args(trees, search_ks, Q, items)
+        shape = (len(trees), len(search_ks), nq)
+        out = dict(ncand=np.empty(shape, np.int32), ndots=np.empty(shape, np.int32))
+        if lists:
+            out.update(ids=np.empty(shape + (n,), np.int32), dist=np.empty(shape + (n,), np.float32), count=np.empty(shape, np.int32))
+        check(lib().morna_search_sweep(self._h, ptr(Q), ptr(items), nq, int(n), ptr(trees), len(trees), ptr(search_ks),
+                                       len(search_ks), ptr(out.get("ids")), ptr(out.get("dist")), ptr(out.get("count")),
+                                       ptr(out["ncand"]), ptr(out["ndots"])))
+        return out
+
+    def recall_sweep(self, n, trees, search_ks, Q=None, items=None, lists=False):
+        """search_sweep beside one exact search of the same queries (morna_recall_sweep; n <= 256): hits [n_t, n_s, nq], the
+        ids every cell shares with the exact answer (-1: the exact search failed for the query, exact_count -1),
+        exact_count [nq], ncand, ndots; lists=True adds ids / dist / count and exact_ids [nq, n]."""
+        Q, items, nq, trees, search_ks = self._sweep_args(trees, search_ks, Q, items)
+        shape = (len(trees), len(search_ks), nq)
+        out = dict(hits=np.empty(shape, np.int32), exact_count=np.empty(nq, np.int32), ncand=np.empty(shape, np.int32),
+                   ndots=np.empty(shape, np.int32))
+        if lists:
+            out.update(ids=np.empty(shape + (n,), np.int32), dist=np.empty(shape + (n,), np.float32), count=np.empty(shape, np.int32),
+                       exact_ids=np.empty((nq, n), np.int32))
+        check(lib().morna_recall_sweep(self._h, ptr(Q), ptr(items), nq, int(n), ptr(trees), len(trees), ptr(search_ks),
+                                       len(search_ks), ptr(out["hits"]), ptr(out["exact_count"]), ptr(out["ncand"]),
+                                       ptr(out["ndots"]), ptr(out.get("ids")), ptr(out.get("dist")), ptr(out.get("count")),
+                                       ptr(out.get("exact_ids"))))
+        return out
+
+    def sweep_stats(self):
+        """Of the last search_sweep / recall_sweep: descents, cells, rows read by canonical dots, contraction (0 / 1)."""
+        st = np.zeros(4, np.float64)
+        check(lib().morna_search_sweep_stats(self._h, ptr(st)))
+        return dict(descents=int(st[0]), cells=int(st[1]), rows_canonical=int(st[2]), contraction=int(st[3]))
+
+    def get_nns_by_item(self, i, n, search_k=-1, include_distances=False, n_trees=None):
+        ids, d, cnt = self.get_nns_by_item_batch(np.array([i], np.int32), n, search_k, n_trees=n_trees)
         m = int(cnt[0])
         out = [int(x) for x in ids[0, :m]]
         if include_distances:
@@ -351,12 +420,16 @@ class AnnoyIndex(object):
         check(lib().morna_get_query_rows(self._h, ptr(r64), ptr(r32)))
         return r64, r32
 
-    def get_nns_by_query_rows(self, n, search_k=-1):
-        """get_nns_by_vector_batch with the resident fp32 query rows as the queries."""
+    def get_nns_by_query_rows(self, n, search_k=-1, n_trees=None):
+        """get_nns_by_vector_batch with the resident fp32 query rows as the queries; n_trees: as there."""
         nq = getattr(self, "_qrows_n", 0)
         ids = np.empty((nq, n), np.int32)
         d = np.empty((nq, n), np.float32)
         cnt = np.empty(nq, np.int32)
+        if n_trees is not None:
+            check(lib().morna_get_nns_prefix(self._h, None, None, nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
+                                             ptr(cnt)))
+            return ids, d, cnt
         check(lib().morna_get_nns_by_query_rows(self._h, int(n), int(search_k), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 

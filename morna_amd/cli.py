@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -50,6 +50,13 @@ query included, and `recovery` then asks for exactly -r results instead of -r + 
 themselves are restricted on the GPU; the output format is unchanged, one line on stderr says what the
 restriction holds.  Without --search-k an allow-list searches with n_trees * r * ceil(n / n_allowed) instead of 100.
 
+`recall` answers what --n-trees and --search-k buy on an index: for every pair of --trees x --search-ks it prints how many of
+the exact search's -r results the approximate search over the first t trees with that search_k returns, with the candidates
+and hyperplane dots it spent, per query and over all queries -- the comparison experiment 3 of the reference's tests/README.md
+makes by eye from five indexes and fifty result files.  One index, one exact search and one sweep on the GPU (DESIGN.md 8,
+N11): tree i of a forest does not depend on the trees behind it, so the first t trees of the index ARE the index --n-trees t
+builds.  `search --use-trees t` searches with those trees alone.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -72,6 +79,8 @@ here do the latter.
     python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --downsample 0.5,0.1,0.01 --junction-file junctions.tsv.gz --lost-only
     python -m morna_amd.cli search -x idx --intropolis new_samples.tsv.gz --within gtex_ids.txt -e -d
     python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --leave-out-groups donors.tsv
+    python -m morna_amd.cli search -x idx -q 1234 --use-trees 50 --search-k 1000 -d
+    python -m morna_amd.cli recall -x idx --sample 100 -r 20 --trees 10,20,50,100,all --search-ks 100,200,500,1000,4000 --summary-only
 """
 import argparse
 import sys
@@ -201,10 +210,14 @@ def build_parser():
                                help='with --unhashed and a query that is not already in the index (a stream, --intropolis), '
                                     'with --supersamples, and with --downsample unless --unhashed: path to the (gzipped) intropolis file the index was made '
                                     'from, which names the junction of every line')
+    search_parser.add_argument('--use-trees', metavar='<int>', type=int, required=False, default=None,
+                               help='search with the first <int> trees of the index only: the answer of an index built with '
+                                    '--n-trees <int> from the same file (approximate search on an index without row shards; '
+                                    'not with -e, --unhashed, --within, --without or --leave-out-groups)')
     junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
                                                                'results for a second alignment pass')
     add_search_parameters(junctions_parser)                    # morna.py:1023
-    junctions_parser.set_defaults(unhashed_junction_file=None)   # (search's --junction-file: the unhashed search's; not this one)
+    junctions_parser.set_defaults(unhashed_junction_file=None, use_trees=None)   # (search's --junction-file: the unhashed search's; not this one; --use-trees is search's alone)
     junctions_parser.add_argument('-i', '--index', metavar='<idx>', type=str, required=False, default=None,
                                   help='accepted for compatibility and ignored (the aligner\'s index; morna.py:1025)')
     junctions_parser.add_argument('-p1', '--pass1-sam', metavar='<sam>', type=str, required=False, default="pass1.sam",
@@ -224,7 +237,7 @@ def build_parser():
                                                              'filters, how many of a query\'s true junctions its results '
                                                              'give back')
     add_search_parameters(recovery_parser)
-    recovery_parser.set_defaults(unhashed_junction_file=None)
+    recovery_parser.set_defaults(unhashed_junction_file=None, use_trees=None)
     recovery_parser.add_argument('--grid', type=str, required=False, default=None,
                                  help='the filters to tabulate, "<f1>,<f2>,...:<c1>,<c2>,...": every frequency with every '
                                       'coverage (at most 15 coverages); default 0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000')
@@ -247,6 +260,29 @@ def build_parser():
                                       '--truth-coverage) that its thinned row does not hold, those the shallow run lost. '
                                       'Precision is then against the lost junctions only, so a result that gives back a '
                                       'junction the query kept counts as a false positive: recall is the number of interest')
+    recall_parser = subparsers.add_parser('recall', help='tabulates the recall of the approximate search against the exact one '
+                                                         'over a grid of tree counts and search_k values, from one index')
+    recall_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                               help='path to junction index basename (an index without row shards)')
+    recall_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
+                               help='the query is the sample already in the index with this sample id')
+    recall_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                               help='comma-separated sample ids already in the index')
+    recall_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
+                               help='every sample of this (gzipped) intropolis file is a query')
+    recall_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
+                               help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
+    recall_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                               help='the seed of --sample (default 0)')
+    recall_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20,
+                               help='the number of nearest neighbor results compared (at most 256)')
+    recall_parser.add_argument('--trees', metavar='<t1,t2,...>', type=str, required=True,
+                               help='tree counts, ascending, at most 64; "all" stands for the index\'s tree count')
+    recall_parser.add_argument('--search-ks', metavar='<s1,s2,...>', type=str, required=True,
+                               help='search_k values, ascending, at most 64')
+    recall_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                               help='print only the table over all queries')
+    recall_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
     super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
@@ -411,6 +447,45 @@ def _check_recovery_flags(parser, args):
         parser.error("--truth cannot be used without --intropolis")
 
 
+def _check_use_trees_flags(parser, args):
+    """search --use-trees: the approximate, unrestricted, hashed search only."""
+    if getattr(args, "use_trees", None) is None:
+        return
+    if args.use_trees < 1:
+        parser.error("--use-trees takes a positive tree count (got %d)" % args.use_trees)
+    for flag, on in (("-e/--exact", args.exact), ("--unhashed", args.unhashed), ("--within", args.within is not None),
+                     ("--without", args.without is not None), ("--leave-out-groups", args.leave_out_groups is not None)):
+        if on:
+            parser.error("--use-trees cannot be used with %s" % flag)
+
+
+def _check_recall_flags(parser, args):
+    """`recall`: exactly one query source, the two lists (`all` is resolved once the index is read), -r within the limit."""
+    from .search import RECALL_MAX_K, parse_int_list
+    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+                                   ("--intropolis", args.intropolis is not None), ("--sample", args.sample is not None)) if on]
+    if len(given) != 1:
+        parser.error("recall needs exactly one query source: -q, --query-ids, --intropolis or --sample"
+                     + (" (got %s)" % " and ".join(given) if given else ""))
+    if args.query_ids is not None:
+        try:
+            args.query_ids = [int(t) for t in args.query_ids.split(',')]
+        except ValueError:
+            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
+    if args.sample is None and getattr(args, "sample_seed_given", False):
+        parser.error("--sample-seed cannot be used without --sample")
+    if args.sample is not None and args.sample < 1:
+        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
+    if not 1 <= args.results <= RECALL_MAX_K:
+        parser.error("-r %d: recall compares 1 to %d results" % (args.results, RECALL_MAX_K))
+    try:
+        parse_int_list(args.trees, "--trees", all_value=1 << 30)      # (checked again with the index's tree count)
+        args.search_k_list = parse_int_list(args.search_ks, "--search-ks")
+    except ValueError as e:
+        parser.error("--trees and --search-ks take comma-separated positive integers in ascending order, at most 64, such as "
+                     "10,20,50 (%s)" % e)
+
+
 def _check_batch_flags(parser, args):
     """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
     batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
@@ -473,6 +548,10 @@ def main(argv=None, stdin=None, stdout=None):
         _check_junction_flags(parser, args)
     if args.subparser_name in ('search', 'junctions', 'recovery'):
         _check_restriction_flags(parser, args)
+    if args.subparser_name == 'search':
+        _check_use_trees_flags(parser, args)
+    if args.subparser_name == 'recall':
+        _check_recall_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -490,6 +569,8 @@ def main(argv=None, stdin=None, stdout=None):
         return 0
     if args.subparser_name == 'supersample':
         return _supersample(args, stdout)
+    if args.subparser_name == 'recall':
+        return _recall(args, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -501,7 +582,7 @@ def main(argv=None, stdin=None, stdout=None):
     junctions = args.subparser_name == 'junctions'
     sharded = world > 1 and os.path.exists(args.basename + ".shards.mor")
     if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed or args.supersamples is not None
-                    or args.downsample is not None):
+                    or args.downsample is not None or _use_trees(args) is not None):
         raise RuntimeError("batch search is not available with one process per shard (torchrun): "
                            "run it in one process, which loads every shard of the index")
     if args.subparser_name in ('junctions', 'recovery'):
@@ -548,6 +629,60 @@ def main(argv=None, stdin=None, stdout=None):
         if dist is not None:
             searcher.annoy_index.close()
             dist.destroy_process_group()
+
+
+def _use_trees(args):
+    """search --use-trees; None without it (and for `junctions` / `recovery`, which do not take it)."""
+    return getattr(args, "use_trees", None)
+
+
+def _recall(args, stdout):
+    """`recall`: one exact search and one sweep over --trees x --search-ks on the GPU; a block per query and the table over
+    all of them."""
+    import os
+    import numpy as np
+    from .search import MornaSearch, TREES_SHARDS_REFUSAL, format_recall_rows, parse_int_list
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
+    if os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(TREES_SHARDS_REFUSAL)
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    n_trees = searcher.annoy_index.get_n_trees()
+    trees = parse_int_list(args.trees, "--trees", all_value=n_trees)
+    if trees[-1] > n_trees:
+        raise ValueError("--trees %d: the index has %d trees" % (trees[-1], n_trees))
+    if args.intropolis is not None:
+        batch = searcher.queries_from_intropolis(args.intropolis)
+        labels, queries = batch.ext_ids, batch
+    else:
+        if args.sample is not None:
+            inv = searcher._inverse_map()
+            n = searcher.annoy_index.get_n_items()
+            if args.sample > n:
+                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
+            picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
+            labels = [inv[int(i)] for i in picked]
+        else:
+            labels = args.query_ids if args.query_ids is not None else [args.query_id]
+        for query_id in labels:
+            if query_id not in searcher.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+        queries = [searcher.internal_id_map[query_id] for query_id in labels]
+    table = searcher.search_recall(queries, args.results, trees, args.search_k_list)
+    if not args.summary_only:
+        for q, label in enumerate(labels):
+            stdout.write("# query %s\n" % label)
+            stdout.write(format_recall_rows(table.rows(q)))
+    rows, failed = table.summary()
+    stdout.write("# all %d queries\n" % len(labels))
+    stdout.write(format_recall_rows(rows))
+    if failed > 0:
+        stdout.write("# exact search failed for %d queries\n" % failed)
+    return 0
 
 
 def _stream_parser(fmt):
@@ -684,7 +819,7 @@ def _downsample_search(args, searcher, n_results, junction_file):
                                                      restriction=r, query_groups=own)
         else:
             results = searcher.search_nn_batch(batch, n_results, _search_k(args), include_distances=args.distances,
-                                               meta_db=args.metadata, restriction=r, query_groups=own)
+                                               meta_db=args.metadata, restriction=r, query_groups=own, n_trees=_use_trees(args))
     return jobs, thinned, results
 
 
@@ -787,7 +922,7 @@ def _search_supersamples(args, searcher, stdout):
                                                      restriction=_restriction(args))
         else:
             results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
-                                               meta_db=args.metadata, restriction=_restriction(args))
+                                               meta_db=args.metadata, restriction=_restriction(args), n_trees=_use_trees(args))
     failed = False
     for label, res in zip(labels, results):
         stdout.write("# query %s\n" % label)
@@ -841,7 +976,7 @@ def _search_batch(args, searcher, stdout, collect=None):
     if args.query_ids is not None:
         internal, results = searcher.search_member_n_batch(args.query_ids, args.results, _search_k(args),
                                                            include_distances=args.distances, meta_db=args.metadata,
-                                                           restriction=_restriction(args))
+                                                           restriction=_restriction(args), n_trees=_use_trees(args))
         for query_id, internal_id, res in zip(args.query_ids, internal, results):
             _write_member_header(stdout, query_id, internal_id, True)
             results_output(res, stdout)
@@ -854,7 +989,7 @@ def _search_batch(args, searcher, stdout, collect=None):
                                                  restriction=_restriction(args))
     else:
         results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
-                                           meta_db=args.metadata, restriction=_restriction(args))
+                                           meta_db=args.metadata, restriction=_restriction(args), n_trees=_use_trees(args))
     failed = False
     for sample_id, res in zip(batch.ext_ids, results):
         stdout.write("# query %d\n" % sample_id)
@@ -888,10 +1023,10 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
             import contextlib
             with contextlib.redirect_stdout(stdout):           # ("querying by sample id ..." is rank 0's to print)
                 results = searcher.search_member_n(args.query_id, args.results, args.search_k,
-                                                   include_distances=args.distances, meta_db=args.metadata)
+                                                   include_distances=args.distances, meta_db=args.metadata, n_trees=_use_trees(args))
         else:
             results = searcher.search_member_n(args.query_id, args.results, args.search_k,
-                                               include_distances=args.distances, meta_db=args.metadata)
+                                               include_distances=args.distances, meta_db=args.metadata, n_trees=_use_trees(args))
         results_output(results, stdout)
         if collect is not None:
             collect.append((args.query_id, results))
@@ -927,7 +1062,7 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
             sys.stderr.write("\n")
             searcher.finalize_query()
             results = searcher.search_nn(args.results, args.search_k, include_distances=args.distances,
-                                         meta_db=args.metadata)
+                                         meta_db=args.metadata, n_trees=_use_trees(args))
             same = True
             for j, result in enumerate(results[0]):
                 if not (result == old_results[j]):
@@ -958,7 +1093,7 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
         results = searcher.exact_search_nn(args.results, include_distances=args.distances, meta_db=args.metadata)
     else:
         results = searcher.search_nn(args.results, args.search_k, include_distances=args.distances,
-                                     meta_db=args.metadata)
+                                     meta_db=args.metadata, n_trees=_use_trees(args))
     results_output(results, stdout)
     if collect is not None:
         collect.append((None, results))

@@ -563,6 +563,134 @@ int morna_exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, i
     return exact_search(h, q, nq, k, ids_out, dist_out, count_out);
 }
 
+// ---- tree-prefix search and the (tree count, search_k) sweep (the contracts are in morna_hip.h) ------------------
+
+static int query_rows_ready(morna_index *h);
+
+int morna_get_nns_prefix(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, int32_t search_k,
+                         int32_t n_trees_used, int32_t *ids, float *dist, int32_t *count)
+{
+    CHECK_H(h);
+    if (!ids) {
+        set_error("get_nns_prefix: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (q && items) {
+        set_error("get_nns_prefix: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    int64_t q_stride = 0;
+    if (!q && !items) {   // the staged query rows, read in place as morna_get_nns_by_query_rows reads them
+        MORNA_TRY(query_rows_ready(h));
+        if (nq != h->qrows.nq) {
+            set_error("get_nns_prefix: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        q = h->qrows.rows32.p;
+        q_stride = h->dpad;
+    }
+    if (!h->built) {
+        set_error("index has not been built: call build() before searching");
+        return MORNA_E_STATE;
+    }
+    if (n_trees_used < 1 || n_trees_used > h->n_trees) {
+        set_error("get_nns_prefix: %d trees asked for, the forest has %d", n_trees_used, h->n_trees);
+        return MORNA_E_RANGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return query_batch(h, q, q_stride, items, nq, k, search_k, ids, dist, count, nullptr, 0, nullptr, nullptr, n_trees_used);
+}
+
+// the query source of a sweep: q, items, or (both null) the staged query rows, whose count nq must be
+static int sweep_source(morna_index *h, const float *&q, const int32_t *items, int64_t nq, int64_t &q_stride, bool &staged,
+                        const char *who)
+{
+    q_stride = 0;
+    staged = false;
+    if (q && items) {
+        set_error("%s: give query vectors or items, not both", who);
+        return MORNA_E_INVALID;
+    }
+    if (!q && !items) {
+        if (!h->qrows.valid) {
+            set_error("no query rows: call morna_build_query_rows first");
+            return MORNA_E_STATE;
+        }
+        if (nq != h->qrows.nq) {
+            set_error("%s: %lld queries asked for, %lld query rows are staged", who, (long long)nq, (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        q = h->qrows.rows32.p;
+        q_stride = h->dpad;
+        staged = true;
+    }
+    return MORNA_OK;
+}
+
+int morna_search_sweep(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, const int32_t *trees,
+                       int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out, int32_t *count_out,
+                       int32_t *ncand_out, int32_t *ndots_out)
+{
+    CHECK_H(h);
+    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    int64_t q_stride;
+    bool staged;
+    MORNA_TRY(sweep_source(h, q, items, nq, q_stride, staged, "search_sweep"));
+    HIP_TRY(hipSetDevice(h->device));
+    return search_sweep(h, q, q_stride, items, nq, k, trees, n_t, search_ks, n_s, ids_out, dist_out, count_out, ncand_out, ndots_out);
+}
+
+int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, const int32_t *trees,
+                       int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *hits_out, int32_t *exact_count_out,
+                       int32_t *ncand_out, int32_t *ndots_out, int32_t *ids_out, float *dist_out, int32_t *count_out,
+                       int32_t *exact_ids_out)
+{
+    CHECK_H(h);
+    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    if (!hits_out) {
+        set_error("recall_sweep: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (k > MORNA_RECALL_MAX_K) {
+        set_error("recall_sweep: n = %d is above the supported %d", k, MORNA_RECALL_MAX_K);
+        return MORNA_E_INVALID;
+    }
+    int64_t q_stride;
+    bool staged;
+    MORNA_TRY(sweep_source(h, q, items, nq, q_stride, staged, "recall_sweep"));
+    HIP_TRY(hipSetDevice(h->device));
+    // the sweep's own checks first (no exact search for a grid that is refused): a call without queries makes them all
+    MORNA_TRY(search_sweep(h, q, q_stride, items, 0, k, trees, n_t, search_ks, n_s, nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (nq == 0) return MORNA_OK;
+    std::vector<int32_t> ex_ids((size_t)nq * k), ex_count((size_t)nq);
+    if (staged) {   // the un-rounded fp64 rows, as morna_exact_search_query_rows
+        MORNA_TRY(exact_search_any(h, nullptr, nullptr, nullptr, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0,
+                                   h->qrows.rows64.p));
+    } else if (q) {
+        std::vector<double> q64((size_t)nq * h->dim);   // the fp32 queries widened
+        for (size_t i = 0; i < q64.size(); i++) q64[i] = (double)q[i];
+        MORNA_TRY(exact_search_any(h, q64.data(), nullptr, nullptr, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
+    } else {
+        MORNA_TRY(exact_search_any(h, nullptr, nullptr, items, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
+    }
+    MORNA_TRY(search_sweep(h, q, q_stride, items, nq, k, trees, n_t, search_ks, n_s, ids_out, dist_out, count_out, ncand_out,
+                           ndots_out, ex_ids.data(), ex_count.data(), hits_out));
+    if (exact_count_out) memcpy(exact_count_out, ex_count.data(), (size_t)nq * 4);
+    if (exact_ids_out) memcpy(exact_ids_out, ex_ids.data(), (size_t)nq * k * 4);
+    return MORNA_OK;
+}
+
+int morna_search_sweep_stats(const morna_index *h, double *stats)
+{
+    CHECK_H(h);
+    if (!stats) {
+        set_error("search_sweep_stats: null buffer");
+        return MORNA_E_INVALID;
+    }
+    for (int i = 0; i < 4; i++) stats[i] = h->sweep_stats[i];
+    return MORNA_OK;
+}
+
 // ---- query rows (morna_build_query_rows is in parse.hip, beside the lines it takes) ---------------------------
 
 static int query_rows_ready(morna_index *h)

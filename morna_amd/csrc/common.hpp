@@ -318,6 +318,8 @@ struct morna_index {
     morna::QueryRows qrows;      // morna_build_query_rows
     // [0] rows read by query kernels (hyperplane dots + candidates + 1 per query)
     morna::DevBuf<unsigned long long> d_stat;
+    // the last search sweep (knn.hip): descents, cells, rows read by canonical dots, whether the fp16 contraction ran
+    double sweep_stats[4] = {0, 0, 0, 0};
 
     // row-sharded search (comm.hip): the RCCL communicator of this shard, every shard's first global id, message buffers
     void *comm = nullptr;              // ncclComm_t
@@ -420,7 +422,14 @@ int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s
 // packed_dev (device memory, or null): [nq][2k] int32 message of the row-sharded search -- ids + id_offset, distance bits
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
                 int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev = nullptr,
-                int64_t id_offset = 0, const morna_restriction *rst = nullptr, const int32_t *q_group_host = nullptr);
+                int64_t id_offset = 0, const morna_restriction *rst = nullptr, const int32_t *q_group_host = nullptr,
+                int32_t n_trees_used = 0 /* the first n_trees_used trees only; 0: the whole forest */);
+// every (tree count, search_k) cell of a grid from one forest (morna_hip.h, "search sweep"); outputs [n_t][n_s][nq] ([k]), any may be null
+// (q_host: host or device memory, q_stride floats apart, 0 = dim; ex_*: the exact answers, for hits_out)
+int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
+                 const int32_t *trees, int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out,
+                 int32_t *count_out, int32_t *ncand_out, int32_t *ndots_out, const int32_t *ex_ids_host = nullptr,
+                 const int32_t *ex_count_host = nullptr, int32_t *hits_out = nullptr);
 int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, int64_t nq, int32_t kk, int32_t k,
                    int32_t *ids_out, float *dist_out, int32_t *count_out);
 int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t *ids_out,

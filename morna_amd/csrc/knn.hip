@@ -95,6 +95,17 @@ __device__ inline bool restrict_eligible(const RestrictArgs &R, int32_t gq, int6
     return gq < 0 || R.group[i] != gq;
 }
 
+// A sweep over (tree count, search_k) cells from one forest (include/morna_hip.h, "search sweep").  Only the *_sweep_kernel
+// forms take it.  A launch's "virtual query" v = i * nq + q is query q of the batch walked over the first trees[i] trees.
+#define SWEEP_MAX_LIST 64
+struct SweepArgs {
+    int32_t n_t, n_s, nq;                  // tree counts, search_k values, queries of the batch
+    int32_t trees[SWEEP_MAX_LIST];         // strictly ascending, the last at most the forest's
+    int32_t search_ks[SWEEP_MAX_LIST];     // strictly ascending
+    const uint64_t *root_pq;               // [nq][n_nodes] the root margins of every query at trees[n_t - 1], read only
+    int32_t *cell_ncand, *cell_ndots;      // [n_t][n_s][nq] unique candidates / hyperplane dots when nn first reached search_ks[j]
+};
+
 __device__ inline uint64_t pq_key(float d, int32_t node)
 {
     return ((uint64_t)f32_orderable(d) << 32) | (uint32_t)node;
@@ -426,8 +437,13 @@ __device__ inline uint32_t wave_max_u32_fast(uint32_t v)
 
 // RST: the restricted form, as in query_traverse_body; the group test sits in the leaf branch only (the pops' chain does
 // not see it), and the first leaf is always copied: its slice of the permutation is not filtered.
-template <bool BM_LDS, int NV, bool RST>
-__device__ __forceinline__ void query_descend_body(const QueryParams &P, const RestrictArgs &R)
+// SWP: the sweep form.  Block v is a virtual query (SweepArgs): the queue is seeded from the first 2 * trees[i] entries of
+// the query's root margins (made once, for the largest tree count: tree t's entries do not depend on the trees behind it),
+// the queue overflow, bitmap and candidates are the block's own, the descent runs to the LARGEST search_k, and whenever a
+// leaf pop carries nn past search_ks[j] -- the moment the search with that search_k would have stopped -- the candidates
+// and hyperplane dots so far are recorded for cell (i, j).  The first leaf is always copied.
+template <bool BM_LDS, int NV, bool RST, bool SWP = false>
+__device__ __forceinline__ void query_descend_body(const QueryParams &P, const RestrictArgs &R, const SweepArgs *S = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // a queue entry = (bound as an orderable 32-bit word, node); an empty slot has bound word 0 (no real bound maps to 0:
@@ -439,10 +455,19 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
     const int lane = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const int nvec = P.dpad / 4;
-    const int T = P.n_trees;
+    int T = P.n_trees;
+    int64_t qsrc = qi;          // the query whose row this block reads
+    int ti = 0, jrec = 0;       // sweep: the tree count's number, the search_k values recorded so far
+    if constexpr (SWP) {
+        ti = (int)(qi / S->nq);
+        qsrc = qi - (int64_t)ti * S->nq;
+        T = S->trees[ti];
+    }
     uint32_t *bm = BM_LDS ? (uint32_t *)smem : P.bm_global + (size_t)qi * P.bm_words;
-    const float4 *q = query_row(P, qi);
+    const float4 *q = query_row(P, qsrc);
     uint64_t *gpq = P.pq + qi * P.n_nodes;
+    const uint64_t *rpq = gpq;  // where the root margins are
+    if constexpr (SWP) rpq = S->root_pq + qsrc * P.n_nodes;
     int32_t *cand = P.cand + qi * P.cap;
     const bool roots_split = P.n_items > P.K;
     int hn = roots_split ? 2 * T : T;
@@ -467,7 +492,7 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
 #pragma unroll
             for (int u = 0; u < nu; u++) {
                 const int i = lane + WAVE * u;
-                k16[u] = i < hn ? (roots_split ? gpq[i] : pq_key(INFINITY, i)) : 0;
+                k16[u] = i < hn ? (roots_split ? rpq[i] : pq_key(INFINITY, i)) : 0;
             }
 #pragma unroll
             for (int u = 0; u < nu; u++) s16[u] = lane + WAVE * u < hn ? P.node_hp[(int32_t)(uint32_t)k16[u]] : -1;
@@ -487,6 +512,19 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
     }
     if (!roots_split)
         for (int i = PQ_LDS + lane; i < hn; i += WAVE) gpq[i] = pq_key(INFINITY, i);
+    if constexpr (SWP) {
+        if (roots_split)   // the root entries past the LDS arrays: into the block's own overflow
+            for (int i = PQ_LDS + lane; i < hn; i += WAVE) gpq[i] = rpq[i];
+    }
+    auto record = [&](int ndots_now) {   // sweep: cell (ti, jrec) stops here
+        if constexpr (SWP) {
+            if (lane == 0) {   // (lane 0 made the counter updates itself: its read follows them)
+                const int64_t cell = ((int64_t)ti * S->n_s + jrec) * S->nq + qsrc;
+                S->cell_ncand[cell] = s_ncand;
+                S->cell_ndots[cell] = ndots_now;
+            }
+        }
+    };
     int32_t gq = -1;
     if constexpr (RST) {
         for (int i = lane; i < P.bm_words; i += WAVE) bm[i] = R.deny[i];
@@ -563,7 +601,7 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
             const int32_t *src_ids = P.perm + (int64_t)P.node_tree[node] * P.n_items + rec.z;
             const int count = rec.w;
             bool whole_leaf = false;
-            if constexpr (!RST) whole_leaf = P.zero_copy && n_leaves == 0 && nn + count >= search_k;
+            if constexpr (!RST && !SWP) whole_leaf = P.zero_copy && n_leaves == 0 && nn + count >= search_k;
             if (whole_leaf) {
                 // the first leaf ends the search: its ids ARE the candidates -- not copied
                 if (lane == 0) {
@@ -607,6 +645,12 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
             }
             nn += count;
             n_leaves++;
+            if constexpr (SWP) {
+                while (jrec < S->n_s && nn >= (int64_t)S->search_ks[jrec]) {
+                    record(ndots);
+                    jrec++;
+                }
+            }
         } else {
             const int4 rec = *(const int4 *)(P.node_rec + 4 * (int64_t)node);
             // the children's slots are wanted when they are popped, not now: requested here, under the hyperplane fetch
@@ -628,6 +672,9 @@ __device__ __forceinline__ void query_descend_body(const QueryParams &P, const R
         }
         __syncthreads();   // one wave: the queue writes above are seen by the next scan
         TP();
+    }
+    if constexpr (SWP) {
+        for (; jrec < S->n_s; jrec++) record(ndots);   // the queue ran empty: the searches that wanted more stop here too
     }
     if (lane == 0) {
         const int nc = s_ncand;
@@ -658,6 +705,12 @@ __global__ __launch_bounds__(WAVE) void query_descend_restricted_kernel(QueryPar
     query_descend_body<BM_LDS, NV, true>(P, R);
 }
 
+template <bool BM_LDS, int NV>
+__global__ __launch_bounds__(WAVE) void query_descend_sweep_kernel(QueryParams P, SweepArgs S)
+{
+    query_descend_body<BM_LDS, NV, false, true>(P, RestrictArgs(), &S);
+}
+
 #define QS_CPW 1   // candidates per wave of query_cand_dots_kernel
 __global__ __launch_bounds__(Q_THREADS) void query_cand_dots_kernel(QueryParams P)
 {
@@ -683,12 +736,44 @@ __global__ __launch_bounds__(Q_THREADS) void query_cand_dots_kernel(QueryParams 
     }
 }
 
+// Sweep: the canonical dot of every candidate of every virtual query's deepest list -- a cell's candidates are a prefix of
+// it, and a candidate's key does not depend on the prefix it is judged in, so no dot is taken twice.  A wave per candidate,
+// the blocks of one virtual query side by side (bpv of them), in a 1-D grid.
+// FLT: only the candidates that pass the threshold of the shortest prefix holding them (below, "sweep with the fp16 filter").
+template <bool FLT>
+__global__ __launch_bounds__(Q_THREADS) void sweep_cand_dots_kernel(QueryParams P, int32_t nq, int32_t bpv, int32_t n_s,
+                                                                   const int32_t *__restrict__ cell_ncand, const float *__restrict__ thr)
+{
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int64_t vq = blockIdx.x / (unsigned)bpv;
+    const int c = (int)(blockIdx.x - vq * bpv) * Q_WAVES + w;
+    const int ncand = P.ncand[vq] < P.cap ? P.ncand[vq] : P.cap;
+    if (c >= ncand) return;
+    const int64_t qsrc = vq % nq;
+    if constexpr (FLT) {
+        const int64_t ti = vq / nq;
+        int j = 0;   // the first cell whose prefix holds candidate c (the deepest one's does)
+        while (j < n_s - 1 && cell_ncand[(ti * n_s + j) * nq + qsrc] <= c) j++;
+        if (P.low[vq * P.cap + c] > thr[(ti * n_s + j) * nq + qsrc]) {   // (a NaN on either side: kept)
+            if (lane == 0) P.keys[vq * P.cap + c] = ~0ull;
+            return;
+        }
+        if (lane == 0) atomicAdd(P.stat + 3, 1ull);
+    }
+    const float4 *q = query_row(P, qsrc);
+    const int32_t id = P.cand[vq * P.cap + c];
+    const float pqv = wave_dot((const float4 *)(P.X + (int64_t)id * P.dpad), q, P.dpad / 4, lane);
+    if (lane == 0)
+        P.keys[vq * P.cap + c] = ((uint64_t)f32_orderable(ang_dist(P.qpp[qsrc], P.norm2[id], pqv)) << 32) | (uint32_t)id;
+}
+
 // The k smallest (distance, id) keys of a query's candidates, in order.  Two looks at the keys instead of k rounds of a
 // block-wide minimum: every thread's own minimum -- the k-th smallest of those 256 bounds the k-th smallest key from above --,
 // then the few keys at or below that bound are collected and ranked by counting (the keys are distinct: the id is in them).
 #define QT_HELD 16
 #define QT_LIST 1024
-__global__ __launch_bounds__(Q_THREADS) void query_topk_kernel(QueryParams P)
+// keys[0 .. nsel): the keys to rank; qi: the slot of the answer in ids_out / dist_out / count_out
+__device__ __forceinline__ void query_topk_body(const QueryParams &P, const uint64_t *keys, const int nsel, const int64_t qi)
 {
     __shared__ uint64_t s_red[Q_WAVES];
     __shared__ uint64_t s_min[Q_THREADS];
@@ -696,9 +781,6 @@ __global__ __launch_bounds__(Q_THREADS) void query_topk_kernel(QueryParams P)
     __shared__ uint64_t s_bound;
     __shared__ int s_n;
     const int tid = threadIdx.x;
-    const int64_t qi = blockIdx.x;
-    const uint64_t *keys = P.keys + qi * P.cap;
-    const int nsel = P.ncand[qi] < P.cap ? P.ncand[qi] : P.cap;
     const int kout = P.k < nsel ? P.k : nsel;
     auto emit = [&](int r, uint64_t key) {
         P.ids_out[qi * P.k + r] = (int32_t)(uint32_t)key;
@@ -761,6 +843,91 @@ __global__ __launch_bounds__(Q_THREADS) void query_topk_kernel(QueryParams P)
         P.dist_out[qi * P.k + r] = INFINITY;
     }
     if (tid == 0) P.count_out[qi] = kout;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void query_topk_kernel(QueryParams P)
+{
+    const int64_t qi = blockIdx.x;
+    query_topk_body(P, P.keys + qi * P.cap, P.ncand[qi] < P.cap ? P.ncand[qi] : P.cap, qi);
+}
+
+// Sweep: block c = (i * n_s + j) * nq + q ranks the first cell_ncand[c] keys of virtual query i * nq + q -- the candidates
+// the search with trees[i] and search_ks[j] had when it stopped -- into answer slot c.
+__global__ __launch_bounds__(Q_THREADS) void sweep_topk_kernel(QueryParams P, int32_t n_s, int32_t nq, const int32_t *cell_ncand)
+{
+    const int64_t cell = blockIdx.x;
+    const int64_t q = cell % nq, ti = cell / ((int64_t)n_s * nq);
+    const int nc = cell_ncand[cell];
+    query_topk_body(P, P.keys + (ti * nq + q) * P.cap, nc < P.cap ? nc : P.cap, cell);
+}
+
+// Recall of a sweep: hits[c] = |ids of cell c  n  exact ids of its query|, a wave per (cell, query); -1 where the exact
+// search failed (count -1: a row parallel to the query).  Lists of at most a few hundred ids: compared pair by pair.
+__global__ __launch_bounds__(WAVE) void sweep_hits_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ count,
+                                                          const int32_t *__restrict__ ex_ids, const int32_t *__restrict__ ex_count,
+                                                          int32_t nq, int32_t k, int32_t *__restrict__ hits)
+{
+    const int lane = threadIdx.x;
+    const int64_t cell = blockIdx.x, q = cell % nq;
+    const int ec = ex_count[q], ac = count[cell];
+    if (ec < 0) {
+        if (lane == 0) hits[cell] = -1;
+        return;
+    }
+    int mine = 0;
+    for (int a = lane; a < ac; a += WAVE) {
+        const int32_t id = ids[cell * k + a];
+        for (int e = 0; e < ec; e++) mine += ex_ids[q * k + e] == id ? 1 : 0;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off, WAVE);
+    if (lane == 0) hits[cell] = mine;
+}
+
+// Sweep with the fp16 filter (the batch's scores[] are there): the bounds of a candidate's distance do not depend on the
+// prefix it is judged in, so they are made once per virtual query (sweep_bounds_kernel: the arithmetic of
+// query_refine_kernel<2>); per cell the k-th smallest UPPER bound of its prefix is the cell's threshold
+// (sweep_threshold_kernel).  That threshold only falls as the prefix grows, so a candidate is wanted by some cell iff it
+// passes the threshold of the SHORTEST prefix that holds it: sweep_cand_dots_kernel<true> takes the canonical dot of those
+// alone -- once -- and leaves ~0 in the key of every other candidate, which no cell's k smallest keys can be.
+__global__ __launch_bounds__(Q_THREADS) void sweep_bounds_kernel(QueryParams P, int32_t nq, uint64_t *__restrict__ ub)
+{
+    const int64_t vq = blockIdx.x, q = vq % nq;
+    const int ncand = P.ncand[vq] < P.cap ? P.ncand[vq] : P.cap;
+    const int32_t qsrc = P.items ? P.items[q] : (int32_t)q;
+    const float qs = P.qscale[qsrc], qn = P.qn16[qsrc], qe = P.qe16[qsrc];
+    const float rq = qe / (qn * 0.996f);
+    const float *sc_row = P.scores + q * P.n_items;
+    const float pp = P.qpp[q];
+    const float nan = __int_as_float(0x7fc00000);
+    for (int c = threadIdx.x; c < ncand; c += Q_THREADS) {
+        const int32_t id = P.cand[vq * P.cap + c];
+        const float sc = P.xscale[id] * qs;
+        const float rx = P.xe16[id] / (P.xn16[id] * 0.996f);
+        float df = nan, dl = 0.f;
+        if (sc != 0.f && rx < 0.125f && rq < 0.125f) {   // (the bound of query_refine_kernel<2>; every row went through the two-chain form)
+            const float cerr = ((P.eacc + rx) + (1.f + rx) * rq) / ((1.f - rx) * (1.f - rq));
+            df = ang_dist(pp, P.norm2[id], sc_row[id] * sc);
+            dl = 2.02f * cerr + 1e-5f;
+        }
+        ub[vq * P.cap + c] = ((uint64_t)f32_orderable(df + dl) << 32) | (uint32_t)c;
+        P.low[vq * P.cap + c] = df - dl;
+    }
+}
+
+__global__ __launch_bounds__(Q_THREADS) void sweep_threshold_kernel(QueryParams P, int32_t n_s, int32_t nq, const int32_t *__restrict__ cell_ncand,
+                                                                   const uint64_t *__restrict__ ub, float *__restrict__ thr)
+{
+    __shared__ uint64_t s_red[Q_WAVES];
+    __shared__ uint64_t s_top[Q_WAVES * KTH_MAX_K];
+    const int64_t cell = blockIdx.x;
+    const int64_t q = cell % nq, ti = cell / ((int64_t)n_s * nq);
+    const int nc = cell_ncand[cell] < P.cap ? cell_ncand[cell] : P.cap;
+    if (nc <= P.k) {   // every candidate is an answer (uniform)
+        if (threadIdx.x == 0) thr[cell] = INFINITY;
+        return;
+    }
+    const uint64_t kth = block_kth_smallest(ub + (ti * nq + q) * P.cap, nc, P.k, threadIdx.x, s_red, s_top);
+    if (threadIdx.x == 0) thr[cell] = f32_from_orderable((uint32_t)(kth >> 32));   // (NaN when fewer than k have a bound: all pass)
 }
 
 // ---- filter dots of a whole batch on the matrix cores ----------------------------------------------------------
@@ -1063,7 +1230,7 @@ static int restriction_usable(const morna_index *h, const morna_restriction *rst
 // search"); only the traversal kernels differ, every kernel behind them reads candidate lists.
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
                 int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out, int32_t *packed_dev, int64_t id_offset,
-                const morna_restriction *rst, const int32_t *q_group_host)
+                const morna_restriction *rst, const int32_t *q_group_host, int32_t n_trees_used)
 {
     if (q_stride <= 0) q_stride = h->dim;
     if (!h->built) {
@@ -1079,8 +1246,14 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         return MORNA_E_INVALID;
     }
     if (rst) MORNA_TRY(restriction_usable(h, rst));
+    if (n_trees_used != 0 && (n_trees_used < 1 || n_trees_used > h->n_trees)) {
+        set_error("get_nns: %d trees asked for, the forest has %d", n_trees_used, h->n_trees);
+        return MORNA_E_RANGE;
+    }
+    // the trees the search walks: all of them, or the first n_trees_used (morna_hip.h, "tree-prefix search")
+    const int32_t T_used = n_trees_used ? n_trees_used : h->n_trees;
     if (nq == 0) return MORNA_OK;
-    if (search_k == -1) search_k = (int32_t)std::min<int64_t>((int64_t)k * h->n_trees, INT32_MAX);
+    if (search_k == -1) search_k = (int32_t)std::min<int64_t>((int64_t)k * T_used, INT32_MAX);
     if (items_host)
         for (int64_t i = 0; i < nq; i++)
             if (items_host[i] < 0 || items_host[i] >= h->n_items) {
@@ -1132,7 +1305,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         const bool dense = may_dense && dense_pays(nb);
         uint8_t *p = h->ws.p;
         QueryParams P;
-        P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = N; P.dpad = h->dpad; P.n_trees = h->n_trees; P.K = h->K;
+        P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = N; P.dpad = h->dpad; P.n_trees = T_used; P.K = h->K;
         P.node_rec = h->node_rec.p; P.node_tree = h->node_tree.p; P.node_hp = h->node_hp.p; P.hp = h->hp.p;
         P.perm = h->perm.p; P.n_nodes = h->n_nodes;
         P.k = k; P.search_k = search_k; P.cap = cap; P.bm_words = bm_words;
@@ -1273,7 +1446,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         if (spread) {
             // a batch too small to fill the chip with one workgroup per query: each query's work is dealt out (kernels above)
             ScopedTimer tm(h, MORNA_T_QUERY, 0);
-            hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((h->n_trees + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
+            hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((T_used + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
                                h->stream, P);
             MORNA_TRY(launch_descend(h->stream));
 #ifdef MORNA_DESCEND_PROBE
@@ -1346,7 +1519,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
             const bool split_traverse = nv_ok && N > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024 &&
                                         env_on("MORNA_QUERY_SPLIT_TRAVERSE");
             if (split_traverse) {
-                const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((h->n_trees + QR_TREES - 1) / QR_TREES));
+                const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((T_used + QR_TREES - 1) / QR_TREES));
                 const size_t ql = (size_t)QR_Q * h->dpad * 4;
 #define ROOTSB(NVV)                                                                                                      \
     do {                                                                                                                 \
@@ -1424,6 +1597,291 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         // (packed answers only: nothing to wait for -- the next batch, and whatever the caller orders on the handle's
         // stream, run behind this one)
     }
+    return MORNA_OK;
+}
+
+// ---- sweep: every (tree count, search_k) cell of a grid from one forest (morna_hip.h, "search sweep") ----------------
+// Per batch: the queries staged once, the root margins once at the largest tree count; per virtual query (query, tree
+// count) one one-wave descent to the largest search_k that records where every smaller search_k stops; the canonical dot
+// of every candidate of the deepest lists once -- for a batch that query_batch's dense_pays rule sends through the
+// whole-batch contraction, only of the candidates the fp16 filter of some cell lets through --; per cell the k smallest
+// keys of its prefix.
+// ex_ids_host [nq][k] / ex_count_host [nq] with hits_out: the exact answers of the same queries, for the recall count.
+// q_host: query vectors in host OR device memory, q_stride floats apart (0 = dim), as query_batch takes them.
+int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
+                 const int32_t *trees, int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out,
+                 int32_t *count_out, int32_t *ncand_out, int32_t *ndots_out, const int32_t *ex_ids_host,
+                 const int32_t *ex_count_host, int32_t *hits_out)
+{
+    if (q_stride <= 0) q_stride = h->dim;
+    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    if (!h->built) {
+        set_error("index has not been built: call build() before searching");
+        return MORNA_E_STATE;
+    }
+    if (k <= 0 || nq < 0) {
+        set_error("search_sweep: n must be positive");
+        return MORNA_E_INVALID;
+    }
+    if (h->dpad > Q_MAX_DPAD) {
+        set_error("search_sweep: dimension %d is above the supported %d", h->dim, Q_MAX_DPAD);
+        return MORNA_E_INVALID;
+    }
+    if (!trees || !search_ks || n_t < 1 || n_s < 1 || n_t > SWEEP_MAX_LIST || n_s > SWEEP_MAX_LIST) {
+        set_error("search_sweep: %d tree counts and %d search_k values given, each list holds 1 to %d", n_t, n_s, SWEEP_MAX_LIST);
+        return MORNA_E_INVALID;
+    }
+    for (int i = 0; i < n_t; i++)
+        if (trees[i] < 1 || (i > 0 && trees[i] <= trees[i - 1])) {
+            set_error("search_sweep: tree counts must be positive and strictly ascending (entry %d is %d)", i, trees[i]);
+            return MORNA_E_INVALID;
+        }
+    for (int j = 0; j < n_s; j++)
+        if (search_ks[j] < 1 || (j > 0 && search_ks[j] <= search_ks[j - 1])) {
+            set_error("search_sweep: search_k values must be positive and strictly ascending (entry %d is %d)", j, search_ks[j]);
+            return MORNA_E_INVALID;
+        }
+    if (trees[n_t - 1] > h->n_trees) {
+        set_error("search_sweep: %d trees asked for, the forest has %d", trees[n_t - 1], h->n_trees);
+        return MORNA_E_RANGE;
+    }
+    if (nq == 0) return MORNA_OK;
+    if (items_host)
+        for (int64_t i = 0; i < nq; i++)
+            if (items_host[i] < 0 || items_host[i] >= h->n_items) {
+                set_error("item id %d out of range [0, %lld)", items_host[i], (long long)h->n_items);
+                return MORNA_E_RANGE;
+            }
+    const int64_t N = h->n_items;
+    const int32_t T_max = trees[n_t - 1], s_max = search_ks[n_s - 1];
+    const int64_t n_cells = (int64_t)n_t * n_s;
+    // |nns| < search_k before the last pop, which adds at most K ids (every cell's own bound is below the deepest one's)
+    const int32_t cap = (int32_t)std::max<int64_t>(std::min<int64_t>(N, (int64_t)s_max + h->K), 1);
+    const int32_t bm_words = (int32_t)((N + 31) / 32);
+    const bool bm_lds = (size_t)bm_words * 4 <= 64 * 1024;
+    const bool want_hits = hits_out && ex_ids_host && ex_count_host;
+    // the fp16 filter through ONE whole-batch contraction, by query_batch's rule for a batch (MORNA_SWEEP_FILTER=0: canonical
+    // dots for every candidate of the deepest lists, as the small batches take them)
+    static const bool filter_on = env_on("MORNA_QUERY_FILTER"), dense_on = env_on("MORNA_QUERY_DENSE");
+    const bool sweep_filter_on = env_on("MORNA_SWEEP_FILTER");
+    auto dense_pays = [&](int64_t nb) { return nb >= 40 && nb * std::min<int64_t>(cap, h->K) >= 2 * N; };
+    const bool may_dense = filter_on && dense_on && sweep_filter_on && cap > 4 * (int64_t)k && dense_pays(nq);
+
+    // the 1 GiB workspace rule of query_batch; the unit is a query with its n_t virtual queries and n_t * n_s cells
+    const size_t per_v = (size_t)h->n_nodes * 8 + (size_t)cap * (may_dense ? 24 : 12) + 16 + (bm_lds ? 0 : (size_t)bm_words * 4);
+    const size_t per_c = (size_t)k * 8 + 20;
+    const size_t per_q = (size_t)h->n_nodes * 8 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) + 16 + (size_t)k * 4 + per_v * n_t +
+                         per_c * n_cells + (may_dense ? (size_t)N * 4 : 0);
+    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 32768), (int64_t)(((size_t)1 << 30) / per_q)));
+    const int64_t bv = batch * n_t, bc = batch * n_cells;
+    const size_t s_rpq = align_up((size_t)batch * h->n_nodes * 8, 256), s_q = q_host ? align_up((size_t)batch * h->dpad * 4, 256) : 0,
+                 s_qf = align_up((size_t)batch * 4, 256), s_exi = want_hits ? align_up((size_t)batch * k * 4, 256) : 0,
+                 s_pq = align_up((size_t)bv * h->n_nodes * 8, 256), s_keys = align_up((size_t)bv * cap * 8, 256),
+                 s_cand = align_up((size_t)bv * cap * 4, 256), s_vf = align_up((size_t)bv * 8, 256),
+                 s_bm = bm_lds ? 0 : align_up((size_t)bv * bm_words * 4, 256), s_ids = align_up((size_t)bc * k * 4, 256),
+                 s_cf = align_up((size_t)bc * 4, 256), s_q16 = q_host && may_dense ? align_up((size_t)batch * h->dpad * 2, 256) : 0,
+                 s_scores = may_dense ? align_up((size_t)batch * N * 4, 256) : 0, s_ub = may_dense ? s_keys : 0,
+                 s_low = may_dense ? s_cand : 0;
+    MORNA_TRY(h->ws.alloc(s_rpq + s_q + 7 * s_qf + s_exi + s_pq + s_keys + s_cand + 2 * s_vf + s_bm + 2 * s_ids + 5 * s_cf + s_q16 +
+                          s_scores + s_ub + s_low));
+    MORNA_TRY(h->d_stat.alloc(4));
+    if (may_dense) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
+    bool contraction_ran = false;
+    const size_t out_bytes = 2 * s_ids + 4 * s_cf;
+    MORNA_TRY(h->host_out.reserve(out_bytes));
+
+    double descents = 0, rows_dots = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+        const int64_t nb = std::min(batch, nq - q0);
+        const int64_t nv = nb * n_t, nc = nb * n_cells;
+        uint8_t *p = h->ws.p;
+        QueryParams P;
+        P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = N; P.dpad = h->dpad; P.n_trees = T_max; P.K = h->K;
+        P.node_rec = h->node_rec.p; P.node_tree = h->node_tree.p; P.node_hp = h->node_hp.p; P.hp = h->hp.p;
+        P.perm = h->perm.p; P.n_nodes = h->n_nodes;
+        P.k = k; P.search_k = s_max; P.cap = cap; P.bm_words = bm_words;
+        uint64_t *root_pq = (uint64_t *)p; p += s_rpq;
+        float *Qd = (float *)p; p += s_q;
+        P.qpp = (float *)p; p += s_qf;
+        int32_t *d_items = (int32_t *)p; p += s_qf;
+        int32_t *d_exc = (int32_t *)p; p += 2 * s_qf;
+        int32_t *d_exi = (int32_t *)p; p += s_exi;
+        P.pq = (uint64_t *)p; p += s_pq;
+        P.keys = (uint64_t *)p; p += s_keys;
+        P.cand = (int32_t *)p; p += s_cand;
+        P.ncand = (int32_t *)p; p += s_vf;
+        P.cand_off = (int64_t *)p; p += s_vf;
+        P.bm_global = (uint32_t *)p; p += s_bm;
+        uint8_t *const out_block = p;   // ids, distances, counts, ncand, ndots, hits of the batch's cells: one copy to the host
+        P.ids_out = (int32_t *)p; p += s_ids;
+        P.dist_out = (float *)p; p += s_ids;
+        P.count_out = (int32_t *)p; p += s_cf;
+        int32_t *cell_ncand = (int32_t *)p; p += s_cf;
+        int32_t *cell_ndots = (int32_t *)p; p += s_cf;
+        int32_t *d_hits = (int32_t *)p; p += s_cf;
+        float *d_thr = (float *)p; p += s_cf;   // (behind the block that goes to the host)
+        float *q_n16 = (float *)p; p += s_qf;
+        float *q_e16 = (float *)p; p += s_qf;
+        float *q_scale = (float *)p; p += s_qf;
+        _Float16 *Q16 = (_Float16 *)p; p += s_q16;
+        float *scores = (float *)p; p += s_scores;
+        uint64_t *d_ub = (uint64_t *)p; p += s_ub;
+        P.low = may_dense ? (float *)p : nullptr; p += s_low;
+        const bool dense = may_dense && dense_pays(nb);
+        P.zero_copy = 0;
+        P.stat = h->d_stat.p;
+        P.X16 = nullptr; P.xscale = nullptr; P.xn16 = P.xe16 = nullptr; P.delta = 0.f;
+        P.scores = nullptr; P.qscale = P.qn16 = P.qe16 = nullptr; P.eacc = P.eacc_big = 0.f; P.big_rows = 0;
+        P.Q = nullptr; P.items = nullptr; P.n_inline = 0;
+        if (q_host) {
+            HIP_TRY(hipMemsetAsync(Qd, 0, (size_t)nb * h->dpad * 4, h->stream));
+            HIP_TRY(hipMemcpy2DAsync(Qd, (size_t)h->dpad * 4, q_host + q0 * q_stride, (size_t)q_stride * 4, (size_t)h->dim * 4, (size_t)nb,
+                                     hipMemcpyDefault, h->stream));
+            P.Q = Qd;
+        } else {
+            HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+            P.items = d_items;
+        }
+        if (want_hits) {
+            HIP_TRY(hipMemcpyAsync(d_exi, ex_ids_host + q0 * k, (size_t)nb * k * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(d_exc, ex_count_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+        }
+        SweepArgs S;
+        S.n_t = n_t; S.n_s = n_s; S.nq = (int32_t)nb;
+        for (int i = 0; i < SWEEP_MAX_LIST; i++) {
+            S.trees[i] = i < n_t ? trees[i] : 0;
+            S.search_ks[i] = i < n_s ? search_ks[i] : 0;
+        }
+        S.root_pq = root_pq; S.cell_ncand = cell_ncand; S.cell_ndots = cell_ndots;
+        {
+            ScopedTimer tm(h, MORNA_T_QUERY, 0);
+            // root margins and the queries' norms, once, for the largest tree count
+            QueryParams PR = P;
+            PR.pq = root_pq;
+            const int nvq = h->dpad / 256;
+            const bool nv_ok = h->dpad % 256 == 0 && (nvq == 1 || nvq == 2 || nvq == 3 || nvq == 4 || nvq == 6 || nvq == 8 || nvq == 12);
+            if (nb >= 64 && nv_ok && N > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024) {
+                const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((T_max + QR_TREES - 1) / QR_TREES));
+                const size_t ql = (size_t)QR_Q * h->dpad * 4;
+#define ROOTSB(NVV)                                                                                                      \
+    do {                                                                                                                 \
+        if (ql > 48 * 1024)                                                                                              \
+            HIP_TRY(hipFuncSetAttribute((const void *)query_roots_batch_kernel<NVV>,                                      \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql));                           \
+        hipLaunchKernelGGL((query_roots_batch_kernel<NVV>), grid, dim3(QR_THREADS), ql, h->stream, PR, (int32_t)nb);     \
+    } while (0)
+                switch (nvq) {
+                case 1: ROOTSB(1); break;
+                case 2: ROOTSB(2); break;
+                case 3: ROOTSB(3); break;
+                case 4: ROOTSB(4); break;
+                case 6: ROOTSB(6); break;
+                case 8: ROOTSB(8); break;
+                default: ROOTSB(12); break;
+                }
+#undef ROOTSB
+            } else {
+                hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((T_max + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
+                                   h->stream, PR);
+            }
+            // one descent per virtual query
+            const size_t bl = bm_lds ? (size_t)bm_words * 4 : 0;
+#define DESCEND(NVV)                                                                                                              \
+    do {                                                                                                                          \
+        if (bm_lds) {                                                                                                             \
+            if (bl > 32 * 1024)                                                                                                   \
+                HIP_TRY(hipFuncSetAttribute((const void *)query_descend_sweep_kernel<true, NVV>,                                  \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bl));                                \
+            hipLaunchKernelGGL((query_descend_sweep_kernel<true, NVV>), dim3((unsigned)nv), dim3(WAVE), bl, h->stream, P, S);     \
+        } else {                                                                                                                  \
+            hipLaunchKernelGGL((query_descend_sweep_kernel<false, NVV>), dim3((unsigned)nv), dim3(WAVE), 0, h->stream, P, S);     \
+        }                                                                                                                         \
+    } while (0)
+            switch (h->dpad % 256 == 0 ? h->dpad / 256 : 0) {   // float4 per lane of a row
+            case 1: DESCEND(1); break;
+            case 2: DESCEND(2); break;
+            case 3: DESCEND(3); break;
+            case 4: DESCEND(4); break;
+            case 6: DESCEND(6); break;
+            case 8: DESCEND(8); break;
+            case 12: DESCEND(12); break;
+            default: DESCEND(0); break;
+            }
+#undef DESCEND
+            const int32_t bpv = (cap + Q_WAVES - 1) / Q_WAVES;
+            if (dense) {
+                // the contraction of the batch's queries against all rows, once (the 128 x 128 form for every row), and from
+                // it the bounds of every virtual query's candidates and every cell's threshold
+                const float *xn = h->half.xn.p;
+                P.X16 = h->half.x16.p;
+                P.xn16 = xn; P.xscale = xn + N; P.xe16 = xn + 2 * N;
+                P.eacc = mm16_eacc(h->dpad);
+                const _Float16 *q16 = P.X16;
+                const int32_t *qrow = P.items;
+                if (q_host) {
+                    split_mm_convert_rows(h, Qd, nb, Q16, q_n16, q_e16, q_scale, h->stream);
+                    q16 = Q16; qrow = nullptr;
+                    P.qn16 = q_n16; P.qe16 = q_e16; P.qscale = q_scale;
+                } else {
+                    P.qn16 = P.xn16; P.qe16 = P.xe16; P.qscale = P.xscale;
+                }
+                {
+                    ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
+                    const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N + 127) / 128);
+                    HIP_TRY(hipFuncSetAttribute((const void *)query_scores_kernel<128, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MM16_LDS));
+                    hipLaunchKernelGGL((query_scores_kernel<128, 64, 2>), dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS,
+                                       h->stream, P.X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, (int64_t)0);
+                }
+                P.scores = scores;
+                contraction_ran = true;
+                hipLaunchKernelGGL(sweep_bounds_kernel, dim3((unsigned)nv), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb, d_ub);
+                hipLaunchKernelGGL(sweep_threshold_kernel, dim3((unsigned)nc), dim3(Q_THREADS), 0, h->stream, P, n_s, (int32_t)nb,
+                                   cell_ncand, d_ub, d_thr);
+                HIP_TRY(hipMemsetAsync(h->d_stat.p + 3, 0, sizeof(unsigned long long), h->stream));
+                hipLaunchKernelGGL(sweep_cand_dots_kernel<true>, dim3((unsigned)(nv * bpv)), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb,
+                                   bpv, n_s, cell_ncand, d_thr);
+            } else {
+                hipLaunchKernelGGL(sweep_cand_dots_kernel<false>, dim3((unsigned)(nv * bpv)), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb,
+                                   bpv, n_s, cell_ncand, d_thr);
+            }
+            hipLaunchKernelGGL(sweep_topk_kernel, dim3((unsigned)nc), dim3(Q_THREADS), 0, h->stream, P, n_s, (int32_t)nb, cell_ncand);
+            if (want_hits)
+                hipLaunchKernelGGL(sweep_hits_kernel, dim3((unsigned)nc), dim3(WAVE), 0, h->stream, P.ids_out, P.count_out, d_exi, d_exc,
+                                   (int32_t)nb, k, d_hits);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h->host_out.p, out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->unsettled = false;
+        // the batch's block is [cell][nb]; the caller's arrays are [cell][nq]
+        const uint8_t *hb = h->host_out.p;
+        const int32_t *b_ids = (const int32_t *)hb, *b_cnt = (const int32_t *)(hb + 2 * s_ids), *b_nc = (const int32_t *)(hb + 2 * s_ids + s_cf),
+                      *b_nd = (const int32_t *)(hb + 2 * s_ids + 2 * s_cf), *b_hit = (const int32_t *)(hb + 2 * s_ids + 3 * s_cf);
+        const float *b_dist = (const float *)(hb + s_ids);
+        for (int64_t c = 0; c < n_cells; c++) {
+            const size_t row = (size_t)nb * 4;
+            if (ids_out) memcpy(ids_out + (c * nq + q0) * k, b_ids + c * nb * k, row * k);
+            if (dist_out) memcpy(dist_out + (c * nq + q0) * k, b_dist + c * nb * k, row * k);
+            if (count_out) memcpy(count_out + c * nq + q0, b_cnt + c * nb, row);
+            if (ncand_out) memcpy(ncand_out + c * nq + q0, b_nc + c * nb, row);
+            if (ndots_out) memcpy(ndots_out + c * nq + q0, b_nd + c * nb, row);
+            if (want_hits) memcpy(hits_out + c * nq + q0, b_hit + c * nb, row);
+        }
+        descents += (double)nv;
+        if (dense) {   // the candidates that passed their filter
+            unsigned long long kept = 0;
+            HIP_TRY(hipMemcpy(&kept, h->d_stat.p + 3, sizeof(kept), hipMemcpyDeviceToHost));
+            rows_dots += (double)kept;
+        } else
+        for (int64_t v = 0; v < nv; v++) {   // the deepest cell of every virtual query: the candidates that got a canonical dot
+            const int64_t ti = v / nb, q = v - ti * nb;
+            rows_dots += (double)std::min<int32_t>(b_nc[((ti * n_s) + (n_s - 1)) * nb + q], cap);
+        }
+    }
+    h->sweep_stats[0] = descents;
+    h->sweep_stats[1] = (double)n_cells * (double)nq;
+    h->sweep_stats[2] = rows_dots;
+    h->sweep_stats[3] = contraction_ran ? 1.0 : 0.0;
     return MORNA_OK;
 }
 

@@ -90,6 +90,94 @@ def restricted_search_k(n_trees, k, n_items, n_allowed):
     return min(int(n_trees) * int(k) * scale, INT32_MAX)
 
 
+TREES_SHARDS_REFUSAL = ("a search over the first trees of the forest (n_trees=, --use-trees, recall) is not available on an index "
+                        "of row shards (.shards.mor, one process per shard, --device a,b): run it on an index built without "
+                        "--shards")
+SWEEP_MAX_LIST = 64
+RECALL_MAX_K = 256
+
+
+def parse_int_list(text, what, all_value=None):
+    """"10,20,all" -> [10, 20, all_value]: a comma-separated list of positive integers, strictly ascending, 1 to 64 entries;
+    the literal `all` stands for all_value (the index's tree count) where one is given.  ValueError says what is wrong."""
+    out = []
+    for token in str(text).split(","):
+        token = token.strip()
+        if token == "all" and all_value is not None:
+            out.append(int(all_value))
+            continue
+        try:
+            value = int(token)
+        except ValueError:
+            raise ValueError("%s: %r is not an integer" % (what, token))
+        if value < 1:
+            raise ValueError("%s: %d is not positive" % (what, value))
+        out.append(value)
+    if len(out) > SWEEP_MAX_LIST:
+        raise ValueError("%s: %d entries, at most %d are taken" % (what, len(out), SWEEP_MAX_LIST))
+    for a, b in zip(out, out[1:]):
+        if b <= a:
+            raise ValueError("%s: %d follows %d, the entries must ascend strictly" % (what, b, a))
+    return out
+
+
+def recall_rows(trees, search_ks, hits, exact_count, ncand, ndots, q):
+    """The lines of one query's block of `morna recall`: per cell (trees, search_k, hits, exact results, recall, candidates,
+    hyperplane dots); recall is hits / exact results (0.0 when the exact search found nothing), None -- with hits -1 --
+    when the exact search failed for the query."""
+    rows = []
+    for i, t in enumerate(trees):
+        for j, s in enumerate(search_ks):
+            h, e = int(hits[i][j][q]), int(exact_count[q])
+            recall = None if h < 0 else (float(h) / e if e > 0 else 0.0)
+            rows.append((int(t), int(s), h, e, recall, int(ncand[i][j][q]), int(ndots[i][j][q])))
+    return rows
+
+
+def recall_summary(trees, search_ks, hits, exact_count, ncand, ndots):
+    """(rows, failed): per cell (trees, search_k, mean recall, minimum recall, queries with recall 1, mean
+    candidates, mean hyperplane dots) over the queries whose exact search succeeded (hits >= 0); `failed` is the number left
+    out.  With no query counted the means are None."""
+    hits, ncand, ndots = np.asarray(hits), np.asarray(ncand), np.asarray(ndots)
+    exact_count = np.asarray(exact_count)
+    nq = len(exact_count)
+    rows = []
+    ok = [q for q in range(nq) if exact_count[q] >= 0]
+    for i, t in enumerate(trees):
+        for j, s in enumerate(search_ks):
+            rec = [r[4] for r in (recall_rows(trees[i:i + 1], search_ks[j:j + 1], hits[i:i + 1, j:j + 1], exact_count,
+                                              ncand[i:i + 1, j:j + 1], ndots[i:i + 1, j:j + 1], q)[0] for q in ok)]
+            if not ok:
+                rows.append((int(t), int(s), None, None, 0, None, None))
+                continue
+            rows.append((int(t), int(s), sum(rec) / len(ok), min(rec), sum(1 for r in rec if r == 1.0),
+                         float(sum(int(ncand[i][j][q]) for q in ok)) / len(ok), float(sum(int(ndots[i][j][q]) for q in ok)) / len(ok)))
+    return rows, nq - len(ok)
+
+
+def format_recall_rows(rows):
+    """One tab-separated line per row of recall_rows / recall_summary: floats with six digits, None as "nan"."""
+    def cell(v):
+        if v is None:
+            return "nan"
+        return "%.6f" % v if isinstance(v, float) else str(v)
+    return "".join("\t".join(cell(v) for v in row) + "\n" for row in rows)
+
+
+class SearchRecall(object):
+    """MornaSearch.search_recall: trees, search_ks, and per cell hits / ncand / ndots [n_t, n_s, nq], exact_count [nq]."""
+
+    def __init__(self, trees, search_ks, out):
+        self.trees, self.search_ks = list(trees), list(search_ks)
+        self.hits, self.exact_count, self.ncand, self.ndots = out["hits"], out["exact_count"], out["ncand"], out["ndots"]
+
+    def rows(self, q):
+        return recall_rows(self.trees, self.search_ks, self.hits, self.exact_count, self.ncand, self.ndots, q)
+
+    def summary(self):
+        return recall_summary(self.trees, self.search_ks, self.hits, self.exact_count, self.ncand, self.ndots)
+
+
 class SearchRestriction(object):
     """MornaSearch.restriction: allow (booleans [n] or None), item_group (int32 [n] or None), the counts, and `handle`,
     the annoy.Restriction on the index's device."""
@@ -187,8 +275,23 @@ class MornaSearch(object):
         sample_ids = [self.inverse_lookup(internal_id) for internal_id in results[0]]
         return results + (lookup_meta(self.basename, sample_ids),)
 
-    def search_nn(self, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None):
-        """Approximate neighbours of query_sample (morna.py:632-678); restriction: MornaSearch.restriction."""
+    def _check_trees(self, n_trees, restriction=None):
+        """n_trees= of the searches: None, or a count the one-handle index searches the first trees with."""
+        if n_trees is None:
+            return
+        if restriction is not None:
+            raise ValueError("n_trees cannot be used with a restriction")
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(TREES_SHARDS_REFUSAL)
+
+    def search_nn(self, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None, n_trees=None):
+        """Approximate neighbours of query_sample (morna.py:632-678); restriction: MornaSearch.restriction; n_trees: search
+        the first n_trees trees only -- the answer of an index built with --n-trees n_trees."""
+        self._check_trees(n_trees, restriction)
+        if n_trees is not None:
+            ids, d, cnt = self.annoy_index.get_nns_by_vector_batch(np.array([self.query_sample], dtype=np.float32), num_neighbors,
+                                                                   search_k, n_trees=n_trees)
+            return self._batch_results(ids, d, cnt, include_distances, meta_db)[0]
         if restriction is not None:
             self._check_restriction(restriction, None)
             ids, d, cnt = self.annoy_index.get_nns_restricted(
@@ -332,11 +435,16 @@ class MornaSearch(object):
         return pop[restriction.allow]
 
     def search_nn_batch(self, batch, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None,
-                        query_groups=None):
+                        query_groups=None, n_trees=None):
         """search_nn for every query of `batch`: a list of result tuples, in query order.  restriction / query_groups:
-        MornaSearch.restriction and the group label every query carries (positions in its groups, negative: none)."""
+        MornaSearch.restriction and the group label every query carries (positions in its groups, negative: none);
+        n_trees: as search_nn."""
         self._check_batch(batch)
         self._check_restriction(restriction, query_groups)
+        self._check_trees(n_trees, restriction)
+        if n_trees is not None:
+            ids, d, cnt = self.annoy_index.get_nns_by_query_rows(num_neighbors, search_k, n_trees=n_trees)
+            return self._batch_results(ids, d, cnt, include_distances, meta_db)
         if restriction is not None:
             ids, d, cnt = self.annoy_index.get_nns_restricted(
                 restriction.handle, num_neighbors, self._restricted_search_k(restriction, num_neighbors, search_k),
@@ -364,8 +472,27 @@ class MornaSearch(object):
             ids, d, cnt = self.annoy_index.exact_search_query_rows(num_neighbors)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
+    def search_recall(self, queries, num_neighbors, trees, search_ks):
+        """The recall of the approximate search against the exact one for every (tree count, search_k) of a grid, from this
+        one index (AnnoyIndex.recall_sweep).  queries: a QueryBatch (queries_from_intropolis) or a list of
+        INTERNAL ids.  trees / search_ks: strictly ascending positive integers, at most 64 each, trees at most the index's
+        tree count; num_neighbors at most 256.  Returns a SearchRecall."""
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(TREES_SHARDS_REFUSAL)
+        trees, search_ks = [int(t) for t in trees], [int(s) for s in search_ks]
+        if isinstance(queries, QueryBatch):
+            self._check_batch(queries)
+            out = self.annoy_index.recall_sweep(num_neighbors, trees, search_ks)
+        else:
+            out = self.annoy_index.recall_sweep(num_neighbors, trees, search_ks, items=np.array(list(queries), np.int32))
+        return SearchRecall(trees, search_ks, out)
+
     def search_member_n_batch(self, query_ids, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None,
-                              query_groups=None):
+                              query_groups=None, n_trees=None):
         """search_member_n for several indexed sample ids, searched together (get_nns_by_item_batch); an unknown id fails
         before any search, with search_member_n's message.  Returns (internal ids, list of result tuples).  restriction:
         MornaSearch.restriction; query_groups None under a restriction with groups: every query carries its own sample's
@@ -383,6 +510,11 @@ class MornaSearch(object):
                                  + "in the index.")
             internal.append(self.internal_id_map[query_id])
         self._check_restriction(restriction, query_groups)
+        self._check_trees(n_trees, restriction)
+        if n_trees is not None:
+            ids, d, cnt = self.annoy_index.get_nns_by_item_batch(np.array(internal, np.int32), num_neighbors, search_k,
+                                                                 n_trees=n_trees)
+            return internal, self._batch_results(ids, d, cnt, include_distances, meta_db)
         if restriction is not None:
             if query_groups is None:
                 query_groups = restriction.own_groups(internal)
@@ -592,8 +724,9 @@ class MornaSearch(object):
         ids = self._unhashed_ids(ids, restriction)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
-    def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False):
-        """Neighbours of an indexed sample (morna.py:733-787)."""
+    def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False, n_trees=None):
+        """Neighbours of an indexed sample (morna.py:733-787); n_trees: as search_nn."""
+        self._check_trees(n_trees)
         print("querying by sample id " + str(query_id))
         try:
             internal_id = self.internal_id_map[query_id]
@@ -603,6 +736,9 @@ class MornaSearch(object):
                              + "sample id. Likely no sample with that id was included "
                              + "in the index.")
         print("this is internal id " + str(internal_id))
+        if n_trees is not None:
+            results = self.annoy_index.get_nns_by_item(internal_id, num_neighbors, search_k, include_distances, n_trees=n_trees)
+            return self._with_meta(results if include_distances else (results,), meta_db)
         if include_distances:
             results = self.annoy_index.get_nns_by_item(internal_id, num_neighbors, search_k, include_distances)
         else:
