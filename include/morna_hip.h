@@ -368,6 +368,44 @@ int morna_jthinned_job(const morna_jthinned *r, int64_t q, const int32_t **lines
 int morna_jthinned_free(morna_jthinned *r);
 int morna_jstore_thin_stats(const morna_jstore *s, double *stats);
 
+/*
+ * ---- hashed rows from store rows: an index of any width from the store ---------------------------------
+ * The store holds every sample's (line, coverage) list in ascending line order, which is file order, so a sample's hashed row
+ * at ANY width is a function of its store row, the weights of morna_jstore_set_weights and one int32 hash per line (the
+ * murmur3 of the line's "chrom start end" key, morna_hash32 / morna_hash_keys).  After the call the items of h are exactly
+ * 0 .. n - 1; item i is the hashed row, at h's dim D, of store sample ext[i] (an EXTERNAL id; the same id may be named more
+ * than once).  Cell c of item i: start from S = +0.0; take every entry (j, cov) of the row in ascending j for which
+ * w[j] != 0 and floormod(line_hash[j], D) == c (Python's floored modulo); for each, S = RN(S + sgn_j * RN(double(cov) * w[j])),
+ * sgn_j = -1 when line_hash[j] < 0, else +1 (the sign is taken before the modulo, morna.py:370-371); the cell is S rounded
+ * once to fp32.  fp64 throughout, one rounding per operation, no FMA: morna.py:376-388 followed by add_item's fp64 -> fp32.
+ * cov is any int32; pad columns are 0.  The canonical norms are made as morna_build_features makes them, and everything that
+ * hangs on the rows is invalidated as it invalidates it.  Nothing but ext, and line_hash when it differs from the last call's,
+ * crosses PCIe.  The result depends on (row, w, line_hash, D) alone: not on the batch, the row's place in ext, or the order in
+ * which workgroups finish; two calls give the same bytes.  For a file without repeated junctions, with the weights of its
+ * index, the rows are the rows morna_build_features makes at that width, bit for bit.
+ *   morna_add_items_from_store    checks first, all before any GPU work and with the store and the handle left usable: a null
+ *                                 pointer, n_lines that is not the store's, or a handle and a store on different devices (the
+ *                                 message names both): MORNA_E_INVALID; a store without weights: MORNA_E_STATE; a built index:
+ *                                 MORNA_E_STATE with morna_add_items_f32's message; an id the store lacks: MORNA_E_RANGE naming
+ *                                 it; n = 0: MORNA_E_EMPTY as morna_build_features; a dim past the row-width limit: what
+ *                                 morna_build returns.  A workgroup per named row, its fp64 cells in LDS; the call returns when
+ *                                 the rows and their norms are made.
+ *   morna_jstore_hash_rows_stats  of the last call, stats[4]: kernel ms (HIP events), bytes read (8 per entry of every named
+ *                                 row, plus 12 per line for hash and weight, counted once), bytes written (4 n dpad, dpad = dim
+ *                                 rounded up to 256), workgroups.  All 0 after a call that failed its checks.  The timers of
+ *                                 retain, nearest, recovery, pool and thin stay their own.
+ *   morna_jstore_row_norms        pp_out[n]: the unhashed squared norm of store rows ext[n] (ids may repeat) under the weights
+ *                                 set, the pp of the unhashed search's contract: x = RN(x + RN(v * v)), v = RN(double(cov) * w),
+ *                                 over the row's entries in line order from 0.0.  Computed for the rows named, whatever the
+ *                                 last search cached.  Null pointer: MORNA_E_INVALID; no weights: MORNA_E_STATE; an id the
+ *                                 store lacks: MORNA_E_RANGE naming it; a negative coverage: MORNA_E_INVALID naming sample and
+ *                                 line, as morna_jstore_nearest_by_sample.
+ */
+int morna_add_items_from_store(morna_index *h, morna_jstore *s, const int64_t *ext /* [n] */, int64_t n,
+                               const int32_t *line_hash /* [n_lines] */, int64_t n_lines);
+int morna_jstore_hash_rows_stats(const morna_jstore *s, double *stats /* [4] */);
+int morna_jstore_row_norms(morna_jstore *s, const int64_t *ext /* [n] */, int64_t n, double *pp_out /* [n] */);
+
 /* AnnoyIndex.get_n_items()                                     morna.py:1174 */
 int64_t morna_get_n_items(const morna_index *h);
 /* AnnoyIndex.get_item_vector(i)                                morna.py:702 */

@@ -90,6 +90,9 @@ SIGNATURES = {
     "morna_jthinned_job": (C.c_int, [_p, _i64] + [C.POINTER(_p)] * 2),
     "morna_jthinned_free": (C.c_int, [_p]),
     "morna_jstore_thin_stats": (C.c_int, [_p, _p]),
+    "morna_add_items_from_store": (C.c_int, [_p, _p, _p, _i64, _p, _i64]),
+    "morna_jstore_hash_rows_stats": (C.c_int, [_p, _p]),
+    "morna_jstore_row_norms": (C.c_int, [_p, _p, _i64, _p]),
     "morna_merge_topk": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_vector_packed": (C.c_int, [_p, _p, _i64, _i32, _i32, _i64, _p]),
     "morna_merge_topk_packed": (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),

@@ -80,6 +80,18 @@ class AnnoyIndex(object):
             raise IndexError("rows must be [n, %d]" % self.f)
         check(lib().morna_add_items_f32(self._h, int(first_id), ptr(rows), rows.shape[0]))
 
+    def add_items_from_store(self, store, sample_ids, line_hash):
+        """The items become 0 .. len(sample_ids) - 1: item i the hashed row, at this index's width, of the junction store's
+        sample sample_ids[i] (external ids; repeats allowed), made on the GPU from the store row, the store's weights
+        (JunctionStore.set_weights) and line_hash, the int32 hash of every line's key (junctions.line_hashes).  Only the ids,
+        and the hashes when they differ from the last call's, go to the device (include/morna_hip.h, "hashed rows from store
+        rows").  IndexError for an id the store lacks, RuntimeError for a built index or a store without weights."""
+        ids = np.ascontiguousarray([int(s) for s in sample_ids], dtype=np.int64)
+        line_hash = np.ascontiguousarray(line_hash, dtype=np.int32)
+        if line_hash.ndim != 1:
+            raise ValueError("add_items_from_store takes one hash per line (a 1-d array)")
+        check(lib().morna_add_items_from_store(self._h, store._p, ptr(ids), len(ids), ptr(line_hash), len(line_hash)))
+
     def get_n_items(self):
         return int(lib().morna_get_n_items(self._h))
 

@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -57,6 +57,13 @@ makes by eye from five indexes and fifty result files.  One index, one exact sea
 N11): tree i of a forest does not depend on the trees behind it, so the first t trees of the index ARE the index --n-trees t
 builds.  `search --use-trees t` searches with those trees alone.
 
+`hashing` answers what --features costs on an index: for every width of its --features list it hashes the index's items again
+at that width, on the GPU and straight from the junction store (the weights of <basename>.jw.mor, the line hashes of
+--junction-file), and prints how many of a sample's unhashed neighbours (`search --unhashed`) the exact search in that hashed
+space returns, the mean distance error over the shared ones, with --n-trees the same for a forest search, and over all items
+the mean and variance of hashed norm / unhashed norm -- experiment 2 of the reference's tests/README.md (test_norm_estimator.py)
+on real rows.  One index; the population is the index's items at every width.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -81,6 +88,7 @@ here do the latter.
     python -m morna_amd.cli recovery -x idx --query-ids 12,34 -r 20 --leave-out-groups donors.tsv
     python -m morna_amd.cli search -x idx -q 1234 --use-trees 50 --search-k 1000 -d
     python -m morna_amd.cli recall -x idx --sample 100 -r 20 --trees 10,20,50,100,all --search-ks 100,200,500,1000,4000 --summary-only
+    python -m morna_amd.cli hashing -x idx --junction-file junctions.tsv.gz --sample 100 -r 20 --features 500,1000,3000,8192,index
 """
 import argparse
 import sys
@@ -283,6 +291,37 @@ def build_parser():
     recall_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
                                help='print only the table over all queries')
     recall_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    hashing_parser = subparsers.add_parser('hashing', help='tabulates what each --features value costs in neighbours and in norm '
+                                                           'distortion against the unhashed search, from one index with a '
+                                                           'junction store')
+    hashing_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                                help='basename of an index built with --junction-store (an index without row shards)')
+    hashing_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
+                                help='path to the (gzipped) intropolis file the index was made from')
+    hashing_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
+                                help='the query is the sample already in the index with this sample id')
+    hashing_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                                help='comma-separated sample ids already in the index')
+    hashing_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
+                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
+    hashing_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                                help='the seed of --sample (default 0)')
+    hashing_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20,
+                                help='the number of nearest neighbor results compared (at most 256)')
+    hashing_parser.add_argument('--features', metavar='<d1,d2,...>', type=str, required=True,
+                                help='hashed widths, ascending, at most 16, each 1 to 32768; "index" stands for the index\'s own')
+    hashing_parser.add_argument('--n-trees', metavar='<int>', type=int, required=False, default=None,
+                                help='also build a forest of this many trees at every width and search it')
+    hashing_parser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
+                                help='search_k of the forest search (with --n-trees; default 100)')
+    hashing_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                                help='print only the table over all queries')
+    hashing_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    # flags of `search` that have no meaning here: taken so that they can be refused with a reason
+    hashing_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    hashing_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    for flag in ('--within', '--without', '--leave-out-groups', '--intropolis'):
+        hashing_parser.add_argument(flag, type=str, required=False, default=None, help=argparse.SUPPRESS)
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
     super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
@@ -486,6 +525,57 @@ def _check_recall_flags(parser, args):
                      "10,20,50 (%s)" % e)
 
 
+def _check_hashing_flags(parser, args):
+    """`hashing`: the flags of `search` that make no sense here, exactly one query source, -r within the limit and the
+    --features list (`index` is resolved once the index is read)."""
+    from .search import RECALL_MAX_K, parse_features_list
+    refused = (("-e/--exact", args.exact, "every width is searched exactly already; --n-trees adds the forest search"),
+               ("--unhashed", args.unhashed, "the unhashed search is the truth every width is compared with"),
+               ("--within", args.within is not None, "the population is the index's items at every width"),
+               ("--without", args.without is not None, "the population is the index's items at every width"),
+               ("--leave-out-groups", args.leave_out_groups is not None, "the population is the index's items at every width"),
+               ("--intropolis", args.intropolis is not None,
+                "the queries are samples of the index, whose rows the junction store holds: name them with -q, --query-ids or "
+                "--sample"))
+    for flag, on, why in refused:
+        if on:
+            parser.error("hashing cannot be used with %s: %s" % (flag, why))
+    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+                                   ("--sample", args.sample is not None)) if on]
+    if len(given) != 1:
+        parser.error("hashing needs exactly one query source: -q, --query-ids or --sample"
+                     + (" (got %s)" % " and ".join(given) if given else ""))
+    if args.query_ids is not None:
+        try:
+            args.query_ids = [int(t) for t in args.query_ids.split(',')]
+        except ValueError:
+            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
+    if args.sample is None and getattr(args, "sample_seed_given", False):
+        parser.error("--sample-seed cannot be used without --sample")
+    if args.sample is not None and args.sample < 1:
+        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
+    if not 1 <= args.results <= RECALL_MAX_K:
+        parser.error("-r %d: hashing compares 1 to %d results" % (args.results, RECALL_MAX_K))
+    if args.n_trees is None and getattr(args, "search_k_given", False):
+        parser.error("--search-k cannot be used without --n-trees")
+    if args.n_trees is not None and args.n_trees < 1:
+        parser.error("--n-trees takes a positive tree count (got %d)" % args.n_trees)
+    if args.search_k < 1:
+        parser.error("--search-k takes a positive number (got %d)" % args.search_k)
+    try:
+        tokens = [t.strip() for t in args.features.split(",")]
+        if tokens.count("index") > 1:
+            raise ValueError("--features: 'index' is named twice")
+        rest = [t for t in tokens if t != "index"]
+        if len(tokens) > 16:
+            raise ValueError("--features: %d entries, at most 16 are taken" % len(tokens))
+        if rest:
+            parse_features_list(",".join(rest))           # (checked again, in place, with the index's width)
+    except ValueError as e:
+        parser.error("--features takes comma-separated widths in ascending order, at most 16, each 1 to 32768 or the word "
+                     "index, such as 500,3000,index (%s)" % e)
+
+
 def _check_batch_flags(parser, args):
     """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
     batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
@@ -552,6 +642,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_use_trees_flags(parser, args)
     if args.subparser_name == 'recall':
         _check_recall_flags(parser, args)
+    if args.subparser_name == 'hashing':
+        _check_hashing_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -571,6 +663,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _supersample(args, stdout)
     if args.subparser_name == 'recall':
         return _recall(args, stdout)
+    if args.subparser_name == 'hashing':
+        return _hashing(args, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -682,6 +776,47 @@ def _recall(args, stdout):
     stdout.write(format_recall_rows(rows))
     if failed > 0:
         stdout.write("# exact search failed for %d queries\n" % failed)
+    return 0
+
+
+def _hashing(args, stdout):
+    """`hashing`: the unhashed neighbours of the queries once, then for every width of --features the index's items hashed
+    again from the junction store and searched on the GPU; a block per query and the table over all of them."""
+    import os
+    import numpy as np
+    from .junctions import STORE_SUFFIX, WEIGHTS_SUFFIX
+    from .search import HASHING_SHARDS_REFUSAL, MornaSearch, format_hashing_rows, parse_features_list
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
+    if os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(HASHING_SHARDS_REFUSAL)
+    if not os.path.exists(args.basename + STORE_SUFFIX):
+        raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
+                      % (args.basename + STORE_SUFFIX))
+    if not os.path.exists(args.basename + WEIGHTS_SUFFIX):
+        raise IOError("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
+                      "to the junction store. They are not written when a junction repeats in the indexed file: "
+                      "the unhashed search is defined for files without repeated junctions" % (args.basename + WEIGHTS_SUFFIX))
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    dims = parse_features_list(args.features, index_dim=searcher.dim)
+    if args.sample is not None:
+        inv = searcher._inverse_map()
+        n = searcher.annoy_index.get_n_items()
+        if args.sample > n:
+            raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
+        picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
+        labels = [inv[int(i)] for i in picked]
+    else:
+        labels = args.query_ids if args.query_ids is not None else [args.query_id]
+    table = searcher.hashing_sweep(labels, args.results, dims, args.junction_file, n_trees=args.n_trees,
+                                   search_k=args.search_k if args.n_trees is not None else None)
+    if not args.summary_only:
+        for q, label in enumerate(labels):
+            stdout.write("# query %s\n" % label)
+            stdout.write(format_hashing_rows(table.rows(q)))
+    stdout.write("# all %d queries\n" % len(labels))
+    stdout.write(format_hashing_rows(table.summary()))
     return 0
 
 

@@ -34,6 +34,13 @@ struct morna_jstore {
     // of the last thin: kernel ms, bytes read and written, draws made, workgroups per pass
     double thin_ms = 0;
     int64_t thin_read = 0, thin_written = 0, thin_draws = 0, thin_groups = 0;
+    // hashed rows (hashrows.hip): the line hashes of the last call, here and in HBM; every line's column and signed weight at
+    // that call's width; the named rows; of the last call: kernel ms, bytes read and written, workgroups
+    std::vector<int32_t> hr_hash;
+    bool hr_hash_resident = false;
+    morna::DevBuf<int32_t> d_hr_hash, d_hr_col, d_hr_rows;
+    morna::DevBuf<double> d_hr_sw;
+    double hr_stats[4] = {0, 0, 0, 0};
     std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
     ~morna_jstore()
     {
@@ -46,6 +53,8 @@ namespace morna {
 
 // the store's stream exists and its host image is in HBM (jstore.hip)
 int jstore_make_resident(morna_jstore *st);
+// the weights of morna_jstore_set_weights in the store's HBM (nearest.hip); the store has weights
+int jstore_device_weights(morna_jstore *st, const double **d_w);
 
 // The body of a C entry point: its code, or `code` with the error "<who>: <what>" for an exception that leaves it.
 template <typename F>

@@ -490,7 +490,68 @@ int begin(morna_jstore *s, const int64_t *pop_ext, int64_t n_pop, int64_t nq, in
 
 }  // namespace
 
+int morna::jstore_device_weights(morna_jstore *st, const double **d_w)
+{
+    MORNA_TRY(prepare_weights(st, st->nearest.get()));
+    *d_w = st->nearest->d_w.p;
+    return MORNA_OK;
+}
+
 extern "C" {
+
+int morna_jstore_row_norms(morna_jstore *s, const int64_t *ext, int64_t n, double *pp_out)
+{
+    if (!s || n < 0 || (n > 0 && (!ext || !pp_out))) {
+        set_error("jstore_row_norms: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (!s->nearest) {
+        set_error("jstore_row_norms: the store has no weights: call morna_jstore_set_weights first");
+        return MORNA_E_STATE;
+    }
+    if (n > INT32_MAX / 16) {
+        set_error("jstore_row_norms: %lld samples: at most %d", (long long)n, INT32_MAX / 16);
+        return MORNA_E_INVALID;
+    }
+    return guarded("jstore_row_norms", MORNA_E_INVALID, [&] {
+        std::vector<int32_t> rows((size_t)n);
+        for (int64_t p = 0; p < n; p++) {
+            auto it = s->row_of.find(ext[p]);
+            if (it == s->row_of.end()) {
+                set_error("jstore_row_norms: sample id %lld (entry %lld) is not in the junction store", (long long)ext[p], (long long)p);
+                return MORNA_E_RANGE;
+            }
+            rows[(size_t)p] = it->second;
+        }
+        if (n == 0) return MORNA_OK;
+        MORNA_TRY(morna::jstore_make_resident(s));
+        morna_jnearest *nr = s->nearest.get();
+        MORNA_TRY(prepare_weights(s, nr));
+        // buffers of the call's own: the cached population and its norms stay what the last search left
+        DevBuf<int32_t> d_rows;
+        DevBuf<double> d_pp;
+        DevBuf<unsigned long long> d_err;
+        MORNA_TRY(d_rows.alloc((size_t)n));
+        MORNA_TRY(d_pp.alloc((size_t)n));
+        MORNA_TRY(d_err.alloc(1));
+        HIP_TRY(hipMemcpy(d_rows.p, rows.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        const unsigned long long none = ~0ull;
+        HIP_TRY(hipMemcpy(d_err.p, &none, sizeof(none), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(jnearest_norms_kernel, dim3((unsigned)((n + JN_WAVES - 1) / JN_WAVES)), dim3(JN_THREADS), 0, s->stream, s->d_ptr.p,
+                           s->d_line.p, s->d_cov.p, nr->d_w.p, d_rows.p, n, d_pp.p, d_err.p);
+        HIP_TRY(hipGetLastError());
+        unsigned long long err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(pp_out, d_pp.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (err != ~0ull) {
+            set_error("jstore_row_norms: sample id %lld has a negative coverage at line %lld: the unhashed search takes coverages >= 0",
+                      (long long)ext[(size_t)(err >> 32)], (long long)(err & 0xffffffffull));
+            return MORNA_E_INVALID;
+        }
+        return MORNA_OK;
+    });
+}
 
 int morna_jstore_set_weights(morna_jstore *s, const double *w, int64_t n_lines)
 {

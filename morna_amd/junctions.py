@@ -500,6 +500,24 @@ class JunctionStore(object):
         return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "draws": int(s[3]),
                 "workgroups": int(s[4])}
 
+    # ---- hashed rows of any width (AnnoyIndex.add_items_from_store) ----------------------------------------
+    def hash_rows_stats(self):
+        """Of the last AnnoyIndex.add_items_from_store over this store: kernel ms (HIP events), bytes read (8 per entry of
+        every named row, 12 per line for hash and weight), bytes written (4 per padded cell) and workgroups; all 0 after a
+        refused call."""
+        s = np.zeros(4, np.float64)
+        check(lib().morna_jstore_hash_rows_stats(self._p, ptr(s)))
+        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "workgroups": int(s[3])}
+
+    def row_norms(self, sample_ids):
+        """The unhashed squared norm (fp64) of the store rows of `sample_ids` (external ids; repeats allowed) under the
+        weights set: the pp of the unhashed search.  IndexError for an id the store lacks, RuntimeError without weights,
+        ValueError for a row with a negative coverage."""
+        ids = np.ascontiguousarray([int(s) for s in sample_ids], np.int64)
+        out = np.zeros(len(ids), np.float64)
+        check(lib().morna_jstore_row_norms(self._p, ptr(ids), len(ids), ptr(out)))
+        return out
+
     def retain(self, result_sample_ids, frequency_filter, coverage_filter):
         """The retention step (morna.py:1539-1569) for every list of `result_sample_ids` (external sample ids in rank
         order, at most 64 per list) in one call on the GPU.  Returns one Retained per list."""
@@ -634,6 +652,20 @@ def key_lines(junction_file, n_lines=None):
         raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
                          % (junction_file, parsed.lines_read, int(n_lines)))
     return {key: j for j, key in enumerate(_line_keys(parsed))}
+
+
+def line_hashes(junction_file, n_lines, handle):
+    """The int32 hash of every line's "chrom start end" key (mmh3.hash, morna.py:369), in line order, from the key arrays
+    of a threshold-0 parse of the indexed file through morna_hash_keys on `handle` (an AnnoyIndex; its items are not
+    touched): what AnnoyIndex.add_items_from_store takes.  ValueError when the file's line count is not `n_lines` (the
+    store's)."""
+    from .index import ParsedLines
+    parsed = ParsedLines(junction_file, sample_count=1, sample_threshold=0)
+    if n_lines is not None and parsed.lines_read != int(n_lines):
+        raise ValueError("%s has %d lines, the junction store has %d: it is not the file that was indexed"
+                         % (junction_file, parsed.lines_read, int(n_lines)))
+    a = parsed.arrays()
+    return handle.hash_keys(a["key_bytes"], a["key_off"])[0]
 
 
 def query_terms(coverage_by_key, key_line, w):

@@ -164,6 +164,117 @@ def format_recall_rows(rows):
     return "".join("\t".join(cell(v) for v in row) + "\n" for row in rows)
 
 
+HASHING_SHARDS_REFUSAL = ("hashing is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                          "run it on an index built without --shards")
+HASHING_MAX_DIMS = 16
+HASHING_MAX_FEATURES = 32768
+HASHING_SEARCH_K = 100          # morna's default: search --search-k
+
+
+def parse_features_list(text, index_dim=None):
+    """--features "500,1000,index" of `morna hashing` -> [500, 1000, index_dim]: parse_int_list's ascending positive
+    integers, `index` the index's own width; at most 16 entries, each 1 to 32768.  ValueError says what is wrong."""
+    tokens = [t.strip() for t in str(text).split(",")]
+    if index_dim is None and "index" in tokens:
+        raise ValueError("--features: 'index' needs an index to stand for")
+    dims = parse_int_list(",".join(str(int(index_dim)) if t == "index" else t for t in tokens), "--features")
+    if len(dims) > HASHING_MAX_DIMS:
+        raise ValueError("--features: %d entries, at most %d are taken" % (len(dims), HASHING_MAX_DIMS))
+    for d in dims:
+        if d > HASHING_MAX_FEATURES:
+            raise ValueError("--features: %d is above %d, the widest row an index takes" % (d, HASHING_MAX_FEATURES))
+    return dims
+
+
+def drop_query(ids, dists, me, r):
+    """A result list without the query `me` and without the -1 of a short list, cut to r: the `others` of
+    scripts/recall_vs_unhashed.py, with the distances kept beside the ids."""
+    kept = [(int(i), float(d)) for i, d in zip(ids, dists) if int(i) != int(me) and int(i) >= 0][:int(r)]
+    return [i for i, _ in kept], [d for _, d in kept]
+
+
+def _hashing_cells(truth, found):
+    """(hits, recall, dist_err) of one found list against the truth, both (ids, distances)."""
+    t_ids, t_d = truth
+    f_ids, f_d = found
+    at = dict(zip(f_ids, f_d))
+    shared = [(t_d[j], at[i]) for j, i in enumerate(t_ids) if i in at]
+    hits = len(shared)
+    recall = float(hits) / len(t_ids) if len(t_ids) else None
+    dist_err = sum(abs(h - u) for u, h in shared) / hits if hits else None
+    return hits, recall, dist_err
+
+
+def hashing_rows(dims, truth, exact, approx=None):
+    """The lines of one query's block of `morna hashing`.  truth: (ids, distances) of the unhashed search with the query
+    dropped; exact[i] / approx[i]: the same of the exact / the forest search in the dims[i]-wide hashed space (approx None
+    without --n-trees).  Per D: (features, truth, hits, recall, dist_err[, hits_approx, recall_approx]); recall is None when
+    the truth is empty, dist_err -- the mean of abs(hashed distance - unhashed distance) over the shared ids -- None when
+    there are none."""
+    rows = []
+    for i, d in enumerate(dims):
+        hits, recall, dist_err = _hashing_cells(truth, exact[i])
+        row = (int(d), len(truth[0]), hits, recall, dist_err)
+        if approx is not None:
+            a_hits, a_recall, _ = _hashing_cells(truth, approx[i])
+            row += (a_hits, a_recall)
+        rows.append(row)
+    return rows
+
+
+def norm_ratio_stats(norm2, pp):
+    """(mean, population variance) of sqrt(norm2) / sqrt(pp) over the items with pp != 0: how well the hashed rows keep the
+    norms of the unhashed ones (the reference's test_norm_estimator.py with the vector's norm divided out).  (None, None)
+    when no item has a norm."""
+    norm2, pp = np.asarray(norm2, np.float64), np.asarray(pp, np.float64)
+    keep = pp != 0.0
+    if not keep.any():
+        return None, None
+    ratio = np.sqrt(norm2[keep]) / np.sqrt(pp[keep])
+    mean = float(ratio.sum() / len(ratio))
+    return mean, float(((ratio - mean) ** 2).sum() / len(ratio))
+
+
+def hashing_summary(tables, norm_stats):
+    """The block over all queries from the queries' own (hashing_rows): per D the truths and hits summed, recall their
+    quotient, dist_err the mean of the queries' dist_err (those that have one), then norm_stats[i] = (norm_ratio_mean,
+    norm_ratio_var) of that D."""
+    tables = list(tables)
+    out = []
+    for i, cell in enumerate(zip(*tables)):
+        truth, hits = sum(r[1] for r in cell), sum(r[2] for r in cell)
+        errs = [r[4] for r in cell if r[4] is not None]
+        row = (cell[0][0], truth, hits, float(hits) / truth if truth else None, sum(errs) / len(errs) if errs else None)
+        if len(cell[0]) > 5:
+            a_hits = sum(r[5] for r in cell)
+            row += (a_hits, float(a_hits) / truth if truth else None)
+        out.append(row + tuple(norm_stats[i]))
+    return out
+
+
+def format_hashing_rows(rows):
+    """One tab-separated line per row of hashing_rows / hashing_summary: floats with six digits, None as "-"."""
+    def cell(v):
+        if v is None:
+            return "-"
+        return "%.6f" % v if isinstance(v, float) else str(v)
+    return "".join("\t".join(cell(v) for v in row) + "\n" for row in rows)
+
+
+class SearchHashing(object):
+    """MornaSearch.hashing_sweep: dims, tables[q] (hashing_rows of query q), norm_stats[i] of dims[i], and kernel_ms[i], the
+    time of the rows' kernel at dims[i]."""
+
+    def __init__(self, dims, tables, norm_stats, kernel_ms):
+        self.dims, self.tables, self.norm_stats, self.kernel_ms = list(dims), tables, norm_stats, kernel_ms
+
+    def rows(self, q):
+        return self.tables[q]
+
+    def summary(self):
+        return hashing_summary(self.tables, self.norm_stats)
+
+
 class SearchRecall(object):
     """MornaSearch.search_recall: trees, search_ks, and per cell hits / ncand / ndots [n_t, n_s, nq], exact_count [nq]."""
 
@@ -490,6 +601,52 @@ class MornaSearch(object):
         else:
             out = self.annoy_index.recall_sweep(num_neighbors, trees, search_ks, items=np.array(list(queries), np.int32))
         return SearchRecall(trees, search_ks, out)
+
+    def hashing_sweep(self, query_ids, num_neighbors, dims, junction_file, n_trees=None, search_k=None):
+        """What every width of `dims` costs in neighbours and in norm distortion, from this one index.
+        query_ids: EXTERNAL sample ids of the index; the truth of a query is its unhashed neighbours (unhashed_search_member_n_
+        batch of num_neighbors + 1, the query dropped).  For every D the index's items are hashed again at width D on the GPU,
+        straight from the junction store (AnnoyIndex.add_items_from_store: the weights of <basename>.jw.mor, the line hashes
+        of `junction_file`, the intropolis file the index was made from), and searched exactly; with n_trees also through a
+        forest of that many trees, search_k morna's default 100 when not given.  The population is the index's items at every
+        D.  Returns a SearchHashing.  ValueError on an index of row shards, for an unknown id, or when the file's line count
+        is not the store's; IOError without the store or its weights."""
+        from .junctions import line_hashes
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(HASHING_SHARDS_REFUSAL)
+        r = int(num_neighbors)
+        dims = [int(d) for d in dims]
+        query_ids = list(query_ids)
+        truth_lists = self.unhashed_search_member_n_batch(query_ids, r + 1)       # (checks the ids)
+        store, _ = self.unhashed_store()
+        population = self._unhashed_population()
+        items = np.array([self.internal_id_map[q] for q in query_ids], np.int32)
+        truth = [drop_query(t[0], t[1], me, r) for t, me in zip(truth_lists, items.tolist())]
+        line_hash = line_hashes(junction_file, store.n_lines, self.annoy_index)
+        pp = store.row_norms(population)
+        if search_k is None:
+            search_k = HASHING_SEARCH_K
+        exact, approx, norm_stats, kernel_ms = [], [], [], []
+        for d in dims:
+            handle = AnnoyIndex(d, metric="angular", device=self._device)
+            try:
+                handle.add_items_from_store(store, population, line_hash)
+                kernel_ms.append(store.hash_rows_stats()["kernel_ms"])
+                norm_stats.append(norm_ratio_stats(handle.get_norms2(), pp))
+                ids, dist, cnt = handle.exact_search_by_item_batch(items, r + 1)
+                if (cnt < 0).any():
+                    raise ValueError("math domain error (the exact search at %d features)" % d)
+                exact.append([drop_query(ids[q, :int(cnt[q])], dist[q, :int(cnt[q])], me, r) for q, me in enumerate(items.tolist())])
+                if n_trees is not None:
+                    handle.build(int(n_trees))
+                    ids, dist, cnt = handle.get_nns_by_item_batch(items, r + 1, int(search_k))
+                    approx.append([drop_query(ids[q, :max(int(cnt[q]), 0)], dist[q, :max(int(cnt[q]), 0)], me, r)
+                                   for q, me in enumerate(items.tolist())])
+            finally:
+                handle.__del__()              # the rows of one width are freed before the next is made
+        tables = [hashing_rows(dims, truth[q], [e[q] for e in exact], [a[q] for a in approx] if n_trees is not None else None)
+                  for q in range(len(query_ids))]
+        return SearchHashing(dims, tables, norm_stats, kernel_ms)
 
     def search_member_n_batch(self, query_ids, num_neighbors, search_k, include_distances=True, meta_db=False, restriction=None,
                               query_groups=None, n_trees=None):
