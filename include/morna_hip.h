@@ -520,6 +520,40 @@ int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, co
                                   const int32_t *q_group, int32_t k, int32_t *ids, double *dist, int32_t *count);
 
 /*
+ * ---- label distance sums (no counterpart in the reference, whose README reads them off `search -m` output by
+ * eye) ---------------------------------------------------------------------------------------------------------------------
+ * For every query q and every label g, the sum of the angular distances from q to the items that carry g, from ONE scan.
+ *   item_label[n_items]: the label of every item, in [-1, n_labels); -1: none.  1 <= n_labels <= MORNA_LABELS_MAX.
+ *   Queries: q ([nq][dim] fp64), or items ([nq] stored rows), or both NULL: the staged query rows of morna_build_query_rows
+ *     (nq must be their count; with none staged there is no query source: MORNA_E_INVALID).  q and items: MORNA_E_INVALID.
+ *   r: a restriction, or NULL for none.  q_group as in the restricted search; q_group without a restriction that holds the
+ *     items' groups is MORNA_E_INVALID.  E(q) is the eligible set defined above, every item when r is NULL.
+ *   v(q, i): the fp32 value the exact search's scan has for (q, i) -- the MFMA scan for a batch of 32 queries or more, the
+ *     vector scan below, the choice morna_exact_search makes -- 2 - 2cos, 2 where the product of the squared norms is not
+ *     positive, within stats[5] of the true value.  d = sqrt((double) max(v, 0.0f)) in fp64, D = (uint64)(d * 2^32 + 0.5).
+ *   Item i is COUNTED for (q, g) iff item_label[i] == g, i is in E(q), and -- for queries given as items -- i != items[q].
+ *   sums_out[q][g] = the sum of D(q, i) over the counted items (fixed point, 32 fractional bits; D < 2^33, so no sum of fewer
+ *     than 2^29 terms passes 2^62); counts_out[q][g] = their number.  Integer sums: the result does not depend on the order
+ *     of summation, the grid or the batch; two calls give the same bytes.
+ *   Domain: an index that holds a row outside the scan's domain (a non-zero row whose fp32 squared norm is below dim' 2^-96,
+ *     dim' = dim rounded up to 256, above 2^126 or not finite) is refused, MORNA_E_INVALID naming the first such row.  A
+ *     zero row, a zero query and a query whose fp64 sum of squares lies outside [2^-900, 2^890] are inside: every v is 2.
+ *     A host query with a non-finite element or sum of squares: MORNA_E_INVALID, as morna_exact_search.
+ *   Errors: MORNA_E_INVALID naming the offender for a label outside [-1, n_labels) and for n_labels outside the limits; an
+ *     item outside the index: MORNA_E_RANGE; the restriction's state errors as in the restricted search; a row-sharded
+ *     handle (morna_comm_init): MORNA_E_INVALID.
+ *   morna_label_sums_stats  of the last call, stats[6]: scan ms (staging and scan kernels, HIP events), sums-kernel ms,
+ *     queries, batches (scan values of a batch: at most 2 GiB), items counted (the sum of counts_out), the scan's error
+ *     bound used (the largest over the batches).  All 0 after a call that failed or had nq = 0.
+ */
+#define MORNA_LABELS_MAX 4096
+int morna_label_sums(morna_index *h, const morna_restriction *r /* or NULL: unrestricted */, const double *q,
+                     const int32_t *items, int64_t nq, const int32_t *q_group /* [nq] or NULL */,
+                     const int32_t *item_label /* [n_items] */, int32_t n_labels, uint64_t *sums_out /* [nq][n_labels] */,
+                     int32_t *counts_out /* [nq][n_labels] */);
+int morna_label_sums_stats(const morna_index *h, double *stats /* [6] */);
+
+/*
  * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
  * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
  * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the

@@ -116,7 +116,9 @@ SIGNATURES = {
     "morna_restriction_free": (C.c_int, [_p]),
     "morna_get_nns_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p]),
     "morna_exact_search_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _p, _p, _p]),
-    "morna_get_nns_prefix": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
+    "morna_label_sums": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _p]),
+    "morna_label_sums_stats": (C.c_int, [_p, _p]),
+    "morna_get_nns_prefix":(C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "morna_search_sweep_stats": (C.c_int, [_p, _p]),

@@ -416,6 +416,49 @@ class AnnoyIndex(object):
                                                   ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
+    # ---- label distance sums (include/morna_hip.h, "label distance sums"; no counterpart in annoy) ----
+    def label_sums(self, item_label, n_labels, Q=None, items=None, restriction=None, query_groups=None):
+        """For every query and every label, the sum of the angular distances to the items that carry the label, in fixed
+        point, and their number: (sums uint64 [nq, n_labels], counts int32 [nq, n_labels]); mean distance = sums / 2**32 /
+        counts.  item_label: int32 [n_items] in [-1, n_labels), -1 for none.  Queries: Q (fp64 [nq, f]), items (stored rows:
+        the item itself is not counted), or neither: the staged query rows.  restriction / query_groups: as
+        exact_search_restricted; None: every item is eligible."""
+        if np.shape(item_label) != (self.get_n_items(),):
+            raise ValueError("item_label must hold one label per item (%d), got shape %r" % (self.get_n_items(), np.shape(item_label)))
+        item_label = np.ascontiguousarray(item_label, dtype=np.int32)
+        n_labels = int(n_labels)
+        if restriction is not None:
+            Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
+        else:
+            if query_groups is not None:
+                raise ValueError("query groups need a restriction made with groups")
+            if Q is not None and items is not None:
+                raise ValueError("give query vectors or items, not both")
+            if Q is not None:
+                Q = np.ascontiguousarray(Q, dtype=np.float64)
+                if Q.ndim != 2 or Q.shape[1] != self.f:
+                    raise IndexError("queries must be [nq, %d]" % self.f)
+                nq = Q.shape[0]
+            elif items is not None:
+                items = np.ascontiguousarray(items, dtype=np.int32)
+                if items.ndim != 1:
+                    raise ValueError("items must be one-dimensional")
+                nq = items.shape[0]
+            else:
+                nq = getattr(self, "_qrows_n", 0)
+        sums = np.zeros((nq, max(n_labels, 0)), np.uint64)
+        counts = np.zeros((nq, max(n_labels, 0)), np.int32)
+        check(lib().morna_label_sums(self._h, restriction._p if restriction is not None else None, ptr(Q), ptr(items), nq,
+                                     ptr(query_groups), ptr(item_label), n_labels, ptr(sums), ptr(counts)))
+        return sums, counts
+
+    def label_sums_stats(self):
+        """Of the last label_sums: scan ms, sums-kernel ms, queries, batches, items counted, the scan's error bound."""
+        stats = np.zeros(6, np.float64)
+        check(lib().morna_label_sums_stats(self._h, ptr(stats)))
+        return dict(scan_ms=float(stats[0]), sums_ms=float(stats[1]), queries=int(stats[2]), batches=int(stats[3]),
+                    counted=int(stats[4]), scan_eps=float(stats[5]))
+
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):
         """Rows of the query samples of `terms` (index.ParsedLines from ParsedLines.query_terms) on this handle, beside the

@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -64,6 +64,14 @@ space returns, the mean distance error over the shared ones, with --n-trees the 
 the mean and variance of hashed norm / unhashed norm -- experiment 2 of the reference's tests/README.md (test_norm_estimator.py)
 on real rows.  One index; the population is the index's items at every width.
 
+`labels` answers whether a sample's expression pattern resembles the samples of its tissue or cell type -- the second purpose
+the reference's README gives `search`, for uncovering contamination and mislabelling: with a sample -> label table (--labels,
+a groups file) it prints for every query the labels nearest to it by mean angular distance to their samples and, for a query
+that is a sample of the index, its silhouette -- (b - a) / max(a, b), a the mean distance to the other samples of its own
+label, b to those of the nearest other one -- and whether the nearest label is its own; over all queries a row per label,
+and with --matrix the map of mean distances between labels.  One scan of the index on the GPU that keeps, per query and
+label, an integer sum of all distances instead of the k smallest.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -89,6 +97,8 @@ here do the latter.
     python -m morna_amd.cli search -x idx -q 1234 --use-trees 50 --search-k 1000 -d
     python -m morna_amd.cli recall -x idx --sample 100 -r 20 --trees 10,20,50,100,all --search-ks 100,200,500,1000,4000 --summary-only
     python -m morna_amd.cli hashing -x idx --junction-file junctions.tsv.gz --sample 100 -r 20 --features 500,1000,3000,8192,index
+    python -m morna_amd.cli labels -x idx --labels tissues.tsv --all --matrix --summary-only
+    python -m morna_amd.cli labels -x idx --labels tissues.tsv --intropolis new_samples.tsv.gz --top 3
 """
 import argparse
 import sys
@@ -322,6 +332,43 @@ def build_parser():
     hashing_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
     for flag in ('--within', '--without', '--leave-out-groups', '--intropolis'):
         hashing_parser.add_argument(flag, type=str, required=False, default=None, help=argparse.SUPPRESS)
+    labels_parser = subparsers.add_parser('labels', help='tabulates, for every query, its mean distance to the samples of every '
+                                                         'label of a sample -> label table, and how well the labels hold '
+                                                         'together in the hashed space, from one scan of the index')
+    labels_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                               help='path to junction index basename (an index without row shards)')
+    labels_parser.add_argument('--labels', metavar='<file>', type=str, required=True,
+                               help='a groups file, "<label><TAB><id>,<id>,..." per line: the samples of every label (a tissue, '
+                                    'a cell type), at most 4096 labels; a sample it does not name has none')
+    labels_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
+                               help='the query is the sample already in the index with this sample id')
+    labels_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                               help='comma-separated sample ids already in the index')
+    labels_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
+                               help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
+    labels_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                               help='the seed of --sample (default 0)')
+    labels_parser.add_argument('--all', action='store_const', const=True, default=False, dest='all_items',
+                               help='every sample of the index is a query')
+    labels_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
+                               help='every sample of this (gzipped) intropolis file is a query')
+    labels_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
+                               help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+    labels_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=3,
+                               help='the nearest labels printed per query (default 3)')
+    labels_parser.add_argument('--matrix', action='store_const', const=True, default=False,
+                               help='append the label map: for every pair of labels (A, B) the mean distance from the queries '
+                                    'of label A to the samples of label B (queries that are samples of the index only)')
+    labels_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                               help='print only the table over all queries')
+    labels_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                               help='count only the samples this file lists, one integer sample id per line')
+    labels_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                               help='never count a sample this file lists, one integer sample id per line')
+    labels_parser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
+                               help='a groups file: a query never counts a sample of its own group -- its donor, its study -- '
+                                    '(queries that are samples of the index only)')
+    labels_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
     super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
@@ -576,6 +623,60 @@ def _check_hashing_flags(parser, args):
                      "index, such as 500,3000,index (%s)" % e)
 
 
+def _check_labels_flags(parser, args):
+    """`labels`: at most one named query source (none: a stream on stdin), the files read and checked against each other and
+    against the query kind; argparse errors, before any index is read.  Leaves the labels in args.label_groups and the
+    restriction's parts where _check_restriction_flags leaves them."""
+    from .junctions import parse_groups_file, parse_sample_ids_file
+    from .search import LABELS_MAX, labels_max_refusal
+    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+                                   ("--sample", args.sample is not None), ("--all", args.all_items),
+                                   ("--intropolis", args.intropolis is not None)) if on]
+    if len(given) > 1:
+        parser.error("labels takes one query source: -q, --query-ids, --sample, --all, --intropolis or a stream on stdin "
+                     "(got %s)" % " and ".join(given))
+    if args.format not in ("sam", "bed", "raw"):
+        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
+    if args.query_ids is not None:
+        try:
+            args.query_ids = [int(t) for t in args.query_ids.split(',')]
+        except ValueError:
+            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
+    if args.sample is None and getattr(args, "sample_seed_given", False):
+        parser.error("--sample-seed cannot be used without --sample")
+    if args.sample is not None and args.sample < 1:
+        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
+    if args.top < 1:
+        parser.error("--top takes a positive number of labels (got %d)" % args.top)
+    args.external = args.intropolis is not None or not given
+    source = "--intropolis" if args.intropolis is not None else "a query from a stream"
+    if args.external and args.matrix:
+        parser.error("--matrix cannot be used with %s: the label map compares the queries' own labels, and only a sample of "
+                     "the index has one (-q, --query-ids, --sample, --all)" % source)
+    if args.external and args.leave_out_groups is not None:
+        parser.error("--leave-out-groups cannot be used with %s: it takes queries that are samples of the index "
+                     "(-q, --query-ids, --sample, --all)" % source)
+    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
+    try:
+        args.label_groups = parse_groups_file(args.labels)
+        if args.within is not None:
+            args.within_ids = parse_sample_ids_file(args.within)
+        if args.without is not None:
+            args.without_ids = parse_sample_ids_file(args.without)
+        if args.leave_out_groups is not None:
+            args.leave_out = parse_groups_file(args.leave_out_groups)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+    if not args.label_groups:
+        parser.error("--labels %s names no label" % args.labels)
+    if len(args.label_groups) > LABELS_MAX:
+        parser.error(labels_max_refusal(len(args.label_groups)))
+    if args.within_ids is not None and args.without_ids is not None:
+        both = sorted(set(args.within_ids) & set(args.without_ids))
+        if both:
+            parser.error("--within and --without both name sample id %d" % both[0])
+
+
 def _check_batch_flags(parser, args):
     """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
     batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
@@ -644,6 +745,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_recall_flags(parser, args)
     if args.subparser_name == 'hashing':
         _check_hashing_flags(parser, args)
+    if args.subparser_name == 'labels':
+        _check_labels_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -665,6 +768,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _recall(args, stdout)
     if args.subparser_name == 'hashing':
         return _hashing(args, stdout)
+    if args.subparser_name == 'labels':
+        return _labels(args, stdin, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -817,6 +922,63 @@ def _hashing(args, stdout):
             stdout.write(format_hashing_rows(table.rows(q)))
     stdout.write("# all %d queries\n" % len(labels))
     stdout.write(format_hashing_rows(table.summary()))
+    return 0
+
+
+def _labels(args, stdin, stdout):
+    """`labels`: one scan of the index on the GPU that keeps, per query and label, the sum of the distances and their number;
+    a block per query, the table over all of them and, with --matrix, the label map."""
+    import os
+    import numpy as np
+    from .search import LABELS_SHARDS_REFUSAL, MornaSearch, format_label_rows
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
+    if os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(LABELS_SHARDS_REFUSAL)
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    if args.intropolis is not None:
+        queries = searcher.queries_from_intropolis(args.intropolis)
+        ids = queries.ext_ids
+    elif args.external:                                        # a stream: one query, as `search` makes it
+        for junction in _stream_parser(args.format)(stdin):
+            if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
+                searcher.update_query(junction)
+        searcher.finalize_query()
+        queries = np.array([searcher.query_sample], dtype=np.float64)
+        ids = ["stdin"]
+    else:
+        n = searcher.annoy_index.get_n_items()
+        if args.all_items or args.sample is not None:
+            inv = searcher._inverse_map()
+            if args.sample is not None and args.sample > n:
+                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
+            picked = range(n) if args.all_items else np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
+            ids = [inv[int(i)] for i in picked]
+        else:
+            ids = args.query_ids if args.query_ids is not None else [args.query_id]
+        for query_id in ids:
+            if query_id not in searcher.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+        queries = [searcher.internal_id_map[query_id] for query_id in ids]
+        args.query_ids = list(ids)                             # (a query the groups file does not name is a group of its own)
+    args.restriction = _make_restriction(args, searcher)
+    table = searcher.label_separation(queries, args.label_groups, restriction=args.restriction)
+    if not args.summary_only:
+        for q, query_id in enumerate(ids):
+            stdout.write("# query %s\tlabel %s\n" % (query_id, table.own_name(q) or "-"))
+            stdout.write(format_label_rows(table.rows(q, args.top)))
+    rows, without = table.summary()
+    stdout.write("# all %d queries\n" % len(ids))
+    stdout.write(format_label_rows(rows))
+    if without > 0:
+        stdout.write("# %d queries without a %s\n" % (without, "labelled sample to compare with" if args.external else "silhouette"))
+    if args.matrix:
+        stdout.write("# label map\n")
+        stdout.write(format_label_rows([(name,) + tuple(row) for name, row in zip(table.names, table.map())]))
     return 0
 
 

@@ -888,6 +888,58 @@ int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, co
     return exact_search_any(h, q, nullptr, items, nq, k, ids, dist, count, nullptr, 0, nullptr, r, q_group);
 }
 
+// ---- label distance sums (the contract is in morna_hip.h) -------------------------------------------------------
+
+int morna_label_sums(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
+                     const int32_t *q_group, const int32_t *item_label, int32_t n_labels, uint64_t *sums_out, int32_t *counts_out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 6; i++) h->label_stats[i] = 0.0;
+    if (!item_label || !sums_out || !counts_out) {
+        set_error("label_sums: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (n_labels < 1 || n_labels > MORNA_LABELS_MAX) {
+        set_error("label_sums: %d labels, 1 to %d are taken", n_labels, MORNA_LABELS_MAX);
+        return MORNA_E_INVALID;
+    }
+    if (q && items) {
+        set_error("label_sums: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    if (q_group && (!r || !r->has_group)) {
+        set_error("label_sums: query groups need a restriction that holds the items' groups");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("label_sums is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (!q && !items) {   // the staged query rows
+        if (!h->qrows.valid) {
+            set_error("label_sums: no query source (give query vectors or items, or call morna_build_query_rows first)");
+            return MORNA_E_INVALID;
+        }
+        if (nq != h->qrows.nq) {
+            set_error("label_sums: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        return label_sums(h, r, nullptr, nullptr, h->qrows.rows64.p, nq, q_group, item_label, n_labels, sums_out, counts_out);
+    }
+    return label_sums(h, r, q, items, nullptr, nq, q_group, item_label, n_labels, sums_out, counts_out);
+}
+
+int morna_label_sums_stats(const morna_index *h, double *stats)
+{
+    if (!h || !stats) {
+        set_error("label_sums_stats: null pointer");
+        return MORNA_E_INVALID;
+    }
+    for (int i = 0; i < 6; i++) stats[i] = h->label_stats[i];
+    return MORNA_OK;
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

@@ -310,6 +310,10 @@ struct morna_index {
     morna::DevBuf<int32_t> ex_out;     // [0] count, [1..] rows
     int32_t ex_out_n = 0;
     bool ex_out_valid = false;
+    // label sums (knn.hip, label_sums): the items' labels and a batch's outputs on the device; the last call's statistics
+    morna::DevBuf<int32_t> lb_label;   // [n_items]
+    morna::DevBuf<uint8_t> lb_out;     // sums uint64 [batch][L] | counts int32 [batch][L] | rows counted uint64
+    double label_stats[6] = {0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
@@ -440,6 +444,11 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
                      int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
                      const double *q_dev64 = nullptr, const morna_restriction *rst = nullptr,
                      const int32_t *q_group_host = nullptr);
+// morna_label_sums behind its argument checks (morna_hip.h, "label distance sums"): rst and q_group_host may be null;
+// the queries are q_host, items_host or q_dev64 (the staged query rows)
+int label_sums(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
+               const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *item_label_host, int32_t L,
+               uint64_t *sums_out, int32_t *counts_out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

@@ -2628,25 +2628,11 @@ static int launch_exact_scan(morna_index *h, int64_t N, int64_t nb, const float 
 size_t exact_msg_dist_offset(int64_t nq, int32_t k) { return align_up((size_t)nq * ((size_t)k + 1) * 4, 8); }
 size_t exact_msg_bytes(int64_t nq, int32_t k) { return exact_msg_dist_offset(nq, k) + (size_t)nq * k * 8; }
 
-// The queries: q_host fp64 [nq][dim] (host), or q_dev fp32 [nq][dim] (this device's memory), or q_dev64 fp64 [nq][dim] (this
-// device's memory: the query rows of morna_build_query_rows, finite by construction), or stored rows items_host.
-// The answers: host arrays, and / or msg_dev (device memory, exact_msg_bytes(nq, k)) with global ids = local + id_offset --
-// then only enqueued on the handle's stream behind the last selection.
-int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
-                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
-                     const double *q_dev64, const morna_restriction *rst, const int32_t *q_group_host)
+// What every caller of the scan checks first (the exact search and the label sums): host queries finite with a finite sum
+// of squares in the reference's order (cosine_distance), stored rows in range, the row width within the scan's.  qt_out: the
+// queries that share one pass of exact_scan_kernel (their fp32 images share 64 KiB of LDS).
+static int exact_check_queries(morna_index *h, const double *q_host, const int32_t *items_host, int64_t nq, int *qt_out)
 {
-    MORNA_TRY(upload_host_rows(h));
-    if (rst) MORNA_TRY(restriction_usable(h, rst));
-    if (h->n_items <= 0) {
-        set_error("exact search on an empty index");
-        return MORNA_E_EMPTY;
-    }
-    if (k <= 0 || nq < 0) {
-        set_error("exact search: k must be positive");
-        return MORNA_E_INVALID;
-    }
-    if (nq == 0) return MORNA_OK;
     const int64_t N = h->n_items;
     const int32_t D = h->dim, dpad = h->dpad;
     if (q_host)   // the contract: finite elements and a finite sum of squares in the reference's order (cosine_distance)
@@ -2668,12 +2654,72 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
                 return MORNA_E_RANGE;
             }
     // queries resident per pass: their fp32 images share 64 KiB of LDS
-    const int qt = (size_t)dpad * 4 * 8 <= 65536 ? 8 : (size_t)dpad * 4 * 4 <= 65536 ? 4
-                   : (size_t)dpad * 4 * 2 <= 65536 ? 2 : 1;
+    *qt_out = (size_t)dpad * 4 * 8 <= 65536 ? 8 : (size_t)dpad * 4 * 4 <= 65536 ? 4 : (size_t)dpad * 4 * 2 <= 65536 ? 2 : 1;
     if (dpad > Q_MAX_DPAD) {   // exact_scan_kernel<1> keeps the query's fp32 image in LDS (128 KiB at 32768)
         set_error("exact search: dimension %d is above the supported %d", D, Q_MAX_DPAD);
         return MORNA_E_INVALID;
     }
+    return MORNA_OK;
+}
+
+// The front of a batch: queries q0 .. q0 + nb of the call staged as fp64 (Qd), their fp32 images and norms made, and the scan
+// run over every row -- approx[nb][N], nothing masked.  The MFMA scan for 32 queries or more, exact_scan_kernel<qt> below.
+static int exact_scan_batch(morna_index *h, const double *q_host, const float *q_dev, const double *q_dev64,
+                            const int32_t *items_host, int64_t q0, int64_t nb, int qt, double *Qd, float *Qf, float *qn2,
+                            int32_t *d_items, float *approx)
+{
+    const int64_t N = h->n_items;
+    const int32_t D = h->dim, dpad = h->dpad;
+    if (q_host) {
+        HIP_TRY(hipMemcpyAsync(Qd, q_host + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
+    } else if (q_dev) {
+        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, q_dev + q0 * D, (int64_t)D, nullptr, D, Qd);
+    } else if (q_dev64) {
+        HIP_TRY(hipMemcpyAsync(Qd, q_dev64 + q0 * D, (size_t)nb * D * 8, hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, d_items, D, Qd);
+    }
+    // one pass over the matrix per qt queries: 4*D*N bytes each
+    const int64_t q_per_pass = nb >= 32 ? MM_TILE : qt;
+    ScopedTimer tm(h, MORNA_T_EXACT, 4 * (int64_t)D * N * ((nb + q_per_pass - 1) / q_per_pass));
+    hipLaunchKernelGGL(exact_prep_kernel, dim3((unsigned)((nb * WAVE + 255) / 256)), dim3(256), 0, h->stream,
+                       Qd, nb, D, dpad, Qf, qn2);
+    ScopedTimer ts(h, MORNA_T_EXACT_SCAN, nb >= 32 ? 2 * (int64_t)nb * N * dpad : 0);   // "bytes" = flops on the matrix cores
+    if (nb >= 32) {   // enough queries to fill MFMA tiles: dense contraction on the matrix cores
+        dim3 grid((unsigned)((N + MM_TILE - 1) / MM_TILE), (unsigned)((nb + MM_TILE - 1) / MM_TILE));
+        hipLaunchKernelGGL(exact_scan_mfma_kernel, grid, dim3(256), 0, h->stream, h->X.p, h->norm2.p, N, dpad, Qf,
+                           qn2, nb, approx);
+    } else if (qt == 8) MORNA_TRY((launch_exact_scan<8>(h, N, nb, Qf, qn2, approx)));
+    else if (qt == 4) MORNA_TRY((launch_exact_scan<4>(h, N, nb, Qf, qn2, approx)));
+    else if (qt == 2) MORNA_TRY((launch_exact_scan<2>(h, N, nb, Qf, qn2, approx)));
+    else MORNA_TRY((launch_exact_scan<1>(h, N, nb, Qf, qn2, approx)));
+    return MORNA_OK;
+}
+
+// The queries: q_host fp64 [nq][dim] (host), or q_dev fp32 [nq][dim] (this device's memory), or q_dev64 fp64 [nq][dim] (this
+// device's memory: the query rows of morna_build_query_rows, finite by construction), or stored rows items_host.
+// The answers: host arrays, and / or msg_dev (device memory, exact_msg_bytes(nq, k)) with global ids = local + id_offset --
+// then only enqueued on the handle's stream behind the last selection.
+int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
+                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
+                     const double *q_dev64, const morna_restriction *rst, const int32_t *q_group_host)
+{
+    MORNA_TRY(upload_host_rows(h));
+    if (rst) MORNA_TRY(restriction_usable(h, rst));
+    if (h->n_items <= 0) {
+        set_error("exact search on an empty index");
+        return MORNA_E_EMPTY;
+    }
+    if (k <= 0 || nq < 0) {
+        set_error("exact search: k must be positive");
+        return MORNA_E_INVALID;
+    }
+    if (nq == 0) return MORNA_OK;
+    const int64_t N = h->n_items;
+    const int32_t D = h->dim, dpad = h->dpad;
+    int qt = 1;
+    MORNA_TRY(exact_check_queries(h, q_host, items_host, nq, &qt));
     MORNA_TRY(exact_outside_rows(h));
     const int32_t n_outs = h->ex_out_n;
     const int32_t *outs = h->ex_out.p + 1;
@@ -2708,32 +2754,7 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     for (int64_t q0 = 0; q0 < nq; q0 += batch) {
         const int64_t nb = std::min(batch, nq - q0);
         if (d_qg) HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-        if (q_host) {
-            HIP_TRY(hipMemcpyAsync(Qd, q_host + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
-        } else if (q_dev) {
-            hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, q_dev + q0 * D, (int64_t)D, nullptr, D, Qd);
-        } else if (q_dev64) {
-            HIP_TRY(hipMemcpyAsync(Qd, q_dev64 + q0 * D, (size_t)nb * D * 8, hipMemcpyDeviceToDevice, h->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, d_items, D, Qd);
-        }
-        {
-            // one pass over the matrix per qt queries: 4*D*N bytes each
-            const int64_t q_per_pass = nb >= 32 ? MM_TILE : qt;
-            ScopedTimer tm(h, MORNA_T_EXACT, 4 * (int64_t)D * N * ((nb + q_per_pass - 1) / q_per_pass));
-            hipLaunchKernelGGL(exact_prep_kernel, dim3((unsigned)((nb * WAVE + 255) / 256)), dim3(256), 0, h->stream,
-                               Qd, nb, D, dpad, Qf, qn2);
-            ScopedTimer ts(h, MORNA_T_EXACT_SCAN, nb >= 32 ? 2 * (int64_t)nb * N * dpad : 0);   // "bytes" = flops on the matrix cores
-            if (nb >= 32) {   // enough queries to fill MFMA tiles: dense contraction on the matrix cores
-                dim3 grid((unsigned)((N + MM_TILE - 1) / MM_TILE), (unsigned)((nb + MM_TILE - 1) / MM_TILE));
-                hipLaunchKernelGGL(exact_scan_mfma_kernel, grid, dim3(256), 0, h->stream, h->X.p, h->norm2.p, N, dpad, Qf,
-                                   qn2, nb, approx);
-            } else if (qt == 8) MORNA_TRY((launch_exact_scan<8>(h, N, nb, Qf, qn2, approx)));
-            else if (qt == 4) MORNA_TRY((launch_exact_scan<4>(h, N, nb, Qf, qn2, approx)));
-            else if (qt == 2) MORNA_TRY((launch_exact_scan<2>(h, N, nb, Qf, qn2, approx)));
-            else MORNA_TRY((launch_exact_scan<1>(h, N, nb, Qf, qn2, approx)));
-        }
+        MORNA_TRY(exact_scan_batch(h, q_host, q_dev, q_dev64, items_host, q0, nb, qt, Qd, Qf, qn2, d_items, approx));
         if (n_outs > 0)
             hipLaunchKernelGGL(exact_mask_kernel, dim3((unsigned)((nb * n_outs + 255) / 256)), dim3(256), 0, h->stream, outs,
                                n_outs, nb, N, approx);
@@ -2788,6 +2809,207 @@ int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t
                  int32_t *count_out)
 {
     return exact_search_any(h, q, nullptr, nullptr, nq, k, ids_out, dist_out, count_out, nullptr, 0);
+}
+
+// =============================================================== label sums (morna_hip.h, "label distance sums")
+
+#define LS_THREADS 256
+#define LS_UNROLL 8
+#define LS_LDS_SLOTS 2048   // (label, replica) accumulators of a workgroup while there is more than one replica: 12 bytes each, 24 KiB
+
+// sums[q][g] += sum of D(q, r), counts[q][g] += 1 over the counted rows r of label g in the workgroup's chunk of rows
+// (blockIdx.y; blockIdx.x is the query), D = (uint64)(sqrt((double)max(v, 0)) * 2^32 + 0.5) of the scan value v.  Integer
+// sums: any order, grid and reduction shape give the same bits.
+// The accumulators live in LDS as [L][R]: R replicas of every label's pair, R the largest power of two with L * R <=
+// LS_LDS_SLOTS, at most LS_THREADS and at least 1; thread t adds into replica t & (R - 1).  With up to 8 labels every thread
+// owns its pairs and no two adds meet; with 64 labels a replica is shared by 8 threads, which meet only on equal labels; only
+// past 1024 labels is there one copy (48 KiB at 4096), and then the adds of a step spread over thousands of addresses.  The
+// replicas are folded in log2(R) steps and the labels that counted a row added to the outputs (zeroed by the host) with
+// integer atomics: several chunks of one query meet there.  counted_total: the rows counted by the whole launch.
+template <bool RST>
+__global__ __launch_bounds__(LS_THREADS) void label_sums_kernel(const float *__restrict__ approx, int64_t n_items, int64_t chunk_rows,
+                                                                const int32_t *__restrict__ item_label, int32_t L, int32_t R,
+                                                                const int32_t *__restrict__ items /* [nq] or null */,
+                                                                RestrictArgs Rst, unsigned long long *__restrict__ sums,
+                                                                int32_t *__restrict__ counts,
+                                                                unsigned long long *__restrict__ counted_total)
+{
+    __shared__ int s_counted;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *s_sum = (unsigned long long *)smem;   // [L][R]
+    int32_t *s_cnt = (int32_t *)(s_sum + (size_t)L * R);       // [L][R]
+    const int tid = threadIdx.x;
+    const int64_t qi = blockIdx.x;
+    for (int i = tid; i < L * R; i += LS_THREADS) {
+        s_sum[i] = 0ull;
+        s_cnt[i] = 0;
+    }
+    if (tid == 0) s_counted = 0;
+    __syncthreads();
+    const float *a = approx + qi * n_items;
+    const int64_t r_begin = (int64_t)blockIdx.y * chunk_rows;
+    const int64_t r_end = r_begin + chunk_rows < n_items ? r_begin + chunk_rows : n_items;
+    const int64_t self = items ? (int64_t)items[qi] : -1;
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(Rst, qi);
+    const int rep = tid & (R - 1);
+    for (int64_t base = r_begin; base < r_end; base += LS_THREADS * LS_UNROLL) {
+        float v[LS_UNROLL];
+        int32_t g[LS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LS_UNROLL; u++) {   // the loads of a step first: LS_UNROLL rows in flight per thread
+            const int64_t r = base + u * LS_THREADS + tid;
+            g[u] = r < r_end ? item_label[r] : -1;
+            v[u] = r < r_end ? a[r] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < LS_UNROLL; u++) {
+            const int64_t r = base + u * LS_THREADS + tid;
+            bool counted = g[u] >= 0 && g[u] < L && r != self;   // (labels are checked on the host: the bound keeps LDS safe)
+            if constexpr (RST) counted = counted && restrict_eligible(Rst, gq, r);
+            if (!counted) continue;
+            const double d = sqrt((double)fmaxf(v[u], 0.f));
+            const unsigned long long fx = (unsigned long long)(d * 4294967296.0 + 0.5);
+            atomicAdd(&s_sum[g[u] * R + rep], fx);
+            atomicAdd(&s_cnt[g[u] * R + rep], 1);
+        }
+    }
+    __syncthreads();
+    for (int s = R >> 1; s >= 1; s >>= 1) {   // replica r += replica r + s, every label
+        for (int i = tid; i < L * s; i += LS_THREADS) {
+            const int lab = i / s, r = i - lab * s;
+            s_sum[lab * R + r] += s_sum[lab * R + r + s];
+            s_cnt[lab * R + r] += s_cnt[lab * R + r + s];
+        }
+        __syncthreads();
+    }
+    int mine = 0;
+    for (int lab = tid; lab < L; lab += LS_THREADS) {
+        const int32_t c = s_cnt[lab * R];
+        if (c == 0) continue;
+        atomicAdd(&sums[qi * L + lab], s_sum[lab * R]);
+        atomicAdd(&counts[qi * L + lab], c);
+        mine += c;
+    }
+    if (mine) atomicAdd(&s_counted, mine);
+    __syncthreads();
+    if (tid == 0 && s_counted) atomicAdd(counted_total, (unsigned long long)s_counted);
+}
+
+// morna_label_sums: the scan of exact_search_any's front, then label_sums_kernel over approx[nb][N]; batches as there.
+int label_sums(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
+               const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *item_label_host, int32_t L,
+               uint64_t *sums_out, int32_t *counts_out)
+{
+    for (int i = 0; i < 6; i++) h->label_stats[i] = 0.0;
+    MORNA_TRY(upload_host_rows(h));
+    if (rst) MORNA_TRY(restriction_usable(h, rst));
+    if (h->n_items <= 0) {
+        set_error("label_sums on an empty index");
+        return MORNA_E_EMPTY;
+    }
+    if (nq < 0) {
+        set_error("label_sums: a negative number of queries");
+        return MORNA_E_INVALID;
+    }
+    const int64_t N = h->n_items;
+    const int32_t D = h->dim, dpad = h->dpad;
+    for (int64_t i = 0; i < N; i++)
+        if (item_label_host[i] < -1 || item_label_host[i] >= L) {
+            set_error("label_sums: item %lld has the label %d, outside [-1, %d)", (long long)i, item_label_host[i], L);
+            return MORNA_E_INVALID;
+        }
+    if (nq == 0) return MORNA_OK;
+    int qt = 1;
+    MORNA_TRY(exact_check_queries(h, q_host, items_host, nq, &qt));
+    MORNA_TRY(exact_outside_rows(h));
+    if (h->ex_out_n > 0) {   // their scan values are NaN: the sums have no meaning with them
+        std::vector<int32_t> outs((size_t)h->ex_out_n);
+        HIP_TRY(hipMemcpy(outs.data(), h->ex_out.p + 1, outs.size() * 4, hipMemcpyDeviceToHost));
+        set_error("label_sums: row %d lies outside the domain of the scan (its squared norm underflows, overflows or is not "
+                  "finite); %d such rows", *std::min_element(outs.begin(), outs.end()), h->ex_out_n);
+        return MORNA_E_INVALID;
+    }
+    int32_t R = 1;
+    while (R * 2 <= LS_THREADS && (int64_t)L * R * 2 <= LS_LDS_SLOTS) R *= 2;   // (1 past LS_LDS_SLOTS / 2 labels)
+    const size_t lds = (size_t)L * R * 12;
+    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 29) / std::max<int64_t>(N, 1)));
+    const size_t s_qd = align_up((size_t)batch * D * 8, 256), s_qf = align_up((size_t)batch * dpad * 4, 256),
+                 s_b4 = align_up((size_t)batch * 4, 256), s_ap = align_up((size_t)batch * N * 4, 256);
+    MORNA_TRY(h->ex_ws.alloc(s_qd + s_qf + 3 * s_b4 + s_ap));
+    uint8_t *p = h->ex_ws.p;
+    double *Qd = (double *)p; p += s_qd;
+    float *Qf = (float *)p; p += s_qf;
+    float *qn2 = (float *)p; p += s_b4;
+    int32_t *d_items = (int32_t *)p; p += s_b4;
+    int32_t *d_qg = (int32_t *)p; p += s_b4;
+    float *approx = (float *)p; p += s_ap;
+    const size_t s_sums = align_up((size_t)batch * L * 8, 256), s_cnts = align_up((size_t)batch * L * 4, 256);
+    MORNA_TRY(h->lb_label.alloc((size_t)N));
+    MORNA_TRY(h->lb_out.alloc(s_sums + s_cnts + 8));   // sums | counts | the rows counted by the launch
+    unsigned long long *d_sums = (unsigned long long *)h->lb_out.p;
+    int32_t *d_cnts = (int32_t *)(h->lb_out.p + s_sums);
+    unsigned long long *d_counted = (unsigned long long *)(h->lb_out.p + s_sums + s_cnts);
+    HIP_TRY(hipMemcpyAsync(h->lb_label.p, item_label_host, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+    RestrictArgs Ra = {nullptr, nullptr, nullptr};
+    if (rst) {
+        Ra.deny = rst->deny.p;
+        Ra.group = rst->has_group ? rst->group.p : nullptr;
+        Ra.q_group = Ra.group && q_group_host ? d_qg : nullptr;
+    }
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]));
+    int rc = MORNA_OK;
+    double scan_ms = 0.0, sums_ms = 0.0, counted = 0.0, eps_half = 0.0;
+    int64_t batches = 0;
+    auto body = [&]() -> int {
+        for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+            const int64_t nb = std::min(batch, nq - q0);
+            if (Ra.q_group) HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemsetAsync(h->lb_out.p, 0, s_sums + s_cnts + 8, h->stream));
+            HIP_TRY(hipEventRecord(ev[0], h->stream));
+            MORNA_TRY(exact_scan_batch(h, q_host, nullptr, q_dev64, items_host, q0, nb, qt, Qd, Qf, qn2, d_items, approx));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[1], h->stream));
+            // a workgroup per (query, chunk of rows): about 2048 workgroups when the batch is small, whole rows past that
+            int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((2048 + nb - 1) / nb, (N + 2047) / 2048));
+            const int64_t chunk_rows = ((N + chunks - 1) / chunks + LS_THREADS - 1) / LS_THREADS * LS_THREADS;
+            chunks = (N + chunk_rows - 1) / chunk_rows;
+            const dim3 grid((unsigned)nb, (unsigned)chunks);
+            if (rst)
+                hipLaunchKernelGGL(label_sums_kernel<true>, grid, dim3(LS_THREADS), lds, h->stream, approx, N, chunk_rows,
+                                   h->lb_label.p, L, R, items_host ? d_items : nullptr, Ra, d_sums, d_cnts, d_counted);
+            else
+                hipLaunchKernelGGL(label_sums_kernel<false>, grid, dim3(LS_THREADS), lds, h->stream, approx, N, chunk_rows,
+                                   h->lb_label.p, L, R, items_host ? d_items : nullptr, Ra, d_sums, d_cnts, d_counted);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[2], h->stream));
+            HIP_TRY(hipMemcpyAsync(sums_out + q0 * L, d_sums, (size_t)nb * L * 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(counts_out + q0 * L, d_cnts, (size_t)nb * L * 4, hipMemcpyDeviceToHost, h->stream));
+            unsigned long long counted_b = 0;
+            HIP_TRY(hipMemcpyAsync(&counted_b, d_counted, 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            counted += (double)counted_b;
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            scan_ms += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
+            sums_ms += ms;
+            eps_half = std::max(eps_half, (double)exact_scan_eps(dpad, nb >= 32) / 2.0);   // which scan ran
+            batches++;
+        }
+        return MORNA_OK;
+    };
+    rc = body();
+    for (int i = 0; i < 3; i++) (void)hipEventDestroy(ev[i]);
+    MORNA_TRY(rc);
+    h->label_stats[0] = scan_ms;
+    h->label_stats[1] = sums_ms;
+    h->label_stats[2] = (double)nq;
+    h->label_stats[3] = (double)batches;
+    h->label_stats[4] = counted;
+    h->label_stats[5] = eps_half;
+    return MORNA_OK;
 }
 
 }  // namespace morna

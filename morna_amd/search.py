@@ -261,6 +261,124 @@ def format_hashing_rows(rows):
     return "".join("\t".join(cell(v) for v in row) + "\n" for row in rows)
 
 
+LABELS_SHARDS_REFUSAL = ("labels is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                         "run it on an index built without --shards")
+LABELS_MAX = 4096               # MORNA_LABELS_MAX: a workgroup keeps every label's sum and count on chip
+LABELS_FIXED_ONE = 4294967296.0  # the sums are fixed point with 32 fractional bits
+LABELS_CALL_CELLS = 1 << 22     # (query, label) cells of one library call: 48 MiB of outputs
+
+
+def labels_max_refusal(n_labels):
+    return ("--labels names %d labels, at most %d are taken: the GPU keeps one sum and one count per label on chip while it "
+            "reads a query's distances" % (n_labels, LABELS_MAX))
+
+
+def label_means(sums_q, counts_q):
+    """m[g] = sums / 2^32 / counts of one query, None where the query counts no sample of the label."""
+    return [int(s) / LABELS_FIXED_ONE / int(c) if int(c) > 0 else None for s, c in zip(sums_q, counts_q)]
+
+
+def label_query(sums_q, counts_q, own=None):
+    """What one query's sums say: means (label_means), predicted (the label of the smallest mean, ties to the lowest label
+    index, None when no label is counted) and, for a query whose own label `own` (None or negative: none) is counted beside
+    at least one other: a (the mean to its own label), other and b (the nearest other label and the mean to it), silhouette
+    (b - a) / max(a, b) (0.0 when both are 0) and agree (predicted == own).  Without them the silhouette is None."""
+    means = label_means(sums_q, counts_q)
+    counted = [g for g, m in enumerate(means) if m is not None]
+    out = dict(means=means, predicted=min(counted, key=lambda g: (means[g], g)) if counted else None,
+               own=None if own is None or own < 0 else int(own), a=None, other=None, b=None, silhouette=None, agree=None)
+    own = out["own"]
+    others = [g for g in counted if g != own]
+    if own is None or means[own] is None or not others:
+        return out
+    other = min(others, key=lambda g: (means[g], g))
+    a, b = means[own], means[other]
+    out.update(a=a, other=other, b=b, silhouette=(b - a) / max(a, b) if max(a, b) > 0 else 0.0, agree=out["predicted"] == own)
+    return out
+
+
+def label_rows(names, sums_q, counts_q, own=None, top=3):
+    """The lines of one query's block of `morna labels`: the `top` nearest labels as ("<rank>.", label, count, mean distance)
+    and, where label_query defines a silhouette, ("silhouette", own label, own count, a, nearest other label, b, silhouette,
+    agree 0 | 1)."""
+    info = label_query(sums_q, counts_q, own)
+    means = info["means"]
+    order = sorted((g for g, m in enumerate(means) if m is not None), key=lambda g: (means[g], g))
+    rows = [("%d." % (rank + 1), names[g], int(counts_q[g]), means[g]) for rank, g in enumerate(order[:max(int(top), 0)])]
+    if info["silhouette"] is not None:
+        rows.append(("silhouette", names[info["own"]], int(counts_q[info["own"]]), info["a"], names[info["other"]], info["b"],
+                     info["silhouette"], 1 if info["agree"] else 0))
+    return rows
+
+
+def label_summary(names, sums, counts, own=None):
+    """(rows, without) over all queries.  own: the own label of every query (by-item queries; negative: none) -- then one row
+    per label that has queries with a silhouette, in file order, (label, queries, mean a, mean b, mean silhouette, queries
+    that agree, their share), an ("all", ...) row over those queries when there are any, and `without`, the number of queries
+    without a silhouette.  own None (queries from outside the index): (label, queries predicted to it) per label, and
+    `without` the queries that count no labelled sample at all."""
+    if own is None:
+        predicted = [label_query(sums[q], counts[q])["predicted"] for q in range(len(sums))]
+        return [(names[g], sum(1 for p in predicted if p == g)) for g in range(len(names))], sum(1 for p in predicted if p is None)
+    infos = [label_query(sums[q], counts[q], own[q]) for q in range(len(sums))]
+    defined = [i for i in infos if i["silhouette"] is not None]
+
+    def row(label, group):
+        n = len(group)
+        agree = sum(1 for i in group if i["agree"])
+        return (label, n, sum(i["a"] for i in group) / n, sum(i["b"] for i in group) / n, sum(i["silhouette"] for i in group) / n,
+                agree, float(agree) / n)
+    rows = []
+    for g in range(len(names)):
+        group = [i for i in defined if i["own"] == g]
+        if group:
+            rows.append(row(names[g], group))
+    if defined:
+        rows.append(row("all", defined))
+    return rows, len(infos) - len(defined)
+
+
+def label_map(n_labels, sums, counts, own):
+    """M[A][B]: the mean of m[q][B] over the queries of own label A that count a sample of B; None where no query does."""
+    total = [[0.0] * n_labels for _ in range(n_labels)]
+    seen = [[0] * n_labels for _ in range(n_labels)]
+    for q in range(len(sums)):
+        a = int(own[q])
+        if a < 0:
+            continue
+        for b, m in enumerate(label_means(sums[q], counts[q])):
+            if m is not None:
+                total[a][b] += m
+                seen[a][b] += 1
+    return [[total[a][b] / seen[a][b] if seen[a][b] else None for b in range(n_labels)] for a in range(n_labels)]
+
+
+def format_label_rows(rows):
+    """One tab-separated line per row of label_rows / label_summary / the label map: floats with six digits, None as "nan"."""
+    return format_recall_rows(rows)
+
+
+class SearchLabels(object):
+    """MornaSearch.label_separation: names (the labels in file order), item_label (int32 [n], -1: none), sums (uint64) and
+    counts (int32) [nq, L] as AnnoyIndex.label_sums returns them, own (the own label of every by-item query, None for queries
+    from outside the index) and stats (AnnoyIndex.label_sums_stats summed over the calls)."""
+
+    def __init__(self, names, item_label, sums, counts, own, stats):
+        self.names, self.item_label, self.sums, self.counts, self.own, self.stats = names, item_label, sums, counts, own, stats
+
+    def rows(self, q, top=3):
+        return label_rows(self.names, self.sums[q], self.counts[q], None if self.own is None else self.own[q], top)
+
+    def own_name(self, q):
+        return None if self.own is None or self.own[q] < 0 else self.names[int(self.own[q])]
+
+    def summary(self):
+        return label_summary(self.names, self.sums, self.counts, self.own)
+
+    def map(self):
+        return label_map(len(self.names), self.sums, self.counts, self.own)
+
+
 class SearchHashing(object):
     """MornaSearch.hashing_sweep: dims, tables[q] (hashing_rows of query q), norm_stats[i] of dims[i], and kernel_ms[i], the
     time of the rows' kernel at dims[i]."""
@@ -601,6 +719,61 @@ class MornaSearch(object):
         else:
             out = self.annoy_index.recall_sweep(num_neighbors, trees, search_ks, items=np.array(list(queries), np.int32))
         return SearchRecall(trees, search_ks, out)
+
+    def label_separation(self, queries, groups, restriction=None, query_groups=None):
+        """For every query and every label of `groups` the sum of the angular distances, in the hashed space, to the samples
+        that carry the label, and their number -- from one scan of the index on the GPU (AnnoyIndex.label_sums; DESIGN.md 8,
+        N13).  queries: a QueryBatch (queries_from_intropolis), fp64 query vectors [nq, dim], or a list of INTERNAL ids -- such
+        a query is not counted among its own label's samples, and its own label is what label_summary / label_map compare
+        with.  groups: [(label, [EXTERNAL ids])] as parse_groups_file returns it, at most 4096 labels; an id in two labels or
+        outside the index is restriction_arrays' ValueError.  restriction / query_groups: as the *_batch searches; a by-item
+        query under a restriction with groups carries its own sample's group unless query_groups says otherwise.  Returns a
+        SearchLabels."""
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(LABELS_SHARDS_REFUSAL)
+        groups = list(groups)
+        if not 1 <= len(groups) <= LABELS_MAX:
+            raise ValueError(labels_max_refusal(len(groups)))
+        n = self.annoy_index.get_n_items()
+        _, item_label, n_labels = restriction_arrays(self.internal_id_map, n, groups=groups)
+        names = [label for label, _ in groups]
+        self._check_restriction(restriction, query_groups)
+        handle = restriction.handle if restriction is not None else None
+        stats = dict(scan_ms=0.0, sums_ms=0.0, queries=0, batches=0, counted=0, scan_eps=0.0)
+
+        def add_stats():
+            last = self.annoy_index.label_sums_stats()
+            for key in ("scan_ms", "sums_ms", "queries", "batches", "counted"):
+                stats[key] += last[key]
+            stats["scan_eps"] = max(stats["scan_eps"], last["scan_eps"])
+        if isinstance(queries, QueryBatch):
+            self._check_batch(queries)
+            sums, counts = self.annoy_index.label_sums(item_label, n_labels, restriction=handle, query_groups=query_groups)
+            add_stats()
+            return SearchLabels(names, item_label, sums, counts, None, stats)
+        by_vector = isinstance(queries, np.ndarray) and queries.ndim == 2
+        if by_vector:
+            queries = np.ascontiguousarray(queries, dtype=np.float64)
+        else:
+            queries = np.array(list(queries), np.int32).reshape(-1)
+            if restriction is not None and query_groups is None:
+                query_groups = restriction.own_groups(queries)
+        if query_groups is not None:
+            query_groups = np.ascontiguousarray(query_groups, dtype=np.int32)
+        nq = len(queries)
+        sums, counts = np.zeros((nq, n_labels), np.uint64), np.zeros((nq, n_labels), np.int32)
+        step = max(1024, LABELS_CALL_CELLS // n_labels)        # queries of one call: its outputs stay modest
+        for q0 in range(0, nq, step):
+            part = queries[q0:q0 + step]
+            sums[q0:q0 + step], counts[q0:q0 + step] = self.annoy_index.label_sums(
+                item_label, n_labels, Q=part if by_vector else None, items=None if by_vector else part, restriction=handle,
+                query_groups=None if query_groups is None else query_groups[q0:q0 + step])
+            add_stats()
+        return SearchLabels(names, item_label, sums, counts, None if by_vector else item_label[queries], stats)
 
     def hashing_sweep(self, query_ids, num_neighbors, dims, junction_file, n_trees=None, search_k=None):
         """What every width of `dims` costs in neighbours and in norm distortion, from this one index.
