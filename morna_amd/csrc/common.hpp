@@ -137,6 +137,16 @@ struct Seg {
     int32_t tree, level, start, count, node;
 };
 
+// A run of positions of one tree whose entries of `inv` (the position of every row in the tree) are to be rewritten from the
+// image the run's items are in (forest.hip, split_inv_kernel): the children of the nodes a level's partitions moved.
+struct InvSeg {
+    int32_t image;         // tree * 2 + (level & 1): the image of the work buffer the run is read from
+    int32_t start, count;  // positions [start, start + count) of the tree
+    int32_t first_chunk;   // chunks of SPLIT_INV_CHUNK positions in the runs before this one
+};
+static_assert(sizeof(InvSeg) == 16, "the runs go up in 16-byte words, behind the tasks");
+#define SPLIT_INV_CHUNK 1024   // positions per workgroup of split_inv_kernel
+
 // Where a node's items are DURING a build: the work buffer holds two images of every tree's permutation, [tree][2][n_items],
 // and a node of depth `level` has its items in image (level & 1) -- a partition reads one image and writes the node's two
 // children into the other, so nothing is copied back (forest.hip; the leaves are gathered into h->perm at the end).
@@ -179,11 +189,12 @@ struct ForestScratch {   // forest.hip
     DevBuf<int32_t> hist, cursor;   // launch order of the chunk split: buckets of 32 row ids
     DevBuf<int2> info, sched;
     DevBuf<int32_t> inv;         // matrix-core split: position of every item (or row) in every tree's permutation
+    DevBuf<InvSeg> inv_segs;     // the runs split_inv_kernel walks on the side stream (d_tasks is the next attempt's by then)
     DevBuf<uint8_t> leaves;      // the leaf segments on their way to gather_leaves_kernel
     void release()
     {
         work.release(); ones.release(); side.release(); tasks.release(); hist.release();
-        cursor.release(); info.release(); sched.release(); inv.release(); leaves.release();
+        cursor.release(); info.release(); sched.release(); inv.release(); inv_segs.release(); leaves.release();
     }
 };
 
@@ -409,8 +420,13 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed);
 int split_mm_prepare_rows(morna_index *h, hipStream_t stream);   // stream: the handle's main or side stream
 int split_mm_convert_rows(morna_index *h, const float *src, int64_t rows, _Float16 *dst, float *norm, float *err,
                           float *inv_scale, hipStream_t stream);
-int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_by_item, int32_t n_trees, hipStream_t stream,
-                        const int32_t **rank_out, int32_t **inv_out);
+// the order of the contraction's rows: begin (buffers, the handle's state; before the level's two_means is launched), then
+// the sort itself on `stream`
+int split_mm_order_begin(morna_index *h, int32_t n_trees, const int32_t **rank_out, int32_t **inv_out);
+int split_mm_order_rows(morna_index *h, const uint8_t *side, int32_t n_trees, hipStream_t stream);
+// inv[tree][rank ? rank[item] : item] = position, for every position of the runs (the side stream, under two_means)
+int split_mm_level_inv(morna_index *h, const InvSeg *d_segs, int32_t n_segs, int32_t n_chunks, const int32_t *perm, const int32_t *rank,
+                       int32_t *inv, hipStream_t stream);
 // a level: begin (buffers; before its two_means is launched), its per-tile task lists (any stream, once the tasks are on the
 // device), then the contraction
 bool split_mm_level_uses_lists(const morna_index *h, int32_t n_tasks);
@@ -418,7 +434,7 @@ int split_mm_level_begin(morna_index *h, int32_t n_tasks, int32_t n_slots, HalfI
 int split_mm_level_lists(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, const int32_t *perm, hipStream_t stream);
 int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, int32_t n_slots, const float *hp_level,
                    const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones, const char *image_from,
-                   bool lists_ready);
+                   bool lists_ready, const char *inv_from, int32_t level);
 // result block in HBM (ids at 0, distances at s_ids, counts at s_ids + s_dist; `bytes` in all) -> the caller's arrays
 // through the handle's page-locked staging (knn.hip); waits for the stream
 int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s_ids, size_t s_dist, size_t dist_elt, int64_t nq,

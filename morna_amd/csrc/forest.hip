@@ -30,17 +30,21 @@
 //   post_counts_kernel  the level's right-side counts into a page-locked mailbox the host polls
 //   (host)            annoy's 3-attempt / 0.95 imbalance rule on the counts
 //   fallback_kernel   random sides for nodes still above 0.99
-//   partition_kernel  stable partition of each segment by side, from one image of the tree into the other; keeps
-//                     inv[tree][row], the position in the tree of the item a row of the contraction stands for,
-//                     current (what the matrix-core split finds a row's node with)
+//   partition_kernel  stable partition of each segment by side, from one image of the tree into the other
+//   (splitmm.hip)     split_inv_kernel: inv[tree][row], the position in the tree of the item a row of the contraction stands
+//                     for (what the matrix-core split finds a row's node with), rewritten for what the level's partitions
+//                     moved -- on the side stream, under the NEXT level's two_means
 //   pull_tasks_kernel / gather_leaves_kernel  task lists and node tables out of page-locked host memory; the leaves
 //                     into perm when the build ends
 // Node ids are handed out breadth-first, children of the i-th split node of a
 // level get consecutive ids, exactly as oracle mode 1 does.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "common.hpp"
@@ -1093,8 +1097,10 @@ __host__ __device__ inline bool sides_stand(int attempt, int64_t n0, int64_t n1)
 // stable partition of one segment by side; one workgroup per node (PT threads: 1024 while nodes are large).
 // Launched right behind the split of every attempt, before the host has seen the counts: a node whose sides do
 // not stand is left alone (its next attempt, or the fallback, partitions it).
-// inv (may be null): inv[tree][item] = position of the item in the tree's permutation, kept current here -- what the
-// matrix-core split looks a row's node up with (one look-up per (row, tree), no separate inversion pass per level).
+// INV (MORNA_PARTITION_INV=1 only): inv[tree][rank ? rank[item] : item] = position of the item in the tree's permutation is
+// kept current here, behind a gather of `rank` and with one scattered store per item.  Nothing on a level's chain reads
+// `inv` before the next level's contraction, so by default it is rewritten beside that level's two_means instead
+// (splitmm.hip, split_inv_kernel) and this kernel -- a chain of memory round trips -- has neither.
 // The right-side counts of a level's tasks, posted to page-locked host memory tagged with the call's epoch: a launch of its
 // own in front of the partition, so that ALL counts are with the host a few microseconds after the split and its
 // bookkeeping for the next attempt or level runs while the partition does (posted by the partition workgroups themselves,
@@ -1111,13 +1117,17 @@ __global__ void post_counts_kernel(const int32_t *__restrict__ ones, int32_t n, 
 
 // the level's task list, pulled out of page-locked host memory by the device itself: a hipMemcpyAsync of more than a few KB
 // goes to the SDMA engine, ~20 us of start-up during which the stream has nothing else to run
-__global__ void pull_tasks_kernel(const int4 *__restrict__ src /* host memory, device-visible */, int4 *__restrict__ dst, int32_t n16)
+// (dst2: where the words from n_first on go -- the runs of split_inv_kernel ride behind the level's tasks)
+__global__ void pull_tasks_kernel(const int4 *__restrict__ src /* host memory, device-visible */, int4 *__restrict__ dst, int32_t n16,
+                                  int4 *__restrict__ dst2 = nullptr, int32_t n_first = 0)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n16) dst[i] = src[i];
+    if (i >= n16) return;
+    if (dst2 && i >= n_first) dst2[i - n_first] = src[i];
+    else dst[i] = src[i];
 }
 
-template <int PT>
+template <int PT, bool INV>
 __global__ __launch_bounds__(PT) void partition_kernel(const SplitTask *__restrict__ tasks, int64_t n_items,
                                                        const uint8_t *__restrict__ side,
                                                        const int32_t *__restrict__ ones, int32_t *__restrict__ perm /* work buffer [tree][2][n_items] */,
@@ -1178,14 +1188,16 @@ __global__ __launch_bounds__(PT) void partition_kernel(const SplitTask *__restri
         const int excl = incl - pk + before;
         int r1 = excl & 0xffff, rv = excl >> 16;   // right-side / valid positions before this thread's first
         int rk[PT_PER];
+        if constexpr (INV) {
 #pragma unroll
-        for (int u = 0; u < PT_PER; u++) rk[u] = (rank && sd[u] >= 0) ? rank[it[u]] : it[u];   // the four look-ups together
+            for (int u = 0; u < PT_PER; u++) rk[u] = (rank && sd[u] >= 0) ? rank[it[u]] : it[u];   // the four look-ups together
+        }
 #pragma unroll
         for (int u = 0; u < PT_PER; u++)
             if (sd[u] >= 0) {
                 const int dst = sd[u] ? (n0 + run1 + r1) : (run0 + (rv - r1));
                 dst_img[dst] = it[u];
-                if (inv) inv[(int64_t)t.tree * n_items + rk[u]] = t.start + dst;
+                if constexpr (INV) inv[(int64_t)t.tree * n_items + rk[u]] = t.start + dst;
                 r1 += sd[u];
                 rv += 1;
             }
@@ -1266,13 +1278,30 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
     const int32_t n_buckets = (int32_t)std::min<int64_t>(SCHED_MAX_BUCKETS, std::max<int64_t>(1, (N + 31) / 32));
     MORNA_TRY(d_hist.alloc((size_t)n_buckets));
     MORNA_TRY(d_cursor.alloc((size_t)n_buckets));
-    // matrix-core split: position of every item in every tree's permutation, kept current by partition_kernel
+    // matrix-core split: position of every item in every tree's permutation.  The roots' identity at level 0; from then on
+    // rewritten for what a level's partitions moved, on the side stream under the next level's two_means (split_inv_kernel)
+    // and only in front of a level that takes the matrix-core form.  MORNA_PARTITION_INV=1: kept current by
+    // partition_kernel instead (the earlier form, for comparison).
     static const bool mm_on = env_on("MORNA_SPLIT_MM");
     static const bool order_on = env_on("MORNA_SPLIT_ORDER");
+    static const bool part_inv = mm_on && getenv("MORNA_PARTITION_INV") && atoi(getenv("MORNA_PARTITION_INV")) != 0;
+    static const bool debug_turn = getenv("MORNA_DEBUG_TURN") && atoi(getenv("MORNA_DEBUG_TURN")) != 0;
     DevBuf<int32_t> &inv = h->forest.inv;
     if (mm_on) MORNA_TRY(inv.alloc((size_t)n_trees * N));
     int32_t *inv_p = mm_on ? inv.p : nullptr;   // by item; by row once the rows have been ordered (rank_p)
     const int32_t *rank_p = nullptr;
+    // `inv` holds the true position of every row as of level inv_level; the leaves made since (those of later levels) start
+    // at leaves[inv_leaf_mark].  inv_from: who brought it there (MORNA_DEBUG_OPEN)
+    int32_t inv_level = 0;
+    size_t inv_leaf_mark = 0;
+    const char *inv_from = "iota";
+    std::vector<InvSeg> inv_segs, inv_segs_next;
+    int32_t inv_chunks_next = 0, inv_next_level = -1;
+    // MORNA_DEBUG_TURN=1: host times (steady clock, us since the build began) of a level's turn-around, one stderr line per attempt
+    const auto turn_t0 = std::chrono::steady_clock::now();
+    auto turn_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - turn_t0).count(); };
+    double turn_counts = 0.0;
+    std::string turn_log;   // printed when the build has been enqueued: a write to stderr between two levels would be in the figures
     h->splitmm.ord_valid = false;
     std::vector<int32_t> tree_first;
     {
@@ -1345,12 +1374,27 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
     while (!cur.empty()) {
         // split nodes of this level, in cur order
         std::vector<int32_t> split_idx;
-        for (size_t i = 0; i < cur.size(); i++) {
+        for (size_t i = 0; i < cur.size(); i++)
             if (cur[i].count > K) split_idx.push_back((int32_t)i);
-            else leaves.push_back(LeafSeg{cur[i].tree, cur[i].level, cur[i].start, cur[i].count});
-        }
+        // (the level's leaves are listed once its two_means has been launched: nothing of the level's start reads them)
+        const size_t leaves_before = leaves.size(), leaves_after = leaves_before + cur.size() - split_idx.size();
+        bool leaves_listed = false;
+        auto list_leaves = [&]() {
+            if (leaves_listed) return;
+            leaves_listed = true;
+            for (const Seg &s : cur)
+                if (s.count <= K) leaves.push_back(LeafSeg{s.tree, s.level, s.start, s.count});
+        };
         h->stats.max_depth = std::max<int64_t>(h->stats.max_depth, level);
-        if (split_idx.empty()) break;
+        if (split_idx.empty()) {
+            list_leaves();
+            break;
+        }
+        if (part_inv && level > 0) {   // the partitions of the level before wrote it
+            inv_level = level;
+            inv_from = "partition";
+        }
+        if (inv_level == level) inv_leaf_mark = leaves_after;
         const int32_t S = (int32_t)split_idx.size();
         {
             const size_t need = (size_t)(n_split_total + S) * dpad;
@@ -1405,12 +1449,15 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                                (unsigned long long *)h->host_counts.p, epoch);
             {
                 ScopedTimer tm(h, MORNA_T_PARTITION, 0);
-                if (level_rows >= (int64_t)A * 2048)
-                    hipLaunchKernelGGL(partition_kernel<1024>, dim3((unsigned)A), dim3(1024), 0, h->stream, d_tasks.p, N, side.p,
-                                       d_ones.p, work.p, inv_p, rank_p);
-                else
-                    hipLaunchKernelGGL(partition_kernel<256>, dim3((unsigned)A), dim3(256), 0, h->stream, d_tasks.p, N, side.p,
-                                       d_ones.p, work.p, inv_p, rank_p);
+#define PART_LAUNCH(PT, INV)                                                                                               \
+    hipLaunchKernelGGL((partition_kernel<PT, INV>), dim3((unsigned)A), dim3(PT), 0, h->stream, d_tasks.p, N, side.p, d_ones.p, \
+                       work.p, inv_p, rank_p)
+                const bool big_nodes = level_rows >= (int64_t)A * 2048;
+                if (part_inv && big_nodes) PART_LAUNCH(1024, true);
+                else if (part_inv) PART_LAUNCH(256, true);
+                else if (big_nodes) PART_LAUNCH(1024, false);
+                else PART_LAUNCH(256, false);
+#undef PART_LAUNCH
             }
             if (hipGetLastError() != hipSuccess) {
                 set_error("forest build: partition launch failed");
@@ -1441,13 +1488,18 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
 
         // the level's task list goes up through page-locked staging (the copy of an earlier attempt has long run: its
         // counts have been read back since)
-        auto upload_tasks = [&](const std::vector<SplitTask> &tk) -> int {
-            const size_t bytes = tk.size() * sizeof(SplitTask);
+        // segs (may be null): the runs of split_inv_kernel, behind the tasks in the same staging and the same pull, into a
+        // buffer of their own -- d_tasks is the next attempt's while the side stream may still be reading them
+        auto upload_tasks = [&](const std::vector<SplitTask> &tk, const std::vector<InvSeg> *segs) -> int {
+            const size_t b_tasks = tk.size() * sizeof(SplitTask), b_segs = segs ? segs->size() * sizeof(InvSeg) : 0;
+            const size_t bytes = b_tasks + b_segs;
+            if (b_segs) MORNA_TRY(h->forest.inv_segs.alloc(segs->size()));
             if (bytes > h->host_tables.cap) {
                 if (hipStreamSynchronize(h->stream) != hipSuccess) return MORNA_E_HIP;
                 MORNA_TRY(h->host_tables.reserve(bytes, 1 << 16));
             }
-            memcpy(h->host_tables.p, tk.data(), bytes);
+            memcpy(h->host_tables.p, tk.data(), b_tasks);
+            if (b_segs) memcpy(h->host_tables.p + b_tasks, segs->data(), b_segs);
             static_assert(sizeof(SplitTask) % 16 == 0, "tasks are moved in 16-byte words");
             void *dev_view = h->host_tables.dev();
             if (!dev_view) {
@@ -1455,7 +1507,9 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                 return MORNA_E_HIP;
             }
             const int32_t n16 = (int32_t)(bytes / 16);
-            if (n16 > 0) hipLaunchKernelGGL(pull_tasks_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, h->stream, (const int4 *)dev_view, (int4 *)d_tasks.p, n16);
+            if (n16 > 0)
+                hipLaunchKernelGGL(pull_tasks_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, h->stream, (const int4 *)dev_view,
+                                   (int4 *)d_tasks.p, n16, b_segs ? (int4 *)h->forest.inv_segs.p : (int4 *)nullptr, (int32_t)(b_tasks / 16));
             if (hipGetLastError() != hipSuccess) {
                 set_error("forest build: task upload failed");
                 return MORNA_E_HIP;
@@ -1491,48 +1545,77 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             const double mm_dense_us = (double)((N + 127) / 128) * (double)((A + 127) / 128) * 0.13, chunk_us = (double)rows * 0.47e-3;
             const bool use_mm = mm_on && max_per_tree >= 1 &&
                                 (mm_lists || (max_per_tree <= 32 && (attempt == 0 ? rows * 2 >= (int64_t)n_trees * N : mm_dense_us < chunk_us)));
-            if ((rc = upload_tasks(tasks))) { cleanup(); return rc; }
+            // What of the level does not depend on its hyperplanes runs on the side stream, under two_means: the fp16 image
+            // of the rows (once per set of rows), the order of the contraction's rows (second level), `inv`, the per-tile
+            // task lists.
+            const bool prep_job = use_mm && !h->half.valid;
+            // second level: the rows of the contraction are put in an order in which neighbours are alike (the sides of
+            // the root splits say which are); from here on `inv` is by row (splitmm.hip, split_mm_order_rows; its
+            // counting sort's table is 16 KB per 256 rows: up to 4 M rows).  (Under MORNA_PARTITION_INV=1 only on a first
+            // attempt: the partitions of the nodes an earlier attempt accepted have written the other buffer.)
+            const bool order_job = use_mm && !prep_job && order_on && level == 1 && (attempt == 0 || !part_inv) && !h->splitmm.ord_valid && N >= 8192 &&
+                                   N <= ((int64_t)1 << 22) && n_trees >= 2;
+            // `inv` is brought up to this level when the contraction is about to read it and it is not there yet: the first
+            // attempt of a level >= 1 (a retry's tasks were not moved, and the rows of the nodes accepted meanwhile keep
+            // positions inside their own old segment, which is no task of the retry), or a retry that is the level's first
+            // attempt in the matrix-core form.  Not in front of chunk-form levels, not after the last level.  The
+            // contraction decides membership by position alone, so EVERY row moved since inv_level must be rewritten, the
+            // rows that landed in a leaf too (a stale position could lie inside their split sibling): the runs cover all of
+            // `cur` and the leaves of the levels in between.  A new order of the rows rewrites everything.
+            const bool inv_job = use_mm && (order_job || inv_level != level);
+            int32_t inv_chunks = 0;
+            if (inv_job && inv_level == level - 1 && inv_next_level == level) {
+                // the rule: the level before was the last `inv` was true for.  Its split nodes were all partitioned, and a
+                // node's segment now holds its two children side by side: the runs are those segments, listed while that
+                // level's kernels ran (the roots' segments are every row: a new order of the rows is covered too)
+                inv_segs.swap(inv_segs_next);
+                inv_chunks = inv_chunks_next;
+            } else if (inv_job) {
+                inv_segs.clear();
+                auto add_run = [&](int32_t tree, int32_t lvl, int32_t start, int32_t count) {
+                    if (count <= 0) return;
+                    inv_segs.push_back(InvSeg{tree * 2 + (lvl & 1), start, count, inv_chunks});
+                    inv_chunks += (count + SPLIT_INV_CHUNK - 1) / SPLIT_INV_CHUNK;
+                };
+                for (size_t l = order_job ? 0 : inv_leaf_mark; l < leaves_before; l++)
+                    add_run(leaves[l].tree, leaves[l].level, leaves[l].start, leaves[l].count);
+                for (const Seg &sg : cur) add_run(sg.tree, sg.level, sg.start, sg.count);
+            }
+            if ((rc = upload_tasks(tasks, inv_job ? &inv_segs : nullptr))) { cleanup(); return rc; }
+            const double turn_pulled = debug_turn ? turn_us() : 0.0;
             // (d_ones is zeroed by the two_means kernel of the attempt, task by task: a hipMemsetAsync costs ~15 us of
             // idle device around its few microseconds)
-            // Work of the level that does not depend on its hyperplanes goes to the side stream, under two_means: ONE fork
-            // behind the task list (and so behind the previous level's partition), one join in front of the split.
-            bool side_work = false;
-            auto fork_side = [&]() -> hipError_t {
-                if (side_work) return hipSuccess;
-                side_work = true;
-                const hipError_t e = hipEventRecord(h->ev_fork, h->stream);
-                return e != hipSuccess ? e : hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
-            };
-            if (use_mm && !h->half.valid) {
-                // once per set of rows: their fp16 image, on the side stream while two_means (a latency chain on few CUs
-                // at the root level) has the main one.  Nothing else of the matrix-core split needs a side stream: a
-                // row's node is looked up through `inv`, which the partition of the previous level left current (round 1
-                // inverted the permutations in a kernel of its own per level, behind two event hand-overs of ~17 us each).
-                F_TRY(fork_side());
-                if ((rc = split_mm_prepare_rows(h, h->stream2))) { cleanup(); return rc; }
-            } else if (use_mm && order_on && level == 1 && !h->splitmm.ord_valid && N >= 8192 && N <= ((int64_t)1 << 22) && n_trees >= 2) {
-                // second level: the rows of the contraction are put in an order in which neighbours are alike (the sides of
-                // the root splits say which are), on the side stream under this level's two_means; from here on `inv` is
-                // kept by row (splitmm.hip, split_mm_order_rows; its counting sort's table is 16 KB per 256 rows: up to 4 M rows)
-                F_TRY(fork_side());
-                if ((rc = split_mm_order_rows(h, side.p, inv_p, n_trees, h->stream2, &rank_p, &inv_p))) { cleanup(); return rc; }
-            }
-            // The matrix-core split's buffers for this attempt, before anything of it is enqueued.  Its per-tile task lists
-            // read the tasks, the permutations and the order of the rows (on the side stream already, if it is this
-            // level's) -- nothing two_means makes: they are built beside it (MORNA_SPLIT_LISTS_AHEAD=0: in front of the
-            // contraction, behind two_means).
+            // The matrix-core split's buffers for this attempt, before anything of it is enqueued (and the buffers and the
+            // state of a new order of the rows: the lists depend on it).  The per-tile task lists read the tasks, the
+            // permutations and the order of the rows -- nothing two_means makes: they are built beside it
+            // (MORNA_SPLIT_LISTS_AHEAD=0: in front of the contraction, behind two_means).
             HalfImageOut img = {nullptr, nullptr, nullptr, nullptr};
             bool lists_ahead = false;
+            if (order_job && (rc = split_mm_order_begin(h, n_trees, &rank_p, &inv_p))) { cleanup(); return rc; }
             if (use_mm) {
                 static const bool ahead_on = env_on("MORNA_SPLIT_LISTS_AHEAD");
                 if ((rc = split_mm_level_begin(h, A, S, &img))) { cleanup(); return rc; }
-                if (ahead_on && split_mm_level_uses_lists(h, A)) {
-                    F_TRY(fork_side());
-                    if ((rc = split_mm_level_lists(h, d_tasks.p, A, work.p, h->stream2))) { cleanup(); return rc; }
-                    lists_ahead = true;
-                }
+                lists_ahead = ahead_on && split_mm_level_uses_lists(h, A);
             }
-            if (side_work) F_TRY(hipEventRecord(h->ev_join, h->stream2));
+            // ONE fork behind the task list (and so behind the previous level's partition), one join in front of the split.
+            // (Enqueued in front of the two_means launch: behind it, which would let two_means start up to ten launches of
+            // host time sooner, measured no different -- the host is not what a level's start waits for.)
+            const bool side_work = prep_job || order_job || inv_job || lists_ahead;
+            if (side_work) {
+                F_TRY(hipEventRecord(h->ev_fork, h->stream));
+                F_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+                if (prep_job && (rc = split_mm_prepare_rows(h, h->stream2))) { cleanup(); return rc; }
+                if (order_job && (rc = split_mm_order_rows(h, side.p, n_trees, h->stream2))) { cleanup(); return rc; }
+                if (inv_job && (rc = split_mm_level_inv(h, h->forest.inv_segs.p, (int32_t)inv_segs.size(), inv_chunks, work.p, rank_p,
+                                                        inv_p, h->stream2))) { cleanup(); return rc; }
+                if (lists_ahead && (rc = split_mm_level_lists(h, d_tasks.p, A, work.p, h->stream2))) { cleanup(); return rc; }
+                F_TRY(hipEventRecord(h->ev_join, h->stream2));
+            }
+            if (inv_job) {
+                inv_level = level;
+                inv_leaf_mark = leaves_after;
+                inv_from = "side";
+            }
             // the two_means forms that end with the hyperplane in registers also write its fp16 image for the split
             // (MORNA_TM_HALF_EPILOGUE=0: a conversion launch behind two_means, as for the LDS form)
             static const bool tm_half_on = env_on("MORNA_TM_HALF_EPILOGUE");
@@ -1596,6 +1679,20 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
 #undef TMS_LAUNCH
 #undef TMX_LAUNCH
             }
+            const double turn_tm = debug_turn ? turn_us() : 0.0;
+            list_leaves();
+            if (attempt == 0 && mm_on && !part_inv) {
+                // the runs the NEXT level's split_inv_kernel walks, should it take the matrix-core form: this level's split
+                // nodes, in the image their children will be in (host time nobody waits for)
+                inv_segs_next.clear();
+                inv_chunks_next = 0;
+                for (int32_t i : split_idx) {
+                    const Seg &sg = cur[(size_t)i];
+                    inv_segs_next.push_back(InvSeg{sg.tree * 2 + ((sg.level + 1) & 1), sg.start, sg.count, inv_chunks_next});
+                    inv_chunks_next += (sg.count + SPLIT_INV_CHUNK - 1) / SPLIT_INV_CHUNK;
+                }
+                inv_next_level = level + 1;
+            }
             if (!use_mm) {
                 // chunk form: launch order = chunks sorted by first row id, one contiguous run per XCD
                 if ((rc = d_info.alloc((size_t)n_chunks)) || (rc = d_sched.alloc((size_t)n_chunks))) { cleanup(); return rc; }
@@ -1610,7 +1707,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             if (side_work) F_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             if (use_mm) {
                 ScopedTimer tm(h, MORNA_T_SPLIT, 4 * (int64_t)D * (rows + A));
-                if ((rc = split_mm_level(h, d_tasks.p, A, S, hp_level, work.p, inv_p, seed, side.p, d_ones.p, image_from, lists_ahead))) {
+                if ((rc = split_mm_level(h, d_tasks.p, A, S, hp_level, work.p, inv_p, seed, side.p, d_ones.p, image_from, lists_ahead, inv_from, level))) {
                     cleanup();
                     return rc;
                 }
@@ -1624,7 +1721,18 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
                                    work.p, d_tasks.p, d_sched.p, n_chunks, seed, hp_level, side.p, d_ones.p);
             }
             F_TRY(hipGetLastError());
+            const double turn_split = debug_turn ? turn_us() : 0.0;
             if ((rc = partition_and_fetch_counts(A, rows))) { cleanup(); return rc; }
+            if (debug_turn) {
+                const double now = turn_us();
+                char line[256];
+                snprintf(line, sizeof line,
+                         "[morna] turn: level=%d attempt=%d tasks=%d counts_complete=%.1f tasks_pulled=%.1f two_means_enqueued=%.1f "
+                         "split_enqueued=%.1f\n",
+                         (int)level, attempt, (int)A, turn_counts, turn_pulled, turn_tm, turn_split);
+                turn_log += line;
+                turn_counts = now;
+            }
             h->stats.split_attempts += A;
             h->stats.split_rows += rows;
             std::vector<int32_t> still;
@@ -1645,7 +1753,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
         if (!fb.empty()) {
             make_tasks(fb, 3, tasks);
             const int32_t A = (int32_t)tasks.size();
-            if ((rc = upload_tasks(tasks))) { cleanup(); return rc; }
+            if ((rc = upload_tasks(tasks, nullptr))) { cleanup(); return rc; }
             hipLaunchKernelGGL(fallback_kernel, dim3((unsigned)A), dim3(256), 0, h->stream, d_tasks.p, N, dpad, seed,
                                side.p, d_ones.p, hp_level);
             F_TRY(hipGetLastError());
@@ -1680,6 +1788,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
     }
 
     write_late_tables();
+    if (debug_turn) fputs(turn_log.c_str(), stderr);
     // consolidate hyperplanes and node tables in HBM
     h->n_split = n_split_total;
     h->n_nodes = (int64_t)ntree.size();
@@ -1717,7 +1826,7 @@ int build_forest(morna_index *h, int32_t n_trees, uint32_t seed)
             const int32_t n16 = (int32_t)(bytes / 16);
             if (n16 > 0)
                 hipLaunchKernelGGL(pull_tasks_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, h->stream, (const int4 *)src,
-                                   (int4 *)dst, n16);
+                                   (int4 *)dst, n16, (int4 *)nullptr, 0);
             if (bytes % 16)   // the tail, if any
                 return hipMemcpyAsync((uint8_t *)dst + (size_t)n16 * 16, h->host_tables.p + (src - dv) + (size_t)n16 * 16, bytes % 16,
                                       hipMemcpyHostToDevice, h->stream);

@@ -483,21 +483,71 @@ __global__ __launch_bounds__(ORD_BLOCK) void order_rank_kernel(const uint16_t *_
     item_at[r] = (int32_t)i;
 }
 
-// inv by row from inv by item: inv_r[tree][rank[item]] = inv[tree][item]
-__global__ __launch_bounds__(256) void order_inv_kernel(const int32_t *__restrict__ inv_by_item, const int32_t *__restrict__ rank,
-                                                        int64_t n_items, int64_t total, int32_t *__restrict__ inv)
+// ---- where every row stands in every tree ---------------------------------------------------------------------------
+// inv[tree][row] = the row's position in the tree, what the contraction's epilogue finds a row's node with.  A partition moves
+// the items of a node; the positions of what a level's partitions moved are rewritten HERE, from the image the children
+// are in, on the side stream under the next level's two_means: the next reader is that level's contraction, which comes
+// after its two_means, and the partition -- a chain of memory round trips on the level's critical path -- neither gathers
+// `rank` nor scatters into `inv` (forest.hip).  One workgroup per SPLIT_INV_CHUNK positions of a run, whatever the run's
+// length (a root's children are 25k positions, a deep level's a few hundred); no chain, no barrier.
+__global__ __launch_bounds__(256) void split_inv_kernel(const InvSeg *__restrict__ segs, int32_t n_segs, int32_t n_chunks,
+                                                        const int32_t *__restrict__ perm /* work buffer [tree][2][n_items] */,
+                                                        int64_t n_items, const int32_t *__restrict__ rank /* row of each item, or null: its id */,
+                                                        int32_t *__restrict__ inv)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int64_t t = i / n_items, item = i - t * n_items;
-    inv[t * n_items + rank[item]] = inv_by_item[i];
+    const int lane = threadIdx.x & (WAVE - 1);
+    // Workgroup g runs on XCD g % 8: each XCD takes one stretch of consecutive chunks, so the scattered stores of a tree
+    // (a window of 4 n_items bytes) meet in ONE L2 and leave it as whole lines -- dealt round-robin, all eight L2s hold
+    // partial lines of every tree and HBM, which two_means lives on just then, gets each line eight times
+    const int run = (n_chunks + 7) >> 3;
+    const int b = (int)(blockIdx.x & 7) * run + (int)(blockIdx.x >> 3);
+    if (b >= n_chunks) return;   // uniform
+    // the last run with first_chunk <= b (first_chunk ascends strictly: no run is empty): every wave searches for itself,
+    // 64 probes a round
+    int lo = 0, hi = n_segs;
+    while (hi - lo > 1) {
+        const int step = (hi - lo + WAVE - 1) / WAVE;
+        const int idx = lo + lane * step;
+        const uint64_t le = __ballot(idx < hi && segs[idx].first_chunk <= b);   // a prefix of the lanes; lane 0 is in it
+        lo += ((int)__builtin_popcountll(le) - 1) * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    const InvSeg s = segs[lo];
+    const int p0 = (b - s.first_chunk) * SPLIT_INV_CHUNK;
+    const int32_t *items = perm + (int64_t)s.image * n_items + s.start;
+    int32_t *out = inv + (int64_t)(s.image >> 1) * n_items;
+    constexpr int PER = SPLIT_INV_CHUNK / 256;
+    int it[PER];
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int p = p0 + u * 256 + (int)threadIdx.x;
+        it[u] = p < s.count ? items[p] : -1;
+    }
+    if (rank) {
+#pragma unroll
+        for (int u = 0; u < PER; u++)
+            if (it[u] >= 0) it[u] = rank[it[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < PER; u++)
+        if (it[u] >= 0) out[it[u]] = s.start + p0 + u * 256 + (int)threadIdx.x;
+}
+
+int split_mm_level_inv(morna_index *h, const InvSeg *d_segs, int32_t n_segs, int32_t n_chunks, const int32_t *perm, const int32_t *rank,
+                       int32_t *inv, hipStream_t stream)
+{
+    if (n_segs <= 0 || n_chunks <= 0) return MORNA_OK;
+    hipLaunchKernelGGL(split_inv_kernel, dim3(8u * (unsigned)((n_chunks + 7) / 8)), dim3(256), 0, stream, d_segs, n_segs, n_chunks, perm,
+                       h->n_items, rank, inv);
+    HIP_TRY(hipGetLastError());
+    return MORNA_OK;
 }
 
 // h->splitmm.maps / invr / table: [rank | item_at], inv by row, the counting sort's table (+ keys).  The fp16 rows stay where they are:
 // a lane of the contraction fetches its row's address through item_at once (a copy of the image in row order cost 0.17 ms
-// of HBM time beside the second level's two_means).  Enqueued on `stream` (the side stream, under that two_means).
-int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_by_item, int32_t n_trees, hipStream_t stream,
-                        const int32_t **rank_out, int32_t **inv_out)
+// of HBM time beside the second level's two_means).  From here on `inv` is by row: the caller fills *inv_out with
+// split_mm_level_inv behind split_mm_order_rows, on the same stream.
+int split_mm_order_begin(morna_index *h, int32_t n_trees, const int32_t **rank_out, int32_t **inv_out)
 {
     const int64_t N = h->n_items;
     DevBuf<int32_t> &maps = h->splitmm.maps, &invr = h->splitmm.invr, &table = h->splitmm.table;
@@ -505,6 +555,18 @@ int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_
     MORNA_TRY(maps.alloc((size_t)N * 2));
     MORNA_TRY(invr.alloc((size_t)n_trees * N));
     MORNA_TRY(table.alloc((size_t)n_blocks * ORD_BINS + ORD_BINS + (size_t)(N + 1) / 2));
+    h->splitmm.ord_valid = true;
+    *rank_out = maps.p;
+    *inv_out = invr.p;
+    return MORNA_OK;
+}
+
+// the sort itself, enqueued on `stream` (the side stream, under the second level's two_means); after split_mm_order_begin
+int split_mm_order_rows(morna_index *h, const uint8_t *side, int32_t n_trees, hipStream_t stream)
+{
+    const int64_t N = h->n_items;
+    DevBuf<int32_t> &maps = h->splitmm.maps, &table = h->splitmm.table;
+    const int32_t n_blocks = (int32_t)((N + ORD_BLOCK - 1) / ORD_BLOCK);
     int32_t *key_base = table.p + (size_t)n_blocks * ORD_BINS;   // [ORD_BINS] items with a smaller key
     uint16_t *key = (uint16_t *)(key_base + ORD_BINS);
     int32_t *rank = maps.p, *item_at = maps.p + N;
@@ -515,12 +577,7 @@ int split_mm_order_rows(morna_index *h, const uint8_t *side, const int32_t *inv_
     hipLaunchKernelGGL(order_scan_keys_kernel, dim3(1), dim3(1024), 0, stream, key_base);
     hipLaunchKernelGGL(order_rank_kernel, dim3((unsigned)n_blocks), dim3(ORD_BLOCK), 0, stream, key, N, n_blocks, table.p, key_base, rank,
                        item_at);
-    const int64_t total = (int64_t)n_trees * N;
-    hipLaunchKernelGGL(order_inv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, inv_by_item, rank, N, total, invr.p);
     HIP_TRY(hipGetLastError());
-    h->splitmm.ord_valid = true;
-    *rank_out = rank;
-    *inv_out = invr.p;
     return MORNA_OK;
 }
 
@@ -619,9 +676,10 @@ int split_mm_level_lists(morna_index *h, const SplitTask *d_tasks, int32_t n_tas
 // number) or the retried ones among them.  After split_mm_level_begin for the same level.  image_from: the two_means form
 // that has written the image of the tasks' slots and reset the open-pair counter, or null: both are done here.
 // lists_ready: split_mm_level_lists has run for these tasks (the caller has ordered it in front of h->stream).
+// inv_from, level: who made `inv` current for this level of the forest, for the MORNA_DEBUG_OPEN line.
 int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, int32_t n_slots, const float *hp_level,
                    const int32_t *perm, const int32_t *inv, uint32_t seed, uint8_t *side, int32_t *ones, const char *image_from,
-                   bool lists_ready)
+                   bool lists_ready, const char *inv_from, int32_t level)
 {
     const int64_t N = h->n_items;
     DevBuf<_Float16> &h16 = h->splitmm.h16;
@@ -680,8 +738,10 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
         fprintf(stderr, "[morna] split_mm level: D=%d split nodes=%d (row, tree) pairs<=%lld open=%u (%.4f %%)\n", h->dim,
                 n_tasks, (long long)cap, n_open, 100.0 * n_open / (double)cap);
         // which way the level went: the tile form, where its task lists were built, who made the hyperplanes' image
-        fprintf(stderr, "[morna] split_mm path: split nodes=%d tiles=%d lists=%s image=%s\n", n_tasks, big ? 256 : 128,
-                !lists ? "none" : lists_ready ? "ahead" : "inline", image_from ? image_from : "converted");
+        // and who left `inv` as the level finds it (forest.hip): the side stream, the partition, the roots' identity
+        fprintf(stderr, "[morna] split_mm path: split nodes=%d tiles=%d lists=%s image=%s inv=%s rows=%s level=%d\n", n_tasks, big ? 256 : 128,
+                !lists ? "none" : lists_ready ? "ahead" : "inline", image_from ? image_from : "converted", inv_from,
+                ord ? "ordered" : "ids", (int)level);
     }
     return MORNA_OK;
 }
