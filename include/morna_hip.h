@@ -422,7 +422,13 @@ int morna_get_norms2(morna_index *h, float *out /* [n] */);
  * Limit that annoy does not have: two_means keeps one centroid on chip (LDS), so the build, the approximate and the
  * exact searches reject dimensions whose padded row (dim rounded up to 256 floats) exceeds 32768 floats
  * (MORNA_E_INVALID, the message names the limit).  Rows past 8192 floats take the wide two_means form.  BASELINE's
- * configurations use 3000 and 8192. */
+ * configurations use 3000 and 8192.
+ * build may return with the forest's last narrow levels (at most n_cus / 8 split nodes) enqueued but not yet followed up:
+ * whichever call touches the handle next finishes them first, and a dense batch of morna_get_nns_by_item / _by_vector /
+ * _by_query_rows starts its contraction beside them.  The forest is the same either way; a failure in that part is
+ * reported by the call that ran it and leaves the index unbuilt.  A caller that orders its own work on the handle's
+ * stream takes the stream from morna_get_stream (or calls morna_synchronize) AFTER build.  MORNA_BUILD_TAIL=0 in the
+ * environment: build returns with everything enqueued, as it always did. */
 int morna_build(morna_index *h, int32_t n_trees, uint32_t seed);
 int32_t morna_get_n_trees(const morna_index *h);
 

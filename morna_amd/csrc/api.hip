@@ -82,11 +82,16 @@ __global__ void gather_rows_kernel(const float *__restrict__ X, const int32_t *_
     for (int z = threadIdx.x; z < dim; z += blockDim.x) dst[z] = src[z];
 }
 
-#define CHECK_H(h)                            \
+#define CHECK_H_ONLY(h)                       \
     if (!(h)) {                                 \
         set_error("null index handle");         \
         return MORNA_E_INVALID;                 \
     }
+// Every entry point that touches the handle first finishes a build that returned with its last narrow levels pending
+// (forest.hip); CHECK_H_ONLY is for the searches that query_batch may start beside that tail (knn.hip).
+#define CHECK_H(h)  \
+    CHECK_H_ONLY(h) \
+    MORNA_TRY(finish_build(h, __func__));
 
 extern "C" {
 
@@ -134,8 +139,12 @@ int morna_index_create(int32_t dim, int32_t device, morna_index **out)
     int rc = h->d_stat.alloc(4);
     if (rc == MORNA_OK && hipMemset(h->d_stat.p, 0, 4 * sizeof(unsigned long long)) != hipSuccess) rc = MORNA_E_HIP;
     if (rc == MORNA_OK && (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
+                           hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking) != hipSuccess ||
                            hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)) {
+                           hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
+                           hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming) != hipSuccess ||
+                           hipEventCreateWithFlags(&h->ev_early_in, hipEventDisableTiming) != hipSuccess ||
+                           hipEventCreateWithFlags(&h->ev_early_out, hipEventDisableTiming) != hipSuccess)) {
         set_error("hipStreamCreate / hipEventCreate failed");
         rc = MORNA_E_HIP;
     }
@@ -143,6 +152,10 @@ int morna_index_create(int32_t dim, int32_t device, morna_index **out)
         if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+        if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
+        if (h->ev_early_in) (void)hipEventDestroy(h->ev_early_in);
+        if (h->ev_early_out) (void)hipEventDestroy(h->ev_early_out);
+        if (h->stream3) (void)hipStreamDestroy(h->stream3);
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
         (void)hipStreamDestroy(h->stream);
         delete h;
@@ -169,7 +182,12 @@ int morna_index_destroy(morna_index *h)
 {
     if (!h) return MORNA_OK;
     (void)hipSetDevice(h->device);
+    // a build that returned with its tail pending is run to its end (its kernels read the handle's memory), then every
+    // stream of the handle is drained before anything is freed
+    (void)finish_build(h, __func__);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
+    if (h->stream3) (void)hipStreamSynchronize(h->stream3);
     (void)morna_comm_destroy(h);
     for (const PendingEv &pe : h->pending_ev) {
         (void)hipEventDestroy(pe.a);
@@ -180,8 +198,12 @@ int morna_index_destroy(morna_index *h)
     if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    hipStream_t s = h->stream, s2 = h->stream2;
+    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
+    if (h->ev_early_in) (void)hipEventDestroy(h->ev_early_in);
+    if (h->ev_early_out) (void)hipEventDestroy(h->ev_early_out);
+    hipStream_t s = h->stream, s2 = h->stream2, s3 = h->stream3;
     delete h;   // DevBuf / PinnedBuf destructors free HBM and the page-locked staging
+    if (s3) (void)hipStreamDestroy(s3);
     if (s2) (void)hipStreamDestroy(s2);
     if (s) (void)hipStreamDestroy(s);
     return MORNA_OK;
@@ -348,6 +370,7 @@ int morna_hash_keys(morna_index *h, const uint8_t *key_bytes, const int64_t *key
 int64_t morna_get_n_items(const morna_index *h)
 {
     if (!h) return 0;
+    (void)finish_build(const_cast<morna_index *>(h), __func__);   // (the ABI's handle is const; a pending build is not the caller's business)
     return h->host_dirty ? h->host_n : h->n_items;
 }
 
@@ -458,11 +481,16 @@ int morna_build(morna_index *h, int32_t n_trees, uint32_t seed)
     return build_forest(h, n_trees, seed);
 }
 
-int32_t morna_get_n_trees(const morna_index *h) { return h && h->built ? h->n_trees : 0; }
+int32_t morna_get_n_trees(const morna_index *h)
+{
+    if (h) (void)finish_build(const_cast<morna_index *>(h), __func__);   // a tail that fails leaves the handle unbuilt: 0 trees
+    return h && h->built ? h->n_trees : 0;
+}
 
 int morna_get_forest_stats(const morna_index *h, morna_forest_stats *out)
 {
-    CHECK_H(h);
+    CHECK_H_ONLY(h);
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));   // the tail's attempts and nodes are part of the stats
     if (!out) return MORNA_E_INVALID;
     *out = h->stats;
     return MORNA_OK;
@@ -505,7 +533,7 @@ int morna_get_forest(morna_index *h, int32_t *node_rec, int32_t *perm, float *hy
 int morna_get_nns_by_vector(morna_index *h, const float *q, int64_t nq, int32_t k, int32_t search_k, int32_t *ids_out,
                             float *dist_out, int32_t *count_out)
 {
-    CHECK_H(h);
+    CHECK_H_ONLY(h);
     if (!q || !ids_out) {
         set_error("get_nns_by_vector: null buffer");
         return MORNA_E_INVALID;
@@ -517,7 +545,7 @@ int morna_get_nns_by_vector(morna_index *h, const float *q, int64_t nq, int32_t 
 int morna_get_nns_by_item(morna_index *h, const int32_t *items, int64_t nq, int32_t k, int32_t search_k,
                           int32_t *ids_out, float *dist_out, int32_t *count_out)
 {
-    CHECK_H(h);
+    CHECK_H_ONLY(h);
     if (!items || !ids_out) {
         set_error("get_nns_by_item: null buffer");
         return MORNA_E_INVALID;
@@ -682,7 +710,8 @@ int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int
 
 int morna_search_sweep_stats(const morna_index *h, double *stats)
 {
-    CHECK_H(h);
+    CHECK_H_ONLY(h);
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
     if (!stats) {
         set_error("search_sweep_stats: null buffer");
         return MORNA_E_INVALID;
@@ -719,7 +748,7 @@ int morna_get_query_rows(morna_index *h, double *rows64, float *rows32)
 
 int morna_get_nns_by_query_rows(morna_index *h, int32_t k, int32_t search_k, int32_t *ids_out, float *dist_out, int32_t *count_out)
 {
-    CHECK_H(h);
+    CHECK_H_ONLY(h);
     MORNA_TRY(query_rows_ready(h));
     if (!ids_out) {
         set_error("get_nns_by_query_rows: null buffer");
@@ -936,6 +965,7 @@ int morna_label_sums_stats(const morna_index *h, double *stats)
         set_error("label_sums_stats: null pointer");
         return MORNA_E_INVALID;
     }
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
     for (int i = 0; i < 6; i++) stats[i] = h->label_stats[i];
     return MORNA_OK;
 }

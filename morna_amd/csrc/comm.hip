@@ -294,11 +294,13 @@ static int exact_sharded(morna_index *h, const double *q_host, const float *q_de
 
 using namespace morna;
 
-#define CHECK_H(h)                      \
-    if (!(h)) {                         \
-        set_error("null index handle"); \
-        return MORNA_E_INVALID;         \
-    }
+// (a build that returned with its last narrow levels pending is finished first: the sharded searches do not overlap it)
+#define CHECK_H(h)                        \
+    if (!(h)) {                           \
+        set_error("null index handle");   \
+        return MORNA_E_INVALID;           \
+    }                                     \
+    MORNA_TRY(finish_build(h, __func__));
 
 extern "C" {
 

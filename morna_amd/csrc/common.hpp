@@ -152,6 +152,57 @@ static_assert(sizeof(InvSeg) == 16, "the runs go up in 16-byte words, behind the
 // children into the other, so nothing is copied back (forest.hip; the leaves are gathered into h->perm at the end).
 #define TASK_ITEMS_AT(t, n_items) (((int64_t)(t).tree * 2 + ((t).level & 1)) * (int64_t)(n_items) + (t).start)
 
+// a finished leaf's items in the work images, on their way into the permutation the searches read (gather_leaves_kernel)
+struct LeafSeg {
+    int32_t tree, level, start, count;
+};
+
+// A forest build under way (forest.hip): what the host driver carries from attempt to attempt and from level to level.
+// build_forest may return with an attempt of a narrow level enqueued and its counts not yet read (`pending`);
+// finish_build collects that attempt and runs every further attempt and level, exactly as the loop would have.
+struct ForestBuild {
+    enum Phase { IDLE, LEVEL, ENQUEUE, COLLECT, FALLBACK, CHILDREN, DONE };
+    int phase = IDLE;
+    bool pending = false;        // an attempt is enqueued and the build has returned to its caller
+    int32_t n_trees = 0;
+    uint32_t seed = 0;
+    // the forest so far
+    std::vector<Seg> cur, nxt;   // the nodes of this level / of the next
+    std::vector<LeafSeg> leaves;
+    int32_t level = 0, next_node_id = 0;
+    int64_t n_split_total = 0;
+    // the node-table entries of the level just finished, written once the next level is under way (or at the end)
+    std::vector<Seg> late_parents;
+    std::vector<int32_t> late_ones;
+    int32_t late_first_id = 0;
+    int64_t late_first_hp = 0;
+    bool late_pending = false;
+    // `inv` (matrix-core split): true as of level inv_level; the leaves made since start at leaves[inv_leaf_mark]
+    int32_t *inv_p = nullptr;
+    const int32_t *rank_p = nullptr;
+    int32_t inv_level = 0;
+    size_t inv_leaf_mark = 0;
+    const char *inv_from = "iota";
+    std::vector<InvSeg> inv_segs, inv_segs_next;
+    int32_t inv_chunks_next = 0, inv_next_level = -1;
+    // the level
+    std::vector<int32_t> split_idx, final_ones, todo, tree_first, h_ones;
+    std::vector<SplitTask> tasks;
+    size_t leaves_before = 0, leaves_after = 0;
+    bool leaves_listed = false;
+    int32_t S = 0;
+    // the attempt
+    int attempt = 0;
+    int32_t A = 0;               // tasks whose counts the mailbox is polled for
+    int64_t rows = 0;
+    uint32_t epoch = 0;
+    // MORNA_DEBUG_TURN
+    double turn_t0 = 0, turn_counts = 0, turn_pulled = 0, turn_tm = 0, turn_split = 0;
+    std::string turn_log;
+    // what ran behind a deferral (MORNA_DEBUG_OPEN)
+    int32_t defer_level = -1, tail_levels = 0, tail_attempts = 0;
+};
+
 struct Timer {
     double ms = 0;
     int64_t launches = 0, bytes = 0;
@@ -261,6 +312,11 @@ struct morna_index {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_tables = nullptr;    // behind the node-table copies of the last forest build
     bool ev_tables_pending = false;
+    // A query batch that starts while a build is pending (knn.hip): its contraction runs on stream3, which waits for
+    // ev_tail (recorded on `stream` in front of the deferred attempt); ev_early_in / ev_early_out: its inputs are in place /
+    // its scores are
+    hipStream_t stream3 = nullptr;
+    hipEvent_t ev_tail = nullptr, ev_early_in = nullptr, ev_early_out = nullptr;
     // right-side counts of a level, written by partition_kernel straight into page-locked host memory ((epoch << 32) |
     // count per task): the host polls them instead of an event hand-over + copy + stream wait per level
     morna::PinnedBuf host_counts{hipHostMallocCoherent | hipHostMallocMapped};
@@ -311,6 +367,9 @@ struct morna_index {
 
     // query workspace (grown on demand)
     morna::DevBuf<uint8_t> ws;
+    // what the contraction of a batch that starts beside a pending build reads and writes: item ids, query image and its
+    // three floats per query, scores (placed before anything is enqueued: `ws` is sized from n_nodes, unknown until the tail ends)
+    morna::DevBuf<uint8_t> q_early;
     // exact search: query images, scan values and results of a batch; the candidates and their fp64 distances (knn.hip)
     morna::DevBuf<uint8_t> ex_ws;
     morna::DevBuf<int32_t> ex_cand;
@@ -328,6 +387,7 @@ struct morna_index {
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
+    morna::ForestBuild fb;
     morna::HalfRows half;
     morna::SplitMmScratch splitmm;
     morna::QueryRows qrows;      // morna_build_query_rows
@@ -415,7 +475,11 @@ int build_query_rows(morna_index *h, const uint8_t *key_bytes, const int64_t *ke
                      const int32_t *ids, const int32_t *cov, const double *w, int64_t nq);
 int hash_keys_device(morna_index *h, const uint8_t *key_bytes, const int64_t *key_off, int64_t J,
                      int32_t *hash_out, int32_t *col_out, int32_t *sign_out);
+// May return with the last narrow levels still to run (h->fb.pending; MORNA_BUILD_TAIL=0: never).  EVERY entry point that
+// touches the handle calls finish_build first, except the dense first batch of query_batch, which starts its contraction first.
 int build_forest(morna_index *h, int32_t n_trees, uint32_t seed);
+// who: the entry point, for the MORNA_DEBUG_OPEN line.  A no-op when nothing is pending; a failure leaves the handle unbuilt.
+int finish_build(morna_index *h, const char *who);
 // splitmm.hip: the split of a whole level on the matrix cores (fp16 filter, exact fp32 for what it cannot decide)
 int split_mm_prepare_rows(morna_index *h, hipStream_t stream);   // stream: the handle's main or side stream
 int split_mm_convert_rows(morna_index *h, const float *src, int64_t rows, _Float16 *dst, float *norm, float *err,

@@ -302,6 +302,7 @@ int morna_add_items_from_store(morna_index *h, morna_jstore *s, const int64_t *e
         set_error("add_items_from_store: the store has no weights: call morna_jstore_set_weights first");
         return MORNA_E_STATE;
     }
+    MORNA_TRY(morna::finish_build(h, __func__));   // a build whose last narrow levels are pending is a built index
     if (h->built) {
         set_error("You can't add an item to a built index");
         return MORNA_E_STATE;

@@ -1233,7 +1233,13 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 const morna_restriction *rst, const int32_t *q_group_host, int32_t n_trees_used)
 {
     if (q_stride <= 0) q_stride = h->dim;
-    if (!h->built) {
+    // A build that returned with its last narrow levels pending (forest.hip): every case but the dense first batch below
+    // finishes it here, first thing.  That one needs nothing of the forest for its contraction and starts it beside the tail.
+    const bool timed = h->timing && (h->timing_mask & ((1u << MORNA_T_QUERY) | (1u << MORNA_T_QUERY_FILTER)));
+    bool early = h->fb.pending && !rst && !packed_dev && n_trees_used == 0 && ids_out && !timed && h->half.valid && k > 0 && nq > 0 &&
+                 h->dpad <= Q_MAX_DPAD;
+    if (!early) MORNA_TRY(finish_build(h, "query_batch"));
+    if (!h->built && !early) {
         set_error("index has not been built: call build() before searching");
         return MORNA_E_STATE;
     }
@@ -1285,9 +1291,106 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
     const bool use_filter = !spread && filter_pays;
     const bool may_dense = use_filter && dense_on && dense_pays(nq);
 
+    // the whole-batch contraction: 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup
+    // per CU), the 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0: for all rows).  st_big / st_rem: the streams
+    // of the two launches; returns the rows the large form took
+    auto launch_contraction = [&](int64_t nb, const _Float16 *q16, const int32_t *qrow, float *scores, hipStream_t st_big,
+                                  hipStream_t st_rem, int64_t *big_rows_out) -> int {
+        static const bool big_on = env_on("MORNA_QUERY_BIG");
+        const _Float16 *X16 = h->half.x16.p;
+        int64_t big_tiles = 0, big_rows = 0;
+        if (big_on && nb >= 512) {
+            const int64_t n_ct_big = (nb + 255) / 256;
+            int64_t a = h->n_cus, b = n_ct_big;   // tiles per round of the chip: n_cus / gcd(n_cus, n_ct_big)
+            while (b) { const int64_t t = a % b; a = b; b = t; }
+            const int64_t per_round = h->n_cus / a;
+            big_tiles = (N / 256) / per_round * per_round;
+        }
+        if (big_tiles > 0) {
+            const unsigned n_ct_big = (unsigned)((nb + 255) / 256);
+            HIP_TRY(hipFuncSetAttribute((const void *)query_scores_big_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 256 * 4));
+            hipLaunchKernelGGL((query_scores_big_kernel<64, 2>), dim3(8u * (unsigned)((big_tiles + 7) / 8) * n_ct_big), dim3(1024), 128 * 256 * 4,
+                               st_big, X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, (int32_t)big_tiles);
+            big_rows = big_tiles * 256;
+        }
+        if (big_rows < N) {
+            const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N - big_rows + 127) / 128);
+            HIP_TRY(hipFuncSetAttribute((const void *)query_scores_kernel<128, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MM16_LDS));
+            // (the rows behind the whole rounds of the 256 x 256 form: on the side stream, in front of the traversal,
+            // when the large form runs -- behind it on the main stream they were 0.05 ms of the batch's critical path)
+            hipLaunchKernelGGL((query_scores_kernel<128, 64, 2>), dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS,
+                               big_tiles > 0 ? st_rem : st_big, X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, big_rows);
+        }
+        HIP_TRY(hipGetLastError());
+        *big_rows_out = big_rows;
+        return MORNA_OK;
+    };
+
+    // ---- the first batch beside a pending build.  What does not depend on the forest -- the item ids or query vectors, their
+    // fp16 image, both contraction launches -- goes onto stream3, behind ev_tail (recorded in front of the deferred
+    // attempt: the wide levels and the fp16 rows are done, the tail's own kernels are not waited for).  Not stream2: a tail
+    // attempt in the matrix-core form puts its side work there and would queue behind the contraction.  Everything these
+    // kernels read or write lies in h->q_early, sized and placed now: h->ws is sized from n_nodes, which only the finished
+    // tail knows, and may move when it grows.  Nothing of the build uses q_early.  Then the tail is finished; root margins
+    // and descents follow it on h->stream; the refine step joins both.
+    uint8_t *e_items = nullptr, *e_q = nullptr, *e_q16 = nullptr, *e_qf = nullptr, *e_scores = nullptr;
+    int64_t e_big_rows = 0;
+    if (early) {
+        // one batch of all queries, whatever n_nodes turns out to be?  Without the per-node term; checked again below
+        const size_t per_q0 = (size_t)cap * 16 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) + (bm_lds ? 0 : (size_t)bm_words * 4) +
+                              (size_t)k * 8 + 16 + (size_t)N * 4;
+        early = may_dense && nq <= (int64_t)(((size_t)1 << 30) / per_q0);
+        if (!early) {   // not the dense case after all
+            MORNA_TRY(finish_build(h, "query_batch"));
+            if (!h->built) {
+                set_error("index has not been built: call build() before searching");
+                return MORNA_E_STATE;
+            }
+        }
+    }
+    if (early) {
+        const size_t z_items = align_up((size_t)nq * 4, 256), z_q = q_host ? align_up((size_t)nq * h->dpad * 4, 256) : 0,
+                     z_q16 = q_host ? align_up((size_t)nq * h->dpad * 2, 256) : 0, z_qf = align_up((size_t)nq * 4, 256),
+                     z_scores = align_up((size_t)nq * N * 4, 256);
+        MORNA_TRY(h->q_early.alloc(z_items + z_q + z_q16 + 3 * z_qf + z_scores));
+        uint8_t *p = h->q_early.p;
+        e_items = p; p += z_items;
+        e_q = p; p += z_q;
+        e_q16 = p; p += z_q16;
+        e_qf = p; p += 3 * z_qf;
+        e_scores = p;
+        hipStream_t s3 = h->stream3;
+        HIP_TRY(hipStreamWaitEvent(s3, h->ev_tail, 0));
+        const _Float16 *q16 = h->half.x16.p;
+        const int32_t *qrow = (const int32_t *)e_items;
+        if (q_host) {
+            HIP_TRY(hipMemsetAsync(e_q, 0, (size_t)nq * h->dpad * 4, s3));
+            HIP_TRY(hipMemcpy2DAsync(e_q, (size_t)h->dpad * 4, q_host, (size_t)q_stride * 4, (size_t)h->dim * 4, (size_t)nq,
+                                     hipMemcpyDefault, s3));
+            MORNA_TRY(split_mm_convert_rows(h, (const float *)e_q, nq, (_Float16 *)e_q16, (float *)e_qf, (float *)(e_qf + z_qf),
+                                            (float *)(e_qf + 2 * z_qf), s3));
+            q16 = (const _Float16 *)e_q16;
+            qrow = nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(e_items, items_host, (size_t)nq * 4, hipMemcpyHostToDevice, s3));
+        }
+        HIP_TRY(hipEventRecord(h->ev_early_in, s3));   // the traversal reads the ids / vectors too
+        MORNA_TRY(launch_contraction(nq, q16, qrow, (float *)e_scores, s3, s3, &e_big_rows));
+        HIP_TRY(hipEventRecord(h->ev_early_out, s3));
+        const int rc = finish_build(h, "query_batch, beside its contraction");
+        if (rc != MORNA_OK) {
+            (void)hipStreamSynchronize(s3);
+            return rc;
+        }
+    }
+
     const size_t per_q = (size_t)h->n_nodes * 8 + (size_t)cap * 16 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) +
                          (bm_lds ? 0 : (size_t)bm_words * 4) + (size_t)k * 8 + 16 + (may_dense ? (size_t)N * 4 : 0);
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(((size_t)1 << 30) / per_q)));
+    if (early && batch != nq) {   // the forest has so many nodes that the queries go in several batches: the early scores are
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_out, 0));   // not used (the same kernels make them again, batch by batch)
+        early = false;
+    }
     const size_t s_pq = align_up((size_t)batch * h->n_nodes * 8, 256), s_keys = align_up((size_t)batch * cap * 8, 256),
                  s_q = q_host ? align_up((size_t)batch * h->dpad * 4, 256) : 0,
                  s_q16 = q_host && may_dense ? align_up((size_t)batch * h->dpad * 2, 256) : 0,
@@ -1295,7 +1398,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                  s_cand = align_up((size_t)batch * cap * 4, 256),
                  s_bm = bm_lds ? 0 : align_up((size_t)batch * bm_words * 4, 256),
                  s_ids = align_up((size_t)batch * k * 4, 256),
-                 s_scores = may_dense ? align_up((size_t)batch * N * 4, 256) : 0;
+                 s_scores = may_dense && !early ? align_up((size_t)batch * N * 4, 256) : 0;
     MORNA_TRY(h->ws.alloc(s_pq + s_keys + s_q + s_q16 + 9 * s_qf + 2 * s_cand + s_bm + 2 * s_ids + s_scores + (rst ? s_qf : 0)));
     MORNA_TRY(h->d_stat.alloc(4));
     if (use_filter) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
@@ -1329,6 +1432,13 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         P.dist_out = (float *)p; p += s_ids;
         P.count_out = (int32_t *)p; p += s_qf;
         float *scores = (float *)p; p += s_scores;
+        if (early) {   // (one batch: q0 == 0, nb == nq) what the contraction on stream3 reads and writes
+            const size_t z_qf = align_up((size_t)nq * 4, 256);
+            Qd = (float *)e_q; Q16 = (_Float16 *)e_q16;
+            q_n16 = (float *)e_qf; q_e16 = (float *)(e_qf + z_qf); q_scale = (float *)(e_qf + 2 * z_qf);
+            d_items = (int32_t *)e_items;
+            scores = (float *)e_scores;
+        }
         RestrictArgs R = {nullptr, nullptr, nullptr};
         if (rst) {
             R.deny = rst->deny.p;
@@ -1357,6 +1467,11 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         if (spread && !q_host && nb <= 16) {
             P.n_inline = (int32_t)nb;
             for (int64_t i = 0; i < nb; i++) P.inline_items[i] = items_host[q0 + i];
+        } else
+        if (early) {   // in place since stream3's copies; whatever reads them on h->stream comes behind those
+            HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_in, 0));
+            if (q_host) P.Q = Qd;
+            else P.items = d_items;
         } else
         if (q_host) {
             bool staged = false;
@@ -1470,47 +1585,28 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 const _Float16 *q16 = P.X16;
                 const int32_t *qrow = P.items;
                 if (q_host) {
-                    split_mm_convert_rows(h, Qd, nb, Q16, q_n16, q_e16, q_scale, h->stream);
+                    if (!early) split_mm_convert_rows(h, Qd, nb, Q16, q_n16, q_e16, q_scale, h->stream);
                     q16 = Q16; qrow = nullptr;
                     P.qn16 = q_n16; P.qe16 = q_e16; P.qscale = q_scale;
                 } else {
                     P.qn16 = P.xn16; P.qe16 = P.xe16; P.qscale = P.xscale;
                 }
-                HIP_TRY(hipEventRecord(h->ev_fork, h->stream));   // the query vectors (and their fp16 image) / item ids are in place
-                HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-                ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
-                // 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup per CU), the
-                // 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0: for all rows)
-                static const bool big_on = env_on("MORNA_QUERY_BIG");
-                int64_t big_tiles = 0;
-                if (big_on && nb >= 512) {
-                    const int64_t n_ct_big = (nb + 255) / 256;
-                    int64_t a = h->n_cus, b = n_ct_big;   // tiles per round of the chip: n_cus / gcd(n_cus, n_ct_big)
-                    while (b) { const int64_t t = a % b; a = b; b = t; }
-                    const int64_t per_round = h->n_cus / a;
-                    big_tiles = (N / 256) / per_round * per_round;
+                if (early) {   // enqueued on stream3 before the tail was finished (above)
+                    P.big_rows = e_big_rows;
+                } else {
+                    HIP_TRY(hipEventRecord(h->ev_fork, h->stream));   // the query vectors (and their fp16 image) / item ids are in place
+                    HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+                    ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
+                    MORNA_TRY(launch_contraction(nb, q16, qrow, scores, h->stream, h->stream2, &P.big_rows));
                 }
-                if (big_tiles > 0) {
-                    const unsigned n_ct_big = (unsigned)((nb + 255) / 256);
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_scores_big_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 256 * 4));
-                    hipLaunchKernelGGL((query_scores_big_kernel<64, 2>), dim3(8u * (unsigned)((big_tiles + 7) / 8) * n_ct_big), dim3(1024), 128 * 256 * 4,
-                                       h->stream, P.X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, (int32_t)big_tiles);
-                    P.big_rows = big_tiles * 256;
-                    P.eacc_big = (4.f * (float)h->dpad + 2.f) * 5.9604645e-8f + 4.1e-6f;   // EACC for ONE chain of dpad products
-                }
-                if (P.big_rows < N) {
-                    const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N - P.big_rows + 127) / 128);
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_scores_kernel<128, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MM16_LDS));
-                    // (the rows behind the whole rounds of the 256 x 256 form: on the side stream, in front of the traversal,
-                    // when the large form runs -- behind it on the main stream they were 0.05 ms of the batch's critical path)
-                    hipLaunchKernelGGL((query_scores_kernel<128, 64, 2>), dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS,
-                                       big_tiles > 0 ? h->stream2 : h->stream, P.X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, P.big_rows);
-                }
+                if (P.big_rows > 0) P.eacc_big = (4.f * (float)h->dpad + 2.f) * 5.9604645e-8f + 4.1e-6f;   // EACC for ONE chain of dpad products
                 P.scores = scores;
             }
             // beside the contraction (matrix cores, LDS) the traversal is a latency chain on one wave per query: it
             // runs on the side stream and the refine step waits for both
-            hipStream_t ts = dense ? h->stream2 : h->stream;   // (forked above, before the contraction was enqueued)
+            // (forked above, before the contraction was enqueued; a batch that started beside a pending build: the
+            // contraction is on stream3 and the traversal follows the tail on the main stream)
+            hipStream_t ts = dense && !early ? h->stream2 : h->stream;
             // Root margins by query groups (a hyperplane fetched once per QR_Q queries), then the one-wave descent of the
             // spread form -- while the rows have a length the register forms are built for and the roots do split;
             // otherwise (and with MORNA_QUERY_SPLIT_TRAVERSE=0) the fused kernel, one workgroup per query.
@@ -1560,7 +1656,9 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
                 hipLaunchKernelGGL(query_traverse_kernel<false>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, ts, P);
             }
-            if (dense) {
+            if (early) {
+                HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_out, 0));
+            } else if (dense) {
                 HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
                 HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             }
@@ -1613,6 +1711,7 @@ int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const in
                  int32_t *count_out, int32_t *ncand_out, int32_t *ndots_out, const int32_t *ex_ids_host,
                  const int32_t *ex_count_host, int32_t *hits_out)
 {
+    MORNA_TRY(finish_build(h, "search_sweep"));   // (reads the node tables the tail of a pending build writes)
     if (q_stride <= 0) q_stride = h->dim;
     h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
     if (!h->built) {
@@ -1930,6 +2029,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const int32_t *__restri
 int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, int64_t nq, int32_t kk, int32_t k,
                    int32_t *ids_out, float *dist_out, int32_t *count_out)
 {
+    MORNA_TRY(finish_build(h, "merge_topk_dev"));
     if (world <= 0 || world > 64 || nq < 0 || kk <= 0 || kk > 255 || k <= 0 || !gathered_dev || !ids_out) {
         set_error("merge_topk_dev: invalid argument (world <= 64, kk <= 255)");
         return MORNA_E_INVALID;
@@ -2705,6 +2805,7 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
                      int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
                      const double *q_dev64, const morna_restriction *rst, const int32_t *q_group_host)
 {
+    MORNA_TRY(finish_build(h, "exact_search"));   // (shares the handle's stream and workspace with the tail of a pending build)
     MORNA_TRY(upload_host_rows(h));
     if (rst) MORNA_TRY(restriction_usable(h, rst));
     if (h->n_items <= 0) {
@@ -2902,6 +3003,7 @@ int label_sums(morna_index *h, const morna_restriction *rst, const double *q_hos
                uint64_t *sums_out, int32_t *counts_out)
 {
     for (int i = 0; i < 6; i++) h->label_stats[i] = 0.0;
+    MORNA_TRY(finish_build(h, "label_sums"));
     MORNA_TRY(upload_host_rows(h));
     if (rst) MORNA_TRY(restriction_usable(h, rst));
     if (h->n_items <= 0) {

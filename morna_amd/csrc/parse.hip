@@ -1015,6 +1015,7 @@ int morna_build_query_rows(morna_index *h, const morna_lines *T)
         set_error("build_query_rows: null argument");
         return MORNA_E_INVALID;
     }
+    MORNA_TRY(morna::finish_build(h, __func__));   // (shares the handle's stream and scratch with a pending build's tail)
     return morna::build_query_rows(h, T->key_bytes.data(), T->key_off.data(), (int64_t)T->idf.size(), T->row_ptr.data(),
                                    T->item_ids.data(), T->cov.data(), T->idf.data(), (int64_t)T->ext_ids.size());
 }
