@@ -1,10 +1,30 @@
 // knn.hip -- batched nearest-neighbour queries on gfx950.
 //
-// query_kernel   : annoy's _get_all_nns (get_nns_by_vector / get_nns_by_item,
-//                  reference call sites morna.py:651, 659, 762, 769) -- one
-//                  workgroup per query fuses the best-first forest traversal
-//                  with the brute-force angular refine of the candidate rows and
-//                  the (distance, id) top-k selection.
+// query_*_kernel : annoy's _get_all_nns (get_nns_by_vector / get_nns_by_item,
+//                  reference call sites morna.py:651, 659, 762, 769) -- the
+//                  best-first forest traversal, the brute-force angular refine
+//                  of the candidate rows and the (distance, id) top-k selection.
+//                  The host side (query_batch, "the approximate search, host
+//                  side" below) runs in stages, and per batch of queries launches
+//                    stage     the queries' vectors or item ids (copies only)
+//                    traverse  spread form (under 64 queries): query_roots_kernel,
+//                              query_descend_kernel; else root margins by query
+//                              groups and one-wave descents: query_roots_batch_kernel,
+//                              query_descend_kernel; or fused: query_traverse_kernel
+//                              (a restricted call: the *_restricted_kernel forms)
+//                    filter    beside the traversal, for a dense batch: the fp16
+//                              image of the queries (splitmm.hip) and the whole-batch
+//                              contraction, query_scores_big_kernel + query_scores_kernel
+//                              -- for the first batch after build() already beside
+//                              the build's tail (EarlyContraction)
+//                    refine    spread form: query_cand_dots_kernel, query_topk_kernel;
+//                              else query_refine_kernel<0 none / 1 gather / 2 dense>
+//                    deliver   one copy of the result block (pack_topk_kernel for
+//                              the row-sharded search)
+//                  search_sweep has the same stages for a grid of (tree count,
+//                  search_k) cells: query_roots[_batch]_kernel, query_descend_sweep_kernel,
+//                  [query_scores_kernel, sweep_bounds_kernel, sweep_threshold_kernel,]
+//                  sweep_cand_dots_kernel, sweep_topk_kernel, [sweep_hits_kernel].
 // exact_*_kernel : MornaSearch.exact_search_nn + cosine_distance (morna.py:
 //                  681-716, 101-114) -- an fp32 scan of all rows picks every row
 //                  that can be in the top k, then those rows are re-evaluated in
@@ -1210,7 +1230,6 @@ int fetch_results(morna_index *h, const uint8_t *d_block, size_t bytes, size_t s
     return MORNA_OK;
 }
 
-// q_host: query vectors in host OR device memory (unified addressing), q_stride floats apart (0 = dim)
 // A restriction a search is about to use: made for this handle and for the rows it holds now.
 static int restriction_usable(const morna_index *h, const morna_restriction *rst)
 {
@@ -1226,6 +1245,465 @@ static int restriction_usable(const morna_index *h, const morna_restriction *rst
     return MORNA_OK;
 }
 
+// ---- the approximate search, host side --------------------------------------------------------------------------------
+// query_batch and search_sweep read from top to bottom: check, plan, [start the early contraction,] then per batch: bind
+// the workspace, stage the queries, traverse, refine, deliver.  What the two share comes first: the dispatch over the row
+// width, the launchers, the set-up of QueryParams, the staging of the queries and the workspace carver.
+
+// float4 per lane of a row, where the kernels have a register form of that width and it is at most max_nv; else 0
+static inline int row_nv(int32_t dpad, int max_nv)
+{
+    const int nv = dpad / 256;
+    const bool built = nv == 1 || nv == 2 || nv == 3 || nv == 4 || nv == 6 || nv == 8 || nv == 12 || nv == 16 || nv == 24 || nv == 32;
+    return dpad % 256 == 0 && built && nv <= max_nv ? nv : 0;
+}
+
+// The one switch over the row width: f(std::integral_constant<int, NV>) with NV = row_nv(dpad, MAX_NV).  MAX_NV bounds what
+// a call site instantiates: 32 for the plain and restricted descents, 12 for the sweep descent and the root margins.
+template <int NV, int MAX_NV>
+using nv_upto = std::integral_constant<int, (NV <= MAX_NV ? NV : 0)>;
+
+template <int MAX_NV, class F>
+static inline int with_row_nv(int32_t dpad, F &&f)
+{
+    switch (row_nv(dpad, MAX_NV)) {
+    case 1: return f(nv_upto<1, MAX_NV>{});
+    case 2: return f(nv_upto<2, MAX_NV>{});
+    case 3: return f(nv_upto<3, MAX_NV>{});
+    case 4: return f(nv_upto<4, MAX_NV>{});
+    case 6: return f(nv_upto<6, MAX_NV>{});
+    case 8: return f(nv_upto<8, MAX_NV>{});
+    case 12: return f(nv_upto<12, MAX_NV>{});
+    case 16: return f(nv_upto<16, MAX_NV>{});
+    case 24: return f(nv_upto<24, MAX_NV>{});
+    case 32: return f(nv_upto<32, MAX_NV>{});
+    default: return f(nv_upto<0, MAX_NV>{});
+    }
+}
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument
+template <class F>
+static inline int with_flag(bool b, F &&f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// A launch with `bytes` of dynamic LDS.  Above `limit` bytes the kernel's dynamic-LDS limit is raised first: LDS_1WAVE for
+// the one-wave descents, LDS_DEFAULT elsewhere, LDS_ALWAYS for the contraction kernels, whose need is above either.  (Not
+// raised more often than that: hipFuncSetAttribute is host time of the single-query path.)
+#define LDS_1WAVE ((size_t)32 * 1024)
+#define LDS_DEFAULT ((size_t)48 * 1024)
+#define LDS_ALWAYS ((size_t)0)
+template <class K, class... A>
+static inline int launch_lds(K kernel, dim3 grid, dim3 block, size_t bytes, size_t limit, hipStream_t st, const A &...args)
+{
+    if (bytes > limit) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL(kernel, grid, block, bytes, st, args...);
+    return MORNA_OK;
+}
+
+// What a search call works out once, before its first batch.  search_sweep fills the same plan for its deepest cell.
+struct QueryPlan {
+    int32_t T_used;        // the trees the search walks: all of them, or a prefix (morna_hip.h, "tree-prefix search")
+    int32_t search_k;
+    int32_t cap;           // candidates per query: |nns| < search_k before the last pop, which adds at most K ids
+    int32_t bm_words;
+    bool bm_lds;           // the sample bitmap lives in LDS (else in the workspace)
+    size_t lds_q, lds_bm;  // dynamic LDS of the query image and of the bitmap (0: not in LDS)
+    bool spread;           // fewer queries than would give every CU a workgroup: each query's work is dealt out
+    bool use_filter;       // candidate filter on the fp16 rows; pays when a query has many more candidates than results
+    bool may_dense;        // ... through the whole-batch contraction, for the batches dense_pays() says so of
+    int64_t batch;         // queries per batch (the 1 GiB workspace rule)
+};
+
+// once per process: MORNA_QUERY_FILTER=0: every candidate gets the fp32 dot; MORNA_QUERY_DENSE=0 keeps the per-candidate
+// gather form of the filter
+static bool query_filter_on() { static const bool on = env_on("MORNA_QUERY_FILTER"); return on; }
+static bool query_dense_on() { static const bool on = env_on("MORNA_QUERY_DENSE"); return on; }
+
+// the whole-batch contraction reads every fp16 row once; the gather form reads min(cap, ~K) rows per query
+// (C3, 48 / 63 queries: 207 us through the contraction, 231 / 282 us through the spread form; 32: the spread form's 174 us)
+static bool dense_pays(const morna_index *h, int32_t cap, int64_t nb)
+{
+    return nb >= 40 && nb * std::min<int64_t>(cap, h->K) >= 2 * h->n_items;
+}
+
+static int require_built(const morna_index *h)
+{
+    if (h->built) return MORNA_OK;
+    set_error("index has not been built: call build() before searching");
+    return MORNA_E_STATE;
+}
+
+// the checks of both searches; what: "get_nns" / "search_sweep"
+static int check_search_call(const morna_index *h, const char *what, int32_t k, int64_t nq)
+{
+    if (k <= 0 || nq < 0) {
+        set_error("%s: n must be positive", what);
+        return MORNA_E_INVALID;
+    }
+    if (h->dpad > Q_MAX_DPAD) {   // the query image and the traversal's LDS (an index built elsewhere, loaded here)
+        set_error("%s: dimension %d is above the supported %d", what, h->dim, Q_MAX_DPAD);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+static int check_tree_count(const morna_index *h, const char *what, int32_t t)
+{
+    if (t >= 1 && t <= h->n_trees) return MORNA_OK;
+    set_error("%s: %d trees asked for, the forest has %d", what, t, h->n_trees);
+    return MORNA_E_RANGE;
+}
+
+static int check_items(const morna_index *h, const int32_t *items_host, int64_t nq)
+{
+    for (int64_t i = 0; i < nq; i++)
+        if (items_host[i] < 0 || items_host[i] >= h->n_items) {
+            set_error("item id %d out of range [0, %lld)", items_host[i], (long long)h->n_items);
+            return MORNA_E_RANGE;
+        }
+    return MORNA_OK;
+}
+
+// the restriction of a call as the *_restricted_kernel forms take it; q_group_dev [nq] or null: the queries' own groups
+static RestrictArgs restrict_args(const morna_restriction *rst, const int32_t *q_group_dev)
+{
+    RestrictArgs R = {nullptr, nullptr, nullptr};
+    if (rst) {
+        R.deny = rst->deny.p;
+        R.group = rst->has_group ? rst->group.p : nullptr;
+        R.q_group = R.group ? q_group_dev : nullptr;
+    }
+    return R;
+}
+
+// the handle's rows and forest, and the plan's numbers; everything of the workspace, the queries and the filter is null
+static QueryParams base_params(const morna_index *h, const QueryPlan &pl, int32_t k)
+{
+    QueryParams P = {};
+    P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = h->n_items; P.dpad = h->dpad; P.n_trees = pl.T_used; P.K = h->K;
+    P.node_rec = h->node_rec.p; P.node_tree = h->node_tree.p; P.node_hp = h->node_hp.p; P.hp = h->hp.p;
+    P.perm = h->perm.p; P.n_nodes = h->n_nodes;
+    P.k = k; P.search_k = pl.search_k; P.cap = pl.cap; P.bm_words = pl.bm_words;
+    P.stat = h->d_stat.p;
+    return P;
+}
+
+// the fp16 image of the rows and its bounds (split_mm_prepare_rows has made them)
+static void set_filter_rows(const morna_index *h, QueryParams &P)
+{
+    const float *xn = h->half.xn.p;
+    P.X16 = h->half.x16.p;
+    P.xn16 = xn; P.xscale = xn + h->n_items; P.xe16 = xn + 2 * h->n_items;
+    // gather form: |cos from the fp16 row - cos from the fp32 row| <= 2^-11 (one rounding to 11 bits, the query
+    // is not rounded) + the fp32 accumulations of both dots (any order: < dpad * 2^-24 each); the distance is
+    // 2 - 2 cos; 1e-5 covers the evaluation of ang_dist itself
+    P.delta = 2.f * (1.02f * 0.00048828125f + 2.f * (float)h->dpad * 5.9604645e-8f) + 1e-5f;
+    P.eacc = mm16_eacc(h->dpad);
+}
+
+// A workspace described once: the same layout code runs over a null base, for the size, and over the allocation, for the
+// pointers, so the two cannot disagree.  Every piece starts on a 256-byte boundary; a piece of no elements takes no room.
+struct Carver {
+    uint8_t *base;   // null: only the size is wanted
+    size_t used = 0;
+    template <class T>
+    T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + used) : nullptr;
+        used += align_up(count * sizeof(T), 256);
+        return p;
+    }
+};
+
+// layout(Carver &) twice: sizes buf, then binds the pointers
+template <class F>
+static int carve_workspace(DevBuf<uint8_t> &buf, F &&layout)
+{
+    Carver size{nullptr};
+    layout(size);
+    MORNA_TRY(buf.alloc(size.used));
+    Carver c{buf.p};
+    layout(c);
+    return MORNA_OK;
+}
+
+// The queries of a batch on the device, and what the whole-batch contraction makes of them.  Part of h->ws; for a batch that
+// starts beside a pending build, of h->q_early (EarlyContraction).
+struct QueryInputs {
+    int32_t *items;                // [n] by item (part of the workspace: a hipMalloc / hipFree per call costs tens of microseconds)
+    float *Q;                      // [n][dpad] by vector
+    _Float16 *Q16;                 // [n][dpad] by vector, when the contraction may run: the fp16 image of Q ...
+    float *qn16, *qe16, *qscale;   // [n] ... and its norms, rounding-error norms and scales
+    float *scores;                 // [n][n_items] the contraction's output
+    void carve(Carver &c, const morna_index *h, int64_t n, bool by_vector, bool half_image, bool with_scores)
+    {
+        items = c.take<int32_t>((size_t)n);
+        Q = c.take<float>(by_vector ? (size_t)n * h->dpad : 0);
+        Q16 = c.take<_Float16>(by_vector && half_image ? (size_t)n * h->dpad : 0);
+        qn16 = c.take<float>((size_t)n);
+        qe16 = c.take<float>((size_t)n);
+        qscale = c.take<float>((size_t)n);
+        scores = c.take<float>(with_scores ? (size_t)n * h->n_items : 0);
+    }
+};
+
+// Queries q0 .. q0 + nb of the call onto stream st: the vectors padded to the row stride (q_host: host OR device memory,
+// q_stride floats apart), or the item ids.
+static int stage_queries(morna_index *h, const QueryInputs &in, const float *q_host, int64_t q_stride, const int32_t *items_host,
+                         int64_t q0, int64_t nb, hipStream_t st)
+{
+    if (q_host) {
+        HIP_TRY(hipMemsetAsync(in.Q, 0, (size_t)nb * h->dpad * 4, st));
+        HIP_TRY(hipMemcpy2DAsync(in.Q, (size_t)h->dpad * 4, q_host + q0 * q_stride, (size_t)q_stride * 4, (size_t)h->dim * 4, (size_t)nb,
+                                 hipMemcpyDefault, st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(in.items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    }
+    return MORNA_OK;
+}
+
+// The queries' fp16 image, for the contraction (q16, qrow) and for the bound of every pair (qn16, qe16, qscale, indexed by
+// the item id or by the query number).  By item it is the image of the stored rows.  By vector it is made from the staged
+// rows on stream st (convert), unless the early contraction has made it.
+struct HalfImage {
+    const _Float16 *q16;
+    const int32_t *qrow;
+    const float *qn16, *qe16, *qscale;
+};
+
+static int half_image(morna_index *h, const QueryInputs &in, bool by_vector, int64_t nb, bool convert, hipStream_t st, HalfImage &im)
+{
+    if (by_vector) {
+        if (convert) MORNA_TRY(split_mm_convert_rows(h, in.Q, nb, in.Q16, in.qn16, in.qe16, in.qscale, st));
+        im = {in.Q16, nullptr, in.qn16, in.qe16, in.qscale};
+    } else {
+        const float *xn = h->half.xn.p;
+        im = {h->half.x16.p, in.items, xn, xn + 2 * h->n_items, xn + h->n_items};
+    }
+    return MORNA_OK;
+}
+
+// The whole-batch contraction: 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup
+// per CU), the 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0, read once per process, or !allow_big: for all
+// rows).  st_big / st_rem: the streams of the two launches; *big_rows_out: the rows the large form took.
+static int launch_contraction(morna_index *h, int64_t nb, const HalfImage &im, float *scores, hipStream_t st_big, hipStream_t st_rem,
+                              bool allow_big, int64_t *big_rows_out)
+{
+    static const bool big_on = env_on("MORNA_QUERY_BIG");
+    const _Float16 *X16 = h->half.x16.p;
+    const int64_t N = h->n_items;
+    int64_t big_tiles = 0, big_rows = 0;
+    if (allow_big && big_on && nb >= 512) {
+        const int64_t n_ct_big = (nb + 255) / 256;
+        int64_t a = h->n_cus, b = n_ct_big;   // tiles per round of the chip: n_cus / gcd(n_cus, n_ct_big)
+        while (b) { const int64_t t = a % b; a = b; b = t; }
+        const int64_t per_round = h->n_cus / a;
+        big_tiles = (N / 256) / per_round * per_round;
+    }
+    if (big_tiles > 0) {
+        const unsigned n_ct_big = (unsigned)((nb + 255) / 256);
+        MORNA_TRY(launch_lds(query_scores_big_kernel<64, 2>, dim3(8u * (unsigned)((big_tiles + 7) / 8) * n_ct_big), dim3(1024),
+                             128 * 256 * 4, LDS_ALWAYS, st_big, X16, N, h->dpad, im.q16, im.qrow, (int32_t)nb, scores, (int32_t)big_tiles));
+        big_rows = big_tiles * 256;
+    }
+    if (big_rows < N) {
+        const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N - big_rows + 127) / 128);
+        // (the rows behind the whole rounds of the 256 x 256 form: on the side stream, in front of the traversal,
+        // when the large form runs -- behind it on the main stream they were 0.05 ms of the batch's critical path)
+        MORNA_TRY(launch_lds(query_scores_kernel<128, 64, 2>, dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS, LDS_ALWAYS,
+                             big_tiles > 0 ? st_rem : st_big, X16, N, h->dpad, im.q16, im.qrow, (int32_t)nb, scores, big_rows));
+    }
+    HIP_TRY(hipGetLastError());
+    *big_rows_out = big_rows;
+    return MORNA_OK;
+}
+
+// ---- traversal launches --------------------------------------------------------------------------------------------
+
+// Root margins by query groups (query_roots_batch_kernel: a hyperplane fetched once per QR_Q queries) exist while the rows
+// have a length its register forms are built for, its query images fit LDS and the roots do split.
+static bool roots_by_groups_ok(const morna_index *h)
+{
+    return row_nv(h->dpad, 12) != 0 && h->n_items > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024;
+}
+
+// ... of nb queries into P.pq; the caller has asked roots_by_groups_ok
+static int launch_roots_by_groups(const QueryParams &P, int64_t nb, hipStream_t st)
+{
+    const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((P.n_trees + QR_TREES - 1) / QR_TREES));
+    const size_t ql = (size_t)QR_Q * P.dpad * 4;
+    return with_row_nv<12>(P.dpad, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if constexpr (NV != 0)   // (the kernel has no form without registers; roots_by_groups_ok keeps such rows away)
+            MORNA_TRY(launch_lds(query_roots_batch_kernel<NV>, grid, dim3(QR_THREADS), ql, LDS_DEFAULT, st, P, (int32_t)nb));
+        return MORNA_OK;
+    });
+}
+
+// the best-first descent, one wave per query (query_descend_kernel; R: its restricted form), behind the root margins on st
+static int launch_descents(const QueryPlan &pl, const QueryParams &P, const RestrictArgs *R, int64_t nb, hipStream_t st)
+{
+    return with_row_nv<32>(P.dpad, [&](auto nv) {
+        return with_flag(pl.bm_lds, [&](auto bm) {
+            constexpr int NV = decltype(nv)::value;
+            constexpr bool BM = decltype(bm)::value;
+            if (R) return launch_lds(query_descend_restricted_kernel<BM, NV>, dim3((unsigned)nb), dim3(WAVE), pl.lds_bm, LDS_1WAVE, st, P, *R);
+            return launch_lds(query_descend_kernel<BM, NV>, dim3((unsigned)nb), dim3(WAVE), pl.lds_bm, LDS_1WAVE, st, P);
+        });
+    });
+}
+
+// ... of the sweep: one per virtual query
+static int launch_sweep_descents(const QueryPlan &pl, const QueryParams &P, const SweepArgs &S, int64_t nv_queries, hipStream_t st)
+{
+    return with_row_nv<12>(P.dpad, [&](auto nv) {
+        return with_flag(pl.bm_lds, [&](auto bm) {
+            return launch_lds(query_descend_sweep_kernel<decltype(bm)::value, decltype(nv)::value>, dim3((unsigned)nv_queries), dim3(WAVE),
+                              pl.lds_bm, LDS_1WAVE, st, P, S);
+        });
+    });
+}
+
+// the split traversal: root margins by query groups, then the one-wave descents
+static int launch_split_traversal(const QueryPlan &pl, const QueryParams &P, const RestrictArgs *R, int64_t nb, hipStream_t st)
+{
+    MORNA_TRY(launch_roots_by_groups(P, nb, st));
+    return launch_descents(pl, P, R, nb, st);
+}
+
+// the fused traversal, one workgroup per query: the query image in LDS, and the sample bitmap beside it when it fits
+static int launch_fused_traversal(const QueryPlan &pl, const QueryParams &P, const RestrictArgs *R, int64_t nb, hipStream_t st)
+{
+    const size_t lds = pl.lds_q + pl.lds_bm;   // (can pass the default dynamic-LDS limit; the query image alone: up to 128 KiB past dpad 12288)
+    return with_flag(pl.bm_lds, [&](auto bm) {
+        constexpr bool BM = decltype(bm)::value;
+        if (R) return launch_lds(query_traverse_restricted_kernel<BM>, dim3((unsigned)nb), dim3(Q_THREADS), lds, LDS_DEFAULT, st, P, *R);
+        return launch_lds(query_traverse_kernel<BM>, dim3((unsigned)nb), dim3(Q_THREADS), lds, LDS_DEFAULT, st, P);
+    });
+}
+
+// the refine step: no filter; the filter dots taken row by row (gather); the scores of the whole batch (dense)
+static int launch_refine(const QueryPlan &pl, const QueryParams &P, bool dense, int64_t nb, hipStream_t st)
+{
+    auto go = [&](auto mode) {
+        return launch_lds(query_refine_kernel<decltype(mode)::value>, dim3((unsigned)nb), dim3(Q_THREADS), pl.lds_q, LDS_DEFAULT, st, P);
+    };
+    if (!pl.use_filter) return go(std::integral_constant<int, 0>{});
+    if (!dense) return go(std::integral_constant<int, 1>{});
+    return go(std::integral_constant<int, 2>{});
+}
+
+// ---- query_batch ---------------------------------------------------------------------------------------------------
+
+static QueryPlan plan_query(const morna_index *h, int64_t nq, int32_t k, int32_t search_k, int32_t T_used)
+{
+    QueryPlan pl = {};
+    const int64_t N = h->n_items;
+    pl.T_used = T_used;
+    pl.search_k = search_k == -1 ? (int32_t)std::min<int64_t>((int64_t)k * T_used, INT32_MAX) : search_k;
+    pl.cap = (int32_t)std::max<int64_t>(std::min<int64_t>(N, (int64_t)std::max(pl.search_k, 0) + h->K), 1);
+    pl.bm_words = (int32_t)((N + 31) / 32);
+    pl.lds_q = (size_t)h->dpad * sizeof(float);
+    // the sample bitmap goes to LDS when it is at most 64 KiB and fits beside the query image (always, up to dpad 8192;
+    // past it the 160 KiB of LDS decide, and the global bitmap takes over)
+    pl.bm_lds = (size_t)pl.bm_words * 4 <= 64 * 1024 && pl.lds_q + (size_t)pl.bm_words * 4 <= Q_LDS_MAX;
+    pl.lds_bm = pl.bm_lds ? (size_t)pl.bm_words * 4 : 0;
+    const bool filter_pays = query_filter_on() && pl.cap > 4 * (int64_t)k;
+    const bool batch_dense = filter_pays && query_dense_on() && dense_pays(h, pl.cap, nq);
+    // (MORNA_QUERY_SPREAD=0, read per call: one workgroup per query)
+    pl.spread = env_on("MORNA_QUERY_SPREAD") && nq < 64 && !batch_dense;
+    pl.use_filter = !pl.spread && filter_pays;
+    pl.may_dense = pl.use_filter && batch_dense;
+    return pl;
+}
+
+// workspace bytes of one query, for the 1 GiB rule; n_nodes 0: without the per-node term
+static size_t query_bytes(const morna_index *h, const QueryPlan &pl, int32_t k, bool by_vector, int64_t n_nodes)
+{
+    return (size_t)n_nodes * 8 + (size_t)pl.cap * 16 + (by_vector ? (size_t)h->dpad * 6 + 16 : 0) +
+           (pl.bm_lds ? 0 : (size_t)pl.bm_words * 4) + (size_t)k * 8 + 16 + (pl.may_dense ? (size_t)h->n_items * 4 : 0);
+}
+
+// ---- The first batch beside a pending build (a build that returned with its last narrow levels pending, forest.hip).  What
+// does not depend on the forest -- the item ids or query vectors, their fp16 image, both contraction launches -- goes onto
+// stream3, behind ev_tail (recorded in front of the deferred attempt: the wide levels and the fp16 rows are done, the tail's
+// own kernels are not waited for).  Not stream2: a tail attempt in the matrix-core form puts its side work there and would
+// queue behind the contraction.  Everything these kernels read or write lies in h->q_early, sized and placed now: h->ws is
+// sized from n_nodes, which only the finished tail knows, and may move when it grows.  Nothing of the build uses q_early.
+// Then the tail is finished; root margins and descents follow it on h->stream; the refine step joins both.
+struct EarlyContraction {
+    bool live = false;      // the batch reads its queries and scores from `in`
+    QueryInputs in = {};    // in h->q_early
+    int64_t big_rows = 0;
+
+    // Decided here and nowhere else: the build is pending, the call is a plain one with its answers wanted on the host and no
+    // timer on it, and its plan is the dense one with all queries in one batch whatever n_nodes turns out to be.  (Only
+    // abandon() below takes it back, when the finished forest says otherwise.)
+    static bool wanted(const morna_index *h, bool by_vector, int64_t nq, int32_t k, int32_t search_k, const int32_t *ids_out,
+                       const int32_t *packed_dev, const morna_restriction *rst, int32_t n_trees_used)
+    {
+        const bool timed = h->timing && (h->timing_mask & ((1u << MORNA_T_QUERY) | (1u << MORNA_T_QUERY_FILTER)));
+        if (!(h->fb.pending && !rst && !packed_dev && n_trees_used == 0 && ids_out && !timed && h->half.valid && k > 0 && nq > 0 &&
+              h->dpad <= Q_MAX_DPAD))
+            return false;
+        const QueryPlan pl = plan_query(h, nq, k, search_k, h->n_trees);
+        return pl.may_dense && nq <= (int64_t)(((size_t)1 << 30) / query_bytes(h, pl, k, by_vector, 0));
+    }
+
+    int start(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq)
+    {
+        MORNA_TRY(carve_workspace(h->q_early, [&](Carver &c) { in.carve(c, h, nq, q_host != nullptr, true, true); }));
+        hipStream_t s3 = h->stream3;
+        HIP_TRY(hipStreamWaitEvent(s3, h->ev_tail, 0));
+        MORNA_TRY(stage_queries(h, in, q_host, q_stride, items_host, 0, nq, s3));
+        HalfImage im;
+        MORNA_TRY(half_image(h, in, q_host != nullptr, nq, true, s3, im));
+        HIP_TRY(hipEventRecord(h->ev_early_in, s3));   // the traversal reads the ids / vectors too
+        MORNA_TRY(launch_contraction(h, nq, im, in.scores, s3, s3, true, &big_rows));
+        HIP_TRY(hipEventRecord(h->ev_early_out, s3));
+        const int rc = finish_build(h, "query_batch, beside its contraction");
+        if (rc != MORNA_OK) {
+            (void)hipStreamSynchronize(s3);
+            return rc;
+        }
+        live = true;
+        return MORNA_OK;
+    }
+
+    // the finished forest has so many nodes that the queries go in several batches: the scores are not used (the same
+    // kernels make them again, batch by batch)
+    int abandon(morna_index *h)
+    {
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_out, 0));
+        live = false;
+        return MORNA_OK;
+    }
+};
+
+// A few query vectors from host memory (spread form): padded on the host into page-locked memory and sent as ONE copy (a
+// memset + a 2-D copy out of pageable memory are two stream operations of ~10 us each).  *staged: q_host was host memory.
+static int stage_queries_pinned(morna_index *h, float *Qd, const float *q_host, int64_t q_stride, int64_t nb, bool *staged)
+{
+    hipPointerAttribute_t at;
+    const bool on_host = hipPointerGetAttributes(&at, q_host) != hipSuccess || at.type == hipMemoryTypeHost ||
+                         at.type == hipMemoryTypeUnregistered;
+    (void)hipGetLastError();   // (an unregistered host pointer reports an error on some runtimes)
+    *staged = on_host;
+    if (!on_host) return MORNA_OK;
+    const size_t need = (size_t)nb * h->dpad * 4;
+    MORNA_TRY(h->host_q.reserve(need));
+    float *hq = (float *)h->host_q.p;
+    for (int64_t i = 0; i < nb; i++) {
+        memcpy(hq + i * h->dpad, q_host + i * q_stride, (size_t)h->dim * 4);
+        memset(hq + i * h->dpad + h->dim, 0, (size_t)(h->dpad - h->dim) * 4);
+    }
+    HIP_TRY(hipMemcpyAsync(Qd, hq, need, hipMemcpyHostToDevice, h->stream));
+    return MORNA_OK;
+}
+
+// q_host: query vectors in host OR device memory (unified addressing), q_stride floats apart (0 = dim)
 // rst (or null): the restriction of the call, q_group_host [nq] (or null) the queries' own groups (morna_hip.h, "restricted
 // search"); only the traversal kernels differ, every kernel behind them reads candidate lists.
 int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
@@ -1233,337 +1711,104 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 const morna_restriction *rst, const int32_t *q_group_host, int32_t n_trees_used)
 {
     if (q_stride <= 0) q_stride = h->dim;
-    // A build that returned with its last narrow levels pending (forest.hip): every case but the dense first batch below
-    // finishes it here, first thing.  That one needs nothing of the forest for its contraction and starts it beside the tail.
-    const bool timed = h->timing && (h->timing_mask & ((1u << MORNA_T_QUERY) | (1u << MORNA_T_QUERY_FILTER)));
-    bool early = h->fb.pending && !rst && !packed_dev && n_trees_used == 0 && ids_out && !timed && h->half.valid && k > 0 && nq > 0 &&
-                 h->dpad <= Q_MAX_DPAD;
-    if (!early) MORNA_TRY(finish_build(h, "query_batch"));
-    if (!h->built && !early) {
-        set_error("index has not been built: call build() before searching");
-        return MORNA_E_STATE;
+    const bool by_vector = q_host != nullptr;
+    // ---- check.  A pending build is finished first thing, unless the first batch's contraction is to start beside it.
+    const bool beside_build = EarlyContraction::wanted(h, by_vector, nq, k, search_k, ids_out, packed_dev, rst, n_trees_used);
+    if (!beside_build) {
+        MORNA_TRY(finish_build(h, "query_batch"));
+        MORNA_TRY(require_built(h));
     }
-    if (k <= 0 || nq < 0) {
-        set_error("get_nns: n must be positive");
-        return MORNA_E_INVALID;
-    }
-    if (h->dpad > Q_MAX_DPAD) {   // the query image and the traversal's LDS (an index built elsewhere, loaded here)
-        set_error("get_nns: dimension %d is above the supported %d", h->dim, Q_MAX_DPAD);
-        return MORNA_E_INVALID;
-    }
+    MORNA_TRY(check_search_call(h, "get_nns", k, nq));
     if (rst) MORNA_TRY(restriction_usable(h, rst));
-    if (n_trees_used != 0 && (n_trees_used < 1 || n_trees_used > h->n_trees)) {
-        set_error("get_nns: %d trees asked for, the forest has %d", n_trees_used, h->n_trees);
-        return MORNA_E_RANGE;
-    }
-    // the trees the search walks: all of them, or the first n_trees_used (morna_hip.h, "tree-prefix search")
-    const int32_t T_used = n_trees_used ? n_trees_used : h->n_trees;
+    if (n_trees_used != 0) MORNA_TRY(check_tree_count(h, "get_nns", n_trees_used));
     if (nq == 0) return MORNA_OK;
-    if (search_k == -1) search_k = (int32_t)std::min<int64_t>((int64_t)k * T_used, INT32_MAX);
-    if (items_host)
-        for (int64_t i = 0; i < nq; i++)
-            if (items_host[i] < 0 || items_host[i] >= h->n_items) {
-                set_error("item id %d out of range [0, %lld)", items_host[i], (long long)h->n_items);
-                return MORNA_E_RANGE;
-            }
+    if (items_host) MORNA_TRY(check_items(h, items_host, nq));
+
+    // ---- plan, and the early contraction (it finishes the build)
+    QueryPlan pl = plan_query(h, nq, k, search_k, n_trees_used ? n_trees_used : h->n_trees);
+    EarlyContraction early;
+    if (beside_build) MORNA_TRY(early.start(h, q_host, q_stride, items_host, nq));
+    pl.batch = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(((size_t)1 << 30) / query_bytes(h, pl, k, by_vector, h->n_nodes))));
+    if (early.live && pl.batch != nq) MORNA_TRY(early.abandon(h));
+
+    // ---- the workspace, one slice per query of a batch: bound once, every batch uses the same slices
     const int64_t N = h->n_items;
-    // |nns| < search_k before the last pop, which adds at most K ids
-    const int64_t cap64 = std::min<int64_t>(N, (int64_t)std::max(search_k, 0) + h->K);
-    const int32_t cap = (int32_t)std::max<int64_t>(cap64, 1);
-    const int32_t bm_words = (int32_t)((N + 31) / 32);
-    const size_t lds_q = (size_t)h->dpad * sizeof(float);
-    // the sample bitmap goes to LDS when it is at most 64 KiB and fits beside the query image (always, up to dpad 8192;
-    // past it the 160 KiB of LDS decide, and the global bitmap takes over)
-    const bool bm_lds = (size_t)bm_words * 4 <= 64 * 1024 && lds_q + (size_t)bm_words * 4 <= Q_LDS_MAX;
-    const size_t lds = lds_q + (bm_lds ? (size_t)bm_words * 4 : 0);
-
-    // candidate filter on the fp16 rows (MORNA_QUERY_FILTER=0: every candidate gets the fp32 dot); pays when a
-    // query has many more candidates than results.  MORNA_QUERY_DENSE=0 keeps the per-candidate gather form.
-    static const bool filter_on = env_on("MORNA_QUERY_FILTER");
-    static const bool dense_on = env_on("MORNA_QUERY_DENSE");
-    // fewer queries than would give every CU a workgroup: the spread form (MORNA_QUERY_SPREAD=0: one workgroup per query)
-    const bool spread_on = env_on("MORNA_QUERY_SPREAD");
-    const bool filter_pays = filter_on && cap > 4 * (int64_t)k;
-    // the whole-batch contraction reads every fp16 row once; the gather form reads min(cap, ~K) rows per query
-    // (C3, 48 / 63 queries: 207 us through the contraction, 231 / 282 us through the spread form; 32: the spread form's 174 us)
-    auto dense_pays = [&](int64_t nb) { return nb >= 40 && nb * std::min<int64_t>(cap, h->K) >= 2 * N; };
-    const bool spread = spread_on && nq < 64 && !(filter_pays && dense_on && dense_pays(nq));
-    const bool use_filter = !spread && filter_pays;
-    const bool may_dense = use_filter && dense_on && dense_pays(nq);
-
-    // the whole-batch contraction: 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup
-    // per CU), the 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0: for all rows).  st_big / st_rem: the streams
-    // of the two launches; returns the rows the large form took
-    auto launch_contraction = [&](int64_t nb, const _Float16 *q16, const int32_t *qrow, float *scores, hipStream_t st_big,
-                                  hipStream_t st_rem, int64_t *big_rows_out) -> int {
-        static const bool big_on = env_on("MORNA_QUERY_BIG");
-        const _Float16 *X16 = h->half.x16.p;
-        int64_t big_tiles = 0, big_rows = 0;
-        if (big_on && nb >= 512) {
-            const int64_t n_ct_big = (nb + 255) / 256;
-            int64_t a = h->n_cus, b = n_ct_big;   // tiles per round of the chip: n_cus / gcd(n_cus, n_ct_big)
-            while (b) { const int64_t t = a % b; a = b; b = t; }
-            const int64_t per_round = h->n_cus / a;
-            big_tiles = (N / 256) / per_round * per_round;
-        }
-        if (big_tiles > 0) {
-            const unsigned n_ct_big = (unsigned)((nb + 255) / 256);
-            HIP_TRY(hipFuncSetAttribute((const void *)query_scores_big_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 256 * 4));
-            hipLaunchKernelGGL((query_scores_big_kernel<64, 2>), dim3(8u * (unsigned)((big_tiles + 7) / 8) * n_ct_big), dim3(1024), 128 * 256 * 4,
-                               st_big, X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, (int32_t)big_tiles);
-            big_rows = big_tiles * 256;
-        }
-        if (big_rows < N) {
-            const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N - big_rows + 127) / 128);
-            HIP_TRY(hipFuncSetAttribute((const void *)query_scores_kernel<128, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MM16_LDS));
-            // (the rows behind the whole rounds of the 256 x 256 form: on the side stream, in front of the traversal,
-            // when the large form runs -- behind it on the main stream they were 0.05 ms of the batch's critical path)
-            hipLaunchKernelGGL((query_scores_kernel<128, 64, 2>), dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS,
-                               big_tiles > 0 ? st_rem : st_big, X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, big_rows);
-        }
-        HIP_TRY(hipGetLastError());
-        *big_rows_out = big_rows;
-        return MORNA_OK;
-    };
-
-    // ---- the first batch beside a pending build.  What does not depend on the forest -- the item ids or query vectors, their
-    // fp16 image, both contraction launches -- goes onto stream3, behind ev_tail (recorded in front of the deferred
-    // attempt: the wide levels and the fp16 rows are done, the tail's own kernels are not waited for).  Not stream2: a tail
-    // attempt in the matrix-core form puts its side work there and would queue behind the contraction.  Everything these
-    // kernels read or write lies in h->q_early, sized and placed now: h->ws is sized from n_nodes, which only the finished
-    // tail knows, and may move when it grows.  Nothing of the build uses q_early.  Then the tail is finished; root margins
-    // and descents follow it on h->stream; the refine step joins both.
-    uint8_t *e_items = nullptr, *e_q = nullptr, *e_q16 = nullptr, *e_qf = nullptr, *e_scores = nullptr;
-    int64_t e_big_rows = 0;
-    if (early) {
-        // one batch of all queries, whatever n_nodes turns out to be?  Without the per-node term; checked again below
-        const size_t per_q0 = (size_t)cap * 16 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) + (bm_lds ? 0 : (size_t)bm_words * 4) +
-                              (size_t)k * 8 + 16 + (size_t)N * 4;
-        early = may_dense && nq <= (int64_t)(((size_t)1 << 30) / per_q0);
-        if (!early) {   // not the dense case after all
-            MORNA_TRY(finish_build(h, "query_batch"));
-            if (!h->built) {
-                set_error("index has not been built: call build() before searching");
-                return MORNA_E_STATE;
-            }
-        }
-    }
-    if (early) {
-        const size_t z_items = align_up((size_t)nq * 4, 256), z_q = q_host ? align_up((size_t)nq * h->dpad * 4, 256) : 0,
-                     z_q16 = q_host ? align_up((size_t)nq * h->dpad * 2, 256) : 0, z_qf = align_up((size_t)nq * 4, 256),
-                     z_scores = align_up((size_t)nq * N * 4, 256);
-        MORNA_TRY(h->q_early.alloc(z_items + z_q + z_q16 + 3 * z_qf + z_scores));
-        uint8_t *p = h->q_early.p;
-        e_items = p; p += z_items;
-        e_q = p; p += z_q;
-        e_q16 = p; p += z_q16;
-        e_qf = p; p += 3 * z_qf;
-        e_scores = p;
-        hipStream_t s3 = h->stream3;
-        HIP_TRY(hipStreamWaitEvent(s3, h->ev_tail, 0));
-        const _Float16 *q16 = h->half.x16.p;
-        const int32_t *qrow = (const int32_t *)e_items;
-        if (q_host) {
-            HIP_TRY(hipMemsetAsync(e_q, 0, (size_t)nq * h->dpad * 4, s3));
-            HIP_TRY(hipMemcpy2DAsync(e_q, (size_t)h->dpad * 4, q_host, (size_t)q_stride * 4, (size_t)h->dim * 4, (size_t)nq,
-                                     hipMemcpyDefault, s3));
-            MORNA_TRY(split_mm_convert_rows(h, (const float *)e_q, nq, (_Float16 *)e_q16, (float *)e_qf, (float *)(e_qf + z_qf),
-                                            (float *)(e_qf + 2 * z_qf), s3));
-            q16 = (const _Float16 *)e_q16;
-            qrow = nullptr;
-        } else {
-            HIP_TRY(hipMemcpyAsync(e_items, items_host, (size_t)nq * 4, hipMemcpyHostToDevice, s3));
-        }
-        HIP_TRY(hipEventRecord(h->ev_early_in, s3));   // the traversal reads the ids / vectors too
-        MORNA_TRY(launch_contraction(nq, q16, qrow, (float *)e_scores, s3, s3, &e_big_rows));
-        HIP_TRY(hipEventRecord(h->ev_early_out, s3));
-        const int rc = finish_build(h, "query_batch, beside its contraction");
-        if (rc != MORNA_OK) {
-            (void)hipStreamSynchronize(s3);
-            return rc;
-        }
-    }
-
-    const size_t per_q = (size_t)h->n_nodes * 8 + (size_t)cap * 16 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) +
-                         (bm_lds ? 0 : (size_t)bm_words * 4) + (size_t)k * 8 + 16 + (may_dense ? (size_t)N * 4 : 0);
-    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(((size_t)1 << 30) / per_q)));
-    if (early && batch != nq) {   // the forest has so many nodes that the queries go in several batches: the early scores are
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_out, 0));   // not used (the same kernels make them again, batch by batch)
-        early = false;
-    }
-    const size_t s_pq = align_up((size_t)batch * h->n_nodes * 8, 256), s_keys = align_up((size_t)batch * cap * 8, 256),
-                 s_q = q_host ? align_up((size_t)batch * h->dpad * 4, 256) : 0,
-                 s_q16 = q_host && may_dense ? align_up((size_t)batch * h->dpad * 2, 256) : 0,
-                 s_qf = align_up((size_t)batch * 4, 256),
-                 s_cand = align_up((size_t)batch * cap * 4, 256),
-                 s_bm = bm_lds ? 0 : align_up((size_t)batch * bm_words * 4, 256),
-                 s_ids = align_up((size_t)batch * k * 4, 256),
-                 s_scores = may_dense && !early ? align_up((size_t)batch * N * 4, 256) : 0;
-    MORNA_TRY(h->ws.alloc(s_pq + s_keys + s_q + s_q16 + 9 * s_qf + 2 * s_cand + s_bm + 2 * s_ids + s_scores + (rst ? s_qf : 0)));
+    const bool q_groups = rst && rst->has_group && q_group_host;
     MORNA_TRY(h->d_stat.alloc(4));
-    if (use_filter) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
+    QueryParams W = base_params(h, pl, k);
+    QueryInputs ws_in;
+    int32_t *d_qg = nullptr;
+    size_t out0 = 0, s_ids = 0, out_bytes = 0;
+    MORNA_TRY(carve_workspace(h->ws, [&](Carver &c) {
+        const size_t b = (size_t)pl.batch;
+        W.pq = c.take<uint64_t>(b * h->n_nodes);
+        W.keys = c.take<uint64_t>(b * pl.cap);
+        W.qpp = c.take<float>(b);
+        W.ncand = c.take<int32_t>(b);
+        W.cand_off = c.take<int64_t>(b);
+        W.cand = c.take<int32_t>(b * pl.cap);
+        W.low = c.take<float>(b * pl.cap);
+        W.bm_global = c.take<uint32_t>(pl.bm_lds ? 0 : b * pl.bm_words);
+        ws_in.carve(c, h, pl.batch, by_vector, pl.may_dense, pl.may_dense && !early.live);
+        d_qg = c.take<int32_t>(q_groups ? b : 0);
+        out0 = c.used;   // ids, distances, counts: one block, one copy to the host
+        W.ids_out = c.take<int32_t>(b * k);
+        s_ids = c.used - out0;
+        W.dist_out = c.take<float>(b * k);
+        W.count_out = c.take<int32_t>(b);
+        out_bytes = c.used - out0;
+    }));
+    const uint8_t *const out_block = (const uint8_t *)W.ids_out;
+    W.zero_copy = pl.spread && !rst ? 1 : 0;   // (a restricted call never takes a leaf's slice of perm as its candidates)
+    if (pl.use_filter) {
+        MORNA_TRY(split_mm_prepare_rows(h, h->stream));
+        set_filter_rows(h, W);
+    }
+    const QueryInputs &in = early.live ? early.in : ws_in;   // (early: one batch, q0 == 0 and nb == nq)
+    const RestrictArgs R = restrict_args(rst, q_groups ? d_qg : nullptr);
+    const RestrictArgs *const Rp = rst ? &R : nullptr;
+    // spread form, answers wanted on the host: the last kernel writes them straight into page-locked memory of the handle
+    // (a copy out of HBM is another ~8 us operation on the stream for 160 bytes per query), and the batch ends with a host wait
+    const bool direct = pl.spread && ids_out && !packed_dev;
+    if (direct) {
+        MORNA_TRY(h->host_small.reserve(out_bytes));
+        uint8_t *dp = (uint8_t *)h->host_small.dev();
+        if (!dp) {
+            set_error("query: the answer staging is not visible to the device");
+            return MORNA_E_HIP;
+        }
+        W.ids_out = (int32_t *)dp;
+        W.dist_out = (float *)(dp + s_ids);
+        W.count_out = (int32_t *)(dp + 2 * s_ids);
+    }
 
-    for (int64_t q0 = 0; q0 < nq; q0 += batch) {
-        const int64_t nb = std::min(batch, nq - q0);
-        const bool dense = may_dense && dense_pays(nb);
-        uint8_t *p = h->ws.p;
-        QueryParams P;
-        P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = N; P.dpad = h->dpad; P.n_trees = T_used; P.K = h->K;
-        P.node_rec = h->node_rec.p; P.node_tree = h->node_tree.p; P.node_hp = h->node_hp.p; P.hp = h->hp.p;
-        P.perm = h->perm.p; P.n_nodes = h->n_nodes;
-        P.k = k; P.search_k = search_k; P.cap = cap; P.bm_words = bm_words;
-        P.pq = (uint64_t *)p; p += s_pq;
-        P.keys = (uint64_t *)p; p += s_keys;
-        float *Qd = (float *)p; p += s_q;
-        _Float16 *Q16 = (_Float16 *)p; p += s_q16;
-        P.qpp = (float *)p; p += s_qf;
-        float *q_n16 = (float *)p; p += s_qf;
-        float *q_e16 = (float *)p; p += s_qf;
-        float *q_scale = (float *)p; p += s_qf;
-        P.ncand = (int32_t *)p; p += s_qf;
-        int32_t *d_items = (int32_t *)p; p += s_qf;   // (part of the workspace: a hipMalloc / hipFree per call costs tens of microseconds)
-        P.cand_off = (int64_t *)p; p += 2 * s_qf;
-        P.zero_copy = spread && !rst ? 1 : 0;   // (a restricted call never takes a leaf's slice of perm as its candidates)
-        P.cand = (int32_t *)p; p += s_cand;
-        P.low = (float *)p; p += s_cand;
-        P.bm_global = (uint32_t *)p; p += s_bm;
-        uint8_t *const out_block = p;   // ids, distances, counts: one block, one copy to the host
-        P.ids_out = (int32_t *)p; p += s_ids;
-        P.dist_out = (float *)p; p += s_ids;
-        P.count_out = (int32_t *)p; p += s_qf;
-        float *scores = (float *)p; p += s_scores;
-        if (early) {   // (one batch: q0 == 0, nb == nq) what the contraction on stream3 reads and writes
-            const size_t z_qf = align_up((size_t)nq * 4, 256);
-            Qd = (float *)e_q; Q16 = (_Float16 *)e_q16;
-            q_n16 = (float *)e_qf; q_e16 = (float *)(e_qf + z_qf); q_scale = (float *)(e_qf + 2 * z_qf);
-            d_items = (int32_t *)e_items;
-            scores = (float *)e_scores;
-        }
-        RestrictArgs R = {nullptr, nullptr, nullptr};
-        if (rst) {
-            R.deny = rst->deny.p;
-            R.group = rst->has_group ? rst->group.p : nullptr;
-            if (R.group && q_group_host) {
-                int32_t *d_qg = (int32_t *)p; p += s_qf;
-                HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-                R.q_group = d_qg;
-            }
-        }
-        P.stat = h->d_stat.p;
-        P.X16 = nullptr; P.xscale = nullptr; P.xn16 = P.xe16 = nullptr; P.delta = 0.f;
-        P.scores = nullptr; P.qscale = P.qn16 = P.qe16 = nullptr; P.eacc = P.eacc_big = 0.f; P.big_rows = 0;
-        if (use_filter) {
-            const float *xn = h->half.xn.p;
-            P.X16 = h->half.x16.p;
-            P.xn16 = xn; P.xscale = xn + N; P.xe16 = xn + 2 * N;
-            // gather form: |cos from the fp16 row - cos from the fp32 row| <= 2^-11 (one rounding to 11 bits, the query
-            // is not rounded) + the fp32 accumulations of both dots (any order: < dpad * 2^-24 each); the distance is
-            // 2 - 2 cos; 1e-5 covers the evaluation of ang_dist itself
-            P.delta = 2.f * (1.02f * 0.00048828125f + 2.f * (float)h->dpad * 5.9604645e-8f) + 1e-5f;
-            P.eacc = mm16_eacc(h->dpad);
-        }
-        P.Q = nullptr; P.items = nullptr;
-        P.n_inline = 0;
-        if (spread && !q_host && nb <= 16) {
+    for (int64_t q0 = 0; q0 < nq; q0 += pl.batch) {
+        const int64_t nb = std::min(pl.batch, nq - q0);
+        const bool dense = pl.may_dense && dense_pays(h, pl.cap, nb);
+        QueryParams P = W;
+        // ---- stage the queries
+        if (q_groups) HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+        if (pl.spread && !by_vector && nb <= 16) {   // the item numbers travel with the launch
             P.n_inline = (int32_t)nb;
             for (int64_t i = 0; i < nb; i++) P.inline_items[i] = items_host[q0 + i];
-        } else
-        if (early) {   // in place since stream3's copies; whatever reads them on h->stream comes behind those
-            HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_in, 0));
-            if (q_host) P.Q = Qd;
-            else P.items = d_items;
-        } else
-        if (q_host) {
-            bool staged = false;
-            if (spread && ids_out && !packed_dev) {   // (the batch ends with a host wait: the staging buffer is free again by then)
-                // a few query vectors from host memory: padded on the host into page-locked memory and sent as ONE copy (a
-                // memset + a 2-D copy out of pageable memory are two stream operations of ~10 us each)
-                hipPointerAttribute_t at;
-                const bool on_host = hipPointerGetAttributes(&at, q_host) != hipSuccess || at.type == hipMemoryTypeHost ||
-                                     at.type == hipMemoryTypeUnregistered;
-                (void)hipGetLastError();   // (an unregistered host pointer reports an error on some runtimes)
-                if (on_host) {
-                    const size_t need = (size_t)nb * h->dpad * 4;
-                    MORNA_TRY(h->host_q.reserve(need));
-                    float *hq = (float *)h->host_q.p;
-                    for (int64_t i = 0; i < nb; i++) {
-                        memcpy(hq + i * h->dpad, q_host + (q0 + i) * q_stride, (size_t)h->dim * 4);
-                        memset(hq + i * h->dpad + h->dim, 0, (size_t)(h->dpad - h->dim) * 4);
-                    }
-                    HIP_TRY(hipMemcpyAsync(Qd, hq, need, hipMemcpyHostToDevice, h->stream));
-                    staged = true;
-                }
-            }
-            if (!staged) {
-                HIP_TRY(hipMemsetAsync(Qd, 0, (size_t)nb * h->dpad * 4, h->stream));
-                HIP_TRY(hipMemcpy2DAsync(Qd, (size_t)h->dpad * 4, q_host + q0 * q_stride, (size_t)q_stride * 4,
-                                         (size_t)h->dim * 4, (size_t)nb, hipMemcpyDefault, h->stream));
-            }
-            P.Q = Qd;
         } else {
-            HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-            P.items = d_items;
-        }
-        // the best-first descent, one wave per query (query_descend_kernel), on stream st
-        auto launch_descend = [&](hipStream_t st) -> int {
-            const size_t bl = bm_lds ? (size_t)bm_words * 4 : 0;
-#define DESCEND(NVV)                                                                                                              \
-    do {                                                                                                                          \
-        if (rst) {                                                                                                                \
-            if (bm_lds) {                                                                                                         \
-                if (bl > 32 * 1024)                                                                                               \
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_descend_restricted_kernel<true, NVV>,                         \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bl));                            \
-                hipLaunchKernelGGL((query_descend_restricted_kernel<true, NVV>), dim3((unsigned)nb), dim3(WAVE), bl, st, P, R);   \
-            } else {                                                                                                              \
-                hipLaunchKernelGGL((query_descend_restricted_kernel<false, NVV>), dim3((unsigned)nb), dim3(WAVE), 0, st, P, R);   \
-            }                                                                                                                     \
-        } else if (bm_lds) {                                                                                                      \
-            if (bl > 32 * 1024)                                                                                                   \
-                HIP_TRY(hipFuncSetAttribute((const void *)query_descend_kernel<true, NVV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                            (int)bl));                                                                            \
-            hipLaunchKernelGGL((query_descend_kernel<true, NVV>), dim3((unsigned)nb), dim3(WAVE), bl, st, P);                     \
-        } else {                                                                                                                  \
-            hipLaunchKernelGGL((query_descend_kernel<false, NVV>), dim3((unsigned)nb), dim3(WAVE), 0, st, P);                     \
-        }                                                                                                                         \
-    } while (0)
-            switch (h->dpad / 256) {   // float4 per lane of a row
-            case 1: DESCEND(1); break;
-            case 2: DESCEND(2); break;
-            case 3: DESCEND(3); break;
-            case 4: DESCEND(4); break;
-            case 6: DESCEND(6); break;
-            case 8: DESCEND(8); break;
-            case 12: DESCEND(12); break;
-            case 16: DESCEND(16); break;
-            case 24: DESCEND(24); break;
-            case 32: DESCEND(32); break;
-            default: DESCEND(0); break;
+            if (early.live) {   // in place since stream3's copies; whatever reads them on h->stream comes behind those
+                HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_in, 0));
+            } else {
+                bool staged = false;
+                if (by_vector && direct) MORNA_TRY(stage_queries_pinned(h, in.Q, q_host + q0 * q_stride, q_stride, nb, &staged));
+                if (!staged) MORNA_TRY(stage_queries(h, in, q_host, q_stride, items_host, q0, nb, h->stream));
             }
-#undef DESCEND
-            return MORNA_OK;
-        };
-        // spread form, answers wanted on the host: the last kernel writes them straight into page-locked memory of the handle
-        // (a copy out of HBM is another ~8 us operation on the stream for 160 bytes per query)
-        const bool direct = spread && ids_out && !packed_dev;
-        if (direct) {
-            const size_t need = 2 * s_ids + s_qf;
-            MORNA_TRY(h->host_small.reserve(need));
-            uint8_t *dp = (uint8_t *)h->host_small.dev();
-            if (!dp) {
-                set_error("query: the answer staging is not visible to the device");
-                return MORNA_E_HIP;
-            }
-            P.ids_out = (int32_t *)dp;
-            P.dist_out = (float *)(dp + s_ids);
-            P.count_out = (int32_t *)(dp + 2 * s_ids);
+            if (by_vector) P.Q = in.Q;
+            else P.items = in.items;
         }
-        if (spread) {
+        // ---- traverse and refine
+        if (pl.spread) {
             // a batch too small to fill the chip with one workgroup per query: each query's work is dealt out (kernels above)
             ScopedTimer tm(h, MORNA_T_QUERY, 0);
-            hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((T_used + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
+            hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((pl.T_used + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
                                h->stream, P);
-            MORNA_TRY(launch_descend(h->stream));
+            MORNA_TRY(launch_descents(pl, P, Rp, nb, h->stream));
 #ifdef MORNA_DESCEND_PROBE
             {
                 float probe[40];
@@ -1574,7 +1819,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 fprintf(stderr, "\n");
             }
 #endif
-            hipLaunchKernelGGL(query_cand_dots_kernel, dim3((unsigned)((cap + Q_WAVES * QS_CPW - 1) / (Q_WAVES * QS_CPW)), (unsigned)nb),
+            hipLaunchKernelGGL(query_cand_dots_kernel, dim3((unsigned)((pl.cap + Q_WAVES * QS_CPW - 1) / (Q_WAVES * QS_CPW)), (unsigned)nb),
                                dim3(Q_THREADS), 0, h->stream, P);
             hipLaunchKernelGGL(query_topk_kernel, dim3((unsigned)nb), dim3(Q_THREADS), 0, h->stream, P);
         } else {
@@ -1582,99 +1827,39 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
             // query; the kernel counts them into d_stat[0], resolve_timers() prices them
             ScopedTimer tm(h, MORNA_T_QUERY, 0);
             if (dense) {
-                const _Float16 *q16 = P.X16;
-                const int32_t *qrow = P.items;
-                if (q_host) {
-                    if (!early) split_mm_convert_rows(h, Qd, nb, Q16, q_n16, q_e16, q_scale, h->stream);
-                    q16 = Q16; qrow = nullptr;
-                    P.qn16 = q_n16; P.qe16 = q_e16; P.qscale = q_scale;
-                } else {
-                    P.qn16 = P.xn16; P.qe16 = P.xe16; P.qscale = P.xscale;
-                }
-                if (early) {   // enqueued on stream3 before the tail was finished (above)
-                    P.big_rows = e_big_rows;
+                HalfImage im;
+                MORNA_TRY(half_image(h, in, by_vector, nb, !early.live, h->stream, im));
+                P.qn16 = im.qn16; P.qe16 = im.qe16; P.qscale = im.qscale;
+                if (early.live) {   // enqueued on stream3 before the tail was finished
+                    P.big_rows = early.big_rows;
                 } else {
                     HIP_TRY(hipEventRecord(h->ev_fork, h->stream));   // the query vectors (and their fp16 image) / item ids are in place
                     HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
                     ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
-                    MORNA_TRY(launch_contraction(nb, q16, qrow, scores, h->stream, h->stream2, &P.big_rows));
+                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream2, true, &P.big_rows));
                 }
                 if (P.big_rows > 0) P.eacc_big = (4.f * (float)h->dpad + 2.f) * 5.9604645e-8f + 4.1e-6f;   // EACC for ONE chain of dpad products
-                P.scores = scores;
+                P.scores = in.scores;
             }
             // beside the contraction (matrix cores, LDS) the traversal is a latency chain on one wave per query: it
             // runs on the side stream and the refine step waits for both
             // (forked above, before the contraction was enqueued; a batch that started beside a pending build: the
             // contraction is on stream3 and the traversal follows the tail on the main stream)
-            hipStream_t ts = dense && !early ? h->stream2 : h->stream;
-            // Root margins by query groups (a hyperplane fetched once per QR_Q queries), then the one-wave descent of the
-            // spread form -- while the rows have a length the register forms are built for and the roots do split;
-            // otherwise (and with MORNA_QUERY_SPLIT_TRAVERSE=0) the fused kernel, one workgroup per query.
-            const int nvq = h->dpad / 256;
-            const bool nv_ok = h->dpad % 256 == 0 && (nvq == 1 || nvq == 2 || nvq == 3 || nvq == 4 || nvq == 6 || nvq == 8 || nvq == 12);
-            const bool split_traverse = nv_ok && N > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024 &&
-                                        env_on("MORNA_QUERY_SPLIT_TRAVERSE");
-            if (split_traverse) {
-                const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((T_used + QR_TREES - 1) / QR_TREES));
-                const size_t ql = (size_t)QR_Q * h->dpad * 4;
-#define ROOTSB(NVV)                                                                                                      \
-    do {                                                                                                                 \
-        if (ql > 48 * 1024)                                                                                              \
-            HIP_TRY(hipFuncSetAttribute((const void *)query_roots_batch_kernel<NVV>,                                      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql));                           \
-        hipLaunchKernelGGL((query_roots_batch_kernel<NVV>), grid, dim3(QR_THREADS), ql, ts, P, (int32_t)nb);             \
-    } while (0)
-                switch (nvq) {
-                case 1: ROOTSB(1); break;
-                case 2: ROOTSB(2); break;
-                case 3: ROOTSB(3); break;
-                case 4: ROOTSB(4); break;
-                case 6: ROOTSB(6); break;
-                case 8: ROOTSB(8); break;
-                default: ROOTSB(12); break;
-                }
-#undef ROOTSB
-                MORNA_TRY(launch_descend(ts));
-            } else if (rst && bm_lds) {
-                if (lds > 48 * 1024)
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_restricted_kernel<true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(query_traverse_restricted_kernel<true>, dim3((unsigned)nb), dim3(Q_THREADS), lds, ts, P, R);
-            } else if (rst) {
-                if (lds_q > 48 * 1024)
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_restricted_kernel<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-                hipLaunchKernelGGL(query_traverse_restricted_kernel<false>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, ts, P, R);
-            } else if (bm_lds) {
-                if (lds > 48 * 1024)   // query image + sample bitmap can pass the default dynamic-LDS limit
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_kernel<true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(query_traverse_kernel<true>, dim3((unsigned)nb), dim3(Q_THREADS), lds, ts, P);
-            } else {
-                if (lds_q > 48 * 1024)   // the query image alone: up to 128 KiB past dpad 12288
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_traverse_kernel<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-                hipLaunchKernelGGL(query_traverse_kernel<false>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, ts, P);
-            }
-            if (early) {
+            const bool forked = dense && !early.live;
+            hipStream_t ts = forked ? h->stream2 : h->stream;
+            // the split traversal where it exists; otherwise (and with MORNA_QUERY_SPLIT_TRAVERSE=0, read per call) the fused kernel
+            if (roots_by_groups_ok(h) && env_on("MORNA_QUERY_SPLIT_TRAVERSE")) MORNA_TRY(launch_split_traversal(pl, P, Rp, nb, ts));
+            else MORNA_TRY(launch_fused_traversal(pl, P, Rp, nb, ts));
+            if (early.live) {
                 HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_early_out, 0));
-            } else if (dense) {
+            } else if (forked) {
                 HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
                 HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             }
-#define REFINE(MODE)                                                                                                         \
-    do {                                                                                                                     \
-        if (lds_q > 48 * 1024)                                                                                               \
-            HIP_TRY(hipFuncSetAttribute((const void *)query_refine_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds_q));                                                                        \
-        hipLaunchKernelGGL(query_refine_kernel<MODE>, dim3((unsigned)nb), dim3(Q_THREADS), lds_q, h->stream, P);             \
-    } while (0)
-            if (!use_filter) REFINE(0);
-            else if (!dense) REFINE(1);
-            else REFINE(2);
-#undef REFINE
+            MORNA_TRY(launch_refine(pl, P, dense, nb, h->stream));
         }
         HIP_TRY(hipGetLastError());
+        // ---- deliver
         if (packed_dev) {
             // row-sharded search: the answers stay in HBM, packed as the message of the top-k all-gather
             hipLaunchKernelGGL(pack_topk_kernel, dim3((unsigned)((nb * k + 255) / 256)), dim3(256), 0, h->stream, P.ids_out,
@@ -1689,7 +1874,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
         } else if (ids_out) {
             // one copy of the whole result block into page-locked memory of the handle (three copies into the caller's
             // pageable arrays cost ~25 us of idle device each), then plain memcpys
-            MORNA_TRY(fetch_results(h, out_block, 2 * s_ids + s_qf, s_ids, s_ids, 4, nb, k, ids_out + q0 * k,
+            MORNA_TRY(fetch_results(h, out_block, out_bytes, s_ids, s_ids, 4, nb, k, ids_out + q0 * k,
                                     dist_out ? dist_out + q0 * k : nullptr, count_out ? count_out + q0 : nullptr));
         }
         // (packed answers only: nothing to wait for -- the next batch, and whatever the caller orders on the handle's
@@ -1704,28 +1889,9 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
 // of every candidate of the deepest lists once -- for a batch that query_batch's dense_pays rule sends through the
 // whole-batch contraction, only of the candidates the fp16 filter of some cell lets through --; per cell the k smallest
 // keys of its prefix.
-// ex_ids_host [nq][k] / ex_count_host [nq] with hits_out: the exact answers of the same queries, for the recall count.
-// q_host: query vectors in host OR device memory, q_stride floats apart (0 = dim), as query_batch takes them.
-int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
-                 const int32_t *trees, int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out,
-                 int32_t *count_out, int32_t *ncand_out, int32_t *ndots_out, const int32_t *ex_ids_host,
-                 const int32_t *ex_count_host, int32_t *hits_out)
+
+static int check_sweep_lists(const int32_t *trees, int32_t n_t, const int32_t *search_ks, int32_t n_s)
 {
-    MORNA_TRY(finish_build(h, "search_sweep"));   // (reads the node tables the tail of a pending build writes)
-    if (q_stride <= 0) q_stride = h->dim;
-    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
-    if (!h->built) {
-        set_error("index has not been built: call build() before searching");
-        return MORNA_E_STATE;
-    }
-    if (k <= 0 || nq < 0) {
-        set_error("search_sweep: n must be positive");
-        return MORNA_E_INVALID;
-    }
-    if (h->dpad > Q_MAX_DPAD) {
-        set_error("search_sweep: dimension %d is above the supported %d", h->dim, Q_MAX_DPAD);
-        return MORNA_E_INVALID;
-    }
     if (!trees || !search_ks || n_t < 1 || n_s < 1 || n_t > SWEEP_MAX_LIST || n_s > SWEEP_MAX_LIST) {
         set_error("search_sweep: %d tree counts and %d search_k values given, each list holds 1 to %d", n_t, n_s, SWEEP_MAX_LIST);
         return MORNA_E_INVALID;
@@ -1740,222 +1906,169 @@ int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const in
             set_error("search_sweep: search_k values must be positive and strictly ascending (entry %d is %d)", j, search_ks[j]);
             return MORNA_E_INVALID;
         }
-    if (trees[n_t - 1] > h->n_trees) {
-        set_error("search_sweep: %d trees asked for, the forest has %d", trees[n_t - 1], h->n_trees);
-        return MORNA_E_RANGE;
-    }
-    if (nq == 0) return MORNA_OK;
-    if (items_host)
-        for (int64_t i = 0; i < nq; i++)
-            if (items_host[i] < 0 || items_host[i] >= h->n_items) {
-                set_error("item id %d out of range [0, %lld)", items_host[i], (long long)h->n_items);
-                return MORNA_E_RANGE;
-            }
-    const int64_t N = h->n_items;
-    const int32_t T_max = trees[n_t - 1], s_max = search_ks[n_s - 1];
-    const int64_t n_cells = (int64_t)n_t * n_s;
-    // |nns| < search_k before the last pop, which adds at most K ids (every cell's own bound is below the deepest one's)
-    const int32_t cap = (int32_t)std::max<int64_t>(std::min<int64_t>(N, (int64_t)s_max + h->K), 1);
-    const int32_t bm_words = (int32_t)((N + 31) / 32);
-    const bool bm_lds = (size_t)bm_words * 4 <= 64 * 1024;
-    const bool want_hits = hits_out && ex_ids_host && ex_count_host;
-    // the fp16 filter through ONE whole-batch contraction, by query_batch's rule for a batch (MORNA_SWEEP_FILTER=0: canonical
-    // dots for every candidate of the deepest lists, as the small batches take them)
-    static const bool filter_on = env_on("MORNA_QUERY_FILTER"), dense_on = env_on("MORNA_QUERY_DENSE");
-    const bool sweep_filter_on = env_on("MORNA_SWEEP_FILTER");
-    auto dense_pays = [&](int64_t nb) { return nb >= 40 && nb * std::min<int64_t>(cap, h->K) >= 2 * N; };
-    const bool may_dense = filter_on && dense_on && sweep_filter_on && cap > 4 * (int64_t)k && dense_pays(nq);
+    return MORNA_OK;
+}
 
+// the plan of the deepest cell: every cell's own candidate bound is below its
+static QueryPlan plan_sweep(const morna_index *h, bool by_vector, int64_t nq, int32_t k, int32_t T_max, int32_t s_max, int32_t n_t,
+                            int32_t n_s)
+{
+    QueryPlan pl = {};
+    const int64_t N = h->n_items, n_cells = (int64_t)n_t * n_s;
+    pl.T_used = T_max;
+    pl.search_k = s_max;
+    pl.cap = (int32_t)std::max<int64_t>(std::min<int64_t>(N, (int64_t)s_max + h->K), 1);
+    pl.bm_words = (int32_t)((N + 31) / 32);
+    pl.lds_q = (size_t)h->dpad * sizeof(float);
+    pl.bm_lds = (size_t)pl.bm_words * 4 <= 64 * 1024;   // (nothing else of the descents is in dynamic LDS)
+    pl.lds_bm = pl.bm_lds ? (size_t)pl.bm_words * 4 : 0;
+    // the fp16 filter through ONE whole-batch contraction, by query_batch's rule for a batch (MORNA_SWEEP_FILTER=0, read per
+    // call: canonical dots for every candidate of the deepest lists, as the small batches take them)
+    const bool sweep_filter_on = env_on("MORNA_SWEEP_FILTER");
+    pl.may_dense = query_filter_on() && query_dense_on() && sweep_filter_on && pl.cap > 4 * (int64_t)k && dense_pays(h, pl.cap, nq);
+    pl.use_filter = pl.may_dense;
     // the 1 GiB workspace rule of query_batch; the unit is a query with its n_t virtual queries and n_t * n_s cells
-    const size_t per_v = (size_t)h->n_nodes * 8 + (size_t)cap * (may_dense ? 24 : 12) + 16 + (bm_lds ? 0 : (size_t)bm_words * 4);
+    const size_t per_v = (size_t)h->n_nodes * 8 + (size_t)pl.cap * (pl.may_dense ? 24 : 12) + 16 + (pl.bm_lds ? 0 : (size_t)pl.bm_words * 4);
     const size_t per_c = (size_t)k * 8 + 20;
-    const size_t per_q = (size_t)h->n_nodes * 8 + (q_host ? (size_t)h->dpad * 6 + 16 : 0) + 16 + (size_t)k * 4 + per_v * n_t +
-                         per_c * n_cells + (may_dense ? (size_t)N * 4 : 0);
-    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 32768), (int64_t)(((size_t)1 << 30) / per_q)));
-    const int64_t bv = batch * n_t, bc = batch * n_cells;
-    const size_t s_rpq = align_up((size_t)batch * h->n_nodes * 8, 256), s_q = q_host ? align_up((size_t)batch * h->dpad * 4, 256) : 0,
-                 s_qf = align_up((size_t)batch * 4, 256), s_exi = want_hits ? align_up((size_t)batch * k * 4, 256) : 0,
-                 s_pq = align_up((size_t)bv * h->n_nodes * 8, 256), s_keys = align_up((size_t)bv * cap * 8, 256),
-                 s_cand = align_up((size_t)bv * cap * 4, 256), s_vf = align_up((size_t)bv * 8, 256),
-                 s_bm = bm_lds ? 0 : align_up((size_t)bv * bm_words * 4, 256), s_ids = align_up((size_t)bc * k * 4, 256),
-                 s_cf = align_up((size_t)bc * 4, 256), s_q16 = q_host && may_dense ? align_up((size_t)batch * h->dpad * 2, 256) : 0,
-                 s_scores = may_dense ? align_up((size_t)batch * N * 4, 256) : 0, s_ub = may_dense ? s_keys : 0,
-                 s_low = may_dense ? s_cand : 0;
-    MORNA_TRY(h->ws.alloc(s_rpq + s_q + 7 * s_qf + s_exi + s_pq + s_keys + s_cand + 2 * s_vf + s_bm + 2 * s_ids + 5 * s_cf + s_q16 +
-                          s_scores + s_ub + s_low));
+    const size_t per_q = (size_t)h->n_nodes * 8 + (by_vector ? (size_t)h->dpad * 6 + 16 : 0) + 16 + (size_t)k * 4 + per_v * n_t +
+                         per_c * n_cells + (pl.may_dense ? (size_t)N * 4 : 0);
+    pl.batch = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 32768), (int64_t)(((size_t)1 << 30) / per_q)));
+    return pl;
+}
+
+// ex_ids_host [nq][k] / ex_count_host [nq] with hits_out: the exact answers of the same queries, for the recall count.
+// q_host: query vectors in host OR device memory, q_stride floats apart (0 = dim), as query_batch takes them.
+int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const int32_t *items_host, int64_t nq, int32_t k,
+                 const int32_t *trees, int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out,
+                 int32_t *count_out, int32_t *ncand_out, int32_t *ndots_out, const int32_t *ex_ids_host,
+                 const int32_t *ex_count_host, int32_t *hits_out)
+{
+    // ---- check
+    MORNA_TRY(finish_build(h, "search_sweep"));   // (reads the node tables the tail of a pending build writes)
+    if (q_stride <= 0) q_stride = h->dim;
+    const bool by_vector = q_host != nullptr;
+    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    MORNA_TRY(require_built(h));
+    MORNA_TRY(check_search_call(h, "search_sweep", k, nq));
+    MORNA_TRY(check_sweep_lists(trees, n_t, search_ks, n_s));
+    MORNA_TRY(check_tree_count(h, "search_sweep", trees[n_t - 1]));
+    if (nq == 0) return MORNA_OK;
+    if (items_host) MORNA_TRY(check_items(h, items_host, nq));
+
+    // ---- plan
+    const int64_t N = h->n_items, n_cells = (int64_t)n_t * n_s;
+    const bool want_hits = hits_out && ex_ids_host && ex_count_host;
+    const QueryPlan pl = plan_sweep(h, by_vector, nq, k, trees[n_t - 1], search_ks[n_s - 1], n_t, n_s);
+    SweepArgs S;
+    S.n_t = n_t; S.n_s = n_s;
+    for (int i = 0; i < SWEEP_MAX_LIST; i++) {
+        S.trees[i] = i < n_t ? trees[i] : 0;
+        S.search_ks[i] = i < n_s ? search_ks[i] : 0;
+    }
+    // ---- the workspace, bound once: slices per query (b), per virtual query (bv) and per cell (bc) of a batch
     MORNA_TRY(h->d_stat.alloc(4));
-    if (may_dense) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
-    bool contraction_ran = false;
-    const size_t out_bytes = 2 * s_ids + 4 * s_cf;
+    QueryParams W = base_params(h, pl, k);
+    QueryInputs in;
+    uint64_t *root_pq = nullptr, *d_ub = nullptr;
+    int32_t *d_exc = nullptr, *d_exi = nullptr, *d_hits = nullptr;
+    float *d_thr = nullptr;
+    size_t out0 = 0, s_ids = 0, s_cf = 0, out_bytes = 0;
+    MORNA_TRY(carve_workspace(h->ws, [&](Carver &c) {
+        const size_t b = (size_t)pl.batch, bv = b * n_t, bc = bv * n_s;
+        root_pq = c.take<uint64_t>(b * h->n_nodes);   // the root margins at the largest tree count
+        W.qpp = c.take<float>(b);
+        in.carve(c, h, pl.batch, by_vector, pl.may_dense, pl.may_dense);
+        d_exc = c.take<int32_t>(b);
+        d_exi = c.take<int32_t>(want_hits ? b * k : 0);
+        W.pq = c.take<uint64_t>(bv * h->n_nodes);
+        W.keys = c.take<uint64_t>(bv * pl.cap);
+        W.cand = c.take<int32_t>(bv * pl.cap);
+        W.ncand = c.take<int32_t>(bv);
+        W.cand_off = c.take<int64_t>(bv);
+        W.bm_global = c.take<uint32_t>(pl.bm_lds ? 0 : bv * pl.bm_words);
+        d_ub = c.take<uint64_t>(pl.may_dense ? bv * pl.cap : 0);
+        W.low = pl.may_dense ? c.take<float>(bv * pl.cap) : nullptr;
+        out0 = c.used;   // ids, distances, counts, ncand, ndots, hits of the batch's cells: one block, one copy to the host
+        W.ids_out = c.take<int32_t>(bc * k);
+        s_ids = c.used - out0;
+        W.dist_out = c.take<float>(bc * k);
+        W.count_out = c.take<int32_t>(bc);
+        s_cf = c.used - out0 - 2 * s_ids;
+        S.cell_ncand = c.take<int32_t>(bc);
+        S.cell_ndots = c.take<int32_t>(bc);
+        d_hits = c.take<int32_t>(bc);
+        out_bytes = c.used - out0;
+        d_thr = c.take<float>(bc);   // (behind the block that goes to the host)
+    }));
+    S.root_pq = root_pq;
+    if (pl.may_dense) MORNA_TRY(split_mm_prepare_rows(h, h->stream));
     MORNA_TRY(h->host_out.reserve(out_bytes));
 
+    bool contraction_ran = false;
     double descents = 0, rows_dots = 0;
-    for (int64_t q0 = 0; q0 < nq; q0 += batch) {
-        const int64_t nb = std::min(batch, nq - q0);
+    for (int64_t q0 = 0; q0 < nq; q0 += pl.batch) {
+        const int64_t nb = std::min(pl.batch, nq - q0);
         const int64_t nv = nb * n_t, nc = nb * n_cells;
-        uint8_t *p = h->ws.p;
-        QueryParams P;
-        P.X = h->X.p; P.norm2 = h->norm2.p; P.n_items = N; P.dpad = h->dpad; P.n_trees = T_max; P.K = h->K;
-        P.node_rec = h->node_rec.p; P.node_tree = h->node_tree.p; P.node_hp = h->node_hp.p; P.hp = h->hp.p;
-        P.perm = h->perm.p; P.n_nodes = h->n_nodes;
-        P.k = k; P.search_k = s_max; P.cap = cap; P.bm_words = bm_words;
-        uint64_t *root_pq = (uint64_t *)p; p += s_rpq;
-        float *Qd = (float *)p; p += s_q;
-        P.qpp = (float *)p; p += s_qf;
-        int32_t *d_items = (int32_t *)p; p += s_qf;
-        int32_t *d_exc = (int32_t *)p; p += 2 * s_qf;
-        int32_t *d_exi = (int32_t *)p; p += s_exi;
-        P.pq = (uint64_t *)p; p += s_pq;
-        P.keys = (uint64_t *)p; p += s_keys;
-        P.cand = (int32_t *)p; p += s_cand;
-        P.ncand = (int32_t *)p; p += s_vf;
-        P.cand_off = (int64_t *)p; p += s_vf;
-        P.bm_global = (uint32_t *)p; p += s_bm;
-        uint8_t *const out_block = p;   // ids, distances, counts, ncand, ndots, hits of the batch's cells: one copy to the host
-        P.ids_out = (int32_t *)p; p += s_ids;
-        P.dist_out = (float *)p; p += s_ids;
-        P.count_out = (int32_t *)p; p += s_cf;
-        int32_t *cell_ncand = (int32_t *)p; p += s_cf;
-        int32_t *cell_ndots = (int32_t *)p; p += s_cf;
-        int32_t *d_hits = (int32_t *)p; p += s_cf;
-        float *d_thr = (float *)p; p += s_cf;   // (behind the block that goes to the host)
-        float *q_n16 = (float *)p; p += s_qf;
-        float *q_e16 = (float *)p; p += s_qf;
-        float *q_scale = (float *)p; p += s_qf;
-        _Float16 *Q16 = (_Float16 *)p; p += s_q16;
-        float *scores = (float *)p; p += s_scores;
-        uint64_t *d_ub = (uint64_t *)p; p += s_ub;
-        P.low = may_dense ? (float *)p : nullptr; p += s_low;
-        const bool dense = may_dense && dense_pays(nb);
-        P.zero_copy = 0;
-        P.stat = h->d_stat.p;
-        P.X16 = nullptr; P.xscale = nullptr; P.xn16 = P.xe16 = nullptr; P.delta = 0.f;
-        P.scores = nullptr; P.qscale = P.qn16 = P.qe16 = nullptr; P.eacc = P.eacc_big = 0.f; P.big_rows = 0;
-        P.Q = nullptr; P.items = nullptr; P.n_inline = 0;
-        if (q_host) {
-            HIP_TRY(hipMemsetAsync(Qd, 0, (size_t)nb * h->dpad * 4, h->stream));
-            HIP_TRY(hipMemcpy2DAsync(Qd, (size_t)h->dpad * 4, q_host + q0 * q_stride, (size_t)q_stride * 4, (size_t)h->dim * 4, (size_t)nb,
-                                     hipMemcpyDefault, h->stream));
-            P.Q = Qd;
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_items, items_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-            P.items = d_items;
-        }
+        const bool dense = pl.may_dense && dense_pays(h, pl.cap, nb);
+        QueryParams P = W;
+        S.nq = (int32_t)nb;
+        // ---- stage the queries, and the exact answers
+        MORNA_TRY(stage_queries(h, in, q_host, q_stride, items_host, q0, nb, h->stream));
+        if (by_vector) P.Q = in.Q;
+        else P.items = in.items;
         if (want_hits) {
             HIP_TRY(hipMemcpyAsync(d_exi, ex_ids_host + q0 * k, (size_t)nb * k * 4, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(hipMemcpyAsync(d_exc, ex_count_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
         }
-        SweepArgs S;
-        S.n_t = n_t; S.n_s = n_s; S.nq = (int32_t)nb;
-        for (int i = 0; i < SWEEP_MAX_LIST; i++) {
-            S.trees[i] = i < n_t ? trees[i] : 0;
-            S.search_ks[i] = i < n_s ? search_ks[i] : 0;
-        }
-        S.root_pq = root_pq; S.cell_ncand = cell_ncand; S.cell_ndots = cell_ndots;
         {
             ScopedTimer tm(h, MORNA_T_QUERY, 0);
-            // root margins and the queries' norms, once, for the largest tree count
+            // ---- traverse: root margins and the queries' norms, once, for the largest tree count; one descent per virtual query
             QueryParams PR = P;
             PR.pq = root_pq;
-            const int nvq = h->dpad / 256;
-            const bool nv_ok = h->dpad % 256 == 0 && (nvq == 1 || nvq == 2 || nvq == 3 || nvq == 4 || nvq == 6 || nvq == 8 || nvq == 12);
-            if (nb >= 64 && nv_ok && N > h->K && (size_t)QR_Q * h->dpad * 4 <= 128 * 1024) {
-                const dim3 grid((unsigned)((nb + QR_Q - 1) / QR_Q), (unsigned)((T_max + QR_TREES - 1) / QR_TREES));
-                const size_t ql = (size_t)QR_Q * h->dpad * 4;
-#define ROOTSB(NVV)                                                                                                      \
-    do {                                                                                                                 \
-        if (ql > 48 * 1024)                                                                                              \
-            HIP_TRY(hipFuncSetAttribute((const void *)query_roots_batch_kernel<NVV>,                                      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql));                           \
-        hipLaunchKernelGGL((query_roots_batch_kernel<NVV>), grid, dim3(QR_THREADS), ql, h->stream, PR, (int32_t)nb);     \
-    } while (0)
-                switch (nvq) {
-                case 1: ROOTSB(1); break;
-                case 2: ROOTSB(2); break;
-                case 3: ROOTSB(3); break;
-                case 4: ROOTSB(4); break;
-                case 6: ROOTSB(6); break;
-                case 8: ROOTSB(8); break;
-                default: ROOTSB(12); break;
-                }
-#undef ROOTSB
-            } else {
-                hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((T_max + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
+            if (nb >= 64 && roots_by_groups_ok(h))
+                MORNA_TRY(launch_roots_by_groups(PR, nb, h->stream));
+            else
+                hipLaunchKernelGGL(query_roots_kernel, dim3((unsigned)((pl.T_used + Q_WAVES - 1) / Q_WAVES), (unsigned)nb), dim3(Q_THREADS), 0,
                                    h->stream, PR);
-            }
-            // one descent per virtual query
-            const size_t bl = bm_lds ? (size_t)bm_words * 4 : 0;
-#define DESCEND(NVV)                                                                                                              \
-    do {                                                                                                                          \
-        if (bm_lds) {                                                                                                             \
-            if (bl > 32 * 1024)                                                                                                   \
-                HIP_TRY(hipFuncSetAttribute((const void *)query_descend_sweep_kernel<true, NVV>,                                  \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bl));                                \
-            hipLaunchKernelGGL((query_descend_sweep_kernel<true, NVV>), dim3((unsigned)nv), dim3(WAVE), bl, h->stream, P, S);     \
-        } else {                                                                                                                  \
-            hipLaunchKernelGGL((query_descend_sweep_kernel<false, NVV>), dim3((unsigned)nv), dim3(WAVE), 0, h->stream, P, S);     \
-        }                                                                                                                         \
-    } while (0)
-            switch (h->dpad % 256 == 0 ? h->dpad / 256 : 0) {   // float4 per lane of a row
-            case 1: DESCEND(1); break;
-            case 2: DESCEND(2); break;
-            case 3: DESCEND(3); break;
-            case 4: DESCEND(4); break;
-            case 6: DESCEND(6); break;
-            case 8: DESCEND(8); break;
-            case 12: DESCEND(12); break;
-            default: DESCEND(0); break;
-            }
-#undef DESCEND
-            const int32_t bpv = (cap + Q_WAVES - 1) / Q_WAVES;
+            MORNA_TRY(launch_sweep_descents(pl, P, S, nv, h->stream));
+            // ---- refine
+            const int32_t bpv = (pl.cap + Q_WAVES - 1) / Q_WAVES;
             if (dense) {
                 // the contraction of the batch's queries against all rows, once (the 128 x 128 form for every row), and from
                 // it the bounds of every virtual query's candidates and every cell's threshold
-                const float *xn = h->half.xn.p;
-                P.X16 = h->half.x16.p;
-                P.xn16 = xn; P.xscale = xn + N; P.xe16 = xn + 2 * N;
-                P.eacc = mm16_eacc(h->dpad);
-                const _Float16 *q16 = P.X16;
-                const int32_t *qrow = P.items;
-                if (q_host) {
-                    split_mm_convert_rows(h, Qd, nb, Q16, q_n16, q_e16, q_scale, h->stream);
-                    q16 = Q16; qrow = nullptr;
-                    P.qn16 = q_n16; P.qe16 = q_e16; P.qscale = q_scale;
-                } else {
-                    P.qn16 = P.xn16; P.qe16 = P.xe16; P.qscale = P.xscale;
-                }
+                set_filter_rows(h, P);
+                HalfImage im;
+                MORNA_TRY(half_image(h, in, by_vector, nb, true, h->stream, im));
+                P.qn16 = im.qn16; P.qe16 = im.qe16; P.qscale = im.qscale;
                 {
                     ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
-                    const unsigned n_ct = (unsigned)((nb + MM16_TILE - 1) / MM16_TILE), n_rt = (unsigned)((N + 127) / 128);
-                    HIP_TRY(hipFuncSetAttribute((const void *)query_scores_kernel<128, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MM16_LDS));
-                    hipLaunchKernelGGL((query_scores_kernel<128, 64, 2>), dim3(8u * ((n_rt + 7) / 8) * n_ct), dim3(MM16_THREADS), MM16_LDS,
-                                       h->stream, P.X16, N, h->dpad, q16, qrow, (int32_t)nb, scores, (int64_t)0);
+                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream, false, &P.big_rows));
                 }
-                P.scores = scores;
+                P.scores = in.scores;
                 contraction_ran = true;
                 hipLaunchKernelGGL(sweep_bounds_kernel, dim3((unsigned)nv), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb, d_ub);
                 hipLaunchKernelGGL(sweep_threshold_kernel, dim3((unsigned)nc), dim3(Q_THREADS), 0, h->stream, P, n_s, (int32_t)nb,
-                                   cell_ncand, d_ub, d_thr);
+                                   S.cell_ncand, d_ub, d_thr);
                 HIP_TRY(hipMemsetAsync(h->d_stat.p + 3, 0, sizeof(unsigned long long), h->stream));
                 hipLaunchKernelGGL(sweep_cand_dots_kernel<true>, dim3((unsigned)(nv * bpv)), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb,
-                                   bpv, n_s, cell_ncand, d_thr);
+                                   bpv, n_s, S.cell_ncand, d_thr);
             } else {
                 hipLaunchKernelGGL(sweep_cand_dots_kernel<false>, dim3((unsigned)(nv * bpv)), dim3(Q_THREADS), 0, h->stream, P, (int32_t)nb,
-                                   bpv, n_s, cell_ncand, d_thr);
+                                   bpv, n_s, S.cell_ncand, d_thr);
             }
-            hipLaunchKernelGGL(sweep_topk_kernel, dim3((unsigned)nc), dim3(Q_THREADS), 0, h->stream, P, n_s, (int32_t)nb, cell_ncand);
+            hipLaunchKernelGGL(sweep_topk_kernel, dim3((unsigned)nc), dim3(Q_THREADS), 0, h->stream, P, n_s, (int32_t)nb, S.cell_ncand);
             if (want_hits)
-                hipLaunchKernelGGL(sweep_hits_kernel, dim3((unsigned)nc), dim3(WAVE), 0, h->stream, P.ids_out, P.count_out, d_exi, d_exc,
-                                   (int32_t)nb, k, d_hits);
+                hipLaunchKernelGGL(sweep_hits_kernel, dim3((unsigned)nc), dim3(WAVE), 0, h->stream, P.ids_out, P.count_out, d_exi,
+                                   d_exc, (int32_t)nb, k, d_hits);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->host_out.p, out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        // ---- deliver: the batch's block is [cell][nb]; the caller's arrays are [cell][nq]
+        HIP_TRY(hipMemcpyAsync(h->host_out.p, W.ids_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->unsettled = false;
-        // the batch's block is [cell][nb]; the caller's arrays are [cell][nq]
-        const uint8_t *hb = h->host_out.p;
-        const int32_t *b_ids = (const int32_t *)hb, *b_cnt = (const int32_t *)(hb + 2 * s_ids), *b_nc = (const int32_t *)(hb + 2 * s_ids + s_cf),
-                      *b_nd = (const int32_t *)(hb + 2 * s_ids + 2 * s_cf), *b_hit = (const int32_t *)(hb + 2 * s_ids + 3 * s_cf);
+        const uint8_t *hb = h->host_out.p, *hc = hb + 2 * s_ids;
+        const int32_t *b_ids = (const int32_t *)hb, *b_cnt = (const int32_t *)hc, *b_nc = (const int32_t *)(hc + s_cf),
+                      *b_nd = (const int32_t *)(hc + 2 * s_cf), *b_hit = (const int32_t *)(hc + 3 * s_cf);
         const float *b_dist = (const float *)(hb + s_ids);
         for (int64_t c = 0; c < n_cells; c++) {
             const size_t row = (size_t)nb * 4;
@@ -1974,7 +2087,7 @@ int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const in
         } else
         for (int64_t v = 0; v < nv; v++) {   // the deepest cell of every virtual query: the candidates that got a canonical dot
             const int64_t ti = v / nb, q = v - ti * nb;
-            rows_dots += (double)std::min<int32_t>(b_nc[((ti * n_s) + (n_s - 1)) * nb + q], cap);
+            rows_dots += (double)std::min<int32_t>(b_nc[((ti * n_s) + (n_s - 1)) * nb + q], pl.cap);
         }
     }
     h->sweep_stats[0] = descents;
@@ -2842,14 +2955,9 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
     int32_t *d_ids = (int32_t *)p; p += s_ids;
     double *d_dist = (double *)p; p += s_dist;
     int32_t *d_cnt = (int32_t *)p; p += s_b4;
-    RestrictArgs R = {nullptr, nullptr, nullptr};
     int32_t *d_qg = nullptr;
-    if (rst) {
-        R.deny = rst->deny.p;
-        R.group = rst->has_group ? rst->group.p : nullptr;
-        if (R.group && q_group_host) { d_qg = (int32_t *)p; p += s_b4; }
-        R.q_group = d_qg;
-    }
+    if (rst && rst->has_group && q_group_host) { d_qg = (int32_t *)p; p += s_b4; }
+    const RestrictArgs R = restrict_args(rst, d_qg);
     std::vector<int32_t> h_ncand((size_t)batch);
     int32_t cap = std::max<int32_t>(std::max(64, 4 * k) + n_outs, h->ex_cap), need_max = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += batch) {
@@ -3053,12 +3161,7 @@ int label_sums(morna_index *h, const morna_restriction *rst, const double *q_hos
     int32_t *d_cnts = (int32_t *)(h->lb_out.p + s_sums);
     unsigned long long *d_counted = (unsigned long long *)(h->lb_out.p + s_sums + s_cnts);
     HIP_TRY(hipMemcpyAsync(h->lb_label.p, item_label_host, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
-    RestrictArgs Ra = {nullptr, nullptr, nullptr};
-    if (rst) {
-        Ra.deny = rst->deny.p;
-        Ra.group = rst->has_group ? rst->group.p : nullptr;
-        Ra.q_group = Ra.group && q_group_host ? d_qg : nullptr;
-    }
+    const RestrictArgs Ra = restrict_args(rst, q_group_host ? d_qg : nullptr);
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]));
     int rc = MORNA_OK;

@@ -100,6 +100,23 @@ def test_filter_form_equals_canonical_form():
                 assert got[key].tobytes() == want[key].tobytes(), (name, k, key)
 
 
+def test_two_batches_equal_one_batch_slices():
+    """10000 queries over 3 tree counts to search_k 4000 (cap = 3000): a query costs at least n_t * 12 * cap = 108000 bytes
+    of the 1 GiB workspace, so at most 9942 fit in a batch: two batches, the second ragged.  The same queries swept in slices
+    of 2500 are one batch each; every returned array is their concatenation along the query axis."""
+    a = index(N, D, 8)
+    nq, k, sks, step = 10000, 20, (10, 4000), 2500
+    for name, kw, _ in sources(a, nq, seed=31):
+        (key, val), = kw.items()
+        got = a.search_sweep(k, TREES, sks, **kw)
+        assert a.sweep_stats()["descents"] == nq * len(TREES)
+        parts = [a.search_sweep(k, TREES, sks, **{key: val[at:at + step]}) for at in range(0, nq, step)]
+        assert set(got) == {"ids", "dist", "count", "ncand", "ndots"}
+        for out in got:
+            want = np.concatenate([p[out] for p in parts], axis=2)
+            assert got[out].shape == want.shape and got[out].tobytes() == want.tobytes(), (name, out)
+
+
 def test_null_outputs_repeats_and_the_default_search():
     from morna_amd._lib import check, lib, ptr
     a = index(N, D, 8)

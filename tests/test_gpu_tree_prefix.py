@@ -153,6 +153,27 @@ def test_whole_forest_is_the_plain_call():
             same(c, b, "default_after_prefix/nq%d" % nq)
 
 
+def test_two_batches_equal_one_batch_slices():
+    """24000 queries at search_k 4000: cap = min(n, search_k + K) = 3000, the candidate arrays alone are 16 * cap = 48000
+    bytes per query, so the 1 GiB workspace rule allows at most 22369 queries per batch whatever the forest's node count:
+    two batches, the second ragged, where every offset by the batch's first query is.  The same queries in slices of 4096
+    are one batch each.  By item, by vector, and restricted with an allow-list and a leave-out group per query."""
+    from test_gpu_restrict import _groups, _query_groups
+    a = index(3000, D, 8)
+    nq, k, search_k, step = 24000, 20, 4000, 4096
+    Q, items = queries(3000, D, nq, seed=24)
+    rng = np.random.default_rng(24)
+    r = a.restriction(rng.random(3000) < 0.5, _groups(rng, 3000))
+    qg = _query_groups(nq)
+    for name, call in (("item", lambda s: a.get_nns_by_item_batch(items[s], k, search_k)),
+                       ("vector", lambda s: a.get_nns_by_vector_batch(Q[s], k, search_k)),
+                       ("restricted", lambda s: a.get_nns_restricted(r, k, search_k, items=items[s], query_groups=qg[s]))):
+        got = call(slice(0, nq))
+        parts = [call(slice(at, at + step)) for at in range(0, nq, step)]
+        same(got, [np.concatenate([p[i] for p in parts]) for i in range(3)], "two_batches/" + name)
+        assert (got[2] > 0).all()
+
+
 def test_prefix_staged_query_rows():
     """Neither Q nor items: the rows of build_query_rows, as get_nns_by_query_rows takes them."""
     from test_gpu_restrict import _stage_rows
