@@ -94,6 +94,8 @@ struct QueryParams {
     float eacc;       // bound of the fp32 accumulation of a filter dot: two chains (128 x 128 form) ...
     float eacc_big;   // ... one chain: the rows below big_rows went through the 256 x 256 form
     int64_t big_rows;
+    // MORNA_DEBUG_OPEN=1 only (else null): query_refine_kernel<2> adds (candidates << 32) + survivors of every query to it
+    unsigned long long *refine_stat;
 };
 
 // A restriction of one search call (include/morna_hip.h, "restricted search"): item i is eligible for query q iff its
@@ -1147,6 +1149,8 @@ __global__ __launch_bounds__(Q_THREADS) void query_refine_kernel(QueryParams P)
         }
         nsel = s_nsurv;
     }
+    if (MODE == 2 && P.refine_stat && tid == 0)   // (one batch: at most 2^26 candidates, the 1 GiB workspace rule)
+        atomicAdd(P.refine_stat, ((unsigned long long)ncand << 32) + (unsigned long long)nsel);
     __syncthreads();
     for (int c = w; c < nsel; c += Q_WAVES) {
         const int32_t id = cand[c];
@@ -1485,11 +1489,19 @@ static int half_image(morna_index *h, const QueryInputs &in, bool by_vector, int
     return MORNA_OK;
 }
 
+// MORNA_DEBUG_OPEN=1 (read once per process): one line per contraction and per dense batch on stderr
+static bool query_debug_open()
+{
+    static const bool on = getenv("MORNA_DEBUG_OPEN") && atoi(getenv("MORNA_DEBUG_OPEN")) != 0;
+    return on;
+}
+
 // The whole-batch contraction: 256 x 256 tiles for as many 256-row tiles as make whole rounds of the chip (one workgroup
 // per CU), the 128 x 128 form for the rows behind them (MORNA_QUERY_BIG=0, read once per process, or !allow_big: for all
 // rows).  st_big / st_rem: the streams of the two launches; *big_rows_out: the rows the large form took.
+// site: the caller, for the MORNA_DEBUG_OPEN line (host values only).
 static int launch_contraction(morna_index *h, int64_t nb, const HalfImage &im, float *scores, hipStream_t st_big, hipStream_t st_rem,
-                              bool allow_big, int64_t *big_rows_out)
+                              bool allow_big, int64_t *big_rows_out, const char *site)
 {
     static const bool big_on = env_on("MORNA_QUERY_BIG");
     const _Float16 *X16 = h->half.x16.p;
@@ -1516,6 +1528,10 @@ static int launch_contraction(morna_index *h, int64_t nb, const HalfImage &im, f
                              big_tiles > 0 ? st_rem : st_big, X16, N, h->dpad, im.q16, im.qrow, (int32_t)nb, scores, big_rows));
     }
     HIP_TRY(hipGetLastError());
+    if (query_debug_open())   // which form took which rows: a test can see what it exercised
+        fprintf(stderr, "[morna] query contraction: site=%s queries=%lld rows=%lld big_tiles=%lld rem_rows=%lld query_tiles=%lld %s\n", site,
+                (long long)nb, (long long)N, (long long)big_tiles, (long long)(N - big_rows),
+                (long long)(big_tiles > 0 ? (nb + 255) / 256 : (nb + MM16_TILE - 1) / MM16_TILE), im.qrow ? "by_item" : "by_vector");
     *big_rows_out = big_rows;
     return MORNA_OK;
 }
@@ -1661,7 +1677,7 @@ struct EarlyContraction {
         HalfImage im;
         MORNA_TRY(half_image(h, in, q_host != nullptr, nq, true, s3, im));
         HIP_TRY(hipEventRecord(h->ev_early_in, s3));   // the traversal reads the ids / vectors too
-        MORNA_TRY(launch_contraction(h, nq, im, in.scores, s3, s3, true, &big_rows));
+        MORNA_TRY(launch_contraction(h, nq, im, in.scores, s3, s3, true, &big_rows, "early"));
         HIP_TRY(hipEventRecord(h->ev_early_out, s3));
         const int rc = finish_build(h, "query_batch, beside its contraction");
         if (rc != MORNA_OK) {
@@ -1836,7 +1852,7 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                     HIP_TRY(hipEventRecord(h->ev_fork, h->stream));   // the query vectors (and their fp16 image) / item ids are in place
                     HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
                     ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
-                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream2, true, &P.big_rows));
+                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream2, true, &P.big_rows, "query_batch"));
                 }
                 if (P.big_rows > 0) P.eacc_big = (4.f * (float)h->dpad + 2.f) * 5.9604645e-8f + 4.1e-6f;   // EACC for ONE chain of dpad products
                 P.scores = in.scores;
@@ -1856,7 +1872,19 @@ int query_batch(morna_index *h, const float *q_host, int64_t q_stride, const int
                 HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
                 HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             }
+            const bool count_refine = dense && query_debug_open();
+            if (count_refine) {
+                P.refine_stat = h->d_stat.p + 2;
+                HIP_TRY(hipMemsetAsync(P.refine_stat, 0, sizeof(unsigned long long), h->stream));
+            }
             MORNA_TRY(launch_refine(pl, P, dense, nb, h->stream));
+            if (count_refine) {   // costs a synchronisation, measurement only
+                unsigned long long packed = 0;
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                HIP_TRY(hipMemcpy(&packed, P.refine_stat, sizeof(packed), hipMemcpyDeviceToHost));
+                fprintf(stderr, "[morna] query refine: queries=%lld candidates=%llu survivors=%llu\n", (long long)nb, packed >> 32,
+                        packed & 0xffffffffull);
+            }
         }
         HIP_TRY(hipGetLastError());
         // ---- deliver
@@ -2042,7 +2070,7 @@ int search_sweep(morna_index *h, const float *q_host, int64_t q_stride, const in
                 P.qn16 = im.qn16; P.qe16 = im.qe16; P.qscale = im.qscale;
                 {
                     ScopedTimer tf(h, MORNA_T_QUERY_FILTER, 2 * (int64_t)nb * N * h->dpad);   // "bytes" = executed flops
-                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream, false, &P.big_rows));
+                    MORNA_TRY(launch_contraction(h, nb, im, in.scores, h->stream, h->stream, false, &P.big_rows, "sweep"));
                 }
                 P.scores = in.scores;
                 contraction_ran = true;

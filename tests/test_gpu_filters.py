@@ -6,7 +6,11 @@ what they can PROVE and hand everything else to the canonical fp32 arithmetic, s
 nothing: whole-forest and search digests are compared across MORNA_SPLIT_MM = 0 / 1, MORNA_QUERY_FILTER = 0 / 1 and
 MORNA_QUERY_DENSE = 0 / 1 (the filter dots of a whole batch as one contraction, or candidate by candidate),
 MORNA_SPLIT_BIG = 0 / 1 and MORNA_QUERY_BIG = 0 / 1 (the contractions' tile shapes, each with its own accumulation
-bound), and across
+bound: the query filter's 256 x 256 form takes rows from 512 queries up only, so the digest holds a by-item batch of the
+4096 items 356 .. 4451 -- every family below -- and, where N >= 16384, a by-vector batch of 1024 perturbed rows; the
+library's "[morna] query contraction:" lines (MORNA_DEBUG_OPEN=1) must show large tiles in the default process, by the
+rule of launch_contraction, and none with MORNA_QUERY_BIG=0; tests/test_gpu_query_big.py compares that form with the
+CPU oracle), and across
 MORNA_QUERY_SPLIT_TRAVERSE = 0 / 1 and MORNA_QUERY_SPREAD = 0 / 1 (how a batch's, and a small batch's, traversal is dealt out),
 MORNA_SPLIT_ORDER = 0 / 1 and MORNA_SPLIT_LISTS = 0 / 1 (the order of the rows of the split contraction, and the per-tile
 task lists: both only choose which products are computed; the 256-wide case with 150 trees has levels with enough split
@@ -26,6 +30,8 @@ import subprocess
 import sys
 
 import pytest
+
+from test_gpu_query_big import _CONTRACTION, _big_tiles, _cus
 
 pytestmark = pytest.mark.gpu
 
@@ -93,12 +99,20 @@ for n, sk in ((20, 100), (10, -1), (50, 4000)):
 Q = (X[items[:32]].astype(np.float64) * (1 + 1e-3 * rng.standard_normal((32, D)))).astype(np.float32)
 ids, d, cnt = a.get_nns_by_vector_batch(Q, 20, 100)
 h.update(ids.tobytes()); h.update(d.tobytes()); h.update(cnt.tobytes())
+# batches wide enough for the 256 x 256 form of the whole-batch contraction (512 queries): every adversarial family by item ...
+ids, d, cnt = a.get_nns_by_item_batch(np.arange(356, 4452).astype(np.int32), 20, 100)
+h.update(ids.tobytes()); h.update(d.tobytes()); h.update(cnt.tobytes())
+if N >= 16384:   # ... and 1024 perturbed rows by vector: the midpoints' tail and everything behind them
+    Q = (X[3428:4452].astype(np.float64) * (1 + 1e-3 * rng.standard_normal((1024, D)))).astype(np.float32)
+    ids, d, cnt = a.get_nns_by_vector_batch(Q, 20, 100)
+    h.update(ids.tobytes()); h.update(d.tobytes()); h.update(cnt.tobytes())
 st = a.forest_stats()
 print("DIGEST", h.hexdigest(), st["n_split"], st["max_depth"])
 """
 
 
-# one process per switch (they are read once per process); the default one also prints the open-pair share per level
+# one process per switch (they are read once per process); the default one also prints the open-pair share per level and
+# which form of the query contraction took which rows, the no_query_big one the latter
 _RUNS = (("default", {"MORNA_DEBUG_OPEN": "1"}), ("no_mm", {"MORNA_SPLIT_MM": "0"}),
          ("no_qf", {"MORNA_QUERY_FILTER": "0"}), ("no_dense", {"MORNA_QUERY_DENSE": "0"}),
          ("no_order", {"MORNA_SPLIT_ORDER": "0"}), ("no_lists", {"MORNA_SPLIT_LISTS": "0", "MORNA_SPLIT_ORDER": "0"}),
@@ -106,15 +120,35 @@ _RUNS = (("default", {"MORNA_DEBUG_OPEN": "1"}), ("no_mm", {"MORNA_SPLIT_MM": "0
          # workgroup per query); small batches dealt out over the chip, or one workgroup per query
          ("fused_traverse", {"MORNA_QUERY_SPLIT_TRAVERSE": "0"}), ("no_spread", {"MORNA_QUERY_SPREAD": "0"}),
          # one accumulation bound or the other: 128 x 128 contraction tiles only (split, query filter)
-         ("no_split_big", {"MORNA_SPLIT_BIG": "0"}), ("no_query_big", {"MORNA_QUERY_BIG": "0"}))
+         ("no_split_big", {"MORNA_SPLIT_BIG": "0"}), ("no_query_big", {"MORNA_QUERY_BIG": "0", "MORNA_DEBUG_OPEN": "1"}))
 
 
 def _digest(script, extra):
-    """(digest fields, split_mm open-pair lines) of one process."""
+    """(digest fields, split_mm open-pair lines, query contraction lines as dicts) of one process."""
     r = subprocess.run([sys.executable, script], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()[1:]
-    return out, [ln for ln in r.stderr.splitlines() if ln.startswith("[morna] split_mm level")]
+    contractions = [_CONTRACTION.match(ln) for ln in r.stderr.splitlines() if ln.startswith("[morna] query contraction:")]
+    assert all(contractions), r.stderr[-2000:]
+    contractions = [dict(queries=int(m.group(2)), rows=int(m.group(3)), big_tiles=int(m.group(4)), rem_rows=int(m.group(5)),
+                         by=m.group(7)) for m in contractions]
+    return out, [ln for ln in r.stderr.splitlines() if ln.startswith("[morna] split_mm level")], contractions
+
+
+def _check_query_forms(N, default, no_big):
+    """The large form of the query contraction took rows in the default process (by item; by vector too where the digest has
+    that batch), as many as launch_contraction's rule says, and none with MORNA_QUERY_BIG=0.  Either list may be None."""
+    if default is not None:
+        n_cus = _cus()
+        print(default)
+        for c in default:
+            assert c["rows"] == N and c["big_tiles"] == _big_tiles(n_cus, N, c["queries"]) and c["rem_rows"] == N - 256 * c["big_tiles"], c
+        assert any(c["big_tiles"] > 0 and c["by"] == "by_item" for c in default), default
+        if N >= 16384:
+            assert any(c["big_tiles"] > 0 and c["by"] == "by_vector" for c in default), default
+    if no_big is not None:
+        assert no_big and all(c["big_tiles"] == 0 and c["rem_rows"] == N for c in no_big), no_big
+        assert any(c["queries"] >= 512 for c in no_big), no_big   # batches the large form would have taken
 
 
 def _check_default(out, open_lines):
@@ -136,15 +170,16 @@ def _write_script(path, D, N, T):
 @pytest.mark.parametrize("D,N,T", [(3000, 16000, 6), (8192, 34000, 3), (256, 40000, 150), (12000, 34000, 3)])
 def test_adversarial_rows_filters_change_nothing(tmp_path, D, N, T):
     script = _write_script(str(tmp_path / "digest.py"), D, N, T)
-    out = {}
+    out, forms = {}, {}
     for name, extra in _RUNS:
-        out[name], lines = _digest(script, extra)
+        out[name], lines, forms[name] = _digest(script, extra)
         if name == "default":
             open_lines = lines
     assert out["default"] == out["no_mm"] == out["no_qf"] == out["no_dense"] == out["no_order"] == out["no_lists"], out
     assert out["default"] == out["fused_traverse"] == out["no_spread"], out
     assert out["default"] == out["no_split_big"] == out["no_query_big"], out
     _check_default(out["default"], open_lines)
+    _check_query_forms(N, forms["default"], forms["no_query_big"])
 
 
 # The widest row: 70000 rows of 32768 floats, past twice annoy's leaf of D + 2 rows, so the forest splits below its root
@@ -155,15 +190,19 @@ _WIDEST = (32768, 70000, 2)
 @pytest.fixture(scope="module")
 def widest(tmp_path_factory):
     script = _write_script(str(tmp_path_factory.mktemp("widest") / "digest.py"), *_WIDEST)
-    out, open_lines = _digest(script, dict(_RUNS)["default"])
-    return script, out, open_lines
+    out, open_lines, forms = _digest(script, dict(_RUNS)["default"])
+    return script, out, open_lines, forms
 
 
 def test_widest_row_adversarial_rows_default(widest):
     _check_default(widest[1], widest[2])
+    _check_query_forms(_WIDEST[1], widest[3], None)
 
 
 @pytest.mark.parametrize("name", [n for n, _ in _RUNS if n != "default"])
 def test_widest_row_filters_change_nothing(widest, name):
-    script, default, _ = widest
-    assert _digest(script, dict(_RUNS)[name])[0] == default, name
+    script, default = widest[:2]
+    out, _, forms = _digest(script, dict(_RUNS)[name])
+    assert out == default, name
+    if name == "no_query_big":
+        _check_query_forms(_WIDEST[1], None, forms)
