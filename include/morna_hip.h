@@ -447,6 +447,12 @@ int morna_get_forest_stats(const morna_index *h, morna_forest_stats *out);
  * Any output pointer may be NULL.
  */
 int morna_get_forest(morna_index *h, int32_t *node_rec, int32_t *perm, float *hyperplanes, int32_t *hp_node);
+/*
+ * For tests and probes: item_at[n_items], the item each row of the split contraction stood for in the last build, from its
+ * second level on ("the order of the rows").  MORNA_E_STATE when that build did not order its rows (fewer than
+ * 8192 items, MORNA_SPLIT_ORDER=0, no level in the matrix-core form) or the index is not built.  Not part of the search.
+ */
+int morna_debug_split_order(morna_index *h, int32_t *item_at);
 
 /* ---- search -------------------------------------------------------------- */
 

@@ -107,6 +107,7 @@ SIGNATURES = {
     "morna_get_n_trees": (_i32, [_p]),
     "morna_get_forest_stats": (C.c_int, [_p, C.POINTER(ForestStats)]),
     "morna_get_forest": (C.c_int, [_p, _p, _p, _p, _p]),
+    "morna_debug_split_order": (C.c_int, [_p, _p]),
     "morna_get_nns_by_vector": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "morna_get_nns_by_item": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "morna_exact_search": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p]),

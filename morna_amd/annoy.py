@@ -217,6 +217,16 @@ class AnnoyIndex(object):
         check(lib().morna_get_forest(self._h, ptr(rec), ptr(perm), ptr(hp), ptr(hp_node)))
         return dict(node_rec=rec, perm=perm, hyperplanes=hp[:st["n_split"]], hp_node=hp_node[:st["n_split"]])
 
+    def split_order(self):
+        """item_at [n_items]: the item each row of the split contraction stood for in the last build (from its second level
+        on), or None when that build did not order its rows.  For tests and scripts/active_pairs_probe.py."""
+        out = np.empty(self.get_n_items(), np.int32)
+        rc = lib().morna_debug_split_order(self._h, ptr(out))
+        if rc == _lib.E_STATE:
+            return None
+        check(rc)
+        return out
+
     # ---- search ------------------------------------------------------------
     def get_nns_by_vector_batch(self, Q, n, search_k=-1, n_trees=None):
         """n_trees: search the first n_trees trees only (morna_get_nns_prefix): the answer of an index built with that

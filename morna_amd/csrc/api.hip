@@ -528,6 +528,18 @@ int morna_get_forest(morna_index *h, int32_t *node_rec, int32_t *perm, float *hy
     return MORNA_OK;
 }
 
+int morna_debug_split_order(morna_index *h, int32_t *item_at)
+{
+    CHECK_H(h);
+    if (!item_at) {
+        set_error("debug_split_order: null buffer");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    MORNA_TRY(settle(h));
+    return split_mm_order_read(h, item_at);
+}
+
 // ---- search ------------------------------------------------------------------
 
 int morna_get_nns_by_vector(morna_index *h, const float *q, int64_t nq, int32_t k, int32_t search_k, int32_t *ids_out,

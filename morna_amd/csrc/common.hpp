@@ -269,6 +269,8 @@ struct SplitMmScratch {   // splitmm.hip
     // the order of the contraction's rows (split_mm_order_rows): [rank | item_at], inv by row, the counting sort's table (+ keys)
     DevBuf<int32_t> maps, invr, table;
     bool ord_valid = false;      // the build under way has ordered its rows (maps / invr)
+    bool ord_line_due = false;   // the MORNA_DEBUG_OPEN line of this order has not been printed yet
+    int ord_bits = 0;            // root sides in a row's code
     void release()
     {
         h16.release(); hn.release(); amb.release(); active.release(); lists.release();
@@ -488,6 +490,8 @@ int split_mm_convert_rows(morna_index *h, const float *src, int64_t rows, _Float
 // the sort itself on `stream`
 int split_mm_order_begin(morna_index *h, int32_t n_trees, const int32_t **rank_out, int32_t **inv_out);
 int split_mm_order_rows(morna_index *h, const uint8_t *side, int32_t n_trees, hipStream_t stream);
+int split_mm_order_read(morna_index *h, int32_t *item_at);
+bool split_mm_order_by_groups();   // MORNA_SPLIT_ORDER_GROUPS (on unless 0)
 // inv[tree][rank ? rank[item] : item] = position, for every position of the runs (the side stream, under two_means)
 int split_mm_level_inv(morna_index *h, const InvSeg *d_segs, int32_t n_segs, int32_t n_chunks, const int32_t *perm, const int32_t *rank,
                        int32_t *inv, hipStream_t stream);

@@ -388,34 +388,71 @@ __global__ __launch_bounds__(256) void split_amb_kernel(const float *__restrict_
 
 // ---- an order of the rows for the deep levels ---------------------------------------------------------------------
 // The lists above are short when the rows of a tile are alike: in every tree they then sit in the same few nodes.  After the
-// root level the forest itself says which rows are alike: key(item) = the side the item took at the root of trees 0 .. 11,
-// one bit per tree.  Rows sorted by that key (ties by id: a counting sort with a stable in-block rank, deterministic) make
-// the ROWS of the contraction from the second level on; `rank` (row of an item) and `item_at` (item of a row) translate.
-// C3, blocks of 256 rows x 256 tasks the lists leave at the levels with 800 / 1600 / 1936 split nodes: 494 / 650 / 546,
-// against 640 / 971 / 964 with the rows in id order and 784 / 1372 / 1568 without lists (scripts/active_pairs_probe.py).
+// root level the forest itself says which rows are alike: code(item) = the side the item took at the root of trees
+// 0 .. n_bits - 1, one bit per tree, tree 0 most significant.  `rank` (row of an item) and `item_at` (item of a row) translate
+// between items and the ROWS of the contraction from the second level on.
+//
+// The order, n_bits = min(n_trees, 24) (MORNA_SPLIT_ORDER_GROUPS=0: n_bits = min(n_trees, 12) and rows by (code, id), the order
+// of before; the same kernels, one pass):
+//   sort    rows by (code, id): two stable 12-bit counting-sort passes (in-block rank: deterministic).
+//   cores   a run of equal codes with at least thr = max(16, ceil(N / 2048)) rows, numbered ascending by code.  A core has
+//           thr rows, so there are at most N / thr <= 2048 = ORD_MAX_CORES of them: the cap follows from thr and nothing is
+//           dropped (the guards below only keep a changed thr inside the arrays: cores past the cap would be ignored in
+//           ascending code order).
+//   components  cores whose codes differ in at most ORD_MERGE_DIST = 2 bits are linked; a component is a connected set, its
+//           id its smallest core.  The neighbours of every core first (all pairs of cores, dealt over the chip), then one
+//           workgroup takes the minimum label over neighbours until nothing changes.
+//   assign  every row goes to the core nearest to its code in Hamming distance, ties to the lower core.
+//   final   rows ascend by (component, core, code, id): one more stable pass over the rows sorted by code, keyed by the
+//           core's place among the cores sorted by (component, core).  No core: every key is 0 and (code, id) stands.
+// Why: lexicographic order alone sends part of a cluster of like rows far away wherever ONE root hyperplane cuts through it
+// (a leading bit flips); tiles then hold fragments of several clusters.  Frequent codes are the clusters' centres in code
+// space, codes near them their cut-off parts.  Integers only, no atomic reaches the order (one counts rows for the
+// MORNA_DEBUG_OPEN line).
+// C3, blocks of 256 rows x 256 tasks the lists leave at the levels with 800 / 1600 / 1936 split nodes: 494 / 650 / 546 by
+// (12-bit code, id) and 407 / 474 / 402 by groups (two rounds of the 256 CUs at every level instead of 2 / 3 / 3), against
+// 640 / 971 / 964 with the rows in id order and 784 / 1372 / 1568 without lists (scripts/active_pairs_probe.py,
+// profiles/split_order_groups_vs_parent.txt).
 // The order changes which products are computed, never a side: tests compare forests with MORNA_SPLIT_ORDER=0.
 #define ORD_BITS 12
 #define ORD_BINS (1 << ORD_BITS)
 #define ORD_BLOCK 256
+#define ORD_GROUP_BITS 24
+#define ORD_MAX_CORES 2048
+#define ORD_MERGE_DIST 2
+#define ORD_SCAN_BLOCK 1024
+#define ORD_MAX_SCAN_BLOCKS 4096   // rows / ORD_SCAN_BLOCK at the most rows the order is made for (2^22)
 
+// stats: [cores, components, rows whose code is a core's]
 __global__ __launch_bounds__(256) void order_key_kernel(const uint8_t *__restrict__ side /* [tree][position = item at the root] */,
-                                                        int64_t n_items, int n_bits, uint16_t *__restrict__ key)
+                                                        int64_t n_items, int n_bits, uint32_t *__restrict__ key, int32_t *__restrict__ stats)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < 3) stats[i] = 0;
     if (i >= n_items) return;
     uint32_t k = 0;
     for (int t = 0; t < n_bits; t++) k = (k << 1) | (side[(int64_t)t * n_items + i] ? 1u : 0u);
-    key[i] = (uint16_t)k;
+    key[i] = k;
 }
 
-__global__ __launch_bounds__(ORD_BLOCK) void order_hist_kernel(const uint16_t *__restrict__ key, int64_t n_items, int32_t n_blocks,
-                                                               int32_t *__restrict__ cnt /* [ORD_BINS][blocks] */)
+// One stable counting-sort pass over the rows src[0 .. n_items) (null: the items in id order) by ORD_BITS bits of val[item]
+__device__ __forceinline__ int order_digit(const uint32_t *__restrict__ val, const int32_t *__restrict__ src, int shift, int64_t pos,
+                                           int32_t *item)
+{
+    const int32_t it = src ? src[pos] : (int32_t)pos;
+    *item = it;
+    return (int)((val[it] >> shift) & (uint32_t)(ORD_BINS - 1));
+}
+
+__global__ __launch_bounds__(ORD_BLOCK) void order_hist_kernel(const uint32_t *__restrict__ val, const int32_t *__restrict__ src, int shift,
+                                                               int64_t n_items, int32_t n_blocks, int32_t *__restrict__ cnt /* [ORD_BINS][blocks] */)
 {
     __shared__ int s_cnt[ORD_BINS];
     for (int k = threadIdx.x; k < ORD_BINS; k += ORD_BLOCK) s_cnt[k] = 0;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * ORD_BLOCK + threadIdx.x;
-    if (i < n_items) atomicAdd(&s_cnt[key[i]], 1);
+    int32_t it;
+    if (i < n_items) atomicAdd(&s_cnt[order_digit(val, src, shift, i, &it)], 1);
     __syncthreads();
     for (int k = threadIdx.x; k < ORD_BINS; k += ORD_BLOCK) cnt[(int64_t)k * n_blocks + blockIdx.x] = s_cnt[k];
 }
@@ -466,21 +503,248 @@ __global__ __launch_bounds__(1024) void order_scan_keys_kernel(int32_t *__restri
     }
 }
 
-__global__ __launch_bounds__(ORD_BLOCK) void order_rank_kernel(const uint16_t *__restrict__ key, int64_t n_items, int32_t n_blocks,
-                                                               const int32_t *__restrict__ cnt, const int32_t *__restrict__ base,
-                                                               int32_t *__restrict__ rank, int32_t *__restrict__ item_at)
+// dst[new row] = item; rank (null but in the last pass): the row of every item
+__global__ __launch_bounds__(ORD_BLOCK) void order_rank_kernel(const uint32_t *__restrict__ val, const int32_t *__restrict__ src, int shift,
+                                                               int64_t n_items, int32_t n_blocks, const int32_t *__restrict__ cnt,
+                                                               const int32_t *__restrict__ base, int32_t *__restrict__ rank,
+                                                               int32_t *__restrict__ dst)
 {
     __shared__ uint16_t s_key[ORD_BLOCK];
     const int64_t i = (int64_t)blockIdx.x * ORD_BLOCK + threadIdx.x;
-    const uint16_t k = i < n_items ? key[i] : (uint16_t)0xFFFF;
+    int32_t it = 0;
+    const uint16_t k = i < n_items ? (uint16_t)order_digit(val, src, shift, i, &it) : (uint16_t)0xFFFF;
     s_key[threadIdx.x] = k;
     __syncthreads();
     if (i >= n_items) return;
-    int same = 0;   // earlier items of the block with the same key
+    int same = 0;   // earlier rows of the block with the same key
     for (int j = 0; j < (int)threadIdx.x; j++) same += s_key[j] == k ? 1 : 0;
     const int32_t r = base[k] + cnt[(int64_t)k * n_blocks + blockIdx.x] + same;
-    rank[i] = r;
-    item_at[r] = (int32_t)i;
+    if (rank) rank[it] = r;
+    dst[r] = it;
+}
+
+// Is the row p of the rows sorted by code the first of a run of at least thr equal codes?  (Sorted: the run reaches row
+// p + thr - 1 exactly when that row's code is the same.)
+__device__ __forceinline__ bool order_core_start(const uint32_t *__restrict__ key, const int32_t *__restrict__ sorted, int64_t n_items,
+                                                 int32_t thr, int64_t p, uint32_t *code)
+{
+    if (p >= n_items) return false;
+    const uint32_t k = key[sorted[p]];
+    *code = k;
+    if (p + thr - 1 >= n_items) return false;
+    if (p > 0 && key[sorted[p - 1]] == k) return false;
+    return key[sorted[p + thr - 1]] == k;
+}
+
+// cores that start in each stretch of ORD_SCAN_BLOCK rows
+__global__ __launch_bounds__(ORD_SCAN_BLOCK) void order_core_count_kernel(const uint32_t *__restrict__ key, const int32_t *__restrict__ sorted,
+                                                                          int64_t n_items, int32_t thr, int32_t *__restrict__ blk_cnt)
+{
+    __shared__ int s_wave[ORD_SCAN_BLOCK / WAVE];
+    uint32_t code;
+    const bool on = order_core_start(key, sorted, n_items, thr, (int64_t)blockIdx.x * ORD_SCAN_BLOCK + threadIdx.x, &code);
+    const uint64_t m = __ballot(on);
+    if ((threadIdx.x & (WAVE - 1)) == 0) s_wave[threadIdx.x / WAVE] = (int)__builtin_popcountll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+        for (int w = 0; w < ORD_SCAN_BLOCK / WAVE; w++) sum += s_wave[w];
+        blk_cnt[blockIdx.x] = sum;
+    }
+}
+
+// core_code[c]: the cores' codes, ascending; stats[0]: how many
+__global__ __launch_bounds__(ORD_SCAN_BLOCK) void order_core_list_kernel(const uint32_t *__restrict__ key, const int32_t *__restrict__ sorted,
+                                                                         int64_t n_items, int32_t thr, const int32_t *__restrict__ blk_cnt,
+                                                                         uint32_t *__restrict__ core_code, int32_t *__restrict__ stats)
+{
+    __shared__ int s_wave[ORD_SCAN_BLOCK / WAVE], s_before[ORD_SCAN_BLOCK / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    // cores of the stretches before this one (at most ORD_MAX_SCAN_BLOCKS of them)
+    int part = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += ORD_SCAN_BLOCK) part += blk_cnt[b];
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, WAVE);
+    if (lane == 0) s_before[w] = part;
+    uint32_t code = 0;
+    const bool on = order_core_start(key, sorted, n_items, thr, (int64_t)blockIdx.x * ORD_SCAN_BLOCK + threadIdx.x, &code);
+    const uint64_t m = __ballot(on);
+    if (lane == 0) s_wave[w] = (int)__builtin_popcountll(m);
+    __syncthreads();
+    int before = 0, here = 0, earlier = 0;   // cores of the stretches before, of this stretch, of its waves before this one
+    for (int k = 0; k < ORD_SCAN_BLOCK / WAVE; k++) {
+        before += s_before[k];
+        here += s_wave[k];
+        if (k < w) earlier += s_wave[k];
+    }
+    const int idx = before + earlier + (int)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    if (on && idx < ORD_MAX_CORES) core_code[idx] = code;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stats[0] = before + here < ORD_MAX_CORES ? before + here : ORD_MAX_CORES;
+}
+
+// The cores' neighbours -- cores whose codes differ in at most ORD_MERGE_DIST bits -- and, further down, their places are
+// counts over all pairs of cores: ORD_PAIR_LANES lanes per core, each with one stretch of the other cores, the lanes' counts
+// put together by shuffles (integer sums in lane order).  nb_cnt[c]: neighbours of core c; nb[c][..]: the first ORD_NB of
+// them, ascending.
+#define ORD_NB 32
+#define ORD_PAIR_LANES 8
+#define ORD_PAIR_GRID (ORD_MAX_CORES * ORD_PAIR_LANES / 256)
+__global__ __launch_bounds__(256) void order_core_nb_kernel(const uint32_t *__restrict__ core_code, const int32_t *__restrict__ stats,
+                                                            int32_t *__restrict__ nb_cnt, uint16_t *__restrict__ nb)
+{
+    __shared__ uint32_t s_code[ORD_MAX_CORES];
+    const int n = stats[0];
+    if ((int)blockIdx.x * (256 / ORD_PAIR_LANES) >= n) return;   // uniform
+    for (int c = threadIdx.x; c < n; c += 256) s_code[c] = core_code[c];
+    __syncthreads();
+    const int c = (int)blockIdx.x * (256 / ORD_PAIR_LANES) + (int)threadIdx.x / ORD_PAIR_LANES, sl = threadIdx.x % ORD_PAIR_LANES;
+    const int per = (n + ORD_PAIR_LANES - 1) / ORD_PAIR_LANES, lo = sl * per, hi = lo + per < n ? lo + per : n;
+    const bool live = c < n;
+    const uint32_t k = live ? s_code[c] : 0u;
+    int mine = 0;
+    if (live)
+        for (int c2 = lo; c2 < hi; c2++) mine += (c2 != c && __builtin_popcount(k ^ s_code[c2]) <= ORD_MERGE_DIST) ? 1 : 0;
+    int incl = mine;   // over the core's lanes, in lane order
+#pragma unroll
+    for (int o = 1; o < ORD_PAIR_LANES; o <<= 1) {
+        const int u = __shfl_up(incl, o, ORD_PAIR_LANES);
+        if (sl >= o) incl += u;
+    }
+    const int total = __shfl(incl, ORD_PAIR_LANES - 1, ORD_PAIR_LANES);
+    if (!live) return;
+    if (sl == 0) nb_cnt[c] = total;
+    int at = incl - mine;
+    if (mine > 0 && at < ORD_NB)
+        for (int c2 = lo; c2 < hi && at < ORD_NB; c2++)
+            if (c2 != c && __builtin_popcount(k ^ s_code[c2]) <= ORD_MERGE_DIST) nb[c * ORD_NB + at++] = (uint16_t)c2;
+}
+
+// One workgroup: label[c] = the smallest core linked to core c through neighbours; stats[1]: components.
+// Every round takes the minimum over the neighbours' labels of the round before (a core with more than ORD_NB neighbours
+// looks at every core) and follows its own label once.  Labels only fall and stay inside the component, so the fixed point
+// is the component's smallest core whatever the number of rounds.
+__global__ __launch_bounds__(1024) void order_components_kernel(const uint32_t *__restrict__ core_code, int32_t *__restrict__ stats,
+                                                                const int32_t *__restrict__ nb_cnt, const uint16_t *__restrict__ nb,
+                                                                int32_t *__restrict__ label)
+{
+    constexpr int PER = ORD_MAX_CORES / 1024;
+    __shared__ uint32_t s_code[ORD_MAX_CORES];
+    __shared__ int s_lab[2][ORD_MAX_CORES];
+    __shared__ int s_changed[2], s_comps;
+    const int n = stats[0];
+    int n_nb[PER];
+    uint32_t my_nb[PER][ORD_NB / 2];   // the core's first neighbours, two to a word, in registers for every round
+    static_assert(ORD_NB % 8 == 0, "neighbours are fetched eight at a time");
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int c = (int)threadIdx.x + u * 1024;
+        n_nb[u] = 0;
+        if (c < n) {
+            s_code[c] = core_code[c];
+            s_lab[0][c] = c;
+            n_nb[u] = nb_cnt[c];
+            const uint4 *src = (const uint4 *)(nb + (size_t)c * ORD_NB);
+#pragma unroll
+            for (int q = 0; q < ORD_NB / 8; q++) {   // (slots past the last neighbour are never looked at)
+                const uint4 v = src[q];
+                my_nb[u][q * 4 + 0] = v.x;
+                my_nb[u][q * 4 + 1] = v.y;
+                my_nb[u][q * 4 + 2] = v.z;
+                my_nb[u][q * 4 + 3] = v.w;
+            }
+        }
+    }
+    if (threadIdx.x == 0) s_changed[0] = s_changed[1] = s_comps = 0;
+    __syncthreads();
+    int cur = 0;
+    for (int round = 0;; round++) {
+        const int *lab = s_lab[cur];
+        int *out = s_lab[cur ^ 1];
+        bool changed = false;
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            const int c = (int)threadIdx.x + u * 1024;
+            if (c >= n) continue;
+            int m = lab[c];
+            if (n_nb[u] > ORD_NB) {
+                const uint32_t k = s_code[c];
+                for (int c2 = 0; c2 < n; c2++)
+                    if (__builtin_popcount(k ^ s_code[c2]) <= ORD_MERGE_DIST) m = lab[c2] < m ? lab[c2] : m;
+            } else {
+#pragma unroll
+                for (int j = 0; j < ORD_NB; j++)
+                    if (j < n_nb[u]) {
+                        const int l = lab[(my_nb[u][j / 2] >> (16 * (j & 1))) & 0xFFFFu];
+                        m = l < m ? l : m;
+                    }
+            }
+            m = lab[m] < m ? lab[m] : m;
+            changed |= m != lab[c];
+            out[c] = m;
+        }
+        if (changed) s_changed[round & 1] = 1;
+        __syncthreads();
+        const bool again = s_changed[round & 1] != 0;
+        if (threadIdx.x == 0) s_changed[(round + 1) & 1] = 0;
+        cur ^= 1;
+        __syncthreads();
+        if (!again) break;   // uniform
+    }
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int c = (int)threadIdx.x + u * 1024;
+        if (c >= n) continue;
+        label[c] = s_lab[cur][c];
+        if (s_lab[cur][c] == c) atomicAdd(&s_comps, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) stats[1] = s_comps;
+}
+
+// place[c] = the core's place among the cores sorted by (label, core)
+__global__ __launch_bounds__(256) void order_core_place_kernel(const int32_t *__restrict__ label, const int32_t *__restrict__ stats,
+                                                               int32_t *__restrict__ place)
+{
+    __shared__ int s_lab[ORD_MAX_CORES];
+    const int n = stats[0];
+    if ((int)blockIdx.x * (256 / ORD_PAIR_LANES) >= n) return;   // uniform
+    for (int c = threadIdx.x; c < n; c += 256) s_lab[c] = label[c];
+    __syncthreads();
+    const int c = (int)blockIdx.x * (256 / ORD_PAIR_LANES) + (int)threadIdx.x / ORD_PAIR_LANES, sl = threadIdx.x % ORD_PAIR_LANES;
+    const int per = (n + ORD_PAIR_LANES - 1) / ORD_PAIR_LANES, lo = sl * per, hi = lo + per < n ? lo + per : n;
+    int before = 0;
+    if (c < n) {
+        const int l = s_lab[c];
+        for (int c2 = lo; c2 < hi; c2++) before += (s_lab[c2] < l || (s_lab[c2] == l && c2 < c)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = ORD_PAIR_LANES / 2; o > 0; o >>= 1) before += __shfl_xor(before, o, ORD_PAIR_LANES);
+    if (c < n && sl == 0) place[c] = before;
+}
+
+// group[item] = the place of the core nearest to the item's code (ties: the lower core); no core: 0
+__global__ __launch_bounds__(256) void order_assign_kernel(const uint32_t *__restrict__ key, int64_t n_items, const uint32_t *__restrict__ core_code,
+                                                           const int32_t *__restrict__ place, int32_t *__restrict__ stats,
+                                                           uint32_t *__restrict__ group)
+{
+    __shared__ uint32_t s_code[ORD_MAX_CORES];
+    const int n = stats[0];
+    for (int c = threadIdx.x; c < n; c += 256) s_code[c] = core_code[c];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool in_core = false;
+    if (i < n_items) {
+        const uint32_t k = key[i];
+        uint32_t best = 0xFFFFFFFFu;   // (distance, core)
+        for (int c = 0; c < n; c++) {
+            const uint32_t v = ((uint32_t)__builtin_popcount(k ^ s_code[c]) << 12) | (uint32_t)c;
+            best = v < best ? v : best;
+        }
+        group[i] = n > 0 ? (uint32_t)place[best & 0xFFFu] : 0u;
+        in_core = n > 0 && (best >> 12) == 0;
+    }
+    const uint64_t m = __ballot(in_core);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&stats[2], (int)__builtin_popcountll(m));   // for the debug line only
 }
 
 // ---- where every row stands in every tree ---------------------------------------------------------------------------
@@ -547,37 +811,132 @@ int split_mm_level_inv(morna_index *h, const InvSeg *d_segs, int32_t n_segs, int
 // a lane of the contraction fetches its row's address through item_at once (a copy of the image in row order cost 0.17 ms
 // of HBM time beside the second level's two_means).  From here on `inv` is by row: the caller fills *inv_out with
 // split_mm_level_inv behind split_mm_order_rows, on the same stream.
+// The table, in int32 words: the counting sort's [ORD_BINS][blocks] counts, [ORD_BINS] bases, the codes [N], the rows sorted
+// by code [N], the key of the last pass [N], the cores' codes, places, labels, neighbour counts [ORD_MAX_CORES] each and
+// neighbours [ORD_MAX_CORES][ORD_NB] (16 bits), the cores per stretch of ORD_SCAN_BLOCK rows, the three numbers of the debug line
+struct OrderTable {
+    int32_t *cnt = nullptr, *base = nullptr, *sorted = nullptr, *place = nullptr, *label = nullptr, *nb_cnt = nullptr, *blk_cnt = nullptr,
+            *stats = nullptr;
+    uint32_t *key = nullptr, *group = nullptr, *core_code = nullptr;
+    uint16_t *nb = nullptr;
+    int32_t n_blocks, n_scan;
+    size_t words;
+    OrderTable(int32_t *p, int64_t N)
+    {
+        n_blocks = (int32_t)((N + ORD_BLOCK - 1) / ORD_BLOCK);
+        n_scan = (int32_t)((N + ORD_SCAN_BLOCK - 1) / ORD_SCAN_BLOCK);
+        const size_t o_base = (size_t)n_blocks * ORD_BINS, o_key = o_base + ORD_BINS, o_sorted = o_key + (size_t)N,
+                     o_group = o_sorted + (size_t)N, o_code = (o_group + (size_t)N + 3) / 4 * 4 /* 16-byte rows of nb */, o_place = o_code + ORD_MAX_CORES,
+                     o_label = o_place + ORD_MAX_CORES, o_nbc = o_label + ORD_MAX_CORES, o_nb = o_nbc + ORD_MAX_CORES,
+                     o_blk = o_nb + ORD_MAX_CORES * ORD_NB / 2, o_stats = o_blk + (size_t)n_scan;
+        words = o_stats + 4;
+        if (!p) return;   // the size alone
+        cnt = p;
+        base = p + o_base;
+        key = (uint32_t *)(p + o_key);
+        sorted = p + o_sorted;
+        group = (uint32_t *)(p + o_group);
+        core_code = (uint32_t *)(p + o_code);
+        place = p + o_place;
+        label = p + o_label;
+        nb_cnt = p + o_nbc;
+        nb = (uint16_t *)(p + o_nb);
+        blk_cnt = p + o_blk;
+        stats = p + o_stats;
+    }
+};
+
+bool split_mm_order_by_groups()
+{
+    static const bool on = env_on("MORNA_SPLIT_ORDER_GROUPS");
+    return on;
+}
+
 int split_mm_order_begin(morna_index *h, int32_t n_trees, const int32_t **rank_out, int32_t **inv_out)
 {
     const int64_t N = h->n_items;
     DevBuf<int32_t> &maps = h->splitmm.maps, &invr = h->splitmm.invr, &table = h->splitmm.table;
-    const int32_t n_blocks = (int32_t)((N + ORD_BLOCK - 1) / ORD_BLOCK);
     MORNA_TRY(maps.alloc((size_t)N * 2));
     MORNA_TRY(invr.alloc((size_t)n_trees * N));
-    MORNA_TRY(table.alloc((size_t)n_blocks * ORD_BINS + ORD_BINS + (size_t)(N + 1) / 2));
+    MORNA_TRY(table.alloc(OrderTable(nullptr, N).words));
     h->splitmm.ord_valid = true;
+    h->splitmm.ord_line_due = true;
     *rank_out = maps.p;
     *inv_out = invr.p;
     return MORNA_OK;
 }
 
-// the sort itself, enqueued on `stream` (the side stream, under the second level's two_means); after split_mm_order_begin
+// one stable pass by ORD_BITS bits of val[item] over the rows src (null: the items by id) into dst (and rank, if given)
+static void order_pass(const OrderTable &t, const uint32_t *val, const int32_t *src, int shift, int64_t N, int32_t *rank, int32_t *dst,
+                       hipStream_t stream)
+{
+    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)t.n_blocks), dim3(ORD_BLOCK), 0, stream, val, src, shift, N, t.n_blocks, t.cnt);
+    hipLaunchKernelGGL(order_scan_bins_kernel, dim3(ORD_BINS / 4), dim3(256), 0, stream, t.cnt, t.n_blocks, t.base);
+    hipLaunchKernelGGL(order_scan_keys_kernel, dim3(1), dim3(1024), 0, stream, t.base);
+    hipLaunchKernelGGL(order_rank_kernel, dim3((unsigned)t.n_blocks), dim3(ORD_BLOCK), 0, stream, val, src, shift, N, t.n_blocks, t.cnt, t.base,
+                       rank, dst);
+}
+
+// the order itself, enqueued on `stream` (the side stream, under the second level's two_means); after split_mm_order_begin
 int split_mm_order_rows(morna_index *h, const uint8_t *side, int32_t n_trees, hipStream_t stream)
 {
     const int64_t N = h->n_items;
-    DevBuf<int32_t> &maps = h->splitmm.maps, &table = h->splitmm.table;
-    const int32_t n_blocks = (int32_t)((N + ORD_BLOCK - 1) / ORD_BLOCK);
-    int32_t *key_base = table.p + (size_t)n_blocks * ORD_BINS;   // [ORD_BINS] items with a smaller key
-    uint16_t *key = (uint16_t *)(key_base + ORD_BINS);
-    int32_t *rank = maps.p, *item_at = maps.p + N;
-    const int n_bits = n_trees < ORD_BITS ? n_trees : ORD_BITS;
-    hipLaunchKernelGGL(order_key_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, side, N, n_bits, key);
-    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)n_blocks), dim3(ORD_BLOCK), 0, stream, key, N, n_blocks, table.p);
-    hipLaunchKernelGGL(order_scan_bins_kernel, dim3(ORD_BINS / 4), dim3(256), 0, stream, table.p, n_blocks, key_base);
-    hipLaunchKernelGGL(order_scan_keys_kernel, dim3(1), dim3(1024), 0, stream, key_base);
-    hipLaunchKernelGGL(order_rank_kernel, dim3((unsigned)n_blocks), dim3(ORD_BLOCK), 0, stream, key, N, n_blocks, table.p, key_base, rank,
-                       item_at);
+    if (N > (int64_t)ORD_MAX_SCAN_BLOCKS * ORD_SCAN_BLOCK) {
+        set_error("split_mm_order_rows: %lld rows", (long long)N);
+        return MORNA_E_INVALID;
+    }
+    const OrderTable t(h->splitmm.table.p, N);
+    int32_t *rank = h->splitmm.maps.p, *item_at = h->splitmm.maps.p + N;
+    const bool groups = split_mm_order_by_groups();
+    const int max_bits = groups ? ORD_GROUP_BITS : ORD_BITS;
+    const int n_bits = n_trees < max_bits ? n_trees : max_bits;
+    h->splitmm.ord_bits = n_bits;
+    hipLaunchKernelGGL(order_key_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, side, N, n_bits, t.key, t.stats);
+    if (!groups) {
+        order_pass(t, t.key, nullptr, 0, N, rank, item_at, stream);
+        HIP_TRY(hipGetLastError());
+        return MORNA_OK;
+    }
+    // rows by (code, id) into t.sorted: least significant digit first (item_at is free until the last pass)
+    if (n_bits > ORD_BITS) {
+        order_pass(t, t.key, nullptr, 0, N, nullptr, item_at, stream);
+        order_pass(t, t.key, item_at, ORD_BITS, N, nullptr, t.sorted, stream);
+    } else
+        order_pass(t, t.key, nullptr, 0, N, nullptr, t.sorted, stream);
+    const int32_t thr = (int32_t)std::max<int64_t>(16, (N + ORD_MAX_CORES - 1) / ORD_MAX_CORES);
+    hipLaunchKernelGGL(order_core_count_kernel, dim3((unsigned)t.n_scan), dim3(ORD_SCAN_BLOCK), 0, stream, t.key, t.sorted, N, thr, t.blk_cnt);
+    hipLaunchKernelGGL(order_core_list_kernel, dim3((unsigned)t.n_scan), dim3(ORD_SCAN_BLOCK), 0, stream, t.key, t.sorted, N, thr, t.blk_cnt,
+                       t.core_code, t.stats);
+    hipLaunchKernelGGL(order_core_nb_kernel, dim3(ORD_PAIR_GRID), dim3(256), 0, stream, t.core_code, t.stats, t.nb_cnt, t.nb);
+    hipLaunchKernelGGL(order_components_kernel, dim3(1), dim3(1024), 0, stream, t.core_code, t.stats, t.nb_cnt, t.nb, t.label);
+    hipLaunchKernelGGL(order_core_place_kernel, dim3(ORD_PAIR_GRID), dim3(256), 0, stream, t.label, t.stats, t.place);
+    hipLaunchKernelGGL(order_assign_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, t.key, N, t.core_code, t.place, t.stats,
+                       t.group);
+    order_pass(t, t.group, t.sorted, 0, N, rank, item_at, stream);
     HIP_TRY(hipGetLastError());
+    return MORNA_OK;
+}
+
+// MORNA_DEBUG_OPEN=1, once per build behind the level the order was made under (the caller has waited for that level)
+static int split_mm_order_line(morna_index *h)
+{
+    if (!h->splitmm.ord_valid || !h->splitmm.ord_line_due) return MORNA_OK;
+    h->splitmm.ord_line_due = false;
+    int32_t st[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(st, OrderTable(h->splitmm.table.p, h->n_items).stats, sizeof(st), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[morna] split order: bits=%d cores=%d components=%d rows_in_cores=%d\n", h->splitmm.ord_bits, (int)st[0], (int)st[1],
+            (int)st[2]);
+    return MORNA_OK;
+}
+
+// item_at of the order the last build made its rows in (tests, scripts/active_pairs_probe.py)
+int split_mm_order_read(morna_index *h, int32_t *item_at)
+{
+    if (!h->built || !h->splitmm.ord_valid || !h->splitmm.maps.p) {
+        set_error("split order: the last build did not order its rows");
+        return MORNA_E_STATE;
+    }
+    HIP_TRY(hipMemcpy(item_at, h->splitmm.maps.p + h->n_items, (size_t)h->n_items * 4, hipMemcpyDeviceToHost));
     return MORNA_OK;
 }
 
@@ -742,6 +1101,7 @@ int split_mm_level(morna_index *h, const SplitTask *d_tasks, int32_t n_tasks, in
         fprintf(stderr, "[morna] split_mm path: split nodes=%d tiles=%d lists=%s image=%s inv=%s rows=%s level=%d\n", n_tasks, big ? 256 : 128,
                 !lists ? "none" : lists_ready ? "ahead" : "inline", image_from ? image_from : "converted", inv_from,
                 ord ? "ordered" : "ids", (int)level);
+        MORNA_TRY(split_mm_order_line(h));
     }
     return MORNA_OK;
 }

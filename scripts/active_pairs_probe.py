@@ -4,7 +4,9 @@
 The split contraction (splitmm.hip) multiplies every tile of 256 rows with every split node of the level, although a row
 belongs to ONE node per tree.  If the rows of a tile lie in few nodes of every tree (rows ordered so that similar rows are
 neighbours), most (tile, node) blocks hold no pair that is needed.  This script builds the C3 forest, reads it back and
-counts, per level and per row ordering, the node columns a tile really needs, in chunks of CH columns.
+counts, per level and per row ordering, the node columns a tile really needs, in chunks of CH columns.  "L1:library" is the
+order the library itself made its rows in under the second level (AnnoyIndex.split_order(): by groups of like root-side
+codes, or with MORNA_SPLIT_ORDER_GROUPS=0 by the 12-bit code alone, which is "L1:tree0..11").
 
     python scripts/active_pairs_probe.py [--samples 50000] [--trees 200]
 """
@@ -41,6 +43,7 @@ def main():
     idx.build_features(N)
     idx.build(a.trees, seed=0)
     f = idx.get_forest()
+    lib_order = idx.split_order()   # None: the build did not order its rows
     rec, perm = f["node_rec"], f["perm"]
     T = perm.shape[0]
     n_nodes = rec.shape[0]
@@ -59,7 +62,8 @@ def main():
         frontier = frontier[frontier >= 0]
         lv += 1
     n_levels = lv
-    out = {"N": int(N), "T": int(T), "tile": a.tile, "levels": []}
+    out = {"N": int(N), "T": int(T), "tile": a.tile, "levels": [],
+           "library_order": None if lib_order is None else "groups" if os.environ.get("MORNA_SPLIT_ORDER_GROUPS", "1") != "0" else "12-bit code"}
     # node_of[L][t][row]: the split node of level L the row is in (or -1)
     n_tiles = (N + a.tile - 1) // a.tile
     fixed = {}
@@ -95,6 +99,8 @@ def main():
             for t in range(12):
                 k12 = k12 * 32 + (node_of[t] + 1)
             fixed["L%d:tree0..11" % L] = np.argsort(k12, kind="stable")
+        if L == 1 and lib_order is not None:
+            fixed["L1:library"] = lib_order.astype(np.int64)
         lvl = {"level": L, "split_nodes": int(S), "dense_blocks_256": int(n_tiles * ((S + 255) // 256)), "orders": {}}
         for name, order in orders.items():
             rank = np.empty(N, np.int64)
