@@ -566,6 +566,51 @@ int morna_label_sums(morna_index *h, const morna_restriction *r /* or NULL: unre
 int morna_label_sums_stats(const morna_index *h, double *stats /* [6] */);
 
 /*
+ * ---- radius search (no counterpart in the reference, which only answers "the k nearest") -------------
+ * Every item within the distance `radius` of a query.  The distance is the one morna_exact_search returns: sqrt(2 - 2cos) in
+ * fp64, accumulated in the reference's sequential order (cosine_distance, morna.py:101-114).
+ *   The answer for query q and radius r (fp64, finite, 0 <= r): the list morna_exact_search returns for q with k = n_items,
+ *     cut after the last entry whose distance is <= r, compared in fp64, inclusive: the same ids, bit-identical distances,
+ *     the same tie order (equal distance: higher id first).  r >= 2 returns every evaluated row.  r < 0, NaN or inf:
+ *     MORNA_E_INVALID.
+ *   count -1: some evaluated row gives a NaN distance, i.e. the reference raises for q.  Such a row has a scan value of
+ *     about 0 and is a candidate for every r >= 0.  The list is still filled, for diagnosis: NaN entries last, by ascending id.
+ *   r (the restriction) may be NULL: every item is eligible.  Else the answer is taken on the eligible set E(q) of the
+ *     restricted search; q_group as there (q_group without a restriction that holds the items' groups: MORNA_E_INVALID).
+ *   after ([nq] or NULL): only items with id > after[q].  Neither ineligible items nor items at or below the bound are
+ *     evaluated: a near-parallel row among them does not fail the query.
+ *   Pairs: every unordered pair {i, j} of stored rows with d(i, j) <= r is the search by item over all items with
+ *     after[q] = items[q].  d is symmetric bit for bit (pq and pp qq are sums and products of the same terms in the same
+ *     order either way).  A pair whose fp64 radicand is negative has the distance NaN and belongs to the result for every r;
+ *     its query has count -1.  (The reference would raise for the whole query; a caller that looks for duplicates must not
+ *     lose exactly these.)
+ *   Queries: q ([nq][dim] fp64), or items ([nq] stored rows), or both NULL: the staged query rows of morna_build_query_rows
+ *     (nq must be their count).  q and items: MORNA_E_INVALID.
+ *   Domain, as morna_exact_search: rows outside the scan's domain are candidates of every query and get the reference's
+ *     value; a query whose fp64 sum of squares lies outside [2^-900, 2^890] is compared with every row; a host query with a
+ *     non-finite element or sum of squares: MORNA_E_INVALID; a row-sharded handle (morna_comm_init): MORNA_E_INVALID.
+ *   Window: a row is a candidate iff its fp32 scan value v <= fl_up((float)(r * r)) + the scan's error bound (stats[7]); every
+ *     candidate is then evaluated in fp64.  Queries are taken in batches (scan values of a batch: at most 2 GiB;
+ *     MORNA_RADIUS_BATCH=<queries> in the environment caps a batch further).  The answer does not depend on the batch, the
+ *     grid or which scan ran.  More than 2^31 - 1 result entries in one call: MORNA_E_INVALID naming the total.
+ *   morna_radius_counts  count_out[nq]: the length of every list, or -1
+ *   morna_radius_query   borrowed views of list q, valid until morna_radius_free: ids[len], dist[len], ordered (len is the
+ *                        list's length also where the count is -1).  The lists lie one after the other in query order:
+ *                        list q + 1 begins where list q ends, in both arrays
+ *   morna_exact_radius_stats  of the last call, stats[8]: scan ms (staging and scan kernels, HIP events), selection ms (count,
+ *     offsets and write kernels), distance ms (the fp64 pass and the ordering on the device), queries, batches, candidates
+ *     (fp64 chains run), result entries, the window used (the largest over the batches).  All 0 after a call that failed.
+ */
+typedef struct morna_radius morna_radius;
+int morna_exact_radius(morna_index *h, const morna_restriction *r /* or NULL */, const double *q, const int32_t *items,
+                       int64_t nq, const int32_t *q_group /* [nq] or NULL */, const int32_t *after /* [nq] or NULL */,
+                       double radius, morna_radius **out);
+int morna_radius_counts(const morna_radius *r, int64_t *count_out /* [nq] */);
+int morna_radius_query(const morna_radius *r, int64_t q, const int32_t **ids, const double **dist, int64_t *len);
+int morna_radius_free(morna_radius *r);
+int morna_exact_radius_stats(const morna_index *h, double *stats /* [8] */);
+
+/*
  * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
  * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
  * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the

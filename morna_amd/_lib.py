@@ -119,6 +119,11 @@ SIGNATURES = {
     "morna_exact_search_restricted": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _p, _p, _p]),
     "morna_label_sums": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _p, _p]),
     "morna_label_sums_stats": (C.c_int, [_p, _p]),
+    "morna_exact_radius": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, C.c_double, C.POINTER(_p)]),
+    "morna_radius_counts": (C.c_int, [_p, _p]),
+    "morna_radius_query": (C.c_int, [_p, _i64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64)]),
+    "morna_radius_free": (C.c_int, [_p]),
+    "morna_exact_radius_stats": (C.c_int, [_p, _p]),
     "morna_get_nns_prefix":(C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -469,6 +469,70 @@ class AnnoyIndex(object):
         return dict(scan_ms=float(stats[0]), sums_ms=float(stats[1]), queries=int(stats[2]), batches=int(stats[3]),
                     counted=int(stats[4]), scan_eps=float(stats[5]))
 
+    # ---- radius search (include/morna_hip.h, "radius search"; no counterpart in annoy) ----
+    def exact_radius(self, radius, Q=None, items=None, restriction=None, query_groups=None, after=None):
+        """Every item within the exact fp64 distance `radius` of every query: (lists, counts).  lists[q] is (ids int32,
+        dist float64) in the order of exact_search_batch (distance ascending, equal distance: higher id first); counts int64
+        [nq] is the list's length, or -1 where the reference would raise (the list then ends with its NaN entries).
+        Queries: Q (fp64 [nq, f]), items (stored rows), or neither: the staged query rows.  restriction / query_groups: as
+        exact_search_restricted; None: every item is eligible.  after: int32 [nq], only items with id > after[q]."""
+        if restriction is not None:
+            Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
+        else:
+            if query_groups is not None:
+                raise ValueError("query groups need a restriction made with groups")
+            if Q is not None and items is not None:
+                raise ValueError("give query vectors or items, not both")
+            if Q is not None:
+                Q = np.ascontiguousarray(Q, dtype=np.float64)
+                if Q.ndim != 2 or Q.shape[1] != self.f:
+                    raise IndexError("queries must be [nq, %d]" % self.f)
+                nq = Q.shape[0]
+            elif items is not None:
+                items = np.ascontiguousarray(items, dtype=np.int32)
+                if items.ndim != 1:
+                    raise ValueError("items must be one-dimensional")
+                nq = items.shape[0]
+            else:
+                nq = getattr(self, "_qrows_n", 0)
+        if after is not None:
+            after = np.ascontiguousarray(after, dtype=np.int32)
+            if after.shape != (nq,):
+                raise ValueError("after must hold one id per query (%d), got shape %r" % (nq, after.shape))
+        r = C.c_void_p()
+        check(lib().morna_exact_radius(self._h, restriction._p if restriction is not None else None, ptr(Q), ptr(items), nq,
+                                       ptr(query_groups), ptr(after), float(radius), C.byref(r)))
+        try:
+            counts = np.zeros(nq, np.int64)
+            check(lib().morna_radius_counts(r, ptr(counts)))
+            # the lists lie one after the other in the result object: one copy of each array, then views per query.  A list's
+            # length is its count, except where the count is -1 (asked for, query by query: they are few)
+            pi, pd, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+            lens = counts.copy()
+            for q in np.nonzero(counts < 0)[0].tolist():
+                check(lib().morna_radius_query(r, q, C.byref(pi), C.byref(pd), C.byref(n)))
+                lens[q] = n.value
+            off = np.zeros(nq + 1, np.int64)
+            np.cumsum(lens, out=off[1:])
+            total = int(off[-1])
+            ids, dist = np.zeros(0, np.int32), np.zeros(0, np.float64)
+            if total:
+                check(lib().morna_radius_query(r, 0, C.byref(pi), C.byref(pd), C.byref(n)))
+                ids = np.ctypeslib.as_array(C.cast(pi, C.POINTER(C.c_int32)), shape=(total,)).copy()
+                dist = np.ctypeslib.as_array(C.cast(pd, C.POINTER(C.c_double)), shape=(total,)).copy()
+            off = off.tolist()
+            return [(ids[off[q]:off[q + 1]], dist[off[q]:off[q + 1]]) for q in range(nq)], counts
+        finally:
+            lib().morna_radius_free(r)
+
+    def exact_radius_stats(self):
+        """Of the last exact_radius: scan ms, selection ms, distance ms, queries, batches, candidates (fp64 chains run),
+        result entries, the window the scan values were compared with."""
+        stats = np.zeros(8, np.float64)
+        check(lib().morna_exact_radius_stats(self._h, ptr(stats)))
+        return dict(scan_ms=float(stats[0]), select_ms=float(stats[1]), dist_ms=float(stats[2]), queries=int(stats[3]),
+                    batches=int(stats[4]), candidates=int(stats[5]), results=int(stats[6]), window=float(stats[7]))
+
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):
         """Rows of the query samples of `terms` (index.ParsedLines from ParsedLines.query_terms) on this handle, beside the

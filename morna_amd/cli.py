@@ -99,6 +99,8 @@ here do the latter.
     python -m morna_amd.cli hashing -x idx --junction-file junctions.tsv.gz --sample 100 -r 20 --features 500,1000,3000,8192,index
     python -m morna_amd.cli labels -x idx --labels tissues.tsv --all --matrix --summary-only
     python -m morna_amd.cli labels -x idx --labels tissues.tsv --intropolis new_samples.tsv.gz --top 3
+    python -m morna_amd.cli search -x idx -e --max-distance 0.15 --query-ids 17,42 -d
+    python -m morna_amd.cli pairs -x idx --max-distance 0.05 --leave-out-groups donors.tsv --clusters
 """
 import argparse
 import sys
@@ -138,7 +140,7 @@ def add_search_parameters(subparser):
                            help='search for nearest neighbors to the sample already in the index with this sample id')
     subparser.add_argument('-e', '--exact', action='store_const', const=True, default=False,
                            help='exact nearest neighbor search within the morna index')
-    subparser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20,
+    subparser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20, action=_StoreGiven,
                            help='the number of nearest neighbor results to return')
     subparser.add_argument('-rl', '--rawlist', action='store_const', const=True, default=False,
                            help='regurgitate junction list for input sample instead of performing search')
@@ -232,10 +234,14 @@ def build_parser():
                                help='search with the first <int> trees of the index only: the answer of an index built with '
                                     '--n-trees <int> from the same file (approximate search on an index without row shards; '
                                     'not with -e, --unhashed, --within, --without or --leave-out-groups)')
+    search_parser.add_argument('--max-distance', metavar='<float>', type=str, required=False, default=None,
+                               help='with -e: every sample within this exact distance of the query instead of the -r nearest, '
+                                    'in the format of the -e output (an explicit -r caps the list); for -q and --query-ids the '
+                                    'exact search by sample (not with --unhashed, --use-trees, -c or an index of row shards)')
     junctions_parser = subparsers.add_parser('junctions', help='searches a morna index and pools the junctions of the '
                                                                'results for a second alignment pass')
     add_search_parameters(junctions_parser)                    # morna.py:1023
-    junctions_parser.set_defaults(unhashed_junction_file=None, use_trees=None)   # (search's --junction-file: the unhashed search's; not this one; --use-trees is search's alone)
+    junctions_parser.set_defaults(unhashed_junction_file=None, use_trees=None, max_distance=None)   # (search's --junction-file: the unhashed search's; not this one; --use-trees is search's alone)
     junctions_parser.add_argument('-i', '--index', metavar='<idx>', type=str, required=False, default=None,
                                   help='accepted for compatibility and ignored (the aligner\'s index; morna.py:1025)')
     junctions_parser.add_argument('-p1', '--pass1-sam', metavar='<sam>', type=str, required=False, default="pass1.sam",
@@ -255,7 +261,7 @@ def build_parser():
                                                              'filters, how many of a query\'s true junctions its results '
                                                              'give back')
     add_search_parameters(recovery_parser)
-    recovery_parser.set_defaults(unhashed_junction_file=None, use_trees=None)
+    recovery_parser.set_defaults(unhashed_junction_file=None, use_trees=None, max_distance=None)
     recovery_parser.add_argument('--grid', type=str, required=False, default=None,
                                  help='the filters to tabulate, "<f1>,<f2>,...:<c1>,<c2>,...": every frequency with every '
                                       'coverage (at most 15 coverages); default 0,.05,.1,.2,.3,.5,.75,1:1,2,3,5,10,20,50,1000')
@@ -383,7 +389,77 @@ def build_parser():
     super_parser.add_argument('-o', '--output', type=str, metavar='<file>', required=True,
                               help='output file: "chrom start end sum" for every line of --junction-file')
     super_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    pairs_parser = subparsers.add_parser('pairs', help='lists every pair of indexed samples within a distance of each other '
+                                                       '(re-submitted runs, replicates, one library under two accessions), '
+                                                       'from one exact scan of the index')
+    pairs_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                              help='path to junction index basename (an index without row shards)')
+    pairs_parser.add_argument('--max-distance', metavar='<float>', type=str, required=True,
+                              help='report the pairs at most this exact distance apart')
+    pairs_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                              help='pair only the samples this file lists, one integer sample id per line')
+    pairs_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                              help='never pair a sample this file lists, one integer sample id per line')
+    pairs_parser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
+                              help='a groups file, "<label><TAB><id>,<id>,..." per line: never pair two samples of one group '
+                                   '(the expected pairs -- one donor, one study -- stay silent, the unexpected ones remain)')
+    pairs_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
+                              help='append both samples\' metadata keywords to every line')
+    pairs_parser.add_argument('--clusters', action='store_const', const=True, default=False,
+                              help='append one line per connected component of the pairs, largest first')
+    pairs_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                              help='print only the summary line (and the clusters with --clusters)')
+    pairs_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     return parser
+
+
+def _check_max_distance_flags(parser, args):
+    """search --max-distance: the exact, hashed search of an index without row shards; leaves the distance in
+    args.max_distance (None without the flag)."""
+    if getattr(args, "max_distance", None) is None:
+        return
+    import os
+    from .search import RADIUS_SHARDS_REFUSAL, parse_max_distance
+    try:
+        args.max_distance = parse_max_distance(args.max_distance)
+    except ValueError as e:
+        parser.error(str(e))
+    if not args.exact:
+        parser.error("--max-distance cannot be used without -e/--exact: the distance is the exact search's")
+    for flag, on in (("--unhashed", args.unhashed), ("--use-trees", getattr(args, "use_trees", None) is not None),
+                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
+        if on:
+            parser.error("--max-distance cannot be used with %s" % flag)
+    if args.results < 1:
+        parser.error("-r takes a positive number of results (got %d)" % args.results)
+    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        parser.error(RADIUS_SHARDS_REFUSAL)
+
+
+def _check_pairs_flags(parser, args):
+    """`pairs`: the distance and the restriction's files, checked against each other; argparse errors, before any index is
+    read.  Leaves the restriction's parts where _check_restriction_flags leaves them."""
+    from .junctions import parse_groups_file, parse_sample_ids_file
+    from .search import parse_max_distance
+    try:
+        args.max_distance = parse_max_distance(args.max_distance)
+    except ValueError as e:
+        parser.error(str(e))
+    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
+    args.query_id = args.query_ids = None
+    try:
+        if args.within is not None:
+            args.within_ids = parse_sample_ids_file(args.within)
+        if args.without is not None:
+            args.without_ids = parse_sample_ids_file(args.without)
+        if args.leave_out_groups is not None:
+            args.leave_out = parse_groups_file(args.leave_out_groups)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+    if args.within_ids is not None and args.without_ids is not None:
+        both = sorted(set(args.within_ids) & set(args.without_ids))
+        if both:
+            parser.error("--within and --without both name sample id %d" % both[0])
 
 
 def _check_downsample_flags(parser, args):
@@ -741,6 +817,9 @@ def main(argv=None, stdin=None, stdout=None):
         _check_restriction_flags(parser, args)
     if args.subparser_name == 'search':
         _check_use_trees_flags(parser, args)
+        _check_max_distance_flags(parser, args)
+    if args.subparser_name == 'pairs':
+        _check_pairs_flags(parser, args)
     if args.subparser_name == 'recall':
         _check_recall_flags(parser, args)
     if args.subparser_name == 'hashing':
@@ -770,6 +849,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _hashing(args, stdout)
     if args.subparser_name == 'labels':
         return _labels(args, stdin, stdout)
+    if args.subparser_name == 'pairs':
+        return _pairs(args, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -982,6 +1063,61 @@ def _labels(args, stdin, stdout):
     return 0
 
 
+def _pairs(args, stdout):
+    """`pairs`: one radius search by item over the whole index on the GPU, every sample bounded to the ids above its own; a
+    line per pair, the summary line and, with --clusters, a line per connected component."""
+    import os
+    from .metadb import lookup_meta
+    from .search import (RADIUS_SHARDS_REFUSAL, MornaSearch, format_cluster_line, format_pair_line, format_pairs_summary,
+                         pair_clusters)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(RADIUS_SHARDS_REFUSAL)
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    args.restriction = _make_restriction(args, searcher)
+    pairs = searcher.sample_pairs(args.max_distance, restriction=args.restriction)
+    clusters = pair_clusters(pairs)
+    if not args.summary_only:
+        meta = {}
+        if args.metadata:
+            ids = sorted(set(i for p in pairs for i in p[:2]))
+            # (a 1-tuple with the rest of the sample's metafile line, newline included, or None: metadb.lookup_meta)
+            meta = dict((i, m[0].strip() if m else "-") for i, m in zip(ids, lookup_meta(args.basename, ids)))
+        for a, b, d in pairs:
+            stdout.write(format_pair_line(a, b, d, (meta[a], meta[b]) if args.metadata else None))
+    n_samples = searcher.annoy_index.get_n_items() if args.restriction is None else args.restriction.n_allowed
+    stdout.write(format_pairs_summary(n_samples, pairs, clusters))
+    if args.clusters:
+        for c in clusters:
+            stdout.write(format_cluster_line(c))
+    return 0
+
+
+def _max_distance(args):
+    """search --max-distance; None without it (and for the commands that do not take it)."""
+    return getattr(args, "max_distance", None)
+
+
+def _radius_cap(args):
+    """-r under --max-distance: a cap when it was given on the command line, None otherwise."""
+    return args.results if getattr(args, "results_given", False) else None
+
+
+def _write_blocks(stdout, labels, results, header, collect=None):
+    """One block per query: header(label), then the result lines or "# error: ..."; 1 when some query failed."""
+    from .search import results_output
+    failed = False
+    for label, res in zip(labels, results):
+        header(label)
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+        else:
+            results_output(res, stdout)
+            if collect is not None:
+                collect.append((label, res))
+    return 1 if failed else 0
+
+
 def _stream_parser(fmt):
     """The generator of junctions for -f sam / bed / raw."""
     from . import streams
@@ -1111,7 +1247,11 @@ def _downsample_search(args, searcher, n_results, junction_file):
                                                     include_distances=args.distances, meta_db=args.metadata, restriction=r)
     else:
         batch = searcher.queries_from_thinned(thinned, junction_file)
-        if args.exact:
+        if _max_distance(args) is not None:
+            results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
+                                                     meta_db=args.metadata, restriction=r, query_groups=own,
+                                                     num_neighbors=_radius_cap(args))
+        elif args.exact:
             results = searcher.exact_search_nn_batch(batch, n_results, include_distances=args.distances, meta_db=args.metadata,
                                                      restriction=r, query_groups=own)
         else:
@@ -1214,7 +1354,11 @@ def _search_supersamples(args, searcher, stdout):
                                                     restriction=_restriction(args))
     else:
         batch = searcher.queries_from_pooled(pooled, labels, args.unhashed_junction_file)
-        if args.exact:
+        if _max_distance(args) is not None:
+            results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
+                                                     meta_db=args.metadata, restriction=_restriction(args),
+                                                     num_neighbors=_radius_cap(args))
+        elif args.exact:
             results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
                                                      restriction=_restriction(args))
         else:
@@ -1265,11 +1409,23 @@ def _search_unhashed(args, searcher, stdin, stdout):
     return 0
 
 
+def _search_radius_members(args, searcher, stdout, query_ids, numbered, collect=None):
+    """-q / --query-ids under --max-distance: the header lines of the by-sample search, then every sample within the
+    distance of the stored row, exactly (the query itself leads its list unless --leave-out-groups leaves it out)."""
+    results = searcher.exact_radius_nn_batch(query_ids, _max_distance(args), include_distances=args.distances,
+                                             meta_db=args.metadata, restriction=_restriction(args),
+                                             num_neighbors=_radius_cap(args))
+    return _write_blocks(stdout, query_ids, results,
+                         lambda query_id: _write_member_header(stdout, query_id, searcher.internal_id_map[query_id], numbered), collect)
+
+
 def _search_batch(args, searcher, stdout, collect=None):
     """--intropolis / --query-ids: one block per query, in query order; 1 when some exact query failed as the
     reference's would (math domain error), after all blocks.  collect: a list that receives (sample id, results) of
     every answered query."""
     from .search import results_output
+    if args.query_ids is not None and _max_distance(args) is not None:
+        return _search_radius_members(args, searcher, stdout, args.query_ids, True, collect)
     if args.query_ids is not None:
         internal, results = searcher.search_member_n_batch(args.query_ids, args.results, _search_k(args),
                                                            include_distances=args.distances, meta_db=args.metadata,
@@ -1281,7 +1437,11 @@ def _search_batch(args, searcher, stdout, collect=None):
                 collect.append((query_id, res))
         return 0
     batch = searcher.queries_from_intropolis(args.intropolis)
-    if args.exact:
+    if _max_distance(args) is not None:
+        results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
+                                                 meta_db=args.metadata, restriction=_restriction(args),
+                                                 num_neighbors=_radius_cap(args))
+    elif args.exact:
         results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
                                                  restriction=_restriction(args))
     else:
@@ -1305,6 +1465,8 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     from .search import results_output
     if args.intropolis is not None or args.query_ids is not None:
         return _search_batch(args, searcher, stdout, collect)
+    if args.query_id is not None and _max_distance(args) is not None:
+        return _search_radius_members(args, searcher, stdout, [args.query_id], False, collect)
     if args.query_id is not None and _restriction(args) is not None:
         # search_member_n under a restriction: its two lines, then the restricted search by item
         internal, results = searcher.search_member_n_batch([args.query_id], args.results, _search_k(args),
@@ -1379,7 +1541,10 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     searcher.finalize_query()
     if args.verbose:
         sys.stderr.write("\n")
-    if _restriction(args) is not None:
+    if _max_distance(args) is not None:
+        results = searcher.exact_radius_nn(_max_distance(args), num_neighbors=_radius_cap(args), include_distances=args.distances,
+                                           meta_db=args.metadata, restriction=_restriction(args))
+    elif _restriction(args) is not None:
         if args.exact:
             results = searcher.exact_search_nn(args.results, include_distances=args.distances, meta_db=args.metadata,
                                                restriction=_restriction(args))

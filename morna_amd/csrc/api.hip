@@ -982,6 +982,104 @@ int morna_label_sums_stats(const morna_index *h, double *stats)
     return MORNA_OK;
 }
 
+// ---- radius search (the contract is in morna_hip.h) ---------------------------------------------------------------
+
+int morna_exact_radius(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
+                       const int32_t *q_group, const int32_t *after, double radius, morna_radius **out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
+    if (!out) {
+        set_error("exact_radius: null buffer");
+        return MORNA_E_INVALID;
+    }
+    *out = nullptr;
+    if (q && items) {
+        set_error("exact_radius: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    if (q_group && (!r || !r->has_group)) {
+        set_error("exact_radius: query groups need a restriction that holds the items' groups");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("exact_radius is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const double *q_dev64 = nullptr;
+    if (!q && !items) {   // the staged query rows
+        if (!h->qrows.valid) {
+            set_error("exact_radius: no query source (give query vectors or items, or call morna_build_query_rows first)");
+            return MORNA_E_INVALID;
+        }
+        if (nq != h->qrows.nq) {
+            set_error("exact_radius: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
+            return MORNA_E_INVALID;
+        }
+        q_dev64 = h->qrows.rows64.p;
+    }
+    morna_radius *R = nullptr;
+    int rc = MORNA_OK;
+    try {   // (the lists grow on the host: bad_alloc / length_error must not cross the C ABI)
+        R = new morna_radius();
+        rc = exact_radius(h, r, q, items, q_dev64, nq, q_group, after, radius, R);
+    } catch (const std::exception &e) {
+        set_error("exact_radius: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK) {
+        delete R;
+        for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
+        return rc;
+    }
+    *out = R;
+    return MORNA_OK;
+}
+
+int morna_radius_counts(const morna_radius *r, int64_t *count_out)
+{
+    if (!r || !count_out) {
+        set_error("radius_counts: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (r->nq > 0) memcpy(count_out, r->count.data(), (size_t)r->nq * 8);
+    return MORNA_OK;
+}
+
+int morna_radius_query(const morna_radius *r, int64_t q, const int32_t **ids, const double **dist, int64_t *len)
+{
+    if (!r || !ids || !dist || !len) {
+        set_error("radius_query: null argument");
+        return MORNA_E_INVALID;
+    }
+    if (q < 0 || q >= r->nq) {
+        set_error("radius_query: query %lld out of range [0, %lld)", (long long)q, (long long)r->nq);
+        return MORNA_E_RANGE;
+    }
+    *ids = r->ids.data() + r->off[(size_t)q];
+    *dist = r->dist.data() + r->off[(size_t)q];
+    *len = r->off[(size_t)q + 1] - r->off[(size_t)q];
+    return MORNA_OK;
+}
+
+int morna_radius_free(morna_radius *r)
+{
+    delete r;
+    return MORNA_OK;
+}
+
+int morna_exact_radius_stats(const morna_index *h, double *stats)
+{
+    if (!h || !stats) {
+        set_error("exact_radius_stats: null pointer");
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
+    for (int i = 0; i < 8; i++) stats[i] = h->radius_stats[i];
+    return MORNA_OK;
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

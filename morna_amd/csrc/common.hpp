@@ -386,6 +386,9 @@ struct morna_index {
     morna::DevBuf<int32_t> lb_label;   // [n_items]
     morna::DevBuf<uint8_t> lb_out;     // sums uint64 [batch][L] | counts int32 [batch][L] | rows counted uint64
     double label_stats[6] = {0, 0, 0, 0, 0, 0};
+    // radius search (knn.hip, exact_radius): chunk counts, offsets and per-query flags of a batch; the last call's statistics
+    morna::DevBuf<uint8_t> rd_ws;
+    double radius_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
@@ -423,6 +426,15 @@ struct morna_restriction {
     morna::DevBuf<uint32_t> deny;      // [(n_items + 31) / 32], the bits past n_items set
     morna::DevBuf<int32_t> group;      // [n_items]
     bool has_group = false;
+};
+
+// The answer of one morna_exact_radius call (morna_hip.h, "radius search"): host memory, every list ordered.
+struct morna_radius {
+    int64_t nq = 0;
+    std::vector<int64_t> off;      // [nq + 1] list q is ids / dist [off[q], off[q + 1])
+    std::vector<int64_t> count;    // [nq] the list's length, or -1 (a NaN distance: the reference raises)
+    std::vector<int32_t> ids;
+    std::vector<double> dist;
 };
 
 namespace morna {
@@ -533,6 +545,11 @@ int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, c
 int label_sums(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
                const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *item_label_host, int32_t L,
                uint64_t *sums_out, int32_t *counts_out);
+// morna_exact_radius behind its argument checks (morna_hip.h, "radius search"): rst, q_group_host and after_host may be null;
+// the queries are q_host, items_host or q_dev64 (the staged query rows); the lists are appended to *out (empty on entry)
+int exact_radius(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
+                 const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *after_host, double radius,
+                 morna_radius *out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

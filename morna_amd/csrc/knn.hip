@@ -2359,6 +2359,40 @@ __global__ __launch_bounds__(256) void exact_select_restricted_kernel(const floa
 // whole workgroup 5.9 ms, a parallel-fp64 narrowing pass in front 4.4 ms, this form 3.4 ms.
 #define RR_COLS 32
 #define RR_THREADS 64   // one wave per query: the candidates are a few dozen, and a wave that waits for its chains leaves the SIMD to other queries
+// The chain itself, one thread, one row: what exact_rerank_kernel and radius_dist_kernel both return.
+__device__ __forceinline__ double exact_ref_distance(const float4 *__restrict__ row, const double *__restrict__ q, int32_t dim)
+{
+    double pp = 0.0, qq = 0.0, pq = 0.0;
+    float4 cur[RR_COLS / 4], nxt[RR_COLS / 4];
+#pragma unroll
+    for (int u = 0; u < RR_COLS / 4; u++) cur[u] = row[u];   // (dpad is a multiple of 256: every line read exists)
+    for (int z0 = 0; z0 < dim; z0 += RR_COLS) {
+        const bool more = z0 + RR_COLS < dim;
+#pragma unroll
+        for (int u = 0; u < RR_COLS / 4; u++) nxt[u] = row[(more ? z0 + RR_COLS : z0) / 4 + u];
+        const int zn = dim - z0 < RR_COLS ? dim - z0 : RR_COLS;
+#pragma unroll
+        for (int u = 0; u < RR_COLS / 4; u++) {
+            const float e4[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                if (4 * u + v < zn) {
+                    const double i = (double)e4[v], j = q[z0 + 4 * u + v];
+                    pp = __dadd_rn(pp, __dmul_rn(i, i));
+                    qq = __dadd_rn(qq, __dmul_rn(j, j));
+                    pq = __dadd_rn(pq, __dmul_rn(i, j));
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RR_COLS / 4; u++) cur[u] = nxt[u];
+    }
+    const double ppqq = __dmul_rn(pp, qq);
+    double distance = 2.0;
+    if (ppqq > 0.0) distance = __dsub_rn(2.0, __ddiv_rn(__dmul_rn(2.0, pq), __dsqrt_rn(ppqq)));
+    return __dsqrt_rn(distance);   // NaN where Python's math.sqrt raises
+}
+
 __global__ __launch_bounds__(RR_THREADS) void exact_rerank_kernel(const float *__restrict__ X, int32_t dim, int32_t dpad,
                                                            const double *__restrict__ Qd /* [nq][dim] */,
                                                            const int32_t *__restrict__ cand, const int32_t *__restrict__ ncand,
@@ -2372,38 +2406,8 @@ __global__ __launch_bounds__(RR_THREADS) void exact_rerank_kernel(const float *_
     const int n = ncand[qi] < cap ? ncand[qi] : cap;
     const int32_t *c = cand + qi * cap;
     double *cd = cdist + qi * cap;
-    for (int t = tid; t < n; t += RR_THREADS) {
-        const float4 *row = (const float4 *)(X + (int64_t)c[t] * dpad);
-        double pp = 0.0, qq = 0.0, pq = 0.0;
-        float4 cur[RR_COLS / 4], nxt[RR_COLS / 4];
-#pragma unroll
-        for (int u = 0; u < RR_COLS / 4; u++) cur[u] = row[u];   // (dpad is a multiple of 256: every line read exists)
-        for (int z0 = 0; z0 < dim; z0 += RR_COLS) {
-            const bool more = z0 + RR_COLS < dim;
-#pragma unroll
-            for (int u = 0; u < RR_COLS / 4; u++) nxt[u] = row[(more ? z0 + RR_COLS : z0) / 4 + u];
-            const int zn = dim - z0 < RR_COLS ? dim - z0 : RR_COLS;
-#pragma unroll
-            for (int u = 0; u < RR_COLS / 4; u++) {
-                const float e4[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-#pragma unroll
-                for (int v = 0; v < 4; v++) {
-                    if (4 * u + v < zn) {
-                        const double i = (double)e4[v], j = q[z0 + 4 * u + v];
-                        pp = __dadd_rn(pp, __dmul_rn(i, i));
-                        qq = __dadd_rn(qq, __dmul_rn(j, j));
-                        pq = __dadd_rn(pq, __dmul_rn(i, j));
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < RR_COLS / 4; u++) cur[u] = nxt[u];
-        }
-        const double ppqq = __dmul_rn(pp, qq);
-        double distance = 2.0;
-        if (ppqq > 0.0) distance = __dsub_rn(2.0, __ddiv_rn(__dmul_rn(2.0, pq), __dsqrt_rn(ppqq)));
-        cd[t] = __dsqrt_rn(distance);   // NaN where Python's math.sqrt raises
-    }
+    for (int t = tid; t < n; t += RR_THREADS)
+        cd[t] = exact_ref_distance((const float4 *)(X + (int64_t)c[t] * dpad), q, dim);
     // A NaN is a row for which Python's math.sqrt raises ValueError (negative radicand: the cosine rounded to more
     // than 1, i.e. a row all but parallel to the query).  The reference evaluates EVERY row, so one such row anywhere
     // fails the whole query; such a row has a scan distance of ~0 and is therefore always among the candidates.  The
@@ -2803,6 +2807,25 @@ static float exact_scan_eps(int32_t dpad, bool mfma)
     const double e_dot = mfma ? (MM_FLUSH + dpad / MM_FLUSH + 8) * u : (dpad / 64 + 8) * u;
     const double e_norm = (dpad / 64 + 8) * u;
     return (float)(2.0 * 2.0 * (e_dot + e_norm + 2 * u + u / 8));
+}
+
+// The window of the radius search (morna_exact_radius): row i is a candidate iff its scan value
+//     v <= fl_up((float)(r * r)) + eps,     eps = exact_scan_eps(dpad, which scan ran), the sum taken in fp64 (exact).
+// Derivation.  Let t be the true 2 - 2cos and D the reference's fp64 radicand (exact_ref_distance returns sqrt(D)).  The row
+// belongs to the answer iff sqrt(D) <= r in fp64.  Correctly rounded sqrt is monotone, so sqrt(D) <= r implies
+// D <= r^2 (1 + 2^-52); the fp64 chain keeps |D - t| below dpad 2^-50, and the scan keeps |v - t| <= eps / 2 (eps is the
+// bound above taken twice, for the two values the top-k threshold compares; here there is one).  So a row of the answer has
+//     v <= t + eps / 2 <= r^2 + eps / 2 + (r^2 2^-52 + dpad 2^-50).
+// w = (float)(r * r) is r^2 rounded twice to nearest, at worst a little under half an fp32 ulp below r^2; the next float up,
+// fl_up(w), is at least r^2 (and +inf when r^2 overflows fp32: every row is then a candidate, which r >= 2 means anyway).
+// The bracket is at most 2^-34 for r <= 2 and dpad <= 32768 while eps / 2 is at least 2^-19: the unused half of eps covers
+// it.  Nothing more is added: every candidate costs one fp64 chain in radius_dist_kernel.
+// NaN rows: the radicand is negative only when the fp64 cosine rounds above 1, so t < dpad 2^-50 and v <= eps / 2 + that:
+// inside the window of every r >= 0.
+static double exact_radius_window(double r, float eps)
+{
+    const float w = (float)(r * r);
+    return (double)nextafterf(w, INFINITY) + (double)eps;
 }
 
 // The rows outside the scan's domain (exact_scan_eps): non-zero rows whose fp32 norm2 is below lo or above EX_N2_HI (NaN
@@ -3242,6 +3265,469 @@ int label_sums(morna_index *h, const morna_restriction *rst, const double *q_hos
     h->label_stats[3] = (double)batches;
     h->label_stats[4] = counted;
     h->label_stats[5] = eps_half;
+    return MORNA_OK;
+}
+
+// =============================================================== radius search (morna_hip.h, "radius search")
+// Every row within the fp64 distance r of a query: the scan of exact_search_any's front, then
+//   radius_count_kernel    per (query, chunk of rows): the rows inside the window (exact_radius_window), counted
+//   radius_offsets_kernel  per query: exclusive scan of its chunk counts; the total is the query's candidate count
+//   (the host sizes the candidate storage from the totals and places the queries one after the other)
+//   radius_write_kernel    the same walk: the candidates written by block scan, ascending by id whatever the grid
+//   radius_dist_kernel     per 64 candidates of a query: the reference's fp64 chain (exact_ref_distance), d <= r decided
+//   radius_sort_kernel     per query of at most RAD_SORT_MAX candidates: the list ordered in LDS
+// No atomic decides a position: the two atomics of radius_dist_kernel count the kept entries and raise the NaN flag.
+
+#define RAD_THREADS 256
+#define RAD_WAVES (RAD_THREADS / WAVE)
+// Lists of up to this many candidates are ordered on the device: key, id key and origin of every entry are 14 bytes, 56 KiB
+// of LDS for a workgroup, so two workgroups fit a CU's 160 KiB.  Longer lists are ordered by the host (exact_radius).
+#define RAD_SORT_MAX 4096
+#define RAD_KEY_PAD (~0ull)
+#define RAD_KEY_DROPPED (~0ull - 1)   // a candidate farther than r: behind everything that is kept
+#define RAD_KEY_NAN (~0ull - 2)       // NaN distances last, by ascending id
+
+struct RadiusArgs {
+    const float *approx;       // [nb][n_items] the scan values, NaN for the rows of `outs`
+    int64_t n_items, chunk_rows;
+    int32_t chunks;            // chunks of rows per query; slot `chunks` of a query is its share of `outs`
+    double thr;                // the window
+    const float *qn2;          // [nb] 0: the query lies outside the scan's domain and is compared with every row
+    const int32_t *after;      // [nb] only rows with id > after[q], or null
+    const int32_t *outs;       // rows outside the scan's domain
+    int32_t n_outs;
+};
+
+__device__ inline int wave_sum_i32(int v)
+{
+#pragma unroll
+    for (int off = WAVE / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
+
+// entry e of the (query, chunk) of a workgroup: its row, and whether the row is a candidate.  Eligibility and the id
+// bound come first: a row that fails them is not evaluated, whatever its scan value.
+template <bool RST>
+__device__ __forceinline__ bool radius_candidate(const RadiusArgs &A, const RestrictArgs &R, int64_t qi, int32_t gq, int32_t aft,
+                                                 bool all, bool in_outs, int64_t e, int32_t &row)
+{
+    row = in_outs ? A.outs[e] : (int32_t)e;
+    if (row <= aft) return false;
+    if constexpr (RST) {
+        if (!restrict_eligible(R, gq, row)) return false;
+    }
+    if (in_outs) return true;
+    const float v = A.approx[qi * A.n_items + row];
+    return all ? v == v : (double)v <= A.thr;
+}
+
+// the entries of chunk c: rows [e0, e1) of the matrix, or positions [0, n_outs) of `outs` for c == chunks
+__device__ inline void radius_chunk(const RadiusArgs &A, int c, int64_t &e0, int64_t &e1)
+{
+    if (c == A.chunks) {
+        e0 = 0;
+        e1 = A.n_outs;
+    } else {
+        e0 = (int64_t)c * A.chunk_rows;
+        e1 = e0 + A.chunk_rows < A.n_items ? e0 + A.chunk_rows : A.n_items;
+    }
+}
+
+template <bool RST>
+__global__ __launch_bounds__(RAD_THREADS) void radius_count_kernel(RadiusArgs A, RestrictArgs R,
+                                                                   int32_t *__restrict__ chunk_cnt /* [nb][chunks + 1] */)
+{
+    __shared__ int s_w[RAD_WAVES];
+    const int tid = threadIdx.x, c = blockIdx.y;
+    const int64_t qi = blockIdx.x;
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(R, qi);
+    const int32_t aft = A.after ? A.after[qi] : -1;
+    const bool all = A.qn2[qi] == 0.f;
+    int64_t e0, e1;
+    radius_chunk(A, c, e0, e1);
+    int mine = 0;
+    for (int64_t e = e0 + tid; e < e1; e += RAD_THREADS) {
+        int32_t row;
+        mine += radius_candidate<RST>(A, R, qi, gq, aft, all, c == A.chunks, e, row) ? 1 : 0;
+    }
+    mine = wave_sum_i32(mine);
+    if ((tid & (WAVE - 1)) == 0) s_w[tid / WAVE] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < RAD_WAVES; w++) total += s_w[w];
+        chunk_cnt[qi * (A.chunks + 1) + c] = total;
+    }
+}
+
+// one wave per query: its chunk counts become their exclusive prefix, the total its candidate count
+__global__ __launch_bounds__(WAVE) void radius_offsets_kernel(int32_t *__restrict__ chunk_cnt, int32_t per_q,
+                                                              int32_t *__restrict__ ncand /* [nb] */)
+{
+    const int lane = threadIdx.x;
+    int32_t *c = chunk_cnt + (int64_t)blockIdx.x * per_q;
+    int run = 0;
+    for (int b = 0; b < per_q; b += WAVE) {
+        const int v = b + lane < per_q ? c[b + lane] : 0;
+        int inc = v;
+#pragma unroll
+        for (int off = 1; off < WAVE; off <<= 1) {
+            const int up = __shfl_up(inc, off, WAVE);
+            if (lane >= off) inc += up;
+        }
+        if (b + lane < per_q) c[b + lane] = run + inc - v;
+        run += __shfl(inc, WAVE - 1, WAVE);
+    }
+    if (lane == 0) ncand[blockIdx.x] = run;
+}
+
+template <bool RST>
+__global__ __launch_bounds__(RAD_THREADS) void radius_write_kernel(RadiusArgs A, RestrictArgs R,
+                                                                   const int32_t *__restrict__ chunk_off /* [nb][chunks + 1] */,
+                                                                   const int64_t *__restrict__ qoff /* [nb] */,
+                                                                   int32_t *__restrict__ cand)
+{
+    __shared__ int s_w[RAD_WAVES];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE, c = blockIdx.y;
+    const int64_t qi = blockIdx.x;
+    int32_t gq = -1;
+    if constexpr (RST) gq = restrict_query_group(R, qi);
+    const int32_t aft = A.after ? A.after[qi] : -1;
+    const bool all = A.qn2[qi] == 0.f;
+    int64_t e0, e1;
+    radius_chunk(A, c, e0, e1);
+    int32_t *dst = cand + qoff[qi] + chunk_off[qi * (A.chunks + 1) + c];
+    int base = 0;
+    for (int64_t t0 = e0; t0 < e1; t0 += RAD_THREADS) {   // (uniform: every thread takes every step)
+        const int64_t e = t0 + tid;
+        int32_t row = -1;
+        const bool is = e < e1 && radius_candidate<RST>(A, R, qi, gq, aft, all, c == A.chunks, e, row);
+        const unsigned long long m = __ballot(is);
+        if (lane == 0) s_w[w] = __popcll(m);
+        __syncthreads();
+        int before = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+        for (int u = 0; u < RAD_WAVES; u++) {
+            before += u < w ? s_w[u] : 0;
+            total += s_w[u];
+        }
+        if (is) dst[base + before] = row;
+        base += total;
+        __syncthreads();
+    }
+}
+
+// workgroup b of the grid is 64 candidates of one query: blkoff[q] <= b < blkoff[q + 1] (blkoff: the prefix of
+// ceil(ncand / 64) over the batch's queries, made by the host beside qoff)
+__global__ __launch_bounds__(WAVE) void radius_dist_kernel(const float *__restrict__ X, int32_t dim, int32_t dpad,
+                                                           const double *__restrict__ Qd /* [nb][dim] */, int64_t nb,
+                                                           const int32_t *__restrict__ cand, const int64_t *__restrict__ qoff,
+                                                           const int64_t *__restrict__ blkoff /* [nb + 1] */, double radius,
+                                                           double *__restrict__ cdist, int32_t *__restrict__ nkeep,
+                                                           int32_t *__restrict__ nan_flag)
+{
+    const int lane = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    int64_t lo = 0, hi = nb - 1;   // the last q with blkoff[q] <= b
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (blkoff[mid] <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t qi = lo;
+    const int64_t n = qoff[qi + 1] - qoff[qi];
+    const int64_t t = (b - blkoff[qi]) * WAVE + lane;
+    bool keep = false, isnan = false;
+    if (t < n) {
+        const int64_t at = qoff[qi] + t;
+        const double d = exact_ref_distance((const float4 *)(X + (int64_t)cand[at] * dpad), Qd + qi * dim, dim);
+        isnan = d != d;
+        keep = isnan || d <= radius;   // fp64, inclusive; a NaN stays, and fails the query
+        cdist[at] = keep ? d : INFINITY;
+    }
+    const unsigned long long mk = __ballot(keep), mn = __ballot(isnan);
+    if (lane == 0) {
+        if (mk) atomicAdd(&nkeep[qi], __popcll(mk));
+        if (mn) atomicOr(&nan_flag[qi], 1);
+    }
+}
+
+// (distance ascending, id descending), NaN last by ascending id, the dropped candidates (distance +inf) behind them: the
+// order of exact_rerank_kernel.  Non-negative doubles order as their bits.
+__device__ inline void radius_key(double d, int32_t id, uint64_t &key, uint32_t &idkey)
+{
+    if (d != d) {
+        key = RAD_KEY_NAN;
+        idkey = (uint32_t)id;
+    } else {
+        key = d == INFINITY ? RAD_KEY_DROPPED : (uint64_t)__double_as_longlong(d);
+        idkey = ~(uint32_t)id;
+    }
+}
+
+__global__ __launch_bounds__(RAD_THREADS) void radius_sort_kernel(int32_t *__restrict__ cand, double *__restrict__ cdist,
+                                                                  const int64_t *__restrict__ qoff /* [nb + 1] */)
+{
+    __shared__ uint64_t s_key[RAD_SORT_MAX];
+    __shared__ uint32_t s_id[RAD_SORT_MAX];
+    __shared__ uint16_t s_org[RAD_SORT_MAX];
+    const int tid = threadIdx.x;
+    const int64_t qi = blockIdx.x;
+    const int64_t n64 = qoff[qi + 1] - qoff[qi];
+    if (n64 < 2 || n64 > RAD_SORT_MAX) return;
+    const int n = (int)n64;
+    int32_t *c = cand + qoff[qi];
+    double *cd = cdist + qoff[qi];
+    int P = 2;
+    while (P < n) P <<= 1;
+    for (int t = tid; t < P; t += RAD_THREADS) {
+        uint64_t key = RAD_KEY_PAD;
+        uint32_t idkey = ~0u;
+        if (t < n) radius_key(cd[t], c[t], key, idkey);
+        s_key[t] = key;
+        s_id[t] = idkey;
+        s_org[t] = (uint16_t)(t < n ? t : 0);
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P / 2; t += RAD_THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const uint64_t ka = s_key[i], kb = s_key[l];
+                const uint32_t ia = s_id[i], ib = s_id[l];
+                const bool gt = ka > kb || (ka == kb && ia > ib);
+                if (gt == ((i & k) == 0)) {
+                    s_key[i] = kb, s_key[l] = ka;
+                    s_id[i] = ib, s_id[l] = ia;
+                    const uint16_t o = s_org[i];
+                    s_org[i] = s_org[l], s_org[l] = o;
+                }
+            }
+            __syncthreads();
+        }
+    // every key below the padding's is one of the n entries, so positions [0, n) hold a permutation of them.  In place: all
+    // reads of the old order come before the barrier, all writes after it.
+    constexpr int PER = RAD_SORT_MAX / RAD_THREADS;
+    int32_t rid[PER];
+    double rd[PER];
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int t = tid + u * RAD_THREADS;
+        if (t < n) {
+            rid[u] = c[s_org[t]];
+            rd[u] = cd[s_org[t]];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int t = tid + u * RAD_THREADS;
+        if (t < n) {
+            c[t] = rid[u];
+            cd[t] = rd[u];
+        }
+    }
+}
+
+// the order of radius_sort_kernel on the host, for the lists that do not fit it
+static bool radius_before(double da, int32_t ia, double db, int32_t ib)
+{
+    const bool an = da != da, bn = db != db;
+    if (an) return bn && ia < ib;
+    return bn || da < db || (da == db && ia > ib);
+}
+
+int exact_radius(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
+                 const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *after_host, double radius,
+                 morna_radius *out)
+{
+    for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
+    MORNA_TRY(finish_build(h, "exact_radius"));
+    MORNA_TRY(upload_host_rows(h));
+    if (rst) MORNA_TRY(restriction_usable(h, rst));
+    if (h->n_items <= 0) {
+        set_error("exact_radius on an empty index");
+        return MORNA_E_EMPTY;
+    }
+    if (nq < 0) {
+        set_error("exact_radius: a negative number of queries");
+        return MORNA_E_INVALID;
+    }
+    if (!(radius >= 0.0) || radius > DBL_MAX) {
+        set_error("exact_radius: the radius %g is not a finite number >= 0", radius);
+        return MORNA_E_INVALID;
+    }
+    out->nq = nq;
+    out->off.assign((size_t)nq + 1, 0);
+    out->count.assign((size_t)nq, 0);
+    if (nq == 0) return MORNA_OK;
+    const int64_t N = h->n_items;
+    const int32_t D = h->dim, dpad = h->dpad;
+    int qt = 1;
+    MORNA_TRY(exact_check_queries(h, q_host, items_host, nq, &qt));
+    MORNA_TRY(exact_outside_rows(h));
+    const int32_t n_outs = h->ex_out_n;
+    const int32_t *outs = h->ex_out.p + 1;
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 29) / std::max<int64_t>(N, 1)));
+    if (const char *e = getenv("MORNA_RADIUS_BATCH"))   // (read per call: a test puts a batch edge inside a small call)
+        if (atoll(e) > 0) batch = std::min<int64_t>(batch, atoll(e));
+    const size_t s_qd = align_up((size_t)batch * D * 8, 256), s_qf = align_up((size_t)batch * dpad * 4, 256),
+                 s_b4 = align_up((size_t)batch * 4, 256), s_b8 = align_up(((size_t)batch + 1) * 8, 256),
+                 s_ap = align_up((size_t)batch * N * 4, 256);
+    MORNA_TRY(h->ex_ws.alloc(s_qd + s_qf + 3 * s_b4 + s_ap));
+    uint8_t *p = h->ex_ws.p;
+    double *Qd = (double *)p; p += s_qd;
+    float *Qf = (float *)p; p += s_qf;
+    float *qn2 = (float *)p; p += s_b4;
+    int32_t *d_items = (int32_t *)p; p += s_b4;
+    int32_t *d_qg = (int32_t *)p; p += s_b4;
+    float *approx = (float *)p; p += s_ap;
+    // a workgroup per (query, chunk of rows): about 2048 workgroups when the batch is small, whole rows past that (the
+    // shape of label_sums); the chunks of a full batch are the fewest, so a short last batch is sized on its own below
+    auto chunking = [&](int64_t nb, int64_t &chunk_rows) -> int32_t {
+        const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((2048 + nb - 1) / nb, (N + 2047) / 2048));
+        chunk_rows = ((N + chunks - 1) / chunks + RAD_THREADS - 1) / RAD_THREADS * RAD_THREADS;
+        return (int32_t)((N + chunk_rows - 1) / chunk_rows);
+    };
+    const RestrictArgs Ra = restrict_args(rst, rst && rst->has_group && q_group_host ? d_qg : nullptr);
+    std::vector<int32_t> h_ncand((size_t)batch), h_flags(2 * (s_b4 / 4)), h_ids;
+    std::vector<int64_t> h_off(2 * (s_b8 / 8));
+    std::vector<double> h_dist;
+    std::vector<std::pair<double, int32_t>> longlist;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&ev[i]));
+    double scan_ms = 0.0, sel_ms = 0.0, dist_ms = 0.0, candidates = 0.0, window = 0.0;
+    int64_t batches = 0, results = 0;
+    auto body = [&]() -> int {
+        for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+            const int64_t nb = std::min(batch, nq - q0);
+            int64_t chunk_rows = 0;
+            const int32_t chunks = chunking(nb, chunk_rows), per_q = chunks + 1;
+            const size_t s_cc = align_up((size_t)nb * per_q * 4, 256);
+            MORNA_TRY(h->rd_ws.alloc(s_cc + 4 * s_b4 + 2 * s_b8));
+            uint8_t *w = h->rd_ws.p;
+            int32_t *chunk_cnt = (int32_t *)w; w += s_cc;
+            int32_t *ncand = (int32_t *)w; w += s_b4;
+            int32_t *nkeep = (int32_t *)w; w += s_b4;      // nkeep | nan_flag: one memset, one copy
+            int32_t *nan_flag = (int32_t *)w; w += s_b4;
+            int32_t *d_after = (int32_t *)w; w += s_b4;
+            int64_t *qoff = (int64_t *)w; w += s_b8;       // qoff | blkoff: one copy
+            int64_t *blkoff = (int64_t *)w; w += s_b8;
+            if (Ra.q_group) HIP_TRY(hipMemcpyAsync(d_qg, q_group_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+            if (after_host) HIP_TRY(hipMemcpyAsync(d_after, after_host + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipEventRecord(ev[0], h->stream));
+            MORNA_TRY(exact_scan_batch(h, q_host, nullptr, q_dev64, items_host, q0, nb, qt, Qd, Qf, qn2, d_items, approx));
+            if (n_outs > 0)
+                hipLaunchKernelGGL(exact_mask_kernel, dim3((unsigned)((nb * n_outs + 255) / 256)), dim3(256), 0, h->stream, outs,
+                                   n_outs, nb, N, approx);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[1], h->stream));
+            RadiusArgs A;
+            A.approx = approx;
+            A.n_items = N;
+            A.chunk_rows = chunk_rows;
+            A.chunks = chunks;
+            A.thr = exact_radius_window(radius, exact_scan_eps(dpad, nb >= 32));   // which scan ran
+            A.qn2 = qn2;
+            A.after = after_host ? d_after : nullptr;
+            A.outs = outs;
+            A.n_outs = n_outs;
+            window = std::max(window, A.thr);
+            const dim3 grid((unsigned)nb, (unsigned)per_q);
+            if (rst) hipLaunchKernelGGL(radius_count_kernel<true>, grid, dim3(RAD_THREADS), 0, h->stream, A, Ra, chunk_cnt);
+            else hipLaunchKernelGGL(radius_count_kernel<false>, grid, dim3(RAD_THREADS), 0, h->stream, A, Ra, chunk_cnt);
+            hipLaunchKernelGGL(radius_offsets_kernel, dim3((unsigned)nb), dim3(WAVE), 0, h->stream, chunk_cnt, per_q, ncand);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[2], h->stream));
+            HIP_TRY(hipMemcpyAsync(h_ncand.data(), ncand, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            int64_t *h_qoff = h_off.data(), *h_blkoff = h_off.data() + s_b8 / 8;   // (the device's layout)
+            h_qoff[0] = h_blkoff[0] = 0;
+            for (int64_t i = 0; i < nb; i++) {
+                h_qoff[i + 1] = h_qoff[i] + h_ncand[(size_t)i];
+                h_blkoff[i + 1] = h_blkoff[i] + (h_ncand[(size_t)i] + WAVE - 1) / WAVE;
+            }
+            const int64_t total = h_qoff[nb], blocks = h_blkoff[nb];
+            candidates += (double)total;
+            MORNA_TRY(h->ex_cand.alloc((size_t)total));
+            MORNA_TRY(h->ex_cdist.alloc((size_t)total));
+            HIP_TRY(hipMemcpyAsync(qoff, h_qoff, s_b8 + ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemsetAsync(nkeep, 0, 2 * s_b4, h->stream));
+            HIP_TRY(hipEventRecord(ev[3], h->stream));
+            if (rst)
+                hipLaunchKernelGGL(radius_write_kernel<true>, grid, dim3(RAD_THREADS), 0, h->stream, A, Ra, chunk_cnt, qoff, h->ex_cand.p);
+            else
+                hipLaunchKernelGGL(radius_write_kernel<false>, grid, dim3(RAD_THREADS), 0, h->stream, A, Ra, chunk_cnt, qoff, h->ex_cand.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[4], h->stream));
+            if (blocks > 0) {
+                hipLaunchKernelGGL(radius_dist_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, h->stream, h->X.p, D, dpad, Qd, nb,
+                                   h->ex_cand.p, qoff, blkoff, radius, h->ex_cdist.p, nkeep, nan_flag);
+                hipLaunchKernelGGL(radius_sort_kernel, dim3((unsigned)nb), dim3(RAD_THREADS), 0, h->stream, h->ex_cand.p,
+                                   h->ex_cdist.p, qoff);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipEventRecord(ev[5], h->stream));
+            h_ids.resize((size_t)total);
+            h_dist.resize((size_t)total);
+            HIP_TRY(hipMemcpyAsync(h_flags.data(), nkeep, s_b4 + (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+            if (total > 0) {
+                HIP_TRY(hipMemcpyAsync(h_ids.data(), h->ex_cand.p, (size_t)total * 4, hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipMemcpyAsync(h_dist.data(), h->ex_cdist.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            const int32_t *h_nkeep = h_flags.data(), *h_nan = h_flags.data() + s_b4 / 4;
+            for (int64_t i = 0; i < nb; i++) {
+                const int64_t n = h_ncand[(size_t)i], keep = h_nkeep[i], at = h_qoff[i];
+                if (n <= RAD_SORT_MAX) {   // ordered by radius_sort_kernel: the kept entries lead
+                    out->ids.insert(out->ids.end(), h_ids.begin() + at, h_ids.begin() + at + keep);
+                    out->dist.insert(out->dist.end(), h_dist.begin() + at, h_dist.begin() + at + keep);
+                } else {
+                    longlist.clear();
+                    for (int64_t t = at; t < at + n; t++)
+                        if (h_dist[(size_t)t] != INFINITY) longlist.emplace_back(h_dist[(size_t)t], h_ids[(size_t)t]);
+                    std::sort(longlist.begin(), longlist.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) {
+                        return radius_before(a.first, a.second, b.first, b.second);
+                    });
+                    for (const auto &e : longlist) {
+                        out->ids.push_back(e.second);
+                        out->dist.push_back(e.first);
+                    }
+                }
+                results += keep;
+                out->off[(size_t)(q0 + i) + 1] = results;
+                out->count[(size_t)(q0 + i)] = h_nan[i] ? -1 : keep;
+                if (results > (int64_t)INT32_MAX) {
+                    set_error("exact_radius: %lld result entries by query %lld, more than the 2^31 - 1 one call returns",
+                              (long long)results, (long long)(q0 + i));
+                    return MORNA_E_INVALID;
+                }
+            }
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            scan_ms += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
+            sel_ms += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4]));
+            sel_ms += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[4], ev[5]));
+            dist_ms += ms;
+            batches++;
+        }
+        return MORNA_OK;
+    };
+    const int rc = body();
+    for (int i = 0; i < 6; i++) (void)hipEventDestroy(ev[i]);
+    MORNA_TRY(rc);
+    h->radius_stats[0] = scan_ms;
+    h->radius_stats[1] = sel_ms;
+    h->radius_stats[2] = dist_ms;
+    h->radius_stats[3] = (double)nq;
+    h->radius_stats[4] = (double)batches;
+    h->radius_stats[5] = candidates;
+    h->radius_stats[6] = (double)results;
+    h->radius_stats[7] = window;
     return MORNA_OK;
 }
 

@@ -90,6 +90,74 @@ def restricted_search_k(n_trees, k, n_items, n_allowed):
     return min(int(n_trees) * int(k) * scale, INT32_MAX)
 
 
+RADIUS_SHARDS_REFUSAL = ("radius search (--max-distance, pairs) is not available on an index of row shards (.shards.mor, one "
+                         "process per shard, --device a,b): run it on an index built without --shards")
+
+
+def parse_max_distance(text):
+    """--max-distance: a finite distance >= 0 (the angular distance lies in [0, 2]; 2 and more returns every sample)."""
+    try:
+        d = float(text)
+    except (TypeError, ValueError):
+        raise ValueError("--max-distance takes a distance, a finite number >= 0 such as 0.15 (got %r)" % (text,))
+    if not (d >= 0.0) or d == float("inf"):
+        raise ValueError("--max-distance takes a distance, a finite number >= 0 such as 0.15 (got %r)" % (text,))
+    return d
+
+
+def sort_pairs(pairs):
+    """(idA, idB, distance) triples in the order `morna pairs` prints them: NaN pairs first, then by (distance, idA, idB)."""
+    return sorted(pairs, key=lambda p: (0, 0.0, p[0], p[1]) if p[2] != p[2] else (1, p[2], p[0], p[1]))
+
+
+def pair_clusters(pairs):
+    """The connected components of the graph whose edges are `pairs` ((idA, idB, ...) tuples): a list of id lists, every
+    list ascending, the largest component first (equal sizes: by their smallest id).  Union-find on the host."""
+    parent = {}
+
+    def find(x):
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:
+            parent[x], x = root, parent[x]
+        return root
+    for p in pairs:
+        a, b = p[0], p[1]
+        parent.setdefault(a, a)
+        parent.setdefault(b, b)
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    members = defaultdict(list)
+    for x in parent:
+        members[find(x)].append(x)
+    return sorted((sorted(m) for m in members.values()), key=lambda m: (-len(m), m[0]))
+
+
+def format_distance(d):
+    """A distance as `search -d` prints it (str of the float); nan for a NaN."""
+    return "nan" if d != d else str(float(d))
+
+
+def format_pair_line(id_a, id_b, d, meta=None):
+    """One line of `morna pairs`: idA<TAB>idB<TAB>distance, and with meta = (keywords of A, keywords of B) both appended."""
+    line = "%s\t%s\t%s" % (id_a, id_b, format_distance(d))
+    if meta is not None:
+        line += "\t%s\t%s" % (meta[0], meta[1])
+    return line + "\n"
+
+
+def format_pairs_summary(n_samples, pairs, clusters):
+    """The summary line of `morna pairs`."""
+    return "# samples %d\tpairs %d\tsamples in any pair %d\tlargest cluster %d\n" % (
+        n_samples, len(pairs), sum(len(c) for c in clusters), len(clusters[0]) if clusters else 0)
+
+
+def format_cluster_line(cluster):
+    return "# cluster %d\t%s\n" % (len(cluster), ",".join(str(i) for i in cluster))
+
+
 TREES_SHARDS_REFUSAL = ("a search over the first trees of the forest (n_trees=, --use-trees, recall) is not available on an index "
                         "of row shards (.shards.mor, one process per shard, --device a,b): run it on an index built without "
                         "--shards")
@@ -700,6 +768,94 @@ class MornaSearch(object):
         else:
             ids, d, cnt = self.annoy_index.exact_search_query_rows(num_neighbors)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
+
+    # ---- radius search and near-duplicate pairs ------------------------------------------------
+    def _check_radius_possible(self):
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(RADIUS_SHARDS_REFUSAL)
+
+    def _radius_results(self, lists, counts, include_distances, meta_db, num_neighbors):
+        """_batch_results for the variable-length lists of AnnoyIndex.exact_radius, cut to num_neighbors when given."""
+        inv = self._inverse_map() if meta_db else None
+        out = []
+        for (ids, d), m in zip(lists, counts):
+            if int(m) < 0:
+                out.append(ValueError("math domain error"))
+                continue
+            if num_neighbors is not None:
+                ids, d = ids[:num_neighbors], d[:num_neighbors]
+            results = ([int(x) for x in ids],)
+            if include_distances:
+                results += ([float(x) for x in d],)
+            if meta_db:
+                results += (lookup_meta(self.basename, [inv.get(i) for i in results[0]]),)
+            out.append(results)
+        return out
+
+    def exact_radius_nn(self, radius, num_neighbors=None, include_distances=True, meta_db=False, restriction=None):
+        """exact_search_nn's list for query_sample with as many results as the index has samples, cut after the last one
+        whose distance is <= radius (and to num_neighbors when given); ValueError where exact_search_nn raises."""
+        self._check_radius_possible()
+        self._check_restriction(restriction, None)
+        lists, counts = self.annoy_index.exact_radius(radius, Q=np.array([self.query_sample], dtype=np.float64),
+                                                      restriction=restriction.handle if restriction is not None else None)
+        res = self._radius_results(lists, counts, include_distances, meta_db, num_neighbors)[0]
+        if isinstance(res, Exception):
+            raise res
+        return res
+
+    def exact_radius_nn_batch(self, batch, radius, include_distances=True, meta_db=False, restriction=None, query_groups=None,
+                              num_neighbors=None):
+        """exact_radius_nn for every query of `batch` (a QueryBatch, or a list of EXTERNAL ids of indexed samples, searched
+        by item): a list of result tuples, in query order; a ValueError instance where the reference would raise.  Under a
+        restriction with groups a by-item query carries its own sample's group unless query_groups says otherwise."""
+        self._check_radius_possible()
+        self._check_restriction(restriction, query_groups)
+        handle = restriction.handle if restriction is not None else None
+        if isinstance(batch, QueryBatch):
+            self._check_batch(batch)
+            lists, counts = self.annoy_index.exact_radius(radius, Q=batch.rows64, restriction=handle, query_groups=query_groups)
+        else:
+            internal = self._internal_ids(batch)
+            if restriction is not None and query_groups is None:
+                query_groups = restriction.own_groups(internal)
+            lists, counts = self.annoy_index.exact_radius(radius, items=np.array(internal, np.int32), restriction=handle,
+                                                          query_groups=query_groups)
+        return self._radius_results(lists, counts, include_distances, meta_db, num_neighbors)
+
+    def _internal_ids(self, query_ids):
+        internal = []
+        for query_id in query_ids:
+            if query_id not in self.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+            internal.append(self.internal_id_map[query_id])
+        return internal
+
+    def sample_pairs(self, radius, restriction=None, groups=True):
+        """Every unordered pair of indexed samples within `radius` of each other: a list of (idA, idB, distance), EXTERNAL
+        ids with idA < idB, in sort_pairs order (NaN pairs -- two rows closer than fp64 can tell -- first).  One radius
+        search by item over all items, every query bounded to the ids above its own.  restriction: only its allowed samples
+        take part; groups: with a restriction made with groups, never pair two samples of one group."""
+        self._check_radius_possible()
+        self._check_restriction(restriction, None)
+        n = self.annoy_index.get_n_items()
+        items = np.arange(n, dtype=np.int32)
+        if restriction is not None and restriction.allow is not None:
+            items = items[restriction.allow]
+        own = restriction.own_groups(items) if restriction is not None and groups else None
+        lists, _ = self.annoy_index.exact_radius(radius, items=items, after=items, query_groups=own,
+                                                 restriction=restriction.handle if restriction is not None else None)
+        inv = self._inverse_map()
+        pairs = []
+        for i, (ids, d) in zip(items.tolist(), lists):
+            a = inv[i]
+            for j, dist in zip(ids.tolist(), d.tolist()):
+                b = inv[j]
+                pairs.append((min(a, b), max(a, b), dist))
+        return sort_pairs(pairs)
 
     def search_recall(self, queries, num_neighbors, trees, search_ks):
         """The recall of the approximate search against the exact one for every (tree count, search_k) of a grid, from this
