@@ -704,14 +704,13 @@ int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int
     if (nq == 0) return MORNA_OK;
     std::vector<int32_t> ex_ids((size_t)nq * k), ex_count((size_t)nq);
     if (staged) {   // the un-rounded fp64 rows, as morna_exact_search_query_rows
-        MORNA_TRY(exact_search_any(h, nullptr, nullptr, nullptr, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0,
-                                   h->qrows.rows64.p));
+        MORNA_TRY(exact_search_any(h, ExactQueries::device64(h->qrows.rows64.p), nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
     } else if (q) {
         std::vector<double> q64((size_t)nq * h->dim);   // the fp32 queries widened
         for (size_t i = 0; i < q64.size(); i++) q64[i] = (double)q[i];
-        MORNA_TRY(exact_search_any(h, q64.data(), nullptr, nullptr, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
+        MORNA_TRY(exact_search_any(h, ExactQueries::host(q64.data()), nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
     } else {
-        MORNA_TRY(exact_search_any(h, nullptr, nullptr, items, nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
+        MORNA_TRY(exact_search_any(h, ExactQueries::stored(items), nq, k, ex_ids.data(), nullptr, ex_count.data(), nullptr, 0));
     }
     MORNA_TRY(search_sweep(h, q, q_stride, items, nq, k, trees, n_t, search_ks, n_s, ids_out, dist_out, count_out, ncand_out,
                            ndots_out, ex_ids.data(), ex_count.data(), hits_out));
@@ -780,7 +779,7 @@ int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, d
         return MORNA_E_INVALID;
     }
     HIP_TRY(hipSetDevice(h->device));
-    return exact_search_any(h, nullptr, nullptr, nullptr, h->qrows.nq, k, ids_out, dist_out, count_out, nullptr, 0, h->qrows.rows64.p);
+    return exact_search_any(h, ExactQueries::device64(h->qrows.rows64.p), h->qrows.nq, k, ids_out, dist_out, count_out, nullptr, 0);
 }
 
 // ---- restricted search (the contract is in morna_hip.h) ---------------------------------------------------------
@@ -924,12 +923,27 @@ int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, co
                       (long long)h->qrows.nq);
             return MORNA_E_INVALID;
         }
-        return exact_search_any(h, nullptr, nullptr, nullptr, nq, k, ids, dist, count, nullptr, 0, h->qrows.rows64.p, r, q_group);
+        return exact_search_any(h, ExactQueries::device64(h->qrows.rows64.p), nq, k, ids, dist, count, nullptr, 0, r, q_group);
     }
-    return exact_search_any(h, q, nullptr, items, nq, k, ids, dist, count, nullptr, 0, nullptr, r, q_group);
+    return exact_search_any(h, q ? ExactQueries::host(q) : ExactQueries::stored(items), nq, k, ids, dist, count, nullptr, 0, r, q_group);
 }
 
 // ---- label distance sums (the contract is in morna_hip.h) -------------------------------------------------------
+
+// the staged query rows as the queries of a call that was given neither vectors nor items
+static int staged_queries(morna_index *h, const char *what, int64_t nq, ExactQueries *Q)
+{
+    if (!h->qrows.valid) {
+        set_error("%s: no query source (give query vectors or items, or call morna_build_query_rows first)", what);
+        return MORNA_E_INVALID;
+    }
+    if (nq != h->qrows.nq) {
+        set_error("%s: %lld queries asked for, %lld query rows are staged", what, (long long)nq, (long long)h->qrows.nq);
+        return MORNA_E_INVALID;
+    }
+    *Q = ExactQueries::device64(h->qrows.rows64.p);
+    return MORNA_OK;
+}
 
 int morna_label_sums(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
                      const int32_t *q_group, const int32_t *item_label, int32_t n_labels, uint64_t *sums_out, int32_t *counts_out)
@@ -957,18 +971,9 @@ int morna_label_sums(morna_index *h, const morna_restriction *r, const double *q
         return MORNA_E_INVALID;
     }
     HIP_TRY(hipSetDevice(h->device));
-    if (!q && !items) {   // the staged query rows
-        if (!h->qrows.valid) {
-            set_error("label_sums: no query source (give query vectors or items, or call morna_build_query_rows first)");
-            return MORNA_E_INVALID;
-        }
-        if (nq != h->qrows.nq) {
-            set_error("label_sums: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        return label_sums(h, r, nullptr, nullptr, h->qrows.rows64.p, nq, q_group, item_label, n_labels, sums_out, counts_out);
-    }
-    return label_sums(h, r, q, items, nullptr, nq, q_group, item_label, n_labels, sums_out, counts_out);
+    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
+    if (!q && !items) MORNA_TRY(staged_queries(h, "label_sums", nq, &Q));
+    return label_sums(h, r, Q, nq, q_group, item_label, n_labels, sums_out, counts_out);
 }
 
 int morna_label_sums_stats(const morna_index *h, double *stats)
@@ -1007,23 +1012,13 @@ int morna_exact_radius(morna_index *h, const morna_restriction *r, const double 
         return MORNA_E_INVALID;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const double *q_dev64 = nullptr;
-    if (!q && !items) {   // the staged query rows
-        if (!h->qrows.valid) {
-            set_error("exact_radius: no query source (give query vectors or items, or call morna_build_query_rows first)");
-            return MORNA_E_INVALID;
-        }
-        if (nq != h->qrows.nq) {
-            set_error("exact_radius: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        q_dev64 = h->qrows.rows64.p;
-    }
+    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
+    if (!q && !items) MORNA_TRY(staged_queries(h, "exact_radius", nq, &Q));
     morna_radius *R = nullptr;
     int rc = MORNA_OK;
     try {   // (the lists grow on the host: bad_alloc / length_error must not cross the C ABI)
         R = new morna_radius();
-        rc = exact_radius(h, r, q, items, q_dev64, nq, q_group, after, radius, R);
+        rc = exact_radius(h, r, Q, nq, q_group, after, radius, R);
     } catch (const std::exception &e) {
         set_error("exact_radius: %s", e.what());
         rc = MORNA_E_INVALID;

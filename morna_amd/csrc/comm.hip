@@ -106,7 +106,7 @@ int sync_sizes(morna_index *h)
 }  // namespace
 
 // ---- merge of the all-gathered exact answers ---------------------------------------------------------------------
-// gathered[world] messages (exact_msg_bytes(nq, kk) each, knn.hip): what exact_search_nn's bisect_left scan over ALL rows
+// gathered[world] messages (exact_msg_bytes(nq, kk) each, exact.hip): what exact_search_nn's bisect_left scan over ALL rows
 // would keep (morna.py:705-712) -- ascending distance, among equal distances the HIGHER global id first.  A shard whose
 // count is -1 ("the reference raises ValueError for this query": a row all but parallel to it) fails the query for the
 // whole matrix.  NaN distances (only such queries have them) go behind the numbers, higher id first; empty slots last.
@@ -273,8 +273,8 @@ static int approx_sharded(morna_index *h, const float *q, int64_t nq, int32_t k,
     return morna_merge_topk_packed(h, gathered, world, nq, k, k, ids_out, dist_out, count_out);
 }
 
-static int exact_sharded(morna_index *h, const double *q_host, const float *q_dev, int64_t nq, int32_t k, int32_t *ids_out,
-                         double *dist_out, int32_t *count_out)
+static int exact_sharded(morna_index *h, const ExactQueries &Q, int64_t nq, int32_t k, int32_t *ids_out, double *dist_out,
+                         int32_t *count_out)
 {
     if (k <= 0 || nq < 0 || !ids_out) {
         set_error("sharded exact search: k must be positive");
@@ -285,7 +285,7 @@ static int exact_sharded(morna_index *h, const double *q_host, const float *q_de
     const size_t msg = exact_msg_bytes(nq, k), s_msg = align_up(msg, 256);
     MORNA_TRY(h->cm_msg.alloc(s_msg + msg * (size_t)world));
     uint8_t *mine = h->cm_msg.p, *gathered = h->cm_msg.p + s_msg;
-    MORNA_TRY(exact_search_any(h, q_host, q_dev, nullptr, nq, k, nullptr, nullptr, nullptr, mine, h->comm_offsets[(size_t)h->comm_rank]));
+    MORNA_TRY(exact_search_any(h, Q, nq, k, nullptr, nullptr, nullptr, mine, h->comm_offsets[(size_t)h->comm_rank]));
     NCCL_TRY(rccl().AllGather(mine, gathered, msg, ncclChar, (ncclComm_t)h->comm, h->stream));
     return merge_exact_dev(h, gathered, world, nq, k, k, ids_out, dist_out, count_out);
 }
@@ -421,7 +421,7 @@ int morna_exact_search_sharded(morna_index *h, const double *q, int64_t nq, int3
         return MORNA_E_INVALID;
     }
     MORNA_TRY(sync_sizes(h));
-    return exact_sharded(h, q, nullptr, nq, k, ids_out, dist_out, count_out);
+    return exact_sharded(h, ExactQueries::host(q), nq, k, ids_out, dist_out, count_out);
 }
 
 int morna_exact_search_by_item_sharded(morna_index *h, const int32_t *local_items, int64_t n_local, const int64_t *n_each, int32_t k,
@@ -434,7 +434,7 @@ int morna_exact_search_by_item_sharded(morna_index *h, const int32_t *local_item
     int64_t nq = 0;
     const float *q_dev = nullptr;
     MORNA_TRY(gather_query_rows(h, local_items, n_local, n_each, &nq, &q_dev));
-    return exact_sharded(h, nullptr, q_dev, nq, k, ids_out, dist_out, count_out);
+    return exact_sharded(h, ExactQueries::device32(q_dev), nq, k, ids_out, dist_out, count_out);
 }
 
 int morna_exact_search_by_item(morna_index *h, const int32_t *items, int64_t nq, int32_t k, int32_t *ids_out, double *dist_out,
@@ -446,7 +446,7 @@ int morna_exact_search_by_item(morna_index *h, const int32_t *items, int64_t nq,
         return MORNA_E_INVALID;
     }
     HIP_TRY(hipSetDevice(h->device));
-    return exact_search_any(h, nullptr, nullptr, items, nq, k, ids_out, dist_out, count_out, nullptr, 0);
+    return exact_search_any(h, ExactQueries::stored(items), nq, k, ids_out, dist_out, count_out, nullptr, 0);
 }
 
 int64_t morna_exact_packed_bytes(int64_t nq, int32_t k) { return nq < 0 || k <= 0 ? 0 : (int64_t)exact_msg_bytes(nq, k); }
@@ -464,7 +464,8 @@ int morna_exact_search_packed(morna_index *h, const double *q, const float *q_de
         return MORNA_E_RANGE;
     }
     HIP_TRY(hipSetDevice(h->device));
-    return exact_search_any(h, q, q_dev, items, nq, k, nullptr, nullptr, nullptr, packed_dev, id_offset);
+    const ExactQueries Q = q ? ExactQueries::host(q) : q_dev ? ExactQueries::device32(q_dev) : ExactQueries::stored(items);
+    return exact_search_any(h, Q, nq, k, nullptr, nullptr, nullptr, packed_dev, id_offset);
 }
 
 int morna_merge_exact_packed(morna_index *h, const uint8_t *gathered_dev, int32_t world, int64_t nq, int32_t kk, int32_t k,

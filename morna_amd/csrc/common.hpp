@@ -372,21 +372,21 @@ struct morna_index {
     // what the contraction of a batch that starts beside a pending build reads and writes: item ids, query image and its
     // three floats per query, scores (placed before anything is enqueued: `ws` is sized from n_nodes, unknown until the tail ends)
     morna::DevBuf<uint8_t> q_early;
-    // exact search: query images, scan values and results of a batch; the candidates and their fp64 distances (knn.hip)
+    // exact search: query images, scan values and results of a batch; the candidates and their fp64 distances (exact.hip)
     morna::DevBuf<uint8_t> ex_ws;
     morna::DevBuf<int32_t> ex_cand;
     morna::DevBuf<double> ex_cdist;
     int32_t ex_cap = 0;                // candidates per query the last exact search needed room for
-    // rows outside the domain of the exact scan's window (knn.hip, exact_outside_kernel): re-ranked for every query.
+    // rows outside the domain of the exact scan's window (exact.hip, exact_outside_kernel): re-ranked for every query.
     // Made at the first exact search after the rows or their norms change; usually empty
     morna::DevBuf<int32_t> ex_out;     // [0] count, [1..] rows
     int32_t ex_out_n = 0;
     bool ex_out_valid = false;
-    // label sums (knn.hip, label_sums): the items' labels and a batch's outputs on the device; the last call's statistics
+    // label sums (exact.hip, label_sums): the items' labels and a batch's outputs on the device; the last call's statistics
     morna::DevBuf<int32_t> lb_label;   // [n_items]
     morna::DevBuf<uint8_t> lb_out;     // sums uint64 [batch][L] | counts int32 [batch][L] | rows counted uint64
     double label_stats[6] = {0, 0, 0, 0, 0, 0};
-    // radius search (knn.hip, exact_radius): chunk counts, offsets and per-query flags of a batch; the last call's statistics
+    // radius search (exact.hip, exact_radius): chunk counts, offsets and per-query flags of a batch; the last call's statistics
     morna::DevBuf<uint8_t> rd_ws;
     double radius_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
@@ -479,7 +479,7 @@ inline int settle(morna_index *h)
     return MORNA_OK;
 }
 
-// implemented in features.hip / forest.hip / knn.hip
+// implemented in features.hip / forest.hip / knn.hip / exact.hip
 int upload_host_rows(morna_index *h);
 int compute_norms(morna_index *h);
 int build_features(morna_index *h, int64_t n_items);
@@ -534,22 +534,32 @@ int merge_topk_dev(morna_index *h, const int32_t *gathered_dev, int32_t world, i
                    int32_t *ids_out, float *dist_out, int32_t *count_out);
 int exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, int32_t *ids_out,
                  double *dist_out, int32_t *count_out);
-// the same for fp32 queries in device memory or for stored rows, answers to the host and / or packed for the sharded merge
-// (q_dev64: fp64 queries [nq][dim] in this device's memory, the query rows of morna_build_query_rows)
-int exact_search_any(morna_index *h, const double *q_host, const float *q_dev, const int32_t *items_host, int64_t nq, int32_t k,
-                     int32_t *ids_out, double *dist_out, int32_t *count_out, uint8_t *msg_dev, int64_t id_offset,
-                     const double *q_dev64 = nullptr, const morna_restriction *rst = nullptr,
+// Where the queries of an exact call are, nq of them: one of four sources.
+struct ExactQueries {
+    enum Source { HOST_F64, DEV_F32, DEV_F64, ITEMS } source;
+    const void *p;
+    static ExactQueries host(const double *q) { return {HOST_F64, q}; }       // fp64 vectors [nq][dim], host memory
+    static ExactQueries device32(const float *q) { return {DEV_F32, q}; }     // fp32 vectors [nq][dim], this device's memory
+    // fp64 rows [nq][dim], this device's memory: the query rows of morna_build_query_rows, finite by construction
+    static ExactQueries device64(const double *q) { return {DEV_F64, q}; }
+    static ExactQueries stored(const int32_t *items) { return {ITEMS, items}; }   // stored rows, their ids [nq] in host memory
+    // the source as its own type, null for the other three
+    const double *host64() const { return source == HOST_F64 ? (const double *)p : nullptr; }
+    const float *dev32() const { return source == DEV_F32 ? (const float *)p : nullptr; }
+    const double *dev64() const { return source == DEV_F64 ? (const double *)p : nullptr; }
+    const int32_t *items() const { return source == ITEMS ? (const int32_t *)p : nullptr; }
+};
+// the same for any source of queries, answers to the host and / or packed for the sharded merge
+int exact_search_any(morna_index *h, const ExactQueries &Q, int64_t nq, int32_t k, int32_t *ids_out, double *dist_out,
+                     int32_t *count_out, uint8_t *msg_dev, int64_t id_offset, const morna_restriction *rst = nullptr,
                      const int32_t *q_group_host = nullptr);
-// morna_label_sums behind its argument checks (morna_hip.h, "label distance sums"): rst and q_group_host may be null;
-// the queries are q_host, items_host or q_dev64 (the staged query rows)
-int label_sums(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
-               const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *item_label_host, int32_t L,
-               uint64_t *sums_out, int32_t *counts_out);
+// morna_label_sums behind its argument checks (morna_hip.h, "label distance sums"): rst and q_group_host may be null
+int label_sums(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *q_group_host,
+               const int32_t *item_label_host, int32_t L, uint64_t *sums_out, int32_t *counts_out);
 // morna_exact_radius behind its argument checks (morna_hip.h, "radius search"): rst, q_group_host and after_host may be null;
-// the queries are q_host, items_host or q_dev64 (the staged query rows); the lists are appended to *out (empty on entry)
-int exact_radius(morna_index *h, const morna_restriction *rst, const double *q_host, const int32_t *items_host,
-                 const double *q_dev64, int64_t nq, const int32_t *q_group_host, const int32_t *after_host, double radius,
-                 morna_radius *out);
+// the lists are appended to *out (empty on entry)
+int exact_radius(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *q_group_host,
+                 const int32_t *after_host, double radius, morna_radius *out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

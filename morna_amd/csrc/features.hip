@@ -872,7 +872,7 @@ int compute_norms(morna_index *h)
     }
     h->norms_valid = true;
     h->half.valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
-    h->ex_out_valid = false; // ... and the exact search's list of rows outside its window (knn.hip)
+    h->ex_out_valid = false; // ... and the exact search's list of rows outside its window (exact.hip)
     return MORNA_OK;
 }
 
@@ -1074,7 +1074,7 @@ int build_features(morna_index *h, int64_t n_items)
         if (fused) {
             h->norms_valid = true;
             h->half.valid = false;   // the rows changed: their fp16 image (splitmm.hip) is made again when next needed
-            h->ex_out_valid = false; // ... and the exact search's list of rows outside its window (knn.hip)
+            h->ex_out_valid = false; // ... and the exact search's list of rows outside its window (exact.hip)
         } else {
             MORNA_TRY(compute_norms(h));
         }

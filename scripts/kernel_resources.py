@@ -1,6 +1,6 @@
 """Registers, spills, LDS and occupancy of every kernel in one csrc file, as hipcc reports them for gfx950.
 
-    python scripts/kernel_resources.py knn [substring-of-kernel-name]
+    python scripts/kernel_resources.py <file stem: knn, exact, forest, ...> [substring-of-kernel-name]
 
 Runs here (hipcc cross-compiles without a GPU); nothing is written into the tree.
 """

@@ -1,7 +1,7 @@
 // mfma_accum_probe.hip -- how the gfx950 matrix cores round while they accumulate, measured.
 //
 // Two filters of the library take dot products on MFMA instructions and reason about the distance between the
-// MFMA result and the exact sum (splitmm.hip: v_mfma_f32_32x32x16_f16, EACC; knn.hip: v_mfma_f32_32x32x2_f32,
+// MFMA result and the exact sum (splitmm.hip: v_mfma_f32_32x32x16_f16, EACC; exact.hip: v_mfma_f32_32x32x2_f32,
 // exact_scan_eps).  The ISA manual does not state the internal summation order or rounding, so this program
 // measures it: chains of L dependent MFMAs on random operands (wide dynamic range, mixed signs), compared on the
 // host with (a) candidate bit-exact models and (b) the exact sum, the error expressed in units of

@@ -409,7 +409,7 @@ def test_c5_exact_all_pairs_shard_8192(capi):
     """configs[4]: exact brute-force all-pairs k-NN at D = 8192 on one GPU's shard of the 50k samples (6250 rows):
     morna.py:681-716 run with every indexed row as the query.  TF-IDF rows of the synthetic intropolis: cluster
     mates are strongly correlated and their distances to a query nearly tie, which is what the candidate window of
-    the fp32 matrix-core scan has to survive (knn.hip eps)."""
+    the fp32 matrix-core scan has to survive (exact.hip eps)."""
     from morna_amd.annoy import AnnoyIndex
     from morna_amd.index import prepare_csr
     from morna_amd.synth import synthetic_intropolis

@@ -2,7 +2,7 @@
 range.  -m gpu
 
 The exact search returns the oracle's ids, fp64 distances and -1 count bit for bit only if the window of
-exact_scan_eps (knn.hip) really bounds the error of the fp32 scan that selects the candidates.  On random or TF-IDF rows
+exact_scan_eps (exact.hip) really bounds the error of the fp32 scan that selects the candidates.  On random or TF-IDF rows
 the k-th and (k+1)-th distances are far apart, so that bound is never tested there.  Here:
 
   * near-tie clusters: a few hundred rows fp32(b + s g_j) around a base row b, the query near b, the spreads s chosen so
@@ -76,7 +76,7 @@ def _sixty(rng, b, n, delta):
 
 
 def _scan_error(D, mfma):
-    """The window of the scan that runs (exact_scan_eps, knn.hip: the matrix-core scan for batches of 32 queries or
+    """The window of the scan that runs (exact_scan_eps, exact.hip: the matrix-core scan for batches of 32 queries or
     more, the vector-ALU scan below): the scale of that scan's error."""
     dpad = (D + 255) // 256 * 256
     u = 2.0 ** -24

@@ -353,7 +353,7 @@ def test_batch_edges_calls_and_lone_queries_give_the_same_bytes():
 
 
 def _scan_eps(dim, mfma):
-    """exact_scan_eps of knn.hip, restated: 4 (e_dot + e_norm + 2u + u/8)."""
+    """exact_scan_eps of exact.hip, restated: 4 (e_dot + e_norm + 2u + u/8)."""
     dpad = (dim + 255) // 256 * 256
     u = 2.0 ** -24
     e_dot = (128 + dpad // 128 + 8) * u if mfma else (dpad // 64 + 8) * u
