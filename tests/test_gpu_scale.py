@@ -189,8 +189,8 @@ import hashlib, sys
 import numpy as np
 sys.path.insert(0, {root!r})
 from morna_amd.annoy import AnnoyIndex
+N, D, T = {N}, {D}, {T}
 rng = np.random.default_rng(20261004)
-N, D, T = 30000, 700, 24
 C = rng.standard_normal((40, D)).astype(np.float32)
 X = (C[rng.integers(0, 40, N)] * rng.uniform(1e-3, 1e3, (N, 1)).astype(np.float32)
      + 0.4 * rng.standard_normal((N, D)).astype(np.float32)).astype(np.float32)
@@ -203,6 +203,7 @@ X[1000:1600] = X[50] * (1.0 + 1e-4 * rng.standard_normal((600, D))).astype(np.fl
 X[1600:1700] = X[50] * np.float32(3.0)                      # exact scaled duplicates: ties broken by id
 X[13, 0] = np.float32(np.inf)                               # a row with no fp16 image at all
 a = AnnoyIndex(D)
+a.timer_enable(only=["tm_strip", "tm_wave"])      # launch counts: which form of two_means this process took
 a.add_items(X)
 a.build(T)
 f = a.get_forest()
@@ -213,32 +214,46 @@ items = np.concatenate([np.arange(64), np.arange(1000, 1064), np.arange(1600, 16
 for n, sk in ((10, -1), (40, 100), (3, 5000)):
     ids, d, cnt = a.get_nns_by_item_batch(items, n, sk)
     h.update(ids.tobytes()); h.update(d.tobytes()); h.update(cnt.tobytes())
-print("DIGEST", h.hexdigest(), a.forest_stats()["n_split"], a.forest_stats()["max_depth"])
+t = a.timers()
+print("DIGEST", h.hexdigest(), a.forest_stats()["n_split"], a.forest_stats()["max_depth"], t["tm_strip"]["launches"],
+      t["tm_wave"]["launches"])
 """
 
 
 def test_filters_do_not_change_results(tmp_path):
     """The fp16 MFMA split filter + exact fallback (splitmm.hip) must write exactly the sides of the plain fp32
     kernels, and the fp16 candidate filter of the approximate search must return exactly what the all-fp32
-    search returns; likewise the four-wave strip form of two_means and the one-wave form: the same seeded build
-    and searches in four processes -- defaults, MORNA_SPLIT_MM=0 (chunk form at every level), MORNA_QUERY_FILTER=0,
-    MORNA_TM_STRIP=0 -- on rows spanning six orders of magnitude in norm, a zero
-    row, duplicates, near-duplicates in the 4th digit, exact scaled duplicates, a row of denormal scale and a row
-    holding an infinity."""
+    search returns: the same seeded build and searches in five processes -- defaults, MORNA_SPLIT_MM=0 (chunk form
+    at every level), MORNA_QUERY_FILTER=0, MORNA_TM_STRIP=0, MORNA_QUERY_DENSE=0 -- on rows spanning six orders of
+    magnitude in norm, a zero row, duplicates, near-duplicates in the 4th digit, exact scaled duplicates, a row of
+    denormal scale and a row holding an infinity.  The four-wave strip form of two_means and the one-wave form are
+    compared at D = 1000 only (the launch counts below say so): at D = 700 there is no strip form, and the
+    MORNA_TM_STRIP=0 process launches what the default one does."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = str(tmp_path / "digest.py")
-    with open(script, "w") as fh:
-        fh.write(_FOREST_DIGEST.format(root=root))
-    out = {}
-    for name, extra in (("default", {}), ("no_mm", {"MORNA_SPLIT_MM": "0"}), ("no_qf", {"MORNA_QUERY_FILTER": "0"}),
-                        ("no_strip", {"MORNA_TM_STRIP": "0"}), ("no_dense", {"MORNA_QUERY_DENSE": "0"})):
-        env = dict(os.environ, **extra)
-        r = subprocess.run([sys.executable, script], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()
-        out[name] = line[1:]
-    assert out["default"] == out["no_mm"] == out["no_qf"] == out["no_strip"] == out["no_dense"], out
-    assert int(out["default"][2]) >= 4                                      # deep enough for every form to run
+    for N, D, T in ((30000, 700, 24),     # 3 float4 per lane: two_means has the one-wave form only
+                    (8000, 1000, 24)):    # 4: four-wave strips at every level of this shape, unless switched off
+        script = str(tmp_path / ("digest%d.py" % D))
+        with open(script, "w") as fh:
+            fh.write(_FOREST_DIGEST.format(root=root, N=N, D=D, T=T))
+        out = {}
+        for name, extra in (("default", {}), ("no_mm", {"MORNA_SPLIT_MM": "0"}), ("no_qf", {"MORNA_QUERY_FILTER": "0"}),
+                            ("no_strip", {"MORNA_TM_STRIP": "0"}), ("no_dense", {"MORNA_QUERY_DENSE": "0"})):
+            env = dict(os.environ, **extra)
+            r = subprocess.run([sys.executable, script], env=env, capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()
+            out[name] = line[1:]
+        digest = {name: v[:3] for name, v in out.items()}      # forest and answers, split nodes, depth
+        assert digest["default"] == digest["no_mm"] == digest["no_qf"] == digest["no_strip"] == digest["no_dense"], out
+        strips = {name: int(v[3]) for name, v in out.items()}
+        waves = {name: int(v[4]) for name, v in out.items()}
+        if D == 700:
+            assert int(out["default"][2]) >= 4                                  # deep enough for every form to run
+            assert all(s == 0 for s in strips.values()) and all(w > 0 for w in waves.values()), out
+        else:
+            assert int(out["default"][2]) >= 2                                  # strips below the roots too
+            assert all(strips[name] > 0 for name in out if name != "no_strip"), out
+            assert strips["no_strip"] == 0 and waves["no_strip"] > 0, out

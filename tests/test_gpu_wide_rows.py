@@ -12,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+from width_forms import compare_approx as _compare_approx, compare_forest as _compare_forest, rows as _rows
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,54 +24,6 @@ def capi():
     from oracle import capi as c
     c.lib()
     return c
-
-
-def _rows(rng, N, f, nc=12, noise=0.3, chunk=2048):
-    """Clustered float32 rows, built chunk by chunk in float32."""
-    centers = rng.standard_normal((nc, f), dtype=np.float32)
-    X = np.empty((N, f), np.float32)
-    for r0 in range(0, N, chunk):
-        r1 = min(N, r0 + chunk)
-        X[r0:r1] = centers[rng.integers(0, nc, r1 - r0)]
-        X[r0:r1] += np.float32(noise) * rng.standard_normal((r1 - r0, f), dtype=np.float32)
-    return X
-
-
-def _compare_forest(a, o):
-    """GPU forest vs oracle mode 1, node for node (as test_gpu_parity.py does)."""
-    f = a.get_forest()
-    rec = f["node_rec"]
-    assert o.n_nodes() == rec.shape[0]
-    hp_of = {int(n): i for i, n in enumerate(f["hp_node"])}
-    n_split = 0
-    for nid in range(rec.shape[0]):
-        nd = o.node(nid)
-        kind, tree, start, count, c0, c1 = [int(x) for x in rec[nid]]
-        assert kind == nd["kind"], nid
-        assert tree == nd["tree"], nid
-        assert count == nd["n_desc"], nid
-        if kind == 1:
-            assert f["perm"][tree, start:start + count].tolist() == nd["items"].tolist(), nid
-        else:
-            n_split += 1
-            assert (c0, c1) == (nd["child0"], nd["child1"]), nid
-            assert f["hyperplanes"][hp_of[nid]].tobytes() == nd["v"].tobytes(), nid
-    return n_split
-
-
-def _compare_approx(a, o, items, Q):
-    for n, sk in ((10, -1), (20, 100)):
-        ids, d, cnt = a.get_nns_by_item_batch(items, n, sk)
-        for qi, it in enumerate(items):
-            rid, rd = o.get_nns_by_item(int(it), n, sk, include_distances=True)
-            m = int(cnt[qi])
-            assert ids[qi, :m].tolist() == rid, (it, n, sk)
-            assert d[qi, :m].tobytes() == np.array(rd, np.float32).tobytes(), (it, n, sk)
-    ids, d, cnt = a.get_nns_by_vector_batch(Q, 10, -1)
-    for qi in range(len(Q)):
-        rid, rd = o.get_nns_by_vector(Q[qi], 10, -1, include_distances=True)
-        assert ids[qi, :int(cnt[qi])].tolist() == rid
-        assert d[qi, :int(cnt[qi])].tobytes() == np.array(rd, np.float32).tobytes()
 
 
 @pytest.mark.parametrize("f,N,T", [(8448, 9000, 2),       # the first width past 8192
@@ -193,6 +147,8 @@ def test_wide_switch_invariance():
     """The build and search switches change nothing at 16384 (each run in its own process: the switches are read once)."""
     script = _SCRIPT.format(root=ROOT, N=18000, D=16384, T=2)
     outs = {}
+    # (MORNA_TM_STRIP=0 launches what the default process launches: past 8192 floats the wide form runs whatever the
+    # switches.  It stays as the check of exactly that; test_gpu_width_forms.py compares the two_means forms.)
     for env in ({}, {"MORNA_SPLIT_MM": "0"}, {"MORNA_TM_STRIP": "0"}, {"MORNA_QUERY_FILTER": "0"},
                 {"MORNA_QUERY_DENSE": "0"}, {"MORNA_QUERY_SPREAD": "0"}):
         e = dict(os.environ)
