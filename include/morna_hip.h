@@ -611,6 +611,49 @@ int morna_radius_free(morna_radius *r);
 int morna_exact_radius_stats(const morna_index *h, double *stats /* [8] */);
 
 /*
+ * ---- spherical k-means (no counterpart in the reference, whose grouping tables come from outside) ------
+ * A partition of the stored rows into k groups by angular distance, bit-reproducible against a CPU restatement.
+ *   Rows: the handle's stored fp32 rows x_i.  The eligible set E: every row, or the allowed rows of a restriction r that holds
+ *     an allow-list only (a restriction that holds groups: MORNA_E_INVALID).  A row-sharded handle: MORNA_E_INVALID.
+ *   Distance: d(i, c) = cosine_distance(x_i, c) of the reference (morna.py:101-114) with c an fp64 vector, accumulated in its
+ *     sequential order, sqrt(2 - 2cos), 2 under the root where the product of the sums of squares is not positive; NaN where
+ *     math.sqrt would raise, returned as the canonical quiet NaN (0x7ff8000000000000).
+ *   Assignment: a_i = the j that minimises d(i, c_j) in fp64.  A NaN orders behind every number; ties, all-NaN included, go
+ *     to the lowest j.  A row outside E gets a_i = -1 and the distance -1.0.
+ *   Update: pp_i = the sequential fp64 sum of squares of row i in cosine_distance's order, s_i = 1.0 / sqrt(pp_i) (a correctly
+ *     rounded sqrt, then one division).  Member i of cluster j is skipped iff not (pp_i > 0 and pp_i < inf); it stays
+ *     assigned.  c_j[z] = the sum of (double) x_i[z] * s_i over the unskipped members in ascending item id, from 0.0, one
+ *     rounding per multiply and one per add, no fused multiply-add, no division by the count (d does not depend on the scale
+ *     of c).  A cluster without an unskipped member keeps its centroid.
+ *   Loop (morna_kmeans): c0_j = the widened row of seed_items[j]; the seeds are distinct (MORNA_E_INVALID), in range
+ *     (MORNA_E_RANGE) and eligible (MORNA_E_INVALID).  For t = 1 .. max_iter (>= 1): a(t) = assign(c(t-1)); if t > 1 and
+ *     a(t) == a(t-1), stop as converged; otherwise c(t) = update(a(t)).  Returned: the last a(t) in assign_out[n_items], its
+ *     distances to the c(t-1) it was made against in dist_out[n_items], those centroids in centroids_out[k][dim], the
+ *     clusters' sizes in sizes_out[k] (skipped members included), info_out[0] = t, info_out[1] = converged (0 or 1).
+ *     dist_out, centroids_out and sizes_out may be NULL.
+ *   morna_kmeans_assign: one assignment against k fp64 centroids in host memory.  A centroid with a non-finite element or
+ *     sum of squares: MORNA_E_INVALID, as morna_exact_search.  dist_out may be NULL.
+ *   Limits: 1 <= k <= min(MORNA_LABELS_MAX, |E|), so that every output can feed morna_label_sums (morna_kmeans_assign, whose
+ *     centroids are given and not drawn from E: 1 <= k <= MORNA_LABELS_MAX); k * n_items <= 2^29 (the scan values of all
+ *     centroids share one batch of at most 2 GiB).  Beyond either: MORNA_E_INVALID naming the limit.  An
+ *     empty index: MORNA_E_EMPTY.
+ *   The result does not depend on the grid, the batch, which scan ran or the order of any launch: the fp32 scan only chooses
+ *     which (row, centroid) pairs are evaluated in fp64 (the window is derived at kmeans_window, csrc/exact.hip), member lists
+ *     are placed by counting, and every sum runs in ascending item id.
+ *   morna_kmeans_stats  of the last call, stats[8]: ms of the scan (staging and scan kernels), of the pick (pick, offsets and
+ *     list kernels), of the resolve (the fp64 chains and the minimum) and of the update (member lists and sums), HIP events,
+ *     summed over the iterations; open rows (rows with more than one centroid inside the window, summed over the iterations);
+ *     fp64 chains run (summed); iterations; the largest cluster of the last iteration (0 for morna_kmeans_assign).  All 0
+ *     after a call that failed.
+ */
+int morna_kmeans(morna_index *h, const morna_restriction *r /* or NULL */, const int32_t *seed_items /* [k] */, int32_t k,
+                 int32_t max_iter, int32_t *assign_out /* [n_items] */, double *dist_out /* [n_items] or NULL */,
+                 double *centroids_out /* [k][dim] or NULL */, int32_t *sizes_out /* [k] or NULL */, int32_t *info_out /* [2] */);
+int morna_kmeans_assign(morna_index *h, const morna_restriction *r /* or NULL */, const double *centroids /* [k][dim] */, int32_t k,
+                        int32_t *assign_out /* [n_items] */, double *dist_out /* [n_items] or NULL */);
+int morna_kmeans_stats(const morna_index *h, double *stats /* [8] */);
+
+/*
  * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
  * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
  * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the

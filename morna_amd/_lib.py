@@ -124,6 +124,9 @@ SIGNATURES = {
     "morna_radius_query": (C.c_int, [_p, _i64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64)]),
     "morna_radius_free": (C.c_int, [_p]),
     "morna_exact_radius_stats": (C.c_int, [_p, _p]),
+    "morna_kmeans": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p]),
+    "morna_kmeans_assign": (C.c_int, [_p, _p, _p, _i32, _p, _p]),
+    "morna_kmeans_stats": (C.c_int, [_p, _p]),
     "morna_get_nns_prefix":(C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -533,6 +533,53 @@ class AnnoyIndex(object):
         return dict(scan_ms=float(stats[0]), select_ms=float(stats[1]), dist_ms=float(stats[2]), queries=int(stats[3]),
                     batches=int(stats[4]), candidates=int(stats[5]), results=int(stats[6]), window=float(stats[7]))
 
+    # ---- spherical k-means (include/morna_hip.h, "spherical k-means"; no counterpart in annoy) ----
+    def _kmeans_restriction(self, restriction):
+        if restriction is None:
+            return None
+        if not isinstance(restriction, Restriction) or restriction.owner is not self:
+            raise ValueError("the restriction was not made by this index (AnnoyIndex.restriction)")
+        return restriction._p
+
+    def kmeans(self, seed_items, max_iterations=100, restriction=None):
+        """Spherical k-means over the stored rows from the rows `seed_items` (distinct, eligible) as the first centroids: a dict
+        of assign (int32 [n_items], -1 for a row the restriction does not allow), dist (float64 [n_items], the distance to
+        the centroid the row was assigned against, -1.0 where assign is -1), centroids (float64 [k, f], the ones the last
+        assignment was made against), sizes (int32 [k]), iterations and converged.  restriction: an allow-list only."""
+        seeds = np.ascontiguousarray(seed_items, dtype=np.int32)
+        if seeds.ndim != 1:
+            raise ValueError("seed_items must be one-dimensional")
+        k, n = int(seeds.shape[0]), self.get_n_items()
+        assign = np.empty(n, np.int32)
+        dist = np.empty(n, np.float64)
+        centroids = np.empty((k, self.f), np.float64)
+        sizes = np.empty(k, np.int32)
+        info = np.zeros(2, np.int32)
+        check(lib().morna_kmeans(self._h, self._kmeans_restriction(restriction), ptr(seeds), k, int(max_iterations), ptr(assign),
+                                 ptr(dist), ptr(centroids), ptr(sizes), ptr(info)))
+        return dict(assign=assign, dist=dist, centroids=centroids, sizes=sizes, iterations=int(info[0]), converged=bool(info[1]))
+
+    def kmeans_assign(self, centroids, restriction=None):
+        """One assignment of every stored row to the nearest of `centroids` (fp64 [k, f]): (assign int32 [n_items], dist
+        float64 [n_items]), as kmeans returns them."""
+        centroids = np.ascontiguousarray(centroids, dtype=np.float64)
+        if centroids.ndim != 2 or centroids.shape[1] != self.f:
+            raise IndexError("centroids must be [k, %d]" % self.f)
+        n = self.get_n_items()
+        assign = np.empty(n, np.int32)
+        dist = np.empty(n, np.float64)
+        check(lib().morna_kmeans_assign(self._h, self._kmeans_restriction(restriction), ptr(centroids), int(centroids.shape[0]),
+                                        ptr(assign), ptr(dist)))
+        return assign, dist
+
+    def kmeans_stats(self):
+        """Of the last kmeans / kmeans_assign: ms of scan, pick, resolve and update; open rows, fp64 chains run, iterations,
+        the largest cluster of the last iteration."""
+        stats = np.zeros(8, np.float64)
+        check(lib().morna_kmeans_stats(self._h, ptr(stats)))
+        return dict(scan_ms=float(stats[0]), pick_ms=float(stats[1]), resolve_ms=float(stats[2]), update_ms=float(stats[3]),
+                    open_rows=int(stats[4]), chains=int(stats[5]), iterations=int(stats[6]), largest=int(stats[7]))
+
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):
         """Rows of the query samples of `terms` (index.ParsedLines from ParsedLines.query_terms) on this handle, beside the

@@ -410,6 +410,33 @@ def build_parser():
     pairs_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
                               help='print only the summary line (and the clusters with --clusters)')
     pairs_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    cluster_parser = subparsers.add_parser('cluster', help='partitions the indexed samples into k groups by their distance in the '
+                                                           'hashed space (spherical k-means on the GPU) and writes the groups '
+                                                           'file that labels, --leave-out-groups and --supersamples read')
+    cluster_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                                help='path to junction index basename (an index without row shards)')
+    cluster_parser.add_argument('-k', '--clusters', metavar='<int>', type=int, required=False, default=None,
+                                help='the number of groups, 1 to 4096 (with --init-ids: their number)')
+    cluster_parser.add_argument('--seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                                help='the first centroids are random.Random(seed).sample of the samples (default 0)')
+    cluster_parser.add_argument('--init-ids', metavar='<file>', type=str, required=False, default=None,
+                                help='the first centroids are the samples this file lists, one integer sample id per line')
+    cluster_parser.add_argument('--max-iterations', metavar='<int>', type=int, required=False, default=100,
+                                help='stop after this many assignments when the groups still change (default 100)')
+    cluster_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                                help='partition only the samples this file lists, one integer sample id per line')
+    cluster_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                                help='leave out the samples this file lists, one integer sample id per line')
+    cluster_parser.add_argument('-o', '--output', metavar='<file>', type=str, required=False, default=None,
+                                help='write the groups file here: "<label><TAB><id>,<id>,..." per group')
+    cluster_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                                help='print only the header and the line of every group')
+    cluster_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
+                                help='append the metadata keywords of every group\'s centre sample')
+    cluster_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    cluster_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    cluster_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    cluster_parser.add_argument('--leave-out-groups', type=str, required=False, default=None, help=argparse.SUPPRESS)
     return parser
 
 
@@ -460,6 +487,53 @@ def _check_pairs_flags(parser, args):
         both = sorted(set(args.within_ids) & set(args.without_ids))
         if both:
             parser.error("--within and --without both name sample id %d" % both[0])
+
+
+def _check_cluster_flags(parser, args):
+    """`cluster`: the flags of the searches that make no sense here, k or the first centroids, the restriction's files; argparse
+    errors, before any index is read.  Leaves the restriction's parts where _check_restriction_flags leaves them and the first
+    centroids in args.init_sample_ids."""
+    import os
+    from .junctions import parse_sample_ids_file
+    from .search import CLUSTER_SHARDS_REFUSAL, LABELS_MAX
+    refused = (("-e/--exact", args.exact, "every distance of a partition is exact already"),
+               ("--unhashed", args.unhashed, "the groups are formed in the hashed space, over the index's rows"),
+               ("--leave-out-groups", args.leave_out_groups is not None,
+                "cluster makes groups, it takes none: --within and --without choose the samples"))
+    for flag, on, why in refused:
+        if on:
+            parser.error("cluster cannot be used with %s: %s" % (flag, why))
+    if args.init_ids is not None and getattr(args, "seed_given", False):
+        parser.error("--seed and --init-ids cannot be used together")
+    if args.init_ids is None and args.clusters is None:
+        parser.error("cluster needs -k, the number of groups, or --init-ids")
+    if args.max_iterations < 1:
+        parser.error("--max-iterations takes a positive number (got %d)" % args.max_iterations)
+    args.within_ids = args.without_ids = args.leave_out = args.restriction = args.init_sample_ids = None
+    args.query_id = args.query_ids = None
+    try:
+        if args.init_ids is not None:
+            args.init_sample_ids = parse_sample_ids_file(args.init_ids)
+        if args.within is not None:
+            args.within_ids = parse_sample_ids_file(args.within)
+        if args.without is not None:
+            args.without_ids = parse_sample_ids_file(args.without)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+    if args.init_sample_ids is not None:
+        if len(set(args.init_sample_ids)) != len(args.init_sample_ids):
+            parser.error("--init-ids %s names a sample twice" % args.init_ids)
+        if args.clusters is not None and args.clusters != len(args.init_sample_ids):
+            parser.error("-k %d, but --init-ids names %d samples" % (args.clusters, len(args.init_sample_ids)))
+        args.clusters = len(args.init_sample_ids)
+    if not 1 <= args.clusters <= LABELS_MAX:
+        parser.error("-k takes 1 to %d groups (got %d)" % (LABELS_MAX, args.clusters))
+    if args.within_ids is not None and args.without_ids is not None:
+        both = sorted(set(args.within_ids) & set(args.without_ids))
+        if both:
+            parser.error("--within and --without both name sample id %d" % both[0])
+    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        parser.error(CLUSTER_SHARDS_REFUSAL)
 
 
 def _check_downsample_flags(parser, args):
@@ -826,6 +900,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_hashing_flags(parser, args)
     if args.subparser_name == 'labels':
         _check_labels_flags(parser, args)
+    if args.subparser_name == 'cluster':
+        _check_cluster_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -851,6 +927,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _labels(args, stdin, stdout)
     if args.subparser_name == 'pairs':
         return _pairs(args, stdout)
+    if args.subparser_name == 'cluster':
+        return _cluster(args, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -1089,6 +1167,28 @@ def _pairs(args, stdout):
     if args.clusters:
         for c in clusters:
             stdout.write(format_cluster_line(c))
+    return 0
+
+
+def _cluster(args, stdout):
+    """`cluster`: spherical k-means over the index rows on the GPU; the header, a line per group, a line per sample and, with
+    -o, the groups file."""
+    from .metadb import lookup_meta
+    from .search import MornaSearch, write_groups_file
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    args.restriction = _make_restriction(args, searcher)
+    clusters = searcher.cluster_samples(args.clusters, seed=args.seed, init_ids=args.init_sample_ids,
+                                        max_iterations=args.max_iterations, restriction=args.restriction)
+    meta = None
+    if args.metadata:
+        ids = [c for c in clusters.centres if c is not None]
+        meta = dict((i, str(m)) for i, m in zip(ids, lookup_meta(args.basename, ids)))   # (as results_output prints an entry)
+    stdout.write(clusters.header())
+    stdout.write(clusters.rows(meta))
+    if not args.summary_only:
+        stdout.write(clusters.sample_lines())
+    if args.output is not None:
+        write_groups_file(args.output, clusters.groups)
     return 0
 
 

@@ -1075,6 +1075,71 @@ int morna_exact_radius_stats(const morna_index *h, double *stats)
     return MORNA_OK;
 }
 
+// ---- spherical k-means (the contract is in morna_hip.h) -----------------------------------------------------------
+
+int morna_kmeans(morna_index *h, const morna_restriction *r, const int32_t *seed_items, int32_t k, int32_t max_iter,
+                 int32_t *assign_out, double *dist_out, double *centroids_out, int32_t *sizes_out, int32_t *info_out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
+    if (!seed_items || !assign_out || !info_out) {
+        set_error("kmeans: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("kmeans is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = MORNA_OK;
+    try {   // (host vectors: bad_alloc must not cross the C ABI)
+        rc = kmeans(h, r, seed_items, nullptr, k, max_iter, assign_out, dist_out, centroids_out, sizes_out, info_out);
+    } catch (const std::exception &e) {
+        set_error("kmeans: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK)
+        for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
+    return rc;
+}
+
+int morna_kmeans_assign(morna_index *h, const morna_restriction *r, const double *centroids, int32_t k, int32_t *assign_out,
+                        double *dist_out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
+    if (!centroids || !assign_out) {
+        set_error("kmeans_assign: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("kmeans_assign is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = MORNA_OK;
+    try {
+        rc = kmeans(h, r, nullptr, centroids, k, 1, assign_out, dist_out, nullptr, nullptr, nullptr);
+    } catch (const std::exception &e) {
+        set_error("kmeans_assign: %s", e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK)
+        for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
+    return rc;
+}
+
+int morna_kmeans_stats(const morna_index *h, double *stats)
+{
+    if (!h || !stats) {
+        set_error("kmeans_stats: null pointer");
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
+    for (int i = 0; i < 8; i++) stats[i] = h->kmeans_stats[i];
+    return MORNA_OK;
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

@@ -389,6 +389,8 @@ struct morna_index {
     // radius search (exact.hip, exact_radius): chunk counts, offsets and per-query flags of a batch; the last call's statistics
     morna::DevBuf<uint8_t> rd_ws;
     double radius_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // spherical k-means (exact.hip, kmeans): the last call's statistics (its arrays are pieces of ex_ws, ex_cand and ex_cdist)
+    double kmeans_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
@@ -560,6 +562,10 @@ int label_sums(morna_index *h, const morna_restriction *rst, const ExactQueries 
 // the lists are appended to *out (empty on entry)
 int exact_radius(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *q_group_host,
                  const int32_t *after_host, double radius, morna_radius *out);
+// morna_kmeans (seeds [k], cent_host null) and morna_kmeans_assign (cent_host [k][dim], seeds null) behind their null checks
+// (morna_hip.h, "spherical k-means"): rst and every output but assign_out may be null
+int kmeans(morna_index *h, const morna_restriction *rst, const int32_t *seeds, const double *cent_host, int32_t k, int32_t max_iter,
+           int32_t *assign_out, double *dist_out, double *cent_out, int32_t *sizes_out, int32_t *info_out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

@@ -1596,4 +1596,534 @@ int exact_radius(morna_index *h, const morna_restriction *rst, const ExactQuerie
     return MORNA_OK;
 }
 
+// =============================================================== spherical k-means (morna_hip.h, "spherical k-means")
+// The transposed selection: for every ROW the nearest of k fp64 centroids, from the scan of the family's front with the
+// centroids as its queries (exact_front_batch), then
+//   kmeans_pick_kernel     per row: the smallest scan value over the centroids and the centroids inside its window
+//                          (kmeans_window), counted; one survivor decides the row, more make it an open row
+//   radius_offsets_kernel  the exclusive prefix of the workgroups' counts
+//   kmeans_list_kernel     the same walk: one entry per (row, centroid inside the window), placed by block scan
+//   kmeans_resolve_kernel  per entry the reference's fp64 chain (exact_ref_distance)
+//   kmeans_min_kernel      per row the minimum of its entries by (distance, centroid), NaN behind every number
+// and for the loop around it
+//   kmeans_norms_kernel    once per call: 1 / sqrt(pp) of every row, pp the sequential fp64 sum of squares
+//   kmeans_hist_kernel     per chunk of rows the members of every cluster, counted; the rows that changed cluster, counted
+//   kmeans_starts_kernel   per cluster the prefix of its chunk counts and its size; the prefix of the sizes
+//   kmeans_scatter_kernel  the same chunks: cluster-major member lists in ascending id (a row's place is a count of the rows
+//                          in front of it, never the arrival order of an atomic)
+//   kmeans_update_kernel   per (cluster, 256 columns): the members' scaled rows added in list order, one rounding per
+//                          multiply and per add
+// Integer atomics count (open rows, changed rows, a chunk's histogram in LDS); none decides a position or a value.
+
+#define KM_THREADS 256
+#define KM_WAVES (KM_THREADS / WAVE)
+#define KM_CHUNK 1024                   // rows of a member-list chunk (KM_THREADS rows a step)
+#define KM_AHEAD 8                      // member rows in flight per thread of kmeans_update_kernel
+#define KM_MAX_VALUES ((int64_t)1 << 29)   // scan values of one batch (2 GiB): all centroids share one batch
+
+// The window of the assignment: centroid j is evaluated for row i iff its scan value
+//     v_j <= min_j' v_j' + eps + 2 dpad 2^-50 + 2^-48,     eps = exact_scan_eps(dpad, which scan ran), compared in fp64.
+// Derivation.  Let t_j be the true 2 - 2cos of (i, j), D_j the reference's fp64 radicand and d_j = sqrt(D_j) correctly
+// rounded, the distance exact_ref_distance returns.  The scan keeps |v_j - t_j| <= eps / 2 (eps is that bound taken twice,
+// for the two values the top-k threshold of exact_select_body compares: here too two scan values are compared, the
+// minimum's and the candidate's, so all of eps is used).  The fp64 chain keeps |D_j - t_j| <= dpad 2^-50.  Let m be the
+// centroid of the smallest scan value and w the winner, d_w <= d_m.  The rounded sqrt is monotone but not injective:
+// d_w <= d_m gives only D_w <= D_m (1 + 2^-52)^2, distinct radicands can round to one distance and the tie then goes to the
+// lower index, which may be the one of the larger radicand; with D <= 4 that slack is below 2^-48.  So
+//     t_w <= D_w + dpad 2^-50 <= D_m + 2^-48 + dpad 2^-50 <= t_m + 2 dpad 2^-50 + 2^-48,   v_w <= v_m + eps + 2 dpad 2^-50 + 2^-48.
+// The two extra terms are at most 2^-34 + 2^-48 for dpad <= 32768 beside an eps of at least 2^-19; they are added all the same.
+// NaN distances.  A radicand is negative only when the fp64 cosine rounds above 1: then t_j <= dpad 2^-50 and v_j <= eps / 2 +
+// dpad 2^-50, below the window itself.  A NaN orders BEHIND every number, so the nearest centroid by the scan may lose to any
+// other: a row whose smallest scan value is inside [.., window] is open against every centroid.  (Such a row is all but
+// parallel to a centroid: the seeds in the first iteration, the only member of a cluster later.)
+// Outside the scan's domain the bound does not hold: a row on the list of exact_outside_kernel (scan values NaN) is open
+// against every centroid, and a centroid with a zero image (exact_prep_kernel: the zero vector, or a sum of squares outside
+// [EX_QQ_LO, EX_QQ_HI]) is evaluated for every row and takes no part in the minimum.
+static double kmeans_window(int32_t dpad, float eps) { return (double)eps + 2.0 * (double)dpad * 0x1p-50 + 0x1p-48; }
+
+struct KmeansArgs {
+    const float *approx;       // [k][n_items] the scan values, NaN for the rows outside the scan's domain
+    const float *qn2;          // [k] 0: the centroid has a zero image
+    const uint32_t *deny;      // the restriction's bitmap, or null: every row is eligible
+    int64_t n_items;
+    int32_t k;
+    double window;
+};
+
+__device__ __forceinline__ bool kmeans_eligible(const uint32_t *__restrict__ deny, int64_t i)
+{
+    return !deny || !((deny[i >> 5] >> (i & 31)) & 1u);
+}
+
+// row i: lim = its smallest scan value + the window; all: it is open against every centroid.  The reads of a wave are 64
+// consecutive rows of one centroid.
+__device__ __forceinline__ void kmeans_row_view(const KmeansArgs &A, int64_t i, double &lim, bool &all)
+{
+    float vmin = INFINITY;
+    all = false;
+    for (int j = 0; j < A.k; j++) {
+        const float v = A.approx[(int64_t)j * A.n_items + i];
+        if (A.qn2[j] == 0.f) continue;
+        if (v != v) all = true;
+        else vmin = fminf(vmin, v);
+    }
+    if ((double)vmin <= A.window) all = true;
+    lim = (double)vmin + A.window;
+}
+
+__device__ __forceinline__ bool kmeans_candidate(const KmeansArgs &A, int64_t i, int j, double lim, bool all)
+{
+    if (all || A.qn2[j] == 0.f) return true;
+    return (double)A.approx[(int64_t)j * A.n_items + i] <= lim;
+}
+
+__device__ inline int km_block_sum(int v, int *s_w, int tid)
+{
+    v = wave_sum_i32(v);
+    __syncthreads();
+    if ((tid & (WAVE - 1)) == 0) s_w[tid / WAVE] = v;
+    __syncthreads();
+    int total = 0;
+#pragma unroll
+    for (int u = 0; u < KM_WAVES; u++) total += s_w[u];
+    return total;
+}
+
+// exclusive prefix of v over the workgroup's threads
+__device__ inline int km_block_excl(int v, int *s_w, int tid)
+{
+    const int lane = tid & (WAVE - 1), w = tid / WAVE;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const int up = __shfl_up(inc, off, WAVE);
+        if (lane >= off) inc += up;
+    }
+    __syncthreads();
+    if (lane == WAVE - 1) s_w[w] = inc;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int u = 0; u < KM_WAVES; u++) base += u < w ? s_w[u] : 0;
+    return base + inc - v;
+}
+
+// cnt[i]: the centroids to evaluate for row i (0: not eligible, and its answer -1 / -1.0 is written here); blk[b]: their sum
+// over workgroup b; totals[1] += the open rows
+__global__ __launch_bounds__(KM_THREADS) void kmeans_pick_kernel(KmeansArgs A, int32_t *__restrict__ cnt, int32_t *__restrict__ blk,
+                                                                 int32_t *__restrict__ totals, int32_t *__restrict__ assign,
+                                                                 double *__restrict__ dist)
+{
+    __shared__ int s_w[KM_WAVES];
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * KM_THREADS + tid;
+    int c = 0;
+    if (i < A.n_items) {
+        if (!kmeans_eligible(A.deny, i)) {
+            assign[i] = -1;
+            dist[i] = -1.0;
+        } else {
+            double lim;
+            bool all;
+            kmeans_row_view(A, i, lim, all);
+            for (int j = 0; j < A.k; j++) c += kmeans_candidate(A, i, j, lim, all) ? 1 : 0;
+        }
+        cnt[i] = c;
+    }
+    const int total = km_block_sum(c, s_w, tid);
+    const int open = km_block_sum(c > 1 ? 1 : 0, s_w, tid);
+    if (tid == 0) {
+        blk[blockIdx.x] = total;
+        if (open) atomicAdd(&totals[1], open);
+    }
+}
+
+// the entries of row i at rowoff[i] .. + cnt[i], ascending by centroid; blkoff: the exclusive prefix of blk
+__global__ __launch_bounds__(KM_THREADS) void kmeans_list_kernel(KmeansArgs A, const int32_t *__restrict__ cnt,
+                                                                 const int32_t *__restrict__ blkoff, int32_t *__restrict__ rowoff,
+                                                                 int32_t *__restrict__ item_row, int32_t *__restrict__ item_j)
+{
+    __shared__ int s_w[KM_WAVES];
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * KM_THREADS + tid;
+    const int c = i < A.n_items ? cnt[i] : 0;
+    const int off = blkoff[blockIdx.x] + km_block_excl(c, s_w, tid);
+    if (i < A.n_items) rowoff[i] = off;
+    if (c > 0) {
+        double lim;
+        bool all;
+        kmeans_row_view(A, i, lim, all);
+        int at = 0;
+        for (int j = 0; j < A.k; j++)
+            if (kmeans_candidate(A, i, j, lim, all) && at < c) {
+                item_row[off + at] = (int32_t)i;
+                item_j[off + at] = j;
+                at++;
+            }
+    }
+}
+
+// one thread per (row, centroid) entry: d(i, c_j), the reference's chain
+__global__ __launch_bounds__(WAVE) void kmeans_resolve_kernel(const float *__restrict__ X, int32_t dim, int32_t dpad,
+                                                              const double *__restrict__ Qd /* [k][dim] */,
+                                                              const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_j,
+                                                              int64_t total, double *__restrict__ item_d)
+{
+    const int64_t t = (int64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (t >= total) return;
+    item_d[t] = exact_ref_distance((const float4 *)(X + (int64_t)item_row[t] * dpad), Qd + (int64_t)item_j[t] * dim, dim);
+}
+
+// a_i: the entry of the smallest distance, the first of equal ones (the entries ascend by centroid), a NaN behind every number;
+// a NaN is returned as the canonical quiet NaN
+__global__ __launch_bounds__(KM_THREADS) void kmeans_min_kernel(const int32_t *__restrict__ cnt, const int32_t *__restrict__ rowoff,
+                                                                const int32_t *__restrict__ item_j, const double *__restrict__ item_d,
+                                                                int64_t n_items, int32_t *__restrict__ assign, double *__restrict__ dist)
+{
+    const int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x;
+    if (i >= n_items) return;
+    const int c = cnt[i];
+    if (c <= 0) return;
+    const int off = rowoff[i];
+    double bd = item_d[off];
+    int32_t bj = item_j[off];
+    for (int w = 1; w < c; w++) {
+        const double d = item_d[off + w];
+        if (d < bd || (bd != bd && d == d)) {
+            bd = d;
+            bj = item_j[off + w];
+        }
+    }
+    assign[i] = bj;
+    dist[i] = bd == bd ? bd : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// scale[i] = s_i = 1 / sqrt(pp_i), pp_i the sum of squares of row i in cosine_distance's order; -1: the member is skipped
+// (not (0 < pp_i < inf))
+__global__ __launch_bounds__(KM_THREADS) void kmeans_norms_kernel(const float *__restrict__ X, int64_t n_items, int32_t dim, int32_t dpad,
+                                                                  double *__restrict__ scale)
+{
+    const int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x;
+    if (i >= n_items) return;
+    const float4 *row = (const float4 *)(X + i * dpad);
+    double pp = 0.0;
+    for (int z0 = 0; z0 < dim; z0 += 4) {
+        const float4 x = row[z0 / 4];
+        const float e4[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+            if (z0 + v < dim) {
+                const double e = (double)e4[v];
+                pp = __dadd_rn(pp, __dmul_rn(e, e));
+            }
+    }
+    scale[i] = pp > 0.0 && pp < INFINITY ? __ddiv_rn(1.0, __dsqrt_rn(pp)) : -1.0;
+}
+
+// chunk_cnt[c][j]: the rows of chunk c assigned to cluster j; totals[2] += the rows whose cluster changed
+__global__ __launch_bounds__(KM_THREADS) void kmeans_hist_kernel(const int32_t *__restrict__ assign, const int32_t *__restrict__ prev,
+                                                                 int64_t n_items, int32_t k, int32_t *__restrict__ chunk_cnt,
+                                                                 int32_t *__restrict__ totals)
+{
+    __shared__ int s_w[KM_WAVES];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int *hist = (int *)smem;   // [k]
+    const int tid = threadIdx.x;
+    for (int j = tid; j < k; j += KM_THREADS) hist[j] = 0;
+    __syncthreads();
+    const int64_t r0 = (int64_t)blockIdx.x * KM_CHUNK;
+    int changed = 0;
+    for (int s = 0; s < KM_CHUNK; s += KM_THREADS) {
+        const int64_t i = r0 + s + tid;
+        if (i < n_items) {
+            const int32_t a = assign[i];
+            changed += a != prev[i] ? 1 : 0;
+            if (a >= 0 && a < k) atomicAdd(&hist[a], 1);
+        }
+    }
+    changed = km_block_sum(changed, s_w, tid);
+    for (int j = tid; j < k; j += KM_THREADS) chunk_cnt[(int64_t)blockIdx.x * k + j] = hist[j];
+    if (tid == 0 && changed) atomicAdd(&totals[2], changed);
+}
+
+// one workgroup: chunk_cnt[c][j] becomes the members of cluster j in the chunks before c, sizes[j] their total, start[j] the
+// exclusive prefix of the sizes (k <= 4096)
+__global__ __launch_bounds__(KM_THREADS) void kmeans_starts_kernel(int32_t *__restrict__ chunk_cnt, int32_t chunks, int32_t k,
+                                                                   int32_t *__restrict__ sizes, int32_t *__restrict__ start)
+{
+    __shared__ int s_w[KM_WAVES];
+    __shared__ int s_sz[MORNA_LABELS_MAX];
+    const int tid = threadIdx.x;
+    for (int j = tid; j < k; j += KM_THREADS) {
+        int run = 0;
+        for (int c = 0; c < chunks; c++) {
+            const int v = chunk_cnt[(int64_t)c * k + j];
+            chunk_cnt[(int64_t)c * k + j] = run;
+            run += v;
+        }
+        s_sz[j] = run;
+        sizes[j] = run;
+    }
+    __syncthreads();
+    const int per = (k + KM_THREADS - 1) / KM_THREADS, lo = tid * per, hi = lo + per < k ? lo + per : k;
+    int mine = 0;
+    for (int j = lo; j < hi; j++) mine += s_sz[j];
+    int at = km_block_excl(mine, s_w, tid);
+    for (int j = lo; j < hi; j++) {
+        start[j] = at;
+        at += s_sz[j];
+    }
+}
+
+// member[start[j] + ...]: the rows of cluster j in ascending id.  A chunk takes its rows KM_THREADS at a time; a row's place
+// is the cluster's running count plus the rows of the step in front of it with the same cluster.
+__global__ __launch_bounds__(KM_THREADS) void kmeans_scatter_kernel(const int32_t *__restrict__ assign, int64_t n_items, int32_t k,
+                                                                    const int32_t *__restrict__ chunk_off, const int32_t *__restrict__ start,
+                                                                    int32_t *__restrict__ member)
+{
+    __shared__ int s_lab[KM_THREADS];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int *run = (int *)smem;   // [k]
+    const int tid = threadIdx.x;
+    for (int j = tid; j < k; j += KM_THREADS) run[j] = start[j] + chunk_off[(int64_t)blockIdx.x * k + j];
+    const int64_t r0 = (int64_t)blockIdx.x * KM_CHUNK;
+    for (int s = 0; s < KM_CHUNK; s += KM_THREADS) {
+        const int64_t i = r0 + s + tid;
+        int32_t a = i < n_items ? assign[i] : -1;
+        if (a >= k) a = -1;
+        s_lab[tid] = a;
+        __syncthreads();
+        int before = 0;
+        bool last = true;
+        if (a >= 0) {
+            for (int u = 0; u < KM_THREADS; u++) {
+                const bool same = s_lab[u] == a;
+                before += same && u < tid ? 1 : 0;
+                last = last && !(same && u > tid);
+            }
+            member[run[a] + before] = (int32_t)i;
+        }
+        __syncthreads();
+        if (a >= 0 && last) run[a] += before + 1;
+        __syncthreads();
+    }
+}
+
+// c_j[z] = sum of (double)x_i[z] * s_i over the unskipped members of cluster j in list order, from 0.0, every product and
+// every sum rounded once (no fma); a cluster without an unskipped member keeps its centroid.  KM_AHEAD member rows are
+// requested before the first of them is consumed; the sum itself is one dependent chain as long as the cluster.
+__global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(const float *__restrict__ X, int32_t dim, int32_t dpad,
+                                                                   const int32_t *__restrict__ member, const int32_t *__restrict__ start,
+                                                                   const int32_t *__restrict__ sizes, const double *__restrict__ scale,
+                                                                   double *__restrict__ cent /* [k][dim] */)
+{
+    const int j = blockIdx.x, z = blockIdx.y * KM_THREADS + threadIdx.x;
+    const bool live = z < dim;
+    const int32_t *mem = member + start[j];
+    const int n = sizes[j];
+    double acc = 0.0;
+    bool any = false;
+    for (int m0 = 0; m0 < n; m0 += KM_AHEAD) {
+        float x[KM_AHEAD];
+        double s[KM_AHEAD];
+#pragma unroll
+        for (int u = 0; u < KM_AHEAD; u++) {
+            const int32_t id = m0 + u < n ? mem[m0 + u] : -1;
+            s[u] = id >= 0 ? scale[id] : -1.0;
+            x[u] = id >= 0 && live ? X[(int64_t)id * dpad + z] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < KM_AHEAD; u++)
+            if (s[u] > 0.0) {
+                acc = __dadd_rn(acc, __dmul_rn((double)x[u], s[u]));
+                any = true;
+            }
+    }
+    if (any && live) cent[(int64_t)j * dim + z] = acc;
+}
+
+// morna_kmeans (seeds: the loop) and morna_kmeans_assign (cent_host: one assignment) behind their null checks.
+int kmeans(morna_index *h, const morna_restriction *rst, const int32_t *seeds, const double *cent_host, int32_t k, int32_t max_iter,
+           int32_t *assign_out, double *dist_out, double *cent_out, int32_t *sizes_out, int32_t *info_out)
+{
+    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
+    const bool loop = seeds != nullptr;
+    const char *who = loop ? "kmeans" : "kmeans_assign";
+    ExactFront F;
+    double *cent = nullptr, *scale = nullptr, *d_dist = nullptr;
+    int32_t *d_assign = nullptr, *d_prev = nullptr, *cnt = nullptr, *rowoff = nullptr, *blk = nullptr, *totals = nullptr;
+    int32_t *member = nullptr, *sizes = nullptr, *start = nullptr, *chunk_cnt = nullptr;
+    int64_t nblk = 0, chunks = 0;
+    MORNA_TRY(exact_front(h, who, who, rst, loop ? ExactQueries::stored(seeds) : ExactQueries::host(cent_host), (int64_t)k, nullptr, 0,
+                          [&]() -> int {
+        const int64_t N = h->n_items;
+        if (rst && rst->has_group) {
+            set_error("%s: a restriction that holds groups is not taken, only an allow-list", who);
+            return MORNA_E_INVALID;
+        }
+        const int64_t n_elig = rst ? rst->n_allowed : N;
+        // (given centroids are not drawn from E: only the loop, whose seeds are k distinct eligible rows, is bounded by |E|)
+        if (k < 1 || k > MORNA_LABELS_MAX || (loop && k > n_elig)) {
+            set_error("%s: k = %d, 1 to min(%d, the %lld eligible rows) are taken", who, k, MORNA_LABELS_MAX, (long long)n_elig);
+            return MORNA_E_INVALID;
+        }
+        if ((int64_t)k * N > KM_MAX_VALUES) {
+            set_error("%s: k * n_items = %lld, above the 2^29 = %lld scan values of one batch", who, (long long)((int64_t)k * N),
+                      (long long)KM_MAX_VALUES);
+            return MORNA_E_INVALID;
+        }
+        if (!loop) return MORNA_OK;
+        if (max_iter < 1) {
+            set_error("kmeans: max_iter = %d, at least 1 is taken", max_iter);
+            return MORNA_E_INVALID;
+        }
+        for (int32_t j = 0; j < k; j++)
+            if (seeds[j] < 0 || seeds[j] >= N) {
+                set_error("Item index %d out of range [0, %lld)", seeds[j], (long long)N);
+                return MORNA_E_RANGE;
+            }
+        std::vector<int32_t> sorted(seeds, seeds + k);
+        std::sort(sorted.begin(), sorted.end());
+        for (int32_t j = 1; j < k; j++)
+            if (sorted[(size_t)j] == sorted[(size_t)j - 1]) {
+                set_error("kmeans: the seed item %d is given twice", sorted[(size_t)j]);
+                return MORNA_E_INVALID;
+            }
+        if (rst) {
+            std::vector<uint32_t> deny((size_t)(N + 31) / 32);
+            HIP_TRY(hipMemcpyAsync(deny.data(), rst->deny.p, deny.size() * 4, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            for (int32_t j = 0; j < k; j++)
+                if ((deny[(size_t)seeds[j] >> 5] >> (seeds[j] & 31)) & 1u) {
+                    set_error("kmeans: the seed item %d is not eligible under the restriction", seeds[j]);
+                    return MORNA_E_INVALID;
+                }
+        }
+        return MORNA_OK;
+    }, [&](Carver &c, int64_t) {
+        const size_t N = (size_t)h->n_items;
+        nblk = (int64_t)((N + KM_THREADS - 1) / KM_THREADS);
+        chunks = (int64_t)((N + KM_CHUNK - 1) / KM_CHUNK);
+        cent = c.take<double>((size_t)k * h->dim);
+        scale = c.take<double>(loop ? N : 0);
+        d_dist = c.take<double>(N);
+        d_assign = c.take<int32_t>(N);
+        d_prev = c.take<int32_t>(loop ? N : 0);
+        cnt = c.take<int32_t>(N);
+        rowoff = c.take<int32_t>(N);
+        blk = c.take<int32_t>((size_t)nblk);
+        totals = c.take<int32_t>(4);   // entries | open rows | rows that changed cluster
+        member = c.take<int32_t>(loop ? N : 0);
+        sizes = c.take<int32_t>(loop ? (size_t)k : 0);
+        start = c.take<int32_t>(loop ? (size_t)k : 0);
+        chunk_cnt = c.take<int32_t>(loop ? (size_t)chunks * k : 0);
+    }, F));
+    const int64_t N = F.N;
+    const int32_t D = F.D, dpad = F.dpad;
+    if (F.batch != k) {   // (k * N <= KM_MAX_VALUES was checked: the front's cap is the same number)
+        set_error("%s: the centroids do not share one batch", who);
+        return MORNA_E_INVALID;
+    }
+    const uint32_t *deny = rst ? rst->deny.p : nullptr;
+    HipEvents ev;
+    MORNA_TRY(ev.create(9));
+    if (loop) {
+        HIP_TRY(hipMemcpyAsync(F.d_items, seeds, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)k), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, F.d_items, D, cent);
+        hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->X.p, N, D, dpad, scale);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_prev, 0xff, (size_t)N * 4, h->stream));
+        F.Q = ExactQueries::device64(cent);   // every iteration scans the centroids where the update left them
+    }
+    int32_t h_tot[4] = {0, 0, 0, 0};
+    double ms[4] = {0.0, 0.0, 0.0, 0.0}, open_rows = 0.0, chains = 0.0;
+    int32_t iterations = 0, converged = 0;
+    bool update_pending = false;
+    for (int32_t t = 1;; t++) {
+        HIP_TRY(hipMemsetAsync(totals, 0, 16, h->stream));
+        float eps = 0.f;
+        MORNA_TRY(exact_front_batch(h, F, 0, k, true, &ev, &eps));   // events 0, 1
+        KmeansArgs A;
+        A.approx = F.approx;
+        A.qn2 = F.qn2;
+        A.deny = deny;
+        A.n_items = N;
+        A.k = k;
+        A.window = kmeans_window(dpad, eps);
+        hipLaunchKernelGGL(kmeans_pick_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, A, cnt, blk, totals, d_assign, d_dist);
+        hipLaunchKernelGGL(radius_offsets_kernel, dim3(1), dim3(WAVE), 0, h->stream, blk, (int32_t)nblk, totals);
+        HIP_TRY(hipGetLastError());
+        MORNA_TRY(ev.record(2, h->stream));
+        HIP_TRY(hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the entries size their storage
+        if (update_pending) MORNA_TRY(ev.elapsed(7, 8, &ms[3]));
+        update_pending = false;
+        const int64_t total = h_tot[0];
+        MORNA_TRY(h->ex_cand.alloc((size_t)std::max<int64_t>(2 * total, 1)));
+        MORNA_TRY(h->ex_cdist.alloc((size_t)std::max<int64_t>(total, 1)));
+        int32_t *item_row = h->ex_cand.p, *item_j = h->ex_cand.p + total;
+        MORNA_TRY(ev.record(3, h->stream));
+        hipLaunchKernelGGL(kmeans_list_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, A, cnt, blk, rowoff, item_row, item_j);
+        HIP_TRY(hipGetLastError());
+        MORNA_TRY(ev.record(4, h->stream));
+        if (total > 0)
+            hipLaunchKernelGGL(kmeans_resolve_kernel, dim3((unsigned)((total + WAVE - 1) / WAVE)), dim3(WAVE), 0, h->stream, h->X.p, D, dpad,
+                               F.Qd, item_row, item_j, total, h->ex_cdist.p);
+        hipLaunchKernelGGL(kmeans_min_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, cnt, rowoff, item_j, h->ex_cdist.p, N,
+                           d_assign, d_dist);
+        HIP_TRY(hipGetLastError());
+        MORNA_TRY(ev.record(5, h->stream));
+        if (loop) {
+            hipLaunchKernelGGL(kmeans_hist_kernel, dim3((unsigned)chunks), dim3(KM_THREADS), (size_t)k * 4, h->stream, d_assign, d_prev, N, k,
+                               chunk_cnt, totals);
+            hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(KM_THREADS), 0, h->stream, chunk_cnt, (int32_t)chunks, k, sizes, start);
+            hipLaunchKernelGGL(kmeans_scatter_kernel, dim3((unsigned)chunks), dim3(KM_THREADS), (size_t)k * 4, h->stream, d_assign, N, k,
+                               chunk_cnt, start, member);
+            HIP_TRY(hipGetLastError());
+        }
+        MORNA_TRY(ev.record(6, h->stream));
+        HIP_TRY(hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the rows that changed cluster
+        MORNA_TRY(ev.elapsed(0, 1, &ms[0]));
+        MORNA_TRY(ev.elapsed(1, 2, &ms[1]));
+        MORNA_TRY(ev.elapsed(3, 4, &ms[1]));
+        MORNA_TRY(ev.elapsed(4, 5, &ms[2]));
+        MORNA_TRY(ev.elapsed(5, 6, &ms[3]));
+        open_rows += (double)h_tot[1];
+        chains += (double)total;
+        iterations = t;
+        if (!loop) break;
+        if (t > 1 && h_tot[2] == 0) {
+            converged = 1;
+            break;
+        }
+        if (t == max_iter) break;   // (the update after the last assignment would not be seen)
+        MORNA_TRY(ev.record(7, h->stream));
+        hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)k, (unsigned)((D + KM_THREADS - 1) / KM_THREADS)), dim3(KM_THREADS), 0,
+                           h->stream, h->X.p, D, dpad, member, start, sizes, scale, cent);
+        HIP_TRY(hipGetLastError());
+        MORNA_TRY(ev.record(8, h->stream));
+        update_pending = true;
+        std::swap(d_assign, d_prev);   // the next assignment is written beside this one
+    }
+    // the last assignment, its distances and the centroids it was made against (F.Qd: the front's copy of them)
+    std::vector<int32_t> h_sizes(loop ? (size_t)k : 0);
+    HIP_TRY(hipMemcpyAsync(assign_out, d_assign, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
+    if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, d_dist, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cent_out) HIP_TRY(hipMemcpyAsync(cent_out, F.Qd, (size_t)k * D * 8, hipMemcpyDeviceToHost, h->stream));
+    if (loop) HIP_TRY(hipMemcpyAsync(h_sizes.data(), sizes, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (sizes_out) memcpy(sizes_out, h_sizes.data(), (size_t)k * 4);
+    if (info_out) {
+        info_out[0] = iterations;
+        info_out[1] = converged;
+    }
+    for (int i = 0; i < 4; i++) h->kmeans_stats[i] = ms[i];
+    h->kmeans_stats[4] = open_rows;
+    h->kmeans_stats[5] = chains;
+    h->kmeans_stats[6] = (double)iterations;
+    h->kmeans_stats[7] = loop ? (double)*std::max_element(h_sizes.begin(), h_sizes.end()) : 0.0;
+    return MORNA_OK;
+}
+
 }  // namespace morna

@@ -426,6 +426,99 @@ def format_label_rows(rows):
     return format_recall_rows(rows)
 
 
+# ---- morna cluster ----------------------------------------------------------------------------------
+CLUSTER_SHARDS_REFUSAL = ("cluster is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                          "run it on an index built without --shards")
+CLUSTER_MAX_VALUES = 1 << 29    # k * samples: the scan values of all centroids share one batch of 2 GiB
+
+
+def cluster_max_refusal(k, n_eligible):
+    return ("cluster takes 1 to %d clusters, and no more than the %d samples it partitions (got %d): every cluster is a label "
+            "that `labels --labels` can read" % (LABELS_MAX, n_eligible, k))
+
+
+def cluster_seed_items(eligible, k, seed):
+    """The first centroids of `morna cluster --seed`: random.Random(seed).sample of the eligible INTERNAL ids in ascending
+    order, k of them."""
+    import random
+    eligible = sorted(int(i) for i in eligible)
+    if not 1 <= k <= len(eligible):
+        raise ValueError(cluster_max_refusal(k, len(eligible)))
+    return random.Random(seed).sample(eligible, k)
+
+
+def cluster_label(j):
+    return "c%04d" % j
+
+
+def cluster_table(assign, dist, k):
+    """Per cluster of an assignment (assign[i] in [-1, k), dist[i] the member's distance): (size, mean member distance,
+    centre), the mean summed on the host in ascending id and None for an empty cluster, the centre the member (an INTERNAL
+    id) with the smallest distance, the lowest id on ties, a NaN behind every number, None for an empty cluster."""
+    size, total, centre, best = [0] * k, [0.0] * k, [None] * k, [None] * k
+    for i, (j, d) in enumerate(zip(assign.tolist(), dist.tolist())):
+        if j < 0:
+            continue
+        size[j] += 1
+        total[j] += d
+        if centre[j] is None or d < best[j] or (best[j] != best[j] and d == d):
+            centre[j], best[j] = i, d
+    return [(size[j], total[j] / size[j] if size[j] else None, centre[j]) for j in range(k)]
+
+
+def format_clusters_header(k, iterations, converged, n_samples, mean):
+    """The first line of `morna cluster`."""
+    return "# clusters %d\titerations %d\tconverged %s\tsamples %d\tmean distance %s\n" % (
+        k, iterations, "yes" if converged else "no", n_samples, format_distance(mean))
+
+
+def format_clusters_row(label, size, mean, centre, meta=None):
+    """One line per cluster: label, size, mean member distance, centre sample ('-' for both in an empty cluster), and with
+    meta (a string) that sample's keywords."""
+    line = "%s\t%d\t%s\t%s" % (label, size, "-" if mean is None else format_distance(mean), "-" if centre is None else centre)
+    if meta is not None:
+        line += "\t%s" % meta
+    return line + "\n"
+
+
+def format_clusters_sample(sample_id, label, d):
+    return "%s\t%s\t%s\n" % (sample_id, label, format_distance(d))
+
+
+def write_groups_file(path, groups):
+    """[(label, [ids])] as the groups file junctions.parse_groups_file reads back unchanged."""
+    with open(path, "w") as fh:
+        for label, ids in groups:
+            fh.write("%s\t%s\n" % (label, ",".join(str(i) for i in ids)))
+
+
+class SearchClusters(object):
+    """MornaSearch.cluster_samples: groups [(label, [EXTERNAL ids])] with the members in ascending internal id; per cluster
+    sizes, means (mean member distance, None when empty) and centres (EXTERNAL id of the member nearest its centroid, None
+    when empty); samples [(EXTERNAL id, cluster, distance)] in ascending internal id; iterations, converged, n_samples, the
+    mean distance over all samples, and stats (AnnoyIndex.kmeans_stats)."""
+
+    def __init__(self, groups, sizes, means, centres, samples, iterations, converged, stats):
+        self.groups, self.sizes, self.means, self.centres, self.samples = groups, sizes, means, centres, samples
+        self.iterations, self.converged, self.stats = iterations, converged, stats
+        self.n_samples = len(samples)
+        total = 0.0
+        for _, _, d in samples:
+            total += d
+        self.mean = total / self.n_samples if self.n_samples else float("nan")
+
+    def header(self):
+        return format_clusters_header(len(self.groups), self.iterations, self.converged, self.n_samples, self.mean)
+
+    def rows(self, meta=None):
+        """The per-cluster lines; meta: {EXTERNAL id: keywords} for the centre samples, or None."""
+        return "".join(format_clusters_row(label, size, mean, centre, None if meta is None else meta.get(centre, "-"))
+                       for (label, _), size, mean, centre in zip(self.groups, self.sizes, self.means, self.centres))
+
+    def sample_lines(self):
+        return "".join(format_clusters_sample(sample_id, self.groups[j][0], d) for sample_id, j, d in self.samples)
+
+
 class SearchLabels(object):
     """MornaSearch.label_separation: names (the labels in file order), item_label (int32 [n], -1: none), sums (uint64) and
     counts (int32) [nq, L] as AnnoyIndex.label_sums returns them, own (the own label of every by-item query, None for queries
@@ -856,6 +949,55 @@ class MornaSearch(object):
                 b = inv[j]
                 pairs.append((min(a, b), max(a, b), dist))
         return sort_pairs(pairs)
+
+    # ---- spherical k-means over the index rows ---------------------------------------------------
+    def cluster_samples(self, k=None, seed=0, init_ids=None, max_iterations=100, restriction=None):
+        """A partition of the indexed samples into k groups by angular distance in the hashed space: spherical k-means on the
+        GPU (AnnoyIndex.kmeans), bit-reproducible.  The first centroids are the rows of init_ids (EXTERNAL ids, distinct; k is
+        then their number) or of cluster_seed_items(eligible, k, seed).  restriction: a SearchRestriction made without groups;
+        only its allowed samples are partitioned.  Returns a SearchClusters."""
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(CLUSTER_SHARDS_REFUSAL)
+        self._check_restriction(restriction, None)
+        if restriction is not None and restriction.item_group is not None:
+            raise ValueError("cluster takes a restriction without groups (within / without only)")
+        n = self.annoy_index.get_n_items()
+        allow = restriction.allow if restriction is not None else None
+        eligible = list(range(n)) if allow is None else np.nonzero(allow)[0].tolist()
+        if init_ids is not None:
+            init_ids = list(init_ids)
+            if k is not None and k != len(init_ids):
+                raise ValueError("cluster: k = %d, but %d first centroids are named" % (k, len(init_ids)))
+            k = len(init_ids)
+            seeds = self._internal_ids(init_ids)
+        else:
+            if k is None:
+                raise ValueError("cluster needs k or init_ids")
+            seeds = None
+        if not 1 <= k <= min(LABELS_MAX, len(eligible)):
+            raise ValueError(cluster_max_refusal(k, len(eligible)))
+        if k * n > CLUSTER_MAX_VALUES:
+            raise ValueError("cluster: k * samples = %d is above 2^29 = %d, the distances one pass keeps on the GPU"
+                             % (k * n, CLUSTER_MAX_VALUES))
+        if seeds is None:
+            seeds = cluster_seed_items(eligible, k, seed)
+        out = self.annoy_index.kmeans(seeds, max_iterations, restriction=restriction.handle if restriction is not None else None)
+        inv = self._inverse_map()
+        assign, dist = out["assign"], out["dist"]
+        members = [[] for _ in range(k)]
+        samples = []
+        for i, (j, d) in enumerate(zip(assign.tolist(), dist.tolist())):
+            if j >= 0:
+                members[j].append(inv[i])
+                samples.append((inv[i], j, d))
+        table = cluster_table(assign, dist, k)
+        return SearchClusters([(cluster_label(j), members[j]) for j in range(k)], [t[0] for t in table], [t[1] for t in table],
+                              [None if t[2] is None else inv[t[2]] for t in table], samples, out["iterations"], out["converged"],
+                              self.annoy_index.kmeans_stats())
 
     def search_recall(self, queries, num_neighbors, trees, search_ks):
         """The recall of the approximate search against the exact one for every (tree count, search_k) of a grid, from this
