@@ -314,3 +314,109 @@ def test_refusals_through_the_raw_call():
     rc = L.morna_kmeans(empty._h, None, _lib.ptr(seeds), 1, 10, _lib.ptr(assign), None, None, None, _lib.ptr(info))
     assert rc == _lib.E_EMPTY
     assert C.sizeof(C.c_int32) == 4
+
+
+# ---- the loop at the sizes its kernels branch on ---------------------------------------------------------------------------
+# kmeans_update_kernel takes a (cluster, 256 columns) per workgroup, kmeans_starts_kernel `ceil(k / 256)` clusters per thread,
+# kmeans_hist / scatter / pick walk k in rounds of 256 threads, and radius_offsets_kernel scans 64 workgroup counts a pass.
+# Every shape below states, on the reference, the condition that makes it reach the branch it is here for.
+
+def _wide_blobs(D):
+    """300 rows of D floats in 5 blobs with unit noise (seed 100 + D); row 40 is zero, row 45 a copy of row 35."""
+    rng = np.random.default_rng(100 + D)
+    g = rng.standard_normal((5, D))
+    X = (g[np.arange(300) % 5] + 1.0 * rng.standard_normal((300, D))).astype(np.float32)
+    X[40] = 0.0
+    X[45] = X[35]
+    return X
+
+
+@pytest.mark.parametrize("D", [3, 37, 301, 1101, 4100, 8200])
+def test_loop_on_wide_and_ragged_rows(D):
+    """All five seeds in one blob, so the centroids travel for several iterations: the update's column blocks 0 .. 32 with
+    dead threads in the last one, the norms of a width that is no multiple of 4, and the scan's images of fp64 centroids
+    that are sums, at every row-width form of the scan."""
+    X = _wide_blobs(D)
+    want = ref_kmeans(X, [0, 5, 10, 15, 20], 100)
+    assert want["converged"] and want["iterations"] >= 3, want["iterations"]
+    assert want["sizes"].min() > 8, want["sizes"].tolist()                              # past KM_AHEAD: a second round of member rows
+    a = _index(X)
+    _same_run(a.kmeans([0, 5, 10, 15, 20], 100), want, "wide blobs D=%d" % D)
+    stats = a.kmeans_stats()
+    assert stats["iterations"] == want["iterations"] and stats["largest"] == want["sizes"].max()
+    assert stats["chains"] >= 300 * want["iterations"]
+
+
+def _many_clusters(n, D, k):
+    """(rows, seeds) of the k > 256 shapes.  k = 4096: rows 4300 .. 4449 are scaled copies of row 0 with 1e-3 of noise, and the
+    seeds are the rows 0 .. 4095."""
+    rng = np.random.default_rng(n + D + k)
+    X = rng.standard_normal((n, D)).astype(np.float32)
+    if k == 4096:
+        scale = np.linspace(0.5, 2.0, 150, dtype=np.float32)
+        X[4300:4450] = X[0][None, :] * scale[:, None] + np.float32(1e-3) * rng.standard_normal((150, D)).astype(np.float32)
+        return X, np.arange(4096)
+    return X, rng.choice(n, size=k, replace=False)
+
+
+@pytest.mark.parametrize("n,D,k,max_iter", [(2100, 3, 300, 4), (9000, 8, 1000, 3), (4500, 4, 4096, 3)])
+def test_loop_with_more_than_256_clusters(n, D, k, max_iter):
+    """kmeans_starts_kernel with 2, 4 and 16 clusters per thread, and the second and later rounds of 256 clusters in the
+    histogram, the scatter and the pick; 9000 rows are nine member-list chunks, the last one ragged."""
+    X, seeds = _many_clusters(n, D, k)
+    want = ref_kmeans(X, seeds, max_iter)
+    assert want["iterations"] >= 2 and want["sizes"].max() > 8, (want["iterations"], int(want["sizes"].max()))
+    assert (want["sizes"][256:] > 0).any()
+    if k == 4096:
+        assert (want["sizes"] == 0).any() and want["sizes"][0] > 100, int(want["sizes"][0])
+    a = _index(X)
+    _same_run(a.kmeans(seeds, max_iter), want, "n=%d D=%d k=%d" % (n, D, k))
+    stats = a.kmeans_stats()
+    assert stats["iterations"] == want["iterations"] and stats["largest"] == want["sizes"].max()
+
+
+@pytest.mark.parametrize("k", [257, 1000, 4096])
+def test_assign_with_more_than_256_centroids(k):
+    """1100 x 8: one assignment against k centroids (the first 40 are widened stored rows, two of them equal), with and
+    without an allow-list of every other row."""
+    if "many" not in _cache:
+        rng = np.random.default_rng(1100 + 8)
+        X = rng.standard_normal((1100, 8)).astype(np.float32)
+        X[ZERO_ROW] = 0.0
+        P = rng.standard_normal((4096, 8))
+        P[:40] = X[100:140].astype(np.float64)
+        P[300] = P[7]                                                                   # the lower index wins
+        _cache["many"] = dict(X=X, P=P, d=ref_distances(X, P), index=_index(X))
+    s = _cache["many"]
+    a, d = s["index"], s["d"][:, :k]
+    want = assign_from_distances(d)
+    assert (want[0] >= 256).any() and want[0][107] == 7
+    _same(a.kmeans_assign(s["P"][:k]), want, "k=%d" % k)
+    assert a.kmeans_stats()["chains"] >= 1100
+    allow = np.arange(1100) % 2 == 0
+    got = a.kmeans_assign(s["P"][:k], restriction=a.restriction(allow=allow))
+    _same(got, assign_from_distances(d, allow), "k=%d, every other row" % k)
+    assert (got[0][~allow] == -1).all() and a.kmeans_stats()["chains"] >= 550
+
+
+@pytest.mark.parametrize("k,max_iter", [(3, 4), (70, 3)], ids=["vector-scan", "mfma-scan"])
+def test_loop_over_more_than_64_row_blocks(k, max_iter):
+    """16700 x 8: 66 workgroups of 256 rows, so the prefix of their entry counts (radius_offsets_kernel) carries its running
+    sum into a second pass of two entries; 17 member-list chunks, the last ragged.  Plain, and two rows in three allowed."""
+    n = 16700
+    if "blocks" not in _cache:
+        X = np.random.default_rng(16700 + 8).standard_normal((n, 8)).astype(np.float32)
+        _cache["blocks"] = (X, _index(X))
+    X, a = _cache["blocks"]
+    assert (n + 255) // 256 > 64
+    allow = np.arange(n) % 3 != 2
+    seeds = (np.random.default_rng(k).choice(n // 3, size=k, replace=False) * 3).tolist()   # rows the allow-list keeps
+    for label, al in (("plain", None), ("two in three", allow)):
+        want = ref_kmeans(X, seeds, max_iter, al)
+        assert want["iterations"] == max_iter and want["sizes"].min() > 0
+        n_elig = n if al is None else int(al.sum())
+        assert (want["assign"][64 * 256:] >= 0).sum() > 0                               # eligible rows in blocks 64 and 65
+        got = a.kmeans(seeds, max_iter, restriction=None if al is None else a.restriction(allow=al))
+        _same_run(got, want, "16700 rows, k=%d, %s" % (k, label))
+        stats = a.kmeans_stats()
+        assert stats["chains"] >= n_elig * max_iter and stats["largest"] == want["sizes"].max()

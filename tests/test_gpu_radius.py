@@ -454,3 +454,50 @@ def test_refusals_through_the_raw_call():
         a.exact_radius(1.0, items=items, after=np.zeros(2, np.int32))
     with pytest.raises(ValueError):
         a.exact_radius(-0.5, items=items)
+
+
+def _row_chunks(N, nb, threads=256):
+    """exact_row_chunks of exact.hip, restated: the chunks of rows a query of a batch of nb is counted in."""
+    chunks = max(1, min((2048 + nb - 1) // nb, (N + 2047) // 2048))
+    chunk_rows = ((N + chunks - 1) // chunks + threads - 1) // threads * threads
+    return (N + chunk_rows - 1) // chunk_rows
+
+
+def test_more_than_64_chunk_counts_per_query():
+    """135000 x 8.  A query's chunk counts (one per chunk of rows and one for the rows outside the scan's domain) are turned
+    into offsets 64 at a time by one wave (radius_offsets_kernel), which carries its running sum from pass to pass: 3 queries
+    have 66 + 1 counts (two passes, a tail of three), 32 and 33 queries 59 + 1 (one pass; a chunk is a multiple of 256 rows),
+    and 3 queries over the first 131072 rows 64 + 1 (two passes, the second of one entry).  The yardstick is the fp64 chain
+    in numpy (kmeans_ref.ref_distances), ordered by distance, then higher id first, and cut at r.  Queries 0 and 1 are rows
+    131500 and 134990 plus 1e-3 of noise: their answers at every radius hold rows of the chunks 64 and 65."""
+    from kmeans_ref import ref_distances
+    N, dim = 135000, 8
+    rng = np.random.default_rng(135000)
+    X = rng.standard_normal((N, dim)).astype(np.float32)
+    X[5] = 0.0                                                   # outside the scan's domain: a candidate of the last count
+    Q = rng.standard_normal((33, dim))
+    Q[0] = X[131500].astype(np.float64) + 1e-3 * rng.standard_normal(dim)
+    Q[1] = X[134990].astype(np.float64) + 1e-3 * rng.standard_normal(dim)
+    d = ref_distances(X, Q)                                      # [N, 33]
+    assert not np.isnan(d).any()                                 # no query fails
+    ids = np.arange(N)
+    assert [_row_chunks(N, nb) + 1 for nb in (3, 32, 33)] == [67, 60, 60] and _row_chunks(131072, 3) + 1 == 65
+    for n_rows, batches in ((N, (3, 32, 33)), (131072, (3,))):
+        order = [np.lexsort((-ids[:n_rows], d[:n_rows, q])) for q in range(max(batches))]
+        d0 = d[:n_rows, 0][order[0]]
+        d20 = float(d0[19])
+        assert d0[19] != d0[20]
+        radii = (d20, float(np.nextafter(d20, 0.0)), float(d0[5000]))
+        a = _index(X[:n_rows])
+        for nq in batches:
+            for r in radii:
+                lists, counts = a.exact_radius(r, Q=Q[:nq])
+                assert a.exact_radius_stats()["batches"] == 1
+                for q in range(nq):
+                    keep = order[q][:int(np.searchsorted(d[:n_rows, q][order[q]], r, side="right"))]
+                    if n_rows == N and q < 2:
+                        assert (keep >= 131072).any(), (q, r)    # results from the chunks 64 and 65
+                    if r == radii[2] and q < 2:
+                        assert len(keep) > 4096, (q, len(keep))  # past the lists the device orders
+                    _same(lists, counts, q, (keep.astype(np.int32), d[:n_rows, q][keep], len(keep)),
+                          "rows=%d nq=%d r=%r" % (n_rows, nq, r))

@@ -1,9 +1,11 @@
 """What the tests that compare a forest and its searches with oracle mode 1 share (test_gpu_wide_rows.py,
-test_gpu_width_forms.py and the child processes of the latter).  Not a test module.
+test_gpu_width_forms.py and its child processes, test_gpu_caller_width_forms.py).  Not a test module.
 
   rows / compare_forest / compare_approx   the row generator and the node-for-node and answer-for-answer comparisons
   tm_form / tm_timer                        which two_means form the library takes at a row width and a level's node
                                             count: a restatement of the dispatch in forest_host.hpp (fb_attempt)
+  descent_nv                                which form of the search's descent and root-margin kernels a row width takes: a
+                                            restatement of row_nv in knn.hip
   check_width                               one shape end to end: forest, split counters, searches in three batch
                                             sizes, and the launch counts of the two two_means timers
 """
@@ -79,6 +81,17 @@ def tm_form(f, A, n_cus, strip_on=True):
     if nv in TM_WAVE_NV:
         return "wave", nv
     return "lds", None
+
+
+DESCENT_NV = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32)   # float4 per lane the search's one-wave kernels have a register form of
+
+
+def descent_nv(f, max_nv):
+    """The template argument NV of a search kernel that is dispatched over the row width, for rows of f floats: a restatement of
+    row_nv in knn.hip.  max_nv is what the call site instantiates: 32 for the plain and the restricted descent, 12 for the sweep
+    descent and the root margins by query groups (which do not exist where this returns 0).  0: the register-free form."""
+    nv = (f + 255) // 256
+    return nv if nv in DESCENT_NV and nv <= max_nv else 0
 
 
 def tm_timer(form):
