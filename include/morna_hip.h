@@ -654,6 +654,55 @@ int morna_kmeans_assign(morna_index *h, const morna_restriction *r /* or NULL */
 int morna_kmeans_stats(const morna_index *h, double *stats /* [8] */);
 
 /*
+ * ---- label mixture (no counterpart in the reference, whose README only names the question: "may uncover
+ * significant contamination") ----------------------------------------------------------------------------------------------
+ * Every query as a non-negative combination of the label centroids: a non-negative least squares fit on the unit sphere,
+ * bit-reproducible against a CPU restatement.
+ *   Arithmetic: fp64, one rounding per operation, no fused multiply-add; every sum starts from 0.0 and runs in ascending index.
+ *   item_label[n_items] in [-1, n_labels); 1 <= n_labels <= MORNA_MIXTURE_LABELS_MAX (the normalised Gram matrix, 128 KiB at the
+ *     limit, stays in the 160 KiB of LDS).  r: a restriction that holds an allow-list only, or NULL (one that holds groups:
+ *     MORNA_E_INVALID, as morna_kmeans); E: the eligible rows.  Queries as in morna_label_sums: q ([nq][dim] fp64), or items, or
+ *     both NULL for the staged query rows.  tol finite and >= 0; max_sweeps >= 1.
+ *   Centroid sums: pp_i and sigma_i = s_i exactly as morna_kmeans defines them; a member with not (0 < pp_i < inf) is skipped.
+ *     s_l[z] = morna_kmeans' update over the members {i in E : item_label[i] = l} (the zero vector without an unskipped
+ *     member); m_l = the unskipped members of l.
+ *   Gram: S_lm = sum_z s_l[z] * s_m[z] for l <= m, S_ml := S_lm.
+ *   Per query y (by item: the widened stored row): yy = sum_z y[z]^2, t_l = sum_z s_l[z] * y[z].
+ *   Own label left out: a by-item query i that is in E, unskipped, with o = item_label[i] >= 0 has tau_m = t_m * sigma_i,
+ *     S'_om = S'_mo = S_om - tau_m (m != o), S'_oo = (S_oo - 2.0 * tau_o) + 1.0, t'_o = t_o - pp_i * sigma_i (pp_i is the
+ *     query's yy: the same sum), m'_o = m_o - 1; everything else unchanged.  This is the centroid without the query's own unit
+ *     row, obtained algebraically: no centroid is rebuilt per query.
+ *   Active labels: l is active iff m'_l >= 1 and 0 < S'_ll < inf.  d_l = sqrt(S'_ll) correctly rounded,
+ *     G_lm = S'_lm / (d_l * d_m) for l != m, G_ll := 1.0, b_l = t'_l / (d_l * sqrt(yy)).  A query with not (0 < yy < inf) or
+ *     without an active label: all weights 0, info = 0, 0, 0, -1.  A host query with a non-finite element or sum of squares:
+ *     MORNA_E_INVALID, as morna_exact_search.
+ *   Solver, cyclic coordinate descent on the active labels: a = 0, g = b.  In sweep s = 1 .. max_sweeps: mx = 0; for every
+ *     active l ascending: delta = g_l; if delta < -a_l, delta = -a_l; if delta != 0: a_l = a_l + delta and, for every active m,
+ *     g_m = g_m - delta * G_ml; mx = max(mx, |delta|).  After a sweep with mx <= tol: stop, status 1.  After max_sweeps sweeps
+ *     without that: status 0.  No step sums across labels, so the answer cannot depend on the wave, the grid or the batch.
+ *   Report, sums over the active labels ascending: h_l = sum_m G_lm * a_m, w_l = b_l - h_l, kkt = the largest of |w_l| where
+ *     a_l > 0 and max(w_l, 0) where a_l = 0 (the Karush-Kuhn-Tucker conditions), u = sum_l a_l * h_l, v = sum_l a_l * b_l,
+ *     rr = (1.0 - 2.0 * v) + u: the squared distance from the unit query to its blend.
+ *   Outputs: weights_out[nq][n_labels] (0.0 for an inactive label), info_out[nq][4] = rr, kkt, sweeps, status,
+ *     active_out[nq][n_labels] bytes (may be NULL).
+ *   morna_label_centroids: s, m and S alone (sums_out[L][dim], counts_out[L], gram_out[L][L] or NULL).
+ *   Errors: a row-sharded handle: MORNA_E_INVALID; an empty index: MORNA_E_EMPTY; a label outside [-1, n_labels), tol,
+ *     max_sweeps or n_labels outside their limits: MORNA_E_INVALID naming the offender; an item outside the index: MORNA_E_RANGE.
+ *   morna_mixture_stats  of the last call, stats[8]: ms of the centroid step (member lists and sums), of the Gram (transpose,
+ *     Gram and normalisation), of the query dots (staging and dots), of the solver, HIP events; queries; sweeps summed; the
+ *     largest sweep count; queries with status != 1.  All 0 after a call that failed.
+ */
+#define MORNA_MIXTURE_LABELS_MAX 128
+int morna_label_centroids(morna_index *h, const morna_restriction *r /* or NULL */, const int32_t *item_label /* [n_items] */,
+                          int32_t n_labels, double *sums_out /* [n_labels][dim] */, int32_t *counts_out /* [n_labels] */,
+                          double *gram_out /* [n_labels][n_labels] or NULL */);
+int morna_mixture(morna_index *h, const morna_restriction *r /* or NULL */, const double *q, const int32_t *items, int64_t nq,
+                  const int32_t *item_label /* [n_items] */, int32_t n_labels, double tol, int32_t max_sweeps,
+                  double *weights_out /* [nq][n_labels] */, double *info_out /* [nq][4] */,
+                  uint8_t *active_out /* [nq][n_labels] or NULL */);
+int morna_mixture_stats(const morna_index *h, double *stats /* [8] */);
+
+/*
  * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
  * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
  * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the

@@ -127,6 +127,11 @@ SIGNATURES = {
     "morna_kmeans": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p]),
     "morna_kmeans_assign": (C.c_int, [_p, _p, _p, _i32, _p, _p]),
     "morna_kmeans_stats": (C.c_int, [_p, _p]),
+    # label mixture: handle, restriction (or NULL), item_label, n_labels, sums_out, counts_out, gram_out (or NULL)
+    "morna_label_centroids": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p]),
+    # handle, restriction, q, items, nq, item_label, n_labels, tol, max_sweeps, weights_out, info_out, active_out (or NULL)
+    "morna_mixture": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, C.c_double, _i32, _p, _p, _p]),
+    "morna_mixture_stats": (C.c_int, [_p, _p]),
     "morna_get_nns_prefix":(C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),

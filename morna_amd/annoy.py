@@ -580,6 +580,61 @@ class AnnoyIndex(object):
         return dict(scan_ms=float(stats[0]), pick_ms=float(stats[1]), resolve_ms=float(stats[2]), update_ms=float(stats[3]),
                     open_rows=int(stats[4]), chains=int(stats[5]), iterations=int(stats[6]), largest=int(stats[7]))
 
+    # ---- label mixture (include/morna_hip.h, "label mixture"; no counterpart in annoy) ----
+    def _item_labels(self, item_label):
+        if np.shape(item_label) != (self.get_n_items(),):
+            raise ValueError("item_label must hold one label per item (%d), got shape %r" % (self.get_n_items(), np.shape(item_label)))
+        return np.ascontiguousarray(item_label, dtype=np.int32)
+
+    def label_centroids(self, item_label, n_labels, restriction=None, gram=True):
+        """The ordered fp64 sums of the unit rows of every label, as kmeans' update makes them: (sums float64 [n_labels, f],
+        counts int32 [n_labels], the members that were not skipped, gram float64 [n_labels, n_labels] or None).  item_label:
+        int32 [n_items] in [-1, n_labels).  restriction: an allow-list only."""
+        item_label = self._item_labels(item_label)
+        n_labels = int(n_labels)
+        sums = np.zeros((max(n_labels, 0), self.f), np.float64)
+        counts = np.zeros(max(n_labels, 0), np.int32)
+        S = np.zeros((max(n_labels, 0), max(n_labels, 0)), np.float64) if gram else None
+        check(lib().morna_label_centroids(self._h, self._kmeans_restriction(restriction), ptr(item_label), n_labels, ptr(sums),
+                                          ptr(counts), ptr(S)))
+        return sums, counts, S
+
+    def mixture(self, item_label, n_labels, Q=None, items=None, restriction=None, tol=1e-9, max_sweeps=10000):
+        """Every query as a non-negative combination of the label centroids: (weights float64 [nq, n_labels], info float64
+        [nq, 4] = squared residual, KKT residual, sweeps, status (1 converged, 0 not, -1 no fit), active bool [nq, n_labels]).
+        Queries: Q (fp64 [nq, f]), items (stored rows: such a query is left out of its own label's centroid), or neither: the
+        staged query rows.  restriction: an allow-list only."""
+        item_label = self._item_labels(item_label)
+        n_labels = int(n_labels)
+        if Q is not None and items is not None:
+            raise ValueError("give query vectors or items, not both")
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[1] != self.f:
+                raise IndexError("queries must be [nq, %d]" % self.f)
+            nq = Q.shape[0]
+        elif items is not None:
+            items = np.ascontiguousarray(items, dtype=np.int32)
+            if items.ndim != 1:
+                raise ValueError("items must be one-dimensional")
+            nq = items.shape[0]
+        else:
+            nq = getattr(self, "_qrows_n", 0)
+        weights = np.zeros((nq, max(n_labels, 0)), np.float64)
+        info = np.zeros((nq, 4), np.float64)
+        active = np.zeros((nq, max(n_labels, 0)), np.uint8)
+        check(lib().morna_mixture(self._h, self._kmeans_restriction(restriction), ptr(Q), ptr(items), nq, ptr(item_label), n_labels,
+                                  float(tol), int(max_sweeps), ptr(weights), ptr(info), ptr(active)))
+        return weights, info, active.astype(bool)
+
+    def mixture_stats(self):
+        """Of the last label_centroids / mixture: ms of the centroid step, the Gram, the query dots and the solver; queries,
+        sweeps summed, the largest sweep count, queries that did not converge (status != 1)."""
+        stats = np.zeros(8, np.float64)
+        check(lib().morna_mixture_stats(self._h, ptr(stats)))
+        return dict(centroids_ms=float(stats[0]), gram_ms=float(stats[1]), dots_ms=float(stats[2]), solve_ms=float(stats[3]),
+                    queries=int(stats[4]), sweeps=int(stats[5]), max_sweeps=int(stats[6]), open=int(stats[7]))
+
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):
         """Rows of the query samples of `terms` (index.ParsedLines from ParsedLines.query_terms) on this handle, beside the

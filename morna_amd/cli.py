@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` / `morna mixture` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -72,6 +72,11 @@ label, b to those of the nearest other one -- and whether the nearest label is i
 and with --matrix the map of mean distances between labels.  One scan of the index on the GPU that keeps, per query and
 label, an integer sum of all distances instead of the k smallest.
 
+`mixture` answers the contamination half of that purpose: it writes every query as a non-negative blend of the centroids of
+the labels (a non-negative least squares fit on the unit sphere, fp64, on the GPU) and prints the weights,
+their shares, how far the blend stays from the query, and whether a second label holds a share of at least --min-share.  A
+query that is a sample of the index is left out of its own label's centroid.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -99,6 +104,8 @@ here do the latter.
     python -m morna_amd.cli hashing -x idx --junction-file junctions.tsv.gz --sample 100 -r 20 --features 500,1000,3000,8192,index
     python -m morna_amd.cli labels -x idx --labels tissues.tsv --all --matrix --summary-only
     python -m morna_amd.cli labels -x idx --labels tissues.tsv --intropolis new_samples.tsv.gz --top 3
+    python -m morna_amd.cli mixture -x idx --labels tissues.tsv --all --matrix --summary-only
+    python -m morna_amd.cli mixture -x idx --labels tissues.tsv --query-ids 17,42 --top 3 --min-share 0.1
     python -m morna_amd.cli search -x idx -e --max-distance 0.15 --query-ids 17,42 -d
     python -m morna_amd.cli pairs -x idx --max-distance 0.05 --leave-out-groups donors.tsv --clusters
 """
@@ -375,6 +382,50 @@ def build_parser():
                                help='a groups file: a query never counts a sample of its own group -- its donor, its study -- '
                                     '(queries that are samples of the index only)')
     labels_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    mixture_parser = subparsers.add_parser('mixture', help='writes every query as a non-negative blend of the centroids of the '
+                                                           'labels of a sample -> label table and says which queries are '
+                                                           'mixed: a contaminated sample shows a second label with a share')
+    mixture_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                                help='path to junction index basename (an index without row shards)')
+    mixture_parser.add_argument('--labels', metavar='<file>', type=str, required=True,
+                                help='a groups file, "<label><TAB><id>,<id>,..." per line: the samples of every label (a tissue, '
+                                     'a cell type), at most 128 labels; a sample it does not name has none')
+    mixture_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
+                                help='the query is the sample already in the index with this sample id')
+    mixture_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                                help='comma-separated sample ids already in the index')
+    mixture_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
+                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
+    mixture_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                                help='the seed of --sample (default 0)')
+    mixture_parser.add_argument('--all', action='store_const', const=True, default=False, dest='all_items',
+                                help='every sample of the index is a query')
+    mixture_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
+                                help='every sample of this (gzipped) intropolis file is a query')
+    mixture_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
+                                help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+    mixture_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=3,
+                                help='the labels of the largest weights printed per query (default 3)')
+    mixture_parser.add_argument('--min-share', metavar='<float>', type=float, required=False, default=0.1,
+                                help='a query is mixed when its second label holds at least this share of the weights (default 0.1)')
+    mixture_parser.add_argument('--tolerance', metavar='<float>', type=float, required=False, default=1e-9,
+                                help='the fit stops after a sweep whose largest step is at most this (default 1e-9)')
+    mixture_parser.add_argument('--max-sweeps', metavar='<int>', type=int, required=False, default=10000,
+                                help='the sweeps a fit may take (default 10000)')
+    mixture_parser.add_argument('--matrix', action='store_const', const=True, default=False,
+                                help='append the table of mean shares: the row is the queries\' own label, the column the fitted '
+                                     'label (queries that are samples of the index only)')
+    mixture_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                                help='print only the table over all queries')
+    mixture_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                                help='the centroids are made of the samples this file lists only, one integer sample id per line')
+    mixture_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                                help='no centroid holds a sample this file lists, one integer sample id per line')
+    mixture_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    mixture_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    mixture_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
+    for flag in ('--leave-out-groups', '--supersamples'):
+        mixture_parser.add_argument(flag, type=str, required=False, default=None, help=argparse.SUPPRESS)
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
     super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
@@ -773,8 +824,9 @@ def _check_hashing_flags(parser, args):
                      "index, such as 500,3000,index (%s)" % e)
 
 
-def _check_labels_flags(parser, args):
-    """`labels`: at most one named query source (none: a stream on stdin), the files read and checked against each other and
+def _check_labels_flags(parser, args, command='labels'):
+    """`labels` (and `mixture`, which takes the same queries and files; more labels than it takes is its own ValueError): at
+    most one named query source (none: a stream on stdin), the files read and checked against each other and
     against the query kind; argparse errors, before any index is read.  Leaves the labels in args.label_groups and the
     restriction's parts where _check_restriction_flags leaves them."""
     from .junctions import parse_groups_file, parse_sample_ids_file
@@ -783,8 +835,8 @@ def _check_labels_flags(parser, args):
                                    ("--sample", args.sample is not None), ("--all", args.all_items),
                                    ("--intropolis", args.intropolis is not None)) if on]
     if len(given) > 1:
-        parser.error("labels takes one query source: -q, --query-ids, --sample, --all, --intropolis or a stream on stdin "
-                     "(got %s)" % " and ".join(given))
+        parser.error("%s takes one query source: -q, --query-ids, --sample, --all, --intropolis or a stream on stdin "
+                     "(got %s)" % (command, " and ".join(given)))
     if args.format not in ("sam", "bed", "raw"):
         parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
     if args.query_ids is not None:
@@ -819,12 +871,33 @@ def _check_labels_flags(parser, args):
         parser.error(str(e))
     if not args.label_groups:
         parser.error("--labels %s names no label" % args.labels)
-    if len(args.label_groups) > LABELS_MAX:
+    if command == 'labels' and len(args.label_groups) > LABELS_MAX:
         parser.error(labels_max_refusal(len(args.label_groups)))
     if args.within_ids is not None and args.without_ids is not None:
         both = sorted(set(args.within_ids) & set(args.without_ids))
         if both:
             parser.error("--within and --without both name sample id %d" % both[0])
+
+
+def _check_mixture_flags(parser, args):
+    """`mixture`: the flags of the searches that make no sense here and the numbers of the fit, then what `labels` checks;
+    argparse errors, before any index is read."""
+    refused = (("-e/--exact", args.exact, "the fit is made in fp64 already"),
+               ("--unhashed", args.unhashed, "the centroids are sums of the index's rows, in the hashed space"),
+               ("--leave-out-groups", args.leave_out_groups is not None,
+                "a query that is a sample of the index is left out of its own label's centroid, nothing else is"),
+               ("--supersamples", args.supersamples is not None,
+                "pool the samples with `morna supersample` and feed its file on stdin with -f raw"))
+    for flag, on, why in refused:
+        if on:
+            parser.error("mixture cannot be used with %s: %s" % (flag, why))
+    if not (args.min_share >= 0.0 and args.min_share <= 1.0):
+        parser.error("--min-share takes a share, 0 to 1 (got %r)" % args.min_share)
+    if not (args.tolerance >= 0.0) or args.tolerance == float("inf"):
+        parser.error("--tolerance takes a finite number >= 0 (got %r)" % args.tolerance)
+    if args.max_sweeps < 1:
+        parser.error("--max-sweeps takes a positive number of sweeps (got %d)" % args.max_sweeps)
+    _check_labels_flags(parser, args, command='mixture')
 
 
 def _check_batch_flags(parser, args):
@@ -902,6 +975,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_labels_flags(parser, args)
     if args.subparser_name == 'cluster':
         _check_cluster_flags(parser, args)
+    if args.subparser_name == 'mixture':
+        _check_mixture_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -925,6 +1000,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _hashing(args, stdout)
     if args.subparser_name == 'labels':
         return _labels(args, stdin, stdout)
+    if args.subparser_name == 'mixture':
+        return _mixture(args, stdin, stdout)
     if args.subparser_name == 'pairs':
         return _pairs(args, stdout)
     if args.subparser_name == 'cluster':
@@ -1084,18 +1161,10 @@ def _hashing(args, stdout):
     return 0
 
 
-def _labels(args, stdin, stdout):
-    """`labels`: one scan of the index on the GPU that keeps, per query and label, the sum of the distances and their number;
-    a block per query, the table over all of them and, with --matrix, the label map."""
-    import os
+def _label_queries(args, searcher, stdin):
+    """The queries of `labels` and `mixture` from their flags: (queries as MornaSearch.label_separation takes them, the ids
+    printed for them)."""
     import numpy as np
-    from .search import LABELS_SHARDS_REFUSAL, MornaSearch, format_label_rows
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(LABELS_SHARDS_REFUSAL)
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
     if args.intropolis is not None:
         queries = searcher.queries_from_intropolis(args.intropolis)
         ids = queries.ext_ids
@@ -1124,6 +1193,53 @@ def _labels(args, stdin, stdout):
                                  + "in the index.")
         queries = [searcher.internal_id_map[query_id] for query_id in ids]
         args.query_ids = list(ids)                             # (a query the groups file does not name is a group of its own)
+    return queries, ids
+
+
+def _mixture(args, stdin, stdout):
+    """`mixture`: every query fitted on the GPU as a non-negative blend of the label centroids; a block per query, the table
+    over all of them and, with --matrix, the table of mean shares."""
+    import os
+    from .search import MIXTURE_LABELS_MAX, MIXTURE_SHARDS_REFUSAL, MornaSearch, format_label_rows, mixture_max_refusal
+    if len(args.label_groups) > MIXTURE_LABELS_MAX:
+        raise ValueError(mixture_max_refusal(len(args.label_groups)))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
+    if os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(MIXTURE_SHARDS_REFUSAL)
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    queries, ids = _label_queries(args, searcher, stdin)
+    args.restriction = _make_restriction(args, searcher)
+    table = searcher.label_mixture(queries, args.label_groups, restriction=args.restriction, tol=args.tolerance,
+                                   max_sweeps=args.max_sweeps)
+    if not args.summary_only:
+        for q, query_id in enumerate(ids):
+            stdout.write(table.header(q, query_id))
+            stdout.write(format_label_rows(table.rows(q, args.top, args.min_share)))
+    rows, without = table.summary(args.min_share)
+    stdout.write("# all %d queries\n" % len(ids))
+    stdout.write(format_label_rows(rows))
+    if without > 0:
+        stdout.write("# %d queries without %s\n" % (without, "a positive weight" if args.external else "a label of their own"))
+    if args.matrix:
+        stdout.write("# share matrix\n")
+        stdout.write(format_label_rows([(name,) + tuple(row) for name, row in zip(table.names, table.matrix())]))
+    return 0
+
+
+def _labels(args, stdin, stdout):
+    """`labels`: one scan of the index on the GPU that keeps, per query and label, the sum of the distances and their number;
+    a block per query, the table over all of them and, with --matrix, the label map."""
+    import os
+    from .search import LABELS_SHARDS_REFUSAL, MornaSearch, format_label_rows
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                           "run it in one process, which loads every shard of the index")
+    if os.path.exists(args.basename + ".shards.mor"):
+        raise ValueError(LABELS_SHARDS_REFUSAL)
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    queries, ids = _label_queries(args, searcher, stdin)
     args.restriction = _make_restriction(args, searcher)
     table = searcher.label_separation(queries, args.label_groups, restriction=args.restriction)
     if not args.summary_only:

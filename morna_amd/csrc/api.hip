@@ -1140,6 +1140,79 @@ int morna_kmeans_stats(const morna_index *h, double *stats)
     return MORNA_OK;
 }
 
+// ---- label mixture (the contract is in morna_hip.h) ------------------------------------------------------------------
+
+static int mixture_guarded(morna_index *h, const char *who, const morna_restriction *r, const ExactQueries &Q, int64_t nq,
+                           const int32_t *item_label, int32_t n_labels, double tol, int32_t max_sweeps, double *sums_out,
+                           int32_t *counts_out, double *gram_out, double *weights_out, double *info_out, uint8_t *active_out)
+{
+    int rc = MORNA_OK;
+    try {   // (host vectors: bad_alloc must not cross the C ABI)
+        rc = mixture(h, r, Q, nq, item_label, n_labels, tol, max_sweeps, sums_out, counts_out, gram_out, weights_out, info_out,
+                     active_out);
+    } catch (const std::exception &e) {
+        set_error("%s: %s", who, e.what());
+        rc = MORNA_E_INVALID;
+    }
+    if (rc != MORNA_OK)
+        for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
+    return rc;
+}
+
+int morna_label_centroids(morna_index *h, const morna_restriction *r, const int32_t *item_label, int32_t n_labels, double *sums_out,
+                          int32_t *counts_out, double *gram_out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
+    if (!item_label || !sums_out || !counts_out) {
+        set_error("label_centroids: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("label_centroids is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return mixture_guarded(h, "label_centroids", r, ExactQueries::host(nullptr), 0, item_label, n_labels, 0.0, 1, sums_out, counts_out,
+                           gram_out, nullptr, nullptr, nullptr);
+}
+
+int morna_mixture(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
+                  const int32_t *item_label, int32_t n_labels, double tol, int32_t max_sweeps, double *weights_out, double *info_out,
+                  uint8_t *active_out)
+{
+    CHECK_H(h);
+    for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
+    if (!item_label || !weights_out || !info_out) {
+        set_error("mixture: null buffer");
+        return MORNA_E_INVALID;
+    }
+    if (q && items) {
+        set_error("mixture: give query vectors or items, not both");
+        return MORNA_E_INVALID;
+    }
+    if (h->comm) {
+        set_error("mixture is not available on a row-sharded handle");
+        return MORNA_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
+    if (!q && !items) MORNA_TRY(staged_queries(h, "mixture", nq, &Q));
+    return mixture_guarded(h, "mixture", r, Q, nq, item_label, n_labels, tol, max_sweeps, nullptr, nullptr, nullptr, weights_out,
+                           info_out, active_out);
+}
+
+int morna_mixture_stats(const morna_index *h, double *stats)
+{
+    if (!h || !stats) {
+        set_error("mixture_stats: null pointer");
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
+    for (int i = 0; i < 8; i++) stats[i] = h->mixture_stats[i];
+    return MORNA_OK;
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

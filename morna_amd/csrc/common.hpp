@@ -391,6 +391,9 @@ struct morna_index {
     double radius_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // spherical k-means (exact.hip, kmeans): the last call's statistics (its arrays are pieces of ex_ws, ex_cand and ex_cdist)
     double kmeans_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // label mixture (mixture.hip): the call's arrays on the device; the last call's statistics
+    morna::DevBuf<uint8_t> mx_ws;
+    double mixture_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
@@ -566,6 +569,25 @@ int exact_radius(morna_index *h, const morna_restriction *rst, const ExactQuerie
 // (morna_hip.h, "spherical k-means"): rst and every output but assign_out may be null
 int kmeans(morna_index *h, const morna_restriction *rst, const int32_t *seeds, const double *cent_host, int32_t k, int32_t max_iter,
            int32_t *assign_out, double *dist_out, double *cent_out, int32_t *sizes_out, int32_t *info_out);
+// What mixture.hip takes from the exact family (exact.hip): the checks every caller of the front makes on its queries (qt_out:
+// the scan's own figure), their staging as fp64 rows, and the update of k-means for a labelling that is given.
+int exact_check_queries(morna_index *h, const char *who, const ExactQueries &Q, int64_t nq, int *qt_out);
+int exact_stage_queries(morna_index *h, const ExactQueries &Q, int64_t q0, int64_t nb, int32_t *d_items, double *Qd);
+struct KmeansLists {
+    double *scale;        // [n_items] 1 / sqrt(pp_i), -1: the member is skipped
+    int32_t *chunk_cnt;   // [kmeans_lists_chunks(n_items)][k]
+    int32_t *sizes;       // [k] members of every label, skipped ones included
+    int32_t *start;       // [k] where a label's list begins in member
+    int32_t *member;      // [n_items] label-major, ascending id
+    int32_t *totals;      // [4] (the counters of the k-means loop: left as they are here)
+};
+int64_t kmeans_lists_chunks(int64_t n_items);
+int kmeans_label_sums(morna_index *h, const int32_t *assign, int32_t k, const KmeansLists &W, double *sums);
+// morna_label_centroids (q, weights_out and info_out null, nq 0) and morna_mixture behind their null checks (morna_hip.h,
+// "label mixture"; mixture.hip)
+int mixture(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *item_label_host, int32_t L,
+            double tol, int32_t max_sweeps, double *sums_out, int32_t *counts_out, double *gram_out, double *weights_out,
+            double *info_out, uint8_t *active_out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

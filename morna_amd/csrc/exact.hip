@@ -739,8 +739,8 @@ size_t exact_msg_bytes(int64_t nq, int32_t k) { return exact_msg_dist_offset(nq,
 
 // What every caller of the scan checks first: host queries finite with a finite sum of squares in the reference's order
 // (cosine_distance), stored rows in range, the row width within the scan's.  qt_out: the queries that share one pass of
-// exact_scan_kernel (their fp32 images share 64 KiB of LDS).
-static int exact_check_queries(morna_index *h, const ExactQueries &Q, int64_t nq, int *qt_out)
+// exact_scan_kernel (their fp32 images share 64 KiB of LDS).  who: the name the messages open with.
+int exact_check_queries(morna_index *h, const char *who, const ExactQueries &Q, int64_t nq, int *qt_out)
 {
     const int64_t N = h->n_items;
     const int32_t D = h->dim, dpad = h->dpad;
@@ -752,7 +752,7 @@ static int exact_check_queries(morna_index *h, const ExactQueries &Q, int64_t nq
                 qq = qq + jj;
             }
             if (!(qq <= DBL_MAX)) {
-                set_error("exact search: query %lld has a non-finite element or sum of squares", (long long)i);
+                set_error("%s: query %lld has a non-finite element or sum of squares", who, (long long)i);
                 return MORNA_E_INVALID;
             }
         }
@@ -765,7 +765,7 @@ static int exact_check_queries(morna_index *h, const ExactQueries &Q, int64_t nq
     // queries resident per pass: their fp32 images share 64 KiB of LDS
     *qt_out = (size_t)dpad * 4 * 8 <= 65536 ? 8 : (size_t)dpad * 4 * 4 <= 65536 ? 4 : (size_t)dpad * 4 * 2 <= 65536 ? 2 : 1;
     if (dpad > Q_MAX_DPAD) {   // exact_scan_kernel<1> keeps the query's fp32 image in LDS (128 KiB at 32768)
-        set_error("exact search: dimension %d is above the supported %d", D, Q_MAX_DPAD);
+        set_error("%s: dimension %d is above the supported %d", who, D, Q_MAX_DPAD);
         return MORNA_E_INVALID;
     }
     return MORNA_OK;
@@ -813,7 +813,7 @@ static int exact_front(morna_index *h, const char *who, const char *name, const 
     F.N = h->n_items;
     F.D = h->dim;
     F.dpad = h->dpad;
-    MORNA_TRY(exact_check_queries(h, Q, nq, &F.qt));
+    MORNA_TRY(exact_check_queries(h, "exact search", Q, nq, &F.qt));   // (the family's wording, whichever entry point)
     MORNA_TRY(exact_outside_rows(h));
     F.n_outs = h->ex_out_n;
     F.outs = h->ex_out.p + 1;
@@ -835,36 +835,28 @@ static int exact_front(morna_index *h, const char *who, const char *name, const 
     return MORNA_OK;
 }
 
-// The HIP events behind a call's own statistics (label_stats, radius_stats), destroyed with the holder on every path.
-struct HipEvents {
-    std::vector<hipEvent_t> ev;
-    ~HipEvents()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+// queries q0 .. q0 + nb of a call staged as fp64 rows Qd[nb][dim] on the handle's stream, from any of the four sources; by
+// item their ids go to d_items[nb] first
+int exact_stage_queries(morna_index *h, const ExactQueries &Q, int64_t q0, int64_t nb, int32_t *d_items, double *Qd)
+{
+    const int32_t D = h->dim, dpad = h->dpad;
+    switch (Q.source) {
+    case ExactQueries::HOST_F64:
+        HIP_TRY(hipMemcpyAsync(Qd, Q.host64() + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
+        break;
+    case ExactQueries::DEV_F32:
+        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, Q.dev32() + q0 * D, (int64_t)D, nullptr, D, Qd);
+        break;
+    case ExactQueries::DEV_F64:
+        HIP_TRY(hipMemcpyAsync(Qd, Q.dev64() + q0 * D, (size_t)nb * D * 8, hipMemcpyDeviceToDevice, h->stream));
+        break;
+    case ExactQueries::ITEMS:
+        HIP_TRY(hipMemcpyAsync(d_items, Q.items() + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, d_items, D, Qd);
+        break;
     }
-    int create(int n)
-    {
-        for (int i = 0; i < n; i++) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            ev.push_back(e);
-        }
-        return MORNA_OK;
-    }
-    int record(int i, hipStream_t st)
-    {
-        HIP_TRY(hipEventRecord(ev[(size_t)i], st));
-        return MORNA_OK;
-    }
-    // *ms += the time from event i to event j
-    int elapsed(int i, int j, double *ms)
-    {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[(size_t)i], ev[(size_t)j]));
-        *ms += t;
-        return MORNA_OK;
-    }
-};
+    return MORNA_OK;
+}
 
 // queries q0 .. q0 + nb of the call staged as fp64 (Qd), their fp32 images and norms made, and the scan run over every row --
 // approx[nb][N], nothing masked.  The MFMA scan for 32 queries or more, exact_scan_kernel<qt> below.
@@ -872,21 +864,7 @@ static int exact_scan_batch(morna_index *h, const ExactFront &F, int64_t q0, int
 {
     const int64_t N = F.N;
     const int32_t D = F.D, dpad = F.dpad;
-    switch (F.Q.source) {
-    case ExactQueries::HOST_F64:
-        HIP_TRY(hipMemcpyAsync(F.Qd, F.Q.host64() + q0 * D, (size_t)nb * D * 8, hipMemcpyHostToDevice, h->stream));
-        break;
-    case ExactQueries::DEV_F32:
-        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, F.Q.dev32() + q0 * D, (int64_t)D, nullptr, D, F.Qd);
-        break;
-    case ExactQueries::DEV_F64:
-        HIP_TRY(hipMemcpyAsync(F.Qd, F.Q.dev64() + q0 * D, (size_t)nb * D * 8, hipMemcpyDeviceToDevice, h->stream));
-        break;
-    case ExactQueries::ITEMS:
-        HIP_TRY(hipMemcpyAsync(F.d_items, F.Q.items() + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(exact_widen_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->X.p, (int64_t)dpad, F.d_items, D, F.Qd);
-        break;
-    }
+    MORNA_TRY(exact_stage_queries(h, F.Q, q0, nb, F.d_items, F.Qd));
     // one pass over the matrix per qt queries: 4*D*N bytes each
     const int64_t q_per_pass = nb >= 32 ? MM_TILE : F.qt;
     ScopedTimer tm(h, MORNA_T_EXACT, 4 * (int64_t)D * N * ((nb + q_per_pass - 1) / q_per_pass));
@@ -2123,6 +2101,28 @@ int kmeans(morna_index *h, const morna_restriction *rst, const int32_t *seeds, c
     h->kmeans_stats[5] = chains;
     h->kmeans_stats[6] = (double)iterations;
     h->kmeans_stats[7] = loop ? (double)*std::max_element(h_sizes.begin(), h_sizes.end()) : 0.0;
+    return MORNA_OK;
+}
+
+// The update alone, for a labelling that is given (mixture.hip): the scales of every row, the label-major member lists of
+// assign[n_items] (in [-1, k): -1 belongs to no list) and the sums, enqueued on the handle's stream.  W: the caller's arrays,
+// sized by kmeans_lists_chunks; sums[k][dim] keeps what it held for a label without an unskipped member.
+int64_t kmeans_lists_chunks(int64_t n_items) { return (n_items + KM_CHUNK - 1) / KM_CHUNK; }
+
+int kmeans_label_sums(morna_index *h, const int32_t *assign, int32_t k, const KmeansLists &W, double *sums)
+{
+    const int64_t N = h->n_items, nblk = (N + KM_THREADS - 1) / KM_THREADS, chunks = kmeans_lists_chunks(N);
+    const int32_t D = h->dim, dpad = h->dpad;
+    hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->X.p, N, D, dpad, W.scale);
+    // (prev = assign: no row counts as changed)
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3((unsigned)chunks), dim3(KM_THREADS), (size_t)k * 4, h->stream, assign, assign, N, k,
+                       W.chunk_cnt, W.totals);
+    hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(KM_THREADS), 0, h->stream, W.chunk_cnt, (int32_t)chunks, k, W.sizes, W.start);
+    hipLaunchKernelGGL(kmeans_scatter_kernel, dim3((unsigned)chunks), dim3(KM_THREADS), (size_t)k * 4, h->stream, assign, N, k,
+                       W.chunk_cnt, W.start, W.member);
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)k, (unsigned)((D + KM_THREADS - 1) / KM_THREADS)), dim3(KM_THREADS), 0,
+                       h->stream, h->X.p, D, dpad, W.member, W.start, W.sizes, W.scale, sums);
+    HIP_TRY(hipGetLastError());
     return MORNA_OK;
 }
 

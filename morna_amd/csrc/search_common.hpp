@@ -1,5 +1,6 @@
 // search_common.hpp -- what the approximate searches (knn.hip) and the exact family (exact.hip) both use: the widest row,
-// the restriction as the kernels take it, the workgroup-wide minimum, the workspace carver and the launch helpers.
+// the restriction as the kernels take it, the workgroup-wide minimum, the workspace carver, the launch helpers and the HIP
+// events behind a call's statistics (mixture.hip takes the last three too).
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -122,5 +123,36 @@ static int carve_workspace(DevBuf<uint8_t> &buf, F &&layout)
     layout(c);
     return MORNA_OK;
 }
+
+// The HIP events behind a call's own statistics (label_stats, radius_stats, mixture_stats), destroyed with the holder on every path.
+struct HipEvents {
+    std::vector<hipEvent_t> ev;
+    ~HipEvents()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    int create(int n)
+    {
+        for (int i = 0; i < n; i++) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e));
+            ev.push_back(e);
+        }
+        return MORNA_OK;
+    }
+    int record(int i, hipStream_t st)
+    {
+        HIP_TRY(hipEventRecord(ev[(size_t)i], st));
+        return MORNA_OK;
+    }
+    // *ms += the time from event i to event j
+    int elapsed(int i, int j, double *ms)
+    {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev[(size_t)i], ev[(size_t)j]));
+        *ms += t;
+        return MORNA_OK;
+    }
+};
 
 }  // namespace morna

@@ -426,6 +426,93 @@ def format_label_rows(rows):
     return format_recall_rows(rows)
 
 
+# ---- morna mixture ----------------------------------------------------------------------------------
+MIXTURE_SHARDS_REFUSAL = ("mixture is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                          "run it on an index built without --shards")
+MIXTURE_LABELS_MAX = 128        # MORNA_MIXTURE_LABELS_MAX: the normalised Gram matrix of the labels stays on chip
+MIXTURE_CALL_CELLS = 1 << 22    # (query, label) cells of one library call
+
+
+def mixture_max_refusal(n_labels):
+    return ("--labels names %d labels, mixture takes 1 to %d: the GPU keeps the labels' Gram matrix on chip while it fits a "
+            "query" % (n_labels, MIXTURE_LABELS_MAX))
+
+
+def mixture_shares(weights_q):
+    """share[g] = weight / the sum of the weights (added in file order); all 0.0 when no weight is positive."""
+    total = 0.0
+    for w in weights_q:
+        total += float(w)
+    return [float(w) / total if total > 0.0 else 0.0 for w in weights_q]
+
+
+def mixture_query(weights_q, min_share=0.1):
+    """What one query's weights say: shares (mixture_shares), order (the labels of positive weight, the largest first, ties in
+    file order), top (order[0] or None) and mixed (a second label holds a share of at least min_share)."""
+    shares = mixture_shares(weights_q)
+    order = sorted((g for g, w in enumerate(weights_q) if float(w) > 0.0), key=lambda g: (-float(weights_q[g]), g))
+    return dict(shares=shares, order=order, top=order[0] if order else None,
+                mixed=len(order) >= 2 and shares[order[1]] >= min_share)
+
+
+def format_mixture_header(query_id, own_name, info_q):
+    """The first line of a query's block of `morna mixture`; info_q: rr, kkt, sweeps, status."""
+    rr = float(info_q[0])
+    return "# query %s\tlabel %s\tresidual %.6f\tsweeps %d\tconverged %d\n" % (
+        query_id, "-" if own_name is None else own_name, max(rr, 0.0) ** 0.5, int(info_q[2]), 1 if info_q[3] == 1 else 0)
+
+
+def mixture_rows(names, weights_q, top=3, min_share=0.1):
+    """The lines of one query's block behind its header: the `top` labels by weight as ("<rank>.", label, weight, share), then
+    ("mixed", 1 | 0)."""
+    info = mixture_query(weights_q, min_share)
+    rows = [("%d." % (rank + 1), names[g], float(weights_q[g]), info["shares"][g])
+            for rank, g in enumerate(info["order"][:max(int(top), 0)])]
+    rows.append(("mixed", 1 if info["mixed"] else 0))
+    return rows
+
+
+def mixture_summary(names, weights, info, own=None, min_share=0.1):
+    """(rows, without) over all queries.  own: the own label of every query (by-item queries; negative: none) -- then one row
+    per label that has queries, in file order, (label, queries, mean share of the own label, queries whose own label is on top,
+    mixed queries, queries that did not converge), an ("all", ...) row over those queries when there are any, and `without`,
+    the queries without an own label.  own None (queries from outside the index): (label, queries whose top label it is) per
+    label, then ("mixed", their number); `without`: the queries with no positive weight."""
+    per = [mixture_query(weights[q], min_share) for q in range(len(weights))]
+    if own is None:
+        rows = [(names[g], sum(1 for p in per if p["top"] == g)) for g in range(len(names))]
+        rows.append(("mixed", sum(1 for p in per if p["mixed"])))
+        return rows, sum(1 for p in per if p["top"] is None)
+
+    def row(label, group):
+        n = len(group)
+        return (label, n, sum(per[q]["shares"][int(own[q])] for q in group) / n,
+                sum(1 for q in group if per[q]["top"] == int(own[q])), sum(1 for q in group if per[q]["mixed"]),
+                sum(1 for q in group if info[q][3] != 1))
+    rows, labelled = [], [q for q in range(len(per)) if int(own[q]) >= 0]
+    for g in range(len(names)):
+        group = [q for q in labelled if int(own[q]) == g]
+        if group:
+            rows.append(row(names[g], group))
+    if labelled:
+        rows.append(row("all", labelled))
+    return rows, len(per) - len(labelled)
+
+
+def mixture_matrix(n_labels, weights, own):
+    """M[A][B]: the mean share of label B over the queries whose own label is A; None where A has no query."""
+    total = [[0.0] * n_labels for _ in range(n_labels)]
+    seen = [0] * n_labels
+    for q in range(len(weights)):
+        a = int(own[q])
+        if a < 0:
+            continue
+        seen[a] += 1
+        for b, s in enumerate(mixture_shares(weights[q])):
+            total[a][b] += s
+    return [[total[a][b] / seen[a] if seen[a] else None for b in range(n_labels)] for a in range(n_labels)]
+
+
 # ---- morna cluster (DESIGN.md 8, N15) ----------------------------------------------------------------------------------
 CLUSTER_SHARDS_REFUSAL = ("cluster is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
                           "run it on an index built without --shards")
@@ -538,6 +625,31 @@ class SearchLabels(object):
 
     def map(self):
         return label_map(len(self.names), self.sums, self.counts, self.own)
+
+
+class SearchMixture(object):
+    """MornaSearch.label_mixture: names (the labels in file order), item_label (int32 [n], -1: none), weights (float64 [nq, L]),
+    info (float64 [nq, 4]: squared residual, KKT residual, sweeps, status), active (bool [nq, L]), own (the own label of every
+    by-item query, None for queries from outside the index) and stats (AnnoyIndex.mixture_stats summed over the calls)."""
+
+    def __init__(self, names, item_label, weights, info, active, own, stats):
+        self.names, self.item_label, self.weights, self.info, self.active = names, item_label, weights, info, active
+        self.own, self.stats = own, stats
+
+    def own_name(self, q):
+        return None if self.own is None or self.own[q] < 0 else self.names[int(self.own[q])]
+
+    def header(self, q, query_id):
+        return format_mixture_header(query_id, self.own_name(q), self.info[q])
+
+    def rows(self, q, top=3, min_share=0.1):
+        return mixture_rows(self.names, self.weights[q], top, min_share)
+
+    def summary(self, min_share=0.1):
+        return mixture_summary(self.names, self.weights, self.info, self.own, min_share)
+
+    def matrix(self):
+        return mixture_matrix(len(self.names), self.weights, self.own)
 
 
 class SearchHashing(object):
@@ -1072,6 +1184,55 @@ class MornaSearch(object):
                 query_groups=None if query_groups is None else query_groups[q0:q0 + step])
             add_stats()
         return SearchLabels(names, item_label, sums, counts, None if by_vector else item_label[queries], stats)
+
+    def label_mixture(self, queries, groups, restriction=None, tol=1e-9, max_sweeps=10000):
+        """Every query as a non-negative combination of the centroids of the labels of `groups`, fitted on the GPU
+        (AnnoyIndex.mixture).  queries: a QueryBatch (queries_from_intropolis), fp64 query vectors [nq, dim],
+        or a list of INTERNAL ids -- such a query is left out of its own label's centroid.  groups: [(label, [EXTERNAL ids])]
+        as parse_groups_file returns it, at most 128 labels; an id in two labels or outside the index is restriction_arrays'
+        ValueError.  restriction: an allow-list only (the library refuses one made with groups).  Returns a SearchMixture."""
+        from .shards import DistShards
+        if isinstance(self.annoy_index, DistShards):
+            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
+                               "run it in one process, which loads every shard of the index")
+        if not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(MIXTURE_SHARDS_REFUSAL)
+        groups = list(groups)
+        if not 1 <= len(groups) <= MIXTURE_LABELS_MAX:
+            raise ValueError(mixture_max_refusal(len(groups)))
+        n = self.annoy_index.get_n_items()
+        _, item_label, n_labels = restriction_arrays(self.internal_id_map, n, groups=groups)
+        names = [label for label, _ in groups]
+        self._check_restriction(restriction, None)
+        handle = restriction.handle if restriction is not None else None
+        stats = dict(centroids_ms=0.0, gram_ms=0.0, dots_ms=0.0, solve_ms=0.0, queries=0, sweeps=0, max_sweeps=0, open=0)
+
+        def add_stats():
+            last = self.annoy_index.mixture_stats()
+            for key in ("centroids_ms", "gram_ms", "dots_ms", "solve_ms", "queries", "sweeps", "open"):
+                stats[key] += last[key]
+            stats["max_sweeps"] = max(stats["max_sweeps"], last["max_sweeps"])
+        if isinstance(queries, QueryBatch):
+            self._check_batch(queries)
+            weights, info, active = self.annoy_index.mixture(item_label, n_labels, restriction=handle, tol=tol, max_sweeps=max_sweeps)
+            add_stats()
+            return SearchMixture(names, item_label, weights, info, active, None, stats)
+        by_vector = isinstance(queries, np.ndarray) and queries.ndim == 2
+        if by_vector:
+            queries = np.ascontiguousarray(queries, dtype=np.float64)
+        else:
+            queries = np.array(list(queries), np.int32).reshape(-1)
+        nq = len(queries)
+        weights, info = np.zeros((nq, n_labels), np.float64), np.zeros((nq, 4), np.float64)
+        active = np.zeros((nq, n_labels), bool)
+        step = max(1024, MIXTURE_CALL_CELLS // n_labels)       # queries of one call: its outputs stay modest
+        for q0 in range(0, nq, step):
+            part = queries[q0:q0 + step]
+            weights[q0:q0 + step], info[q0:q0 + step], active[q0:q0 + step] = self.annoy_index.mixture(
+                item_label, n_labels, Q=part if by_vector else None, items=None if by_vector else part, restriction=handle,
+                tol=tol, max_sweeps=max_sweeps)
+            add_stats()
+        return SearchMixture(names, item_label, weights, info, active, None if by_vector else item_label[queries], stats)
 
     def hashing_sweep(self, query_ids, num_neighbors, dims, junction_file, n_trees=None, search_k=None):
         """What every width of `dims` costs in neighbours and in norm distortion, from this one index.
