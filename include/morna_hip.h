@@ -61,6 +61,9 @@ int morna_add_items_f32(morna_index *h, int32_t first_id, const float *rows, int
  *   key_bytes/key_off[J+1]  the "chrom start end" strings        morna.py:849
  *   row_ptr[J+1]            extent of each line's lists
  *   item_ids[nnz]           INTERNAL id of each sample           morna.py:377-382
+ *                           (every id lies in [0, n_items) of the build_features call that follows: stage records the
+ *                           smallest and the largest, and build_features answers MORNA_E_RANGE, naming the bound
+ *                           that is broken, before it launches anything)
  *   cov[nnz]                coverages                            morna.py:852
  *   idf[J]                  log(sample_count / cumulative freq)  morna.py:372-374
  *                           (host libm, so that it is bit-identical to Python)

@@ -301,7 +301,19 @@ int morna_stage_junctions(morna_index *h, const uint8_t *key_bytes, const int64_
         HIP_TRY(hipMemcpyAsync(h->s_cov.p, cov, (size_t)nnz * 4, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(h->s_idf.p, idf, (size_t)J * 8, hipMemcpyHostToDevice, h->stream));
     }
+    // the range of the ids, taken while they are on the host (the copies above are in flight): build_features learns
+    // n_items only later, and the flag kernels index an LDS bitmap with the raw id
+    int32_t id_min = 0, id_max = -1;
+    if (nnz > 0) {
+        id_min = id_max = item_ids[0];
+        for (int64_t t = 1; t < nnz; t++) {
+            id_min = std::min(id_min, item_ids[t]);
+            id_max = std::max(id_max, item_ids[t]);
+        }
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->s_id_min = id_min;
+    h->s_id_max = id_max;
     h->J = J;
     h->nnz = nnz;
     h->key_bytes_n = nbytes;

@@ -349,6 +349,7 @@ struct morna_index {
     morna::DevBuf<int32_t> s_ids, s_cov;
     morna::DevBuf<double> s_idf;
     bool staged = false;
+    int32_t s_id_min = 0, s_id_max = -1;   // smallest and largest staged item id (nnz > 0): build_features checks them against n_items
     // optional order of the items in which the lines' sample lists ascend (morna_stage_item_order): rank of every item
     // and the item at every rank
     morna::DevBuf<int32_t> item_rank, item_at;

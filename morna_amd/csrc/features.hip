@@ -950,6 +950,16 @@ int build_features(morna_index *h, int64_t n_items)
         set_error("no internal ids were assigned: no sample passes the sample threshold");
         return MORNA_E_EMPTY;
     }
+    // the flag kernels index their LDS bitmap with the raw id: an id outside [0, n_items) is refused before any launch
+    if (h->nnz > 0 && h->s_id_min < 0) {
+        set_error("build_features: the smallest staged item id is %d: ids must lie in [0, n_items)", (int)h->s_id_min);
+        return MORNA_E_RANGE;
+    }
+    if (h->nnz > 0 && (int64_t)h->s_id_max >= n_items) {
+        set_error("build_features: the largest staged item id is %d: ids must lie in [0, n_items = %lld)", (int)h->s_id_max,
+                  (long long)n_items);
+        return MORNA_E_RANGE;
+    }
     const int64_t J = h->J;
     const int32_t D = h->dim;
     if (J > INT32_MAX) {

@@ -550,9 +550,10 @@ def test_feature_build_norms_are_canonical(capi, D, order):
     assert (X != 0).any()
 
 
-def test_feature_build_ignores_ids_past_n_items():
-    """Entries whose internal id is not below the n_items of build_features have no cell: both forms of the accumulation
-    skip them (the one that looks positions up in the item order must not read past its table)."""
+def test_feature_build_refuses_ids_past_n_items():
+    """Entries whose internal id is not below the n_items of build_features have no cell, and the flag kernels would index
+    their LDS bitmap with them: build_features answers MORNA_E_RANGE from the range morna_stage_junctions recorded, with
+    and without an item order, and builds the same lines once n_items covers them -- the same matrix in all three forms."""
     from morna_amd.annoy import AnnoyIndex
     rng = np.random.default_rng(8)
     D, n_items, J = 64, 300, 120
@@ -568,17 +569,23 @@ def test_feature_build_ignores_ids_past_n_items():
         rp.append(len(ids))
     args = (np.frombuffer(b"".join(kb), np.uint8), key_off, np.array(rp, np.int64), np.array(ids, np.int32), np.array(cov, np.int32),
             rng.random(J) + 0.5)
+    assert max(ids) == n_items + 49
     out = []
-    for order in (None, np.arange(n_items, dtype=np.int64), np.arange(n_items, dtype=np.int64)[::-1].copy()):
+    for order in (None, np.arange(n_items + 50, dtype=np.int64), np.arange(n_items + 50, dtype=np.int64)[::-1].copy()):
         a = AnnoyIndex(D)
         a.stage_junctions(*args)
         if order is not None:
+            a.stage_item_order(order[:n_items])
+        for n in (n_items, n_items + 49):
+            with pytest.raises(IndexError, match="largest staged item id is %d" % (n_items + 49)):
+                a.build_features(n)
+            assert a.get_n_items() == 0
+        if order is not None:
             a.stage_item_order(order)
-        a.build_features(n_items)
+        a.build_features(n_items + 50)
         out.append(a.get_items())
     assert out[0].tobytes() == out[1].tobytes() == out[2].tobytes()
-    keep = np.array(ids) < n_items
-    assert (out[0] != 0).any() and keep.sum() < len(ids)
+    assert (out[0] != 0).any() and out[0].shape == (n_items + 50, D)
 
 
 def test_exact_search_large_shard_selection_edges(capi):
