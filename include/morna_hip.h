@@ -258,6 +258,46 @@ int morna_jstore_nearest_by_sample(morna_jstore *s, const int64_t *pop_ext, int6
 int morna_jstore_nearest_stats(const morna_jstore *s, double *stats);
 
 /*
+ * ---- the junctions behind a query and each result -----------------------------------------------------
+ * The decomposition of the unhashed cosine above for (query, result row) pairs; no counterpart in the reference.  All
+ * arithmetic is that search's: v = RN(double(cov) * w[line]); every sum is x = RN(x + term) from 0.0 over the RESULT ROW's
+ * entries in ascending line order (qq: over the query's); a line the query lacks has query component +0.0.  Per pair:
+ * pq = sum RN(v_r * v_q), pp = sum RN(v_r * v_r), qq, distance (as morna_jstore_nearest); shared = the row's entries with
+ * v_r != 0 and v_q != 0; pp_shared = sum of RN(v_r * v_r) where v_q != 0; qq_shared = sum of RN(v_q * v_q) where v_r != 0;
+ * n_q, n_r = the entries of query and row with a nonzero component; the top list = the min(top, shared) shared lines of
+ * largest RN(v_r * v_q), equal terms by ascending line.  Bit-identical on every run, whatever the tiling.
+ *   morna_jstore_explain      nq sparse queries as morna_jstore_nearest takes and checks them; results[nq][k] (external
+ *                             sample ids in rank order; list q holds n_results[q] <= k of them, the layout of
+ *                             morna_jstore_retain).  Every (query, result) pair of every query in one call; an id may stand
+ *                             at several ranks.  1 <= k <= MORNA_JNEAREST_MAX_K, 1 <= top <= MORNA_JEXPLAIN_MAX_TOP,
+ *                             nq * k * top <= 2^28 (MORNA_E_INVALID naming the limit); no weights: MORNA_E_STATE; a result id
+ *                             the store lacks: MORNA_E_RANGE naming it; a negative coverage in a result row: MORNA_E_INVALID
+ *                             naming sample and line.
+ *   morna_jstore_explain_by_sample   the same with the queries taken from the store rows q_ext[nq] (external ids; an id the
+ *                             store lacks is MORNA_E_RANGE): nothing but ids crosses to the device.
+ *   morna_jexplained_pair     the pair (query q, rank < n_results[q]; MORNA_E_RANGE otherwise): sums[6] = pq, pp, qq,
+ *                             pp_shared, qq_shared, distance; counts[3] = shared, n_q, n_r; *n_top = min(top, shared);
+ *                             lines / terms / cov_r [*n_top]: the top list's line numbers, terms and the RESULT's coverages
+ *                             (library-owned, valid until morna_jexplained_free; the lists of a query's ranks follow one
+ *                             another, `top` places each).  Any output may be NULL.
+ *   morna_jstore_explain_stats       of the last call, stats[6]: pairs, store entries streamed, passes, kernel ms (HIP
+ *                             events), algorithmic bytes (8 per entry streamed), queries per pass (QT).  All 0 after a call
+ *                             that failed its checks.
+ */
+#define MORNA_JEXPLAIN_MAX_TOP 64
+typedef struct morna_jexplained morna_jexplained;
+int morna_jstore_explain(morna_jstore *s, const int64_t *q_ptr, const int32_t *q_line, const int32_t *q_cov, int64_t nq,
+                         const int64_t *results /* [nq][k] external ids, rank order */, const int32_t *n_results /* [nq] */,
+                         int32_t k, int32_t top, morna_jexplained **out);
+int morna_jstore_explain_by_sample(morna_jstore *s, const int64_t *q_ext /* [nq] */, int64_t nq, const int64_t *results,
+                                   const int32_t *n_results, int32_t k, int32_t top, morna_jexplained **out);
+int morna_jexplained_pair(const morna_jexplained *e, int64_t q, int32_t rank, double *sums /* [6]: pq pp qq pp_shared qq_shared distance */,
+                          int64_t *counts /* [3]: shared n_q n_r */, int32_t *n_top, const int32_t **lines, const double **terms,
+                          const int32_t **cov_r);
+int morna_jexplained_free(morna_jexplained *e);
+int morna_jstore_explain_stats(const morna_jstore *s, double *stats /* [6]: pairs, store entries streamed, passes, kernel ms, algorithmic bytes (8 per entry streamed), QT */);
+
+/*
  * ---- junction recovery tables over the filter grid -------------------------------------------------
  * How much of a truth set of lines the retention step gives back under EVERY (frequency, coverage) pair of a grid, from
  * one pass over the result rows.  (The quantities are those junction_recovery_performance.py of the reference's tests/

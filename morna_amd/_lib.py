@@ -75,6 +75,11 @@ SIGNATURES = {
     "morna_jstore_nearest": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p]),
     "morna_jstore_nearest_by_sample": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "morna_jstore_nearest_stats": (C.c_int, [_p, _p]),
+    "morna_jstore_explain": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _i32, C.POINTER(_p)]),
+    "morna_jstore_explain_by_sample": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, C.POINTER(_p)]),
+    "morna_jexplained_pair": (C.c_int, [_p, _i64, _i32, _p, _p, C.POINTER(_i32)] + [C.POINTER(_p)] * 3),
+    "morna_jexplained_free": (C.c_int, [_p]),
+    "morna_jstore_explain_stats": (C.c_int, [_p, _p]),
     "morna_jstore_recovery": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _p]),
     "morna_jstore_recovery_by_sample": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _p, _i32, _p]),
     "morna_jstore_recovery_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _p, _i32, _p]),

@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` / `morna mixture` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` / `morna mixture` / `morna explain` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -77,6 +77,13 @@ the labels (a non-negative least squares fit on the unit sphere, fp64, on the GP
 their shares, how far the blend stays from the query, and whether a second label holds a share of at least --min-share.  A
 query that is a sample of the index is left out of its own label's centroid.
 
+`explain` answers the question left after every search -- why is this sample near mine: it searches as `search` does with the
+same flags (or takes the samples of --against, the follow-up to a line of `morna pairs`) and prints for every (query, result)
+pair the unhashed distance beside the search's own, the number of junctions both hold, the share of either sample's squared
+TF-IDF weight that lies outside those, and under it the --top junctions that carry most of the cosine, each with both
+coverages, its weight and its share.  Every pair of every query in one call on the GPU, from the junction store and its
+weights; the reference has no counterpart.
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -108,6 +115,8 @@ here do the latter.
     python -m morna_amd.cli mixture -x idx --labels tissues.tsv --query-ids 17,42 --top 3 --min-share 0.1
     python -m morna_amd.cli search -x idx -e --max-distance 0.15 --query-ids 17,42 -d
     python -m morna_amd.cli pairs -x idx --max-distance 0.05 --leave-out-groups donors.tsv --clusters
+    python -m morna_amd.cli explain -x idx --junction-file junctions.tsv.gz --query-ids 17,42 -r 20 --top 10
+    python -m morna_amd.cli explain -x idx --junction-file junctions.tsv.gz -q 17 --against 42,1234 --summary-only
 """
 import argparse
 import sys
@@ -488,6 +497,47 @@ def build_parser():
     cluster_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
     cluster_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
     cluster_parser.add_argument('--leave-out-groups', type=str, required=False, default=None, help=argparse.SUPPRESS)
+    explain_parser = subparsers.add_parser('explain', help='searches a morna index and prints, for every query and result, the '
+                                                           'junctions behind their distance: how many they share, how much of '
+                                                           'either sample lies outside those, and the junctions that carry most')
+    explain_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
+                                help='basename of an index built with --junction-store (an index without row shards)')
+    explain_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
+                                help='path to the (gzipped) intropolis file the index was made from: it names the junctions')
+    explain_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
+                                help='the query is the sample already in the index with this sample id')
+    explain_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
+                                help='comma-separated sample ids already in the index')
+    explain_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
+                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
+    explain_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                                help='the seed of --sample (default 0)')
+    explain_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
+                                help='every sample of this (gzipped) intropolis file is a query')
+    explain_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
+                                help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+    explain_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20, action=_StoreGiven,
+                                help='the number of nearest neighbor results to search for and explain (default 20)')
+    explain_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False,
+                                help='search exactly, as `search -e` does')
+    explain_parser.add_argument('--unhashed', action='store_const', const=True, default=False,
+                                help='search in the space of the junctions themselves, as `search --unhashed` does')
+    explain_parser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
+                                help='a larger value makes for more accurate search')
+    explain_parser.add_argument('--against', metavar='<ids>', type=str, required=False, default=None,
+                                help='comma-separated sample ids of the index: no search runs, every query is explained against '
+                                     'every one of them, in this order (the follow-up to a line of `morna pairs`)')
+    explain_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=10,
+                                help='the junctions of largest contribution printed per pair, 1 to 64 (default 10)')
+    explain_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
+                                help='answer only with the samples this file lists, one integer sample id per line')
+    explain_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
+                                help='never answer with a sample this file lists, one integer sample id per line')
+    explain_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
+                                help='print only the line of every pair, not the junctions under it')
+    explain_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
+                                help='append the metadata keywords of every result, as `search -m` does')
+    explain_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
     return parser
 
 
@@ -900,6 +950,74 @@ def _check_mixture_flags(parser, args):
     _check_labels_flags(parser, args, command='mixture')
 
 
+def _check_explain_flags(parser, args):
+    """`explain`: at most one named query source (none: a stream on stdin), the numbers, what --against excludes, and the
+    files the command cannot do without; argparse errors, before any index is read.  Leaves the ids of --against in
+    args.against_ids and the restriction's parts where _check_restriction_flags leaves them."""
+    import os
+    from .junctions import MAX_NEAREST, STORE_SUFFIX, WEIGHTS_SUFFIX, parse_sample_ids_file
+    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+                                   ("--sample", args.sample is not None), ("--intropolis", args.intropolis is not None)) if on]
+    if len(given) > 1:
+        parser.error("explain takes one query source: -q, --query-ids, --sample, --intropolis or a stream on stdin "
+                     "(got %s)" % " and ".join(given))
+    if args.format not in ("sam", "bed", "raw"):
+        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
+    if args.query_ids is not None:
+        try:
+            args.query_ids = [int(t) for t in args.query_ids.split(',')]
+        except ValueError:
+            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
+    if args.sample is None and getattr(args, "sample_seed_given", False):
+        parser.error("--sample-seed cannot be used without --sample")
+    if args.sample is not None and args.sample < 1:
+        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
+    if args.top < 1 or args.top > 64:
+        parser.error("--top takes 1 to 64 junctions per pair (got %d)" % args.top)
+    if args.results < 1 or args.results > MAX_NEAREST:
+        parser.error("-r takes 1 to %d results (got %d)" % (MAX_NEAREST, args.results))
+    args.external = not given or args.intropolis is not None
+    args.against_ids = None
+    if args.against is not None:
+        for flag, on in (("-r/--results", getattr(args, "results_given", False)), ("-e/--exact", args.exact),
+                         ("--unhashed", args.unhashed), ("--search-k", getattr(args, "search_k_given", False)),
+                         ("--within", args.within is not None), ("--without", args.without is not None)):
+            if on:
+                parser.error("--against cannot be used with %s: no search runs, the samples it lists are the results" % flag)
+        try:
+            args.against_ids = [int(t) for t in args.against.split(',')]
+        except ValueError:
+            parser.error("--against takes comma-separated integer sample ids (got %r)" % args.against)
+        if len(args.against_ids) > MAX_NEAREST:
+            parser.error("--against takes at most %d samples (got %d)" % (MAX_NEAREST, len(args.against_ids)))
+    if args.unhashed:
+        for flag, on in (("-e/--exact", args.exact), ("--search-k", getattr(args, "search_k_given", False))):
+            if on:
+                parser.error("--unhashed cannot be used with %s" % flag)
+    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
+    try:
+        if args.within is not None:
+            args.within_ids = parse_sample_ids_file(args.within)
+        if args.without is not None:
+            args.without_ids = parse_sample_ids_file(args.without)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+    if args.within_ids is not None and args.without_ids is not None:
+        both = sorted(set(args.within_ids) & set(args.without_ids))
+        if both:
+            parser.error("--within and --without both name sample id %d" % both[0])
+    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        parser.error("explain is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                     "run it on an index built without --shards")
+    if not os.path.exists(args.basename + STORE_SUFFIX):
+        parser.error("%s not found: this index has no junction store; build it with `morna index --junction-store`"
+                     % (args.basename + STORE_SUFFIX))
+    if not os.path.exists(args.basename + WEIGHTS_SUFFIX):
+        parser.error("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
+                     "to the junction store. They are not written when a junction repeats in the indexed file: "
+                     "the unhashed search is defined for files without repeated junctions" % (args.basename + WEIGHTS_SUFFIX))
+
+
 def _check_batch_flags(parser, args):
     """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
     batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
@@ -977,6 +1095,8 @@ def main(argv=None, stdin=None, stdout=None):
         _check_cluster_flags(parser, args)
     if args.subparser_name == 'mixture':
         _check_mixture_flags(parser, args)
+    if args.subparser_name == 'explain':
+        _check_explain_flags(parser, args)
     stdin = stdin or sys.stdin
     stdout = stdout or sys.stdout
     if args.subparser_name == 'index':
@@ -1006,6 +1126,8 @@ def main(argv=None, stdin=None, stdout=None):
         return _pairs(args, stdout)
     if args.subparser_name == 'cluster':
         return _cluster(args, stdout)
+    if args.subparser_name == 'explain':
+        return _explain(args, stdin, stdout)
     if args.subparser_name not in ('search', 'junctions', 'recovery'):
         build_parser().print_help()
         return 2
@@ -1255,6 +1377,144 @@ def _labels(args, stdin, stdout):
         stdout.write("# label map\n")
         stdout.write(format_label_rows([(name,) + tuple(row) for name, row in zip(table.names, table.map())]))
     return 0
+
+
+def _by_label(labels, ext_ids, found):
+    """The results of a batch of the hashed searches (sample ids ext_ids) in the order of `labels`."""
+    by_id = dict(zip(ext_ids, found))
+    return [by_id.get(label, ValueError("sample %s holds no junction of the index" % label)) for label in labels]
+
+
+def _explain_searches(args, searcher, stream, terms, query_ids, labels):
+    """The searches of `explain` without --against: what `search` runs with the same flags, distances included; one result
+    tuple (or exception) per query."""
+    restriction = _restriction(args)
+    if query_ids is not None:
+        if args.unhashed:
+            return searcher.unhashed_search_member_n_batch(query_ids, args.results, include_distances=True, meta_db=args.metadata,
+                                                           restriction=restriction)
+        return searcher.search_member_n_batch(query_ids, args.results, _search_k(args), include_distances=True,
+                                              meta_db=args.metadata, restriction=restriction)[1]
+    if args.unhashed:
+        return searcher.unhashed_search_nn_batch(terms, args.results, include_distances=True, meta_db=args.metadata,
+                                                 restriction=restriction)
+    if args.intropolis is not None:
+        batch = searcher.queries_from_intropolis(args.intropolis)
+        if args.exact:
+            found = searcher.exact_search_nn_batch(batch, args.results, include_distances=True, meta_db=args.metadata,
+                                                   restriction=restriction)
+        else:
+            found = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=True, meta_db=args.metadata,
+                                             restriction=restriction)
+        return _by_label(labels, batch.ext_ids, found)
+    for junction in stream:
+        if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
+            searcher.update_query(junction)
+    searcher.finalize_query()
+    if args.exact:
+        return [searcher.exact_search_nn(args.results, include_distances=True, meta_db=args.metadata, restriction=restriction)]
+    return [searcher.search_nn(args.results, _search_k(args), include_distances=True, meta_db=args.metadata, restriction=restriction)]
+
+
+def _explain_against(args, searcher, stream, query_ids, labels):
+    """explain --against: no search; every query gets the listed samples in the order listed, each with its distance in
+    the exact search restricted to them."""
+    import numpy as np
+    from .metadb import lookup_meta
+    for sample_id in args.against_ids:
+        if sample_id not in searcher.internal_id_map:
+            raise ValueError("--against names sample id %d, which is not a sample of the index" % sample_id)
+    listed = [searcher.internal_id_map[s] for s in args.against_ids]
+    restriction = searcher.restriction(within=sorted(set(args.against_ids)))
+    n = len(set(listed))
+    if query_ids is not None:
+        ids, d, cnt = searcher.annoy_index.exact_search_restricted(
+            restriction.handle, n, items=np.array([searcher.internal_id_map[q] for q in query_ids], np.int32))
+        found = searcher._batch_results(ids, d, cnt, True, False)
+    elif args.intropolis is not None:
+        batch = searcher.queries_from_intropolis(args.intropolis)
+        found = _by_label(labels, batch.ext_ids, searcher.exact_search_nn_batch(batch, n, include_distances=True,
+                                                                                restriction=restriction))
+    else:
+        for junction in stream:
+            if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
+                searcher.update_query(junction)
+        searcher.finalize_query()
+        found = [searcher.exact_search_nn(n, include_distances=True, restriction=restriction)]
+    meta = lookup_meta(searcher.basename, list(args.against_ids)) if args.metadata else None
+    results = []
+    for res in found:
+        if isinstance(res, Exception):
+            results.append(res)
+            continue
+        distance = dict(zip(res[0], res[1]))
+        results.append((listed, [distance.get(i, float("nan")) for i in listed]) + ((meta,) if meta is not None else ()))
+    return results
+
+
+def _explain(args, stdin, stdout):
+    """`explain`: the search of `search` with the same flags (or the samples of --against), then every (query, result) pair
+    explained in one call on the GPU; a block per query, a line per pair and under it a line per junction of its top
+    list."""
+    import numpy as np
+    from .junctions import (explain_rows, format_explain_rows, intropolis_query_terms, key_lines, line_names, query_terms)
+    from .search import MornaSearch
+    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    store, w = searcher.unhashed_store()
+    stream, terms, query_ids = None, None, None
+    if args.intropolis is not None:
+        labels, terms = intropolis_query_terms(args.intropolis, key_lines(args.junction_file, store.n_lines), w)
+    elif args.external:                                        # a stream: one query, its coverages summed per junction
+        stream = list(_stream_parser(args.format)(stdin))
+        coverage = {}
+        for junction in stream:
+            key = " ".join(str(_) for _ in junction[:3])
+            coverage[key] = coverage.get(key, 0) + int(junction[3])
+        labels, terms = ["stdin"], [query_terms(coverage, key_lines(args.junction_file, store.n_lines), w)]
+    else:
+        if args.sample is not None:
+            inv = searcher._inverse_map()
+            n = searcher.annoy_index.get_n_items()
+            if args.sample > n:
+                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
+            picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
+            query_ids = [inv[int(i)] for i in picked]
+        else:
+            query_ids = args.query_ids if args.query_ids is not None else [args.query_id]
+        for query_id in query_ids:
+            if query_id not in searcher.internal_id_map:
+                raise ValueError("Querying sample id " + str(query_id)
+                                 + " is not possible because no internal id is mapped to that "
+                                 + "sample id. Likely no sample with that id was included "
+                                 + "in the index.")
+        labels = list(query_ids)
+    if args.against_ids is not None:
+        results = _explain_against(args, searcher, stream, query_ids, labels)
+    else:
+        args.restriction = _make_restriction(args, searcher)
+        results = _explain_searches(args, searcher, stream, terms, query_ids, labels)
+    if len(results) != len(labels):
+        raise RuntimeError("explain: %d queries, %d result lists" % (len(labels), len(results)))
+    lists = [[] if isinstance(res, Exception) else list(res[0]) for res in results]
+    rows = [store.sample(q) for q in query_ids] if query_ids is not None else terms
+    explained = searcher.explain_results(lists, [searcher.internal_id_map[q] for q in query_ids] if query_ids is not None else terms,
+                                         args.top)
+    names = None
+    if not args.summary_only:
+        names = line_names(args.junction_file, [int(l) for pairs in explained for p in pairs for l in p.lines])
+    inv = searcher._inverse_map()
+    failed = False
+    for label, res, pairs, (q_lines, q_cov) in zip(labels, results, explained, rows):
+        stdout.write("# query %s\n" % label)
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+            continue
+        for rank, pair in enumerate(pairs):
+            summary, top_rows = explain_rows(pair, q_lines, q_cov, w, names)
+            stdout.write(format_explain_rows(rank + 1, res[0][rank], inv[int(res[0][rank])], res[1][rank], summary,
+                                             () if args.summary_only else top_rows, res[2][rank] if args.metadata else None))
+    return 1 if failed else 0
 
 
 def _pairs(args, stdout):

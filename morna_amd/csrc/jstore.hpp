@@ -1,4 +1,5 @@
-// jstore.hpp -- the junction store as jstore.hip (build, load, filter) and nearest.hip (unhashed search) share it.
+// jstore.hpp -- the junction store as jstore.hip (build, load, filter), nearest.hip (unhashed search) and explain.hip (the
+// junctions behind a result) share it.
 #pragma once
 #include <exception>
 #include <memory>
@@ -41,6 +42,8 @@ struct morna_jstore {
     morna::DevBuf<int32_t> d_hr_hash, d_hr_col, d_hr_rows;
     morna::DevBuf<double> d_hr_sw;
     double hr_stats[4] = {0, 0, 0, 0};
+    // of the last explain (explain.hip): pairs, store entries streamed, passes, kernel ms, algorithmic bytes, queries per pass
+    double explain_stats[6] = {0, 0, 0, 0, 0, 0};
     std::shared_ptr<morna_jnearest> nearest;   // made by morna_jstore_set_weights
     ~morna_jstore()
     {

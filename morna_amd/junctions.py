@@ -201,6 +201,32 @@ class Thinned(object):
         return len(self.lines)
 
 
+class Explained(object):
+    """One (query, result) pair of JunctionStore.explain: the sums pq, pp, qq, pp_shared, qq_shared and
+    the unhashed distance (fp64, in the contract's order), the counts shared, n_q, n_r, and the top list -- lines (int32),
+    terms (fp64, descending; equal terms by ascending line) and cov_r (the result's coverages, int32)."""
+    SUMS = ("pq", "pp", "qq", "pp_shared", "qq_shared", "distance")
+    COUNTS = ("shared", "n_q", "n_r")
+
+    def __init__(self, sums, counts, lines, terms, cov_r):
+        self.sums, self.counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
+        for name, x in zip(self.SUMS, self.sums.tolist()):
+            setattr(self, name, x)
+        for name, n in zip(self.COUNTS, self.counts.tolist()):
+            setattr(self, name, n)
+        self.lines, self.terms, self.cov_r = lines, terms, cov_r
+
+    @property
+    def query_outside(self):
+        """The share of the query's squared weight on lines the result lacks: 1 - qq_shared / qq (nan for qq = 0)."""
+        return 1.0 - self.qq_shared / self.qq if self.qq > 0 else float("nan")
+
+    @property
+    def result_outside(self):
+        """The share of the result's squared weight on lines the query lacks: 1 - pp_shared / pp (nan for pp = 0)."""
+        return 1.0 - self.pp_shared / self.pp if self.pp > 0 else float("nan")
+
+
 def lost_lines(row_lines, row_cov, thinned_lines, min_coverage=1):
     """The truth of `recovery --downsample --lost-only`: the lines of a sample's full row covered at least min_coverage
     times that its thinned row does not hold -- what the shallow sequencing lost -- ascending, int32.  Pure host code."""
@@ -221,13 +247,13 @@ def _clamp62(x):
     return min(max(int(x), -2**62), 2**62)
 
 
-def _pack_lists(lists, what):
+def _pack_lists(lists, what, limit=MAX_RESULTS):
     """Result lists (external sample ids in rank order) as (res [nq][k] int64, n_res [nq] int32, k), k the longest
-    list's length, at least 1; past 64 results ValueError, `what` the words for who takes no more."""
+    list's length, at least 1; past `limit` (64) results ValueError, `what` the words for who takes no more."""
     lists = [[int(s) for s in lst] for lst in lists]
     k = max([len(lst) for lst in lists] + [1])
-    if k > MAX_RESULTS:
-        raise ValueError(("a result list holds %d results: " + what) % (k, MAX_RESULTS))
+    if k > limit:
+        raise ValueError(("a result list holds %d results: " + what) % (k, limit))
     res = np.zeros((len(lists), k), np.int64)
     n_res = np.zeros(len(lists), np.int32)
     for q, lst in enumerate(lists):
@@ -348,6 +374,69 @@ class JunctionStore(object):
         check(lib().morna_jstore_nearest_stats(self._p, ptr(s)))
         return {"candidates": int(s[0]), "max_candidates": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]),
                 "bytes": int(s[4]), "queries_per_pass": int(s[5]), "norms_ms": float(s[6]), "window": float(s[7])}
+
+    # ---- the junctions behind a query and each result (csrc/explain.hip) ---------------------------
+    def _explained(self, r, n_res, top):
+        """The Explained objects of a morna_jexplained, list by list; frees it."""
+        try:
+            out = []
+            sums, counts, n_top = np.zeros(6, np.float64), np.zeros(3, np.int64), C.c_int32()
+            pair = lib().morna_jexplained_pair
+            p_sums, p_counts, p_top = ptr(sums), ptr(counts), C.byref(n_top)
+            for q, n in enumerate(n_res.tolist()):
+                pairs = []
+                if n:                                          # a query's lists are [k][top], rank-major: one view of each
+                    p = [C.c_void_p() for _ in range(3)]
+                    check(pair(r, q, 0, None, None, None, *[C.byref(x) for x in p]))
+                    lines, terms, cov_r = [view(x, t, n * top).reshape(n, top) for x, t in zip(p, (C.c_int32, C.c_double, C.c_int32))]
+                for rank in range(n):
+                    check(pair(r, q, rank, p_sums, p_counts, p_top, None, None, None))
+                    m = n_top.value
+                    pairs.append(Explained(sums.copy(), counts.copy(), lines[rank, :m], terms[rank, :m], cov_r[rank, :m]))
+                out.append(pairs)
+            return out
+        finally:
+            lib().morna_jexplained_free(r)
+
+    def explain(self, queries, result_sample_ids, top):
+        """For every query -- a (lines ascending, coverages >= 0) pair as nearest() takes them -- and every sample of its
+        list in `result_sample_ids` (external ids in rank order, at most 1024 per list; an id may stand at several ranks),
+        the decomposition of the unhashed cosine of the pair: one list of Explained per query.  All pairs in one call on
+        the GPU.  IndexError for an id the store lacks, ValueError for a negative coverage, unsorted lines, or `top`
+        outside [1, 64], RuntimeError without weights."""
+        queries = [(np.ascontiguousarray(l, np.int32), np.ascontiguousarray(c, np.int32)) for l, c in queries]
+        for l, c in queries:
+            if l.ndim != 1 or l.shape != c.shape:
+                raise ValueError("an unhashed query is a pair of 1-d arrays of one length: lines and coverages")
+        res, n_res, k = _pack_lists(result_sample_ids, "explain takes at most %d", MAX_NEAREST)
+        if len(n_res) != len(queries):
+            raise ValueError("explain takes one result list per query (%d queries, %d lists)" % (len(queries), len(n_res)))
+        q_ptr = np.zeros(len(queries) + 1, np.int64)
+        np.cumsum([len(l) for l, _ in queries], out=q_ptr[1:])
+        q_line = np.concatenate([l for l, _ in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+        q_cov = np.concatenate([c for _, c in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+        r = C.c_void_p()
+        check(lib().morna_jstore_explain(self._p, ptr(q_ptr), ptr(q_line), ptr(q_cov), len(queries), ptr(res), ptr(n_res), k, int(top),
+                                         C.byref(r)))
+        return self._explained(r, n_res, int(top))
+
+    def explain_by_sample(self, query_sample_ids, result_sample_ids, top):
+        """explain() with the store's own rows as the queries (external sample ids): only ids go to the device."""
+        q = np.ascontiguousarray([int(s) for s in query_sample_ids], np.int64)
+        res, n_res, k = _pack_lists(result_sample_ids, "explain takes at most %d", MAX_NEAREST)
+        if len(n_res) != len(q):
+            raise ValueError("explain takes one result list per query (%d queries, %d lists)" % (len(q), len(n_res)))
+        r = C.c_void_p()
+        check(lib().morna_jstore_explain_by_sample(self._p, ptr(q), len(q), ptr(res), ptr(n_res), k, int(top), C.byref(r)))
+        return self._explained(r, n_res, int(top))
+
+    def explain_stats(self):
+        """Of the last explain / explain_by_sample: pairs explained, store entries streamed, passes (query tiles), kernel ms
+        (HIP events), algorithmic bytes (8 per entry streamed) and queries per pass; all 0 after a refused call."""
+        s = np.zeros(6, np.float64)
+        check(lib().morna_jstore_explain_stats(self._p, ptr(s)))
+        return {"pairs": int(s[0]), "entries": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]), "bytes": int(s[4]),
+                "queries_per_pass": int(s[5])}
 
     # ---- recovery tables over the filter grid (DESIGN.md 8, N6) -------------------------------------------------------
     def _recovery_arguments(self, result_sample_ids, coverage_grid, prefixes=None):
@@ -778,6 +867,73 @@ def write_splice_files(junction_file, jobs):
     finally:
         for fh in handles:
             fh.close()
+
+
+# ---- the junctions behind a result: the lines of `morna explain` ---------------------------------------
+def line_names(junction_file, lines):
+    """{line number: "chrom start end"} for the line numbers `lines` of `junction_file`, from one pass over the file that
+    keeps only the lines asked for and stops behind the last.  ValueError when the file ends before one of them or a
+    line has fewer than three fields."""
+    wanted = sorted(set(int(j) for j in lines))
+    names = {}
+    if not wanted:
+        return names
+    at = 0
+    with _open_text(junction_file) as fh:
+        for i, text in enumerate(fh):
+            if i != wanted[at]:
+                continue
+            pieces = text.split()
+            if len(pieces) < 3:
+                raise ValueError("line %d of %s has %d fields, a junction has at least 3" % (i, junction_file, len(pieces)))
+            names[i] = " ".join(pieces[:3])
+            at += 1
+            if at == len(wanted):
+                break
+    if at < len(wanted):
+        raise ValueError("%s ends before line %d: it is not the file that was indexed" % (junction_file, wanted[at]))
+    return names
+
+
+def explain_rows(pair, q_lines, q_cov, w, names=None):
+    """What `morna explain` prints for one Explained: (summary, rows).  summary: (unhashed distance, shared, the share of the
+    query's squared weight outside the intersection, the share of the result's, the share of pq the top list carries);
+    rows, one per top entry: ("chrom start end" from `names`, or the line number without them; the query's coverage,
+    looked up in its row (q_lines ascending, q_cov); the result's coverage; the line's weight; its share of pq).  A
+    share whose denominator is 0 is nan.  Pure host code."""
+    q_lines, q_cov = np.asarray(q_lines, np.int64), np.asarray(q_cov, np.int64)
+    terms = [float(t) for t in pair.terms]
+    pq = float(pair.pq)
+    share = lambda x: x / pq if pq > 0 else float("nan")
+    rows = []
+    for l, t, c in zip([int(x) for x in pair.lines], terms, [int(x) for x in pair.cov_r]):
+        at = int(np.searchsorted(q_lines, l))
+        if at >= len(q_lines) or q_lines[at] != l:
+            raise ValueError("line %d of a top list is not in the query's row: the row is not the one that was explained" % l)
+        rows.append((names[l] if names is not None else l, int(q_cov[at]), c, float(w[l]), share(t)))
+    return (float(pair.distance), int(pair.shared), pair.query_outside, pair.result_outside, share(sum(terms))), rows
+
+
+def _explain_cell(v):
+    if isinstance(v, float):
+        return "nan" if v != v else "%.6f" % v
+    return str(v)
+
+
+def format_explain_rows(rank, shown_id, sample_id, search_distance, summary, rows=(), meta=None):
+    """One pair of `morna explain`: the line "rank. id sample-id search-distance distance shared query-outside
+    result-outside top-share" (tab-separated; `id` as `search` prints it, both distances as `search -d` prints them, the
+    shares as %.6f or nan; `meta` appended as `search -m` appends it), then one line per row of explain_rows, led by a tab:
+    junction, query coverage, result coverage, weight (as str of the float), share of pq."""
+    dist = lambda d: "nan" if d != d else str(float(d))
+    head = [str(rank) + ".", str(shown_id), str(sample_id), dist(search_distance), dist(summary[0]), str(summary[1])]
+    head += [_explain_cell(float(x)) for x in summary[2:]]
+    if meta is not None:
+        head.append(str(meta))
+    out = ["\t".join(head) + "\n"]
+    for name, cov_q, cov_r, weight, share in rows:
+        out.append("\t%s\t%d\t%d\t%s\t%s\n" % (name, cov_q, cov_r, str(float(weight)), _explain_cell(float(share))))
+    return "".join(out)
 
 
 # ---- pooled samples: the files of create_supersample.py (DESIGN.md 8, N8) ----------------------------------------------

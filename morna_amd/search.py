@@ -1513,6 +1513,19 @@ class MornaSearch(object):
         ids = self._unhashed_ids(ids, restriction)
         return self._batch_results(ids, d, cnt, include_distances, meta_db)
 
+    # ---- the junctions behind a query and each result: no counterpart in the reference -----------
+    def explain_results(self, result_lists, queries, top=10):
+        """For every query and every result of its list (internal ids in rank order, as retain_junctions takes them; at most
+        1024 per list) the decomposition of their unhashed cosine (junctions.JunctionStore.explain): one list of
+        junctions.Explained per query.  queries: internal ids, or the (lines ascending, coverages) term lists of
+        unhashed_search_nn_batch.  All pairs in one call on the GPU."""
+        store, _ = self.unhashed_store()
+        lists = [self.result_sample_ids(lst) for lst in result_lists]
+        queries = list(queries)
+        if all(np.ndim(q) == 0 for q in queries):
+            return store.explain_by_sample(self.result_sample_ids(queries), lists, top)
+        return store.explain(queries, lists, top)
+
     def search_member_n(self, query_id, num_neighbors, search_k, include_distances=True, meta_db=False, n_trees=None):
         """Neighbours of an indexed sample (morna.py:733-787); n_trees: as search_nn."""
         self._check_trees(n_trees)
