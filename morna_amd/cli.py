@@ -134,49 +134,110 @@ class _StoreGiven(argparse.Action):
         setattr(namespace, self.dest + "_given", True)
 
 
+# ---- the parser -------------------------------------------------------------------------------------------------------------
+_CONST = dict(action='store_const', const=True, default=False)
+_FILE = dict(metavar='<file>', type=str, required=False, default=None)
+_INT = dict(metavar='<int>', type=int, required=False, default=None)
+# the flags several commands take, by dest: their names and everything but the help text, which is every command's own
+_SHARED = {
+    'basename': (('-x', '--basename'), dict(metavar='<idx>', type=str, required=True)),
+    'verbose': (('-v', '--verbose'), _CONST),
+    'query_id': (('-q', '--query-id'), _INT),
+    'query_ids': (('--query-ids',), dict(metavar='<ids>', type=str, required=False, default=None)),
+    'sample': (('--sample',), _INT),
+    'sample_seed': (('--sample-seed',), dict(metavar='<int>', type=int, required=False, default=0, action=_StoreGiven)),
+    'all_items': (('--all',), dict(dest='all_items', **_CONST)),
+    'intropolis': (('--intropolis',), _FILE),
+    'format': (('-f', '--format'), dict(metavar='<choice>', type=str, required=False, default='sam')),
+    'exact': (('-e', '--exact'), _CONST),
+    'unhashed': (('--unhashed',), _CONST),
+    'search_k': (('--search-k',), dict(metavar='<int>', type=int, required=False, default=100, action=_StoreGiven)),
+    'supersamples': (('--supersamples',), _FILE),
+    'within': (('--within',), _FILE),
+    'without': (('--without',), _FILE),
+    'leave_out_groups': (('--leave-out-groups',), _FILE),
+    'metadata': (('-m', '--metadata'), _CONST),
+    'summary_only': (('--summary-only',), _CONST),
+    'device': (('--device',), dict(type=str, default='0')),
+}
+# what the commands after `search` say of their query sources
+_SOURCE_HELP = dict(query_id='the query is the sample already in the index with this sample id',
+                    query_ids='comma-separated sample ids already in the index',
+                    sample='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)',
+                    sample_seed='the seed of --sample (default 0)',
+                    all_items='every sample of the index is a query',
+                    intropolis='every sample of this (gzipped) intropolis file is a query',
+                    format='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+_DEVICE_HELP = 'HIP device ordinal'
+_SUMMARY_HELP = 'print only the table over all queries'
+_COMPARED_HELP = 'the number of nearest neighbor results compared (at most 256)'
+_UNSHARDED_HELP = 'path to junction index basename (an index without row shards)'
+_STORE_INDEX_HELP = 'basename of an index built with --junction-store (an index without row shards)'
+
+
+def _add_flags(subparser, **helps):
+    """The shared flags named, by dest and in this order, each with the help text this command gives it."""
+    for dest, text in helps.items():
+        names, rest = _SHARED[dest]
+        subparser.add_argument(*names, help=text, **rest)
+
+
+def _add_sources(subparser, *dests):
+    """The query-source flags named, with the help text of the commands after `search`."""
+    _add_flags(subparser, **dict((dest, _SOURCE_HELP[dest]) for dest in dests))
+
+
+def _add_refused(subparser, *dests):
+    """Flags of `search` that have no meaning for this command: taken, and hidden, so that they can be refused with a reason."""
+    for dest in dests:
+        names, rest = _SHARED[dest]
+        if rest is _CONST:
+            subparser.add_argument(*names, help=argparse.SUPPRESS, **_CONST)
+        else:
+            subparser.add_argument(*names, type=str, required=False, default=None, help=argparse.SUPPRESS)
+
+
+def _add_junction_file(subparser, text='path to the (gzipped) intropolis file the index was made from', required=True, **rest):
+    subparser.add_argument('--junction-file', type=str, metavar='<gz>', required=required, help=text, **rest)
+
+
+def _add_results(subparser, text, given=True):
+    """-r; given: note in results_given that it was on the command line."""
+    subparser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20, help=text,
+                           **(dict(action=_StoreGiven) if given else {}))
+
+
 def add_search_parameters(subparser):
-    subparser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                           help='path to junction index basename for search')
-    subparser.add_argument('-v', '--verbose', action='store_const', const=True, default=False, help='be talkative')
-    subparser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
-                           help='a larger value makes for more accurate search')
-    subparser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
-                           help='one of {sam, bed, raw}')
+    _add_flags(subparser, basename='path to junction index basename for search', verbose='be talkative',
+               search_k='a larger value makes for more accurate search', format='one of {sam, bed, raw}')
     subparser.add_argument('-d', '--distances', action='store_const', const=True, default=False,
                            help='include distances to nearest neighbors')
-    subparser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
-                           help='display results mapped to metadata')
+    _add_flags(subparser, metadata='display results mapped to metadata')
     subparser.add_argument('-c', '--convergence-backoff', metavar='<int>', type=int, required=False, default=None,
                            help='attempt to converge on a solution with this backoff interval '
                                 '(check after c, then 2c, then 4c, and stop when no change)')
     subparser.add_argument('-ch', '--checkpoint', metavar='<int>', type=int, required=False, default=0,
                            help='do not start backoff until this point (check at checkpoint, '
                                 'then checkpoint + c, then continue exponential backoff)')
-    subparser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                           help='search for nearest neighbors to the sample already in the index with this sample id')
-    subparser.add_argument('-e', '--exact', action='store_const', const=True, default=False,
-                           help='exact nearest neighbor search within the morna index')
-    subparser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20, action=_StoreGiven,
-                           help='the number of nearest neighbor results to return')
+    _add_flags(subparser, query_id='search for nearest neighbors to the sample already in the index with this sample id',
+               exact='exact nearest neighbor search within the morna index')
+    _add_results(subparser, 'the number of nearest neighbor results to return')
     subparser.add_argument('-rl', '--rawlist', action='store_const', const=True, default=False,
                            help='regurgitate junction list for input sample instead of performing search')
-    subparser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
-                           help='search every sample of this (gzipped) intropolis file at once: one block per sample, '
-                                '"# query <sample id>" and then what -f raw prints for that sample\'s junctions '
-                                '(-f is ignored)')
-    subparser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                           help='comma-separated sample ids already in the index, searched together: one block per id, '
-                                '"# query <id>" and then what -q <id> prints')
-    subparser.add_argument('--supersamples', metavar='<file>', type=str, required=False, default=None,
-                           help='search with pooled samples: a groups file, "<label><TAB><id>,<id>,..." per line; every '
-                                'group\'s samples are summed junction by junction on the GPU (needs the store of `index '
-                                '--junction-store`) and the sums searched together: one block per group, "# query <label>" '
-                                'and then what --intropolis prints for a sample with those sums (`search` only; needs '
-                                '--junction-file)')
-    subparser.add_argument('--unhashed', action='store_const', const=True, default=False,
-                           help='rank by the TF-IDF cosine distance over the junctions themselves, one dimension per '
-                                'line of the indexed file, instead of the hashed features (needs the store and weights '
-                                'of `index --junction-store`; `search` only)')
+    _add_flags(subparser,
+               intropolis='search every sample of this (gzipped) intropolis file at once: one block per sample, '
+                          '"# query <sample id>" and then what -f raw prints for that sample\'s junctions '
+                          '(-f is ignored)',
+               query_ids='comma-separated sample ids already in the index, searched together: one block per id, '
+                         '"# query <id>" and then what -q <id> prints',
+               supersamples='search with pooled samples: a groups file, "<label><TAB><id>,<id>,..." per line; every '
+                            'group\'s samples are summed junction by junction on the GPU (needs the store of `index '
+                            '--junction-store`) and the sums searched together: one block per group, "# query <label>" '
+                            'and then what --intropolis prints for a sample with those sums (`search` only; needs '
+                            '--junction-file)',
+               unhashed='rank by the TF-IDF cosine distance over the junctions themselves, one dimension per '
+                        'line of the indexed file, instead of the hashed features (needs the store and weights '
+                        'of `index --junction-store`; `search` only)')
     subparser.add_argument('--downsample', metavar='<p1,p2,...>', type=str, required=False, default=None,
                            help='with -q or --query-ids: search with each sample\'s row of the junction store at these '
                                 'fractions of its depth (1 to 16 rates in [0, 1]): every read of every junction is kept '
@@ -186,18 +247,15 @@ def add_search_parameters(subparser):
                                 'thinned coverages (`search` and `recovery`)')
     subparser.add_argument('--downsample-seed', metavar='<int>', type=int, required=False, default=8675309, action=_StoreGiven,
                            help='the seed of --downsample (default 8675309); the same seed gives the same reads')
-    subparser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                           help='answer only with the samples this file lists, one integer sample id per line')
-    subparser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                           help='never answer with a sample this file lists, one integer sample id per line')
-    subparser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
-                           help='with -q, --query-ids and --downsample: a groups file, "<label><TAB><id>,<id>,..." per line; '
+    _add_flags(subparser,
+               within='answer only with the samples this file lists, one integer sample id per line',
+               without='never answer with a sample this file lists, one integer sample id per line',
+               leave_out_groups='with -q, --query-ids and --downsample: a groups file, "<label><TAB><id>,<id>,..." per line; '
                                 'a query is never answered with a sample of its own group, itself included, and a query '
                                 'sample the file does not name is a group of its own.  `recovery` then asks for exactly -r '
-                                'results instead of -r + 1 with the query dropped')
-    subparser.add_argument('--device', type=str, default='0',
-                           help='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
-                                'dealt to these devices in turn')
+                                'results instead of -r + 1 with the query dropped',
+               device='HIP device ordinal; for an index built with --shards also a list, "0,1,2,3": the shards are '
+                      'dealt to these devices in turn')
 
 
 def build_parser():
@@ -221,7 +279,7 @@ def build_parser():
     index_parser.add_argument('-b', '--buffer-size', metavar='<int>', type=int, required=False, default=1024,
                               help='accepted for compatibility and ignored: the junctions-by-sample store is written '
                                    'in one piece (--junction-store)')
-    index_parser.add_argument('-v', '--verbose', action='store_const', const=True, default=False, help='be talkative')
+    _add_flags(index_parser, verbose='be talkative')
     index_parser.add_argument('-m', '--metafile', metavar='<file>', type=str, required=False, default=None,
                               help='path to metadata file with sample index in first column '
                                    'and other keywords in other columns, whitespace delimited')
@@ -242,10 +300,9 @@ def build_parser():
                                    '(a second parse of the file, every line kept, transposed on the GPU); without this '
                                    'flag a store left by an earlier index of the same basename is removed')
     add_search_parameters(search_parser)
-    search_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None, dest='unhashed_junction_file',
-                               help='with --unhashed and a query that is not already in the index (a stream, --intropolis), '
-                                    'with --supersamples, and with --downsample unless --unhashed: path to the (gzipped) intropolis file the index was made '
-                                    'from, which names the junction of every line')
+    _add_junction_file(search_parser, 'with --unhashed and a query that is not already in the index (a stream, --intropolis), '
+                       'with --supersamples, and with --downsample unless --unhashed: path to the (gzipped) intropolis file the index was made '
+                       'from, which names the junction of every line', required=False, default=None, dest='unhashed_junction_file')
     search_parser.add_argument('--use-trees', metavar='<int>', type=int, required=False, default=None,
                                help='search with the first <int> trees of the index only: the answer of an index built with '
                                     '--n-trees <int> from the same file (approximate search on an index without row shards; '
@@ -267,8 +324,7 @@ def build_parser():
                                   help='two parts separated by a comma: retain the junctions found in at least {first part} '
                                        'proportion of the result samples, or with at least {second part} coverage in any '
                                        'one result sample')
-    junctions_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
-                                  help='path to the (gzipped) intropolis file the index was made from')
+    _add_junction_file(junctions_parser)
     junctions_parser.add_argument('-sf', '--splicefile', type=str, metavar='<file>', required=True,
                                   help='intropolis-like output file with the retained junctions and, as one more field, '
                                        'the ranks of the results that hold each; a batch (--intropolis, --query-ids) '
@@ -286,11 +342,9 @@ def build_parser():
     recovery_parser.add_argument('--truth', type=str, metavar='<gz>', required=False, default=None,
                                  help='with --intropolis: the (gzipped) intropolis file that holds the true junctions of the '
                                       'same sample ids (the samples sequenced deeply)')
-    recovery_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=False, default=None,
-                                 help='with --truth and with --downsample: path to the (gzipped) intropolis file the index was made from, which '
-                                      'names the junction of every line')
-    recovery_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                                 help='print only the table over all queries')
+    _add_junction_file(recovery_parser, 'with --truth and with --downsample: path to the (gzipped) intropolis file the index was made from, which '
+                       'names the junction of every line', required=False, default=None)
+    _add_flags(recovery_parser, summary_only=_SUMMARY_HELP)
     recovery_parser.add_argument('--results-sweep', type=str, metavar='<p1,p2,...>', required=False, default=None,
                                  help='tabulate these result counts (at most 8, each at most -r) from the one search -r deep '
                                       'and one pass over its results: a block per count for every query, then a table over '
@@ -302,117 +356,55 @@ def build_parser():
                                       'junction the query kept counts as a false positive: recall is the number of interest')
     recall_parser = subparsers.add_parser('recall', help='tabulates the recall of the approximate search against the exact one '
                                                          'over a grid of tree counts and search_k values, from one index')
-    recall_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                               help='path to junction index basename (an index without row shards)')
-    recall_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                               help='the query is the sample already in the index with this sample id')
-    recall_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                               help='comma-separated sample ids already in the index')
-    recall_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
-                               help='every sample of this (gzipped) intropolis file is a query')
-    recall_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
-                               help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
-    recall_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
-                               help='the seed of --sample (default 0)')
-    recall_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20,
-                               help='the number of nearest neighbor results compared (at most 256)')
+    _add_flags(recall_parser, basename=_UNSHARDED_HELP)
+    _add_sources(recall_parser, 'query_id', 'query_ids', 'intropolis', 'sample', 'sample_seed')
+    _add_results(recall_parser, _COMPARED_HELP, given=False)
     recall_parser.add_argument('--trees', metavar='<t1,t2,...>', type=str, required=True,
                                help='tree counts, ascending, at most 64; "all" stands for the index\'s tree count')
     recall_parser.add_argument('--search-ks', metavar='<s1,s2,...>', type=str, required=True,
                                help='search_k values, ascending, at most 64')
-    recall_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                               help='print only the table over all queries')
-    recall_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    _add_flags(recall_parser, summary_only=_SUMMARY_HELP, device=_DEVICE_HELP)
     hashing_parser = subparsers.add_parser('hashing', help='tabulates what each --features value costs in neighbours and in norm '
                                                            'distortion against the unhashed search, from one index with a '
                                                            'junction store')
-    hashing_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                                help='basename of an index built with --junction-store (an index without row shards)')
-    hashing_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
-                                help='path to the (gzipped) intropolis file the index was made from')
-    hashing_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                                help='the query is the sample already in the index with this sample id')
-    hashing_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                                help='comma-separated sample ids already in the index')
-    hashing_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
-                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
-    hashing_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
-                                help='the seed of --sample (default 0)')
-    hashing_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20,
-                                help='the number of nearest neighbor results compared (at most 256)')
+    _add_flags(hashing_parser, basename=_STORE_INDEX_HELP)
+    _add_junction_file(hashing_parser)
+    _add_sources(hashing_parser, 'query_id', 'query_ids', 'sample', 'sample_seed')
+    _add_results(hashing_parser, _COMPARED_HELP, given=False)
     hashing_parser.add_argument('--features', metavar='<d1,d2,...>', type=str, required=True,
                                 help='hashed widths, ascending, at most 16, each 1 to 32768; "index" stands for the index\'s own')
     hashing_parser.add_argument('--n-trees', metavar='<int>', type=int, required=False, default=None,
                                 help='also build a forest of this many trees at every width and search it')
-    hashing_parser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
-                                help='search_k of the forest search (with --n-trees; default 100)')
-    hashing_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                                help='print only the table over all queries')
-    hashing_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
-    # flags of `search` that have no meaning here: taken so that they can be refused with a reason
-    hashing_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    hashing_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    for flag in ('--within', '--without', '--leave-out-groups', '--intropolis'):
-        hashing_parser.add_argument(flag, type=str, required=False, default=None, help=argparse.SUPPRESS)
+    _add_flags(hashing_parser, search_k='search_k of the forest search (with --n-trees; default 100)', summary_only=_SUMMARY_HELP,
+               device=_DEVICE_HELP)
+    _add_refused(hashing_parser, 'exact', 'unhashed', 'within', 'without', 'leave_out_groups', 'intropolis')
     labels_parser = subparsers.add_parser('labels', help='tabulates, for every query, its mean distance to the samples of every '
                                                          'label of a sample -> label table, and how well the labels hold '
                                                          'together in the hashed space, from one scan of the index')
-    labels_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                               help='path to junction index basename (an index without row shards)')
+    _add_flags(labels_parser, basename=_UNSHARDED_HELP)
     labels_parser.add_argument('--labels', metavar='<file>', type=str, required=True,
                                help='a groups file, "<label><TAB><id>,<id>,..." per line: the samples of every label (a tissue, '
                                     'a cell type), at most 4096 labels; a sample it does not name has none')
-    labels_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                               help='the query is the sample already in the index with this sample id')
-    labels_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                               help='comma-separated sample ids already in the index')
-    labels_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
-                               help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
-    labels_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
-                               help='the seed of --sample (default 0)')
-    labels_parser.add_argument('--all', action='store_const', const=True, default=False, dest='all_items',
-                               help='every sample of the index is a query')
-    labels_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
-                               help='every sample of this (gzipped) intropolis file is a query')
-    labels_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
-                               help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+    _add_sources(labels_parser, 'query_id', 'query_ids', 'sample', 'sample_seed', 'all_items', 'intropolis', 'format')
     labels_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=3,
                                help='the nearest labels printed per query (default 3)')
     labels_parser.add_argument('--matrix', action='store_const', const=True, default=False,
                                help='append the label map: for every pair of labels (A, B) the mean distance from the queries '
                                     'of label A to the samples of label B (queries that are samples of the index only)')
-    labels_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                               help='print only the table over all queries')
-    labels_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                               help='count only the samples this file lists, one integer sample id per line')
-    labels_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                               help='never count a sample this file lists, one integer sample id per line')
-    labels_parser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
-                               help='a groups file: a query never counts a sample of its own group -- its donor, its study -- '
-                                    '(queries that are samples of the index only)')
-    labels_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    _add_flags(labels_parser, summary_only=_SUMMARY_HELP,
+               within='count only the samples this file lists, one integer sample id per line',
+               without='never count a sample this file lists, one integer sample id per line',
+               leave_out_groups='a groups file: a query never counts a sample of its own group -- its donor, its study -- '
+                                '(queries that are samples of the index only)',
+               device=_DEVICE_HELP)
     mixture_parser = subparsers.add_parser('mixture', help='writes every query as a non-negative blend of the centroids of the '
                                                            'labels of a sample -> label table and says which queries are '
                                                            'mixed: a contaminated sample shows a second label with a share')
-    mixture_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                                help='path to junction index basename (an index without row shards)')
+    _add_flags(mixture_parser, basename=_UNSHARDED_HELP)
     mixture_parser.add_argument('--labels', metavar='<file>', type=str, required=True,
                                 help='a groups file, "<label><TAB><id>,<id>,..." per line: the samples of every label (a tissue, '
                                      'a cell type), at most 128 labels; a sample it does not name has none')
-    mixture_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                                help='the query is the sample already in the index with this sample id')
-    mixture_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                                help='comma-separated sample ids already in the index')
-    mixture_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
-                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
-    mixture_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
-                                help='the seed of --sample (default 0)')
-    mixture_parser.add_argument('--all', action='store_const', const=True, default=False, dest='all_items',
-                                help='every sample of the index is a query')
-    mixture_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
-                                help='every sample of this (gzipped) intropolis file is a query')
-    mixture_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
-                                help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
+    _add_sources(mixture_parser, 'query_id', 'query_ids', 'sample', 'sample_seed', 'all_items', 'intropolis', 'format')
     mixture_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=3,
                                 help='the labels of the largest weights printed per query (default 3)')
     mixture_parser.add_argument('--min-share', metavar='<float>', type=float, required=False, default=0.1,
@@ -424,57 +416,40 @@ def build_parser():
     mixture_parser.add_argument('--matrix', action='store_const', const=True, default=False,
                                 help='append the table of mean shares: the row is the queries\' own label, the column the fitted '
                                      'label (queries that are samples of the index only)')
-    mixture_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                                help='print only the table over all queries')
-    mixture_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                                help='the centroids are made of the samples this file lists only, one integer sample id per line')
-    mixture_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                                help='no centroid holds a sample this file lists, one integer sample id per line')
-    mixture_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
-    mixture_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    mixture_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    for flag in ('--leave-out-groups', '--supersamples'):
-        mixture_parser.add_argument(flag, type=str, required=False, default=None, help=argparse.SUPPRESS)
+    _add_flags(mixture_parser, summary_only=_SUMMARY_HELP,
+               within='the centroids are made of the samples this file lists only, one integer sample id per line',
+               without='no centroid holds a sample this file lists, one integer sample id per line', device=_DEVICE_HELP)
+    _add_refused(mixture_parser, 'exact', 'unhashed', 'leave_out_groups', 'supersamples')
     super_parser = subparsers.add_parser('supersample', help='sums the coverage of every junction over groups of indexed '
                                                              'samples (create_supersample.py on the junction store)')
-    super_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                              help='basename of an index built with --junction-store')
+    _add_flags(super_parser, basename='basename of an index built with --junction-store')
     which = super_parser.add_mutually_exclusive_group(required=True)
     which.add_argument('--sample-ids', metavar='<file>', type=str, default=None,
                        help='one integer sample id per line (the --sampleids file of create_supersample.py): one output file')
     which.add_argument('--groups', metavar='<file>', type=str, default=None,
                        help='"<label><TAB><id>,<id>,..." per line: one output file per group, <out>.<label>')
-    super_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
-                              help='path to the (gzipped) intropolis file the index was made from')
+    _add_junction_file(super_parser)
     super_parser.add_argument('-o', '--output', type=str, metavar='<file>', required=True,
                               help='output file: "chrom start end sum" for every line of --junction-file')
-    super_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    _add_flags(super_parser, device=_DEVICE_HELP)
     pairs_parser = subparsers.add_parser('pairs', help='lists every pair of indexed samples within a distance of each other '
                                                        '(re-submitted runs, replicates, one library under two accessions), '
                                                        'from one exact scan of the index')
-    pairs_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                              help='path to junction index basename (an index without row shards)')
+    _add_flags(pairs_parser, basename=_UNSHARDED_HELP)
     pairs_parser.add_argument('--max-distance', metavar='<float>', type=str, required=True,
                               help='report the pairs at most this exact distance apart')
-    pairs_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                              help='pair only the samples this file lists, one integer sample id per line')
-    pairs_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                              help='never pair a sample this file lists, one integer sample id per line')
-    pairs_parser.add_argument('--leave-out-groups', metavar='<file>', type=str, required=False, default=None,
-                              help='a groups file, "<label><TAB><id>,<id>,..." per line: never pair two samples of one group '
-                                   '(the expected pairs -- one donor, one study -- stay silent, the unexpected ones remain)')
-    pairs_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
-                              help='append both samples\' metadata keywords to every line')
+    _add_flags(pairs_parser, within='pair only the samples this file lists, one integer sample id per line',
+               without='never pair a sample this file lists, one integer sample id per line',
+               leave_out_groups='a groups file, "<label><TAB><id>,<id>,..." per line: never pair two samples of one group '
+                                '(the expected pairs -- one donor, one study -- stay silent, the unexpected ones remain)',
+               metadata='append both samples\' metadata keywords to every line')
     pairs_parser.add_argument('--clusters', action='store_const', const=True, default=False,
                               help='append one line per connected component of the pairs, largest first')
-    pairs_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                              help='print only the summary line (and the clusters with --clusters)')
-    pairs_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    _add_flags(pairs_parser, summary_only='print only the summary line (and the clusters with --clusters)', device=_DEVICE_HELP)
     cluster_parser = subparsers.add_parser('cluster', help='partitions the indexed samples into k groups by their distance in the '
                                                            'hashed space (spherical k-means on the GPU) and writes the groups '
                                                            'file that labels, --leave-out-groups and --supersamples read')
-    cluster_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                                help='path to junction index basename (an index without row shards)')
+    _add_flags(cluster_parser, basename=_UNSHARDED_HELP)
     cluster_parser.add_argument('-k', '--clusters', metavar='<int>', type=int, required=False, default=None,
                                 help='the number of groups, 1 to 4096 (with --init-ids: their number)')
     cluster_parser.add_argument('--seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
@@ -483,144 +458,214 @@ def build_parser():
                                 help='the first centroids are the samples this file lists, one integer sample id per line')
     cluster_parser.add_argument('--max-iterations', metavar='<int>', type=int, required=False, default=100,
                                 help='stop after this many assignments when the groups still change (default 100)')
-    cluster_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                                help='partition only the samples this file lists, one integer sample id per line')
-    cluster_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                                help='leave out the samples this file lists, one integer sample id per line')
+    _add_flags(cluster_parser, within='partition only the samples this file lists, one integer sample id per line',
+               without='leave out the samples this file lists, one integer sample id per line')
     cluster_parser.add_argument('-o', '--output', metavar='<file>', type=str, required=False, default=None,
                                 help='write the groups file here: "<label><TAB><id>,<id>,..." per group')
-    cluster_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                                help='print only the header and the line of every group')
-    cluster_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
-                                help='append the metadata keywords of every group\'s centre sample')
-    cluster_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
-    cluster_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    cluster_parser.add_argument('--unhashed', action='store_const', const=True, default=False, help=argparse.SUPPRESS)
-    cluster_parser.add_argument('--leave-out-groups', type=str, required=False, default=None, help=argparse.SUPPRESS)
+    _add_flags(cluster_parser, summary_only='print only the header and the line of every group',
+               metadata='append the metadata keywords of every group\'s centre sample', device=_DEVICE_HELP)
+    _add_refused(cluster_parser, 'exact', 'unhashed', 'leave_out_groups')
     explain_parser = subparsers.add_parser('explain', help='searches a morna index and prints, for every query and result, the '
                                                            'junctions behind their distance: how many they share, how much of '
                                                            'either sample lies outside those, and the junctions that carry most')
-    explain_parser.add_argument('-x', '--basename', metavar='<idx>', type=str, required=True,
-                                help='basename of an index built with --junction-store (an index without row shards)')
-    explain_parser.add_argument('--junction-file', type=str, metavar='<gz>', required=True,
-                                help='path to the (gzipped) intropolis file the index was made from: it names the junctions')
-    explain_parser.add_argument('-q', '--query-id', metavar='<int>', type=int, required=False, default=None,
-                                help='the query is the sample already in the index with this sample id')
-    explain_parser.add_argument('--query-ids', metavar='<ids>', type=str, required=False, default=None,
-                                help='comma-separated sample ids already in the index')
-    explain_parser.add_argument('--sample', metavar='<int>', type=int, required=False, default=None,
-                                help='this many distinct indexed samples, drawn with numpy.random.RandomState(--sample-seed)')
-    explain_parser.add_argument('--sample-seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
-                                help='the seed of --sample (default 0)')
-    explain_parser.add_argument('--intropolis', metavar='<file>', type=str, required=False, default=None,
-                                help='every sample of this (gzipped) intropolis file is a query')
-    explain_parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default='sam',
-                                help='one of {sam, bed, raw}: the format of a query read from stdin, when no other query is named')
-    explain_parser.add_argument('-r', '--results', metavar='<int>', type=int, required=False, default=20, action=_StoreGiven,
-                                help='the number of nearest neighbor results to search for and explain (default 20)')
-    explain_parser.add_argument('-e', '--exact', action='store_const', const=True, default=False,
-                                help='search exactly, as `search -e` does')
-    explain_parser.add_argument('--unhashed', action='store_const', const=True, default=False,
-                                help='search in the space of the junctions themselves, as `search --unhashed` does')
-    explain_parser.add_argument('--search-k', metavar='<int>', type=int, required=False, default=100, action=_StoreGiven,
-                                help='a larger value makes for more accurate search')
+    _add_flags(explain_parser, basename=_STORE_INDEX_HELP)
+    _add_junction_file(explain_parser, 'path to the (gzipped) intropolis file the index was made from: it names the junctions')
+    _add_sources(explain_parser, 'query_id', 'query_ids', 'sample', 'sample_seed', 'intropolis', 'format')
+    _add_results(explain_parser, 'the number of nearest neighbor results to search for and explain (default 20)')
+    _add_flags(explain_parser, exact='search exactly, as `search -e` does',
+               unhashed='search in the space of the junctions themselves, as `search --unhashed` does',
+               search_k='a larger value makes for more accurate search')
     explain_parser.add_argument('--against', metavar='<ids>', type=str, required=False, default=None,
                                 help='comma-separated sample ids of the index: no search runs, every query is explained against '
                                      'every one of them, in this order (the follow-up to a line of `morna pairs`)')
     explain_parser.add_argument('--top', metavar='<int>', type=int, required=False, default=10,
                                 help='the junctions of largest contribution printed per pair, 1 to 64 (default 10)')
-    explain_parser.add_argument('--within', metavar='<file>', type=str, required=False, default=None,
-                                help='answer only with the samples this file lists, one integer sample id per line')
-    explain_parser.add_argument('--without', metavar='<file>', type=str, required=False, default=None,
-                                help='never answer with a sample this file lists, one integer sample id per line')
-    explain_parser.add_argument('--summary-only', action='store_const', const=True, default=False,
-                                help='print only the line of every pair, not the junctions under it')
-    explain_parser.add_argument('-m', '--metadata', action='store_const', const=True, default=False,
-                                help='append the metadata keywords of every result, as `search -m` does')
-    explain_parser.add_argument('--device', type=str, default='0', help='HIP device ordinal')
+    _add_flags(explain_parser, within='answer only with the samples this file lists, one integer sample id per line',
+               without='never answer with a sample this file lists, one integer sample id per line',
+               summary_only='print only the line of every pair, not the junctions under it',
+               metadata='append the metadata keywords of every result, as `search -m` does', device=_DEVICE_HELP)
     return parser
 
 
-def _check_max_distance_flags(parser, args):
-    """search --max-distance: the exact, hashed search of an index without row shards; leaves the distance in
-    args.max_distance (None without the flag)."""
-    if getattr(args, "max_distance", None) is None:
-        return
-    import os
-    from .search import RADIUS_SHARDS_REFUSAL, parse_max_distance
-    try:
-        args.max_distance = parse_max_distance(args.max_distance)
-    except ValueError as e:
-        parser.error(str(e))
-    if not args.exact:
-        parser.error("--max-distance cannot be used without -e/--exact: the distance is the exact search's")
-    for flag, on in (("--unhashed", args.unhashed), ("--use-trees", getattr(args, "use_trees", None) is not None),
-                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
+# ---- the pieces the flag checks share: argparse errors, before any index is read -----------------------------------------------
+_SOURCE_FLAGS = dict(query_id="-q/--query-id", query_ids="--query-ids", sample="--sample", all_items="--all", intropolis="--intropolis")
+_ONE_PROCESS_REFUSAL = ("batch search is not available with one process per shard (torchrun): "
+                        "run it in one process, which loads every shard of the index")
+
+
+def _refuse(parser, template, flags):
+    """template % flag is the parser's error for the first of `flags`, (flag, on) or (flag, on, reason), that is on; the
+    reason follows a colon."""
+    for flag, on, *why in flags:
         if on:
-            parser.error("--max-distance cannot be used with %s" % flag)
-    if args.results < 1:
-        parser.error("-r takes a positive number of results (got %d)" % args.results)
-    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        parser.error(RADIUS_SHARDS_REFUSAL)
+            parser.error(template % flag + "".join(": " + reason for reason in why))
 
 
-def _check_pairs_flags(parser, args):
-    """`pairs`: the distance and the restriction's files, checked against each other; argparse errors, before any index is
-    read.  Leaves the restriction's parts where _check_restriction_flags leaves them."""
-    from .junctions import parse_groups_file, parse_sample_ids_file
+def _given(args, dest):
+    """The flag of a _StoreGiven action was on the command line."""
+    return getattr(args, dest + "_given", False)
+
+
+def _stream_flags(args):
+    """-c and -rl as _refuse takes them: what only the search of one stream does."""
+    return [("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)]
+
+
+def _parse_ids(parser, text, flag="--query-ids"):
+    """The ids of --query-ids (or --against); "--query-ids takes comma-separated integer sample ids (got ...)" otherwise."""
+    try:
+        return [int(t) for t in text.split(',')]
+    except ValueError:
+        parser.error("%s takes comma-separated integer sample ids (got %r)" % (flag, text))
+
+
+def _parse_distance(parser, text):
     from .search import parse_max_distance
     try:
-        args.max_distance = parse_max_distance(args.max_distance)
+        return parse_max_distance(text)
     except ValueError as e:
         parser.error(str(e))
+
+
+def _check_sample(parser, args):
+    """--sample is a positive count, --sample-seed comes only with it."""
+    if args.sample is None and _given(args, "sample_seed"):
+        parser.error("--sample-seed cannot be used without --sample")
+    if args.sample is not None and args.sample < 1:
+        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
+
+
+def _check_sources(parser, args, command, dests, stream):
+    """The query sources of a command after `search`: one of the flags `dests` -- exactly one, or with `stream` at most one
+    and -f for the query on stdin -- in the command's wording, then --query-ids parsed and --sample checked.  Returns the
+    flags given."""
+    given = [_SOURCE_FLAGS[dest] for dest in dests if getattr(args, dest) is not None and getattr(args, dest) is not False]
+    short = [_SOURCE_FLAGS[dest].split("/")[0] for dest in dests] + (["a stream on stdin"] if stream else [])
+    listed = ", ".join(short[:-1]) + " or " + short[-1]
+    if stream and len(given) > 1:
+        parser.error("%s takes one query source: %s (got %s)" % (command, listed, " and ".join(given)))
+    if not stream and len(given) != 1:
+        parser.error("%s needs exactly one query source: %s" % (command, listed) + (" (got %s)" % " and ".join(given) if given else ""))
+    if stream and args.format not in ("sam", "bed", "raw"):
+        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
+    if args.query_ids is not None:
+        args.query_ids = _parse_ids(parser, args.query_ids)
+    _check_sample(parser, args)
+    return given
+
+
+def _read_file(parser, parse, path):
+    """parse(path), None without a path; what it raises is the parser's error."""
+    if path is None:
+        return None
+    try:
+        return parse(path)
+    except (ValueError, IOError, OSError) as e:
+        parser.error(str(e))
+
+
+def _read_restriction(parser, args, groups=True):
+    """The files of --within / --without / --leave-out-groups (groups=False: a command that takes no groups file) read into
+    args.within_ids / args.without_ids / args.leave_out, None where the flag is absent, and args.restriction = None for the
+    command to fill in."""
+    from .junctions import parse_groups_file, parse_sample_ids_file
     args.within_ids = args.without_ids = args.leave_out = args.restriction = None
-    args.query_id = args.query_ids = None
     try:
         if args.within is not None:
             args.within_ids = parse_sample_ids_file(args.within)
         if args.without is not None:
             args.without_ids = parse_sample_ids_file(args.without)
-        if args.leave_out_groups is not None:
+        if groups and args.leave_out_groups is not None:
             args.leave_out = parse_groups_file(args.leave_out_groups)
     except (ValueError, IOError, OSError) as e:
         parser.error(str(e))
+
+
+def _check_within_without(parser, args):
     if args.within_ids is not None and args.without_ids is not None:
         both = sorted(set(args.within_ids) & set(args.without_ids))
         if both:
             parser.error("--within and --without both name sample id %d" % both[0])
 
 
-def _check_cluster_flags(parser, args):
-    """`cluster`: the flags of the searches that make no sense here, k or the first centroids, the restriction's files; argparse
-    errors, before any index is read.  Leaves the restriction's parts where _check_restriction_flags leaves them and the first
-    centroids in args.init_sample_ids."""
+def _shards(args):
+    """(the index is one of row shards, WORLD_SIZE): what every shard refusal and main's tail ask."""
     import os
+    return os.path.exists(args.basename + ".shards.mor"), int(os.environ.get("WORLD_SIZE", "1"))
+
+
+def _refuse_shards(parser, args, refusal):
+    """A command that runs in one process on an index without row shards and says so in the parser."""
+    on_shards, world = _shards(args)
+    if on_shards or world > 1:
+        parser.error(refusal)
+
+
+def _require_store(args, weights=False, parser=None):
+    """The junction store next to the index and, with `weights`, the line weights of the unhashed search: the parser's error
+    with a parser, IOError without."""
+    import os
+    from .junctions import STORE_SUFFIX, WEIGHTS_SUFFIX
+
+    def missing(text):
+        if parser is not None:
+            parser.error(text)
+        raise IOError(text)
+    if not os.path.exists(args.basename + STORE_SUFFIX):
+        missing("%s not found: this index has no junction store; build it with `morna index --junction-store`"
+                % (args.basename + STORE_SUFFIX))
+    if weights and not os.path.exists(args.basename + WEIGHTS_SUFFIX):
+        missing("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
+                "to the junction store. They are not written when a junction repeats in the indexed file: "
+                "the unhashed search is defined for files without repeated junctions" % (args.basename + WEIGHTS_SUFFIX))
+
+
+# ---- the flag checks of the commands, in the order main() runs them ---------------------------------------------------------------
+def _check_max_distance_flags(parser, args):
+    """search --max-distance: the exact, hashed search of an index without row shards; leaves the distance in
+    args.max_distance (None without the flag)."""
+    if getattr(args, "max_distance", None) is None:
+        return
+    from .search import RADIUS_SHARDS_REFUSAL
+    args.max_distance = _parse_distance(parser, args.max_distance)
+    if not args.exact:
+        parser.error("--max-distance cannot be used without -e/--exact: the distance is the exact search's")
+    _refuse(parser, "--max-distance cannot be used with %s",
+            [("--unhashed", args.unhashed), ("--use-trees", _use_trees(args) is not None)] + _stream_flags(args))
+    if args.results < 1:
+        parser.error("-r takes a positive number of results (got %d)" % args.results)
+    _refuse_shards(parser, args, RADIUS_SHARDS_REFUSAL)
+
+
+def _check_pairs_flags(parser, args):
+    """`pairs`: the distance and the restriction's files, checked against each other.  Leaves the restriction's parts
+    where _check_restriction_flags leaves them."""
+    args.max_distance = _parse_distance(parser, args.max_distance)
+    args.query_id = args.query_ids = None
+    _read_restriction(parser, args)
+    _check_within_without(parser, args)
+
+
+def _check_cluster_flags(parser, args):
+    """`cluster`: the flags of the searches that make no sense here, k or the first centroids, the restriction's files.
+    Leaves the restriction's parts where _check_restriction_flags leaves them and the first centroids in
+    args.init_sample_ids."""
     from .junctions import parse_sample_ids_file
     from .search import CLUSTER_SHARDS_REFUSAL, LABELS_MAX
-    refused = (("-e/--exact", args.exact, "every distance of a partition is exact already"),
-               ("--unhashed", args.unhashed, "the groups are formed in the hashed space, over the index's rows"),
-               ("--leave-out-groups", args.leave_out_groups is not None,
-                "cluster makes groups, it takes none: --within and --without choose the samples"))
-    for flag, on, why in refused:
-        if on:
-            parser.error("cluster cannot be used with %s: %s" % (flag, why))
-    if args.init_ids is not None and getattr(args, "seed_given", False):
+    _refuse(parser, "cluster cannot be used with %s",
+            (("-e/--exact", args.exact, "every distance of a partition is exact already"),
+             ("--unhashed", args.unhashed, "the groups are formed in the hashed space, over the index's rows"),
+             ("--leave-out-groups", args.leave_out_groups is not None,
+              "cluster makes groups, it takes none: --within and --without choose the samples")))
+    if args.init_ids is not None and _given(args, "seed"):
         parser.error("--seed and --init-ids cannot be used together")
     if args.init_ids is None and args.clusters is None:
         parser.error("cluster needs -k, the number of groups, or --init-ids")
     if args.max_iterations < 1:
         parser.error("--max-iterations takes a positive number (got %d)" % args.max_iterations)
-    args.within_ids = args.without_ids = args.leave_out = args.restriction = args.init_sample_ids = None
     args.query_id = args.query_ids = None
-    try:
-        if args.init_ids is not None:
-            args.init_sample_ids = parse_sample_ids_file(args.init_ids)
-        if args.within is not None:
-            args.within_ids = parse_sample_ids_file(args.within)
-        if args.without is not None:
-            args.without_ids = parse_sample_ids_file(args.without)
-    except (ValueError, IOError, OSError) as e:
-        parser.error(str(e))
+    args.init_sample_ids = _read_file(parser, parse_sample_ids_file, args.init_ids)
+    _read_restriction(parser, args, groups=False)
     if args.init_sample_ids is not None:
         if len(set(args.init_sample_ids)) != len(args.init_sample_ids):
             parser.error("--init-ids %s names a sample twice" % args.init_ids)
@@ -629,12 +674,8 @@ def _check_cluster_flags(parser, args):
         args.clusters = len(args.init_sample_ids)
     if not 1 <= args.clusters <= LABELS_MAX:
         parser.error("-k takes 1 to %d groups (got %d)" % (LABELS_MAX, args.clusters))
-    if args.within_ids is not None and args.without_ids is not None:
-        both = sorted(set(args.within_ids) & set(args.without_ids))
-        if both:
-            parser.error("--within and --without both name sample id %d" % both[0])
-    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        parser.error(CLUSTER_SHARDS_REFUSAL)
+    _check_within_without(parser, args)
+    _refuse_shards(parser, args, CLUSTER_SHARDS_REFUSAL)
 
 
 def _check_downsample_flags(parser, args):
@@ -642,18 +683,14 @@ def _check_downsample_flags(parser, args):
     and --downsample-seed only with it.  Leaves the rates in args.downsample_parts."""
     args.downsample_parts = None
     if args.downsample is None:
-        for flag, on in (("--lost-only", getattr(args, "lost_only", False)),
-                         ("--downsample-seed", getattr(args, "downsample_seed_given", False))):
-            if on:
-                parser.error("%s cannot be used without --downsample" % flag)
+        _refuse(parser, "%s cannot be used without --downsample",
+                (("--lost-only", getattr(args, "lost_only", False)), ("--downsample-seed", _given(args, "downsample_seed"))))
         return
     if args.subparser_name == 'junctions':
         parser.error("--downsample cannot be used with junctions")
-    for flag, on in (("--intropolis", args.intropolis is not None), ("--supersamples", args.supersamples is not None),
-                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist),
-                     ("--results-sweep", getattr(args, "results_sweep", None) is not None)):
-        if on:
-            parser.error("--downsample cannot be used with %s" % flag)
+    _refuse(parser, "--downsample cannot be used with %s",
+            [("--intropolis", args.intropolis is not None), ("--supersamples", args.supersamples is not None)] + _stream_flags(args)
+            + [("--results-sweep", getattr(args, "results_sweep", None) is not None)])
     if args.query_id is None and args.query_ids is None:
         parser.error("--downsample thins samples of the index: it needs -q or --query-ids, not a query from a stream")
     junction_file = args.junction_file if args.subparser_name == 'recovery' else args.unhashed_junction_file
@@ -668,39 +705,293 @@ def _check_downsample_flags(parser, args):
 
 def _check_restriction_flags(parser, args):
     """--within / --without / --leave-out-groups: the files read and checked against each other and against the query
-    kind; argparse errors, before any index is read.  Leaves the ids in args.within_ids / args.without_ids and the groups in
-    args.leave_out (None where the flag is absent), and args.restriction = None for main() to fill in."""
+    kind.  Leaves the ids in args.within_ids / args.without_ids and the groups in args.leave_out (None where the flag is
+    absent), and args.restriction = None for main() to fill in."""
     args.within_ids = args.without_ids = args.leave_out = args.restriction = None
     if args.within is None and args.without is None and args.leave_out_groups is None:
         return
-    from .junctions import parse_groups_file, parse_sample_ids_file
-    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
-        if on:
-            parser.error("--within, --without and --leave-out-groups cannot be used with %s" % flag)
-    try:
-        if args.within is not None:
-            args.within_ids = parse_sample_ids_file(args.within)
-        if args.without is not None:
-            args.without_ids = parse_sample_ids_file(args.without)
-        if args.leave_out_groups is not None:
-            args.leave_out = parse_groups_file(args.leave_out_groups)
-    except (ValueError, IOError, OSError) as e:
-        parser.error(str(e))
-    if args.within_ids is not None and args.without_ids is not None:
-        both = sorted(set(args.within_ids) & set(args.without_ids))
-        if both:
-            parser.error("--within and --without both name sample id %d" % both[0])
+    _refuse(parser, "--within, --without and --leave-out-groups cannot be used with %s", _stream_flags(args))
+    _read_restriction(parser, args)
+    _check_within_without(parser, args)
     if args.leave_out is not None:
-        for flag, on in (("--intropolis", args.intropolis is not None), ("--supersamples", args.supersamples is not None),
-                         ("--unhashed", args.unhashed)):
-            if on:
-                parser.error("--leave-out-groups cannot be used with %s: it takes queries that are samples of the index "
-                             "(-q, --query-ids, --downsample)" % flag)
-        if args.query_id is None and args.query_ids is None:
-            parser.error("--leave-out-groups cannot be used with a query from a stream: it takes queries that are samples of "
-                         "the index (-q, --query-ids, --downsample)")
+        why = "it takes queries that are samples of the index (-q, --query-ids, --downsample)"
+        _refuse(parser, "--leave-out-groups cannot be used with %s",
+                (("--intropolis", args.intropolis is not None, why), ("--supersamples", args.supersamples is not None, why),
+                 ("--unhashed", args.unhashed, why),
+                 ("a query from a stream", args.query_id is None and args.query_ids is None, why)))
 
 
+def _check_supersample_flags(parser, args):
+    """--supersamples: `search` only, with the file that names the lines and without another query."""
+    if args.supersamples is None:
+        return
+    if args.subparser_name != 'search':
+        parser.error("--supersamples cannot be used with %s" % args.subparser_name)
+    if args.unhashed_junction_file is None:
+        parser.error("--supersamples needs --junction-file, the intropolis file the index was made from")
+    _refuse(parser, "--supersamples cannot be used with %s",
+            [("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
+             ("--intropolis", args.intropolis is not None)] + _stream_flags(args))
+
+
+def _check_recovery_flags(parser, args):
+    """`recovery`: the grid, the flags that make no sense here, and a query that names its truth."""
+    from .junctions import parse_recovery_grid
+    try:
+        args.grid_parts = parse_recovery_grid(args.grid)
+    except ValueError as e:
+        parser.error("--grid takes <frequencies>:<coverages>, such as 0,.05,.5:1,5,50, with at most 15 coverages (%s)" % e)
+    args.sweep = None
+    if args.results_sweep is not None:
+        from .junctions import parse_results_sweep
+        try:
+            args.sweep = parse_results_sweep(args.results_sweep)
+        except ValueError as e:
+            parser.error("--results-sweep takes at most 8 comma-separated result counts, each 1 to 64, such as 5,10,20 (%s)" % e)
+        if args.sweep[-1] > args.results:
+            parser.error("--results-sweep %d is more than -r %d: the counts are prefixes of the one search -r deep"
+                         % (args.sweep[-1], args.results))
+    _refuse(parser, "%s cannot be used with recovery",
+            _stream_flags(args) + [("-m/--metadata", args.metadata), ("-d/--distances", args.distances), ("--unhashed", args.unhashed)])
+    if args.query_id is None and args.query_ids is None and args.intropolis is None:
+        parser.error("recovery needs a query whose true junctions are known: -q, --query-ids, or --intropolis with --truth")
+    if args.intropolis is not None and (args.truth is None or args.junction_file is None):
+        parser.error("recovery --intropolis needs --truth, the file with the true junctions of the same samples, and "
+                     "--junction-file, the intropolis file the index was made from")
+    if args.truth is not None and args.intropolis is None:
+        parser.error("--truth cannot be used without --intropolis")
+
+
+def _check_use_trees_flags(parser, args):
+    """search --use-trees: the approximate, unrestricted, hashed search only."""
+    if _use_trees(args) is None:
+        return
+    if args.use_trees < 1:
+        parser.error("--use-trees takes a positive tree count (got %d)" % args.use_trees)
+    _refuse(parser, "--use-trees cannot be used with %s",
+            (("-e/--exact", args.exact), ("--unhashed", args.unhashed), ("--within", args.within is not None),
+             ("--without", args.without is not None), ("--leave-out-groups", args.leave_out_groups is not None)))
+
+
+def _check_recall_flags(parser, args):
+    """`recall`: exactly one query source, the two lists (`all` is resolved once the index is read), -r within the limit."""
+    from .search import RECALL_MAX_K, parse_int_list
+    _check_sources(parser, args, "recall", ("query_id", "query_ids", "intropolis", "sample"), stream=False)
+    if not 1 <= args.results <= RECALL_MAX_K:
+        parser.error("-r %d: recall compares 1 to %d results" % (args.results, RECALL_MAX_K))
+    try:
+        parse_int_list(args.trees, "--trees", all_value=1 << 30)      # (checked again with the index's tree count)
+        args.search_k_list = parse_int_list(args.search_ks, "--search-ks")
+    except ValueError as e:
+        parser.error("--trees and --search-ks take comma-separated positive integers in ascending order, at most 64, such as "
+                     "10,20,50 (%s)" % e)
+
+
+def _check_hashing_flags(parser, args):
+    """`hashing`: the flags of `search` that make no sense here, exactly one query source, -r within the limit and the
+    --features list (`index` is resolved once the index is read)."""
+    from .search import RECALL_MAX_K, parse_features_list
+    population = "the population is the index's items at every width"
+    _refuse(parser, "hashing cannot be used with %s",
+            (("-e/--exact", args.exact, "every width is searched exactly already; --n-trees adds the forest search"),
+             ("--unhashed", args.unhashed, "the unhashed search is the truth every width is compared with"),
+             ("--within", args.within is not None, population), ("--without", args.without is not None, population),
+             ("--leave-out-groups", args.leave_out_groups is not None, population),
+             ("--intropolis", args.intropolis is not None,
+              "the queries are samples of the index, whose rows the junction store holds: name them with -q, --query-ids or "
+              "--sample")))
+    _check_sources(parser, args, "hashing", ("query_id", "query_ids", "sample"), stream=False)
+    if not 1 <= args.results <= RECALL_MAX_K:
+        parser.error("-r %d: hashing compares 1 to %d results" % (args.results, RECALL_MAX_K))
+    if args.n_trees is None and _given(args, "search_k"):
+        parser.error("--search-k cannot be used without --n-trees")
+    if args.n_trees is not None and args.n_trees < 1:
+        parser.error("--n-trees takes a positive tree count (got %d)" % args.n_trees)
+    if args.search_k < 1:
+        parser.error("--search-k takes a positive number (got %d)" % args.search_k)
+    try:
+        tokens = [t.strip() for t in args.features.split(",")]
+        if tokens.count("index") > 1:
+            raise ValueError("--features: 'index' is named twice")
+        rest = [t for t in tokens if t != "index"]
+        if len(tokens) > 16:
+            raise ValueError("--features: %d entries, at most 16 are taken" % len(tokens))
+        if rest:
+            parse_features_list(",".join(rest))           # (checked again, in place, with the index's width)
+    except ValueError as e:
+        parser.error("--features takes comma-separated widths in ascending order, at most 16, each 1 to 32768 or the word "
+                     "index, such as 500,3000,index (%s)" % e)
+
+
+def _check_labels_flags(parser, args, command='labels'):
+    """`labels` (and `mixture`, which takes the same queries and files; more labels than it takes is its own ValueError): at
+    most one named query source (none: a stream on stdin), the files read and checked against each other and
+    against the query kind.  Leaves the labels in args.label_groups and the restriction's parts where
+    _check_restriction_flags leaves them."""
+    from .junctions import parse_groups_file
+    from .search import LABELS_MAX, labels_max_refusal
+    given = _check_sources(parser, args, command, ("query_id", "query_ids", "sample", "all_items", "intropolis"), stream=True)
+    if args.top < 1:
+        parser.error("--top takes a positive number of labels (got %d)" % args.top)
+    args.external = args.intropolis is not None or not given
+    source = "--intropolis" if args.intropolis is not None else "a query from a stream"
+    if args.external and args.matrix:
+        parser.error("--matrix cannot be used with %s: the label map compares the queries' own labels, and only a sample of "
+                     "the index has one (-q, --query-ids, --sample, --all)" % source)
+    if args.external and args.leave_out_groups is not None:
+        parser.error("--leave-out-groups cannot be used with %s: it takes queries that are samples of the index "
+                     "(-q, --query-ids, --sample, --all)" % source)
+    args.label_groups = _read_file(parser, parse_groups_file, args.labels)
+    _read_restriction(parser, args)
+    if not args.label_groups:
+        parser.error("--labels %s names no label" % args.labels)
+    if command == 'labels' and len(args.label_groups) > LABELS_MAX:
+        parser.error(labels_max_refusal(len(args.label_groups)))
+    _check_within_without(parser, args)
+
+
+def _check_mixture_flags(parser, args):
+    """`mixture`: the flags of the searches that make no sense here and the numbers of the fit, then what `labels` checks."""
+    _refuse(parser, "mixture cannot be used with %s",
+            (("-e/--exact", args.exact, "the fit is made in fp64 already"),
+             ("--unhashed", args.unhashed, "the centroids are sums of the index's rows, in the hashed space"),
+             ("--leave-out-groups", args.leave_out_groups is not None,
+              "a query that is a sample of the index is left out of its own label's centroid, nothing else is"),
+             ("--supersamples", args.supersamples is not None,
+              "pool the samples with `morna supersample` and feed its file on stdin with -f raw")))
+    if not (args.min_share >= 0.0 and args.min_share <= 1.0):
+        parser.error("--min-share takes a share, 0 to 1 (got %r)" % args.min_share)
+    if not (args.tolerance >= 0.0) or args.tolerance == float("inf"):
+        parser.error("--tolerance takes a finite number >= 0 (got %r)" % args.tolerance)
+    if args.max_sweeps < 1:
+        parser.error("--max-sweeps takes a positive number of sweeps (got %d)" % args.max_sweeps)
+    _check_labels_flags(parser, args, command='mixture')
+
+
+def _check_explain_flags(parser, args):
+    """`explain`: at most one named query source (none: a stream on stdin), the numbers, what --against excludes, and the
+    files the command cannot do without.  Leaves the ids of --against in args.against_ids and the restriction's parts where
+    _check_restriction_flags leaves them."""
+    from .junctions import MAX_NEAREST
+    given = _check_sources(parser, args, "explain", ("query_id", "query_ids", "sample", "intropolis"), stream=True)
+    if args.top < 1 or args.top > 64:
+        parser.error("--top takes 1 to 64 junctions per pair (got %d)" % args.top)
+    if args.results < 1 or args.results > MAX_NEAREST:
+        parser.error("-r takes 1 to %d results (got %d)" % (MAX_NEAREST, args.results))
+    args.external = not given or args.intropolis is not None
+    args.against_ids = None
+    if args.against is not None:
+        why = "no search runs, the samples it lists are the results"
+        _refuse(parser, "--against cannot be used with %s",
+                (("-r/--results", _given(args, "results"), why), ("-e/--exact", args.exact, why), ("--unhashed", args.unhashed, why),
+                 ("--search-k", _given(args, "search_k"), why), ("--within", args.within is not None, why),
+                 ("--without", args.without is not None, why)))
+        args.against_ids = _parse_ids(parser, args.against, "--against")
+        if len(args.against_ids) > MAX_NEAREST:
+            parser.error("--against takes at most %d samples (got %d)" % (MAX_NEAREST, len(args.against_ids)))
+    if args.unhashed:
+        _refuse(parser, "--unhashed cannot be used with %s", (("-e/--exact", args.exact), ("--search-k", _given(args, "search_k"))))
+    _read_restriction(parser, args, groups=False)
+    _check_within_without(parser, args)
+    _refuse_shards(parser, args, "explain is not available on an index of row shards (.shards.mor, one process per shard, "
+                   "--device a,b): run it on an index built without --shards")
+    _require_store(args, weights=True, parser=parser)
+
+
+def _check_batch_flags(parser, args):
+    """--intropolis / --query-ids exclude each other and the single-query flags."""
+    batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
+    if not batch:
+        return
+    if len(batch) > 1:
+        parser.error("--intropolis and --query-ids cannot be used together")
+    _refuse(parser, batch[0] + " cannot be used with %s", [("-q/--query-id", args.query_id is not None)] + _stream_flags(args))
+    if args.query_ids is not None:
+        args.query_ids = _parse_ids(parser, args.query_ids)
+
+
+def _check_unhashed_flags(parser, args):
+    """--unhashed: `search` only, without the flags of the hashed searches; a query from outside the index needs the file
+    that names the lines."""
+    if not args.unhashed:
+        return
+    if args.subparser_name == 'junctions':
+        parser.error("--unhashed cannot be used with junctions")
+    _refuse(parser, "--unhashed cannot be used with %s",
+            [("-e/--exact", args.exact)] + _stream_flags(args) + [("--search-k", _given(args, "search_k"))])
+    if args.query_id is None and args.query_ids is None and args.unhashed_junction_file is None:
+        parser.error("--unhashed with a query from %s needs --junction-file, the intropolis file the index was made from"
+                     % ("--intropolis" if args.intropolis is not None else "a stream"))
+
+
+def _check_junction_flags(parser, args):
+    """`junctions`: the filter's two parts, what the result limit allows, and the flags that make no sense here."""
+    from .junctions import parse_junction_filter
+    try:
+        args.junction_filter_parts = parse_junction_filter(args.junction_filter)
+    except ValueError:
+        parser.error("--junction-filter takes <proportion>,<coverage>, such as .05,5 (got %r)" % args.junction_filter)
+    _refuse(parser, "%s cannot be used with junctions", _stream_flags(args))
+
+
+def _searching(args, stdin, stdout):
+    """`search`, `junctions` and `recovery`: the searcher of the index, over several devices or with one process per shard
+    where the index has shards, its restriction, and the command on it."""
+    import os
+    from .search import MornaSearch
+    devices = [int(d) for d in str(args.device).split(',')]
+    on_shards, world = _shards(args)
+    rank = int(os.environ.get("RANK", "0"))
+    dist = None
+    pooling = args.subparser_name in ('junctions', 'recovery')
+    sharded = world > 1 and on_shards
+    if sharded and (pooling or args.unhashed or args.supersamples is not None or args.downsample is not None
+                    or _use_trees(args) is not None):
+        raise RuntimeError(_ONE_PROCESS_REFUSAL)
+    if pooling:
+        from .junctions import MAX_RESULTS
+        if args.results > MAX_RESULTS:
+            raise ValueError("-r %d: junctions takes at most %d results (found_in is one 64-bit word per junction)"
+                             % (args.results, MAX_RESULTS))
+    if pooling or args.downsample is not None:
+        _require_store(args)
+    if sharded:
+        # torchrun with one process per shard: every rank runs this function with the same query (rank 0 reads the stream
+        # and hands it over) and calls the same collectives; rank 0 prints
+        import io
+        import torch
+        import torch.distributed as dist
+        from ._lib import device_count
+        n_dev = device_count()
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        backend = "nccl" if n_dev >= int(os.environ.get("LOCAL_WORLD_SIZE", str(world))) else "gloo"   # RCCL wants a GPU per rank
+        torch.cuda.set_device(local % n_dev)
+        dist.init_process_group(backend, rank=rank, world_size=world)
+        searcher = MornaSearch(basename=args.basename, device=local % n_dev, rank=rank, world=world)
+        if rank != 0:
+            stdout = io.StringIO()
+    else:
+        searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
+    try:
+        args.restriction = _make_restriction(args, searcher)
+        if args.supersamples is not None:
+            return _search_supersamples(args, searcher, stdout)
+        if args.downsample is not None and args.subparser_name == 'search':
+            return _search_downsample(args, searcher, stdout)
+        if args.unhashed:
+            return _search_unhashed(args, searcher, stdin, stdout)
+        if args.subparser_name == 'junctions':
+            return _junctions(args, searcher, stdin, stdout)
+        if args.subparser_name == 'recovery':
+            return _recovery(args, searcher, stdin, stdout)
+        return _search(args, searcher, stdin, stdout, dist, rank)
+    finally:
+        if dist is not None:
+            searcher.annoy_index.close()
+            dist.destroy_process_group()
+
+
+# ---- what the flags mean once an index is open ------------------------------------------------------------------------------------
 def _make_restriction(args, searcher):
     """The searcher's restriction of the three flags (None without them), its one line on stderr.  Every query sample the
     groups file does not name becomes a group of its own."""
@@ -734,458 +1025,9 @@ def _search_k(args):
     """--search-k as given; without it the command's default of 100, or under an allow-list -1: the searcher then scales
     annoy's default by the share of the index that is allowed (search.restricted_search_k)."""
     r = _restriction(args)
-    if r is not None and r.allow is not None and not getattr(args, "search_k_given", False):
+    if r is not None and r.allow is not None and not _given(args, "search_k"):
         return -1
     return args.search_k
-
-
-def _check_supersample_flags(parser, args):
-    """--supersamples: `search` only, with the file that names the lines and without another query."""
-    if args.supersamples is None:
-        return
-    if args.subparser_name != 'search':
-        parser.error("--supersamples cannot be used with %s" % args.subparser_name)
-    if args.unhashed_junction_file is None:
-        parser.error("--supersamples needs --junction-file, the intropolis file the index was made from")
-    for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
-                     ("--intropolis", args.intropolis is not None),
-                     ("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
-        if on:
-            parser.error("--supersamples cannot be used with %s" % flag)
-
-
-def _check_recovery_flags(parser, args):
-    """`recovery`: the grid, the flags that make no sense here, and a query that names its truth."""
-    from .junctions import parse_recovery_grid
-    try:
-        args.grid_parts = parse_recovery_grid(args.grid)
-    except ValueError as e:
-        parser.error("--grid takes <frequencies>:<coverages>, such as 0,.05,.5:1,5,50, with at most 15 coverages (%s)" % e)
-    args.sweep = None
-    if args.results_sweep is not None:
-        from .junctions import parse_results_sweep
-        try:
-            args.sweep = parse_results_sweep(args.results_sweep)
-        except ValueError as e:
-            parser.error("--results-sweep takes at most 8 comma-separated result counts, each 1 to 64, such as 5,10,20 (%s)" % e)
-        if args.sweep[-1] > args.results:
-            parser.error("--results-sweep %d is more than -r %d: the counts are prefixes of the one search -r deep"
-                         % (args.sweep[-1], args.results))
-    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist),
-                     ("-m/--metadata", args.metadata), ("-d/--distances", args.distances), ("--unhashed", args.unhashed)):
-        if on:
-            parser.error("%s cannot be used with recovery" % flag)
-    if args.query_id is None and args.query_ids is None and args.intropolis is None:
-        parser.error("recovery needs a query whose true junctions are known: -q, --query-ids, or --intropolis with --truth")
-    if args.intropolis is not None and (args.truth is None or args.junction_file is None):
-        parser.error("recovery --intropolis needs --truth, the file with the true junctions of the same samples, and "
-                     "--junction-file, the intropolis file the index was made from")
-    if args.truth is not None and args.intropolis is None:
-        parser.error("--truth cannot be used without --intropolis")
-
-
-def _check_use_trees_flags(parser, args):
-    """search --use-trees: the approximate, unrestricted, hashed search only."""
-    if getattr(args, "use_trees", None) is None:
-        return
-    if args.use_trees < 1:
-        parser.error("--use-trees takes a positive tree count (got %d)" % args.use_trees)
-    for flag, on in (("-e/--exact", args.exact), ("--unhashed", args.unhashed), ("--within", args.within is not None),
-                     ("--without", args.without is not None), ("--leave-out-groups", args.leave_out_groups is not None)):
-        if on:
-            parser.error("--use-trees cannot be used with %s" % flag)
-
-
-def _check_recall_flags(parser, args):
-    """`recall`: exactly one query source, the two lists (`all` is resolved once the index is read), -r within the limit."""
-    from .search import RECALL_MAX_K, parse_int_list
-    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
-                                   ("--intropolis", args.intropolis is not None), ("--sample", args.sample is not None)) if on]
-    if len(given) != 1:
-        parser.error("recall needs exactly one query source: -q, --query-ids, --intropolis or --sample"
-                     + (" (got %s)" % " and ".join(given) if given else ""))
-    if args.query_ids is not None:
-        try:
-            args.query_ids = [int(t) for t in args.query_ids.split(',')]
-        except ValueError:
-            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
-    if args.sample is None and getattr(args, "sample_seed_given", False):
-        parser.error("--sample-seed cannot be used without --sample")
-    if args.sample is not None and args.sample < 1:
-        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
-    if not 1 <= args.results <= RECALL_MAX_K:
-        parser.error("-r %d: recall compares 1 to %d results" % (args.results, RECALL_MAX_K))
-    try:
-        parse_int_list(args.trees, "--trees", all_value=1 << 30)      # (checked again with the index's tree count)
-        args.search_k_list = parse_int_list(args.search_ks, "--search-ks")
-    except ValueError as e:
-        parser.error("--trees and --search-ks take comma-separated positive integers in ascending order, at most 64, such as "
-                     "10,20,50 (%s)" % e)
-
-
-def _check_hashing_flags(parser, args):
-    """`hashing`: the flags of `search` that make no sense here, exactly one query source, -r within the limit and the
-    --features list (`index` is resolved once the index is read)."""
-    from .search import RECALL_MAX_K, parse_features_list
-    refused = (("-e/--exact", args.exact, "every width is searched exactly already; --n-trees adds the forest search"),
-               ("--unhashed", args.unhashed, "the unhashed search is the truth every width is compared with"),
-               ("--within", args.within is not None, "the population is the index's items at every width"),
-               ("--without", args.without is not None, "the population is the index's items at every width"),
-               ("--leave-out-groups", args.leave_out_groups is not None, "the population is the index's items at every width"),
-               ("--intropolis", args.intropolis is not None,
-                "the queries are samples of the index, whose rows the junction store holds: name them with -q, --query-ids or "
-                "--sample"))
-    for flag, on, why in refused:
-        if on:
-            parser.error("hashing cannot be used with %s: %s" % (flag, why))
-    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
-                                   ("--sample", args.sample is not None)) if on]
-    if len(given) != 1:
-        parser.error("hashing needs exactly one query source: -q, --query-ids or --sample"
-                     + (" (got %s)" % " and ".join(given) if given else ""))
-    if args.query_ids is not None:
-        try:
-            args.query_ids = [int(t) for t in args.query_ids.split(',')]
-        except ValueError:
-            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
-    if args.sample is None and getattr(args, "sample_seed_given", False):
-        parser.error("--sample-seed cannot be used without --sample")
-    if args.sample is not None and args.sample < 1:
-        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
-    if not 1 <= args.results <= RECALL_MAX_K:
-        parser.error("-r %d: hashing compares 1 to %d results" % (args.results, RECALL_MAX_K))
-    if args.n_trees is None and getattr(args, "search_k_given", False):
-        parser.error("--search-k cannot be used without --n-trees")
-    if args.n_trees is not None and args.n_trees < 1:
-        parser.error("--n-trees takes a positive tree count (got %d)" % args.n_trees)
-    if args.search_k < 1:
-        parser.error("--search-k takes a positive number (got %d)" % args.search_k)
-    try:
-        tokens = [t.strip() for t in args.features.split(",")]
-        if tokens.count("index") > 1:
-            raise ValueError("--features: 'index' is named twice")
-        rest = [t for t in tokens if t != "index"]
-        if len(tokens) > 16:
-            raise ValueError("--features: %d entries, at most 16 are taken" % len(tokens))
-        if rest:
-            parse_features_list(",".join(rest))           # (checked again, in place, with the index's width)
-    except ValueError as e:
-        parser.error("--features takes comma-separated widths in ascending order, at most 16, each 1 to 32768 or the word "
-                     "index, such as 500,3000,index (%s)" % e)
-
-
-def _check_labels_flags(parser, args, command='labels'):
-    """`labels` (and `mixture`, which takes the same queries and files; more labels than it takes is its own ValueError): at
-    most one named query source (none: a stream on stdin), the files read and checked against each other and
-    against the query kind; argparse errors, before any index is read.  Leaves the labels in args.label_groups and the
-    restriction's parts where _check_restriction_flags leaves them."""
-    from .junctions import parse_groups_file, parse_sample_ids_file
-    from .search import LABELS_MAX, labels_max_refusal
-    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
-                                   ("--sample", args.sample is not None), ("--all", args.all_items),
-                                   ("--intropolis", args.intropolis is not None)) if on]
-    if len(given) > 1:
-        parser.error("%s takes one query source: -q, --query-ids, --sample, --all, --intropolis or a stream on stdin "
-                     "(got %s)" % (command, " and ".join(given)))
-    if args.format not in ("sam", "bed", "raw"):
-        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
-    if args.query_ids is not None:
-        try:
-            args.query_ids = [int(t) for t in args.query_ids.split(',')]
-        except ValueError:
-            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
-    if args.sample is None and getattr(args, "sample_seed_given", False):
-        parser.error("--sample-seed cannot be used without --sample")
-    if args.sample is not None and args.sample < 1:
-        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
-    if args.top < 1:
-        parser.error("--top takes a positive number of labels (got %d)" % args.top)
-    args.external = args.intropolis is not None or not given
-    source = "--intropolis" if args.intropolis is not None else "a query from a stream"
-    if args.external and args.matrix:
-        parser.error("--matrix cannot be used with %s: the label map compares the queries' own labels, and only a sample of "
-                     "the index has one (-q, --query-ids, --sample, --all)" % source)
-    if args.external and args.leave_out_groups is not None:
-        parser.error("--leave-out-groups cannot be used with %s: it takes queries that are samples of the index "
-                     "(-q, --query-ids, --sample, --all)" % source)
-    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
-    try:
-        args.label_groups = parse_groups_file(args.labels)
-        if args.within is not None:
-            args.within_ids = parse_sample_ids_file(args.within)
-        if args.without is not None:
-            args.without_ids = parse_sample_ids_file(args.without)
-        if args.leave_out_groups is not None:
-            args.leave_out = parse_groups_file(args.leave_out_groups)
-    except (ValueError, IOError, OSError) as e:
-        parser.error(str(e))
-    if not args.label_groups:
-        parser.error("--labels %s names no label" % args.labels)
-    if command == 'labels' and len(args.label_groups) > LABELS_MAX:
-        parser.error(labels_max_refusal(len(args.label_groups)))
-    if args.within_ids is not None and args.without_ids is not None:
-        both = sorted(set(args.within_ids) & set(args.without_ids))
-        if both:
-            parser.error("--within and --without both name sample id %d" % both[0])
-
-
-def _check_mixture_flags(parser, args):
-    """`mixture`: the flags of the searches that make no sense here and the numbers of the fit, then what `labels` checks;
-    argparse errors, before any index is read."""
-    refused = (("-e/--exact", args.exact, "the fit is made in fp64 already"),
-               ("--unhashed", args.unhashed, "the centroids are sums of the index's rows, in the hashed space"),
-               ("--leave-out-groups", args.leave_out_groups is not None,
-                "a query that is a sample of the index is left out of its own label's centroid, nothing else is"),
-               ("--supersamples", args.supersamples is not None,
-                "pool the samples with `morna supersample` and feed its file on stdin with -f raw"))
-    for flag, on, why in refused:
-        if on:
-            parser.error("mixture cannot be used with %s: %s" % (flag, why))
-    if not (args.min_share >= 0.0 and args.min_share <= 1.0):
-        parser.error("--min-share takes a share, 0 to 1 (got %r)" % args.min_share)
-    if not (args.tolerance >= 0.0) or args.tolerance == float("inf"):
-        parser.error("--tolerance takes a finite number >= 0 (got %r)" % args.tolerance)
-    if args.max_sweeps < 1:
-        parser.error("--max-sweeps takes a positive number of sweeps (got %d)" % args.max_sweeps)
-    _check_labels_flags(parser, args, command='mixture')
-
-
-def _check_explain_flags(parser, args):
-    """`explain`: at most one named query source (none: a stream on stdin), the numbers, what --against excludes, and the
-    files the command cannot do without; argparse errors, before any index is read.  Leaves the ids of --against in
-    args.against_ids and the restriction's parts where _check_restriction_flags leaves them."""
-    import os
-    from .junctions import MAX_NEAREST, STORE_SUFFIX, WEIGHTS_SUFFIX, parse_sample_ids_file
-    given = [flag for flag, on in (("-q/--query-id", args.query_id is not None), ("--query-ids", args.query_ids is not None),
-                                   ("--sample", args.sample is not None), ("--intropolis", args.intropolis is not None)) if on]
-    if len(given) > 1:
-        parser.error("explain takes one query source: -q, --query-ids, --sample, --intropolis or a stream on stdin "
-                     "(got %s)" % " and ".join(given))
-    if args.format not in ("sam", "bed", "raw"):
-        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
-    if args.query_ids is not None:
-        try:
-            args.query_ids = [int(t) for t in args.query_ids.split(',')]
-        except ValueError:
-            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
-    if args.sample is None and getattr(args, "sample_seed_given", False):
-        parser.error("--sample-seed cannot be used without --sample")
-    if args.sample is not None and args.sample < 1:
-        parser.error("--sample takes a positive number of samples (got %d)" % args.sample)
-    if args.top < 1 or args.top > 64:
-        parser.error("--top takes 1 to 64 junctions per pair (got %d)" % args.top)
-    if args.results < 1 or args.results > MAX_NEAREST:
-        parser.error("-r takes 1 to %d results (got %d)" % (MAX_NEAREST, args.results))
-    args.external = not given or args.intropolis is not None
-    args.against_ids = None
-    if args.against is not None:
-        for flag, on in (("-r/--results", getattr(args, "results_given", False)), ("-e/--exact", args.exact),
-                         ("--unhashed", args.unhashed), ("--search-k", getattr(args, "search_k_given", False)),
-                         ("--within", args.within is not None), ("--without", args.without is not None)):
-            if on:
-                parser.error("--against cannot be used with %s: no search runs, the samples it lists are the results" % flag)
-        try:
-            args.against_ids = [int(t) for t in args.against.split(',')]
-        except ValueError:
-            parser.error("--against takes comma-separated integer sample ids (got %r)" % args.against)
-        if len(args.against_ids) > MAX_NEAREST:
-            parser.error("--against takes at most %d samples (got %d)" % (MAX_NEAREST, len(args.against_ids)))
-    if args.unhashed:
-        for flag, on in (("-e/--exact", args.exact), ("--search-k", getattr(args, "search_k_given", False))):
-            if on:
-                parser.error("--unhashed cannot be used with %s" % flag)
-    args.within_ids = args.without_ids = args.leave_out = args.restriction = None
-    try:
-        if args.within is not None:
-            args.within_ids = parse_sample_ids_file(args.within)
-        if args.without is not None:
-            args.without_ids = parse_sample_ids_file(args.without)
-    except (ValueError, IOError, OSError) as e:
-        parser.error(str(e))
-    if args.within_ids is not None and args.without_ids is not None:
-        both = sorted(set(args.within_ids) & set(args.without_ids))
-        if both:
-            parser.error("--within and --without both name sample id %d" % both[0])
-    if os.path.exists(args.basename + ".shards.mor") or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        parser.error("explain is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
-                     "run it on an index built without --shards")
-    if not os.path.exists(args.basename + STORE_SUFFIX):
-        parser.error("%s not found: this index has no junction store; build it with `morna index --junction-store`"
-                     % (args.basename + STORE_SUFFIX))
-    if not os.path.exists(args.basename + WEIGHTS_SUFFIX):
-        parser.error("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
-                     "to the junction store. They are not written when a junction repeats in the indexed file: "
-                     "the unhashed search is defined for files without repeated junctions" % (args.basename + WEIGHTS_SUFFIX))
-
-
-def _check_batch_flags(parser, args):
-    """--intropolis / --query-ids exclude each other and the single-query flags; argparse errors, before any index is read."""
-    batch = [flag for flag, on in (("--intropolis", args.intropolis is not None), ("--query-ids", args.query_ids is not None)) if on]
-    if not batch:
-        return
-    if len(batch) > 1:
-        parser.error("--intropolis and --query-ids cannot be used together")
-    for flag, on in (("-q/--query-id", args.query_id is not None), ("-c/--convergence-backoff", args.convergence_backoff is not None),
-                     ("-rl/--rawlist", args.rawlist)):
-        if on:
-            parser.error("%s cannot be used with %s" % (batch[0], flag))
-    if args.query_ids is not None:
-        try:
-            args.query_ids = [int(t) for t in args.query_ids.split(',')]
-        except ValueError:
-            parser.error("--query-ids takes comma-separated integer sample ids (got %r)" % args.query_ids)
-
-
-def _check_unhashed_flags(parser, args):
-    """--unhashed: `search` only, without the flags of the hashed searches; a query from outside the index needs the file
-    that names the lines."""
-    if not args.unhashed:
-        return
-    if args.subparser_name == 'junctions':
-        parser.error("--unhashed cannot be used with junctions")
-    for flag, on in (("-e/--exact", args.exact), ("-c/--convergence-backoff", args.convergence_backoff is not None),
-                     ("-rl/--rawlist", args.rawlist), ("--search-k", getattr(args, "search_k_given", False))):
-        if on:
-            parser.error("--unhashed cannot be used with %s" % flag)
-    if args.query_id is None and args.query_ids is None and args.unhashed_junction_file is None:
-        parser.error("--unhashed with a query from %s needs --junction-file, the intropolis file the index was made from"
-                     % ("--intropolis" if args.intropolis is not None else "a stream"))
-
-
-def _check_junction_flags(parser, args):
-    """`junctions`: the filter's two parts, what the result limit allows, and the flags that make no sense here."""
-    from .junctions import parse_junction_filter
-    try:
-        args.junction_filter_parts = parse_junction_filter(args.junction_filter)
-    except ValueError:
-        parser.error("--junction-filter takes <proportion>,<coverage>, such as .05,5 (got %r)" % args.junction_filter)
-    for flag, on in (("-c/--convergence-backoff", args.convergence_backoff is not None), ("-rl/--rawlist", args.rawlist)):
-        if on:
-            parser.error("%s cannot be used with junctions" % flag)
-
-
-def main(argv=None, stdin=None, stdout=None):
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    if args.subparser_name in ('search', 'junctions', 'recovery'):
-        _check_downsample_flags(parser, args)
-        _check_supersample_flags(parser, args)
-    if args.subparser_name in ('search', 'junctions'):
-        _check_batch_flags(parser, args)
-        _check_unhashed_flags(parser, args)
-    if args.subparser_name == 'recovery':
-        _check_recovery_flags(parser, args)
-        _check_batch_flags(parser, args)
-    if args.subparser_name == 'junctions':
-        _check_junction_flags(parser, args)
-    if args.subparser_name in ('search', 'junctions', 'recovery'):
-        _check_restriction_flags(parser, args)
-    if args.subparser_name == 'search':
-        _check_use_trees_flags(parser, args)
-        _check_max_distance_flags(parser, args)
-    if args.subparser_name == 'pairs':
-        _check_pairs_flags(parser, args)
-    if args.subparser_name == 'recall':
-        _check_recall_flags(parser, args)
-    if args.subparser_name == 'hashing':
-        _check_hashing_flags(parser, args)
-    if args.subparser_name == 'labels':
-        _check_labels_flags(parser, args)
-    if args.subparser_name == 'cluster':
-        _check_cluster_flags(parser, args)
-    if args.subparser_name == 'mixture':
-        _check_mixture_flags(parser, args)
-    if args.subparser_name == 'explain':
-        _check_explain_flags(parser, args)
-    stdin = stdin or sys.stdin
-    stdout = stdout or sys.stdout
-    if args.subparser_name == 'index':
-        import os
-        from .index import go_index
-        rank, device = None, int(str(args.device).split(',')[0])
-        if args.shards > 1 and int(os.environ.get("WORLD_SIZE", "1")) == args.shards:   # one process per GPU
-            from ._lib import device_count
-            rank = int(os.environ.get("RANK", "0"))
-            device = int(os.environ.get("LOCAL_RANK", "0")) % device_count()   # (fewer GPUs than ranks: the ranks share them)
-        go_index(args.intropolis, args.basename, args.features, args.n_trees, args.sample_count,
-                 args.sample_threshold, args.buffer_size, args.verbose, args.metafile, device=device,
-                 native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank,
-                 junction_store=args.junction_store)
-        return 0
-    if args.subparser_name == 'supersample':
-        return _supersample(args, stdout)
-    if args.subparser_name == 'recall':
-        return _recall(args, stdout)
-    if args.subparser_name == 'hashing':
-        return _hashing(args, stdout)
-    if args.subparser_name == 'labels':
-        return _labels(args, stdin, stdout)
-    if args.subparser_name == 'mixture':
-        return _mixture(args, stdin, stdout)
-    if args.subparser_name == 'pairs':
-        return _pairs(args, stdout)
-    if args.subparser_name == 'cluster':
-        return _cluster(args, stdout)
-    if args.subparser_name == 'explain':
-        return _explain(args, stdin, stdout)
-    if args.subparser_name not in ('search', 'junctions', 'recovery'):
-        build_parser().print_help()
-        return 2
-    from .search import MornaSearch
-    devices = [int(d) for d in str(args.device).split(',')]
-    import os
-    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    dist = None
-    junctions = args.subparser_name == 'junctions'
-    sharded = world > 1 and os.path.exists(args.basename + ".shards.mor")
-    if sharded and (args.subparser_name in ('junctions', 'recovery') or args.unhashed or args.supersamples is not None
-                    or args.downsample is not None or _use_trees(args) is not None):
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if args.subparser_name in ('junctions', 'recovery'):
-        from .junctions import MAX_RESULTS, STORE_SUFFIX
-        if args.results > MAX_RESULTS:
-            raise ValueError("-r %d: junctions takes at most %d results (found_in is one 64-bit word per junction)"
-                             % (args.results, MAX_RESULTS))
-    if args.subparser_name in ('junctions', 'recovery') or args.downsample is not None:
-        from .junctions import STORE_SUFFIX
-        if not os.path.exists(args.basename + STORE_SUFFIX):
-            raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
-                          % (args.basename + STORE_SUFFIX))
-    if sharded:
-        # torchrun with one process per shard: every rank runs this function with the same query (rank 0 reads the stream
-        # and hands it over) and calls the same collectives; rank 0 prints
-        import io
-        import torch
-        import torch.distributed as dist
-        from ._lib import device_count
-        n_dev = device_count()
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        backend = "nccl" if n_dev >= int(os.environ.get("LOCAL_WORLD_SIZE", str(world))) else "gloo"   # RCCL wants a GPU per rank
-        torch.cuda.set_device(local % n_dev)
-        dist.init_process_group(backend, rank=rank, world_size=world)
-        searcher = MornaSearch(basename=args.basename, device=local % n_dev, rank=rank, world=world)
-        if rank != 0:
-            stdout = io.StringIO()
-    else:
-        searcher = MornaSearch(basename=args.basename, device=devices if len(devices) > 1 else devices[0])
-    try:
-        args.restriction = _make_restriction(args, searcher)
-        if args.supersamples is not None:
-            return _search_supersamples(args, searcher, stdout)
-        if args.downsample is not None and args.subparser_name == 'search':
-            return _search_downsample(args, searcher, stdout)
-        if args.unhashed:
-            return _search_unhashed(args, searcher, stdin, stdout)
-        if junctions:
-            return _junctions(args, searcher, stdin, stdout)
-        if args.subparser_name == 'recovery':
-            return _recovery(args, searcher, stdin, stdout)
-        return _search(args, searcher, stdin, stdout, dist, rank)
-    finally:
-        if dist is not None:
-            searcher.annoy_index.close()
-            dist.destroy_process_group()
 
 
 def _use_trees(args):
@@ -1193,18 +1035,146 @@ def _use_trees(args):
     return getattr(args, "use_trees", None)
 
 
-def _recall(args, stdout):
+def _max_distance(args):
+    """search --max-distance; None without it (and for the commands that do not take it)."""
+    return getattr(args, "max_distance", None)
+
+
+def _radius_cap(args):
+    """-r under --max-distance: a cap when it was given on the command line, None otherwise."""
+    return args.results if _given(args, "results") else None
+
+
+def _single(args):
+    """The MornaSearch of a command that runs on one device."""
+    from .search import MornaSearch
+    return MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+
+
+def _open_single(args, refusal, world=None, weights=None):
+    """_single() for a command that refuses shards once it runs: RuntimeError under WORLD_SIZE > 1 (or `world`, the
+    exception of a command that words it otherwise), ValueError(refusal) on an index of row shards; weights: the junction
+    store, and with True its weights, must be there too."""
+    on_shards, processes = _shards(args)
+    if processes > 1:
+        raise world or RuntimeError(_ONE_PROCESS_REFUSAL)
+    if on_shards:
+        raise ValueError(refusal)
+    if weights is not None:
+        _require_store(args, weights=weights)
+    return _single(args)
+
+
+def _query_sample_ids(args, searcher, check=True):
+    """-q / --query-ids / --sample / --all as sample ids; check: every one is a sample of the index (`hashing` leaves that to
+    hashing_sweep)."""
+    all_items = getattr(args, "all_items", False)
+    if all_items or getattr(args, "sample", None) is not None:
+        import numpy as np
+        n = searcher.annoy_index.get_n_items()
+        inv = searcher._inverse_map()
+        if not all_items and args.sample > n:
+            raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
+        picked = range(n) if all_items else np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
+        ids = [inv[int(i)] for i in picked]
+    else:
+        ids = args.query_ids if args.query_ids is not None else [args.query_id]
+    for query_id in ids if check else ():
+        if query_id not in searcher.internal_id_map:
+            raise ValueError("Querying sample id " + str(query_id)
+                             + " is not possible because no internal id is mapped to that "
+                             + "sample id. Likely no sample with that id was included "
+                             + "in the index.")
+    return ids
+
+
+def _stream_parser(fmt):
+    """The generator of junctions for -f sam / bed / raw."""
+    from . import streams
+    return {"sam": streams.junctions_from_sam_stream, "bed": streams.junctions_from_bed_stream,
+            "raw": streams.junctions_from_raw_stream}[fmt]
+
+
+def _hash_stream(searcher, junctions):
+    """A stream as the searcher's hashed query: the junctions the index knows, then finalize_query."""
+    for junction in junctions:
+        if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
+            searcher.update_query(junction)
+    searcher.finalize_query()
+
+
+def _stream_coverage(junctions):
+    """A stream's coverage summed per junction, as update_query sums it."""
+    coverage = {}
+    for junction in junctions:
+        key = " ".join(str(_) for _ in junction[:3])
+        coverage[key] = coverage.get(key, 0) + int(junction[3])
+    return coverage
+
+
+def _batch_search(args, searcher, batch, n_results, distances=None, **query_groups):
+    """The radius (--max-distance), exact (-e) or approximate search of a batch of hashed queries with the command's flags;
+    query_groups: the group every query carries, from the caller whose queries have one.  The radius form takes no n_trees."""
+    common = dict(include_distances=args.distances if distances is None else distances, meta_db=args.metadata,
+                  restriction=_restriction(args), **query_groups)
+    if _max_distance(args) is not None:
+        return searcher.exact_radius_nn_batch(batch, _max_distance(args), num_neighbors=_radius_cap(args), **common)
+    if args.exact:
+        return searcher.exact_search_nn_batch(batch, n_results, **common)
+    return searcher.search_nn_batch(batch, n_results, _search_k(args), n_trees=_use_trees(args), **common)
+
+
+def _unhashed_search(args, searcher, terms, n_results, distances=None):
+    """The unhashed search of a batch of queries given as term lists, with the command's flags."""
+    return searcher.unhashed_search_nn_batch(terms, n_results, include_distances=args.distances if distances is None else distances,
+                                             meta_db=args.metadata, restriction=_restriction(args))
+
+
+def _write_blocks(stdout, labels, results, header, collect=None):
+    """One block per query: header(label), then the result lines or "# error: ..."; 1 when some query failed."""
+    from .search import results_output
+    failed = False
+    for label, res in zip(labels, results):
+        header(label)
+        if isinstance(res, Exception):
+            stdout.write("# error: %s\n" % res)
+            failed = True
+        else:
+            results_output(res, stdout)
+            if collect is not None:
+                collect.append((label, res))
+    return 1 if failed else 0
+
+
+def _write_member_header(stdout, query_id, internal_id, numbered):
+    """A by-sample query's "# query" line (in a batch) and search_member_n's two lines."""
+    if numbered:
+        stdout.write("# query %d\n" % query_id)
+    stdout.write("querying by sample id " + str(query_id) + "\n")
+    stdout.write("this is internal id " + str(internal_id) + "\n")
+
+
+# ---- the commands -----------------------------------------------------------------------------------------------------------------
+def _index(args, stdin, stdout):
+    import os
+    from .index import go_index
+    rank, device = None, int(str(args.device).split(',')[0])
+    if args.shards > 1 and int(os.environ.get("WORLD_SIZE", "1")) == args.shards:   # one process per GPU
+        from ._lib import device_count
+        rank = int(os.environ.get("RANK", "0"))
+        device = int(os.environ.get("LOCAL_RANK", "0")) % device_count()   # (fewer GPUs than ranks: the ranks share them)
+    go_index(args.intropolis, args.basename, args.features, args.n_trees, args.sample_count,
+             args.sample_threshold, args.buffer_size, args.verbose, args.metafile, device=device,
+             native=not args.python_parse, cache=args.cache, shards=args.shards, rank=rank,
+             junction_store=args.junction_store)
+    return 0
+
+
+def _recall(args, stdin, stdout):
     """`recall`: one exact search and one sweep over --trees x --search-ks on the GPU; a block per query and the table over
     all of them."""
-    import os
-    import numpy as np
-    from .search import MornaSearch, TREES_SHARDS_REFUSAL, format_recall_rows, parse_int_list
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(TREES_SHARDS_REFUSAL)
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    from .search import TREES_SHARDS_REFUSAL, format_recall_rows, parse_int_list
+    searcher = _open_single(args, TREES_SHARDS_REFUSAL)
     n_trees = searcher.annoy_index.get_n_trees()
     trees = parse_int_list(args.trees, "--trees", all_value=n_trees)
     if trees[-1] > n_trees:
@@ -1213,21 +1183,7 @@ def _recall(args, stdout):
         batch = searcher.queries_from_intropolis(args.intropolis)
         labels, queries = batch.ext_ids, batch
     else:
-        if args.sample is not None:
-            inv = searcher._inverse_map()
-            n = searcher.annoy_index.get_n_items()
-            if args.sample > n:
-                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
-            picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
-            labels = [inv[int(i)] for i in picked]
-        else:
-            labels = args.query_ids if args.query_ids is not None else [args.query_id]
-        for query_id in labels:
-            if query_id not in searcher.internal_id_map:
-                raise ValueError("Querying sample id " + str(query_id)
-                                 + " is not possible because no internal id is mapped to that "
-                                 + "sample id. Likely no sample with that id was included "
-                                 + "in the index.")
+        labels = _query_sample_ids(args, searcher)
         queries = [searcher.internal_id_map[query_id] for query_id in labels]
     table = searcher.search_recall(queries, args.results, trees, args.search_k_list)
     if not args.summary_only:
@@ -1242,36 +1198,13 @@ def _recall(args, stdout):
     return 0
 
 
-def _hashing(args, stdout):
+def _hashing(args, stdin, stdout):
     """`hashing`: the unhashed neighbours of the queries once, then for every width of --features the index's items hashed
     again from the junction store and searched on the GPU; a block per query and the table over all of them."""
-    import os
-    import numpy as np
-    from .junctions import STORE_SUFFIX, WEIGHTS_SUFFIX
-    from .search import HASHING_SHARDS_REFUSAL, MornaSearch, format_hashing_rows, parse_features_list
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(HASHING_SHARDS_REFUSAL)
-    if not os.path.exists(args.basename + STORE_SUFFIX):
-        raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
-                      % (args.basename + STORE_SUFFIX))
-    if not os.path.exists(args.basename + WEIGHTS_SUFFIX):
-        raise IOError("%s not found: --unhashed needs the line weights `morna index --junction-store` writes next "
-                      "to the junction store. They are not written when a junction repeats in the indexed file: "
-                      "the unhashed search is defined for files without repeated junctions" % (args.basename + WEIGHTS_SUFFIX))
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    from .search import HASHING_SHARDS_REFUSAL, format_hashing_rows, parse_features_list
+    searcher = _open_single(args, HASHING_SHARDS_REFUSAL, weights=True)
     dims = parse_features_list(args.features, index_dim=searcher.dim)
-    if args.sample is not None:
-        inv = searcher._inverse_map()
-        n = searcher.annoy_index.get_n_items()
-        if args.sample > n:
-            raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
-        picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
-        labels = [inv[int(i)] for i in picked]
-    else:
-        labels = args.query_ids if args.query_ids is not None else [args.query_id]
+    labels = _query_sample_ids(args, searcher, check=False)
     table = searcher.hashing_sweep(labels, args.results, dims, args.junction_file, n_trees=args.n_trees,
                                    search_k=args.search_k if args.n_trees is not None else None)
     if not args.summary_only:
@@ -1286,51 +1219,25 @@ def _hashing(args, stdout):
 def _label_queries(args, searcher, stdin):
     """The queries of `labels` and `mixture` from their flags: (queries as MornaSearch.label_separation takes them, the ids
     printed for them)."""
-    import numpy as np
     if args.intropolis is not None:
         queries = searcher.queries_from_intropolis(args.intropolis)
-        ids = queries.ext_ids
-    elif args.external:                                        # a stream: one query, as `search` makes it
-        for junction in _stream_parser(args.format)(stdin):
-            if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
-                searcher.update_query(junction)
-        searcher.finalize_query()
-        queries = np.array([searcher.query_sample], dtype=np.float64)
-        ids = ["stdin"]
-    else:
-        n = searcher.annoy_index.get_n_items()
-        if args.all_items or args.sample is not None:
-            inv = searcher._inverse_map()
-            if args.sample is not None and args.sample > n:
-                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
-            picked = range(n) if args.all_items else np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
-            ids = [inv[int(i)] for i in picked]
-        else:
-            ids = args.query_ids if args.query_ids is not None else [args.query_id]
-        for query_id in ids:
-            if query_id not in searcher.internal_id_map:
-                raise ValueError("Querying sample id " + str(query_id)
-                                 + " is not possible because no internal id is mapped to that "
-                                 + "sample id. Likely no sample with that id was included "
-                                 + "in the index.")
-        queries = [searcher.internal_id_map[query_id] for query_id in ids]
-        args.query_ids = list(ids)                             # (a query the groups file does not name is a group of its own)
-    return queries, ids
+        return queries, queries.ext_ids
+    if args.external:                                          # a stream: one query, as `search` makes it
+        import numpy as np
+        _hash_stream(searcher, _stream_parser(args.format)(stdin))
+        return np.array([searcher.query_sample], dtype=np.float64), ["stdin"]
+    ids = _query_sample_ids(args, searcher)
+    args.query_ids = list(ids)                                 # (a query the groups file does not name is a group of its own)
+    return [searcher.internal_id_map[query_id] for query_id in ids], ids
 
 
 def _mixture(args, stdin, stdout):
     """`mixture`: every query fitted on the GPU as a non-negative blend of the label centroids; a block per query, the table
     over all of them and, with --matrix, the table of mean shares."""
-    import os
-    from .search import MIXTURE_LABELS_MAX, MIXTURE_SHARDS_REFUSAL, MornaSearch, format_label_rows, mixture_max_refusal
+    from .search import MIXTURE_LABELS_MAX, MIXTURE_SHARDS_REFUSAL, format_label_rows, mixture_max_refusal
     if len(args.label_groups) > MIXTURE_LABELS_MAX:
         raise ValueError(mixture_max_refusal(len(args.label_groups)))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(MIXTURE_SHARDS_REFUSAL)
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    searcher = _open_single(args, MIXTURE_SHARDS_REFUSAL)
     queries, ids = _label_queries(args, searcher, stdin)
     args.restriction = _make_restriction(args, searcher)
     table = searcher.label_mixture(queries, args.label_groups, restriction=args.restriction, tol=args.tolerance,
@@ -1353,14 +1260,8 @@ def _mixture(args, stdin, stdout):
 def _labels(args, stdin, stdout):
     """`labels`: one scan of the index on the GPU that keeps, per query and label, the sum of the distances and their number;
     a block per query, the table over all of them and, with --matrix, the label map."""
-    import os
-    from .search import LABELS_SHARDS_REFUSAL, MornaSearch, format_label_rows
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                           "run it in one process, which loads every shard of the index")
-    if os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(LABELS_SHARDS_REFUSAL)
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    from .search import LABELS_SHARDS_REFUSAL, format_label_rows
+    searcher = _open_single(args, LABELS_SHARDS_REFUSAL)
     queries, ids = _label_queries(args, searcher, stdin)
     args.restriction = _make_restriction(args, searcher)
     table = searcher.label_separation(queries, args.label_groups, restriction=args.restriction)
@@ -1388,32 +1289,22 @@ def _by_label(labels, ext_ids, found):
 def _explain_searches(args, searcher, stream, terms, query_ids, labels):
     """The searches of `explain` without --against: what `search` runs with the same flags, distances included; one result
     tuple (or exception) per query."""
-    restriction = _restriction(args)
+    if query_ids is not None and args.unhashed:
+        return searcher.unhashed_search_member_n_batch(query_ids, args.results, include_distances=True, meta_db=args.metadata,
+                                                       restriction=_restriction(args))
     if query_ids is not None:
-        if args.unhashed:
-            return searcher.unhashed_search_member_n_batch(query_ids, args.results, include_distances=True, meta_db=args.metadata,
-                                                           restriction=restriction)
         return searcher.search_member_n_batch(query_ids, args.results, _search_k(args), include_distances=True,
-                                              meta_db=args.metadata, restriction=restriction)[1]
+                                              meta_db=args.metadata, restriction=_restriction(args))[1]
     if args.unhashed:
-        return searcher.unhashed_search_nn_batch(terms, args.results, include_distances=True, meta_db=args.metadata,
-                                                 restriction=restriction)
+        return _unhashed_search(args, searcher, terms, args.results, distances=True)
     if args.intropolis is not None:
         batch = searcher.queries_from_intropolis(args.intropolis)
-        if args.exact:
-            found = searcher.exact_search_nn_batch(batch, args.results, include_distances=True, meta_db=args.metadata,
-                                                   restriction=restriction)
-        else:
-            found = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=True, meta_db=args.metadata,
-                                             restriction=restriction)
-        return _by_label(labels, batch.ext_ids, found)
-    for junction in stream:
-        if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
-            searcher.update_query(junction)
-    searcher.finalize_query()
+        return _by_label(labels, batch.ext_ids, _batch_search(args, searcher, batch, args.results, distances=True))
+    _hash_stream(searcher, stream)
     if args.exact:
-        return [searcher.exact_search_nn(args.results, include_distances=True, meta_db=args.metadata, restriction=restriction)]
-    return [searcher.search_nn(args.results, _search_k(args), include_distances=True, meta_db=args.metadata, restriction=restriction)]
+        return [searcher.exact_search_nn(args.results, include_distances=True, meta_db=args.metadata, restriction=_restriction(args))]
+    return [searcher.search_nn(args.results, _search_k(args), include_distances=True, meta_db=args.metadata,
+                               restriction=_restriction(args))]
 
 
 def _explain_against(args, searcher, stream, query_ids, labels):
@@ -1436,10 +1327,7 @@ def _explain_against(args, searcher, stream, query_ids, labels):
         found = _by_label(labels, batch.ext_ids, searcher.exact_search_nn_batch(batch, n, include_distances=True,
                                                                                 restriction=restriction))
     else:
-        for junction in stream:
-            if " ".join(str(_) for _ in junction[:3]) in searcher.sample_frequencies:
-                searcher.update_query(junction)
-        searcher.finalize_query()
+        _hash_stream(searcher, stream)
         found = [searcher.exact_search_nn(n, include_distances=True, restriction=restriction)]
     meta = lookup_meta(searcher.basename, list(args.against_ids)) if args.metadata else None
     results = []
@@ -1456,37 +1344,17 @@ def _explain(args, stdin, stdout):
     """`explain`: the search of `search` with the same flags (or the samples of --against), then every (query, result) pair
     explained in one call on the GPU; a block per query, a line per pair and under it a line per junction of its top
     list."""
-    import numpy as np
     from .junctions import (explain_rows, format_explain_rows, intropolis_query_terms, key_lines, line_names, query_terms)
-    from .search import MornaSearch
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    searcher = _single(args)
     store, w = searcher.unhashed_store()
     stream, terms, query_ids = None, None, None
     if args.intropolis is not None:
         labels, terms = intropolis_query_terms(args.intropolis, key_lines(args.junction_file, store.n_lines), w)
     elif args.external:                                        # a stream: one query, its coverages summed per junction
         stream = list(_stream_parser(args.format)(stdin))
-        coverage = {}
-        for junction in stream:
-            key = " ".join(str(_) for _ in junction[:3])
-            coverage[key] = coverage.get(key, 0) + int(junction[3])
-        labels, terms = ["stdin"], [query_terms(coverage, key_lines(args.junction_file, store.n_lines), w)]
+        labels, terms = ["stdin"], [query_terms(_stream_coverage(stream), key_lines(args.junction_file, store.n_lines), w)]
     else:
-        if args.sample is not None:
-            inv = searcher._inverse_map()
-            n = searcher.annoy_index.get_n_items()
-            if args.sample > n:
-                raise ValueError("--sample %d: the index holds %d samples" % (args.sample, n))
-            picked = np.random.RandomState(args.sample_seed).choice(n, size=args.sample, replace=False)
-            query_ids = [inv[int(i)] for i in picked]
-        else:
-            query_ids = args.query_ids if args.query_ids is not None else [args.query_id]
-        for query_id in query_ids:
-            if query_id not in searcher.internal_id_map:
-                raise ValueError("Querying sample id " + str(query_id)
-                                 + " is not possible because no internal id is mapped to that "
-                                 + "sample id. Likely no sample with that id was included "
-                                 + "in the index.")
+        query_ids = _query_sample_ids(args, searcher)
         labels = list(query_ids)
     if args.against_ids is not None:
         results = _explain_against(args, searcher, stream, query_ids, labels)
@@ -1517,16 +1385,12 @@ def _explain(args, stdin, stdout):
     return 1 if failed else 0
 
 
-def _pairs(args, stdout):
+def _pairs(args, stdin, stdout):
     """`pairs`: one radius search by item over the whole index on the GPU, every sample bounded to the ids above its own; a
     line per pair, the summary line and, with --clusters, a line per connected component."""
-    import os
     from .metadb import lookup_meta
-    from .search import (RADIUS_SHARDS_REFUSAL, MornaSearch, format_cluster_line, format_pair_line, format_pairs_summary,
-                         pair_clusters)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.path.exists(args.basename + ".shards.mor"):
-        raise ValueError(RADIUS_SHARDS_REFUSAL)
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    from .search import RADIUS_SHARDS_REFUSAL, format_cluster_line, format_pair_line, format_pairs_summary, pair_clusters
+    searcher = _open_single(args, RADIUS_SHARDS_REFUSAL, world=ValueError(RADIUS_SHARDS_REFUSAL))
     args.restriction = _make_restriction(args, searcher)
     pairs = searcher.sample_pairs(args.max_distance, restriction=args.restriction)
     clusters = pair_clusters(pairs)
@@ -1546,12 +1410,12 @@ def _pairs(args, stdout):
     return 0
 
 
-def _cluster(args, stdout):
+def _cluster(args, stdin, stdout):
     """`cluster`: spherical k-means over the index rows on the GPU; the header, a line per group, a line per sample and, with
     -o, the groups file."""
     from .metadb import lookup_meta
-    from .search import MornaSearch, write_groups_file
-    searcher = MornaSearch(basename=args.basename, device=int(str(args.device).split(',')[0]))
+    from .search import write_groups_file
+    searcher = _single(args)
     args.restriction = _make_restriction(args, searcher)
     clusters = searcher.cluster_samples(args.clusters, seed=args.seed, init_ids=args.init_sample_ids,
                                         max_iterations=args.max_iterations, restriction=args.restriction)
@@ -1568,51 +1432,9 @@ def _cluster(args, stdout):
     return 0
 
 
-def _max_distance(args):
-    """search --max-distance; None without it (and for the commands that do not take it)."""
-    return getattr(args, "max_distance", None)
-
-
-def _radius_cap(args):
-    """-r under --max-distance: a cap when it was given on the command line, None otherwise."""
-    return args.results if getattr(args, "results_given", False) else None
-
-
-def _write_blocks(stdout, labels, results, header, collect=None):
-    """One block per query: header(label), then the result lines or "# error: ..."; 1 when some query failed."""
-    from .search import results_output
-    failed = False
-    for label, res in zip(labels, results):
-        header(label)
-        if isinstance(res, Exception):
-            stdout.write("# error: %s\n" % res)
-            failed = True
-        else:
-            results_output(res, stdout)
-            if collect is not None:
-                collect.append((label, res))
-    return 1 if failed else 0
-
-
-def _stream_parser(fmt):
-    """The generator of junctions for -f sam / bed / raw."""
-    from . import streams
-    return {"sam": streams.junctions_from_sam_stream, "bed": streams.junctions_from_bed_stream,
-            "raw": streams.junctions_from_raw_stream}[fmt]
-
-
-def _write_member_header(stdout, query_id, internal_id, numbered):
-    """A by-sample query's "# query" line (in a batch) and search_member_n's two lines."""
-    if numbered:
-        stdout.write("# query %d\n" % query_id)
-    stdout.write("querying by sample id " + str(query_id) + "\n")
-    stdout.write("this is internal id " + str(internal_id) + "\n")
-
-
 def _junctions(args, searcher, stdin, stdout):
     """morna.py:1351-1353, 1486-1638: the search, printed as `search` prints it, then the junctions of every query's
     results filtered on the GPU in one call and written in one pass over --junction-file."""
-    import sys
     from .junctions import write_splice_files
     batch = args.intropolis is not None or args.query_ids is not None
     collected = []
@@ -1640,7 +1462,6 @@ def _recovery(args, searcher, stdin, stdout):
     of every (frequency, coverage) pair of the grid from it."""
     import contextlib
     import io
-    import sys
     from .junctions import format_recovery_rows, intropolis_truth, key_lines, recovery_rows, sum_recovery_rows
     if args.downsample is not None:
         return _recovery_downsample(args, searcher, stdout)
@@ -1701,13 +1522,7 @@ def _downsample_search(args, searcher, n_results, junction_file):
     """--downsample: every (query id, rate) a job, all jobs thinned in one call and searched in one batch.  Returns (jobs:
     (sample id, rate as typed) in the order (id given, rate typed), their junctions.Thinned, their results, an Exception
     instance where the reference's search would raise)."""
-    ids = args.query_ids if args.query_ids is not None else [args.query_id]
-    for query_id in ids:
-        if query_id not in searcher.internal_id_map:
-            raise ValueError("Querying sample id " + str(query_id)
-                             + " is not possible because no internal id is mapped to that "
-                             + "sample id. Likely no sample with that id was included "
-                             + "in the index.")
+    ids = _query_sample_ids(args, searcher)
     typed, keep = args.downsample_parts
     jobs = [(query_id, t) for query_id in ids for t in typed]
     thinned = searcher.thin_samples([query_id for query_id, _ in jobs], keep * len(ids), args.downsample_seed)
@@ -1719,36 +1534,15 @@ def _downsample_search(args, searcher, n_results, junction_file):
     if r is not None and r.item_group is not None:
         own = r.own_groups([searcher.internal_id_map[query_id] for query_id, _ in jobs])
     if args.unhashed:
-        results = searcher.unhashed_search_nn_batch(searcher.unhashed_terms_from_thinned(thinned), n_results,
-                                                    include_distances=args.distances, meta_db=args.metadata, restriction=r)
-    else:
-        batch = searcher.queries_from_thinned(thinned, junction_file)
-        if _max_distance(args) is not None:
-            results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
-                                                     meta_db=args.metadata, restriction=r, query_groups=own,
-                                                     num_neighbors=_radius_cap(args))
-        elif args.exact:
-            results = searcher.exact_search_nn_batch(batch, n_results, include_distances=args.distances, meta_db=args.metadata,
-                                                     restriction=r, query_groups=own)
-        else:
-            results = searcher.search_nn_batch(batch, n_results, _search_k(args), include_distances=args.distances,
-                                               meta_db=args.metadata, restriction=r, query_groups=own, n_trees=_use_trees(args))
-    return jobs, thinned, results
+        return jobs, thinned, _unhashed_search(args, searcher, searcher.unhashed_terms_from_thinned(thinned), n_results)
+    return jobs, thinned, _batch_search(args, searcher, searcher.queries_from_thinned(thinned, junction_file), n_results,
+                                        query_groups=own)
 
 
 def _search_downsample(args, searcher, stdout):
     """search --downsample: a block per (query id, rate), printed as --intropolis prints a sample's."""
-    from .search import results_output
     jobs, _, results = _downsample_search(args, searcher, args.results, args.unhashed_junction_file)
-    failed = False
-    for (query_id, rate), res in zip(jobs, results):
-        stdout.write("# query %d\tkeep %s\n" % (query_id, rate))
-        if isinstance(res, Exception):
-            stdout.write("# error: %s\n" % res)
-            failed = True
-        else:
-            results_output(res, stdout)
-    return 1 if failed else 0
+    return _write_blocks(stdout, jobs, results, lambda job: stdout.write("# query %d\tkeep %s\n" % job))
 
 
 def _recovery_downsample(args, searcher, stdout):
@@ -1756,7 +1550,6 @@ def _recovery_downsample(args, searcher, stdout):
     is searched with the thinned row, leave one out; the truth is the query's full row at --truth-coverage, or with
     --lost-only the lines of it the thinned row does not hold.  A job no search answers (no read kept, under -e) is tabulated
     with no results, named on stderr, and makes the return code 1, as `search --downsample` returns 1 for it."""
-    import sys
     from .junctions import format_recovery_rows, lost_lines, recovery_rows, sum_recovery_rows
     frequencies, coverages = args.grid_parts
     wanted = args.results
@@ -1791,10 +1584,9 @@ def _recovery_downsample(args, searcher, stdout):
     return 1 if failed else 0
 
 
-def _supersample(args, stdout):
+def _supersample(args, stdin, stdout):
     """create_supersample.py for one id list or several: the sums on the GPU in one call, the files in one pass over
     --junction-file."""
-    import os
     from .junctions import STORE_SUFFIX, JunctionStore, parse_groups_file, parse_sample_ids_file, write_supersample_files
     if args.sample_ids is not None:
         groups = [("supersample", parse_sample_ids_file(args.sample_ids))]
@@ -1802,9 +1594,7 @@ def _supersample(args, stdout):
     else:
         groups = parse_groups_file(args.groups)
         paths = [args.output + "." + label for label, _ in groups]
-    if not os.path.exists(args.basename + STORE_SUFFIX):
-        raise IOError("%s not found: this index has no junction store; build it with `morna index --junction-store`"
-                      % (args.basename + STORE_SUFFIX))
+    _require_store(args)
     store = JunctionStore.load(args.basename + STORE_SUFFIX, device=int(str(args.device).split(',')[0]))
     pooled = store.pool([ids for _, ids in groups])
     write_supersample_files(args.junction_file, zip(paths, pooled))
@@ -1818,37 +1608,16 @@ def _search_supersamples(args, searcher, stdout):
     """search --supersamples: every group pooled in one call and searched in one batch; a block per group, printed as
     --intropolis prints a sample's."""
     from .junctions import parse_groups_file
-    from .search import results_output
     groups = parse_groups_file(args.supersamples)
     if not groups:
         return 0
     labels = [label for label, _ in groups]
     pooled = searcher.pool_samples([ids for _, ids in groups])
     if args.unhashed:
-        terms = searcher.unhashed_terms_from_pooled(pooled, labels)
-        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata,
-                                                    restriction=_restriction(args))
+        results = _unhashed_search(args, searcher, searcher.unhashed_terms_from_pooled(pooled, labels), args.results)
     else:
-        batch = searcher.queries_from_pooled(pooled, labels, args.unhashed_junction_file)
-        if _max_distance(args) is not None:
-            results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
-                                                     meta_db=args.metadata, restriction=_restriction(args),
-                                                     num_neighbors=_radius_cap(args))
-        elif args.exact:
-            results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
-                                                     restriction=_restriction(args))
-        else:
-            results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
-                                               meta_db=args.metadata, restriction=_restriction(args), n_trees=_use_trees(args))
-    failed = False
-    for label, res in zip(labels, results):
-        stdout.write("# query %s\n" % label)
-        if isinstance(res, Exception):
-            stdout.write("# error: %s\n" % res)
-            failed = True
-        else:
-            results_output(res, stdout)
-    return 1 if failed else 0
+        results = _batch_search(args, searcher, searcher.queries_from_pooled(pooled, labels, args.unhashed_junction_file), args.results)
+    return _write_blocks(stdout, labels, results, lambda label: stdout.write("# query %s\n" % label))
 
 
 def _search_unhashed(args, searcher, stdin, stdout):
@@ -1868,29 +1637,19 @@ def _search_unhashed(args, searcher, stdin, stdout):
     key_line = key_lines(args.unhashed_junction_file, store.n_lines)
     if args.intropolis is not None:
         sample_ids, terms = intropolis_query_terms(args.intropolis, key_line, w)
-        results = searcher.unhashed_search_nn_batch(terms, args.results, include_distances=args.distances, meta_db=args.metadata,
-                                                    restriction=_restriction(args))
-        for sample_id, res in zip(sample_ids, results):
+        for sample_id, res in zip(sample_ids, _unhashed_search(args, searcher, terms, args.results)):
             stdout.write("# query %d\n" % sample_id)
             results_output(res, stdout)
         return 0
-    coverage = {}
-    for junction in _stream_parser(args.format)(stdin):        # summed per junction, as update_query sums them
-        key = " ".join(str(_) for _ in junction[:3])
-        coverage[key] = coverage.get(key, 0) + int(junction[3])
-    results = searcher.unhashed_search_nn_batch([query_terms(coverage, key_line, w)], args.results,
-                                                include_distances=args.distances, meta_db=args.metadata,
-                                                restriction=_restriction(args))
-    results_output(results[0], stdout)
+    coverage = _stream_coverage(_stream_parser(args.format)(stdin))
+    results_output(_unhashed_search(args, searcher, [query_terms(coverage, key_line, w)], args.results)[0], stdout)
     return 0
 
 
 def _search_radius_members(args, searcher, stdout, query_ids, numbered, collect=None):
     """-q / --query-ids under --max-distance: the header lines of the by-sample search, then every sample within the
     distance of the stored row, exactly (the query itself leads its list unless --leave-out-groups leaves it out)."""
-    results = searcher.exact_radius_nn_batch(query_ids, _max_distance(args), include_distances=args.distances,
-                                             meta_db=args.metadata, restriction=_restriction(args),
-                                             num_neighbors=_radius_cap(args))
+    results = _batch_search(args, searcher, query_ids, None)
     return _write_blocks(stdout, query_ids, results,
                          lambda query_id: _write_member_header(stdout, query_id, searcher.internal_id_map[query_id], numbered), collect)
 
@@ -1913,27 +1672,8 @@ def _search_batch(args, searcher, stdout, collect=None):
                 collect.append((query_id, res))
         return 0
     batch = searcher.queries_from_intropolis(args.intropolis)
-    if _max_distance(args) is not None:
-        results = searcher.exact_radius_nn_batch(batch, _max_distance(args), include_distances=args.distances,
-                                                 meta_db=args.metadata, restriction=_restriction(args),
-                                                 num_neighbors=_radius_cap(args))
-    elif args.exact:
-        results = searcher.exact_search_nn_batch(batch, args.results, include_distances=args.distances, meta_db=args.metadata,
-                                                 restriction=_restriction(args))
-    else:
-        results = searcher.search_nn_batch(batch, args.results, _search_k(args), include_distances=args.distances,
-                                           meta_db=args.metadata, restriction=_restriction(args), n_trees=_use_trees(args))
-    failed = False
-    for sample_id, res in zip(batch.ext_ids, results):
-        stdout.write("# query %d\n" % sample_id)
-        if isinstance(res, Exception):
-            stdout.write("# error: %s\n" % res)
-            failed = True
-        else:
-            results_output(res, stdout)
-            if collect is not None:
-                collect.append((sample_id, res))
-    return 1 if failed else 0
+    return _write_blocks(stdout, batch.ext_ids, _batch_search(args, searcher, batch, args.results),
+                         lambda sample_id: stdout.write("# query %d\n" % sample_id), collect)
 
 
 def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
@@ -2036,6 +1776,38 @@ def _search(args, searcher, stdin, stdout, dist, rank, collect=None):
     if collect is not None:
         collect.append((None, results))
     return 0
+
+
+_THIN_POOL = (_check_downsample_flags, _check_supersample_flags)
+# subcommand: (its flag checks in the order they run, its function of (args, stdin, stdout))
+_COMMANDS = {
+    'index': ((), _index),
+    'search': (_THIN_POOL + (_check_batch_flags, _check_unhashed_flags, _check_restriction_flags, _check_use_trees_flags,
+                             _check_max_distance_flags), _searching),
+    'junctions': (_THIN_POOL + (_check_batch_flags, _check_unhashed_flags, _check_junction_flags, _check_restriction_flags),
+                  _searching),
+    'recovery': (_THIN_POOL + (_check_recovery_flags, _check_batch_flags, _check_restriction_flags), _searching),
+    'supersample': ((), _supersample),
+    'pairs': ((_check_pairs_flags,), _pairs),
+    'recall': ((_check_recall_flags,), _recall),
+    'hashing': ((_check_hashing_flags,), _hashing),
+    'labels': ((_check_labels_flags,), _labels),
+    'cluster': ((_check_cluster_flags,), _cluster),
+    'mixture': ((_check_mixture_flags,), _mixture),
+    'explain': ((_check_explain_flags,), _explain),
+}
+
+
+def main(argv=None, stdin=None, stdout=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.subparser_name is None:
+        build_parser().print_help()
+        return 2
+    checks, command = _COMMANDS[args.subparser_name]
+    for check in checks:
+        check(parser, args)
+    return command(args, stdin or sys.stdin, stdout or sys.stdout)
 
 
 if __name__ == '__main__':
