@@ -200,3 +200,11 @@ def device_count():
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def read_stats(fn, handle, fields):
+    """The doubles of a morna_*_stats call as a dict: fields is a tuple of (name, int | float), in the order of the array."""
+    import numpy as np
+    stats = np.zeros(len(fields), np.float64)
+    check(fn(handle, ptr(stats)))
+    return {name: kind(x) for (name, kind), x in zip(fields, stats)}

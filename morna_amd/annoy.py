@@ -16,7 +16,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib, ptr
+from ._lib import check, lib, ptr, read_stats
+
+# the doubles of every morna_*_stats call of an index, in the order of the C array (the *_stats methods say what they mean)
+SWEEP_STATS = (("descents", int), ("cells", int), ("rows_canonical", int), ("contraction", int))
+LABEL_SUMS_STATS = (("scan_ms", float), ("sums_ms", float), ("queries", int), ("batches", int), ("counted", int), ("scan_eps", float))
+RADIUS_STATS = (("scan_ms", float), ("select_ms", float), ("dist_ms", float), ("queries", int), ("batches", int), ("candidates", int),
+                ("results", int), ("window", float))
+KMEANS_STATS = (("scan_ms", float), ("pick_ms", float), ("resolve_ms", float), ("update_ms", float), ("open_rows", int), ("chains", int),
+                ("iterations", int), ("largest", int))
+MIXTURE_STATS = (("centroids_ms", float), ("gram_ms", float), ("dots_ms", float), ("solve_ms", float), ("queries", int), ("sweeps", int),
+                 ("max_sweeps", int), ("open", int))
 
 
 def pack_allow_bits(allow):
@@ -25,6 +35,11 @@ def pack_allow_bits(allow):
     padded = np.zeros((len(allow) + 31) // 32 * 32, bool)
     padded[:len(allow)] = allow
     return np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def _results(nq, n, dist_dtype):
+    """The (ids, distances, counts) buffers of nq answers of n entries."""
+    return np.empty((nq, n), np.int32), np.empty((nq, n), dist_dtype), np.empty(nq, np.int32)
 
 
 class Restriction(object):
@@ -125,9 +140,7 @@ class AnnoyIndex(object):
 
     def get_nns_by_vector_ptr(self, q_ptr, nq, n, search_k=-1):
         """get_nns_by_vector_batch for nq contiguous fp32 rows at a raw (host or device) address."""
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         check(lib().morna_get_nns_by_vector(self._h, C.c_void_p(int(q_ptr)), int(nq), int(n), int(search_k),
                                             ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
@@ -141,9 +154,7 @@ class AnnoyIndex(object):
 
     def merge_topk_packed(self, gathered_ptr, world, nq, kk, n):
         """Merge of the all-gathered messages [world, nq, 2kk] (device memory) on the device."""
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         check(lib().morna_merge_topk_packed(self._h, C.c_void_p(int(gathered_ptr)), int(world), int(nq), int(kk), int(n),
                                             ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
@@ -235,9 +246,7 @@ class AnnoyIndex(object):
         if Q.ndim != 2 or Q.shape[1] != self.f:
             raise IndexError("queries must be [nq, %d]" % self.f)
         nq = Q.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         if n_trees is not None:
             check(lib().morna_get_nns_prefix(self._h, ptr(Q), None, nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
                                              ptr(cnt)))
@@ -249,9 +258,7 @@ class AnnoyIndex(object):
         """n_trees: as get_nns_by_vector_batch."""
         items = np.ascontiguousarray(items, dtype=np.int32)
         nq = items.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         if n_trees is not None:
             check(lib().morna_get_nns_prefix(self._h, None, ptr(items), nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
                                              ptr(cnt)))
@@ -270,21 +277,27 @@ class AnnoyIndex(object):
             return out, [float(x) for x in d[0, :m]]
         return out
 
-    def _sweep_args(self, trees, search_ks, Q, items):
+    def _query_source(self, Q, items, qtype):
+        """(Q, items, nq) of a call that takes query vectors Q (made [nq, f] of qtype), stored rows `items` (int32 [nq]) or
+        neither: the rows staged by build_query_rows."""
         if Q is not None and items is not None:
             raise ValueError("give query vectors or items, not both")
-        if Q is None and items is None:
-            nq = getattr(self, "_qrows_n", 0)          # the staged query rows (build_query_rows)
-        elif Q is not None:
-            Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=qtype)
             if Q.ndim != 2 or Q.shape[1] != self.f:
                 raise IndexError("queries must be [nq, %d]" % self.f)
             nq = Q.shape[0]
-        else:
+        elif items is not None:
             items = np.ascontiguousarray(items, dtype=np.int32)
             if items.ndim != 1:
                 raise ValueError("items must be one-dimensional")
             nq = items.shape[0]
+        else:
+            nq = getattr(self, "_qrows_n", 0)
+        return Q, items, nq
+
+    def _sweep_args(self, trees, search_ks, Q, items):
+        Q, items, nq = self._query_source(Q, items, np.float32)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         search_ks = np.ascontiguousarray(search_ks, dtype=np.int32).reshape(-1)
         return Q, items, nq, trees, search_ks
@@ -324,9 +337,7 @@ class AnnoyIndex(object):
 
     def sweep_stats(self):
         """Of the last search_sweep / recall_sweep: descents, cells, rows read by canonical dots, contraction (0 / 1)."""
-        st = np.zeros(4, np.float64)
-        check(lib().morna_search_sweep_stats(self._h, ptr(st)))
-        return dict(descents=int(st[0]), cells=int(st[1]), rows_canonical=int(st[2]), contraction=int(st[3]))
+        return read_stats(lib().morna_search_sweep_stats, self._h, SWEEP_STATS)
 
     def get_nns_by_item(self, i, n, search_k=-1, include_distances=False, n_trees=None):
         ids, d, cnt = self.get_nns_by_item_batch(np.array([i], np.int32), n, search_k, n_trees=n_trees)
@@ -342,9 +353,7 @@ class AnnoyIndex(object):
         if Q.ndim != 2 or Q.shape[1] != self.f:
             raise IndexError("queries must be [nq, %d]" % self.f)
         nq = Q.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_exact_search(self._h, ptr(Q), nq, int(n), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -352,9 +361,7 @@ class AnnoyIndex(object):
         """exact_search_nn for stored rows as the queries (morna_exact_search_by_item): only the item numbers are sent."""
         items = np.ascontiguousarray(items, dtype=np.int32)
         nq = items.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_exact_search_by_item(self._h, ptr(items), nq, int(n), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -378,51 +385,44 @@ class AnnoyIndex(object):
         check(lib().morna_restriction_create(self._h, ptr(bits), ptr(groups), C.byref(out)))
         return Restriction(self, out, groups)
 
-    def _restricted_queries(self, restriction, Q, items, query_groups, qtype):
-        """(q pointer, items pointer, nq, q_group pointer and the arrays that must outlive the call)"""
+    def _restriction_ptr(self, restriction, optional=True):
+        """The handle of a restriction, which must be one of this index; optional: None for None."""
+        if restriction is None and optional:
+            return None
         if not isinstance(restriction, Restriction) or restriction.owner is not self:
             raise ValueError("the restriction was not made by this index (AnnoyIndex.restriction)")
-        if Q is not None and items is not None:
-            raise ValueError("give query vectors or items, not both")
-        if Q is not None:
-            Q = np.ascontiguousarray(Q, dtype=qtype)
-            if Q.ndim != 2 or Q.shape[1] != self.f:
-                raise IndexError("queries must be [nq, %d]" % self.f)
-            nq = Q.shape[0]
-        elif items is not None:
-            items = np.ascontiguousarray(items, dtype=np.int32)
-            if items.ndim != 1:
-                raise ValueError("items must be one-dimensional")
-            nq = items.shape[0]
-        else:
-            nq = getattr(self, "_qrows_n", 0)
+        return restriction._p
+
+    def _restricted_queries(self, restriction, Q, items, query_groups, qtype, optional=False):
+        """(restriction pointer, Q, items, nq, query_groups): _query_source under a restriction (optional: or None), with the
+        label every query carries"""
+        r = self._restriction_ptr(restriction, optional)
+        if restriction is None and query_groups is not None:
+            raise ValueError("query groups need a restriction made with groups")
+        Q, items, nq = self._query_source(Q, items, qtype)
         if query_groups is not None:
             if restriction.groups is None:
                 raise ValueError("query groups need a restriction made with groups")
             query_groups = np.ascontiguousarray(query_groups, dtype=np.int32)
             if query_groups.shape != (nq,):
                 raise ValueError("query_groups must hold one label per query (%d), got shape %r" % (nq, query_groups.shape))
-        return Q, items, nq, query_groups
+        return r, Q, items, nq, query_groups
 
     def get_nns_restricted(self, restriction, n, search_k=-1, Q=None, items=None, query_groups=None):
         """get_nns_by_vector_batch (Q), get_nns_by_item_batch (items) or get_nns_by_query_rows (neither) under a
         restriction; query_groups: the label every query carries (int32 [nq], negative: none), None: no query has one."""
-        Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float32)
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
-        check(lib().morna_get_nns_restricted(self._h, restriction._p, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
+        r, Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float32)
+        ids, d, cnt = _results(nq, n, np.float32)
+        check(lib().morna_get_nns_restricted(self._h, r, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
                                              int(search_k), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
     def exact_search_restricted(self, restriction, n, Q=None, items=None, query_groups=None):
         """exact_search_batch (Q, fp64), exact_search_by_item_batch (items) or exact_search_query_rows (neither) under a
         restriction: the answer of the same search on an index of the eligible rows only, ids mapped back."""
-        Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
-        check(lib().morna_exact_search_restricted(self._h, restriction._p, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
+        r, Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
+        ids, d, cnt = _results(nq, n, np.float64)
+        check(lib().morna_exact_search_restricted(self._h, r, ptr(Q), ptr(items), nq, ptr(query_groups), int(n),
                                                   ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -433,41 +433,18 @@ class AnnoyIndex(object):
         counts.  item_label: int32 [n_items] in [-1, n_labels), -1 for none.  Queries: Q (fp64 [nq, f]), items (stored rows:
         the item itself is not counted), or neither: the staged query rows.  restriction / query_groups: as
         exact_search_restricted; None: every item is eligible."""
-        if np.shape(item_label) != (self.get_n_items(),):
-            raise ValueError("item_label must hold one label per item (%d), got shape %r" % (self.get_n_items(), np.shape(item_label)))
-        item_label = np.ascontiguousarray(item_label, dtype=np.int32)
+        item_label = self._item_labels(item_label)
         n_labels = int(n_labels)
-        if restriction is not None:
-            Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
-        else:
-            if query_groups is not None:
-                raise ValueError("query groups need a restriction made with groups")
-            if Q is not None and items is not None:
-                raise ValueError("give query vectors or items, not both")
-            if Q is not None:
-                Q = np.ascontiguousarray(Q, dtype=np.float64)
-                if Q.ndim != 2 or Q.shape[1] != self.f:
-                    raise IndexError("queries must be [nq, %d]" % self.f)
-                nq = Q.shape[0]
-            elif items is not None:
-                items = np.ascontiguousarray(items, dtype=np.int32)
-                if items.ndim != 1:
-                    raise ValueError("items must be one-dimensional")
-                nq = items.shape[0]
-            else:
-                nq = getattr(self, "_qrows_n", 0)
+        r, Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64, optional=True)
         sums = np.zeros((nq, max(n_labels, 0)), np.uint64)
         counts = np.zeros((nq, max(n_labels, 0)), np.int32)
-        check(lib().morna_label_sums(self._h, restriction._p if restriction is not None else None, ptr(Q), ptr(items), nq,
-                                     ptr(query_groups), ptr(item_label), n_labels, ptr(sums), ptr(counts)))
+        check(lib().morna_label_sums(self._h, r, ptr(Q), ptr(items), nq, ptr(query_groups), ptr(item_label), n_labels, ptr(sums),
+                                     ptr(counts)))
         return sums, counts
 
     def label_sums_stats(self):
         """Of the last label_sums: scan ms, sums-kernel ms, queries, batches, items counted, the scan's error bound."""
-        stats = np.zeros(6, np.float64)
-        check(lib().morna_label_sums_stats(self._h, ptr(stats)))
-        return dict(scan_ms=float(stats[0]), sums_ms=float(stats[1]), queries=int(stats[2]), batches=int(stats[3]),
-                    counted=int(stats[4]), scan_eps=float(stats[5]))
+        return read_stats(lib().morna_label_sums_stats, self._h, LABEL_SUMS_STATS)
 
     # ---- radius search (include/morna_hip.h, "radius search"; no counterpart in annoy) ----
     def exact_radius(self, radius, Q=None, items=None, restriction=None, query_groups=None, after=None):
@@ -476,32 +453,14 @@ class AnnoyIndex(object):
         [nq] is the list's length, or -1 where the reference would raise (the list then ends with its NaN entries).
         Queries: Q (fp64 [nq, f]), items (stored rows), or neither: the staged query rows.  restriction / query_groups: as
         exact_search_restricted; None: every item is eligible.  after: int32 [nq], only items with id > after[q]."""
-        if restriction is not None:
-            Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64)
-        else:
-            if query_groups is not None:
-                raise ValueError("query groups need a restriction made with groups")
-            if Q is not None and items is not None:
-                raise ValueError("give query vectors or items, not both")
-            if Q is not None:
-                Q = np.ascontiguousarray(Q, dtype=np.float64)
-                if Q.ndim != 2 or Q.shape[1] != self.f:
-                    raise IndexError("queries must be [nq, %d]" % self.f)
-                nq = Q.shape[0]
-            elif items is not None:
-                items = np.ascontiguousarray(items, dtype=np.int32)
-                if items.ndim != 1:
-                    raise ValueError("items must be one-dimensional")
-                nq = items.shape[0]
-            else:
-                nq = getattr(self, "_qrows_n", 0)
+        r, Q, items, nq, query_groups = self._restricted_queries(restriction, Q, items, query_groups, np.float64, optional=True)
         if after is not None:
             after = np.ascontiguousarray(after, dtype=np.int32)
             if after.shape != (nq,):
                 raise ValueError("after must hold one id per query (%d), got shape %r" % (nq, after.shape))
-        r = C.c_void_p()
-        check(lib().morna_exact_radius(self._h, restriction._p if restriction is not None else None, ptr(Q), ptr(items), nq,
-                                       ptr(query_groups), ptr(after), float(radius), C.byref(r)))
+        out = C.c_void_p()
+        check(lib().morna_exact_radius(self._h, r, ptr(Q), ptr(items), nq, ptr(query_groups), ptr(after), float(radius), C.byref(out)))
+        r = out
         try:
             counts = np.zeros(nq, np.int64)
             check(lib().morna_radius_counts(r, ptr(counts)))
@@ -528,19 +487,9 @@ class AnnoyIndex(object):
     def exact_radius_stats(self):
         """Of the last exact_radius: scan ms, selection ms, distance ms, queries, batches, candidates (fp64 chains run),
         result entries, the window the scan values were compared with."""
-        stats = np.zeros(8, np.float64)
-        check(lib().morna_exact_radius_stats(self._h, ptr(stats)))
-        return dict(scan_ms=float(stats[0]), select_ms=float(stats[1]), dist_ms=float(stats[2]), queries=int(stats[3]),
-                    batches=int(stats[4]), candidates=int(stats[5]), results=int(stats[6]), window=float(stats[7]))
+        return read_stats(lib().morna_exact_radius_stats, self._h, RADIUS_STATS)
 
     # ---- spherical k-means (include/morna_hip.h, "spherical k-means"; no counterpart in annoy) ----
-    def _kmeans_restriction(self, restriction):
-        if restriction is None:
-            return None
-        if not isinstance(restriction, Restriction) or restriction.owner is not self:
-            raise ValueError("the restriction was not made by this index (AnnoyIndex.restriction)")
-        return restriction._p
-
     def kmeans(self, seed_items, max_iterations=100, restriction=None):
         """Spherical k-means over the stored rows from the rows `seed_items` (distinct, eligible) as the first centroids: a dict
         of assign (int32 [n_items], -1 for a row the restriction does not allow), dist (float64 [n_items], the distance to
@@ -555,7 +504,7 @@ class AnnoyIndex(object):
         centroids = np.empty((k, self.f), np.float64)
         sizes = np.empty(k, np.int32)
         info = np.zeros(2, np.int32)
-        check(lib().morna_kmeans(self._h, self._kmeans_restriction(restriction), ptr(seeds), k, int(max_iterations), ptr(assign),
+        check(lib().morna_kmeans(self._h, self._restriction_ptr(restriction), ptr(seeds), k, int(max_iterations), ptr(assign),
                                  ptr(dist), ptr(centroids), ptr(sizes), ptr(info)))
         return dict(assign=assign, dist=dist, centroids=centroids, sizes=sizes, iterations=int(info[0]), converged=bool(info[1]))
 
@@ -568,17 +517,14 @@ class AnnoyIndex(object):
         n = self.get_n_items()
         assign = np.empty(n, np.int32)
         dist = np.empty(n, np.float64)
-        check(lib().morna_kmeans_assign(self._h, self._kmeans_restriction(restriction), ptr(centroids), int(centroids.shape[0]),
+        check(lib().morna_kmeans_assign(self._h, self._restriction_ptr(restriction), ptr(centroids), int(centroids.shape[0]),
                                         ptr(assign), ptr(dist)))
         return assign, dist
 
     def kmeans_stats(self):
         """Of the last kmeans / kmeans_assign: ms of scan, pick, resolve and update; open rows, fp64 chains run, iterations,
         the largest cluster of the last iteration."""
-        stats = np.zeros(8, np.float64)
-        check(lib().morna_kmeans_stats(self._h, ptr(stats)))
-        return dict(scan_ms=float(stats[0]), pick_ms=float(stats[1]), resolve_ms=float(stats[2]), update_ms=float(stats[3]),
-                    open_rows=int(stats[4]), chains=int(stats[5]), iterations=int(stats[6]), largest=int(stats[7]))
+        return read_stats(lib().morna_kmeans_stats, self._h, KMEANS_STATS)
 
     # ---- label mixture (include/morna_hip.h, "label mixture"; no counterpart in annoy) ----
     def _item_labels(self, item_label):
@@ -595,7 +541,7 @@ class AnnoyIndex(object):
         sums = np.zeros((max(n_labels, 0), self.f), np.float64)
         counts = np.zeros(max(n_labels, 0), np.int32)
         S = np.zeros((max(n_labels, 0), max(n_labels, 0)), np.float64) if gram else None
-        check(lib().morna_label_centroids(self._h, self._kmeans_restriction(restriction), ptr(item_label), n_labels, ptr(sums),
+        check(lib().morna_label_centroids(self._h, self._restriction_ptr(restriction), ptr(item_label), n_labels, ptr(sums),
                                           ptr(counts), ptr(S)))
         return sums, counts, S
 
@@ -606,34 +552,18 @@ class AnnoyIndex(object):
         staged query rows.  restriction: an allow-list only."""
         item_label = self._item_labels(item_label)
         n_labels = int(n_labels)
-        if Q is not None and items is not None:
-            raise ValueError("give query vectors or items, not both")
-        if Q is not None:
-            Q = np.ascontiguousarray(Q, dtype=np.float64)
-            if Q.ndim != 2 or Q.shape[1] != self.f:
-                raise IndexError("queries must be [nq, %d]" % self.f)
-            nq = Q.shape[0]
-        elif items is not None:
-            items = np.ascontiguousarray(items, dtype=np.int32)
-            if items.ndim != 1:
-                raise ValueError("items must be one-dimensional")
-            nq = items.shape[0]
-        else:
-            nq = getattr(self, "_qrows_n", 0)
+        Q, items, nq = self._query_source(Q, items, np.float64)
         weights = np.zeros((nq, max(n_labels, 0)), np.float64)
         info = np.zeros((nq, 4), np.float64)
         active = np.zeros((nq, max(n_labels, 0)), np.uint8)
-        check(lib().morna_mixture(self._h, self._kmeans_restriction(restriction), ptr(Q), ptr(items), nq, ptr(item_label), n_labels,
+        check(lib().morna_mixture(self._h, self._restriction_ptr(restriction), ptr(Q), ptr(items), nq, ptr(item_label), n_labels,
                                   float(tol), int(max_sweeps), ptr(weights), ptr(info), ptr(active)))
         return weights, info, active.astype(bool)
 
     def mixture_stats(self):
         """Of the last label_centroids / mixture: ms of the centroid step, the Gram, the query dots and the solver; queries,
         sweeps summed, the largest sweep count, queries that did not converge (status != 1)."""
-        stats = np.zeros(8, np.float64)
-        check(lib().morna_mixture_stats(self._h, ptr(stats)))
-        return dict(centroids_ms=float(stats[0]), gram_ms=float(stats[1]), dots_ms=float(stats[2]), solve_ms=float(stats[3]),
-                    queries=int(stats[4]), sweeps=int(stats[5]), max_sweeps=int(stats[6]), open=int(stats[7]))
+        return read_stats(lib().morna_mixture_stats, self._h, MIXTURE_STATS)
 
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):
@@ -654,9 +584,7 @@ class AnnoyIndex(object):
     def get_nns_by_query_rows(self, n, search_k=-1, n_trees=None):
         """get_nns_by_vector_batch with the resident fp32 query rows as the queries; n_trees: as there."""
         nq = getattr(self, "_qrows_n", 0)
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         if n_trees is not None:
             check(lib().morna_get_nns_prefix(self._h, None, None, nq, int(n), int(search_k), int(n_trees), ptr(ids), ptr(d),
                                              ptr(cnt)))
@@ -667,9 +595,7 @@ class AnnoyIndex(object):
     def exact_search_query_rows(self, n):
         """exact_search_batch with the resident fp64 query rows as the queries (they do not cross PCIe)."""
         nq = getattr(self, "_qrows_n", 0)
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_exact_search_query_rows(self._h, int(n), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -707,9 +633,7 @@ class AnnoyIndex(object):
         else:
             Q = np.ascontiguousarray(Q, dtype=np.float32)
             q_ptr, nq = ptr(Q), Q.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         check(lib().morna_get_nns_by_vector_sharded(self._h, q_ptr, nq, int(n), int(search_k), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -724,9 +648,7 @@ class AnnoyIndex(object):
             n_each = [len(items)]
         n_each = np.ascontiguousarray(n_each, dtype=np.int64)
         nq = int(n_each.sum())
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float32)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float32)
         check(lib().morna_get_nns_by_item_sharded(self._h, ptr(items), len(items), ptr(n_each), int(n), int(search_k),
                                                   ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
@@ -734,9 +656,7 @@ class AnnoyIndex(object):
     def exact_search_sharded(self, Q, n):
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         nq = Q.shape[0]
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_exact_search_sharded(self._h, ptr(Q), nq, int(n), ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -744,9 +664,7 @@ class AnnoyIndex(object):
         items = np.ascontiguousarray(local_items, dtype=np.int32)
         n_each = np.ascontiguousarray(n_each, dtype=np.int64)
         nq = int(n_each.sum())
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_exact_search_by_item_sharded(self._h, ptr(items), len(items), ptr(n_each), int(n),
                                                        ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
@@ -769,9 +687,7 @@ class AnnoyIndex(object):
         check(lib().morna_exact_search_packed(self._h, qp, dp, ip, nq, int(n), int(id_offset), C.c_void_p(int(packed_ptr))))
 
     def merge_exact_packed(self, gathered_ptr, world, nq, kk, n):
-        ids = np.empty((nq, n), np.int32)
-        d = np.empty((nq, n), np.float64)
-        cnt = np.empty(nq, np.int32)
+        ids, d, cnt = _results(nq, n, np.float64)
         check(lib().morna_merge_exact_packed(self._h, C.c_void_p(int(gathered_ptr)), int(world), int(nq), int(kk), int(n),
                                              ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt

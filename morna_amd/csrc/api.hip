@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -93,11 +94,146 @@ __global__ void gather_rows_kernel(const float *__restrict__ X, const int32_t *_
     CHECK_H_ONLY(h) \
     MORNA_TRY(finish_build(h, __func__));
 
+// ---- the query source of a call: vectors, stored items, or (both null) the rows of morna_build_query_rows ---------
+// Two families resolve it, and with nothing staged they answer differently.  The approximate one (fp32: get_nns_prefix,
+// search_sweep, recall_sweep, get_nns_restricted) says MORNA_E_STATE, "no query rows: ...", as the *_query_rows calls do
+// (query_rows_ready); morna_exact_search_restricted answers with it.  The whole scans (fp64: label_sums, exact_radius,
+// mixture) say MORNA_E_INVALID, "...: no query source (...)".  tests/test_gpu_entry_refusals.py holds both, line by line;
+// test_gpu_restrict.py and test_gpu_labels.py each pin one.  Making them answer alike is a change of behaviour.
+
+static int query_rows_ready(morna_index *h)
+{
+    if (!h->qrows.valid) {
+        set_error("no query rows: call morna_build_query_rows first");
+        return MORNA_E_STATE;
+    }
+    return MORNA_OK;
+}
+
+static int one_query_source(const char *who, const void *q, const int32_t *items)
+{
+    if (q && items) {
+        set_error("%s: give query vectors or items, not both", who);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+static int staged_count_is(morna_index *h, const char *who, int64_t nq)
+{
+    if (nq != h->qrows.nq) {
+        set_error("%s: %lld queries asked for, %lld query rows are staged", who, (long long)nq, (long long)h->qrows.nq);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
+// fp32: q as query_batch and search_sweep take it (host vectors, or the staged image read in place, q_stride floats apart)
+static int approx_queries(morna_index *h, const char *who, const float *&q, const int32_t *items, int64_t nq, int64_t &q_stride,
+                          bool *staged = nullptr)
+{
+    q_stride = 0;
+    if (staged) *staged = false;
+    MORNA_TRY(one_query_source(who, q, items));
+    if (q || items) return MORNA_OK;
+    MORNA_TRY(query_rows_ready(h));
+    MORNA_TRY(staged_count_is(h, who, nq));
+    q = h->qrows.rows32.p;
+    q_stride = h->dpad;
+    if (staged) *staged = true;
+    return MORNA_OK;
+}
+
+// fp64: the un-rounded rows.  Its callers make the one_query_source check themselves, earlier: their refusals of query
+// groups and of a row-sharded handle stand between the two.  as_approx: morna_exact_search_restricted (above)
+static int exact_queries(morna_index *h, const char *who, const double *q, const int32_t *items, int64_t nq, ExactQueries *Q,
+                         bool as_approx = false)
+{
+    *Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
+    if (q || items) return MORNA_OK;
+    if (as_approx) MORNA_TRY(query_rows_ready(h));
+    if (!h->qrows.valid) {
+        set_error("%s: no query source (give query vectors or items, or call morna_build_query_rows first)", who);
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(staged_count_is(h, who, nq));
+    *Q = ExactQueries::device64(h->qrows.rows64.p);
+    return MORNA_OK;
+}
+
+// ---- statistics of the last call -------------------------------------------------------------------------------------
+
+template <size_t N>
+static void clear_stats(double (&stats)[N])
+{
+    std::fill(stats, stats + N, 0.0);
+}
+
+// The five morna_*_stats (who: the entry point's __func__; the messages name it without "morna_").  handle_first:
+// morna_search_sweep_stats looks at the handle, finishes a pending build and only then at the array
+template <size_t N>
+static int read_stats(const morna_index *h, double (morna_index::*stats)[N], double *out, const char *who, bool handle_first = false)
+{
+    const char *name = who + 6;
+    if (handle_first) {
+        CHECK_H_ONLY(h);
+    } else if (!h || !out) {
+        set_error("%s: null pointer", name);
+        return MORNA_E_INVALID;
+    }
+    MORNA_TRY(finish_build(const_cast<morna_index *>(h), who));
+    if (!out) {
+        set_error("%s: null buffer", name);
+        return MORNA_E_INVALID;
+    }
+    std::copy(h->*stats, h->*stats + N, out);
+    return MORNA_OK;
+}
+
+// The guard of a whole-scan entry point (label_sums, exact_radius, kmeans, kmeans_assign, label_centroids, mixture), behind
+// CHECK_H: the call's statistics read zero unless it succeeds; args, the call's own null and range checks, come before
+// the refusal of a row-sharded handle, as they always have; no C++ exception of run (host vectors: bad_alloc, length_error)
+// crosses the C ABI.
+template <size_t N, class Args, class Run>
+static int whole_scan(morna_index *h, const char *who, double (&stats)[N], Args args, Run run)
+{
+    auto guarded = [&]() -> int {
+        MORNA_TRY(args());
+        if (h->comm) {
+            set_error("%s is not available on a row-sharded handle", who);
+            return MORNA_E_INVALID;
+        }
+        HIP_TRY(hipSetDevice(h->device));
+        try {
+            return run();
+        } catch (const std::exception &e) {
+            set_error("%s: %s", who, e.what());
+            return MORNA_E_INVALID;
+        }
+    };
+    clear_stats(stats);
+    const int rc = guarded();
+    if (rc != MORNA_OK) clear_stats(stats);
+    return rc;
+}
+
 extern "C" {
 
 const char *morna_last_error(void) { return g_err; }
 
 int32_t morna_hash32(const uint8_t *key, int64_t len) { return (int32_t)murmur3_32(key, len, 0u); }
+
+// The end of a handle: its events, the handle itself (the DevBuf / PinnedBuf destructors free HBM and the page-locked
+// staging), then its streams.  morna_index_destroy drains the streams first; morna_index_create comes here when it fails.
+static void free_handle(morna_index *h)
+{
+    for (hipEvent_t e : {h->ev_tables, h->ev_fork, h->ev_join, h->ev_tail, h->ev_early_in, h->ev_early_out})
+        if (e) (void)hipEventDestroy(e);
+    const hipStream_t streams[] = {h->stream3, h->stream2, h->stream};
+    delete h;
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamDestroy(s);
+}
 
 int morna_index_create(int32_t dim, int32_t device, morna_index **out)
 {
@@ -133,7 +269,7 @@ int morna_index_create(int32_t dim, int32_t device, morna_index **out)
     e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error("hipStreamCreate: %s", hipGetErrorString(e));
-        delete h;
+        free_handle(h);
         return MORNA_E_HIP;
     }
     int rc = h->d_stat.alloc(4);
@@ -149,16 +285,7 @@ int morna_index_create(int32_t dim, int32_t device, morna_index **out)
         rc = MORNA_E_HIP;
     }
     if (rc != MORNA_OK) {
-        if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-        if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-        if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-        if (h->ev_early_in) (void)hipEventDestroy(h->ev_early_in);
-        if (h->ev_early_out) (void)hipEventDestroy(h->ev_early_out);
-        if (h->stream3) (void)hipStreamDestroy(h->stream3);
-        if (h->stream2) (void)hipStreamDestroy(h->stream2);
-        (void)hipStreamDestroy(h->stream);
-        delete h;
+        free_handle(h);
         return rc;
     }
     *out = h;
@@ -195,17 +322,7 @@ int morna_index_destroy(morna_index *h)
     }
     for (hipEvent_t e : h->free_ev) (void)hipEventDestroy(e);
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-    if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    if (h->ev_early_in) (void)hipEventDestroy(h->ev_early_in);
-    if (h->ev_early_out) (void)hipEventDestroy(h->ev_early_out);
-    hipStream_t s = h->stream, s2 = h->stream2, s3 = h->stream3;
-    delete h;   // DevBuf / PinnedBuf destructors free HBM and the page-locked staging
-    if (s3) (void)hipStreamDestroy(s3);
-    if (s2) (void)hipStreamDestroy(s2);
-    if (s) (void)hipStreamDestroy(s);
+    free_handle(h);
     return MORNA_OK;
 }
 
@@ -617,8 +734,6 @@ int morna_exact_search(morna_index *h, const double *q, int64_t nq, int32_t k, i
 
 // ---- tree-prefix search and the (tree count, search_k) sweep (the contracts are in morna_hip.h) ------------------
 
-static int query_rows_ready(morna_index *h);
-
 int morna_get_nns_prefix(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, int32_t search_k,
                          int32_t n_trees_used, int32_t *ids, float *dist, int32_t *count)
 {
@@ -627,20 +742,8 @@ int morna_get_nns_prefix(morna_index *h, const float *q, const int32_t *items, i
         set_error("get_nns_prefix: null buffer");
         return MORNA_E_INVALID;
     }
-    if (q && items) {
-        set_error("get_nns_prefix: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
-    int64_t q_stride = 0;
-    if (!q && !items) {   // the staged query rows, read in place as morna_get_nns_by_query_rows reads them
-        MORNA_TRY(query_rows_ready(h));
-        if (nq != h->qrows.nq) {
-            set_error("get_nns_prefix: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        q = h->qrows.rows32.p;
-        q_stride = h->dpad;
-    }
+    int64_t q_stride;
+    MORNA_TRY(approx_queries(h, "get_nns_prefix", q, items, nq, q_stride));
     if (!h->built) {
         set_error("index has not been built: call build() before searching");
         return MORNA_E_STATE;
@@ -653,41 +756,14 @@ int morna_get_nns_prefix(morna_index *h, const float *q, const int32_t *items, i
     return query_batch(h, q, q_stride, items, nq, k, search_k, ids, dist, count, nullptr, 0, nullptr, nullptr, n_trees_used);
 }
 
-// the query source of a sweep: q, items, or (both null) the staged query rows, whose count nq must be
-static int sweep_source(morna_index *h, const float *&q, const int32_t *items, int64_t nq, int64_t &q_stride, bool &staged,
-                        const char *who)
-{
-    q_stride = 0;
-    staged = false;
-    if (q && items) {
-        set_error("%s: give query vectors or items, not both", who);
-        return MORNA_E_INVALID;
-    }
-    if (!q && !items) {
-        if (!h->qrows.valid) {
-            set_error("no query rows: call morna_build_query_rows first");
-            return MORNA_E_STATE;
-        }
-        if (nq != h->qrows.nq) {
-            set_error("%s: %lld queries asked for, %lld query rows are staged", who, (long long)nq, (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        q = h->qrows.rows32.p;
-        q_stride = h->dpad;
-        staged = true;
-    }
-    return MORNA_OK;
-}
-
 int morna_search_sweep(morna_index *h, const float *q, const int32_t *items, int64_t nq, int32_t k, const int32_t *trees,
                        int32_t n_t, const int32_t *search_ks, int32_t n_s, int32_t *ids_out, float *dist_out, int32_t *count_out,
                        int32_t *ncand_out, int32_t *ndots_out)
 {
     CHECK_H(h);
-    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    clear_stats(h->sweep_stats);
     int64_t q_stride;
-    bool staged;
-    MORNA_TRY(sweep_source(h, q, items, nq, q_stride, staged, "search_sweep"));
+    MORNA_TRY(approx_queries(h, "search_sweep", q, items, nq, q_stride));
     HIP_TRY(hipSetDevice(h->device));
     return search_sweep(h, q, q_stride, items, nq, k, trees, n_t, search_ks, n_s, ids_out, dist_out, count_out, ncand_out, ndots_out);
 }
@@ -698,7 +774,7 @@ int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int
                        int32_t *exact_ids_out)
 {
     CHECK_H(h);
-    h->sweep_stats[0] = h->sweep_stats[1] = h->sweep_stats[2] = h->sweep_stats[3] = 0.0;
+    clear_stats(h->sweep_stats);
     if (!hits_out) {
         set_error("recall_sweep: null buffer");
         return MORNA_E_INVALID;
@@ -709,7 +785,7 @@ int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int
     }
     int64_t q_stride;
     bool staged;
-    MORNA_TRY(sweep_source(h, q, items, nq, q_stride, staged, "recall_sweep"));
+    MORNA_TRY(approx_queries(h, "recall_sweep", q, items, nq, q_stride, &staged));
     HIP_TRY(hipSetDevice(h->device));
     // the sweep's own checks first (no exact search for a grid that is refused): a call without queries makes them all
     MORNA_TRY(search_sweep(h, q, q_stride, items, 0, k, trees, n_t, search_ks, n_s, nullptr, nullptr, nullptr, nullptr, nullptr));
@@ -733,26 +809,10 @@ int morna_recall_sweep(morna_index *h, const float *q, const int32_t *items, int
 
 int morna_search_sweep_stats(const morna_index *h, double *stats)
 {
-    CHECK_H_ONLY(h);
-    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
-    if (!stats) {
-        set_error("search_sweep_stats: null buffer");
-        return MORNA_E_INVALID;
-    }
-    for (int i = 0; i < 4; i++) stats[i] = h->sweep_stats[i];
-    return MORNA_OK;
+    return read_stats(h, &morna_index::sweep_stats, stats, __func__, true);
 }
 
 // ---- query rows (morna_build_query_rows is in parse.hip, beside the lines it takes) ---------------------------
-
-static int query_rows_ready(morna_index *h)
-{
-    if (!h->qrows.valid) {
-        set_error("no query rows: call morna_build_query_rows first");
-        return MORNA_E_STATE;
-    }
-    return MORNA_OK;
-}
 
 int morna_get_query_rows(morna_index *h, double *rows64, float *rows32)
 {
@@ -878,6 +938,15 @@ int morna_restriction_free(morna_restriction *r)
     return MORNA_OK;
 }
 
+static int query_groups_ok(const char *who, const morna_restriction *r, const int32_t *q_group)
+{
+    if (q_group && (!r || !r->has_group)) {
+        set_error("%s: query groups need a restriction that holds the items' groups", who);
+        return MORNA_E_INVALID;
+    }
+    return MORNA_OK;
+}
+
 // r == NULL with q_group == NULL is refused: such a call would be an unrestricted search under another name
 static int restricted_args_ok(const morna_restriction *r, const int32_t *q_group, const void *ids, const char *who)
 {
@@ -885,16 +954,11 @@ static int restricted_args_ok(const morna_restriction *r, const int32_t *q_group
         set_error("%s: null buffer", who);
         return MORNA_E_INVALID;
     }
-    if (!r) {
-        set_error(q_group ? "%s: query groups need a restriction that holds the items' groups"
-                          : "%s: no restriction (use the unrestricted call)", who);
+    if (!r && !q_group) {
+        set_error("%s: no restriction (use the unrestricted call)", who);
         return MORNA_E_INVALID;
     }
-    if (q_group && !r->has_group) {
-        set_error("%s: query groups need a restriction that holds the items' groups", who);
-        return MORNA_E_INVALID;
-    }
-    return MORNA_OK;
+    return query_groups_ok(who, r, q_group);
 }
 
 int morna_get_nns_restricted(morna_index *h, const morna_restriction *r, const float *q, const int32_t *items, int64_t nq,
@@ -902,20 +966,10 @@ int morna_get_nns_restricted(morna_index *h, const morna_restriction *r, const f
 {
     CHECK_H(h);
     MORNA_TRY(restricted_args_ok(r, q_group, ids, "get_nns_restricted"));
-    if (q && items) {
-        set_error("get_nns_restricted: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
+    int64_t q_stride;
+    MORNA_TRY(approx_queries(h, "get_nns_restricted", q, items, nq, q_stride));
     HIP_TRY(hipSetDevice(h->device));
-    if (!q && !items) {   // the staged query rows
-        MORNA_TRY(query_rows_ready(h));
-        if (nq != h->qrows.nq) {
-            set_error("get_nns_restricted: %lld queries asked for, %lld query rows are staged", (long long)nq, (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        return query_batch(h, h->qrows.rows32.p, h->dpad, nullptr, nq, k, search_k, ids, dist, count, nullptr, 0, r, q_group);
-    }
-    return query_batch(h, q, 0, items, nq, k, search_k, ids, dist, count, nullptr, 0, r, q_group);
+    return query_batch(h, q, q_stride, items, nq, k, search_k, ids, dist, count, nullptr, 0, r, q_group);
 }
 
 int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
@@ -923,80 +977,40 @@ int morna_exact_search_restricted(morna_index *h, const morna_restriction *r, co
 {
     CHECK_H(h);
     MORNA_TRY(restricted_args_ok(r, q_group, ids, "exact_search_restricted"));
-    if (q && items) {
-        set_error("exact_search_restricted: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
+    MORNA_TRY(one_query_source("exact_search_restricted", q, items));
+    ExactQueries Q;
+    MORNA_TRY(exact_queries(h, "exact_search_restricted", q, items, nq, &Q, true));
     HIP_TRY(hipSetDevice(h->device));
-    if (!q && !items) {
-        MORNA_TRY(query_rows_ready(h));
-        if (nq != h->qrows.nq) {
-            set_error("exact_search_restricted: %lld queries asked for, %lld query rows are staged", (long long)nq,
-                      (long long)h->qrows.nq);
-            return MORNA_E_INVALID;
-        }
-        return exact_search_any(h, ExactQueries::device64(h->qrows.rows64.p), nq, k, ids, dist, count, nullptr, 0, r, q_group);
-    }
-    return exact_search_any(h, q ? ExactQueries::host(q) : ExactQueries::stored(items), nq, k, ids, dist, count, nullptr, 0, r, q_group);
+    return exact_search_any(h, Q, nq, k, ids, dist, count, nullptr, 0, r, q_group);
 }
 
 // ---- label distance sums (the contract is in morna_hip.h) -------------------------------------------------------
-
-// the staged query rows as the queries of a call that was given neither vectors nor items
-static int staged_queries(morna_index *h, const char *what, int64_t nq, ExactQueries *Q)
-{
-    if (!h->qrows.valid) {
-        set_error("%s: no query source (give query vectors or items, or call morna_build_query_rows first)", what);
-        return MORNA_E_INVALID;
-    }
-    if (nq != h->qrows.nq) {
-        set_error("%s: %lld queries asked for, %lld query rows are staged", what, (long long)nq, (long long)h->qrows.nq);
-        return MORNA_E_INVALID;
-    }
-    *Q = ExactQueries::device64(h->qrows.rows64.p);
-    return MORNA_OK;
-}
 
 int morna_label_sums(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
                      const int32_t *q_group, const int32_t *item_label, int32_t n_labels, uint64_t *sums_out, int32_t *counts_out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 6; i++) h->label_stats[i] = 0.0;
-    if (!item_label || !sums_out || !counts_out) {
-        set_error("label_sums: null buffer");
-        return MORNA_E_INVALID;
-    }
-    if (n_labels < 1 || n_labels > MORNA_LABELS_MAX) {
-        set_error("label_sums: %d labels, 1 to %d are taken", n_labels, MORNA_LABELS_MAX);
-        return MORNA_E_INVALID;
-    }
-    if (q && items) {
-        set_error("label_sums: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
-    if (q_group && (!r || !r->has_group)) {
-        set_error("label_sums: query groups need a restriction that holds the items' groups");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("label_sums is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
-    if (!q && !items) MORNA_TRY(staged_queries(h, "label_sums", nq, &Q));
-    return label_sums(h, r, Q, nq, q_group, item_label, n_labels, sums_out, counts_out);
+    return whole_scan(h, "label_sums", h->label_stats, [&]() -> int {
+        if (!item_label || !sums_out || !counts_out) {
+            set_error("label_sums: null buffer");
+            return MORNA_E_INVALID;
+        }
+        if (n_labels < 1 || n_labels > MORNA_LABELS_MAX) {
+            set_error("label_sums: %d labels, 1 to %d are taken", n_labels, MORNA_LABELS_MAX);
+            return MORNA_E_INVALID;
+        }
+        MORNA_TRY(one_query_source("label_sums", q, items));
+        return query_groups_ok("label_sums", r, q_group);
+    }, [&]() -> int {
+        ExactQueries Q;
+        MORNA_TRY(exact_queries(h, "label_sums", q, items, nq, &Q));
+        return label_sums(h, r, Q, nq, q_group, item_label, n_labels, sums_out, counts_out);
+    });
 }
 
 int morna_label_sums_stats(const morna_index *h, double *stats)
 {
-    if (!h || !stats) {
-        set_error("label_sums_stats: null pointer");
-        return MORNA_E_INVALID;
-    }
-    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
-    for (int i = 0; i < 6; i++) stats[i] = h->label_stats[i];
-    return MORNA_OK;
+    return read_stats(h, &morna_index::label_stats, stats, __func__);
 }
 
 // ---- radius search (the contract is in morna_hip.h) ---------------------------------------------------------------
@@ -1005,43 +1019,22 @@ int morna_exact_radius(morna_index *h, const morna_restriction *r, const double 
                        const int32_t *q_group, const int32_t *after, double radius, morna_radius **out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
-    if (!out) {
-        set_error("exact_radius: null buffer");
-        return MORNA_E_INVALID;
-    }
-    *out = nullptr;
-    if (q && items) {
-        set_error("exact_radius: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
-    if (q_group && (!r || !r->has_group)) {
-        set_error("exact_radius: query groups need a restriction that holds the items' groups");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("exact_radius is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
-    if (!q && !items) MORNA_TRY(staged_queries(h, "exact_radius", nq, &Q));
-    morna_radius *R = nullptr;
-    int rc = MORNA_OK;
-    try {   // (the lists grow on the host: bad_alloc / length_error must not cross the C ABI)
-        R = new morna_radius();
-        rc = exact_radius(h, r, Q, nq, q_group, after, radius, R);
-    } catch (const std::exception &e) {
-        set_error("exact_radius: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK) {
-        delete R;
-        for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
-        return rc;
-    }
-    *out = R;
-    return MORNA_OK;
+    return whole_scan(h, "exact_radius", h->radius_stats, [&]() -> int {
+        if (!out) {
+            set_error("exact_radius: null buffer");
+            return MORNA_E_INVALID;
+        }
+        *out = nullptr;
+        MORNA_TRY(one_query_source("exact_radius", q, items));
+        return query_groups_ok("exact_radius", r, q_group);
+    }, [&]() -> int {
+        ExactQueries Q;
+        MORNA_TRY(exact_queries(h, "exact_radius", q, items, nq, &Q));
+        std::unique_ptr<morna_radius> R(new morna_radius());   // (the lists grow on the host)
+        MORNA_TRY(exact_radius(h, r, Q, nq, q_group, after, radius, R.get()));
+        *out = R.release();
+        return MORNA_OK;
+    });
 }
 
 int morna_radius_counts(const morna_radius *r, int64_t *count_out)
@@ -1078,13 +1071,7 @@ int morna_radius_free(morna_radius *r)
 
 int morna_exact_radius_stats(const morna_index *h, double *stats)
 {
-    if (!h || !stats) {
-        set_error("exact_radius_stats: null pointer");
-        return MORNA_E_INVALID;
-    }
-    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
-    for (int i = 0; i < 8; i++) stats[i] = h->radius_stats[i];
-    return MORNA_OK;
+    return read_stats(h, &morna_index::radius_stats, stats, __func__);
 }
 
 // ---- spherical k-means (the contract is in morna_hip.h) -----------------------------------------------------------
@@ -1093,100 +1080,53 @@ int morna_kmeans(morna_index *h, const morna_restriction *r, const int32_t *seed
                  int32_t *assign_out, double *dist_out, double *centroids_out, int32_t *sizes_out, int32_t *info_out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
-    if (!seed_items || !assign_out || !info_out) {
-        set_error("kmeans: null buffer");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("kmeans is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    int rc = MORNA_OK;
-    try {   // (host vectors: bad_alloc must not cross the C ABI)
-        rc = kmeans(h, r, seed_items, nullptr, k, max_iter, assign_out, dist_out, centroids_out, sizes_out, info_out);
-    } catch (const std::exception &e) {
-        set_error("kmeans: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK)
-        for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
-    return rc;
+    return whole_scan(h, "kmeans", h->kmeans_stats, [&]() -> int {
+        if (!seed_items || !assign_out || !info_out) {
+            set_error("kmeans: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return MORNA_OK;
+    }, [&]() -> int {
+        return kmeans(h, r, seed_items, nullptr, k, max_iter, assign_out, dist_out, centroids_out, sizes_out, info_out);
+    });
 }
 
 int morna_kmeans_assign(morna_index *h, const morna_restriction *r, const double *centroids, int32_t k, int32_t *assign_out,
                         double *dist_out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
-    if (!centroids || !assign_out) {
-        set_error("kmeans_assign: null buffer");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("kmeans_assign is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    int rc = MORNA_OK;
-    try {
-        rc = kmeans(h, r, nullptr, centroids, k, 1, assign_out, dist_out, nullptr, nullptr, nullptr);
-    } catch (const std::exception &e) {
-        set_error("kmeans_assign: %s", e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK)
-        for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
-    return rc;
+    return whole_scan(h, "kmeans_assign", h->kmeans_stats, [&]() -> int {
+        if (!centroids || !assign_out) {
+            set_error("kmeans_assign: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return MORNA_OK;
+    }, [&]() -> int {
+        return kmeans(h, r, nullptr, centroids, k, 1, assign_out, dist_out, nullptr, nullptr, nullptr);
+    });
 }
 
 int morna_kmeans_stats(const morna_index *h, double *stats)
 {
-    if (!h || !stats) {
-        set_error("kmeans_stats: null pointer");
-        return MORNA_E_INVALID;
-    }
-    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
-    for (int i = 0; i < 8; i++) stats[i] = h->kmeans_stats[i];
-    return MORNA_OK;
+    return read_stats(h, &morna_index::kmeans_stats, stats, __func__);
 }
 
 // ---- label mixture (the contract is in morna_hip.h) ------------------------------------------------------------------
-
-static int mixture_guarded(morna_index *h, const char *who, const morna_restriction *r, const ExactQueries &Q, int64_t nq,
-                           const int32_t *item_label, int32_t n_labels, double tol, int32_t max_sweeps, double *sums_out,
-                           int32_t *counts_out, double *gram_out, double *weights_out, double *info_out, uint8_t *active_out)
-{
-    int rc = MORNA_OK;
-    try {   // (host vectors: bad_alloc must not cross the C ABI)
-        rc = mixture(h, r, Q, nq, item_label, n_labels, tol, max_sweeps, sums_out, counts_out, gram_out, weights_out, info_out,
-                     active_out);
-    } catch (const std::exception &e) {
-        set_error("%s: %s", who, e.what());
-        rc = MORNA_E_INVALID;
-    }
-    if (rc != MORNA_OK)
-        for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
-    return rc;
-}
 
 int morna_label_centroids(morna_index *h, const morna_restriction *r, const int32_t *item_label, int32_t n_labels, double *sums_out,
                           int32_t *counts_out, double *gram_out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
-    if (!item_label || !sums_out || !counts_out) {
-        set_error("label_centroids: null buffer");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("label_centroids is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    return mixture_guarded(h, "label_centroids", r, ExactQueries::host(nullptr), 0, item_label, n_labels, 0.0, 1, sums_out, counts_out,
-                           gram_out, nullptr, nullptr, nullptr);
+    return whole_scan(h, "label_centroids", h->mixture_stats, [&]() -> int {
+        if (!item_label || !sums_out || !counts_out) {
+            set_error("label_centroids: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return MORNA_OK;
+    }, [&]() -> int {
+        return mixture(h, r, ExactQueries::host(nullptr), 0, item_label, n_labels, 0.0, 1, sums_out, counts_out, gram_out, nullptr,
+                       nullptr, nullptr);
+    });
 }
 
 int morna_mixture(morna_index *h, const morna_restriction *r, const double *q, const int32_t *items, int64_t nq,
@@ -1194,35 +1134,22 @@ int morna_mixture(morna_index *h, const morna_restriction *r, const double *q, c
                   uint8_t *active_out)
 {
     CHECK_H(h);
-    for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
-    if (!item_label || !weights_out || !info_out) {
-        set_error("mixture: null buffer");
-        return MORNA_E_INVALID;
-    }
-    if (q && items) {
-        set_error("mixture: give query vectors or items, not both");
-        return MORNA_E_INVALID;
-    }
-    if (h->comm) {
-        set_error("mixture is not available on a row-sharded handle");
-        return MORNA_E_INVALID;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    ExactQueries Q = q ? ExactQueries::host(q) : ExactQueries::stored(items);
-    if (!q && !items) MORNA_TRY(staged_queries(h, "mixture", nq, &Q));
-    return mixture_guarded(h, "mixture", r, Q, nq, item_label, n_labels, tol, max_sweeps, nullptr, nullptr, nullptr, weights_out,
-                           info_out, active_out);
+    return whole_scan(h, "mixture", h->mixture_stats, [&]() -> int {
+        if (!item_label || !weights_out || !info_out) {
+            set_error("mixture: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return one_query_source("mixture", q, items);
+    }, [&]() -> int {
+        ExactQueries Q;
+        MORNA_TRY(exact_queries(h, "mixture", q, items, nq, &Q));
+        return mixture(h, r, Q, nq, item_label, n_labels, tol, max_sweeps, nullptr, nullptr, nullptr, weights_out, info_out, active_out);
+    });
 }
 
 int morna_mixture_stats(const morna_index *h, double *stats)
 {
-    if (!h || !stats) {
-        set_error("mixture_stats: null pointer");
-        return MORNA_E_INVALID;
-    }
-    MORNA_TRY(finish_build(const_cast<morna_index *>(h), __func__));
-    for (int i = 0; i < 8; i++) stats[i] = h->mixture_stats[i];
-    return MORNA_OK;
+    return read_stats(h, &morna_index::mixture_stats, stats, __func__);
 }
 
 // ---- persistence ---------------------------------------------------------------

@@ -1082,7 +1082,6 @@ __global__ __launch_bounds__(LS_THREADS) void label_sums_kernel(const float *__r
 int label_sums(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *q_group_host,
                const int32_t *item_label_host, int32_t L, uint64_t *sums_out, int32_t *counts_out)
 {
-    for (int i = 0; i < 6; i++) h->label_stats[i] = 0.0;
     ExactFront F;
     MORNA_TRY(exact_front(h, "label_sums", "label_sums", rst, Q, nq, q_group_host, 0, [&]() -> int {
         if (nq < 0) {
@@ -1426,7 +1425,6 @@ static bool radius_before(double da, int32_t ia, double db, int32_t ib)
 int exact_radius(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *q_group_host,
                  const int32_t *after_host, double radius, morna_radius *out)
 {
-    for (int i = 0; i < 8; i++) h->radius_stats[i] = 0.0;
     int64_t batch_cap = 0;
     if (const char *e = getenv("MORNA_RADIUS_BATCH")) batch_cap = atoll(e);   // (read per call: a test puts a batch edge inside a small call)
     ExactFront F;
@@ -1924,7 +1922,6 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(const float *
 int kmeans(morna_index *h, const morna_restriction *rst, const int32_t *seeds, const double *cent_host, int32_t k, int32_t max_iter,
            int32_t *assign_out, double *dist_out, double *cent_out, int32_t *sizes_out, int32_t *info_out)
 {
-    for (int i = 0; i < 8; i++) h->kmeans_stats[i] = 0.0;
     const bool loop = seeds != nullptr;
     const char *who = loop ? "kmeans" : "kmeans_assign";
     ExactFront F;

@@ -331,7 +331,6 @@ int mixture(morna_index *h, const morna_restriction *rst, const ExactQueries &Q,
             double tol, int32_t max_sweeps, double *sums_out, int32_t *counts_out, double *gram_out, double *weights_out,
             double *info_out, uint8_t *active_out)
 {
-    for (int i = 0; i < 8; i++) h->mixture_stats[i] = 0.0;
     const bool solve = weights_out != nullptr;
     const char *who = solve ? "mixture" : "label_centroids";
     MORNA_TRY(finish_build(h, who));

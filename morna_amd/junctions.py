@@ -23,7 +23,7 @@ from math import ceil, isfinite
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import check, lib, ptr, read_stats
 
 MAX_RESULTS = 64        # found_in is one 64-bit word per line (morna_jstore_retain)
 STORE_SUFFIX = ".junc.mor"
@@ -262,6 +262,30 @@ def _pack_lists(lists, what, limit=MAX_RESULTS):
     return res, n_res, k
 
 
+def _pack_queries(queries):
+    """Unhashed queries, a (lines, coverages) pair each, as the CSR the library takes: (q_ptr int64 [nq + 1], q_line int32,
+    q_cov int32); ValueError for a pair that is not two 1-d arrays of one length."""
+    queries = [(np.ascontiguousarray(l, np.int32), np.ascontiguousarray(c, np.int32)) for l, c in queries]
+    for l, c in queries:
+        if l.ndim != 1 or l.shape != c.shape:
+            raise ValueError("an unhashed query is a pair of 1-d arrays of one length: lines and coverages")
+    q_ptr = np.zeros(len(queries) + 1, np.int64)
+    np.cumsum([len(l) for l, _ in queries], out=q_ptr[1:])
+    q_line = np.concatenate([l for l, _ in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+    q_cov = np.concatenate([c for _, c in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+    return q_ptr, q_line, q_cov
+
+
+# the doubles of every morna_jstore_*_stats call, in the order of the C array (the *_stats methods say what they mean)
+NEAREST_STATS = (("candidates", int), ("max_candidates", int), ("passes", int), ("kernel_ms", float), ("bytes", int),
+                 ("queries_per_pass", int), ("norms_ms", float), ("window", float))
+EXPLAIN_STATS = (("pairs", int), ("entries", int), ("passes", int), ("kernel_ms", float), ("bytes", int), ("queries_per_pass", int))
+RECOVERY_STATS = (("kernel_ms", float), ("bytes", int), ("workgroups", int))
+POOL_STATS = (("kernel_ms", float), ("bytes_read", int), ("bytes_written", int), ("workgroups", int))
+THIN_STATS = (("kernel_ms", float), ("bytes_read", int), ("bytes_written", int), ("draws", int), ("workgroups", int))
+HASH_ROWS_STATS = (("kernel_ms", float), ("bytes_read", int), ("bytes_written", int), ("workgroups", int))
+
+
 class JunctionStore(object):
     """A junction store held by the library (morna_jstore)."""
 
@@ -344,16 +368,9 @@ class JunctionStore(object):
         past min(k, len(population)).  IndexError for a population id the store lacks, ValueError for a negative
         coverage, unsorted lines, or k outside [1, 1024]."""
         pop = np.ascontiguousarray(population, np.int64)
-        queries = [(np.ascontiguousarray(l, np.int32), np.ascontiguousarray(c, np.int32)) for l, c in queries]
-        for l, c in queries:
-            if l.ndim != 1 or l.shape != c.shape:
-                raise ValueError("an unhashed query is a pair of 1-d arrays of one length: lines and coverages")
-        q_ptr = np.zeros(len(queries) + 1, np.int64)
-        np.cumsum([len(l) for l, _ in queries], out=q_ptr[1:])
-        q_line = np.concatenate([l for l, _ in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
-        q_cov = np.concatenate([c for _, c in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
-        ids, d, cnt = self._nearest_out(len(queries), max(int(k), 1))
-        check(lib().morna_jstore_nearest(self._p, ptr(pop), len(pop), ptr(q_ptr), ptr(q_line), ptr(q_cov), len(queries), int(k),
+        q_ptr, q_line, q_cov = _pack_queries(queries)
+        ids, d, cnt = self._nearest_out(len(q_ptr) - 1, max(int(k), 1))
+        check(lib().morna_jstore_nearest(self._p, ptr(pop), len(pop), ptr(q_ptr), ptr(q_line), ptr(q_cov), len(q_ptr) - 1, int(k),
                                          ptr(ids), ptr(d), ptr(cnt)))
         return ids, d, cnt
 
@@ -370,10 +387,7 @@ class JunctionStore(object):
         """Of the last nearest / nearest_by_sample: candidates re-ranked in all and the most for one query, passes over
         the store, kernel ms (HIP events), algorithmic bytes (8 per store entry of the population per pass), queries per
         pass, kernel ms of the row-norm pass (0.0 when the norms were cached), and the selection window."""
-        s = np.zeros(8, np.float64)
-        check(lib().morna_jstore_nearest_stats(self._p, ptr(s)))
-        return {"candidates": int(s[0]), "max_candidates": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]),
-                "bytes": int(s[4]), "queries_per_pass": int(s[5]), "norms_ms": float(s[6]), "window": float(s[7])}
+        return read_stats(lib().morna_jstore_nearest_stats, self._p, NEAREST_STATS)
 
     # ---- the junctions behind a query and each result (DESIGN.md 8, N17; csrc/explain.hip) ---------------------------
     def _explained(self, r, n_res, top):
@@ -404,19 +418,13 @@ class JunctionStore(object):
         the decomposition of the unhashed cosine of the pair: one list of Explained per query.  All pairs in one call on
         the GPU.  IndexError for an id the store lacks, ValueError for a negative coverage, unsorted lines, or `top`
         outside [1, 64], RuntimeError without weights."""
-        queries = [(np.ascontiguousarray(l, np.int32), np.ascontiguousarray(c, np.int32)) for l, c in queries]
-        for l, c in queries:
-            if l.ndim != 1 or l.shape != c.shape:
-                raise ValueError("an unhashed query is a pair of 1-d arrays of one length: lines and coverages")
+        q_ptr, q_line, q_cov = _pack_queries(queries)
+        nq = len(q_ptr) - 1
         res, n_res, k = _pack_lists(result_sample_ids, "explain takes at most %d", MAX_NEAREST)
-        if len(n_res) != len(queries):
-            raise ValueError("explain takes one result list per query (%d queries, %d lists)" % (len(queries), len(n_res)))
-        q_ptr = np.zeros(len(queries) + 1, np.int64)
-        np.cumsum([len(l) for l, _ in queries], out=q_ptr[1:])
-        q_line = np.concatenate([l for l, _ in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
-        q_cov = np.concatenate([c for _, c in queries] + [np.zeros(0, np.int32)]).astype(np.int32)
+        if len(n_res) != nq:
+            raise ValueError("explain takes one result list per query (%d queries, %d lists)" % (nq, len(n_res)))
         r = C.c_void_p()
-        check(lib().morna_jstore_explain(self._p, ptr(q_ptr), ptr(q_line), ptr(q_cov), len(queries), ptr(res), ptr(n_res), k, int(top),
+        check(lib().morna_jstore_explain(self._p, ptr(q_ptr), ptr(q_line), ptr(q_cov), nq, ptr(res), ptr(n_res), k, int(top),
                                          C.byref(r)))
         return self._explained(r, n_res, int(top))
 
@@ -433,10 +441,7 @@ class JunctionStore(object):
     def explain_stats(self):
         """Of the last explain / explain_by_sample: pairs explained, store entries streamed, passes (query tiles), kernel ms
         (HIP events), algorithmic bytes (8 per entry streamed) and queries per pass; all 0 after a refused call."""
-        s = np.zeros(6, np.float64)
-        check(lib().morna_jstore_explain_stats(self._p, ptr(s)))
-        return {"pairs": int(s[0]), "entries": int(s[1]), "passes": int(s[2]), "kernel_ms": float(s[3]), "bytes": int(s[4]),
-                "queries_per_pass": int(s[5])}
+        return read_stats(lib().morna_jstore_explain_stats, self._p, EXPLAIN_STATS)
 
     # ---- recovery tables over the filter grid (DESIGN.md 8, N6) -------------------------------------------------------
     def _recovery_arguments(self, result_sample_ids, coverage_grid, prefixes=None):
@@ -514,9 +519,7 @@ class JunctionStore(object):
         """Of the last recovery / recovery_by_sample or sweep: kernel ms (HIP events), algorithmic bytes (8 per entry of the
         result and truth rows named, 4 per line of a truth given as lines; a sweep reads the rows up to its last prefix,
         once) and workgroups launched."""
-        s = np.zeros(3, np.float64)
-        check(lib().morna_jstore_recovery_stats(self._p, ptr(s)))
-        return {"kernel_ms": float(s[0]), "bytes": int(s[1]), "workgroups": int(s[2])}
+        return read_stats(lib().morna_jstore_recovery_stats, self._p, RECOVERY_STATS)
 
     # ---- pooled samples (DESIGN.md 8, N8) -------------------------------------------------------------------------------
     def pool(self, groups):
@@ -546,9 +549,7 @@ class JunctionStore(object):
     def pool_stats(self):
         """Of the last pool: kernel ms (HIP events, both passes), bytes read (8 per entry of every member row, per pass),
         bytes written (16 per held line) and workgroups per pass."""
-        s = np.zeros(4, np.float64)
-        check(lib().morna_jstore_pool_stats(self._p, ptr(s)))
-        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "workgroups": int(s[3])}
+        return read_stats(lib().morna_jstore_pool_stats, self._p, POOL_STATS)
 
     # ---- depth thinning (DESIGN.md 8, N9) -----------------------------------------------------------------------------------
     def thin(self, sample_ids, keep, seed):
@@ -584,19 +585,14 @@ class JunctionStore(object):
         """Of the last thin: kernel ms (HIP events: both passes and the scan), bytes read (16 per entry of every named row),
         bytes written (4 per entry and 8 per surviving line), draws made (the summed coverage of the named rows) and
         workgroups per pass."""
-        s = np.zeros(5, np.float64)
-        check(lib().morna_jstore_thin_stats(self._p, ptr(s)))
-        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "draws": int(s[3]),
-                "workgroups": int(s[4])}
+        return read_stats(lib().morna_jstore_thin_stats, self._p, THIN_STATS)
 
     # ---- hashed rows of any width (DESIGN.md 8, N12; AnnoyIndex.add_items_from_store) ----------------------------------------
     def hash_rows_stats(self):
         """Of the last AnnoyIndex.add_items_from_store over this store: kernel ms (HIP events), bytes read (8 per entry of
         every named row, 12 per line for hash and weight), bytes written (4 per padded cell) and workgroups; all 0 after a
         refused call."""
-        s = np.zeros(4, np.float64)
-        check(lib().morna_jstore_hash_rows_stats(self._p, ptr(s)))
-        return {"kernel_ms": float(s[0]), "bytes_read": int(s[1]), "bytes_written": int(s[2]), "workgroups": int(s[3])}
+        return read_stats(lib().morna_jstore_hash_rows_stats, self._p, HASH_ROWS_STATS)
 
     def row_norms(self, sample_ids):
         """The unhashed squared norm (fp64) of the store rows of `sample_ids` (external ids; repeats allowed) under the

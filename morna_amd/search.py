@@ -26,7 +26,7 @@ from math import log
 import numpy as np
 
 from . import _lib
-from .annoy import AnnoyIndex
+from .annoy import LABEL_SUMS_STATS, MIXTURE_STATS, AnnoyIndex
 from .metadb import lookup_meta
 
 
@@ -579,6 +579,30 @@ def write_groups_file(path, groups):
             fh.write("%s\t%s\n" % (label, ",".join(str(i) for i in ids)))
 
 
+def accumulate_stats(total, last, maxima=()):
+    """The statistics of one more call (a *_stats dict) into those of a scan made of several: every key summed, the keys of
+    `maxima` the largest seen."""
+    for key, value in last.items():
+        total[key] = max(total[key], value) if key in maxima else total[key] + value
+
+
+def vectors_or_items(queries):
+    """The queries of a label scan that are no QueryBatch, under the keyword AnnoyIndex takes them by: ("Q", fp64 vectors
+    [nq, dim]) for a 2-d array, else ("items", int32 INTERNAL ids [nq])."""
+    if isinstance(queries, np.ndarray) and queries.ndim == 2:
+        return "Q", np.ascontiguousarray(queries, dtype=np.float64)
+    return "items", np.array(list(queries), np.int32).reshape(-1)
+
+
+def chunked_call(call, nq, step, outs):
+    """call(q0, q1) for the queries [q0, q1) of every chunk of `step`, in order; what it returns, one array per entry of
+    `outs`, is stored to their rows [q0, q1)."""
+    for q0 in range(0, nq, step):
+        q1 = min(q0 + step, nq)
+        for out, part in zip(outs, call(q0, q1)):
+            out[q0:q1] = part
+
+
 class SearchClusters(object):
     """MornaSearch.cluster_samples: groups [(label, [EXTERNAL ids])] with the members in ascending internal id; per cluster
     sizes, means (mean member distance, None when empty) and centres (EXTERNAL id of the member nearest its centroid, None
@@ -835,11 +859,18 @@ class MornaSearch(object):
             self._vocab_arrays = pack_vocab(self.sample_frequencies)
         return self._vocab_arrays
 
-    def _check_batch_possible(self):
+    def _device_index(self, shards_refusal=None):
+        """What every batch call asks first: RuntimeError with one process per shard (torchrun); with shards_refusal, that
+        ValueError on any other index of row shards."""
         from .shards import DistShards
         if isinstance(self.annoy_index, DistShards):
             raise RuntimeError("batch search is not available with one process per shard (torchrun): "
                                "run it in one process, which loads every shard of the index")
+        if shards_refusal is not None and not isinstance(self.annoy_index, AnnoyIndex):
+            raise ValueError(shards_refusal)
+
+    def _check_batch_possible(self):
+        self._device_index()
         if self.sample_count <= 0:
             raise ValueError("the index's sample count must be positive (got %d)" % self.sample_count)
 
@@ -882,23 +913,27 @@ class MornaSearch(object):
             self._inverse = inv
         return self._inverse
 
-    def _batch_results(self, ids, d, cnt, include_distances, meta_db):
-        """One result per query, shaped as search_nn / exact_search_nn return it; for an exact query the reference raises
-        on (count -1), a ValueError instance."""
+    def _result_rows(self, lists, counts, include_distances, meta_db):
+        """One result per (ids, distances) list, shaped as search_nn / exact_search_nn return it; where the count is negative
+        (an exact query the reference raises on) a ValueError instance."""
         inv = self._inverse_map() if meta_db else None
         out = []
-        for q in range(len(cnt)):
-            m = int(cnt[q])
-            if m < 0:
+        for (ids, d), m in zip(lists, counts):
+            if int(m) < 0:
                 out.append(ValueError("math domain error"))
                 continue
-            results = ([int(x) for x in ids[q, :m]],)
+            results = ([int(x) for x in ids],)
             if include_distances:
-                results += ([float(x) for x in d[q, :m]],)
+                results += ([float(x) for x in d],)
             if meta_db:
                 results += (lookup_meta(self.basename, [inv.get(i) for i in results[0]]),)
             out.append(results)
         return out
+
+    def _batch_results(self, ids, d, cnt, include_distances, meta_db):
+        """_result_rows for the padded arrays of the *_batch searches: row q holds cnt[q] results."""
+        return self._result_rows([(ids[q, :max(int(m), 0)], d[q, :max(int(m), 0)]) for q, m in enumerate(cnt)], cnt, include_distances,
+                                 meta_db)
 
     # ---- restricted search (DESIGN.md 8, N10) -------------------------------------------------------------------
     def restriction(self, within=None, without=None, groups=None):
@@ -980,22 +1015,10 @@ class MornaSearch(object):
             raise ValueError(RADIUS_SHARDS_REFUSAL)
 
     def _radius_results(self, lists, counts, include_distances, meta_db, num_neighbors):
-        """_batch_results for the variable-length lists of AnnoyIndex.exact_radius, cut to num_neighbors when given."""
-        inv = self._inverse_map() if meta_db else None
-        out = []
-        for (ids, d), m in zip(lists, counts):
-            if int(m) < 0:
-                out.append(ValueError("math domain error"))
-                continue
-            if num_neighbors is not None:
-                ids, d = ids[:num_neighbors], d[:num_neighbors]
-            results = ([int(x) for x in ids],)
-            if include_distances:
-                results += ([float(x) for x in d],)
-            if meta_db:
-                results += (lookup_meta(self.basename, [inv.get(i) for i in results[0]]),)
-            out.append(results)
-        return out
+        """_result_rows for the variable-length lists of AnnoyIndex.exact_radius, cut to num_neighbors when given."""
+        if num_neighbors is not None:
+            lists = [(ids[:num_neighbors], d[:num_neighbors]) for ids, d in lists]
+        return self._result_rows(lists, counts, include_distances, meta_db)
 
     def exact_radius_nn(self, radius, num_neighbors=None, include_distances=True, meta_db=False, restriction=None):
         """exact_search_nn's list for query_sample with as many results as the index has samples, cut after the last one
@@ -1068,12 +1091,7 @@ class MornaSearch(object):
         GPU (AnnoyIndex.kmeans), bit-reproducible.  The first centroids are the rows of init_ids (EXTERNAL ids, distinct; k is
         then their number) or of cluster_seed_items(eligible, k, seed).  restriction: a SearchRestriction made without groups;
         only its allowed samples are partitioned.  Returns a SearchClusters."""
-        from .shards import DistShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        if not isinstance(self.annoy_index, AnnoyIndex):
-            raise ValueError(CLUSTER_SHARDS_REFUSAL)
+        self._device_index(CLUSTER_SHARDS_REFUSAL)
         self._check_restriction(restriction, None)
         if restriction is not None and restriction.item_group is not None:
             raise ValueError("cluster takes a restriction without groups (within / without only)")
@@ -1116,12 +1134,7 @@ class MornaSearch(object):
         one index (AnnoyIndex.recall_sweep).  queries: a QueryBatch (queries_from_intropolis) or a list of
         INTERNAL ids.  trees / search_ks: strictly ascending positive integers, at most 64 each, trees at most the index's
         tree count; num_neighbors at most 256.  Returns a SearchRecall."""
-        from .shards import DistShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        if not isinstance(self.annoy_index, AnnoyIndex):
-            raise ValueError(TREES_SHARDS_REFUSAL)
+        self._device_index(TREES_SHARDS_REFUSAL)
         trees, search_ks = [int(t) for t in trees], [int(s) for s in search_ks]
         if isinstance(queries, QueryBatch):
             self._check_batch(queries)
@@ -1129,6 +1142,15 @@ class MornaSearch(object):
         else:
             out = self.annoy_index.recall_sweep(num_neighbors, trees, search_ks, items=np.array(list(queries), np.int32))
         return SearchRecall(trees, search_ks, out)
+
+    def _group_labels(self, groups, maximum, refusal):
+        """(names, item_label int32 [n_items], n_labels) of `groups`, [(label, [EXTERNAL ids])]: 1 to `maximum` labels, else
+        ValueError(refusal(their number)); an id in two labels or outside the index is restriction_arrays' ValueError."""
+        groups = list(groups)
+        if not 1 <= len(groups) <= maximum:
+            raise ValueError(refusal(len(groups)))
+        _, item_label, n_labels = restriction_arrays(self.internal_id_map, self.annoy_index.get_n_items(), groups=groups)
+        return [label for label, _ in groups], item_label, n_labels
 
     def label_separation(self, queries, groups, restriction=None, query_groups=None):
         """For every query and every label of `groups` the sum of the angular distances, in the hashed space, to the samples
@@ -1139,51 +1161,31 @@ class MornaSearch(object):
         outside the index is restriction_arrays' ValueError.  restriction / query_groups: as the *_batch searches; a by-item
         query under a restriction with groups carries its own sample's group unless query_groups says otherwise.  Returns a
         SearchLabels."""
-        from .shards import DistShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        if not isinstance(self.annoy_index, AnnoyIndex):
-            raise ValueError(LABELS_SHARDS_REFUSAL)
-        groups = list(groups)
-        if not 1 <= len(groups) <= LABELS_MAX:
-            raise ValueError(labels_max_refusal(len(groups)))
-        n = self.annoy_index.get_n_items()
-        _, item_label, n_labels = restriction_arrays(self.internal_id_map, n, groups=groups)
-        names = [label for label, _ in groups]
+        self._device_index(LABELS_SHARDS_REFUSAL)
+        names, item_label, n_labels = self._group_labels(groups, LABELS_MAX, labels_max_refusal)
         self._check_restriction(restriction, query_groups)
         handle = restriction.handle if restriction is not None else None
-        stats = dict(scan_ms=0.0, sums_ms=0.0, queries=0, batches=0, counted=0, scan_eps=0.0)
+        stats = {name: kind() for name, kind in LABEL_SUMS_STATS}
 
-        def add_stats():
-            last = self.annoy_index.label_sums_stats()
-            for key in ("scan_ms", "sums_ms", "queries", "batches", "counted"):
-                stats[key] += last[key]
-            stats["scan_eps"] = max(stats["scan_eps"], last["scan_eps"])
+        def scan(**source):
+            out = self.annoy_index.label_sums(item_label, n_labels, restriction=handle, **source)
+            accumulate_stats(stats, self.annoy_index.label_sums_stats(), maxima=("scan_eps",))
+            return out
         if isinstance(queries, QueryBatch):
             self._check_batch(queries)
-            sums, counts = self.annoy_index.label_sums(item_label, n_labels, restriction=handle, query_groups=query_groups)
-            add_stats()
+            sums, counts = scan(query_groups=query_groups)
             return SearchLabels(names, item_label, sums, counts, None, stats)
-        by_vector = isinstance(queries, np.ndarray) and queries.ndim == 2
-        if by_vector:
-            queries = np.ascontiguousarray(queries, dtype=np.float64)
-        else:
-            queries = np.array(list(queries), np.int32).reshape(-1)
-            if restriction is not None and query_groups is None:
-                query_groups = restriction.own_groups(queries)
+        source, queries = vectors_or_items(queries)
+        if source == "items" and restriction is not None and query_groups is None:
+            query_groups = restriction.own_groups(queries)
         if query_groups is not None:
             query_groups = np.ascontiguousarray(query_groups, dtype=np.int32)
         nq = len(queries)
         sums, counts = np.zeros((nq, n_labels), np.uint64), np.zeros((nq, n_labels), np.int32)
         step = max(1024, LABELS_CALL_CELLS // n_labels)        # queries of one call: its outputs stay modest
-        for q0 in range(0, nq, step):
-            part = queries[q0:q0 + step]
-            sums[q0:q0 + step], counts[q0:q0 + step] = self.annoy_index.label_sums(
-                item_label, n_labels, Q=part if by_vector else None, items=None if by_vector else part, restriction=handle,
-                query_groups=None if query_groups is None else query_groups[q0:q0 + step])
-            add_stats()
-        return SearchLabels(names, item_label, sums, counts, None if by_vector else item_label[queries], stats)
+        chunked_call(lambda q0, q1: scan(query_groups=None if query_groups is None else query_groups[q0:q1],
+                                         **{source: queries[q0:q1]}), nq, step, (sums, counts))
+        return SearchLabels(names, item_label, sums, counts, item_label[queries] if source == "items" else None, stats)
 
     def label_mixture(self, queries, groups, restriction=None, tol=1e-9, max_sweeps=10000):
         """Every query as a non-negative combination of the centroids of the labels of `groups`, fitted on the GPU
@@ -1191,48 +1193,27 @@ class MornaSearch(object):
         or a list of INTERNAL ids -- such a query is left out of its own label's centroid.  groups: [(label, [EXTERNAL ids])]
         as parse_groups_file returns it, at most 128 labels; an id in two labels or outside the index is restriction_arrays'
         ValueError.  restriction: an allow-list only (the library refuses one made with groups).  Returns a SearchMixture."""
-        from .shards import DistShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        if not isinstance(self.annoy_index, AnnoyIndex):
-            raise ValueError(MIXTURE_SHARDS_REFUSAL)
-        groups = list(groups)
-        if not 1 <= len(groups) <= MIXTURE_LABELS_MAX:
-            raise ValueError(mixture_max_refusal(len(groups)))
-        n = self.annoy_index.get_n_items()
-        _, item_label, n_labels = restriction_arrays(self.internal_id_map, n, groups=groups)
-        names = [label for label, _ in groups]
+        self._device_index(MIXTURE_SHARDS_REFUSAL)
+        names, item_label, n_labels = self._group_labels(groups, MIXTURE_LABELS_MAX, mixture_max_refusal)
         self._check_restriction(restriction, None)
         handle = restriction.handle if restriction is not None else None
-        stats = dict(centroids_ms=0.0, gram_ms=0.0, dots_ms=0.0, solve_ms=0.0, queries=0, sweeps=0, max_sweeps=0, open=0)
+        stats = {name: kind() for name, kind in MIXTURE_STATS}
 
-        def add_stats():
-            last = self.annoy_index.mixture_stats()
-            for key in ("centroids_ms", "gram_ms", "dots_ms", "solve_ms", "queries", "sweeps", "open"):
-                stats[key] += last[key]
-            stats["max_sweeps"] = max(stats["max_sweeps"], last["max_sweeps"])
+        def fit(**source):
+            out = self.annoy_index.mixture(item_label, n_labels, restriction=handle, tol=tol, max_sweeps=max_sweeps, **source)
+            accumulate_stats(stats, self.annoy_index.mixture_stats(), maxima=("max_sweeps",))
+            return out
         if isinstance(queries, QueryBatch):
             self._check_batch(queries)
-            weights, info, active = self.annoy_index.mixture(item_label, n_labels, restriction=handle, tol=tol, max_sweeps=max_sweeps)
-            add_stats()
+            weights, info, active = fit()
             return SearchMixture(names, item_label, weights, info, active, None, stats)
-        by_vector = isinstance(queries, np.ndarray) and queries.ndim == 2
-        if by_vector:
-            queries = np.ascontiguousarray(queries, dtype=np.float64)
-        else:
-            queries = np.array(list(queries), np.int32).reshape(-1)
+        source, queries = vectors_or_items(queries)
         nq = len(queries)
         weights, info = np.zeros((nq, n_labels), np.float64), np.zeros((nq, 4), np.float64)
         active = np.zeros((nq, n_labels), bool)
         step = max(1024, MIXTURE_CALL_CELLS // n_labels)       # queries of one call: its outputs stay modest
-        for q0 in range(0, nq, step):
-            part = queries[q0:q0 + step]
-            weights[q0:q0 + step], info[q0:q0 + step], active[q0:q0 + step] = self.annoy_index.mixture(
-                item_label, n_labels, Q=part if by_vector else None, items=None if by_vector else part, restriction=handle,
-                tol=tol, max_sweeps=max_sweeps)
-            add_stats()
-        return SearchMixture(names, item_label, weights, info, active, None if by_vector else item_label[queries], stats)
+        chunked_call(lambda q0, q1: fit(**{source: queries[q0:q1]}), nq, step, (weights, info, active))
+        return SearchMixture(names, item_label, weights, info, active, item_label[queries] if source == "items" else None, stats)
 
     def hashing_sweep(self, query_ids, num_neighbors, dims, junction_file, n_trees=None, search_k=None):
         """What every width of `dims` costs in neighbours and in norm distortion, from this one index.
@@ -1286,18 +1267,8 @@ class MornaSearch(object):
         before any search, with search_member_n's message.  Returns (internal ids, list of result tuples).  restriction:
         MornaSearch.restriction; query_groups None under a restriction with groups: every query carries its own sample's
         group."""
-        from .shards import DistShards
-        if isinstance(self.annoy_index, DistShards):
-            raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                               "run it in one process, which loads every shard of the index")
-        internal = []
-        for query_id in query_ids:
-            if query_id not in self.internal_id_map:
-                raise ValueError("Querying sample id " + str(query_id)
-                                 + " is not possible because no internal id is mapped to that "
-                                 + "sample id. Likely no sample with that id was included "
-                                 + "in the index.")
-            internal.append(self.internal_id_map[query_id])
+        self._device_index()
+        internal = self._internal_ids(query_ids)
         self._check_restriction(restriction, query_groups)
         self._check_trees(n_trees, restriction)
         if n_trees is not None:
@@ -1319,10 +1290,7 @@ class MornaSearch(object):
         """<basename>.junc.mor, loaded on first use."""
         if self._junction_store is None:
             from .junctions import STORE_SUFFIX, JunctionStore
-            from .shards import DistShards
-            if isinstance(self.annoy_index, DistShards):
-                raise RuntimeError("batch search is not available with one process per shard (torchrun): "
-                                   "run it in one process, which loads every shard of the index")
+            self._device_index()
             path = self.basename + STORE_SUFFIX
             if not os.path.exists(path):
                 raise IOError("%s not found: this index has no junction store; build it with `morna index "
@@ -1494,12 +1462,7 @@ class MornaSearch(object):
     def unhashed_search_member_n_batch(self, query_ids, num_neighbors, include_distances=True, meta_db=False, restriction=None):
         """The unhashed neighbours of several indexed sample ids: a list of result tuples in query order, as
         exact_search_nn_batch returns them (internal ids); an unknown id fails with search_member_n's message."""
-        for query_id in query_ids:
-            if query_id not in self.internal_id_map:
-                raise ValueError("Querying sample id " + str(query_id)
-                                 + " is not possible because no internal id is mapped to that "
-                                 + "sample id. Likely no sample with that id was included "
-                                 + "in the index.")
+        self._internal_ids(query_ids)
         store, _ = self.unhashed_store()
         ids, d, cnt = store.nearest_by_sample(self._unhashed_population_of(restriction), [int(q) for q in query_ids], num_neighbors)
         ids = self._unhashed_ids(ids, restriction)
@@ -1530,13 +1493,7 @@ class MornaSearch(object):
         """Neighbours of an indexed sample (morna.py:733-787); n_trees: as search_nn."""
         self._check_trees(n_trees)
         print("querying by sample id " + str(query_id))
-        try:
-            internal_id = self.internal_id_map[query_id]
-        except KeyError:
-            raise ValueError("Querying sample id " + str(query_id)
-                             + " is not possible because no internal id is mapped to that "
-                             + "sample id. Likely no sample with that id was included "
-                             + "in the index.")
+        internal_id = self._internal_ids([query_id])[0]
         print("this is internal id " + str(internal_id))
         if n_trees is not None:
             results = self.annoy_index.get_nns_by_item(internal_id, num_neighbors, search_k, include_distances, n_trees=n_trees)
