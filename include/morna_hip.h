@@ -180,8 +180,9 @@ int morna_exact_search_query_rows(morna_index *h, int32_t k, int32_t *ids_out, d
  *                             (MORNA_E_INVALID when the lines kept are not the lines read: kept line j must be file line j).
  *                             Deterministic: a stable counting sort without global atomics, the same bytes on every run, a
  *                             sample's lines ascending whatever order a line lists its samples in.  A line that lists a
- *                             sample twice is MORNA_E_INVALID naming the line and the sample.  The store is resident in
- *                             HBM and mirrored on the host (what save writes).
+ *                             sample twice is MORNA_E_INVALID naming the line and the sample: the first such line of the
+ *                             file and, of the samples it repeats, the one first seen in the file, whatever the number
+ *                             of samples.  The store is resident in HBM and mirrored on the host (what save writes).
  *   morna_jstore_from_arrays  a store from the caller's arrays: ext_ids[n_samples], ptr[n_samples + 1], line / cov
  *                             [ptr[n_samples]].  Validated as load validates (MORNA_E_INVALID).  No GPU work: the arrays
  *                             go to `device` at the first retain.

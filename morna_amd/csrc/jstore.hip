@@ -950,18 +950,21 @@ int build_impl(morna_jstore *st, const morna_lines *L)
     if (per > INT32_MAX) per = INT32_MAX;
     const int64_t n_blocks = (J + per - 1) / per;
     const bool dup_on_device = (S + 31) / 32 <= JS_BITMAP_WORDS;
-    if (!dup_on_device) {   // more samples than the LDS bitmap holds: the same check on the host
-        std::vector<int32_t> last((size_t)S, -1);
-        for (int64_t l = 0; l < J; l++)
+    if (!dup_on_device) {   // more samples than the LDS bitmap holds: the same check on the host, with the kernel's answer --
+        std::vector<int32_t> last((size_t)S, -1);   // of the first line that repeats a sample, the smallest sample it repeats
+        for (int64_t l = 0; l < J; l++) {
+            int32_t repeated = -1;
             for (int64_t e = row_ptr[l]; e < row_ptr[l + 1]; e++) {
                 const int32_t s = ids[e];
                 if (s < 0 || s >= S) continue;   // (reported by the count kernel)
-                if (last[(size_t)s] == (int32_t)l) {
-                    set_error("jstore_build: line %lld lists sample %lld twice", (long long)l, (long long)ext[s]);
-                    return MORNA_E_INVALID;
-                }
+                if (last[(size_t)s] == (int32_t)l && (repeated < 0 || s < repeated)) repeated = s;
                 last[(size_t)s] = (int32_t)l;
             }
+            if (repeated >= 0) {
+                set_error("jstore_build: line %lld lists sample %lld twice", (long long)l, (long long)ext[repeated]);
+                return MORNA_E_INVALID;
+            }
+        }
     }
     DevBuf<int64_t> d_row_ptr, d_total;
     DevBuf<int32_t> d_ids, d_covin, d_cnt;

@@ -620,7 +620,7 @@ class JunctionStore(object):
                 p = [C.c_void_p() for _ in range(4)]
                 check(lib().morna_jretained_query(r, q, *[C.byref(x) for x in p]))
                 cov_ptr = view(p[2], C.c_int64, n + 1)
-                lo, hi = (int(cov_ptr[0]), int(cov_ptr[-1])) if n else (0, 0)
+                lo, hi = int(cov_ptr[0]), int(cov_ptr[-1])     # (an empty list: one offset, its place in the flat array)
                 cov = view(C.c_void_p(p[3].value + 4 * lo) if p[3].value else p[3], C.c_int32, hi - lo)
                 out.append(Retained(view(p[0], C.c_int32, n), view(p[1], C.c_uint64, n), cov_ptr - lo, cov))
             return out

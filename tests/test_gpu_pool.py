@@ -1,7 +1,8 @@
 """Pooled samples on the GPU: `JunctionStore.pool` against its numpy restatement (test_pool_cpu.ref_pool)
 entry for entry on synthetic stores at the tile edges and with groups at the edges of a round of 64 members; and the
 command line -- `supersample` files against the restatement of create_supersample.py byte for byte, `search --supersamples`
-blocks against those `search --intropolis` prints for a file that holds the same sums.  Integers and whole text.  -m gpu"""
+blocks against those `search --intropolis` prints for a file that holds the same sums.  Integers and whole text.  -m gpu
+Stores of more than 64 tiles, where rounds of 64 members meet rounds of 64 tiles: test_gpu_jstore_many_tiles.py."""
 import gzip
 
 import numpy as np

@@ -1,6 +1,7 @@
 """`morna recovery` on the GPU: the library's histogram against its numpy restatement (test_recovery_cpu.ref_hist), entry
 for entry; every cell of a grid against the shipped filter (`retain`); and whole tables of the command line against the
-restatement fed the result lists the search itself printed.  Integers and whole text only, no tolerance.  -m gpu"""
+restatement fed the result lists the search itself printed.  Integers and whole text only, no tolerance.  -m gpu
+Stores of more than 64 tiles, where the tile scan takes a second round: test_gpu_jstore_many_tiles.py."""
 import gzip
 
 import numpy as np
