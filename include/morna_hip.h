@@ -747,6 +747,76 @@ int morna_mixture(morna_index *h, const morna_restriction *r /* or NULL */, cons
 int morna_mixture_stats(const morna_index *h, double *stats /* [8] */);
 
 /*
+ * ---- principal axes (no counterpart in the reference, whose README asks whether "a sample's global
+ * expression patterns are similar to those of samples from the same tissue") ------------------------------------------------
+ * The leading principal axes of the unit-scaled stored rows by a deterministic block power iteration, and the coordinates of
+ * any row or query on them, bit-reproducible against a CPU restatement (tests/pca_ref.py).
+ *   Arithmetic: fp64, one rounding per operation (+, -, *, /, sqrt correctly rounded), no fused multiply-add.
+ *   BS, the blocked ascending sum, is the one summation rule of this contract.  BS of terms t_0 .. t_{n-1}: for every block
+ *     B = 0, 1, .. of 256 consecutive indices [256 B, 256 B + 256), P_B = the terms of the block added one by one in ascending
+ *     index to 0.0; BS = the P_B added one by one in ascending B to 0.0.  The index is the column z for a sum over columns and
+ *     the item id i for a sum over rows.  A row that is left out of a sum over rows adds no term to its block and moves no
+ *     block edge; a block without a term has P_B = 0.0 and is still added.
+ *   Rows: pp_i, s_i and the skip rule not (0 < pp_i < inf) exactly as morna_kmeans defines them.  u_i[z] = (double) x_i[z] * s_i.
+ *     The fitted set F: the rows that are eligible and not skipped; eligible is every row, or the allowed rows of a
+ *     restriction r that holds an allow-list only (one that holds groups: MORNA_E_INVALID).  m = |F|; m < 2: MORNA_E_INVALID.
+ *   Mean: mu[z] = BS_{i in F}(u_i[z]) / (double) m with center != 0; with center == 0, mu[z] = 0.0 and every formula below is
+ *     used unchanged.
+ *   Widths: p components, 1 <= p <= MORNA_PCA_MAX_COMPONENTS; extra >= 0; b = p + extra columns are iterated,
+ *     b <= MORNA_PCA_MAX_BLOCK and b <= min(dim, m - 1).  Beyond either: MORNA_E_INVALID naming the limit.
+ *   Start: G[z][j] = (double) (mix(seed * 0x9E3779B97F4A7C15 + 64 z + j) >> 11) * 2^-53 - 0.5 for z < dim, j < b, in
+ *     unsigned 64-bit arithmetic modulo 2^64; mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *     x *= 0x94D049BB133111EB; x ^= x >> 31.  Q = Orth(G).
+ *   Orth(A), A[dim][b] -> Q[dim][b], columns j = 0 .. b - 1 in turn, a = column j of A: twice { r_k = BS_z(q_k[z] * a[z]) for
+ *     every k < j, all from the same a; then for k = 0 .. j - 1 in turn and every z, a[z] = a[z] - r_k * q_k[z] }.  Then
+ *     nn = BS_z(a[z] * a[z]); not (0 < nn < inf) ends the call with MORNA_E_INVALID naming column j ("fewer than b independent
+ *     directions"); otherwise q_j[z] = a[z] / sqrt(nn) (one sqrt, then one division per element).
+ *   Iteration t = 1 .. max_iter (>= 1):
+ *     c_j = BS_z(mu[z] * Q[z][j]);  T[i][j] = BS_z(u_i[z] * Q[z][j]) - c_j for i in F;  S_j = BS_{i in F}(T[i][j]);
+ *     Y[z][j] = BS_{i in F}(u_i[z] * T[i][j]);  Z[z][j] = (Y[z][j] - mu[z] * S_j) / (double) m;
+ *     B_jk = BS_z(Q[z][j] * Z[z][k]) for j <= k, B_kj := B_jk.
+ *     theta, W = Eig(B) (below).
+ *     If t >= 2 and max over j < p of |theta_j(t) - theta_j(t-1)| <= tol * theta_0(t): stop, converged.
+ *     If t == max_iter: stop, not converged.  Otherwise Q = Orth(M), M[z][j] = the sum over k = 0 .. b - 1 ascending, from 0.0,
+ *     of Z[z][k] * W[k][j].
+ *   Eig(B), cyclic Jacobi by rows on a copy A of B with W = the identity: a sweep visits the pairs (p, q), p = 0 .. b - 2,
+ *     q = p + 1 .. b - 1, in that order.  A pair with A[p][q] == 0.0 or |A[p][q]| <= 2^-54 * (|A[p][p]| + |A[q][q]|) is passed
+ *     over.  Otherwise tau = (A[q][q] - A[p][p]) / (2.0 * A[p][q]); t = 1.0 / (|tau| + sqrt(1.0 + tau * tau)), negated when
+ *     tau < 0; c = 1.0 / sqrt(1.0 + t * t); s = t * c.  Columns first: for every k = 0 .. b - 1, with x = A[k][p] and
+ *     y = A[k][q]: A[k][p] = c * x - s * y, A[k][q] = s * x + c * y.  Then rows: for every k, with x = A[p][k] and y = A[q][k]:
+ *     A[p][k] = c * x - s * y, A[q][k] = s * x + c * y.  Then A[p][q] = A[q][p] = 0.0.  W takes the column step alone
+ *     (x = W[k][p], y = W[k][q]).  The sweeps end after the first sweep that rotated nothing, or after 64 sweeps.
+ *     theta_j = A[j][j] ordered descending, equal values in ascending j; the columns of W are ordered with them.
+ *   Result, at the iteration that stopped: V[z][j] = the sum over k ascending, from 0.0, of Q[z][k] * W[k][j], j < p; axis j is
+ *     negated when its element of largest magnitude (the lowest z among equals) is negative.  axes_out[p][dim] = V transposed,
+ *     mean_out[dim] = mu, values_out[p] = theta_j, info_out[4] = iterations t, converged (0.0 or 1.0), m,
+ *     tv = BS_{i in F}(BS_z((u_i[z] - mu[z]) * (u_i[z] - mu[z]))) / (double) m, the total variance.
+ *   tol finite and >= 0.  A non-finite theta: MORNA_E_INVALID.
+ *   morna_pca_project: queries as in morna_label_sums (q [nq][dim] fp64 in host memory, or items, or both NULL for the staged
+ *     query rows).  For a query y: pp = the sequential sum of squares in cosine_distance's order, s = 1.0 / sqrt(pp),
+ *     u[z] = y[z] * s (by item, y = the widened stored row, so u = u_i);
+ *     coords_out[q][j] = BS_z(u[z] * axes[j][z]) - BS_z(mean[z] * axes[j][z]).  A query with not (0 < pp < inf): the canonical
+ *     quiet NaN (0x7ff8000000000000) in every coordinate.  A restriction plays no part: every row can be placed.  A host query
+ *     with a non-finite element or sum of squares: MORNA_E_INVALID, as morna_exact_search; a non-finite element of axes or
+ *     mean: MORNA_E_INVALID; 1 <= p <= MORNA_PCA_MAX_COMPONENTS; an item outside the index: MORNA_E_RANGE.
+ *   Errors of both: a row-sharded handle: MORNA_E_INVALID; an empty index: MORNA_E_EMPTY.
+ *   Nothing depends on the grid, the wave or the batch: every BS is evaluated as its definition reads, partial by partial,
+ *     and no atomic is used.
+ *   morna_pca_stats  of the last morna_pca, stats[8]: ms of the T passes, of the Y passes (S and Z with them), of the
+ *     orthonormalisations (the start's included), of the small products (c, B, Z W, Q W), HIP events, summed over the
+ *     iterations; ms of Eig on the host; iterations; rows fitted m; bytes of rows read, 4 dim (n_items + m (2 + 2 iterations)):
+ *     the scales, the mean and the total variance once, T and Y per iteration.  All 0 after a call that failed.
+ */
+#define MORNA_PCA_MAX_COMPONENTS 32
+#define MORNA_PCA_MAX_BLOCK 64
+int morna_pca(morna_index *h, const morna_restriction *r /* or NULL */, int32_t p, int32_t extra, int32_t center, uint64_t seed,
+              double tol, int32_t max_iter, double *axes_out /* [p][dim] */, double *mean_out /* [dim] */,
+              double *values_out /* [p] */, double *info_out /* [4] */);
+int morna_pca_project(morna_index *h, const double *axes /* [p][dim] */, const double *mean /* [dim] */, int32_t p, const double *q,
+                      const int32_t *items, int64_t nq, double *coords_out /* [nq][p] */);
+int morna_pca_stats(const morna_index *h, double *stats /* [8] */);
+
+/*
  * ---- tree-prefix search and the (tree count, search_k) sweep (no counterpart in the reference, whose
  * tests/README.md experiment 3 builds one index per tree count and compares result files by eye) -------------------------
  * Tree i of a forest does not depend on the number of trees built with it, and node ids keep their relative order when the

@@ -137,6 +137,11 @@ SIGNATURES = {
     # handle, restriction, q, items, nq, item_label, n_labels, tol, max_sweeps, weights_out, info_out, active_out (or NULL)
     "morna_mixture": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, C.c_double, _i32, _p, _p, _p]),
     "morna_mixture_stats": (C.c_int, [_p, _p]),
+    # principal axes: handle, restriction (or NULL), p, extra, center, seed, tol, max_iter, axes_out, mean_out, values_out, info_out
+    "morna_pca": (C.c_int, [_p, _p, _i32, _i32, _i32, C.c_uint64, C.c_double, _i32, _p, _p, _p, _p]),
+    # handle, axes, mean, p, q, items, nq, coords_out
+    "morna_pca_project": (C.c_int, [_p, _p, _p, _i32, _p, _p, _i64, _p]),
+    "morna_pca_stats": (C.c_int, [_p, _p]),
     "morna_get_nns_prefix":(C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "morna_search_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "morna_recall_sweep": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),

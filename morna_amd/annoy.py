@@ -27,6 +27,8 @@ KMEANS_STATS = (("scan_ms", float), ("pick_ms", float), ("resolve_ms", float), (
                 ("iterations", int), ("largest", int))
 MIXTURE_STATS = (("centroids_ms", float), ("gram_ms", float), ("dots_ms", float), ("solve_ms", float), ("queries", int), ("sweeps", int),
                  ("max_sweeps", int), ("open", int))
+PCA_STATS = (("t_ms", float), ("y_ms", float), ("orth_ms", float), ("small_ms", float), ("eig_ms", float), ("iterations", int),
+             ("fitted", int), ("row_bytes", int))
 
 
 def pack_allow_bits(allow):
@@ -564,6 +566,39 @@ class AnnoyIndex(object):
         """Of the last label_centroids / mixture: ms of the centroid step, the Gram, the query dots and the solver; queries,
         sweeps summed, the largest sweep count, queries that did not converge (status != 1)."""
         return read_stats(lib().morna_mixture_stats, self._h, MIXTURE_STATS)
+
+    # ---- principal axes (include/morna_hip.h, "principal axes"; no counterpart in annoy) ----
+    def pca(self, p=10, extra=8, center=True, seed=0, tol=1e-9, max_iterations=500, restriction=None):
+        """The p leading principal axes of the unit-scaled stored rows (of the allowed rows under a restriction, an allow-list
+        only) by a block power iteration over p + extra columns: a dict of axes (float64 [p, f]), mean (float64 [f], zeros
+        with center=False), values (float64 [p], the variances along the axes), iterations, converged, fitted (rows that
+        took part) and total_variance."""
+        p = int(p)
+        axes = np.zeros((max(p, 0), self.f), np.float64)
+        mean = np.zeros(self.f, np.float64)
+        values = np.zeros(max(p, 0), np.float64)
+        info = np.zeros(4, np.float64)
+        check(lib().morna_pca(self._h, self._restriction_ptr(restriction), p, int(extra), 1 if center else 0, int(seed) & (2 ** 64 - 1),
+                              float(tol), int(max_iterations), ptr(axes), ptr(mean), ptr(values), ptr(info)))
+        return dict(axes=axes, mean=mean, values=values, iterations=int(info[0]), converged=bool(info[1]), fitted=int(info[2]),
+                    total_variance=float(info[3]))
+
+    def pca_project(self, axes, mean, Q=None, items=None):
+        """The coordinates (float64 [nq, p]) of the query vectors Q (fp64 [nq, f]), the stored rows `items`, or (neither) the
+        staged query rows on `axes` (fp64 [p, f]) about `mean` (fp64 [f]); NaN for a query without a direction."""
+        axes = np.ascontiguousarray(axes, dtype=np.float64)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if axes.ndim != 2 or axes.shape[1] != self.f or mean.shape != (self.f,):
+            raise IndexError("axes must be [p, %d] and mean [%d]" % (self.f, self.f))
+        Q, items, nq = self._query_source(Q, items, np.float64)
+        coords = np.zeros((nq, axes.shape[0]), np.float64)
+        check(lib().morna_pca_project(self._h, ptr(axes), ptr(mean), int(axes.shape[0]), ptr(Q), ptr(items), nq, ptr(coords)))
+        return coords
+
+    def pca_stats(self):
+        """Of the last pca: ms of the T passes, the Y passes, the orthonormalisations, the small products and the host's
+        eigen step; iterations, rows fitted, bytes of rows read."""
+        return read_stats(lib().morna_pca_stats, self._h, PCA_STATS)
 
     # ---- query rows built on the device (MornaSearch.queries_from_intropolis) ----
     def build_query_rows(self, terms):

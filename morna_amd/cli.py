@@ -1,4 +1,4 @@
-"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` / `morna mixture` / `morna explain` command line on the MI355X library.
+"""`morna index` / `morna search` / `morna junctions` / `morna recovery` / `morna supersample` / `morna recall` / `morna hashing` / `morna labels` / `morna mixture` / `morna explain` / `morna pca` command line on the MI355X library.
 
 Mirrors the reference's parser and dispatch (commanderson/morna
 morna.py:867-1054, 1338-1638): same subcommands, flag names, defaults and output
@@ -84,6 +84,13 @@ TF-IDF weight that lies outside those, and under it the --top junctions that car
 coverages, its weight and its share.  Every pair of every query in one call on the GPU, from the junction store and its
 weights; the reference has no counterpart.
 
+`pca` gives a cohort its picture: the p leading principal axes of the unit-scaled index rows, fitted on the GPU by a
+deterministic block power iteration, the share of the variance along each, and every indexed sample's
+coordinates on them -- with --labels the label beside them and the labels' mean coordinates.  --within / --without choose
+the samples the axes are fitted to; every sample is still placed.  --save-axes keeps the axes, --axes reads them back and
+places the samples of --intropolis, or a stream, on the axes of the cohort.  It has a parser of its own (build_pca_parser):
+main() hands it everything behind the word "pca".
+
 One deliberate difference in the back-off loop: when the stream ends without
 convergence the reference's quiet branch prints the results of the LAST CHECKPOINT
 (morna.py:1452, a NameError if no checkpoint was reached) while its verbose branch
@@ -117,6 +124,8 @@ here do the latter.
     python -m morna_amd.cli pairs -x idx --max-distance 0.05 --leave-out-groups donors.tsv --clusters
     python -m morna_amd.cli explain -x idx --junction-file junctions.tsv.gz --query-ids 17,42 -r 20 --top 10
     python -m morna_amd.cli explain -x idx --junction-file junctions.tsv.gz -q 17 --against 42,1234 --summary-only
+    python -m morna_amd.cli pca -x idx -p 10 --labels tissues.tsv --save-axes cohort.npz -o coords.tsv
+    python -m morna_amd.cli pca -x idx --axes cohort.npz --intropolis new_samples.tsv.gz --summary-only
 """
 import argparse
 import sys
@@ -487,6 +496,45 @@ def build_parser():
     return parser
 
 
+def build_pca_parser():
+    """The parser of `morna pca`, a command with a parser of its own: main() hands it everything behind the word "pca"."""
+    parser = argparse.ArgumentParser(prog='morna pca',
+                                     description='principal axes of the indexed samples in the hashed space, fitted on the GPU, and '
+                                                 'every sample\'s coordinates on them: the picture of a cohort')
+    _add_flags(parser, basename=_UNSHARDED_HELP)
+    parser.add_argument('-p', '--components', metavar='<int>', type=int, required=False, default=10, action=_StoreGiven,
+                        help='the number of axes, 1 to 32 (default 10)')
+    parser.add_argument('--extra', metavar='<int>', type=int, required=False, default=8, action=_StoreGiven,
+                        help='columns iterated beside the axes: more of them, fewer iterations; -p and --extra together at most '
+                             '64 (default 8)')
+    parser.add_argument('--no-center', action='store_const', const=True, default=False,
+                        help='do not subtract the mean sample: axes of the second moments about the origin')
+    parser.add_argument('--seed', metavar='<int>', type=int, required=False, default=0, action=_StoreGiven,
+                        help='the seed of the first block of columns (default 0); the same seed gives the same bytes')
+    parser.add_argument('--tolerance', metavar='<float>', type=float, required=False, default=1e-9, action=_StoreGiven,
+                        help='stop when no variance changed by more than this share of the largest (default 1e-9)')
+    parser.add_argument('--max-iterations', metavar='<int>', type=int, required=False, default=500, action=_StoreGiven,
+                        help='the iterations the fit may take (default 500)')
+    _add_flags(parser, within='fit the axes to the samples this file lists only, one integer sample id per line (every sample is '
+                              'still placed)',
+               without='leave the samples this file lists out of the fit, one integer sample id per line')
+    parser.add_argument('--labels', metavar='<file>', type=str, required=False, default=None,
+                        help='a groups file, "<label><TAB><id>,<id>,..." per line: every sample\'s line carries its label, and a '
+                             'block of per-label mean coordinates follows')
+    _add_sources(parser, 'intropolis')
+    parser.add_argument('-f', '--format', metavar='<choice>', type=str, required=False, default=None,
+                        help='one of {sam, bed, raw}: place the query read from stdin in this format, featurised as `search` does')
+    parser.add_argument('--save-axes', metavar='<file>', type=str, required=False, default=None,
+                        help='write mean, axes, variances and the fit\'s figures to this .npz file')
+    parser.add_argument('--axes', metavar='<file>', type=str, required=False, default=None,
+                        help='read the axes from this file of --save-axes and fit nothing: only place samples and queries')
+    parser.add_argument('-o', '--output', metavar='<file>', type=str, required=False, default=None,
+                        help='write the line of every indexed sample to this file and not to stdout')
+    _add_flags(parser, summary_only='print no line per indexed sample',
+               metadata='append the metadata keywords of every sample', device=_DEVICE_HELP)
+    return parser
+
+
 # ---- the pieces the flag checks share: argparse errors, before any index is read -----------------------------------------------
 _SOURCE_FLAGS = dict(query_id="-q/--query-id", query_ids="--query-ids", sample="--sample", all_items="--all", intropolis="--intropolis")
 _ONE_PROCESS_REFUSAL = ("batch search is not available with one process per shard (torchrun): "
@@ -676,6 +724,41 @@ def _check_cluster_flags(parser, args):
         parser.error("-k takes 1 to %d groups (got %d)" % (LABELS_MAX, args.clusters))
     _check_within_without(parser, args)
     _refuse_shards(parser, args, CLUSTER_SHARDS_REFUSAL)
+
+
+def _check_pca_flags(parser, args):
+    """`pca`: the numbers of the fit, what --axes leaves no room for, one query source at most, the files read.  Leaves the
+    labels in args.label_groups (None without --labels) and the restriction's parts where _check_restriction_flags leaves
+    them."""
+    from .junctions import parse_groups_file
+    from .search import PCA_MAX_BLOCK, PCA_MAX_COMPONENTS, PCA_SHARDS_REFUSAL, pca_width_refusal
+    fit_flags = (("-p/--components", _given(args, "components")), ("--extra", _given(args, "extra")), ("--no-center", args.no_center),
+                 ("--seed", _given(args, "seed")), ("--tolerance", _given(args, "tolerance")),
+                 ("--max-iterations", _given(args, "max_iterations")), ("--within", args.within is not None),
+                 ("--without", args.without is not None), ("--save-axes", args.save_axes is not None))
+    if args.axes is not None:
+        _refuse(parser, "--axes cannot be used with %s: the axes are read from the file and nothing is fitted", fit_flags)
+    if not 1 <= args.components <= PCA_MAX_COMPONENTS or args.extra < 0 or args.components + args.extra > PCA_MAX_BLOCK:
+        parser.error(pca_width_refusal(args.components, args.extra))
+    if args.seed < 0:
+        parser.error("--seed takes a number >= 0 (got %d)" % args.seed)
+    if not (args.tolerance >= 0.0) or args.tolerance == float("inf"):
+        parser.error("--tolerance takes a finite number >= 0 (got %r)" % args.tolerance)
+    if args.max_iterations < 1:
+        parser.error("--max-iterations takes a positive number (got %d)" % args.max_iterations)
+    if args.format is not None and args.format not in ("sam", "bed", "raw"):
+        parser.error("-f takes one of sam, bed, raw (got %r)" % args.format)
+    if args.format is not None and args.intropolis is not None:
+        parser.error("pca takes one query source: --intropolis or a stream on stdin with -f (got both)")
+    if args.summary_only and args.output is not None:
+        parser.error("--summary-only and -o cannot be used together: -o takes the lines --summary-only leaves out")
+    args.query_id = args.query_ids = args.leave_out_groups = None
+    args.label_groups = _read_file(parser, parse_groups_file, args.labels)
+    if args.labels is not None and not args.label_groups:
+        parser.error("--labels %s names no label" % args.labels)
+    _read_restriction(parser, args, groups=False)
+    _check_within_without(parser, args)
+    _refuse_shards(parser, args, PCA_SHARDS_REFUSAL)
 
 
 def _check_downsample_flags(parser, args):
@@ -1432,6 +1515,58 @@ def _cluster(args, stdin, stdout):
     return 0
 
 
+def _pca(args, stdin, stdout):
+    """`pca`: the axes fitted on the GPU (or read with --axes); the header, a line per component, a line per indexed sample,
+    with --labels the block of label means, and a line per query."""
+    import numpy as np
+    from .metadb import lookup_meta
+    from .search import (PCA_SHARDS_REFUSAL, format_pca_label_means, format_pca_row, load_pca_axes, pca_label_means,
+                         restriction_arrays, save_pca_axes)
+    searcher = _open_single(args, PCA_SHARDS_REFUSAL)
+    n, dim = searcher.annoy_index.get_n_items(), searcher.annoy_index.f
+    names = item_label = None
+    if args.label_groups is not None:
+        names = [label for label, _ in args.label_groups]
+        _, item_label, _ = restriction_arrays(searcher.internal_id_map, n, groups=args.label_groups)
+    if args.axes is not None:
+        pca = load_pca_axes(args.axes, dim)
+    else:
+        args.restriction = _make_restriction(args, searcher)
+        pca = searcher.principal_axes(args.components, extra=args.extra, center=not args.no_center, seed=args.seed,
+                                      tol=args.tolerance, max_iterations=args.max_iterations, restriction=args.restriction)
+    if args.save_axes is not None:
+        save_pca_axes(args.save_axes, pca, dim)
+    stdout.write(pca.header())
+    stdout.write(pca.components())
+    if not args.summary_only or names is not None:
+        searcher.pca_samples(pca)
+    if not args.summary_only:
+        labels = meta = None
+        if names is not None:
+            labels = dict((sample_id, names[l]) for sample_id, l in zip(pca.samples, item_label.tolist()) if l >= 0)
+        if args.metadata:
+            meta = dict((i, str(m)) for i, m in zip(pca.samples, lookup_meta(args.basename, pca.samples)))
+        lines = pca.sample_lines(labels, meta)
+        if args.output is not None:
+            with open(args.output, "w") as fh:
+                fh.write(lines)
+        else:
+            stdout.write(lines)
+    if names is not None:
+        stdout.write(format_pca_label_means(pca_label_means(names, item_label, pca.coords)))
+    queries = ids = None
+    if args.intropolis is not None:
+        queries = searcher.queries_from_intropolis(args.intropolis)
+        ids = queries.ext_ids
+    elif args.format is not None:                              # a stream: one query, as `search` makes it
+        _hash_stream(searcher, _stream_parser(args.format)(stdin))
+        queries, ids = np.array([searcher.query_sample], dtype=np.float64), ["stdin"]
+    if queries is not None:
+        for query_id, row in zip(ids, searcher.pca_coordinates(pca, queries).tolist()):
+            stdout.write(format_pca_row("# query %s" % query_id, row))
+    return 0
+
+
 def _junctions(args, searcher, stdin, stdout):
     """morna.py:1351-1353, 1486-1638: the search, printed as `search` prints it, then the junctions of every query's
     results filtered on the GPU in one call and written in one pass over --junction-file."""
@@ -1799,6 +1934,12 @@ _COMMANDS = {
 
 
 def main(argv=None, stdin=None, stdout=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv[:1] == ['pca']:                                    # (a parser of its own: build_parser() stays as it is pinned)
+        parser = build_pca_parser()
+        args = parser.parse_args(argv[1:])
+        _check_pca_flags(parser, args)
+        return _pca(args, stdin or sys.stdin, stdout or sys.stdout)
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.subparser_name is None:

@@ -1152,6 +1152,47 @@ int morna_mixture_stats(const morna_index *h, double *stats)
     return read_stats(h, &morna_index::mixture_stats, stats, __func__);
 }
 
+// ---- principal axes (the contract is in morna_hip.h) -----------------------------------------------------------------
+
+int morna_pca(morna_index *h, const morna_restriction *r, int32_t p, int32_t extra, int32_t center, uint64_t seed, double tol,
+              int32_t max_iter, double *axes_out, double *mean_out, double *values_out, double *info_out)
+{
+    CHECK_H(h);
+    return whole_scan(h, "pca", h->pca_stats, [&]() -> int {
+        if (!axes_out || !mean_out || !values_out || !info_out) {
+            set_error("pca: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return MORNA_OK;
+    }, [&]() -> int {
+        return pca(h, r, p, extra, center != 0, seed, tol, max_iter, axes_out, mean_out, values_out, info_out);
+    });
+}
+
+// (the statistics are those of the last morna_pca: a projection leaves them as they are)
+int morna_pca_project(morna_index *h, const double *axes, const double *mean, int32_t p, const double *q, const int32_t *items,
+                      int64_t nq, double *coords_out)
+{
+    CHECK_H(h);
+    double none[1] = {0.0};
+    return whole_scan(h, "pca_project", none, [&]() -> int {
+        if (!axes || !mean || !coords_out) {
+            set_error("pca_project: null buffer");
+            return MORNA_E_INVALID;
+        }
+        return one_query_source("pca_project", q, items);
+    }, [&]() -> int {
+        ExactQueries Q;
+        MORNA_TRY(exact_queries(h, "pca_project", q, items, nq, &Q));
+        return pca_project(h, axes, mean, p, Q, nq, coords_out);
+    });
+}
+
+int morna_pca_stats(const morna_index *h, double *stats)
+{
+    return read_stats(h, &morna_index::pca_stats, stats, __func__);
+}
+
 // ---- persistence ---------------------------------------------------------------
 // One little-endian blob: header, matrix rows [n][dim], norms, forest tables.
 // It stands in for annoy's mmap file (basename.annoy.mor); byte compatibility

@@ -395,6 +395,9 @@ struct morna_index {
     // label mixture (mixture.hip): the call's arrays on the device; the last call's statistics
     morna::DevBuf<uint8_t> mx_ws;
     double mixture_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // principal axes (pca.hip): the call's arrays on the device; the last call's statistics
+    morna::DevBuf<uint8_t> pca_ws;
+    double pca_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // build scratch kept between calls
     morna::FeatScratch feat;
     morna::ForestScratch forest;
@@ -589,6 +592,14 @@ int kmeans_label_sums(morna_index *h, const int32_t *assign, int32_t k, const Km
 int mixture(morna_index *h, const morna_restriction *rst, const ExactQueries &Q, int64_t nq, const int32_t *item_label_host, int32_t L,
             double tol, int32_t max_sweeps, double *sums_out, int32_t *counts_out, double *gram_out, double *weights_out,
             double *info_out, uint8_t *active_out);
+// What pca.hip takes from the exact family besides the two query calls above: scale[n_items] of kmeans_norms_kernel on the
+// handle's stream
+int kmeans_row_scales(morna_index *h, double *scale);
+// morna_pca and morna_pca_project behind their null checks (morna_hip.h, "principal axes"; pca.hip): rst may be null
+int pca(morna_index *h, const morna_restriction *rst, int32_t p, int32_t extra, bool center, uint64_t seed, double tol, int32_t max_iter,
+        double *axes_out, double *mean_out, double *values_out, double *info_out);
+int pca_project(morna_index *h, const double *axes_host, const double *mean_host, int32_t p, const ExactQueries &Q, int64_t nq,
+                double *coords_out);
 size_t exact_msg_dist_offset(int64_t nq, int32_t k);
 size_t exact_msg_bytes(int64_t nq, int32_t k);
 

@@ -2123,4 +2123,13 @@ int kmeans_label_sums(morna_index *h, const int32_t *assign, int32_t k, const Km
     return MORNA_OK;
 }
 
+// The scales alone (pca.hip), enqueued on the handle's stream.
+int kmeans_row_scales(morna_index *h, double *scale)
+{
+    const int64_t N = h->n_items, nblk = (N + KM_THREADS - 1) / KM_THREADS;
+    hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->X.p, N, h->dim, h->dpad, scale);
+    HIP_TRY(hipGetLastError());
+    return MORNA_OK;
+}
+
 }  // namespace morna

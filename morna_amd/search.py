@@ -579,6 +579,100 @@ def write_groups_file(path, groups):
             fh.write("%s\t%s\n" % (label, ",".join(str(i) for i in ids)))
 
 
+PCA_SHARDS_REFUSAL = ("pca is not available on an index of row shards (.shards.mor, one process per shard, --device a,b): "
+                      "run it on an index built without --shards")
+PCA_MAX_COMPONENTS = 32         # MORNA_PCA_MAX_COMPONENTS
+PCA_MAX_BLOCK = 64              # MORNA_PCA_MAX_BLOCK: components and extra columns together
+PCA_CALL_VALUES = 1 << 24       # row elements of one projection call
+
+
+def pca_width_refusal(p, extra):
+    return ("pca takes 1 to %d components and, with --extra, a block of at most %d columns (got -p %d --extra %d)"
+            % (PCA_MAX_COMPONENTS, PCA_MAX_BLOCK, p, extra))
+
+
+def format_pca_header(p, iterations, converged, n_samples, total_variance):
+    """The first line of `morna pca`."""
+    return "# pca %d\titerations %d\tconverged %s\tsamples %d\ttotal variance %s\n" % (
+        p, iterations, "yes" if converged else "no", n_samples, format_distance(total_variance))
+
+
+def pca_shares(values, total_variance):
+    """[(variance, share of the total variance, cumulative share)] per component, the cumulative share summed in order;
+    NaN shares where the total variance is not positive."""
+    rows, running = [], 0.0
+    for v in values:
+        share = float(v) / total_variance if total_variance > 0.0 else float("nan")
+        running += share
+        rows.append((float(v), share, running))
+    return rows
+
+
+def format_pca_components(values, total_variance):
+    """One "# pc<j>" line per component: variance, share, cumulative share."""
+    return "".join("# pc%d\t%s\t%s\t%s\n" % (j + 1, format_distance(v), format_distance(share), format_distance(cum))
+                   for j, (v, share, cum) in enumerate(pca_shares(values, total_variance)))
+
+
+def format_pca_row(name, coords, label=None, meta=None):
+    """id<TAB>[label<TAB>]c1<TAB>..<TAB>cp and, with meta (a string), the keywords."""
+    fields = [str(name)] + ([str(label)] if label is not None else []) + [format_distance(c) for c in coords]
+    if meta is not None:
+        fields.append(meta)
+    return "\t".join(fields) + "\n"
+
+
+def pca_label_means(names, item_label, coords):
+    """[(label, members with coordinates, mean coordinates or None)] in the order of `names`: the mean of the members'
+    coordinates summed on the host in ascending internal id, a member with NaN coordinates left out."""
+    p = coords.shape[1]
+    out = []
+    for l, name in enumerate(names):
+        total, count = [0.0] * p, 0
+        for i in np.nonzero(item_label == l)[0].tolist():
+            row = coords[i].tolist()
+            if row[0] != row[0]:
+                continue
+            count += 1
+            for j in range(p):
+                total[j] += row[j]
+        out.append((name, count, [t / count for t in total] if count else None))
+    return out
+
+
+def format_pca_label_means(means):
+    """The block of per-label mean coordinates: "# label means", then label<TAB>members<TAB>c1..cp ('-' without a member)."""
+    lines = ["# label means\n"]
+    for name, count, mean in means:
+        lines.append("%s\t%d\t%s\n" % (name, count, "-" if mean is None else "\t".join(format_distance(c) for c in mean)))
+    return "".join(lines)
+
+
+def save_pca_axes(path, pca, dim):
+    """The axes of a SearchPCA as one .npz: mean, axes, values, info (iterations, converged, fitted, total variance) and dim.
+    Written to exactly `path`."""
+    info = np.array([pca.iterations, 1.0 if pca.converged else 0.0, pca.fitted, pca.total_variance], np.float64)
+    with open(path, "wb") as fh:
+        np.savez(fh, mean=np.asarray(pca.mean, np.float64), axes=np.asarray(pca.axes, np.float64),
+                 values=np.asarray(pca.values, np.float64), info=info, dim=np.array(dim, np.int64))
+
+
+def load_pca_axes(path, dim):
+    """The SearchPCA (without samples) that save_pca_axes wrote; ValueError for a file that lacks an array, whose arrays do
+    not fit each other, or that was made for an index of another dimension."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("mean", "axes", "values", "info", "dim") if k not in z.files]
+        if missing:
+            raise ValueError("%s is no file of --save-axes: it lacks %s" % (path, ", ".join(missing)))
+        mean, axes, values, info, file_dim = (np.asarray(z[k]) for k in ("mean", "axes", "values", "info", "dim"))
+    if int(file_dim) != dim:
+        raise ValueError("%s holds axes of dimension %d, the index has %d" % (path, int(file_dim), dim))
+    if axes.ndim != 2 or axes.shape[1] != dim or mean.shape != (dim,) or values.shape != (axes.shape[0],) or info.shape != (4,):
+        raise ValueError("%s is no file of --save-axes: its arrays do not fit each other" % path)
+    return SearchPCA(axes.astype(np.float64), mean.astype(np.float64), values.astype(np.float64), int(info[0]), bool(info[1]),
+                     int(info[2]), float(info[3]), None)
+
+
 def accumulate_stats(total, last, maxima=()):
     """The statistics of one more call (a *_stats dict) into those of a scan made of several: every key summed, the keys of
     `maxima` the largest seen."""
@@ -628,6 +722,29 @@ class SearchClusters(object):
 
     def sample_lines(self):
         return "".join(format_clusters_sample(sample_id, self.groups[j][0], d) for sample_id, j, d in self.samples)
+
+
+class SearchPCA(object):
+    """MornaSearch.principal_axes: axes (float64 [p, dim]), mean ([dim]), values ([p], the variances), iterations, converged,
+    fitted (the rows that took part), total_variance and stats (AnnoyIndex.pca_stats; None for axes read from a file);
+    after MornaSearch.pca_samples also samples (EXTERNAL ids in ascending internal id) and coords (float64 [n, p])."""
+
+    def __init__(self, axes, mean, values, iterations, converged, fitted, total_variance, stats):
+        self.axes, self.mean, self.values = axes, mean, values
+        self.iterations, self.converged, self.fitted, self.total_variance, self.stats = iterations, converged, fitted, total_variance, stats
+        self.samples, self.coords = None, None
+
+    def header(self):
+        return format_pca_header(len(self.values), self.iterations, self.converged, self.fitted, self.total_variance)
+
+    def components(self):
+        return format_pca_components(self.values, self.total_variance)
+
+    def sample_lines(self, labels=None, meta=None):
+        """A line per indexed sample; labels: {EXTERNAL id: label} ('-' for a sample without one), meta: {EXTERNAL id: keywords}."""
+        return "".join(format_pca_row(sample_id, row, None if labels is None else labels.get(sample_id, "-"),
+                                      None if meta is None else meta.get(sample_id, "-"))
+                       for sample_id, row in zip(self.samples, self.coords.tolist()))
 
 
 class SearchLabels(object):
@@ -1128,6 +1245,45 @@ class MornaSearch(object):
         return SearchClusters([(cluster_label(j), members[j]) for j in range(k)], [t[0] for t in table], [t[1] for t in table],
                               [None if t[2] is None else inv[t[2]] for t in table], samples, out["iterations"], out["converged"],
                               self.annoy_index.kmeans_stats())
+
+    # ---- principal axes of the index rows ---------------------------------------------------------
+    def principal_axes(self, p=10, extra=8, center=True, seed=0, tol=1e-9, max_iterations=500, restriction=None):
+        """The p leading principal axes of the unit-scaled rows of the indexed samples, fitted on the GPU (AnnoyIndex.pca),
+        bit-reproducible.  restriction: a SearchRestriction made without groups; only its allowed samples are fitted (every
+        sample can still be placed: pca_samples, pca_coordinates).  Returns a SearchPCA."""
+        self._device_index(PCA_SHARDS_REFUSAL)
+        self._check_restriction(restriction, None)
+        if restriction is not None and restriction.item_group is not None:
+            raise ValueError("pca takes a restriction without groups (within / without only)")
+        if not 1 <= p <= PCA_MAX_COMPONENTS or extra < 0 or p + extra > PCA_MAX_BLOCK:
+            raise ValueError(pca_width_refusal(p, extra))
+        out = self.annoy_index.pca(p, extra, center, seed, tol, max_iterations,
+                                   restriction=restriction.handle if restriction is not None else None)
+        return SearchPCA(out["axes"], out["mean"], out["values"], out["iterations"], out["converged"], out["fitted"],
+                         out["total_variance"], self.annoy_index.pca_stats())
+
+    def pca_coordinates(self, pca, queries):
+        """The coordinates (float64 [nq, p]) on the axes of `pca` of a QueryBatch (queries_from_intropolis), of fp64 query
+        vectors [nq, dim], or of a list of INTERNAL ids."""
+        self._device_index(PCA_SHARDS_REFUSAL)
+        if isinstance(queries, QueryBatch):
+            self._check_batch(queries)
+            return self.annoy_index.pca_project(pca.axes, pca.mean)
+        source, queries = vectors_or_items(queries)
+        nq = len(queries)
+        coords = np.zeros((nq, pca.axes.shape[0]), np.float64)
+        step = max(1024, PCA_CALL_VALUES // self.annoy_index.f)   # queries of one call: its staging stays modest
+        chunked_call(lambda q0, q1: (self.annoy_index.pca_project(pca.axes, pca.mean, **{source: queries[q0:q1]}),), nq, step, (coords,))
+        return coords
+
+    def pca_samples(self, pca):
+        """Places every indexed sample on the axes of `pca`: fills pca.samples (EXTERNAL ids in ascending internal id) and
+        pca.coords, and returns pca."""
+        n = self.annoy_index.get_n_items()
+        inv = self._inverse_map()
+        pca.coords = self.pca_coordinates(pca, range(n))
+        pca.samples = [inv[i] for i in range(n)]
+        return pca
 
     def search_recall(self, queries, num_neighbors, trees, search_ks):
         """The recall of the approximate search against the exact one for every (tree count, search_k) of a grid, from this
