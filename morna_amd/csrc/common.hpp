@@ -235,6 +235,7 @@ struct FeatScratch {   // features.hip
 struct ForestScratch {   // forest.hip
     DevBuf<int32_t> work;        // two images of every tree's permutation (TASK_ITEMS_AT)
     DevBuf<int32_t> ones;        // right-side count per task
+    DevBuf<int32_t> part_counts; // right-side count per chunk of a task (partition_count_kernel)
     DevBuf<uint8_t> side;        // [n_trees][n_items] side of every row
     DevBuf<SplitTask> tasks;
     DevBuf<int32_t> hist, cursor;   // launch order of the chunk split: buckets of 32 row ids
@@ -244,7 +245,7 @@ struct ForestScratch {   // forest.hip
     DevBuf<uint8_t> leaves;      // the leaf segments on their way to gather_leaves_kernel
     void release()
     {
-        work.release(); ones.release(); side.release(); tasks.release(); hist.release();
+        work.release(); ones.release(); part_counts.release(); side.release(); tasks.release(); hist.release();
         cursor.release(); info.release(); sched.release(); inv.release(); inv_segs.release(); leaves.release();
     }
 };

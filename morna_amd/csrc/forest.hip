@@ -30,7 +30,10 @@
 //   post_counts_kernel  the level's right-side counts into a page-locked mailbox the host polls
 //   (host)            annoy's 3-attempt / 0.95 imbalance rule on the counts
 //   fallback_kernel   random sides for nodes still above 0.99
-//   partition_kernel  stable partition of each segment by side, from one image of the tree into the other
+//   partition_stream_kernel  stable partition of each segment by side, from one image of the tree into the other: wide
+//                     aligned loads, the chunk compacted through LDS, 16-byte stores; one workgroup per 4096-position
+//                     chunk behind partition_count_kernel (which posts the counts too) where nodes span several chunks
+//   partition_kernel  the earlier form (MORNA_PARTITION_FORM=0, and the one that keeps `inv`: MORNA_PARTITION_INV=1)
 //   (splitmm.hip)     split_inv_kernel: inv[tree][row], the position in the tree of the item a row of the contraction stands
 //                     for (what the matrix-core split finds a row's node with), rewritten for what the level's partitions
 //                     moved -- on the side stream, under the NEXT level's two_means
@@ -1204,6 +1207,199 @@ __global__ __launch_bounds__(PT) void partition_kernel(const SplitTask *__restri
         run1 += total & 0xffff;
         run0 += (total >> 16) - (total & 0xffff);
         __syncthreads();
+    }
+}
+
+// ---- the streaming form of the partition (the default; MORNA_PARTITION_FORM=0: partition_kernel above) -------------
+// Same result -- a stable partition has one -- by wide, aligned accesses: a thread takes PS_PER = 16 consecutive
+// positions (its sides are two aligned 16-byte loads and a byte shift, its items four dwordx4), the chunk's items are
+// compacted through LDS in their final order, the left block then the right block, and go out so that consecutive lanes
+// store consecutive 16-byte groups, scalar only at a block's unaligned head and tail.  A chunk is PS_CHUNK positions
+// (one round of a 256-thread workgroup) and starts where the node's items are 16-byte aligned in their image: chunk k
+// of a node holds the positions [k PS_CHUNK - m, (k + 1) PS_CHUNK - m) that exist, m = (element index of the node's
+// first item) & 3.  One workgroup per node walks its chunks one after the other (gridDim.y == 1), or, where nodes
+// span several chunks, one workgroup per chunk (CHUNKS): the right-side counts of the chunks come from
+// partition_count_kernel, and a workgroup sums those in front of its own.
+#define PS_THREADS 256
+#define PS_WAVES (PS_THREADS / WAVE)
+#define PS_PER 16
+#define PS_CHUNK (PS_THREADS * PS_PER)
+
+__host__ __device__ inline int part_chunks(int count, int m) { return (count + m + PS_CHUNK - 1) / PS_CHUNK; }
+
+// 16 side bytes at the 16-byte aligned offset o, zeros for what lies outside the array
+__device__ inline uint4 side_quad(const uint8_t *__restrict__ side, int64_t o, int64_t total)
+{
+    if (o >= 0 && o + 16 <= total) return *(const uint4 *)(side + o);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const int64_t a = o + j;
+        if (a >= 0 && a < total) w[j >> 2] |= (uint32_t)side[a] << (8 * (j & 3));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The sides of the positions [p0, p0 + 16) of the node whose side bytes start at sbase, of which [vlo, vhi) exist: four
+// words of 0 / 1 bytes, zero where no position is.  The byte offset of p0 has any alignment, the same (mod 16) for every
+// thread of the workgroup: the selects below are uniform.
+__device__ inline void part_sides(const uint8_t *__restrict__ side, int64_t side_total, int64_t sbase, int p0, int vlo, int vhi,
+                                  uint32_t s[4])
+{
+    s[0] = s[1] = s[2] = s[3] = 0u;
+    if (vlo >= vhi) return;
+    const int64_t b = sbase + p0, o = b & ~(int64_t)15;
+    const int a = (int)(b - o), q = a >> 2, r = a & 3;
+    const uint4 lo = side_quad(side, o, side_total);
+    const uint4 hi = a ? side_quad(side, o + 16, side_total) : make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t v[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) v[j] = q == 0 ? w[j] : q == 1 ? w[j + 1] : q == 2 ? w[j + 2] : w[j + 3];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int l = vlo - 4 * j < 0 ? 0 : vlo - 4 * j, h = vhi - 4 * j > 4 ? 4 : vhi - 4 * j;   // bytes [l, h) of word j exist
+        const uint32_t m = h > l ? (0xffffffffu >> (8 * (4 - h))) & (0xffffffffu << (8 * l)) : 0u;
+        s[j] = __builtin_amdgcn_alignbyte(v[j + 1], v[j], (uint32_t)r) & m & 0x01010101u;
+    }
+}
+
+// right-side count of every chunk but a node's last (nobody sums that one), cc[task * stride + chunk]; grid (tasks, stride).
+// Its first workgroups post the level's counts to the host, as post_counts_kernel does where this kernel does not run.
+__global__ __launch_bounds__(PS_THREADS) void partition_count_kernel(const SplitTask *__restrict__ tasks, int32_t n_tasks, int64_t n_items,
+                                                                     const uint8_t *__restrict__ side, int64_t side_total,
+                                                                     const int32_t *__restrict__ ones, int32_t *__restrict__ cc,
+                                                                     unsigned long long *__restrict__ host_counts, uint32_t epoch)
+{
+    __shared__ int s_w[PS_WAVES];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int64_t post = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * PS_THREADS + tid;   // the first workgroups dispatched
+    if (post < n_tasks)
+        __hip_atomic_store(&host_counts[post], ((unsigned long long)epoch << 32) | (unsigned int)ones[post], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    const SplitTask t = tasks[blockIdx.x];
+    const int m = (int)(TASK_ITEMS_AT(t, n_items) & 3), k = blockIdx.y;
+    if (k + 1 >= part_chunks(t.count, m)) return;   // uniform
+    const int p0 = k * PS_CHUNK - m + tid * PS_PER;
+    const int vlo = p0 < 0 ? -p0 : 0, vhi = t.count - p0 < PS_PER ? t.count - p0 : PS_PER;
+    uint32_t s[4];
+    part_sides(side, side_total, (int64_t)t.tree * n_items + t.start, p0, vlo, vhi, s);
+    int c = __builtin_popcount(s[0]) + __builtin_popcount(s[1]) + __builtin_popcount(s[2]) + __builtin_popcount(s[3]);
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, WAVE);
+    if (lane == 0) s_w[w] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int i = 0; i < PS_WAVES; i++) sum += s_w[i];
+        cc[(int64_t)blockIdx.x * gridDim.y + k] = sum;
+    }
+}
+
+// one block of a chunk, `len` items in LDS, to perm[d0, d0 + len): 16-byte stores where a whole aligned group is the block's
+__device__ inline void part_store_block(int32_t *__restrict__ perm, int64_t d0, int len, const int32_t *ls, int tid)
+{
+    const int64_t q0 = d0 >> 2, q1 = (d0 + len + 3) >> 2;
+    for (int64_t q = q0 + tid; q < q1; q += PS_THREADS) {
+        const int64_t e = q * 4;
+        const int off = (int)(e - d0);
+        if (off >= 0 && off + 4 <= len) {
+            *(int4 *)(perm + e) = make_int4(ls[off], ls[off + 1], ls[off + 2], ls[off + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (off + j >= 0 && off + j < len) perm[e + j] = ls[off + j];
+        }
+    }
+}
+
+// grid (tasks, CHUNKS ? most chunks of a node : 1)
+template <bool CHUNKS>
+__global__ __launch_bounds__(PS_THREADS) void partition_stream_kernel(const SplitTask *__restrict__ tasks, int64_t n_items,
+                                                                      const uint8_t *__restrict__ side, int64_t side_total,
+                                                                      const int32_t *__restrict__ ones,
+                                                                      int32_t *__restrict__ perm /* work buffer [tree][2][n_items] */,
+                                                                      int64_t perm_total, const int32_t *__restrict__ cc)
+{
+    __shared__ int32_t s_items[PS_CHUNK];
+    __shared__ int s_w[PS_WAVES], s_c[PS_WAVES];
+    const SplitTask t = tasks[blockIdx.x];
+    const int n1 = ones[blockIdx.x], n0 = t.count - n1;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int64_t gsrc = TASK_ITEMS_AT(t, n_items);
+    const int64_t gdst = ((int64_t)t.tree * 2 + ((t.level + 1) & 1)) * n_items + t.start;
+    const int64_t sbase = (int64_t)t.tree * n_items + t.start;
+    const int m = (int)(gsrc & 3), nchunks = part_chunks(t.count, m);
+    if ((int)blockIdx.y >= nchunks) return;   // uniform
+    int run1 = 0;                             // right-side items of the chunks before (one workgroup per node)
+    for (int k = blockIdx.y; k < nchunks; k += gridDim.y) {
+        // the chunk's sides and items are asked for before the counts are looked at: their addresses need the task alone
+        const int p0 = k * PS_CHUNK - m + tid * PS_PER;
+        const int vlo = p0 < 0 ? -p0 : 0, vhi = t.count - p0 < PS_PER ? t.count - p0 : PS_PER;
+        uint32_t s[4];
+        part_sides(side, side_total, sbase, p0, vlo, vhi, s);
+        int it[PS_PER];
+        const int64_t e0 = gsrc + p0;   // a multiple of 4, never below 0
+#pragma unroll
+        for (int j = 0; j < PS_PER / 4; j++) {
+            int4 v = make_int4(0, 0, 0, 0);
+            if (4 * j + 4 > vlo && 4 * j < vhi) {
+                const int64_t e = e0 + 4 * j;
+                if (e + 4 <= perm_total) v = *(const int4 *)(perm + e);
+                else {
+                    v.x = perm[e];   // e itself exists: the group holds an item of the node
+                    if (e + 1 < perm_total) v.y = perm[e + 1];
+                    if (e + 2 < perm_total) v.z = perm[e + 2];
+                }
+            }
+            it[4 * j] = v.x, it[4 * j + 1] = v.y, it[4 * j + 2] = v.z, it[4 * j + 3] = v.w;
+        }
+        // the right-side counts of the chunks in front of this one (asked for with the rest), beside the scan's wave totals
+        int c = 0;
+        if constexpr (CHUNKS)
+            for (int j = tid; j < k; j += PS_THREADS) c += cc[(int64_t)blockIdx.x * gridDim.y + j];
+        if (k == (int)blockIdx.y && !sides_stand(t.attempt, n0, n1)) return;   // uniform; nothing has been stored
+        if constexpr (CHUNKS) {
+#pragma unroll
+            for (int o = WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, WAVE);
+        }
+        // right-side and existing positions of a thread packed into one integer (16 bits each: a chunk has 4096 positions)
+        const int c1 = __builtin_popcount(s[0]) + __builtin_popcount(s[1]) + __builtin_popcount(s[2]) + __builtin_popcount(s[3]);
+        const int pk = ((vhi > vlo ? vhi - vlo : 0) << 16) | c1;
+        int incl = pk;
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int v = __shfl_up(incl, o, WAVE);
+            if (lane >= o) incl += v;
+        }
+        if (lane == WAVE - 1) s_w[w] = incl;
+        if (CHUNKS && lane == 0) s_c[w] = c;
+        __syncthreads();
+        int before = 0, total = 0, before1 = run1;
+#pragma unroll
+        for (int i = 0; i < PS_WAVES; i++) {
+            if (i < w) before += s_w[i];
+            total += s_w[i];
+            if constexpr (CHUNKS) before1 += s_c[i];
+        }
+        const int excl = incl - pk + before;
+        int r1 = excl & 0xffff, rv = excl >> 16;   // right-side / existing positions of the chunk before this thread's first
+        const int R = total & 0xffff, L = (total >> 16) - R;
+        const int before0 = (k * PS_CHUNK - m > 0 ? k * PS_CHUNK - m : 0) - before1;
+#pragma unroll
+        for (int u = 0; u < PS_PER; u++)
+            if (u >= vlo && u < vhi) {
+                const int sd = (int)((s[u >> 2] >> (8 * (u & 3))) & 1u);
+                s_items[sd ? L + r1 : rv - r1] = it[u];
+                r1 += sd;
+                rv += 1;
+            }
+        __syncthreads();
+        part_store_block(perm, gdst + before0, L, s_items, tid);
+        part_store_block(perm, gdst + n0 + before1, R, s_items + L, tid);
+        run1 += R;
+        if (k + (int)gridDim.y < nchunks) __syncthreads();   // the next chunk reuses the LDS
     }
 }
 

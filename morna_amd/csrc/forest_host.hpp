@@ -30,6 +30,13 @@ static bool fb_part_inv()
     static const bool on = fb_mm_on() && getenv("MORNA_PARTITION_INV") && atoi(getenv("MORNA_PARTITION_INV")) != 0;
     return on;
 }
+// MORNA_PARTITION_FORM: 0 = partition_kernel (the earlier form), 2 = the streaming form with one workgroup per node at every
+// level; anything else, or unset: the streaming form, one workgroup per chunk where nodes span several
+static int fb_part_form()
+{
+    static const int form = !env_on("MORNA_PARTITION_FORM") ? 0 : getenv("MORNA_PARTITION_FORM") && atoi(getenv("MORNA_PARTITION_FORM")) == 2 ? 2 : 1;
+    return form;
+}
 static bool fb_debug_turn()
 {
     static const bool on = getenv("MORNA_DEBUG_TURN") && atoi(getenv("MORNA_DEBUG_TURN")) != 0;
@@ -109,6 +116,45 @@ static int fb_partition(morna_index *h, int32_t A, int64_t level_rows)
     }
     B.epoch = ++h->count_epoch ? h->count_epoch : ++h->count_epoch;   // never 0: the mailbox starts zeroed
     B.A = A;
+    // The streaming form (forest.hip, partition_stream_kernel) unless MORNA_PARTITION_FORM=0 or the partition keeps `inv`.
+    // Where a node of the attempt spans more than two chunks, one workgroup per chunk, behind a counting pass that also posts
+    // the counts; else one workgroup per node and post_counts_kernel as ever.  (MORNA_PARTITION_FORM=2: one workgroup per
+    // node whatever the nodes' sizes, for comparison.)
+    const int form = fb_part_form();
+    if (form != 0 && !fb_part_inv()) {
+        int32_t most = 0;
+        for (const SplitTask &t : B.tasks) most = std::max(most, t.count);
+        const unsigned mc = (unsigned)part_chunks(most, 3);   // no node of the attempt has more chunks
+        const int64_t side_total = (int64_t)B.n_trees * N, perm_total = side_total * 2;
+        // one workgroup per chunk from three chunks to a node on: at two (the default run's level 4) both forms take the
+        // same time, counting pass included (profiles/partition_forms_vs_parent.txt)
+        const bool chunks = form != 2 && mc > 2 && mc <= 65535;   // (a grid's second dimension ends there)
+        if (chunks) {
+            MORNA_TRY(h->forest.part_counts.alloc((size_t)A * mc));
+            hipLaunchKernelGGL(partition_count_kernel, dim3((unsigned)A, mc), dim3(PS_THREADS), 0, h->stream, h->forest.tasks.p, A, N,
+                               h->forest.side.p, side_total, h->forest.ones.p, h->forest.part_counts.p,
+                               (unsigned long long *)h->host_counts.p, B.epoch);
+        } else
+            hipLaunchKernelGGL(post_counts_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, h->stream, h->forest.ones.p, A,
+                               (unsigned long long *)h->host_counts.p, B.epoch);
+        {
+            ScopedTimer tm(h, MORNA_T_PARTITION, 0);
+            if (chunks)
+                hipLaunchKernelGGL(partition_stream_kernel<true>, dim3((unsigned)A, mc), dim3(PS_THREADS), 0, h->stream, h->forest.tasks.p,
+                                   N, h->forest.side.p, side_total, h->forest.ones.p, h->forest.work.p, perm_total,
+                                   h->forest.part_counts.p);
+            else
+                hipLaunchKernelGGL(partition_stream_kernel<false>, dim3((unsigned)A), dim3(PS_THREADS), 0, h->stream,
+                                   h->forest.tasks.p, N, h->forest.side.p, side_total, h->forest.ones.p, h->forest.work.p, perm_total,
+                                   (const int32_t *)nullptr);
+        }
+        if (hipGetLastError() != hipSuccess) {
+            set_error("forest build: partition launch failed");
+            return MORNA_E_HIP;
+        }
+        fb_write_late_tables(h);
+        return MORNA_OK;
+    }
     hipLaunchKernelGGL(post_counts_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, h->stream, h->forest.ones.p, A,
                        (unsigned long long *)h->host_counts.p, B.epoch);
     {
@@ -227,6 +273,8 @@ static int fb_begin(morna_index *h, int32_t n_trees, uint32_t seed)
     // scratch lives in the handle: a rebuild (or the next level) reuses it without hipMalloc
     MORNA_TRY(h->forest.work.alloc((size_t)n_trees * N * 2));
     MORNA_TRY(h->forest.side.alloc((size_t)n_trees * N));
+    // per-chunk counts of the chunk-parallel partition: what levels of like-sized nodes need (a level of unlike nodes may grow it)
+    if (fb_part_form() == 1 && !fb_part_inv()) MORNA_TRY(h->forest.part_counts.alloc((size_t)n_trees * (size_t)(N / PS_CHUNK + 2) * 2));
     // launch-order scratch of the split kernel: buckets of 32 row ids
     const int32_t n_buckets = (int32_t)std::min<int64_t>(SCHED_MAX_BUCKETS, std::max<int64_t>(1, (N + 31) / 32));
     MORNA_TRY(h->forest.hist.alloc((size_t)n_buckets));
@@ -422,7 +470,11 @@ static int fb_enqueue(morna_index *h)
     // The order by groups is some twenty launches, 0.12 ms of host time that this level's two_means would start later by: there
     // the fork alone goes in front of the two_means launch and the side stream's launches behind it.
     const bool side_work = prep_job || order_job || inv_job || lists_ahead;
-    const bool side_late = order_job && split_mm_order_by_groups();
+    // With the streaming partition the device is through a level's partition before the host has enqueued the next level:
+    // whatever is launched first starts first, and a side-stream kernel that starts in front of two_means takes the CUs its
+    // workgroups would have started on (level 2 of the default run: split_inv_kernel 3 us ahead, two_means 0.54 instead of
+    // 0.39 ms).  So there, too, the side stream's launches go behind the two_means launch.
+    const bool side_late = (order_job && split_mm_order_by_groups()) || (fb_part_form() != 0 && !part_inv);
     auto enqueue_side = [&]() -> int {
         if (prep_job) MORNA_TRY(split_mm_prepare_rows(h, h->stream2));
         if (order_job) MORNA_TRY(split_mm_order_rows(h, side.p, n_trees, h->stream2));
